@@ -1,15 +1,22 @@
 #!/usr/bin/env python3
 """Headline benchmark: FISTA iterations/second on dense A (BASELINE.json metric), MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg4|cfg5] [--dump-outputs DIR] [--full]
 
 Every N runs the SAME workload, cfg4: Lasso, A in R^{2^20 x 16384} fp32 - BASELINE's "iters/sec reported at 1/2/4/8
 GPUs" configuration.  Rows are sharded over the N ranks (launched by `python -m torch.distributed.run --nproc-per-node
 N ... bench.py --gpus N`), ONE RCCL all-reduce of n+1 floats per iteration; total work is fixed -> "scaling":
 "strong"; 64 GiB fits one MI355X, so N = 1 is a real point of the series and `value` is comparable across N.
-The >= 70 % single-GPU roofline target is quoted on cfg2 (A in R^{65536 x 8192} fp32): the default N = 1 run measures
-that configuration too and reports it as "target_ref" (value, roofline, cpu_baseline of its own).
 `--workload cfg2|cfg4|cfg5` selects one workload explicitly.
+
+A plain run measures the headline alone: set-up, W warm-up steps, ONE timed region of exactly K steps, the JSON line.
+`--full` adds everything else, as the official bench line of each round carried it: the median of 5 timed regions,
+`roofline` (HIP events around the dominant kernel, a loads-only pass over the same A), `cpu_baseline` with the parity
+sample, and in the default N = 1 run the riders `target_ref` (cfg2, A in R^{65536 x 8192} fp32, the configuration the
+>= 70 % single-GPU roofline target is quoted on, with roofline and cpu_baseline of its own), `lbfgs_ref`, `mfma_ref`
+and `fused_ref`.
+`--dump-outputs DIR` writes what the timed path returns after its last step, x (float64), as DIR/x.npy; the inputs
+are generated from fixed seeds, so two builds can be compared output for output.
 
 A "step" is one full FISTA iteration (gradient A^T(Ay-b) in a single pass over A, prox, momentum), inputs
 resident in HBM, nothing skipped.  One JSON line is printed by rank 0.
@@ -156,7 +163,14 @@ def cpu_baseline(cfg, A_dev, b_dev, a1, a2, L, x_gpu_k, k_check, budget_s=25.0):
                 physical_cores=topo["physical"], logical_cpus=topo["logical"], blas=topo["blas"]), parity
 
 
-def run_workload(name, args, rank, world, device, steps, warmup, want_cpu, dist, repeats=1):
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array the timed path hands its caller."""
+    os.makedirs(path, exist_ok=True)
+    for key, a in arrays.items():
+        np.save(os.path.join(path, key + ".npy"), a)
+
+
+def run_workload(name, args, rank, world, device, steps, warmup, want_cpu, dist, repeats=1, dump_dir=None):
     import ctypes as C
     import fastoptsolver_amd as fos
     from fastoptsolver_amd import _lib, distributed as fd
@@ -192,21 +206,24 @@ def run_workload(name, args, rank, world, device, steps, warmup, want_cpu, dist,
         # collective alone: all-reduce of n + 1 floats, 100 back-to-back calls on the stream, max over ranks
         nr, rk = C.c_int(), C.c_int()
         _lib.check(comm.lib.fos_comm_info(comm.h, C.byref(nr), C.byref(rk)), "fos_comm_info")
-        probe = torch.zeros(cfg["n"] + 4, dtype=torch.float32, device=device)
-        for _ in range(10):
-            comm.allreduce(probe[: cfg["n"] + 1])
-        torch.cuda.synchronize()
-        dist.barrier()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(100):
-            comm.allreduce(probe[: cfg["n"] + 1])
-        e1.record()
-        e1.synchronize()
-        t_ar = torch.tensor([e0.elapsed_time(e1) * 10.0], dtype=torch.float64, device=device)      # us per call
-        dist.all_reduce(t_ar, op=dist.ReduceOp.MAX)
+        t_ar = None
+        if args.full:
+            probe = torch.zeros(cfg["n"] + 4, dtype=torch.float32, device=device)
+            for _ in range(10):
+                comm.allreduce(probe[: cfg["n"] + 1])
+            torch.cuda.synchronize()
+            dist.barrier()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(100):
+                comm.allreduce(probe[: cfg["n"] + 1])
+            e1.record()
+            e1.synchronize()
+            t_ar = torch.tensor([e0.elapsed_time(e1) * 10.0], dtype=torch.float64, device=device)      # us per call
+            dist.all_reduce(t_ar, op=dist.ReduceOp.MAX)
+            t_ar = float(t_ar.item())
         args.comm_info = dict(ranks_seen_by_communicator=int(nr.value), this_rank=int(rk.value), transport=comm.transport(),
-                              allreduce_elements=cfg["n"] + 1, allreduce_us_standalone=float(t_ar.item()))
+                              allreduce_elements=cfg["n"] + 1, allreduce_us_standalone=t_ar)
         comm.check()
     eng = fd.HipShardEngine(A, b, comm=comm, group=dist.group.WORLD if world > 1 else None)
     matvec_prob = fos.prepare(A, None)                       # same A, b = 0: power iteration / A^T b
@@ -275,10 +292,11 @@ def run_workload(name, args, rank, world, device, steps, warmup, want_cpu, dist,
         x_moved = float(np.linalg.norm(x_check))
         assert x_moved > 0.0, "parity sample did not move: vacuous check"
         del sub
-    # HIP events around the launches of the dominant kernel: all of them for short runs, every 8th otherwise (the
-    # markers cost ~1 % when they bracket every launch of a long run)
-    eng.prob.profile(1 if steps <= 32 else 8)
-    eng.prob.profile_read()
+    if args.full:
+        # HIP events around the launches of the dominant kernel: all of them for short runs, every 8th otherwise (the
+        # markers cost ~1 % when they bracket every launch of a long run)
+        eng.prob.profile(1 if steps <= 32 else 8)
+        eng.prob.profile_read()
     # `repeats` timed regions of EXACTLY `steps` iterations each, every one bracketed by barrier + synchronize on both sides
     # and taken as the MAX over ranks; the reported time is their median ("median of 5 runs").
     runs = []
@@ -294,12 +312,18 @@ def run_workload(name, args, rank, world, device, steps, warmup, want_cpu, dist,
             el = float(tmax.item())
         runs.append(el)
     elapsed = float(np.median(runs))
-    k_ms, k_launches = eng.prob.profile_read()
-    eng.prob.profile(0)
-    # beside the nominal 8 TB/s, what THIS box delivers to a kernel that only loads (the same A, after the timed
-    # regions): fos_stream_read_probe, 8 non-temporal 16-byte loads in flight per thread, HIP events around the launches.
-    from fastoptsolver_amd import _core
-    read_gbps, read_us = _core.stream_read_probe(A, launches=max(4, min(40, int(2e11 // max(A.numel() * A.element_size(), 1)))))
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {"x": eng.x().cpu().numpy()})     # replicated on every rank: rank 0's copy is the answer
+    k_ms, k_launches, read_gbps, read_us = None, 0, None, None
+    if args.full:
+        k_ms, k_launches = eng.prob.profile_read()
+        eng.prob.profile(0)
+        # beside the nominal 8 TB/s, what THIS box delivers to a kernel that only loads (the same A, after the
+        # timed regions): fos_stream_read_probe, 8 non-temporal 16-byte loads in flight per thread, HIP events around the
+        # launches.
+        from fastoptsolver_amd import _core
+        read_gbps, read_us = _core.stream_read_probe(
+            A, launches=max(4, min(40, int(2e11 // max(A.numel() * A.element_size(), 1)))))
     st = eng.status()
     assert int(st.k) == warmup + steps * repeats and st.stopped == 0, (int(st.k), st.stopped)
     assert math.isfinite(st.this_step) and st.this_step > 0.0, "iterate did not move: invalid run"
@@ -316,7 +340,7 @@ def run_workload(name, args, rank, world, device, steps, warmup, want_cpu, dist,
         assert replicas_identical, "replicated iterates differ between ranks: invalid run"
 
     b_iter = bytes_per_iter(hi - lo, n, cfg["dtype"])
-    kern_us = k_ms * 1e3 / max(k_launches, 1)
+    kern_us = k_ms * 1e3 / max(k_launches, 1) if k_ms is not None else None
     res = dict(
         workload=name, ms_per_step=elapsed * 1e3 / steps, value=steps / elapsed, steps=steps, warmup=warmup, repeats=repeats,
         ms_per_step_runs=[e * 1e3 / steps for e in runs],
@@ -521,17 +545,26 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of exactly --steps iterations each; the median is reported (1 = a single region)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of exactly --steps iterations each; the median is reported "
+                         "(default: 1 = a single region; 5 with --full)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline, cpu_baseline + parity, and the riders "
+                         "of the default N=1 run (target_ref, lbfgs_ref, mfma_ref, fused_ref)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline's result after the last timed step (x, float64) as DIR/x.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and the parity sample")
     ap.add_argument("--no-target-ref", "--no-scale-ref", dest="no_target_ref", action="store_true",
-                    help="skip the cfg2 (65536 x 8192) single-GPU measurement that the default N=1 run adds")
+                    help="with --full: skip the cfg2 (65536 x 8192) single-GPU measurement that the default N=1 run adds")
     ap.add_argument("--geometry", type=str, default="", help="THREADSxCHUNKSxROWSxWORKGROUPS override (tuning)")
     ap.add_argument("--interleave", choices=("auto", "on", "off"), default="auto",
                     help="row order of the streaming pass: planner default / round-robin rows / contiguous blocks (A/B)")
     ap.add_argument("--rows", type=int, default=0, help="override m (rehearsal / tuning only; reported in config)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    want_cpu = args.full and not args.no_cpu_baseline
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -560,12 +593,13 @@ def main():
 
     # ONE series for every N: BASELINE's "iters/sec reported at 1/2/4/8 GPUs on A in R^{2^20 x 16384}" (cfg4, total work
     # fixed -> strong scaling; 64 GiB fits one MI355X, so N=1 is a real point of the series).  The single-GPU roofline
-    # target is quoted on cfg2 (65536 x 8192): the default N=1 run measures it as well and reports it as `target_ref`
-    # with its own roofline and cpu_baseline objects.
+    # target is quoted on cfg2 (65536 x 8192): the default N=1 run with --full measures it as well and reports it as
+    # `target_ref` with its own roofline and cpu_baseline objects.
     name = args.workload or "cfg4"
     if args.rows:
         WORKLOADS[name] = dict(WORKLOADS[name], m=int(args.rows))
-    default_run = world == 1 and name == "cfg4" and not args.no_target_ref and args.workload is None and not args.rows
+    default_run = (args.full and world == 1 and name == "cfg4" and not args.no_target_ref and args.workload is None
+                   and not args.rows)
 
     def settle(seconds):
         # Returning VRAM to the driver (empty_cache at the end of a workload) leaves the device busy for a while: the same
@@ -576,13 +610,13 @@ def main():
         torch.cuda.empty_cache()
         time.sleep(seconds)
 
-    # The riders of the default N=1 run go FIRST (2 GiB each), the 64 GiB headline last.
+    # The riders of the default N=1 --full run go FIRST (2 GiB each), the 64 GiB headline last.
     target_ref = None
     settle(4.0)            # a process that ended just before this one (a test suite, the previous N) is still being released
     if default_run:
         try:
             r2 = run_workload("cfg2", args, rank, world, device, steps=200, warmup=10,
-                              want_cpu=not args.no_cpu_baseline, dist=dist, repeats=args.repeats)
+                              want_cpu=want_cpu, dist=dist, repeats=args.repeats)
             c2 = WORKLOADS["cfg2"]
             target_ref = dict(
                 workload=f"cfg2: {c2['reg']} FISTA, A {c2['m']}x{c2['n']} f32 on 1 GPU - the configuration the "
@@ -598,7 +632,7 @@ def main():
             target_ref = dict(error=str(exc)[:200])
         settle(2.0)
 
-    # BASELINE config 3 (L-BFGS, ridge, on the cfg2 matrix) rides along in the default N=1 run as `lbfgs_ref`
+    # BASELINE config 3 (L-BFGS, ridge, on the cfg2 matrix) rides along in the default N=1 --full run as `lbfgs_ref`
     lbfgs_ref = None
     if default_run:
         try:
@@ -626,7 +660,7 @@ def main():
         settle(3.0)
 
     res = run_workload(name, args, rank, world, device, args.steps, args.warmup,
-                       want_cpu=not args.no_cpu_baseline, dist=dist, repeats=args.repeats)
+                       want_cpu=want_cpu, dist=dist, repeats=args.repeats, dump_dir=args.dump_outputs)
 
     if rank == 0:
         cfg = WORKLOADS[name]
@@ -663,7 +697,7 @@ def main():
                 "replicas_identical": res["replicas_identical"],
                 "communicator": getattr(args, "comm_info", None),
             },
-            "roofline": roofline_obj(res, name if world == 1 else None),
+            "roofline": roofline_obj(res, name if world == 1 else None) if args.full else None,
             "cpu_baseline": res["cpu_baseline"],
             "parity_rel_err_vs_cpu_at_warmup_iterate": res["parity_rel_err"],
             "parity": {"rel_err": res["parity_rel_err"], "iterate": res["parity_k"], "rows": res["parity_rows"],

@@ -8,9 +8,10 @@ mkdir -p $OUT
 for round in 1 2; do
   for tree in r01 r02 new; do
     dir=$ROOT/ab_trees/$tree
-    [ $tree = new ] && dir=$ROOT
+    full=
+    [ $tree = new ] && dir=$ROOT && full=--full      # older trees measured everything by default
     echo "== $tree round $round $(date +%T)"
-    (cd $dir && timeout -k 10 300 python bench.py --no-cpu-baseline --steps 200 --warmup 10 > $OUT/${tree}_$round.json 2> $OUT/${tree}_$round.err) || exit 1
+    (cd $dir && timeout -k 10 300 python bench.py $full --no-cpu-baseline --steps 200 --warmup 10 > $OUT/${tree}_$round.json 2> $OUT/${tree}_$round.err) || exit 1
     python - <<PY
 import json
 d = json.load(open("$OUT/${tree}_$round.json"))

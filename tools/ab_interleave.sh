@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $ROOT
 for round in 1 2 3; do
   for mode in off on; do
-    timeout -k 10 300 python bench.py --no-cpu-baseline --steps 200 --warmup 10 --interleave $mode > $OUT/${mode}_$round.json 2> $OUT/${mode}_$round.err || exit 1
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 200 --warmup 10 --interleave $mode > $OUT/${mode}_$round.json 2> $OUT/${mode}_$round.err || exit 1
     python - <<PY
 import json
 d = json.load(open("$OUT/${mode}_$round.json"))

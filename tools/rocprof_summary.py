@@ -54,7 +54,7 @@ def main():
     ap.add_argument("--kernel-trace", required=True)
     ap.add_argument("--fetch", required=True)
     ap.add_argument("--write", required=True)
-    ap.add_argument("--command", default="python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline")
+    ap.add_argument("--command", default="python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline")
     ap.add_argument("--match", default="", help="extra substring the dominant kernel's name must contain "
                                                  "(e.g. 'float, 512' to pick one geometry when a run holds several)")
     a = ap.parse_args()
