@@ -44,3 +44,22 @@ def rel(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     den = np.linalg.norm(b)
     return float(np.linalg.norm(a - b) / den) if den > 0 else float(np.linalg.norm(a - b))
+
+
+def fp32_pass_tolerances(A, y, b, g_ref, rr_ref):
+    """(gradient, ||r||^2) bounds of one fp32 pass over A against the fp64 oracle on the stored A.  r_i = A_i.y - b_i is
+    formed with an absolute error of a few eps32 * (|A_i|.|y| + |b_i|) however small r_i itself is (m = 1, 2 rows with a
+    nearly exact fit: seeds 438, 1409, 1444 of a 2000-case soak), grad = A^T r inherits it times |A|, ||r||^2 inherits
+    2|r| times it.  b may be None."""
+    A = np.asarray(A, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    m, n = A.shape
+    eps32 = float(np.finfo(np.float32).eps)
+    ab = np.abs(A) @ np.abs(y)
+    if b is not None:
+        ab = ab + np.abs(np.asarray(b, dtype=np.float64))
+    dr = 4.0 * eps32 * float(np.linalg.norm(ab))
+    r_norm = float(np.sqrt(rr_ref))
+    g_tol = 2e-6 * float(np.linalg.norm(g_ref)) + float(np.linalg.norm(A, 2) if m * n <= 1 << 16 else np.linalg.norm(A)) * dr
+    rr_tol = 5e-6 * rr_ref + 2.0 * r_norm * dr + dr * dr
+    return g_tol, rr_tol

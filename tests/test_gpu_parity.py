@@ -356,9 +356,10 @@ def test_lbfgs_vs_reference_goldens(fos, tag):
 
 
 def test_gemv_pair_dd_every_path(fos):
-    """fos_gemv_pair_dd (the fp64 fg of L-BFGS) through every kernel that serves it - resident, row-per-thread, every
-    streaming fp64 geometry (registers / y in LDS), fp64 two-pass for ragged and over-wide rows, bf16 storage - against
-    the fp64 oracle on the stored (rounded) A: 1e-12, i.e. only the summation order differs."""
+    """fos_gemv_pair_dd (the fp64 fg of L-BFGS) through every kind of kernel that serves it - resident, row-per-thread,
+    streaming fp64 geometries (registers / y in LDS), fp64 two-pass for ragged and over-wide rows, bf16 storage - against
+    the fp64 oracle on the stored (rounded) A: 1e-12, i.e. only the summation order differs.  These shapes sample the
+    kDdMenu geometries; every entry and its interleaved form is covered by tests/test_gpu_kernel_menu.py."""
     from fastoptsolver_amd import _core, _lib
     lib = _lib.load()
     rng = np.random.default_rng(17)
