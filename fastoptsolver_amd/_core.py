@@ -138,6 +138,21 @@ class Problem:
         self.lda = int(At.stride(0)) if self.m > 1 else self.n_dev
         self.device = At.device
         self.dtype = "bf16" if want_bf16 else "f32"
+        self._bind(b, lib)
+
+    def sibling(self, b):
+        """Another handle on the SAME device A (borrowed as it is: no upload, no padding) with its own b - the column-by-column
+        runs of a multi-target solve."""
+        sib = Problem.__new__(Problem)
+        sib.like = self.like
+        sib.A, sib.m, sib.n, sib.n_dev, sib.lda = self.A, self.m, self.n, self.n_dev, self.lda
+        sib.device, sib.dtype = self.device, self.dtype
+        sib._bind(b, self.lib)
+        return sib
+
+    def _bind(self, b, lib):
+        """Create the fos_problem handle on self.A and b."""
+        want_bf16 = self.dtype == "bf16"
         self.b = None if b is None else to_device_vec(b, self.device)
         if self.b is not None and self.b.numel() != self.m:
             raise ValueError("b must have m entries")
@@ -284,6 +299,21 @@ class Problem:
         with self.ctx():
             _lib.check(self.lib.fos_residual_batch(self.h, ptr(Xf), nv, int(bool(use_b)), ptr(self.scratch)),
                        "fos_residual_batch")
+        return self.scratch[:nv].cpu().tolist()
+
+    def residual_batch_rhs(self, X, B):
+        """||A X_j - B_j||^2 for the nv <= 16 columns of X (n x nv) against the columns of B (m x nv fp32 device tensor with
+        unit column stride, any row stride) in one MFMA pass; host list, or None where the shape has no such pass.
+        Synchronises."""
+        X = torch.as_tensor(X, device=self.device, dtype=torch.float32)
+        nv = X.shape[1]
+        Xf = torch.zeros(self.n_dev, 16, dtype=torch.float32, device=self.device)
+        Xf[: X.shape[0], :nv] = X
+        with self.ctx():
+            rc = self.lib.fos_residual_batch_rhs(self.h, ptr(Xf), nv, ptr(B), int(B.stride(0)), ptr(self.scratch))
+        if rc == -4:
+            return None
+        _lib.check(rc, "fos_residual_batch_rhs")
         return self.scratch[:nv].cpu().tolist()
 
     def power_iter(self, v0, n_iter=100, tol=1e-6):
@@ -535,4 +565,18 @@ def run_multi(handles, iters):
     if rc == -4:
         return False
     _lib.check(rc, "fos_fista_run_multi")
+    return True
+
+
+def run_multi_rhs(handles, B, iters):
+    """Advance up to 16 Fista handles of one Problem in lockstep, handle v solving for column v of B (an m x nv fp32 device
+    tensor with unit column stride, any row stride; the problem's own b is not used) (fos_fista_run_multi_rhs).
+    Returns False when this shape / configuration has no multi-vector kernel (callers then run the columns one by one)."""
+    lib = handles[0].lib
+    arr = (C.c_void_p * len(handles))(*[h.h for h in handles])
+    with handles[0].prob.ctx():
+        rc = lib.fos_fista_run_multi_rhs(arr, len(handles), ptr(B), int(B.stride(0)), int(iters))
+    if rc == -4:
+        return False
+    _lib.check(rc, "fos_fista_run_multi_rhs")
     return True

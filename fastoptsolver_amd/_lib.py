@@ -77,6 +77,7 @@ SIGNATURES = {
     "fos_gemv_pair_dd": (_i32, [_vp, _vp, _f64, _vp]),
     "fos_residual_objective": (_i32, [_vp, _vp, _vp]),
     "fos_residual_batch": (_i32, [_vp, _vp, _i32, _i32, _vp]),
+    "fos_residual_batch_rhs": (_i32, [_vp, _vp, _i32, _vp, _i64, _vp]),
     "fos_power_iter": (_i32, [_vp, _vp, _i32, _f64, C.POINTER(_f64), C.POINTER(_i32)]),
     "fos_prox_l1": (_i32, [_vp, _f32, _vp, _i64, _vp]),
     "fos_prox_l1_vec": (_i32, [_vp, _vp, _vp, _i64, _vp]),
@@ -93,6 +94,7 @@ SIGNATURES = {
     "fos_fista_run_history": (_i32, [_vp, _i32, _vp, _vp, _vp]),
     "fos_fista_run_resident": (_i32, [_vp, _i32, _i32, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fos_fista_run_multi": (_i32, [C.POINTER(_vp), _i32, _i32]),
+    "fos_fista_run_multi_rhs": (_i32, [C.POINTER(_vp), _i32, _vp, _i64, _i32]),
     "fos_fista_run_fused": (_i32, [_vp, _i32]),
     "fos_fista_grad": (_i32, [_vp]),
     "fos_fista_grad_dual": (_i32, [_vp]),

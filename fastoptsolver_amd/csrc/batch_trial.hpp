@@ -101,7 +101,9 @@ static __global__ __launch_bounds__(256) void fista_trial_batch_kernel(GradSrc g
 // Requirements (host-checked): n % 4 == 0, lda % 4 == 0, A 16-byte aligned, Xp zero-padded to n_pad = 64*ceil(n/64).
 // STORE_R = true (multi-lambda gradient, gram_batch.hpp): the residuals themselves, rout[row][16 candidates] fp32,
 // are kept for the second product G = A^T R.
-template <int RB, bool STORE_R = false>
+// BBLOCK = true (several right-hand sides): b is the m x 16 block B16 and column j subtracts its own B16[row][j] - 16
+// lanes read one contiguous 64-byte row, the pattern of the rout store beside it.
+template <int RB, bool STORE_R = false, bool BBLOCK = false>
 __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const float* __restrict__ A, int64_t lda,
                                                                         const float* __restrict__ b, int use_b,
                                                                         int64_t m, int n,
@@ -186,7 +188,11 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const f
           const int64_t row = row0 + r;
           if (row < m) {
             float v = acc[rb][r];
-            if (use_b) v -= b[row];
+            if constexpr (BBLOCK) {
+              if (use_b) v -= b[row * BT_NV + (lane & 15)];
+            } else {
+              if (use_b) v -= b[row];
+            }
             qsum += (double)v * (double)v;
             if constexpr (STORE_R) rout[row * BT_NV + (lane & 15)] = v;      // 16 lanes: one 64-byte row of R
           }
@@ -332,7 +338,8 @@ static __global__ void xq_pack_kernel(const float* __restrict__ X, int n, int n_
 // RB = 16-row blocks per wave (the candidate fragments read from LDS are reused for RB row blocks: X is 96 bytes per
 // column against 32 bytes of A per row block, so LDS traffic per byte of A falls with RB); COLS = bf16 columns per tile.
 // Requirements: n % 8 == 0, lda % 8 == 0, A 16-byte aligned, Xq zero-padded to n_pad (a multiple of 128).
-template <int RB, int COLS, bool STORE_R = false>
+// BBLOCK: b is the m x 16 right-hand-side block, as in residual_batch_mfma_kernel.
+template <int RB, int COLS, bool STORE_R = false, bool BBLOCK = false>
 __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_bf16_kernel(
     const bf16_t* __restrict__ A, int64_t lda, const float* __restrict__ b, int use_b, int64_t m, int n,
     const unsigned short* __restrict__ xq, int64_t groups_per_wg, double* __restrict__ q_part,
@@ -421,7 +428,11 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_bf16_kernel(
           const int64_t row = row0 + r;
           if (row < m) {
             float v = acc[rb][r];
-            if (use_b) v -= b[row];
+            if constexpr (BBLOCK) {
+              if (use_b) v -= b[row * BT_NV + (lane & 15)];
+            } else {
+              if (use_b) v -= b[row];
+            }
             qsum += (double)v * (double)v;
             if constexpr (STORE_R) rout[row * BT_NV + (lane & 15)] = v;
           }
@@ -457,6 +468,18 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_bf16_kernel(
   if (lane < BT_NV) wsum[wave][lane] = qsum;
   __syncthreads();
   if (tid < BT_NV) q_part[(int64_t)blockIdx.x * BT_NV + tid] = (wsum[0][tid] + wsum[1][tid]) + (wsum[2][tid] + wsum[3][tid]);
+}
+
+// Several right-hand sides: the caller's B (m x nv, row-major, leading dimension ldb >= nv) -> the zero-padded m x 16
+// block B16 the BBLOCK forms read.  One thread per entry of B16: 16 consecutive threads write one 64-byte row.
+static __global__ __launch_bounds__(256) void stage_b16_kernel(const float* __restrict__ B, int64_t ldb, int nv, int64_t m,
+                                                               float* __restrict__ b16) {
+  const int64_t total = m * BT_NV;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t row = i / BT_NV;
+    const int j = (int)(i % BT_NV);
+    b16[i] = j < nv ? B[row * ldb + j] : 0.f;
+  }
 }
 
 }  // namespace fos

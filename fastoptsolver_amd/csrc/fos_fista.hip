@@ -686,7 +686,9 @@ int fos_fista_run_chip(fos_fista* f, int iters) {
 // Up to 16 state machines in lockstep on the matrix cores (gram_batch.hpp): per iteration and per row panel, product 1
 // (R = A_panel Y - b, from HBM) and product 2 (G += R^T A_panel, the panel again from the Infinity Cache), then one
 // update kernel per state machine, which leaves its y_{k+1} in the candidate block of the next product 1.
-static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controlled = false) {
+// b16 (several right-hand sides, unsharded): product 1 subtracts column j of this m x 16 block from candidate column j
+// instead of the problem's b; always the two-product form (the planner's cluster layout, if any, is left as it is).
+static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controlled = false, const float* b16 = nullptr) {
   fos_problem* p = fs[0]->p;
   int rc = ensure_batch_workspace(p);
   if (rc) return rc;
@@ -738,6 +740,16 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
     HIP_TRY(hipMalloc(&p->rbuf16, (size_t)p->panel_rows * fos::BT_NV * sizeof(float)));
     HIP_TRY(hipMalloc(&p->slabs16, (size_t)p->gram_splits * fos::BT_NV * p->n * sizeof(float)));
   }
+  // row splits of product 2: the planned ones, or - a B-block run on a problem planned for the cluster form, whose slab
+  // count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated
+  const bool use_cluster = p->cp_cs && !b16;
+  int g_splits = p->gram_splits;
+  if (p->cp_cs && b16) {
+    g_splits = (int)((p->panel_rows + p->gram_rows_per_split - 1) / p->gram_rows_per_split);
+    if (g_splits > p->gram_splits)
+      return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs: the cluster layout of this problem has too few slabs "
+                                       "for the two-product form");
+  }
   // candidate block: zero everywhere (padding columns, unused slots), then y_k of every state machine
   const size_t per_entry = is_bf16 ? 3 * sizeof(unsigned short) : sizeof(float);
   HIP_TRY(hipMemsetAsync(p->xp, 0, (size_t)p->n_pad * fos::BT_NV * per_entry, p->stream));
@@ -780,7 +792,7 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
   }
   for (int it = 0; it < iters; ++it) {
     if ((rc = prof_mark(p, true))) return rc;
-    if (p->cp_cs) {
+    if (use_cluster) {
       if ((rc = launch_cluster_pass(p))) {
         if (p->cp_mode == 1 || it > 0) return rc;
         (void)hipGetLastError();                 // planner's own choice refused (cooperative launch): two products instead
@@ -789,7 +801,7 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
         HIP_TRY(hipStreamSynchronize(p->stream));
         (void)hipFree(p->rbuf16); (void)hipFree(p->slabs16);       // sized for the cluster form: re-planned by the re-entry
         p->rbuf16 = p->slabs16 = nullptr;
-        return run_multi_mfma(fs, nv, iters, controlled);
+        return run_multi_mfma(fs, nv, iters, controlled, b16);
       }
     } else
     for (int64_t row0 = 0, panel = 0; row0 < p->m; row0 += p->panel_rows, ++panel) {
@@ -797,10 +809,10 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
       const char* Ap = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz;
       int nwg1 = 0;
       // column-sharded: b enters the sum over the ranks once (rank 0); R = sum_p A_p Y_p - b is the ONE exchange per panel
-      const float* bp = (p->b && !(cols && p->comm->rank != 0)) ? p->b + row0 : nullptr;
-      if ((rc = launch_batch_product(p, Ap, bp, rows, 1, p->rbuf16, &nwg1))) return rc;
+      const float* bp = b16 ? b16 + row0 * fos::BT_NV : (p->b && !(cols && p->comm->rank != 0)) ? p->b + row0 : nullptr;
+      if ((rc = launch_batch_product(p, Ap, bp, rows, 1, p->rbuf16, &nwg1, nullptr, b16 != nullptr))) return rc;
       if (cols && (rc = reduce_across(p, p->rbuf16, (size_t)rows * fos::BT_NV, false))) return rc;
-      const dim3 grid((unsigned)strips, (unsigned)p->gram_splits);
+      const dim3 grid((unsigned)strips, (unsigned)g_splits);
 #define FOS_GRAM(T, ACC)                                                                                                  \
   hipLaunchKernelGGL((fos::gram_batch_mfma_kernel<T, ACC>), grid, dim3(fos::GB_THREADS), 0, p->stream, (const T*)Ap, p->lda, \
                      rows, (int)p->n, p->rbuf16, p->gram_rows_per_split, p->slabs16, p->n)
@@ -818,7 +830,7 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
     if ((rc = prof_mark(p, false))) return rc;
     // row-sharded problem: the 16 partial gradients (all row splits) are summed over the ranks before the updates
     // (column-sharded: the gradient block is local)
-    if (!cols && (rc = reduce_across(p, p->slabs16, (size_t)p->gram_splits * fos::BT_NV * p->n, false))) return rc;
+    if (!cols && (rc = reduce_across(p, p->slabs16, (size_t)g_splits * fos::BT_NV * p->n, false))) return rc;
     if (controlled) {                            // update (device beta) -> bookkeeping of all weights -> their y_{k+1}
       fos::MultiUpdate mu{};
       for (int v = 0; v < nv; ++v) {
@@ -827,7 +839,7 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
         mu.alpha1[v] = f->prm.alpha1; mu.alpha2[v] = f->prm.alpha2; mu.tau[v] = f->prm.tau;
       }
       hipLaunchKernelGGL(fos::fista_update_multi_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->slabs16,
-                         p->gram_splits, (int)p->n, mu, fs[0]->prm, p->xp, is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP, 0);
+                         g_splits, (int)p->n, mu, fs[0]->prm, p->xp, is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP, 0);
       LAUNCH_CHECK();
       if (cols) {                                // step norms, ||x||^2, ||x||_1 are sums over the column blocks of all ranks
         hipLaunchKernelGGL(fold4_multi_kernel, dim3(nv), dim3(64), 0, p->stream, mc, fs[0]->nupd, p->mfold);
@@ -856,7 +868,7 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
         f->plain_count += 1;
       }
       hipLaunchKernelGGL(fos::fista_update_multi_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->slabs16,
-                         p->gram_splits, (int)p->n, mu, fs[0]->prm, p->xp, is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP);
+                         g_splits, (int)p->n, mu, fs[0]->prm, p->xp, is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP);
       LAUNCH_CHECK();
     } else {
       for (int v = 0; v < nv; ++v) {
@@ -864,7 +876,7 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
         const double beta_k = f->h_beta;
         host_momentum(f->prm, f->h_k, &f->h_t, &f->h_beta);
         launch_update_from_slabs(f, f->part2 + (size_t)(f->h_k & 1) * psz, 1, beta_k, nullptr, p->xp, f->h_beta,
-                                 p->slabs16 + (size_t)v * p->n, (int64_t)fos::BT_NV * p->n, p->gram_splits,
+                                 p->slabs16 + (size_t)v * p->n, (int64_t)fos::BT_NV * p->n, g_splits,
                                  is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP, v);
         LAUNCH_CHECK();
         f->h_k += 1;
@@ -872,7 +884,7 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
       }
     }
   }
-  if (p->cp_cs) {        // a cluster member that waited out its bound parked itself and raised the flag: the sums are invalid
+  if (use_cluster) {     // a cluster member that waited out its bound parked itself and raised the flag: the sums are invalid
     int bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, p->cp_error, sizeof(int), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
@@ -893,12 +905,20 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
   return FOS_OK;
 }
 
-int fos_fista_run_multi(fos_fista* const* fs, int nv, int iters) {
-  if (!fs || nv < 1 || nv > fos::BT_NV || iters < 0) return fail(FOS_ERR_ARG, "fos_fista_run_multi: bad argument");
-  for (int v = 0; v < nv; ++v)
-    if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi: handles must share one problem");
-  if (nv == 1) return fos_fista_run(fs[0], iters);
+// The lockstep dispatcher of fos_fista_run_multi (B == nullptr: the problem's b) and fos_fista_run_multi_rhs (B: column v of
+// the caller's m x nv block for state machine v, staged once per call into the m x 16 block p->b16).  Arguments are checked.
+static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, int64_t ldb) {
   fos_problem* p = fs[0]->p;
+  const bool rhs = B != nullptr;
+  if (rhs && (p->comm || p->col_sharded))
+    return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs: row- or column-sharded problems are not served");
+  if (nv == 1) {
+    if (rhs) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs: one column runs as a problem of its own");
+    return fos_fista_run(fs[0], iters);
+  }
+  // B is staged once per call, after the kernel choice and only when there are iterations to run
+  auto stage = [&]() { return rhs ? stage_b16(p, B, ldb, nv) : FOS_OK; };
+  const float* b16 = nullptr;                    // p->b16 once staged
   bool all_plain = true, controllable = true, same_family = true;
   for (int v = 0; v < nv; ++v) {
     all_plain = all_plain && plain_run(fs[v]);
@@ -920,19 +940,28 @@ int fos_fista_run_multi(fos_fista* const* fs, int nv, int iters) {
   }
   if (!all_plain && controllable && same_family && shape_ok && p->entry != wide_entry(p->dtype) && (nv >= 3 || p->comm)) {
     if (iters == 0) return FOS_OK;
-    return run_multi_mfma(fs, nv, iters, true);
+    int rc = stage();
+    if (rc) return rc;
+    return run_multi_mfma(fs, nv, iters, true, rhs ? p->b16 : nullptr);
   }
   const bool streaming = shape_ok && all_plain;
   // (a sharded problem takes the matrix-core pass for any number of weights: its 16 gradients are one 16 x n all-reduce)
-  MultiLaunch fn = (streaming && !p->tall && !p->comm && p->dtype == FOS_F32 && p->entry != wide_entry(p->dtype)) ? find_multi(p->n, nv) : nullptr;
+  MultiLaunch fn = (streaming && !p->tall && !p->comm && p->dtype == FOS_F32 && p->entry != wide_entry(p->dtype)) ? find_multi(p->n, nv, rhs) : nullptr;
   // the two-product pass costs about two single-vector passes per iteration whatever the number of weights: it pays
   // from three weights on (profiles/r02_multilambda.md); two weights without a VALU multi-vector kernel run one by one
   if (!fn && streaming && p->entry != wide_entry(p->dtype) && (nv >= 3 || p->comm)) {
     if (iters == 0) return FOS_OK;
-    return run_multi_mfma(fs, nv, iters);          // 5..16 weights, n up to 16384, fp32 and bf16
+    int rc = stage();
+    if (rc) return rc;
+    return run_multi_mfma(fs, nv, iters, false, rhs ? p->b16 : nullptr);   // 5..16 weights, n up to 16384, fp32 and bf16
   }
   if (!fn) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi: no multi-vector kernel for this shape / configuration");
   if (iters == 0) return FOS_OK;
+  {
+    int rc = stage();
+    if (rc) return rc;
+    b16 = rhs ? p->b16 : nullptr;
+  }
   // workspace: nv interleaved slab sets and rr partials per workgroup
   const int nwg = p->nwg;
   if (nwg * nv > p->slab_cap) {
@@ -973,7 +1002,7 @@ int fos_fista_run_multi(fos_fista* const* fs, int nv, int iters) {
   for (int it = 0; it < iters; ++it) {
     int rc = prof_mark(p, true);
     if (rc) return rc;
-    fn((const float*)p->A, p->lda, p->b, p->m, (int)p->n, ys, p->rows_per_wg, p->slabs, p->rr_part, nwg, p->stream);
+    fn((const float*)p->A, p->lda, rhs ? b16 : p->b, p->m, (int)p->n, ys, p->rows_per_wg, p->slabs, p->rr_part, nwg, p->stream);
     LAUNCH_CHECK();
     if ((rc = prof_mark(p, false))) return rc;
     for (int v = 0; v < nv; ++v) {
@@ -998,6 +1027,21 @@ int fos_fista_run_multi(fos_fista* const* fs, int nv, int iters) {
     LAUNCH_CHECK();
   }
   return FOS_OK;
+}
+
+int fos_fista_run_multi(fos_fista* const* fs, int nv, int iters) {
+  if (!fs || nv < 1 || nv > fos::BT_NV || iters < 0) return fail(FOS_ERR_ARG, "fos_fista_run_multi: bad argument");
+  for (int v = 0; v < nv; ++v)
+    if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi: handles must share one problem");
+  return run_multi(fs, nv, iters, nullptr, 0);
+}
+
+int fos_fista_run_multi_rhs(fos_fista* const* fs, int nv, const float* B, int64_t ldb, int iters) {
+  if (!fs || !B || nv < 1 || nv > fos::BT_NV || ldb < nv || iters < 0)
+    return fail(FOS_ERR_ARG, "fos_fista_run_multi_rhs: bad argument (null pointer, nv outside 1..16, ldb < nv or iters < 0)");
+  for (int v = 0; v < nv; ++v)
+    if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi_rhs: handles must share one problem");
+  return run_multi(fs, nv, iters, B, ldb);
 }
 
 int fos_fista_grad(fos_fista* f) {

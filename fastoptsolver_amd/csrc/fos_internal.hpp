@@ -157,6 +157,7 @@ struct fos_problem {
   // multi-lambda pass on the matrix cores (gram_batch.hpp): residual panel and the 16 gradient slab sets
   float* rbuf16 = nullptr;           // panel_rows x 16 floats
   float* rcols16 = nullptr;          // column-sharded candidate pass: m x 16 partial residuals (summed over the ranks)
+  float* b16 = nullptr;              // several right-hand sides: m x 16 zero-padded block of the caller's B (stage_b16)
   double* cr_part = nullptr;         // chip-resident loop (chip_resident.hpp): [2][G][17] partials + [8] step sums + [1] rr
   unsigned* cr_bar = nullptr;
   unsigned long long* fz_stamps = nullptr;   // caller-owned (fos_problem_set_fused_stamps), [ncu][8]
@@ -233,16 +234,19 @@ int prof_drain(fos_problem* p);
 int prof_mark(fos_problem* p, bool start);
 int aligned_vec(fos_problem* p, const float* v, const float** out);
 bool batch_supported(const fos_problem* p);
-MultiLaunch find_multi(int64_t n, int nv);
+MultiLaunch find_multi(int64_t n, int nv, bool bblock = false);
+// several right-hand sides: the caller's B (m x nv, leading dimension ldb) -> p->b16, zero beyond column nv
+int stage_b16(fos_problem* p, const float* B, int64_t ldb, int nv);
 // Enqueue the A pass for `ys`.  with_g: also produce the slabs (A^T r).  *n_rr: number of rr partials written.
 int launch_pass(fos_problem* p, const YSource& ys, const float* b, bool with_g, int* n_rr, bool dual = false);
 // slabs -> gbuf[0..n], summed over the ranks when the problem is row-sharded; rr_out (nullable) = the global ||r||^2
 int launch_slab_reduce(fos_problem* p, int n_rr, float* gbuf, double* rr_out, const int* stopped);
 // Product 1 on `rows` rows starting at A / b: q_part[wg][16] partial squared norms, rout (nullable): the residuals
+// (bblock: b is the rows x 16 right-hand-side block, column j subtracts its own b[row * 16 + j])
 int launch_batch_product(fos_problem* p, const void* A, const float* b, int64_t rows_total, int use_b, float* rout, int* nwg_out,
-                         const int* stopped = nullptr);
-// q[j] = ||A Xp_j - use_b*b||^2 -> out16 (device); Xp already in p->xp
-int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* stopped = nullptr);
+                         const int* stopped = nullptr, bool bblock = false);
+// q[j] = ||A Xp_j - use_b*b||^2 -> out16 (device); Xp already in p->xp.  b16 (unsharded only): subtract its column j instead
+int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* stopped = nullptr, const float* b16 = nullptr);
 int launch_cluster_pass(fos_problem* p);
 // the fp64-accumulating pass for any y source: out[0..n) = A^T (A y - b) + alpha2*l2vec, out[n] = ||A y - b||^2
 int launch_pass_dd(fos_problem* p, const YSource& ys, double alpha2, const double* l2vec, double* out);

@@ -585,25 +585,30 @@ int ensure_batch_workspace(fos_problem* p) {
 // tile is kept for short problems, where it gives twice as many workgroups.
 typedef void (*Bf16Batch)(const fos::bf16_t*, int64_t, const float*, int, int64_t, int, const unsigned short*, int64_t, double*,
                           float*, const int*);
-struct Bf16BatchVariant { Bf16Batch fn, fn_store; int rows; int wg_per_cu; };     // fn_store: also keeps R (gram_batch.hpp)
+// fn_store: also keeps R (gram_batch.hpp); fn_rhs / fn_store_rhs: the same with a right-hand side per column (B16 block)
+struct Bf16BatchVariant { Bf16Batch fn, fn_store; int rows; int wg_per_cu; Bf16Batch fn_rhs, fn_store_rhs; };
 const Bf16BatchVariant kBf16Batch[] = {
-    {fos::residual_batch_mfma_bf16_kernel<1, 128>, fos::residual_batch_mfma_bf16_kernel<1, 128, true>, 64, 2},
-    {fos::residual_batch_mfma_bf16_kernel<2, 128>, fos::residual_batch_mfma_bf16_kernel<2, 128, true>, 128, 1},
+    {fos::residual_batch_mfma_bf16_kernel<1, 128>, fos::residual_batch_mfma_bf16_kernel<1, 128, true>, 64, 2,
+     fos::residual_batch_mfma_bf16_kernel<1, 128, false, true>, fos::residual_batch_mfma_bf16_kernel<1, 128, true, true>},
+    {fos::residual_batch_mfma_bf16_kernel<2, 128>, fos::residual_batch_mfma_bf16_kernel<2, 128, true>, 128, 1,
+     fos::residual_batch_mfma_bf16_kernel<2, 128, false, true>, fos::residual_batch_mfma_bf16_kernel<2, 128, true, true>},
 };
 
 typedef void (*F32Batch)(const float*, int64_t, const float*, int, int64_t, int, const float*, int64_t, double*, float*,
                          const int*);
-struct F32BatchVariant { F32Batch fn, fn_store; int rows; int wg_per_cu; };
+struct F32BatchVariant { F32Batch fn, fn_store; int rows; int wg_per_cu; F32Batch fn_rhs, fn_store_rhs; };
 // fp32, measured at 65536 x 8192: <1> 64-row tile 368-395 us, <2> 128-row tile 335.7 us (80 % of HBM), <4> 336.8 us.
 const F32BatchVariant kF32Batch[] = {
-    {fos::residual_batch_mfma_kernel<1>, fos::residual_batch_mfma_kernel<1, true>, 64, 3},
-    {fos::residual_batch_mfma_kernel<2>, fos::residual_batch_mfma_kernel<2, true>, 128, 2},
+    {fos::residual_batch_mfma_kernel<1>, fos::residual_batch_mfma_kernel<1, true>, 64, 3,
+     fos::residual_batch_mfma_kernel<1, false, true>, fos::residual_batch_mfma_kernel<1, true, true>},
+    {fos::residual_batch_mfma_kernel<2>, fos::residual_batch_mfma_kernel<2, true>, 128, 2,
+     fos::residual_batch_mfma_kernel<2, false, true>, fos::residual_batch_mfma_kernel<2, true, true>},
 };
 
 // Product 1 on `rows` rows starting at A / b: q_part[wg][16] partial squared norms, rout (nullable): the residuals.
 // Returns the number of workgroups (rows of q_part).
 int launch_batch_product(fos_problem* p, const void* A, const float* b, int64_t rows_total, int use_b, float* rout, int* nwg_out,
-                         const int* stopped) {
+                         const int* stopped, bool bblock) {
   const bool is_bf16 = p->dtype == FOS_BF16;
   const int variant = rows_total >= 128 * (int64_t)p->ncu ? 1 : 0;
   const int rows = is_bf16 ? kBf16Batch[variant].rows : kF32Batch[variant].rows;
@@ -612,12 +617,14 @@ int launch_batch_product(fos_problem* p, const void* A, const float* b, int64_t 
   int64_t nwg = std::min<int64_t>(ngroups, per_cu * (int64_t)p->ncu);
   const int64_t gpw = (ngroups + nwg - 1) / nwg;
   nwg = (ngroups + gpw - 1) / gpw;
+  const Bf16BatchVariant& vq = kBf16Batch[variant];
+  const F32BatchVariant& vf = kF32Batch[variant];
   if (is_bf16)
-    hipLaunchKernelGGL(rout ? kBf16Batch[variant].fn_store : kBf16Batch[variant].fn, dim3((unsigned)nwg),
+    hipLaunchKernelGGL(bblock ? (rout ? vq.fn_store_rhs : vq.fn_rhs) : (rout ? vq.fn_store : vq.fn), dim3((unsigned)nwg),
                        dim3(fos::BT_THREADS), 0, p->stream, (const fos::bf16_t*)A, p->lda, b, (use_b && b) ? 1 : 0,
                        rows_total, (int)p->n, (const unsigned short*)p->xp, gpw, p->q_part, rout, stopped);
   else
-    hipLaunchKernelGGL(rout ? kF32Batch[variant].fn_store : kF32Batch[variant].fn, dim3((unsigned)nwg),
+    hipLaunchKernelGGL(bblock ? (rout ? vf.fn_store_rhs : vf.fn_rhs) : (rout ? vf.fn_store : vf.fn), dim3((unsigned)nwg),
                        dim3(fos::BT_THREADS), 0, p->stream, (const float*)A, p->lda, b, (use_b && b) ? 1 : 0, rows_total,
                        (int)p->n, p->xp, gpw, p->q_part, rout, stopped);
   LAUNCH_CHECK();
@@ -650,7 +657,7 @@ __global__ __launch_bounds__(256) void unsum16_if_stopped_kernel(float* __restri
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) v[i] *= scale;
 }
 
-int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* stopped) {
+int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* stopped, const float* b16) {
   int rc = prof_mark(p, true);
   if (rc) return rc;
   int nwg = 0;
@@ -674,7 +681,7 @@ int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* s
     LAUNCH_CHECK();
     return FOS_OK;
   }
-  if ((rc = launch_batch_product(p, p->A, p->b, p->m, use_b, nullptr, &nwg, stopped))) return rc;
+  if ((rc = launch_batch_product(p, p->A, b16 ? b16 : p->b, p->m, use_b, nullptr, &nwg, stopped, b16 != nullptr))) return rc;
   if ((rc = prof_mark(p, false))) return rc;
   hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->q_part, (int)nwg, fos::BT_NV, out16);
   LAUNCH_CHECK();
@@ -683,19 +690,32 @@ int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* s
 
 // ---- multi-lambda lockstep run ----------------------------------------------------------------------------------
 
-template <int THREADS, int K, int NVEC>
+// BBLOCK: b is the m x 16 right-hand-side block (one b per vector)
+template <int THREADS, int K, int NVEC, bool BBLOCK = false>
 void multi_launch(const float* A, int64_t lda, const float* b, int64_t m, int n, fos::MultiY ys, int64_t rpw,
                          float* slabs, double* rr_part, int nwg, hipStream_t st) {
-  hipLaunchKernelGGL((fos::gemv_multi_kernel<float, THREADS, K, 2, NVEC, 2>), dim3(nwg), dim3(THREADS), 0, st, A, lda, b,
-                     m, n, ys, rpw, slabs, rr_part);
+  hipLaunchKernelGGL((fos::gemv_multi_kernel<float, THREADS, K, 2, NVEC, 2, BBLOCK>), dim3(nwg), dim3(THREADS), 0, st, A, lda,
+                     b, m, n, ys, rpw, slabs, rr_part);
 }
-MultiLaunch find_multi(int64_t n, int nv) {
+MultiLaunch find_multi(int64_t n, int nv, bool bblock) {
   static const MultiLaunch small[3] = {multi_launch<256, 4, 2>, multi_launch<256, 4, 3>, multi_launch<256, 4, 4>};
   static const MultiLaunch big[3] = {multi_launch<512, 4, 2>, multi_launch<512, 4, 3>, multi_launch<512, 4, 4>};
+  static const MultiLaunch small_rhs[3] = {multi_launch<256, 4, 2, true>, multi_launch<256, 4, 3, true>,
+                                           multi_launch<256, 4, 4, true>};
+  static const MultiLaunch big_rhs[3] = {multi_launch<512, 4, 2, true>, multi_launch<512, 4, 3, true>,
+                                         multi_launch<512, 4, 4, true>};
   if (nv < 2 || nv > 4) return nullptr;
-  if (n <= 4096) return small[nv - 2];
-  if (n <= 8192) return big[nv - 2];
+  if (n <= 4096) return (bblock ? small_rhs : small)[nv - 2];
+  if (n <= 8192) return (bblock ? big_rhs : big)[nv - 2];
   return nullptr;
+}
+
+int stage_b16(fos_problem* p, const float* B, int64_t ldb, int nv) {
+  if (!p->b16) HIP_TRY(hipMalloc(&p->b16, (size_t)p->m * fos::BT_NV * sizeof(float)));
+  hipLaunchKernelGGL(fos::stage_b16_kernel, dim3(grid_1d(p->m * fos::BT_NV, 256, 4 * p->ncu)), dim3(256), 0, p->stream, B,
+                     ldb, nv, p->m, p->b16);
+  LAUNCH_CHECK();
+  return FOS_OK;
 }
 
 // The matrix-core passes (16 candidates / 16 weights) need the aligned layout only - not a streaming plan: rows of 65..128
@@ -1081,7 +1101,7 @@ int fos_problem_destroy(fos_problem* p) {
   if (!p) return FOS_OK;
   for (hipEvent_t e : p->ev_pool) (void)hipEventDestroy(e);
   void* bufs[] = {p->slabs, p->rr_part, p->rr2_part, p->rvec, p->gbuf_own, p->ybuf, p->dscal, p->part, p->xp, p->q_part, p->bt_out,
-                  p->slabs_dd, p->rr_dd, p->lhist, p->rbuf16, p->rcols16, p->mfold, p->cr_part, p->cr_bar, p->slabs16, p->rneg, p->zeros, p->cp_xchg, p->cp_flags, p->fz_bar, p->fz_part, p->fz_beta,
+                  p->slabs_dd, p->rr_dd, p->lhist, p->rbuf16, p->rcols16, p->b16, p->mfold, p->cr_part, p->cr_bar, p->slabs16, p->rneg, p->zeros, p->cp_xchg, p->cp_flags, p->fz_bar, p->fz_part, p->fz_beta,
                   p->cp_error};
   for (void* q : bufs)
     if (q) (void)hipFree(q);
@@ -1355,6 +1375,24 @@ int fos_residual_batch(fos_problem* p, const float* X, int nv, int use_b, double
                        (int)p->n_pad, nv, p->xp);
   LAUNCH_CHECK();
   return launch_residual_batch(p, use_b, out16);
+}
+
+int fos_residual_batch_rhs(fos_problem* p, const float* X, int nv, const float* B, int64_t ldb, double* out16) {
+  if (!p || !X || !B || !out16 || nv < 1 || nv > fos::BT_NV || ldb < nv)
+    return fail(FOS_ERR_ARG, "fos_residual_batch_rhs: bad argument (null pointer, nv outside 1..16 or ldb < nv)");
+  if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_rhs: sharded problems are not served");
+  if (!batch_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_rhs: needs the fused path");
+  int rc = ensure_batch_workspace(p);
+  if (rc) return rc;
+  if ((rc = stage_b16(p, B, ldb, nv))) return rc;
+  if (p->dtype == FOS_BF16)
+    hipLaunchKernelGGL(fos::xq_pack_kernel, dim3(grid_1d(p->n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
+                       (int)p->n_pad, nv, (unsigned short*)p->xp);
+  else
+    hipLaunchKernelGGL(xp_pack_kernel, dim3(grid_1d(p->n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
+                       (int)p->n_pad, nv, p->xp);
+  LAUNCH_CHECK();
+  return launch_residual_batch(p, 1, out16, nullptr, p->b16);
 }
 
 int fos_power_iter(fos_problem* p, float* v_inout, int n_iter, double tol, double* L_out, int* iters_out) {

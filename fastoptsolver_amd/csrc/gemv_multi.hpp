@@ -17,7 +17,9 @@ struct MultiY {
   const int* stopped;     // optional device flag of the first state machine
 };
 
-template <typename T, int THREADS, int K, int NBUF, int NVEC, int MINW>
+// BBLOCK = true (several right-hand sides): b is the m x 16 block B16 (stage_b16_kernel) and vector v subtracts its own
+// B16[i][v] - one 16-byte load per row beside the row of A.
+template <typename T, int THREADS, int K, int NBUF, int NVEC, int MINW, bool BBLOCK = false>
 __global__ __launch_bounds__(THREADS, MINW) void gemv_multi_kernel(
     const T* __restrict__ A, int64_t lda, const float* __restrict__ b, int64_t m, int n, MultiY ys,
     int64_t rows_per_wg, float* __restrict__ slabs, double* __restrict__ rr_part) {
@@ -67,11 +69,15 @@ __global__ __launch_bounds__(THREADS, MINW) void gemv_multi_kernel(
 
   u32x4 tile[NBUF][K];
   float bval[NBUF];
+  f32x4 bvec[NBUF];
   const float* b_src = b != nullptr ? b : reinterpret_cast<const float*>(A);
   auto issue = [&](int buf, int64_t step) {
     int64_t row = row_lo + step;
     if (row >= row_hi) row = row_hi - 1;
-    bval[buf] = b_src[b != nullptr ? row : 0];
+    if constexpr (BBLOCK)
+      bvec[buf] = *reinterpret_cast<const f32x4*>(b + row * 16);
+    else
+      bval[buf] = b_src[b != nullptr ? row : 0];
     const char* rp = base + row * row_bytes;
 #pragma unroll
     for (int c = 0; c < K; ++c) tile[buf][c] = load16<true>(rp + voff[c]);
@@ -100,14 +106,17 @@ __global__ __launch_bounds__(THREADS, MINW) void gemv_multi_kernel(
     }
     __syncthreads();
     const bool valid = row_lo + step < row_hi;
-    const float bi = b != nullptr ? bval[buf] : 0.f;
+    const float bi = BBLOCK ? 0.f : (b != nullptr ? bval[buf] : 0.f);
     float res[NVEC];
 #pragma unroll
     for (int v = 0; v < NVEC; ++v) {
       float s = 0.f;
 #pragma unroll
       for (int w = 0; w < NW; ++w) s += red[pb][v][w];
-      s = valid ? s - bi : 0.f;
+      if constexpr (BBLOCK)
+        s = valid ? s - bvec[buf][v] : 0.f;
+      else
+        s = valid ? s - bi : 0.f;
       rr[v] += (double)s * (double)s;
       res[v] = s;
     }

@@ -624,6 +624,93 @@ def _sharded_problem(A, b, dtype, comm, group, cols=None):
 
 
 # ---------------------------------------------------------------------
+# Several targets: fista(A, B) / fista_delta(A, B) with a 2-D B (extension)
+# ---------------------------------------------------------------------
+def _targets(A, b):
+    """The right-hand sides of a multi-target call - a 2-D b with k >= 2 columns against an A without a b of its own - or
+    None.  A 1-D b, a b of shape (m, 1) or (1, m) and a Problem prepared with its own b keep the single-target path."""
+    if b is None or (isinstance(A, _core.Problem) and A.b is not None):
+        return None
+    shape = tuple(b.shape) if hasattr(b, "shape") else np.shape(b)
+    if len(shape) != 2 or shape[1] < 2:
+        return None
+    m = A.m if isinstance(A, _core.Problem) else (A.shape[0] if hasattr(A, "shape") else np.shape(A)[0])
+    return None if shape[0] * shape[1] == m else b
+
+
+def _metrics_apart(fn):
+    """Run `fn` (one single-target solve) against empty metric lists, then put the earlier entries back in front: the
+    solve's own bookkeeping indexes the lists from their start."""
+    lists = (grad_call_times, ls_call_times, ls_call_iters)
+    saved = [list(v) for v in lists]
+    reset_metrics()
+    try:
+        return fn()
+    finally:
+        for v, old in zip(lists, saved):
+            v[:0] = old
+
+
+def _solve_targets(A, B, *, delta, alpha1, alpha2, backtracking, eta, t_init_factor, max_iter, tol, tol_ratio,
+                   adaptive_restart, restart_threshold, L, dtype, check_every, sharded, return_history):
+    """X[:, j] = fista(A, B[:, j], ...) (fista_delta when `delta` is given) for every column j, with A bound once and L
+    estimated once.  Groups of up to 16 columns advance in lockstep on one read of A per iteration
+    (fos_fista_run_multi_rhs); what the lockstep does not serve - shapes without a multi-vector kernel, a last group of
+    one column, backtracking, fista's gradient-norm rule (tol > 0) - runs column by column on sibling problems that borrow
+    the same device A."""
+    if sharded:
+        raise ValueError("a 2-D b (several targets) cannot be combined with comm= / group= / cols=")
+    if return_history:
+        raise ValueError("return_history=True is not available with a 2-D b (several targets)")
+    prob = _core.prepare(A, None, dtype)
+    like = prob.like
+    Bt = B.detach() if _core.is_tensor(B) else torch.from_numpy(np.ascontiguousarray(np.asarray(B)))
+    Bt = Bt.to(device=prob.device, dtype=torch.float32).contiguous()
+    if Bt.shape[0] != prob.m:
+        raise ValueError("b must have m rows")
+    k = int(Bt.shape[1])
+    L_val = float(L) if L is not None else estimate_lipschitz(prob)                    # once for all columns
+    if alpha2 > 0:
+        L_val += alpha2
+    tau = t_init_factor / L_val
+    mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
+    restart = bool(adaptive_restart) and delta is None
+    # fista's tol is also the gradient-norm rule, which sits before the update; fista_delta's is a step stop only
+    lockstep = not backtracking and (tol == 0.0 or delta is not None)
+
+    def one(j):
+        sib = prob.sibling(Bt[:, j].contiguous())
+        return _metrics_apart(lambda: _drive(
+            sib, like, mode=mode, prox_kind=_lib.PROX_L1, alpha1=alpha1, alpha2=alpha2, tau=tau, delta=delta or 0.0,
+            backtracking=backtracking, eta=eta, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio, adaptive_restart=restart,
+            restart_threshold=restart_threshold, grad_tol_check=delta is None, check_every=check_every)).x_tensor()
+
+    X = torch.zeros(prob.n, k, dtype=torch.float64, device=prob.device)
+    width = 4 if k <= 4 else 16            # up to 4: the multi-vector VALU pass where the shape has one; else matrix cores
+    for g0 in range(0, k, width):
+        g1 = min(k, g0 + width)
+        if lockstep and g1 - g0 >= 2:
+            handles = []
+            for _ in range(g0, g1):
+                st = _core.Fista(prob)
+                st.reset(tau, alpha1, alpha2, mode=mode, delta=delta or 0.0, adaptive_restart=restart,
+                         restart_threshold=restart_threshold, tol_step=tol if tol > 0.0 else 0.0,
+                         tol_ratio=tol_ratio if tol_ratio > 0.0 else 0.0)
+                handles.append(st)
+            gtimer = _EventTimer(grad_call_times)
+            ev = gtimer.start()
+            if _core.run_multi_rhs(handles, Bt[:, g0:g1], max_iter):
+                gtimer.stop(ev, max_iter)                  # one gradient per lockstep iteration, as fista_path counts
+                gtimer.flush()
+                for j, st in zip(range(g0, g1), handles):
+                    X[:, j] = st.x_tensor()
+                continue
+        for j in range(g0, g1):
+            X[:, j] = one(j)
+    return _core.from_device_vec(X, like)
+
+
+# ---------------------------------------------------------------------
 # FISTA                                                        ref:132-245
 # ---------------------------------------------------------------------
 def fista(A, b, reg_type: str, alpha1: float, alpha2: float, backtracking: bool = False, eta: float = 0.5,
@@ -636,8 +723,17 @@ def fista(A, b, reg_type: str, alpha1: float, alpha2: float, backtracking: bool 
     torch.distributed group, any backend) does it between the kernels from Python.
     ``cols=(lo, hi, n_total)`` with ``comm=``: COLUMN sharding for very wide A - A is this rank's columns [lo, hi) of
     all rows, b the whole vector; x is partitioned (the result and the history are this rank's block), one all-reduce of
-    an m-vector per iteration (backtracking: plus ONE all-reduce of the 16 candidates' m-vectors per search)."""
+    an m-vector per iteration (backtracking: plus ONE all-reduce of the 16 candidates' m-vectors per search).
+    Several targets: a 2-D ``b`` of shape (m, k), k >= 2, returns x of shape (n, k) whose column j is
+    ``fista(A, b[:, j], ...)`` with the same L (estimated once); up to 16 columns share each read of A."""
     reset_metrics()
+    B = _targets(A, b)
+    if B is not None:
+        return _solve_targets(A, B, delta=None, alpha1=alpha1, alpha2=alpha2, backtracking=backtracking, eta=eta,
+                              t_init_factor=t_init_factor, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio,
+                              adaptive_restart=adaptive_restart, restart_threshold=restart_threshold, L=L, dtype=dtype,
+                              check_every=check_every, sharded=any(v is not None for v in (comm, group, cols)),
+                              return_history=return_history)
     prob, reducer = _sharded_problem(A, b, dtype, comm, group, cols)
     like = prob.like
     if L is not None:
@@ -672,6 +768,12 @@ def fista_delta(A, b, reg_type: str, alpha1: float, alpha2: float, delta: float,
     reset_metrics()
     # Course requirement: delta > 2 for convergence guarantee                   ref:268
     assert delta > 2, "In FISTA-Δ, delta must be > 2 for convergence (course requirement)"
+    B = _targets(A, b)
+    if B is not None:            # several targets: see fista
+        return _solve_targets(A, B, delta=delta, alpha1=alpha1, alpha2=alpha2, backtracking=backtracking, eta=eta,
+                              t_init_factor=t_init_factor, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio,
+                              adaptive_restart=False, restart_threshold=1.0, L=L, dtype=dtype, check_every=check_every,
+                              sharded=any(v is not None for v in (comm, group, cols)), return_history=return_history)
     prob, reducer = _sharded_problem(A, b, dtype, comm, group, cols)
     like = prob.like
     if L is not None:

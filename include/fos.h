@@ -206,6 +206,11 @@ int fos_residual_objective(fos_problem* p, const float* x, double* out3);
  * bf16 A: v_mfma_f32_16x16x32_bf16 with each vector split into three bf16 terms (24 mantissa bits), so both keep
  * fp32 accuracy.  FOS_ERR_UNSUPPORTED on fallback-path problems. */
 int fos_residual_batch(fos_problem* p, const float* X, int nv, int use_b, double* out16);
+/* Several right-hand sides: out16[j] (device doubles) = ||A X_j - B_j||^2 for the nv <= 16 columns of X (layout of
+ * fos_residual_batch) against column j of B (device fp32, m x nv, row-major, leading dimension ldb >= nv); the problem's own
+ * b is not used.  One pass over A; B is staged into an m x 16 zero-padded block first.  FOS_ERR_ARG (checked before any HIP
+ * call): null p / X / B / out16, nv outside 1..16, ldb < nv.  FOS_ERR_UNSUPPORTED on fallback-path and sharded problems. */
+int fos_residual_batch_rhs(fos_problem* p, const float* X, int nv, const float* B, int64_t ldb, double* out16);
 
 /* Power iteration, iterative_solvers.py:45-60.  v_inout: start vector (n floats, need not be normalised),
  * overwritten with the last iterate.  Any n_iter >= 1.  Synchronises; *L_out and *iters_out are host values. */
@@ -277,6 +282,16 @@ int fos_fista_run_history(fos_fista* f, int iters, double* x_hist, double* hist,
  * gradient blocks stay local, 4 doubles per weight of step norms cross per iteration.
  * SURVEY.md 8(f) rank 3. */
 int fos_fista_run_multi(fos_fista* const* fs, int nv, int iters);
+/* Several right-hand sides: nv <= 16 state machines bound to the SAME fos_problem advance `iters` iterations in lockstep,
+ * state machine v solving for column v of B (device fp32, m x nv, row-major, leading dimension ldb >= nv); the problem's
+ * own b is not used.  Same kernel choice, same data-dependent control (adaptive restart, step / ratio stops per state
+ * machine, stopped ones become masked columns) and same FOS_ERR_UNSUPPORTED cases as fos_fista_run_multi, except that the
+ * matrix-core pass always takes the two-product form (no one-read cluster form); also FOS_ERR_UNSUPPORTED for nv = 1 (a
+ * single column runs as a problem of its own) and on row- or column-sharded problems.  B is staged once per call into an
+ * m x 16 zero-padded block that the B-block forms of the kernels read (column j of product 1 subtracts its own B[i][j];
+ * the multi-vector VALU pass subtracts B[i][v] for vector v).  FOS_ERR_ARG (checked before any HIP call): null fs / B,
+ * nv outside 1..16, ldb < nv, iters < 0, handles on different problems.  Enqueues only (like fos_fista_run_multi). */
+int fos_fista_run_multi_rhs(fos_fista* const* fs, int nv, const float* B, int64_t ldb, int iters);
 /* BASELINE north_star's literal step, opt-in: `iters` plain iterations in ONE persistent launch - A staged through LDS
  * in 4-row panels, the row dots A y on v_mfma_f32_4x4x1_16B_f32, A^T r on the VALU from the staged tile, a grid-wide
  * barrier, then prox + momentum by the workgroup that OWNS the columns, whose slice of x_k, x_{k-1} stays in its LDS for
