@@ -123,6 +123,9 @@ SIGNATURES = {
     "fos_linesearch_step": (_f64, [C.POINTER(LineSearchState), _f64, _f64, _f64]),
     "fos_lbfgs_minimize": (_i32, [_vp, _f64, _i32, _f64, _vp, C.POINTER(_f64), _vp, C.POINTER(C.c_float), _i32,
                                   C.POINTER(LbfgsResult)]),
+    "fos_gemv_pair_dd_multi": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _f64, _vp, _vp]),
+    "fos_lbfgs_minimize_multi": (_i32, [_vp, _i32, _vp, _i64, _f64, _i32, _f64, _vp, _i64, C.POINTER(_f64),
+                                        C.POINTER(C.c_float), _i32, C.POINTER(_i32), C.POINTER(LbfgsResult)]),
 }
 
 _lib = None

@@ -25,6 +25,7 @@
 #include "gemv_tall.hpp"
 #include "gemv_wide.hpp"
 #include "gram_batch.hpp"
+#include "gram_batch_dd.hpp"
 #include "lbfgs_driver.hpp"
 #include "lbfgs_kernels.hpp"
 #include "reduce_update.hpp"
@@ -97,6 +98,23 @@ struct LbfgsWork {
   }
 };
 
+// Device + pinned workspace of fos_lbfgs_minimize_multi (16 columns, column-contiguous), cached like LbfgsWork.
+struct LbfgsMultiWork {
+  int64_t n = 0;
+  double *g = nullptr;                 // [2][16][n]: the two gradient buffers of every column (current / previous)
+  double *d = nullptr, *x_old = nullptr, *S = nullptr, *Y = nullptr, *vl = nullptr, *rr = nullptr;
+  double* host = nullptr;              // pinned: 16 columns x 16 doubles, then the sequence number
+  unsigned* count = nullptr;           // device: workgroups of the statistics launch that have reported
+  unsigned long long* t_start = nullptr;
+  double ticks_per_ms = 1e5;
+  ~LbfgsMultiWork() {
+    void* bufs[] = {g, d, x_old, S, Y, vl, rr, count, t_start};
+    for (void* q : bufs)
+      if (q) (void)hipFree(q);
+    if (host) (void)hipHostFree(host);
+  }
+};
+
 struct fos_problem {
   const void* A = nullptr;
   const float* b = nullptr;
@@ -106,6 +124,7 @@ struct fos_problem {
   int ncu = 256;
   fos_comm* comm = nullptr;          // row-sharded problem: sums of partial results go through it (comm.hpp)
   LbfgsWork* lbfgs = nullptr;        // fos_lbfgs_minimize workspace, allocated by the first fit
+  LbfgsMultiWork* lbfgs_multi = nullptr;   // fos_lbfgs_minimize_multi workspace
   bool col_sharded = false;          // comm splits the COLUMNS instead: this rank holds A[:, its columns], x is partitioned
   unsigned plan_flags = 0;           // FOS_PLAN_* given to fos_problem_replan
   bool allow_resident = true;
@@ -166,6 +185,14 @@ struct fos_problem {
   int64_t panel_rows = 0;
   int gram_splits = 0;
   int64_t gram_rows_per_split = 0;
+  // fp64 multi-point pass on the matrix cores (gram_batch_dd.hpp, fos_gemv_pair_dd_multi): staged points, residual panel,
+  // slab sets and product-1 partials of all panels; geometry decided on first use
+  double* xd = nullptr;              // n_pad64 x 16 doubles (Xp layout)
+  double* rdd = nullptr;             // dm_panel_rows x 16 doubles
+  double* slabs_dd16 = nullptr;      // dm_splits x 16 x n doubles
+  double* qdd_part = nullptr;        // panels x 2 * ncu x 16 doubles
+  int64_t dm_n_pad = 0, dm_panel_rows = 0, dm_rows_per_split = 0;
+  int dm_splits = 0;
   // one-read form of the same pass (cluster_pass.hpp): hand-off ring, flags, launch epoch
   int cp_cs = 0, cp_clusters = 0;    // members per cluster (0: shape not served), clusters
   int64_t cp_rows_per_cluster = 0;
@@ -252,6 +279,11 @@ int launch_cluster_pass(fos_problem* p);
 int launch_pass_dd(fos_problem* p, const YSource& ys, double alpha2, const double* l2vec, double* out);
 int gemv_pair_dd_stamped(fos_problem* p, const double* x, double alpha2, double* grad_rr, unsigned long long* t_stamp, bool* stamped);
 int dd_pass_stamps(fos_problem* p, bool* yes);
+// fp64 multi-point pass (gram_batch_dd.hpp) over the columns c.col[0..ncols) (bit j of `live`: column j takes part; the
+// others are zero in the staged block): g_j = A^T (A x_j - b16_j) + alpha2 x_j, *rr_j = ||A x_j - b16_j||^2.  b16: the
+// staged m x 16 block (stage_b16).  FOS_ERR_UNSUPPORTED where the shape has no matrix-core pair (pair_dd_multi_supported).
+bool pair_dd_multi_supported(const fos_problem* p);
+int pair_dd_multi(fos_problem* p, const fos::DdMultiCols& c, int ncols, unsigned live, double alpha2, const float* b16);
 // ---- fos_comm.hip ---------------------------------------------------------------------------------------------------
 // in-place sum over the ranks of a communicator on `st`: RCCL, or the one-shot full-mesh kernel (comm.hpp)
 int comm_allreduce(fos_comm* c, void* buf, size_t count, bool f64, hipStream_t st);

@@ -319,6 +319,303 @@ int fos_lbfgs_minimize(fos_problem* p, double alpha2, int max_iter, double pgtol
   }
 }
 
+// nv fits of fos_lbfgs_minimize in lockstep (include/fos.h).  Every fit runs the single-target driver above as a state
+// machine that stops wherever it waits for an evaluation: after the host step of a round, every unfinished fit has
+// enqueued exactly one next point, and ONE fos_gemv_pair_dd_multi pass evaluates them all.  Between passes the vector work
+// of all fits is one launch per kind (store_pair, direction, first trial, line-search step, statistics), column from
+// blockIdx.y, each with the arithmetic of its single-target kernel.
+int fos_lbfgs_minimize_multi(fos_problem* p, int nv, const float* B, int64_t ldb, double alpha2, int max_iter, double pgtol,
+                             double* X, int64_t ldx, double* hist, float* round_ms, int round_cap, int* rounds,
+                             fos_lbfgs_result* res) {
+  if (!p || !B || !X || !res || nv < 2 || nv > fos::LM_MAXV || ldb < nv || ldx < 1 || max_iter < 0)
+    return fail(FOS_ERR_ARG, "fos_lbfgs_minimize_multi: bad argument (null pointer, nv outside 2..16, ldb < nv, ldx < n or "
+                             "max_iter < 0)");
+  if (ldx < p->n) return fail(FOS_ERR_ARG, "fos_lbfgs_minimize_multi: bad argument (ldx < n)");
+  if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_lbfgs_minimize_multi: sharded problems are not served");
+  if (!pair_dd_multi_supported(p))
+    return fail(FOS_ERR_UNSUPPORTED, "fos_lbfgs_minimize_multi: no multi-point fp64 pass for this shape (fit the columns one by one)");
+  constexpr int M = 10, MAXLS = 20, NV = fos::LM_MAXV, SLOTS = 16;
+  constexpr double FACTR = 1e7, EPS = 2.220446049250313e-16;
+  const int64_t n = p->n;
+  const size_t nb = (size_t)n * sizeof(double);
+  const int64_t vlw = fos_lbfgs_direction_work(n);
+  hipStream_t st = p->stream;
+  if (p->lbfgs_multi == nullptr || p->lbfgs_multi->n != n) {
+    delete p->lbfgs_multi;
+    p->lbfgs_multi = new LbfgsMultiWork();
+    LbfgsMultiWork& nw = *p->lbfgs_multi;
+    HIP_TRY(hipMalloc(&nw.g, 2 * NV * nb));
+    HIP_TRY(hipMalloc(&nw.d, NV * nb));
+    HIP_TRY(hipMalloc(&nw.x_old, NV * nb));
+    HIP_TRY(hipMalloc(&nw.S, (size_t)NV * M * nb));
+    HIP_TRY(hipMalloc(&nw.Y, (size_t)NV * M * nb));
+    HIP_TRY(hipMalloc(&nw.vl, (size_t)NV * vlw * sizeof(double)));
+    HIP_TRY(hipMalloc(&nw.rr, NV * sizeof(double)));
+    HIP_TRY(hipMalloc(&nw.count, sizeof(unsigned)));
+    HIP_TRY(hipMemsetAsync(nw.count, 0, sizeof(unsigned), st));
+    HIP_TRY(hipHostMalloc(&nw.host, (NV * SLOTS + 8) * sizeof(double)));
+    HIP_TRY(hipMalloc(&nw.t_start, sizeof(unsigned long long)));
+    int dev = 0, khz = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && khz > 0) nw.ticks_per_ms = (double)khz;
+    nw.n = n;                                  // complete: a partial allocation is rebuilt by the next call
+  }
+  LbfgsMultiWork& w = *p->lbfgs_multi;
+  double* host_dev = nullptr;
+  HIP_TRY(hipHostGetDevicePointer((void**)&host_dev, w.host, 0));
+  unsigned long long* flag_host = reinterpret_cast<unsigned long long*>(w.host + NV * SLOTS);
+  unsigned long long* flag_dev = reinterpret_cast<unsigned long long*>(host_dev + NV * SLOTS);
+  *flag_host = 0;
+  unsigned long long seq = 0;
+  int rc = stage_b16(p, B, ldb, nv);
+  if (rc) return rc;
+
+  auto xv = [&](int j) { return X + (size_t)j * ldx; };
+  auto gbuf = [&](int j, int which) { return w.g + ((size_t)which * NV + j) * n; };
+  auto dv = [&](int j) { return w.d + (size_t)j * n; };
+  auto xov = [&](int j) { return w.x_old + (size_t)j * n; };
+  auto hs = [&](int j) { return w.host + (size_t)j * SLOTS; };
+  struct Col {
+    int stage = 0;                 // 0 first evaluation, 1 speculative first trial, 2 line-search trial, 3 finished
+    int gi = 0;                    // gradient buffer holding g (the other one holds g_old)
+    int hist_n = 0, head = 0, nit = 0, nfev = 0, evals = 0;
+    bool need_dir = false, step = false, pair = false;
+    int pair_slot = 0;
+    double f = 0.0, gmax = 0.0, f_old = 0.0, gmax_old = 0.0, gd0 = 0.0, gd1 = 0.0, stp = 1.0, stp_used = 1.0, xnorm1 = 0.0;
+    fos_linesearch ls{};
+  };
+  Col col[NV];
+  int nround = 0;
+  const int ax_grid = grid_1d(n, 256, 1024);
+
+  auto finish = [&](int j, int task) {
+    Col& c = col[j];
+    res[j].f = c.f; res[j].gmax = c.gmax; res[j].nit = c.nit; res[j].nfev = c.nfev; res[j].task = task; res[j].reserved = 0;
+    c.stage = 3;
+    c.need_dir = c.step = false;
+  };
+  // one pass for every unfinished fit at its point, then the statistics of all of them; the host polls the sequence flag
+  auto round = [&]() -> int {
+    fos::DdMultiCols pc{};
+    fos::LbMulti sc{};
+    unsigned live = 0;
+    int k = 0;
+    for (int j = 0; j < nv; ++j) {
+      if (col[j].stage == 3) continue;
+      live |= 1u << j;
+      pc.x[j] = xv(j); pc.g[j] = gbuf(j, col[j].gi); pc.rr[j] = w.rr + j; pc.col[k] = j;
+      sc.x[k] = xv(j); sc.g[k] = gbuf(j, col[j].gi); sc.d[k] = col[j].stage == 0 ? nullptr : dv(j);
+      sc.out[k] = host_dev + (size_t)j * SLOTS; sc.rr[k] = w.rr + j;
+      ++k;
+    }
+    if (round_ms) {
+      hipLaunchKernelGGL(fos::stamp_kernel, dim3(1), dim3(1), 0, st, w.t_start);
+      LAUNCH_CHECK();
+    }
+    int rc2 = pair_dd_multi(p, pc, k, live, alpha2, p->b16);
+    if (rc2) return rc2;
+    seq += 1;
+    hipLaunchKernelGGL(fos::vec_stats_multi_kernel, dim3(1, k), dim3(fos::LB_THREADS), 0, st, sc, n, w.count, flag_dev, seq,
+                       round_ms ? (const unsigned long long*)w.t_start : nullptr);
+    LAUNCH_CHECK();
+    const auto t0 = std::chrono::steady_clock::now();
+    bool seen = false;
+    for (int spin = 0;; ++spin) {
+      if (__atomic_load_n(flag_host, __ATOMIC_ACQUIRE) == seq) { seen = true; break; }
+      if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(4)) break;
+    }
+    if (!seen) {
+      HIP_TRY(hipStreamSynchronize(st));
+      if (__atomic_load_n(flag_host, __ATOMIC_ACQUIRE) != seq)
+        return fail(FOS_ERR_HIP, "fos_lbfgs_minimize_multi: evaluation did not report");
+    }
+    if (round_ms && nround < round_cap) round_ms[nround] = (float)(hs(pc.col[0])[9] / w.ticks_per_ms);
+    nround += 1;
+    return FOS_OK;
+  };
+  auto take_fg = [&](int j, double* gd) {
+    Col& c = col[j];
+    const double* h = hs(j);
+    c.nfev += 1;
+    c.f = 0.5 * h[5] + 0.5 * alpha2 * h[0];
+    *gd = h[1];
+    c.gmax = h[3];
+    c.xnorm1 = h[4];
+  };
+  auto restore = [&](int j) -> int {          // the evaluations since x_old never happened
+    HIP_TRY(hipMemcpyAsync(xv(j), xov(j), nb, hipMemcpyDeviceToDevice, st));
+    col[j].gi ^= 1;
+    return FOS_OK;
+  };
+  auto drop_memory = [&](int j) {             // L-BFGS-B info = -4, or the line search failed: start again from x
+    Col& c = col[j];
+    if (c.hist_n == 0) { finish(j, 3); return; }
+    c.hist_n = 0; c.head = 0;
+    c.need_dir = true;
+  };
+  // the line search of fit j after an evaluation (fos_lbfgs_minimize's inner loop and what follows it)
+  auto line_search = [&](int j) -> int {
+    Col& c = col[j];
+    take_fg(j, &c.gd1);
+    c.evals += 1;
+    c.stp_used = c.stp;
+    c.stp = fos_ls_step_impl(&c.ls, c.stp, c.f, c.gd1);
+    bool failed = false;
+    if (c.ls.status == FOS_LS_FG) {
+      if (c.evals < MAXLS) { c.stage = 2; c.step = true; return FOS_OK; }     // next trial x = x_old + stp*d
+      failed = true;
+    }
+    if (failed || c.ls.status == FOS_LS_ERROR) {
+      int rc2 = restore(j);
+      if (rc2) return rc2;
+      c.f = c.f_old; c.gmax = c.gmax_old;
+      drop_memory(j);
+      return FOS_OK;
+    }
+    c.stp = c.stp_used;
+    if (hist && c.nit < max_iter) {
+      hist[(size_t)j * 2 * max_iter + 2 * c.nit] = c.f;
+      hist[(size_t)j * 2 * max_iter + 2 * c.nit + 1] = c.xnorm1;
+    }
+    const double sy = (c.gd1 - c.gd0) * c.stp;  // keep the pair only if its curvature is positive
+    if (sy > EPS * (-c.gd0 * c.stp)) {
+      c.pair_slot = (c.head + c.hist_n) % M;
+      if (c.hist_n == M) c.head = (c.head + 1) % M;
+      else c.hist_n += 1;
+      c.pair = true;
+    }
+    c.nit += 1;
+    if (c.nit >= max_iter) finish(j, 2);
+    else if (c.gmax <= pgtol) finish(j, 0);
+    else if ((c.f_old - c.f) <= EPS * FACTR * std::max(std::max(std::fabs(c.f_old), std::fabs(c.f)), 1.0)) finish(j, 1);
+    else c.need_dir = true;
+    return FOS_OK;
+  };
+  auto fill = [&](fos::LbMulti& c, int k, int j) {
+    c.g[k] = gbuf(j, col[j].gi); c.g_old[k] = gbuf(j, col[j].gi ^ 1);
+    c.S[k] = w.S + (size_t)j * M * n; c.Y[k] = w.Y + (size_t)j * M * n;
+    c.x[k] = xv(j); c.x_old[k] = xov(j); c.d[k] = dv(j);
+    c.out[k] = host_dev + (size_t)j * SLOTS; c.work[k] = w.vl + (size_t)j * vlw; c.rr[k] = w.rr + j;
+    c.stp[k] = col[j].stp; c.hist[k] = col[j].hist_n; c.head[k] = col[j].head;
+    c.fuse[k] = n >= 2048 && col[j].nit > 0;
+  };
+
+  if ((rc = round())) return rc;
+  for (int j = 0; j < nv; ++j) {
+    double gd = 0.0;
+    take_fg(j, &gd);
+    if (col[j].gmax <= pgtol) finish(j, 0);
+    else col[j].need_dir = true;
+  }
+  for (;;) {
+    // curvature pairs kept by the last host step: s = stp*d, y = g - g_old
+    {
+      fos::LbMulti c{};
+      int k = 0;
+      for (int j = 0; j < nv; ++j) {
+        if (!col[j].pair) continue;
+        fill(c, k, j);
+        c.stp[k] = col[j].stp;
+        c.s_out[k] = w.S + ((size_t)j * M + col[j].pair_slot) * n;
+        c.y_out[k] = w.Y + ((size_t)j * M + col[j].pair_slot) * n;
+        col[j].pair = false;
+        ++k;
+      }
+      if (k) {
+        hipLaunchKernelGGL(fos::lbfgs_store_pair_multi_kernel, dim3(ax_grid, k), dim3(256), 0, st, c, n);
+        LAUNCH_CHECK();
+      }
+    }
+    // new directions d = -H g, then the first trial point of each (fused into the combine step where it is the unit step)
+    {
+      fos::LbMulti c{};
+      int idx[NV], k = 0;
+      bool first = false;
+      for (int j = 0; j < nv; ++j) {
+        if (!col[j].need_dir) continue;
+        fill(c, k, j);
+        first = first || col[j].nit == 0;
+        idx[k++] = j;
+      }
+      if (k) {
+        if (n >= 2048) {
+          const int parts = vl_parts(n);
+          hipLaunchKernelGGL(fos::lbfgs_gram_multi_kernel, dim3(parts, k), dim3(fos::VL_THREADS), 0, st, c, M, n);
+          hipLaunchKernelGGL(fos::lbfgs_combine_multi_kernel, dim3((unsigned)((n + fos::VL_THREADS - 1) / fos::VL_THREADS), k),
+                             dim3(fos::VL_THREADS), 0, st, c, M, n, parts);
+        } else if (n % 4 == 0) {
+          hipLaunchKernelGGL(fos::lbfgs_two_loop_multi_kernel<1>, dim3(1, k), dim3(fos::LB_THREADS), 0, st, c, M, n);
+        } else {
+          hipLaunchKernelGGL(fos::lbfgs_two_loop_multi_kernel<0>, dim3(1, k), dim3(fos::LB_THREADS), 0, st, c, M, n);
+        }
+        LAUNCH_CHECK();
+        if (first) HIP_TRY(hipStreamSynchronize(st));           // the first step is 1/||d|| (read back once per fit)
+        fos::LbMulti t{};
+        int kt = 0;
+        for (int y = 0; y < k; ++y) {
+          const int j = idx[y];
+          Col& cj = col[j];
+          cj.stp = 1.0;
+          if (cj.nit == 0) {
+            if (hs(j)[6] >= 0.0) { finish(j, 3); continue; }      // not a descent direction and no memory to drop
+            cj.stp = std::min(1.0 / std::sqrt(hs(j)[7]), 1e10);
+          }
+          if (!c.fuse[y]) {
+            fill(t, kt, j);
+            ++kt;
+          }
+          cj.gi ^= 1;                         // g_old holds the gradient at x_old; g receives the trial gradients
+          cj.stage = 1;
+          cj.need_dir = false;
+        }
+        if (kt) {
+          hipLaunchKernelGGL(fos::lbfgs_first_trial_multi_kernel, dim3(ax_grid, kt), dim3(256), 0, st, t, n);
+          LAUNCH_CHECK();
+        }
+      }
+    }
+    // line-search trials: x = x_old + stp*d
+    {
+      fos::LbMulti c{};
+      int k = 0;
+      for (int j = 0; j < nv; ++j) {
+        if (!col[j].step) continue;
+        fill(c, k++, j);
+        col[j].step = false;
+      }
+      if (k) {
+        hipLaunchKernelGGL(fos::lbfgs_step_multi_kernel, dim3(ax_grid, k), dim3(256), 0, st, c, n);
+        LAUNCH_CHECK();
+      }
+    }
+    bool any = false;
+    for (int j = 0; j < nv; ++j) any = any || col[j].stage != 3;
+    if (!any) break;
+    if ((rc = round())) return rc;
+    for (int j = 0; j < nv; ++j) {
+      Col& c = col[j];
+      if (c.stage == 1) {
+        c.gd0 = hs(j)[6];
+        c.f_old = c.f; c.gmax_old = c.gmax;
+        if (c.gd0 >= 0.0) {                   // not a descent direction: the speculative evaluation never happened
+          if ((rc = restore(j))) return rc;
+          drop_memory(j);
+          continue;
+        }
+        c.stp = fos_ls_begin_impl(&c.ls, c.stp, c.f_old, c.gd0);
+        c.evals = 0;
+        c.gd1 = c.gd0;
+        c.stp_used = c.stp;
+        if ((rc = line_search(j))) return rc;
+      } else if (c.stage == 2) {
+        if ((rc = line_search(j))) return rc;
+      }
+    }
+  }
+  if (rounds) *rounds = nround;
+  return FOS_OK;
+}
+
 int fos_vec_stats(const float* x, const float* g, const float* d, int64_t n, double* out5, void* stream) {
   if (!out5 || n <= 0) return fail(FOS_ERR_ARG, "fos_vec_stats: bad argument");
   hipLaunchKernelGGL(fos::vec_stats_kernel<float>, dim3(1), dim3(fos::LB_THREADS), 0, (hipStream_t)stream, x, g, d, n,

@@ -722,6 +722,98 @@ int stage_b16(fos_problem* p, const float* B, int64_t ldb, int nv) {
 // columns run the chunk-per-lane pass (p->tall) and keep them; n <= 64 may be ragged / misaligned and does not.
 bool batch_supported(const fos_problem* p) { return p->path == 0 && (!p->tall || p->n > fos::TL_MAX_N); }   // fp32: f32 MFMA; bf16: 3-term bf16 MFMA
 
+// ---- fp64 multi-point pass on the matrix cores (gram_batch_dd.hpp) ---------------------------------------------------
+// The shapes of the fp32 matrix-core pair (run_multi_mfma): the aligned layout, fp32 and bf16, up to 16384 columns, any
+// number of row panels; not the two-pass / LDS-resident / n <= 64 plans, column blocks, the y-in-LDS rows or sharding.
+bool pair_dd_multi_supported(const fos_problem* p) {
+  return batch_supported(p) && !p->colblock && !p->resident && !p->col_sharded && !p->comm && p->entry != wide_entry(p->dtype) &&
+         p->n <= 16384;
+}
+
+// Geometry and workspace, decided on first use.  Panel and row splits of product 2 as in run_multi_mfma; product 1 gives a
+// workgroup groups of 64 rows, at most two workgroups per CU (51 KiB of LDS each for fp32).
+constexpr int DM_P1_PER_CU = 2;
+int ensure_dd_multi(fos_problem* p) {
+  if (p->xd && p->rdd && p->slabs_dd16 && p->qdd_part) return FOS_OK;
+  const int64_t n = p->n;
+  p->dm_n_pad = (n + fos::DM_COLS - 1) / fos::DM_COLS * fos::DM_COLS;
+  p->dm_panel_rows = std::min<int64_t>(256 * (int64_t)p->ncu, (p->m + 255) / 256 * 256);
+  const int64_t strips = (n + fos::DM_COLS - 1) / fos::DM_COLS;
+  int64_t splits = std::max<int64_t>(1, (2 * (int64_t)p->ncu + strips - 1) / strips);
+  splits = std::min<int64_t>(splits, std::max<int64_t>(1, p->dm_panel_rows / 256));
+  p->dm_rows_per_split = ((p->dm_panel_rows + splits - 1) / splits + fos::DM_ROWS - 1) / fos::DM_ROWS * fos::DM_ROWS;
+  p->dm_splits = (int)((p->dm_panel_rows + p->dm_rows_per_split - 1) / p->dm_rows_per_split);
+  const int64_t panels = (p->m + p->dm_panel_rows - 1) / p->dm_panel_rows;
+  if (!p->xd) HIP_TRY(hipMalloc(&p->xd, (size_t)p->dm_n_pad * fos::BT_NV * sizeof(double)));
+  if (!p->rdd) HIP_TRY(hipMalloc(&p->rdd, (size_t)p->dm_panel_rows * fos::BT_NV * sizeof(double)));
+  if (!p->slabs_dd16) HIP_TRY(hipMalloc(&p->slabs_dd16, (size_t)p->dm_splits * fos::BT_NV * n * sizeof(double)));
+  if (!p->qdd_part)
+    HIP_TRY(hipMalloc(&p->qdd_part, (size_t)panels * DM_P1_PER_CU * p->ncu * fos::BT_NV * sizeof(double)));
+  return FOS_OK;
+}
+
+// Per panel: product 1 (R = A_panel X - B16_panel and its squared column norms), product 2 (slabs (+)= R^T A_panel), each
+// bracketed by the launch profiler; then one launch sums the slab sets into the gradients and folds ||r||^2.
+template <typename T>
+int run_pair_dd_multi(fos_problem* p, const fos::DdMultiCols& c, int ncols, unsigned live, double alpha2, const float* b16) {
+  const int64_t n = p->n, esz = sizeof(T);
+  hipLaunchKernelGGL(fos::xd_pack_kernel, dim3(grid_1d(p->dm_n_pad * fos::BT_NV, 256, 4 * p->ncu)), dim3(256), 0, p->stream, c,
+                     live, (int)n, (int)p->dm_n_pad, p->xd);
+  LAUNCH_CHECK();
+  const int64_t strips = (n + fos::DM_COLS - 1) / fos::DM_COLS;
+  int64_t nparts = 0;
+  int rc;
+  for (int64_t row0 = 0, panel = 0; row0 < p->m; row0 += p->dm_panel_rows, ++panel) {
+    const int64_t rows = std::min<int64_t>(p->dm_panel_rows, p->m - row0);
+    const T* Ap = reinterpret_cast<const T*>(reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz);
+    const int64_t ngroups = (rows + fos::DM_ROWS - 1) / fos::DM_ROWS;
+    int64_t nwg = std::min<int64_t>(ngroups, DM_P1_PER_CU * (int64_t)p->ncu);
+    const int64_t gpw = (ngroups + nwg - 1) / nwg;
+    nwg = (ngroups + gpw - 1) / gpw;
+    if ((rc = prof_mark(p, true))) return rc;
+    hipLaunchKernelGGL(fos::residual_dd_mfma_kernel<T>, dim3((unsigned)nwg), dim3(fos::DM_THREADS), 0, p->stream, Ap, p->lda,
+                       b16 + row0 * fos::BT_NV, rows, (int)n, (const double*)p->xd, gpw, p->qdd_part + nparts * fos::BT_NV,
+                       p->rdd);
+    LAUNCH_CHECK();
+    if ((rc = prof_mark(p, false))) return rc;
+    nparts += nwg;
+    const dim3 grid((unsigned)strips, (unsigned)p->dm_splits);
+    if ((rc = prof_mark(p, true))) return rc;
+    if (panel)
+      hipLaunchKernelGGL((fos::gram_dd_mfma_kernel<T, true>), grid, dim3(fos::DM_THREADS), 0, p->stream, Ap, p->lda, rows,
+                         (int)n, (const double*)p->rdd, p->dm_rows_per_split, p->slabs_dd16, n);
+    else
+      hipLaunchKernelGGL((fos::gram_dd_mfma_kernel<T, false>), grid, dim3(fos::DM_THREADS), 0, p->stream, Ap, p->lda, rows,
+                         (int)n, (const double*)p->rdd, p->dm_rows_per_split, p->slabs_dd16, n);
+    LAUNCH_CHECK();
+    if ((rc = prof_mark(p, false))) return rc;
+  }
+  hipLaunchKernelGGL(fos::pair_dd_multi_finish_kernel, dim3(grid_1d(n, 256, 64), ncols), dim3(256), 0, p->stream,
+                     (const double*)p->slabs_dd16, p->dm_splits, (int)n, (const double*)p->qdd_part, (int)nparts, alpha2, c);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
+// The dispatch of the fp64 multi-point pass: one entry per storage type (a table of its own, apart from the streaming menus)
+typedef int (*PairDdMultiRun)(fos_problem*, const fos::DdMultiCols&, int, unsigned, double, const float*);
+struct PairDdMultiEntry { int dtype; PairDdMultiRun run; };
+const PairDdMultiEntry kPairDdMulti[] = {
+    {FOS_F32, run_pair_dd_multi<float>},
+    {FOS_BF16, run_pair_dd_multi<fos::bf16_t>},
+};
+
+int pair_dd_multi(fos_problem* p, const fos::DdMultiCols& c, int ncols, unsigned live, double alpha2, const float* b16) {
+  if (!pair_dd_multi_supported(p))
+    return fail(FOS_ERR_UNSUPPORTED, "fos_gemv_pair_dd_multi: no matrix-core pair for this shape (needs the aligned streaming "
+                                     "layout, 65..16384 columns, unsharded)");
+  if (ncols < 1) return FOS_OK;
+  int rc = ensure_dd_multi(p);
+  if (rc) return rc;
+  for (const auto& e : kPairDdMulti)
+    if (e.dtype == p->dtype) return e.run(p, c, ncols, live, alpha2, b16);
+  return fail(FOS_ERR_UNSUPPORTED, "fos_gemv_pair_dd_multi: storage type not served");
+}
+
 // A caller vector the fused prologue can read with 16-byte loads.
 int aligned_vec(fos_problem* p, const float* v, const float** out) {
   if ((reinterpret_cast<uintptr_t>(v) & 15u) == 0) {
@@ -1102,10 +1194,11 @@ int fos_problem_destroy(fos_problem* p) {
   for (hipEvent_t e : p->ev_pool) (void)hipEventDestroy(e);
   void* bufs[] = {p->slabs, p->rr_part, p->rr2_part, p->rvec, p->gbuf_own, p->ybuf, p->dscal, p->part, p->xp, p->q_part, p->bt_out,
                   p->slabs_dd, p->rr_dd, p->lhist, p->rbuf16, p->rcols16, p->b16, p->mfold, p->cr_part, p->cr_bar, p->slabs16, p->rneg, p->zeros, p->cp_xchg, p->cp_flags, p->fz_bar, p->fz_part, p->fz_beta,
-                  p->cp_error};
+                  p->cp_error, p->xd, p->rdd, p->slabs_dd16, p->qdd_part};
   for (void* q : bufs)
     if (q) (void)hipFree(q);
   delete p->lbfgs;
+  delete p->lbfgs_multi;
   delete p;
   return FOS_OK;
 }
@@ -1393,6 +1486,24 @@ int fos_residual_batch_rhs(fos_problem* p, const float* X, int nv, const float* 
                        (int)p->n_pad, nv, p->xp);
   LAUNCH_CHECK();
   return launch_residual_batch(p, 1, out16, nullptr, p->b16);
+}
+
+int fos_gemv_pair_dd_multi(fos_problem* p, const double* X, int nv, int64_t ldx, const float* B, int64_t ldb, double alpha2,
+                           double* G, double* rr) {
+  if (!p || !X || !B || !G || !rr || nv < 1 || nv > fos::BT_NV || ldb < nv || ldx < 1)
+    return fail(FOS_ERR_ARG, "fos_gemv_pair_dd_multi: bad argument (null pointer, nv outside 1..16, ldb < nv or ldx < n)");
+  if (ldx < p->n) return fail(FOS_ERR_ARG, "fos_gemv_pair_dd_multi: bad argument (ldx < n)");
+  if (!pair_dd_multi_supported(p)) return pair_dd_multi(p, fos::DdMultiCols{}, 0, 0u, alpha2, nullptr);
+  fos::DdMultiCols c{};
+  for (int j = 0; j < nv; ++j) {
+    c.x[j] = X + (size_t)j * ldx;
+    c.g[j] = G + (size_t)j * ldx;
+    c.rr[j] = rr + j;
+    c.col[j] = j;
+  }
+  int rc = stage_b16(p, B, ldb, nv);
+  if (rc) return rc;
+  return pair_dd_multi(p, c, nv, (1u << nv) - 1u, alpha2, p->b16);
 }
 
 int fos_power_iter(fos_problem* p, float* v_inout, int n_iter, double tol, double* L_out, int* iters_out) {

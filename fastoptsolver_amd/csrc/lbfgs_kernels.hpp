@@ -83,11 +83,9 @@ __device__ inline void loadv(const double* p, double (&o)[4]) {
 // of the history behind it: the pair of step k+1 is requested before the reduction of step k and lands while the
 // workgroup sums (one load latency in total instead of one per step).
 template <typename VT, int NQ>
-__global__ __launch_bounds__(LB_THREADS) void lbfgs_two_loop_kernel(const VT* __restrict__ g,
-                                                                    const VT* __restrict__ S,
-                                                                    const VT* __restrict__ Y, int hist, int head,
-                                                                    int cap, int64_t n, VT* __restrict__ qout,
-                                                                    double* __restrict__ gd_out = nullptr) {
+__device__ __forceinline__ void lbfgs_two_loop_body(const VT* __restrict__ g, const VT* __restrict__ S,
+                                                    const VT* __restrict__ Y, int hist, int head, int cap, int64_t n,
+                                                    VT* __restrict__ qout, double* __restrict__ gd_out) {
   __shared__ double lds[3][LB_THREADS / 64];
   __shared__ double coef[LB_MAXHIST];
   __shared__ double rho[LB_MAXHIST];
@@ -263,6 +261,15 @@ __global__ __launch_bounds__(LB_THREADS) void lbfgs_two_loop_kernel(const VT* __
   }
 }
 
+template <typename VT, int NQ>
+__global__ __launch_bounds__(LB_THREADS) void lbfgs_two_loop_kernel(const VT* __restrict__ g,
+                                                                    const VT* __restrict__ S,
+                                                                    const VT* __restrict__ Y, int hist, int head,
+                                                                    int cap, int64_t n, VT* __restrict__ qout,
+                                                                    double* __restrict__ gd_out = nullptr) {
+  lbfgs_two_loop_body<VT, NQ>(g, S, Y, hist, head, cap, n, qout, gd_out);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // The same direction on MANY compute units (fos_lbfgs_direction_dd).  The two-loop chain above is 2*hist dependent
 // dot -> axpy steps, which only one workgroup can run: its time is (4*hist + 2) n-vectors through ONE CU's L2 port
@@ -298,9 +305,9 @@ __device__ inline int vl_index(int i, int j, int nb) {          // i <= j
   return i * nb - i * (i - 1) / 2 + (j - i);
 }
 
-static __global__ __launch_bounds__(VL_THREADS) void lbfgs_gram_kernel(const double* __restrict__ g, const double* __restrict__ S,
-                                                                const double* __restrict__ Y, int hist, int head, int cap,
-                                                                int64_t n, double* __restrict__ partial) {
+__device__ __forceinline__ void lbfgs_gram_body(const double* __restrict__ g, const double* __restrict__ S,
+                                                const double* __restrict__ Y, int hist, int head, int cap, int64_t n,
+                                                double* __restrict__ partial, int bx, int gx) {
   __shared__ double L[VL_NB][VL_COLS + 1];
   const int nb = 2 * hist + 1, tid = threadIdx.x;
   const int npairs = nb * (nb + 1) / 2;
@@ -310,7 +317,7 @@ static __global__ __launch_bounds__(VL_THREADS) void lbfgs_gram_kernel(const dou
   const int64_t nchunks = (n + VL_COLS - 1) / VL_COLS;
   constexpr int RPT = (VL_NB + 1) / 2;               // rows per thread: 128 columns x 2 row phases = 256 threads
   const int c = tid % VL_COLS, r0 = tid / VL_COLS;
-  for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {     // at most VL_MAXPARTS workgroups
+  for (int64_t chunk = bx; chunk < nchunks; chunk += gx) {                    // at most VL_MAXPARTS workgroups
     const int64_t col = chunk * VL_COLS + c;
     const bool in = col < n;
     double v[RPT];
@@ -331,15 +338,20 @@ static __global__ __launch_bounds__(VL_THREADS) void lbfgs_gram_kernel(const dou
       for (int cc = 0; cc < VL_COLS; ++cc) acc += L[i][cc] * L[j][cc];
     }
   }
-  if (tid < npairs) partial[(int64_t)blockIdx.x * VL_PSTRIDE + tid] = acc;
+  if (tid < npairs) partial[(int64_t)bx * VL_PSTRIDE + tid] = acc;
 }
 
-static __global__ __launch_bounds__(VL_THREADS) void lbfgs_combine_kernel(const double* __restrict__ g, const double* __restrict__ S,
-                                                                   const double* __restrict__ Y, int hist, int head, int cap,
-                                                                   int64_t n, const double* __restrict__ partial, int nparts,
-                                                                   double* __restrict__ d_out, double* __restrict__ gd_out,
-                                                                   double* __restrict__ x_step = nullptr,
-                                                                   double* __restrict__ x_old = nullptr) {
+static __global__ __launch_bounds__(VL_THREADS) void lbfgs_gram_kernel(const double* __restrict__ g, const double* __restrict__ S,
+                                                                const double* __restrict__ Y, int hist, int head, int cap,
+                                                                int64_t n, double* __restrict__ partial) {
+  lbfgs_gram_body(g, S, Y, hist, head, cap, n, partial, blockIdx.x, gridDim.x);
+}
+
+__device__ __forceinline__ void lbfgs_combine_body(const double* __restrict__ g, const double* __restrict__ S,
+                                                   const double* __restrict__ Y, int hist, int head, int cap, int64_t n,
+                                                   const double* __restrict__ partial, int nparts, double* __restrict__ d_out,
+                                                   double* __restrict__ gd_out, double* __restrict__ x_step,
+                                                   double* __restrict__ x_old, int bx) {
   // x_step (fos_lbfgs_minimize, every iteration but the first): the first trial point of the line search rides along -
   // x_old = x, x = 1.0*d + x (L-BFGS-B's unit first step, products and sum rounded as lbfgs_first_trial_kernel does)
   __shared__ double G[VL_NB][VL_NB + 1];
@@ -347,7 +359,7 @@ static __global__ __launch_bounds__(VL_THREADS) void lbfgs_combine_kernel(const 
   const int nb = 2 * hist + 1, tid = threadIdx.x;
   const int npairs = nb * (nb + 1) / 2;
   // this thread's column: the 2h+1 basis values are requested first and land while the coefficients are worked out
-  const int64_t col = (int64_t)blockIdx.x * VL_THREADS + tid;
+  const int64_t col = (int64_t)bx * VL_THREADS + tid;
   double bv[VL_NB];
 #pragma unroll
   for (int r = 0; r < VL_NB; ++r)
@@ -389,7 +401,7 @@ static __global__ __launch_bounds__(VL_THREADS) void lbfgs_combine_kernel(const 
       if (j == i) delta += a_mine - beta;                                    // q += s_i (a_i - beta)
     }
     if (on) delta_s[j] = delta;
-    if (blockIdx.x == 0 && gd_out != nullptr) {
+    if (bx == 0 && gd_out != nullptr) {
       // d = -q:  g.d = -sum_j delta_j G[g][j],  d.d = sum_ij delta_i delta_j G[i][j]
       const double gq = wave_sum_dpp(on ? delta * G[2 * hist][j] : 0.0);
       double row = 0.0;
@@ -413,20 +425,23 @@ static __global__ __launch_bounds__(VL_THREADS) void lbfgs_combine_kernel(const 
   }
 }
 
+static __global__ __launch_bounds__(VL_THREADS) void lbfgs_combine_kernel(const double* __restrict__ g, const double* __restrict__ S,
+                                                                   const double* __restrict__ Y, int hist, int head, int cap,
+                                                                   int64_t n, const double* __restrict__ partial, int nparts,
+                                                                   double* __restrict__ d_out, double* __restrict__ gd_out,
+                                                                   double* __restrict__ x_step = nullptr,
+                                                                   double* __restrict__ x_old = nullptr) {
+  lbfgs_combine_body(g, S, Y, hist, head, cap, n, partial, nparts, d_out, gd_out, x_step, x_old, blockIdx.x);
+}
+
 // out5 = { x.x, g.d, d.d, max|g|, ||x||_1 }; any pointer may be NULL (its entries are then 0).  XT: float or double
 // iterate.  With `extra` the scalar *extra rides along as out5[5] (the ||r||^2 of the evaluation: one host read for all).
-template <typename XT, typename GT = float>
-__global__ __launch_bounds__(LB_THREADS) void vec_stats_kernel(const XT* __restrict__ x, const GT* __restrict__ g,
-                                                               const GT* __restrict__ d, int64_t n,
-                                                               double* __restrict__ out5,
-                                                               const double* __restrict__ extra = nullptr,
-                                                               unsigned long long* flag = nullptr,
-                                                               unsigned long long seq = 0,
-                                                               const unsigned long long* t_start = nullptr) {
+// The sums of vec_stats_kernel; thread 0 writes out5 (and out5[5] = *extra, out5[9] = t_now - *t_start when given).
+template <typename XT, typename GT>
+__device__ __forceinline__ void vec_stats_body(const XT* __restrict__ x, const GT* __restrict__ g, const GT* __restrict__ d,
+                                               int64_t n, double* __restrict__ out5, const double* __restrict__ extra,
+                                               const unsigned long long* t_start, unsigned long long t_now) {
   __shared__ double lds[5][16];
-  // t_start (fos_lbfgs_minimize): the constant-rate wall clock read by stamp_kernel in front of the evaluation; this
-  // kernel runs right behind it, so (now - *t_start) is the evaluation's device time - out5[9], no hipEvent on the stream
-  const unsigned long long t_now = t_start != nullptr ? wall_clock64() : 0ull;
   double xx = 0.0, gd = 0.0, dd = 0.0, gm = 0.0, x1 = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += LB_THREADS) {
     const double xv = x ? (double)x[i] : 0.0, gv = g ? (double)g[i] : 0.0, dv = d ? (double)d[i] : 0.0;
@@ -448,10 +463,24 @@ __global__ __launch_bounds__(LB_THREADS) void vec_stats_kernel(const XT* __restr
     out5[0] = a; out5[1] = b; out5[2] = c; out5[3] = e; out5[4] = f;
     if (extra != nullptr) out5[5] = *extra;
     if (t_start != nullptr) out5[9] = (double)(t_now - *t_start);
-    if (flag != nullptr) {                  // out5 in pinned host memory: the host polls `flag` instead of draining the stream
-      __threadfence_system();
-      __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+  }
+}
+
+template <typename XT, typename GT = float>
+__global__ __launch_bounds__(LB_THREADS) void vec_stats_kernel(const XT* __restrict__ x, const GT* __restrict__ g,
+                                                               const GT* __restrict__ d, int64_t n,
+                                                               double* __restrict__ out5,
+                                                               const double* __restrict__ extra = nullptr,
+                                                               unsigned long long* flag = nullptr,
+                                                               unsigned long long seq = 0,
+                                                               const unsigned long long* t_start = nullptr) {
+  // t_start (fos_lbfgs_minimize): the constant-rate wall clock read by stamp_kernel in front of the evaluation; this
+  // kernel runs right behind it, so (now - *t_start) is the evaluation's device time - out5[9], no hipEvent on the stream
+  const unsigned long long t_now = t_start != nullptr ? wall_clock64() : 0ull;
+  vec_stats_body<XT, GT>(x, g, d, n, out5, extra, t_start, t_now);
+  if (threadIdx.x == 0 && flag != nullptr) {   // out5 in pinned host memory: the host polls `flag` instead of draining the stream
+    __threadfence_system();
+    __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -531,6 +560,108 @@ static __global__ __launch_bounds__(256) void lbfgs_store_pair_kernel(double stp
     if (s_out != nullptr) {
       s_out[i] = __dmul_rn(stp, d[i]);
       y_out[i] = __dadd_rn(g[i], -g_old[i]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Several fits in lockstep (fos_lbfgs_minimize_multi): every kernel below serves all unfinished columns in ONE launch,
+// blockIdx.y = the entry of LbMulti it works on, and runs for it the body / arithmetic of its single-target kernel above.
+// Per-column state is column-contiguous ([column][n]); the pointers are the column's own.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int LM_MAXV = 16;
+struct LbMulti {
+  const double* g[LM_MAXV];          // gradient at the current point
+  const double* g_old[LM_MAXV];      // gradient at the previous iterate (store_pair)
+  const double* S[LM_MAXV];          // history base ([cap][n]) of the column
+  const double* Y[LM_MAXV];
+  double* x[LM_MAXV];
+  double* x_old[LM_MAXV];
+  double* d[LM_MAXV];
+  double* s_out[LM_MAXV];            // store_pair: slot of the new pair (nullptr: curvature test failed, keep none)
+  double* y_out[LM_MAXV];
+  double* out[LM_MAXV];              // the column's 16 host slots: [0..4] stats, [5] ||r||^2, [6] g.d, [7] d.d, [9] time
+  double* work[LM_MAXV];             // whole-chip direction: partial Gram matrices
+  const double* rr[LM_MAXV];         // ||r||^2 of the column's last evaluation
+  double stp[LM_MAXV];
+  int hist[LM_MAXV], head[LM_MAXV];
+  int fuse[LM_MAXV];                 // combine: also take the unit first step (x_old = x, x += d)
+};
+
+template <int NQ>
+__global__ __launch_bounds__(LB_THREADS) void lbfgs_two_loop_multi_kernel(LbMulti c, int cap, int64_t n) {
+  const int v = blockIdx.y;
+  lbfgs_two_loop_body<double, NQ>(c.g[v], c.S[v], c.Y[v], c.hist[v], c.head[v], cap, n, c.d[v], c.out[v] + 6);
+}
+
+static __global__ __launch_bounds__(VL_THREADS) void lbfgs_gram_multi_kernel(LbMulti c, int cap, int64_t n) {
+  const int v = blockIdx.y;
+  lbfgs_gram_body(c.g[v], c.S[v], c.Y[v], c.hist[v], c.head[v], cap, n, c.work[v], blockIdx.x, gridDim.x);
+}
+
+static __global__ __launch_bounds__(VL_THREADS) void lbfgs_combine_multi_kernel(LbMulti c, int cap, int64_t n, int nparts) {
+  const int v = blockIdx.y;
+  lbfgs_combine_body(c.g[v], c.S[v], c.Y[v], c.hist[v], c.head[v], cap, n, c.work[v], nparts, c.d[v], c.out[v] + 6,
+                     c.fuse[v] ? c.x[v] : nullptr, c.fuse[v] ? c.x_old[v] : nullptr, blockIdx.x);
+}
+
+// lbfgs_first_trial_kernel per column: x_old = x, x = stp*d + x_old
+static __global__ __launch_bounds__(256) void lbfgs_first_trial_multi_kernel(LbMulti c, int64_t n) {
+  const int v = blockIdx.y;
+  double* __restrict__ x = c.x[v];
+  double* __restrict__ x_old = c.x_old[v];
+  const double* __restrict__ d = c.d[v];
+  const double stp = c.stp[v];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const double xo = x[i];
+    x_old[i] = xo;
+    x[i] = __dadd_rn(__dmul_rn(stp, d[i]), xo);
+  }
+}
+
+// vec_axpby_f64_kernel per column: x = 1.0*x_old + stp*d, products and sum rounded separately (NumPy's stp * d + x_old)
+static __global__ __launch_bounds__(256) void lbfgs_step_multi_kernel(LbMulti c, int64_t n) {
+  const int v = blockIdx.y;
+  double* __restrict__ x = c.x[v];
+  const double* __restrict__ x_old = c.x_old[v];
+  const double* __restrict__ d = c.d[v];
+  const double stp = c.stp[v];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    double w = __dmul_rn(1.0, x_old[i]);
+    w = __dadd_rn(__dmul_rn(stp, d[i]), w);
+    x[i] = w;
+  }
+}
+
+// lbfgs_store_pair_kernel per column: s = stp * d, y = g - g_old
+static __global__ __launch_bounds__(256) void lbfgs_store_pair_multi_kernel(LbMulti c, int64_t n) {
+  const int v = blockIdx.y;
+  const double* __restrict__ d = c.d[v];
+  const double* __restrict__ g = c.g[v];
+  const double* __restrict__ g_old = c.g_old[v];
+  double* __restrict__ s_out = c.s_out[v];
+  double* __restrict__ y_out = c.y_out[v];
+  const double stp = c.stp[v];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    s_out[i] = __dmul_rn(stp, d[i]);
+    y_out[i] = __dadd_rn(g[i], -g_old[i]);
+  }
+}
+
+// vec_stats_kernel per column into its host slots; the last workgroup to finish raises the round's sequence number
+// (every workgroup fences its slots system-wide before it counts itself in).
+static __global__ __launch_bounds__(LB_THREADS) void vec_stats_multi_kernel(LbMulti c, int64_t n, unsigned* __restrict__ count,
+                                                                       unsigned long long* flag, unsigned long long seq,
+                                                                       const unsigned long long* t_start) {
+  const int v = blockIdx.y;
+  const unsigned long long t_now = t_start != nullptr ? wall_clock64() : 0ull;
+  vec_stats_body<double, double>(c.x[v], c.g[v], c.d[v], n, c.out[v], c.rr[v], t_start, t_now);
+  if (threadIdx.x == 0) {
+    __threadfence_system();
+    if (atomicAdd(count, 1u) == gridDim.y - 1) {
+      *count = 0u;
+      __threadfence_system();
+      __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
 }

@@ -19,7 +19,7 @@ import torch.distributed as dist
 
 from . import _core, _lib
 from ._linesearch import LineSearch
-from .iterative_solvers import _EventTimer, grad_call_times, reset_metrics
+from .iterative_solvers import _EventTimer, _metrics_apart, _targets, grad_call_times, reset_metrics
 
 _M, _FACTR, _MAXLS = 10, 1e7, 20
 _EPS = float(np.finfo(np.float64).eps)
@@ -183,6 +183,70 @@ class LBFGSSolver:
         self.iterates_ = list(ops.to_caller(iterates[: self.nit_])) if keep and self.nit_ else []
         self.x_ = ops.to_caller(x)                                                    # lbfgs.py:71
         self.final_obj_ = float(res.f)                                                # lbfgs.py:72
+        self._x_dev = x
+        return self
+
+    _LOCKSTEP_MIN, _GROUP = 3, 16         # fos_fista_run_multi's convention: the shared pass pays from three columns on
+
+    def _fit_targets(self, A, B):
+        """X[:, j] = fit(A, B[:, j]) for every column j, with A bound once.  Groups of up to 16 columns run in lockstep
+        (fos_lbfgs_minimize_multi: one fp64 multi-point pass per round serves every unfinished fit); a group of two, a lone
+        last column and shapes without the multi-point pass run column by column on sibling problems that borrow the same
+        device A."""
+        import ctypes as C
+        prob = _core.prepare(A, None)
+        lib = _lib.load()
+        Bt = B.detach() if _core.is_tensor(B) else torch.from_numpy(np.ascontiguousarray(np.asarray(B)))
+        Bt = Bt.to(device=prob.device, dtype=torch.float32)
+        if Bt.shape[0] != prob.m:
+            raise ValueError("b must have m rows")
+        k, n = int(Bt.shape[1]), prob.n_dev
+        a2 = float(self.alpha2) if self.reg_type in ("ridge", "elasticnet") else 0.0   # lbfgs.py:49-51
+        max_iter = int(self.max_iter)
+        l1 = self.reg_type in ("lasso", "elasticnet")
+        X = torch.zeros(k, n, dtype=torch.float64, device=prob.device)        # row j: the iterate of column j
+        nit, nfev = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int64)
+        task, fobj, hist_out = [None] * k, np.zeros(k, dtype=np.float64), [[] for _ in range(k)]
+
+        def one(j):
+            solo = LBFGSSolver.__new__(LBFGSSolver)
+            solo.reg_type, solo.alpha1, solo.alpha2 = self.reg_type, self.alpha1, self.alpha2
+            solo.max_iter, solo.tol, solo.history_ = self.max_iter, self.tol, []
+            _metrics_apart(lambda: solo._fit_native(_HipOps(prob.sibling(Bt[:, j].contiguous()), None)))
+            X[j] = solo._x_dev
+            nit[j], nfev[j], task[j], fobj[j], hist_out[j] = solo.nit_, solo.nfev_, solo.task_, solo.final_obj_, solo.history_
+
+        for g0 in range(0, k, self._GROUP):
+            g1 = min(k, g0 + self._GROUP)
+            nv = g1 - g0
+            if nv >= self._LOCKSTEP_MIN:
+                Bg = Bt[:, g0:g1].contiguous()
+                hstride = 2 * max_iter
+                hist = (C.c_double * max(nv * hstride, 1))()
+                cap = 22 * max_iter + 64
+                round_ms = (C.c_float * cap)()
+                rounds = C.c_int(0)
+                res = (_lib.LbfgsResult * nv)()
+                with prob.ctx():
+                    rc = lib.fos_lbfgs_minimize_multi(prob.h, nv, _core.ptr(Bg), nv, a2, max_iter, float(self.tol),
+                                                      _core.ptr(X[g0:g1]), n, hist, round_ms, cap, C.byref(rounds), res)
+                if rc == 0:
+                    r = int(rounds.value)
+                    times = [float(round_ms[i]) * 1e-3 for i in range(min(r, cap))]
+                    grad_call_times.extend(times + [times[-1] if times else 0.0] * (r - len(times)))   # one per round
+                    for v, j in enumerate(range(g0, g1)):
+                        nit[j], nfev[j], task[j], fobj[j] = res[v].nit, res[v].nfev, self._TASKS[res[v].task], res[v].f
+                        h0 = v * hstride
+                        hist_out[j] = [hist[h0 + 2 * i] + (self.alpha1 * hist[h0 + 2 * i + 1] if l1 else 0.0)
+                                       for i in range(nit[j])]
+                    continue
+                if rc != -4:                                  # anything but FOS_ERR_UNSUPPORTED is an error
+                    _lib.check(rc, "fos_lbfgs_minimize_multi")
+            for j in range(g0, g1):
+                one(j)
+        self.x_ = _core.from_device_vec(X[:, : prob.n].t().contiguous(), prob.like)
+        self.nit_, self.nfev_, self.task_, self.final_obj_, self.history_ = nit, nfev, task, fobj, hist_out
+        self.iterates_ = []
         return self
 
     def fit(self, A, b, *, group=None, comm=None, ops=None, cols=None):
@@ -191,7 +255,19 @@ class LBFGSSolver:
         identical numbers, so x stays replicated bit for bit.  ``comm`` (a `distributed.Comm`): the all-reduce runs
         under the C ABI on the kernels' stream (inside fos_gemv_pair_dd); ``group`` (a torch.distributed group, any
         backend): it runs here, between the kernels.  ``ops``: the vector/pass primitives (default: the HIP kernels;
-        the gloo CPU test injects a stand-in)."""
+        the gloo CPU test injects a stand-in).
+
+        Several targets: a 2-D ``b`` of shape (m, k), k >= 2 (the rule of ``fista(A, B)``), fits every column on one bound A
+        and gives ``x_`` of shape (n, k) in the caller's type, ``nit_`` / ``nfev_`` (int arrays), ``task_`` (k strings),
+        ``final_obj_`` (float64 array), ``history_`` (k lists) and ``iterates_ = []``.  Groups of 3..16 columns advance in
+        lockstep, one fp64 pass over A per round for all of them; ``get_metrics()`` counts one gradient call per round.
+        Not combinable with ``group=``, ``comm=``, ``cols=`` or ``ops=``."""
+        B = _targets(A, b)
+        if B is not None:
+            if group is not None or comm is not None or cols is not None or ops is not None:
+                raise ValueError("a 2-D b (several targets) cannot be combined with group= / comm= / cols= / ops=")
+            reset_metrics()
+            return self._fit_targets(A, B)
         reset_metrics()
         if cols is not None:
             # ``cols=(lo, hi, n_total)`` with ``comm=``: COLUMN sharding - A is this rank's columns of all rows, b the whole

@@ -442,6 +442,32 @@ typedef struct fos_lbfgs_result {
 int fos_lbfgs_minimize(fos_problem* p, double alpha2, int max_iter, double pgtol, double* x, double* hist,
                        double* iterates, float* fg_ms, int fg_cap, fos_lbfgs_result* res);
 
+/* fg of fos_gemv_pair_dd for up to 16 points at once, on the fp64 matrix cores, column j against its own target:
+ *   G[:, j] = A^T (A X[:, j] - B[:, j]) + alpha2 X[:, j],   rr[j] = ||A X[:, j] - B[:, j]||^2     (j < nv <= 16)
+ * every product and sum in fp64 (A widened exactly, X never rounded): fos_gemv_pair_dd's arithmetic per column, in another
+ * summation order.  X, G: device, n x nv doubles, column j at X + j*ldx (ldx >= n); B: device, m x nv floats, row-major
+ * (leading dimension ldb >= nv); rr: device, nv doubles.  Two products over row panels: R = A_panel X - B (A from HBM),
+ * G += R^T A_panel (the panel again).  Served on the shapes of the fp32 matrix-core pair (aligned layout, fp32 / bf16,
+ * 65..16384 columns, unsharded); FOS_ERR_UNSUPPORTED elsewhere.  Argument errors return FOS_ERR_ARG before any device
+ * work.  Enqueues only. */
+int fos_gemv_pair_dd_multi(fos_problem* p, const double* X, int nv, int64_t ldx, const float* B, int64_t ldb, double alpha2,
+                           double* G, double* rr);
+
+/* nv (2..16) fits of fos_lbfgs_minimize in lockstep on one problem, fit j against target column j of B (device, m x nv
+ * floats, row-major, ldb >= nv).  Every fit keeps its own memory, line search and exit, with the single-target rules; all
+ * unfinished fits take their next evaluation in ONE fos_gemv_pair_dd_multi pass (a round), so A is read about
+ * max_j nfev_j times instead of sum_j nfev_j.  One host round trip per round (plus one in the first iteration).
+ *   X         device, n x nv doubles, column j at X + j*ldx (ldx >= n): start points in, solutions out
+ *   hist      host, nv x 2*max_iter doubles (nullable): fit j's pairs (loss, ||x||_1) at hist + j*2*max_iter
+ *   round_ms  host, round_cap floats (nullable): device milliseconds of every round's pass
+ *   rounds    host (nullable): number of rounds (passes over A) of the call
+ *   res       host, nv results
+ * FOS_ERR_UNSUPPORTED on sharded problems and on shapes without the multi-point pass (nothing has run then).
+ * Synchronises. */
+int fos_lbfgs_minimize_multi(fos_problem* p, int nv, const float* B, int64_t ldb, double alpha2, int max_iter, double pgtol,
+                             double* X, int64_t ldx, double* hist, float* round_ms, int round_cap, int* rounds,
+                             fos_lbfgs_result* res);
+
 #ifdef __cplusplus
 }
 #endif
