@@ -215,45 +215,131 @@ static void host_momentum(const fos::FistaParams& prm, long long k, double* t, d
   }
 }
 
-static void launch_update_from_slabs(fos_fista* f, double* part, int host_beta, double beta_val,
-                                     double* x_hist = nullptr, float* y_next = nullptr, double beta_next = 0.0,
-                                     const float* slabs = nullptr, int64_t slab_stride = 0, int nslabs = 0,
-                                     int y_mode = fos::YOUT_VECTOR, int y_slot = 0) {
+// fista_update_kernel: the gradient from the slab sets (slabs != null) or from gsrc; vec4: float4 epilogues
+static int launch_update(fos_fista* f, const float* slabs, int nslabs, fos::GradSrc gsrc, const fos::FistaParams& prm,
+                         double* part, int host_beta, double beta_val, double* x_hist, float* y_next, double beta_next,
+                         int64_t slab_stride = 0, int y_mode = fos::YOUT_VECTOR, int y_slot = 0) {
   fos_problem* p = f->p;
-  if (slabs == nullptr) slabs = p->slabs;
-  if (slab_stride == 0) slab_stride = p->slab_stride;
-  if (nslabs == 0) nslabs = p->nslabs;
-  if (p->vec4)
-    hipLaunchKernelGGL((fos::fista_update_kernel<true, true>), dim3(f->nupd), dim3(256), 0, p->stream, slabs,
-                       nslabs, fos::GradSrc{nullptr, nullptr}, (int)p->n, f->x_cur, f->x_prev, f->scal, f->prm, part, host_beta,
-                       beta_val, x_hist, y_next, beta_next, slab_stride, y_mode, y_slot);
-  else
-    hipLaunchKernelGGL((fos::fista_update_kernel<true, false>), dim3(f->nupd), dim3(256), 0, p->stream, slabs,
-                       nslabs, fos::GradSrc{nullptr, nullptr}, (int)p->n, f->x_cur, f->x_prev, f->scal, f->prm, part, host_beta,
-                       beta_val, x_hist, y_next, beta_next, slab_stride, y_mode, y_slot);
+#define FOS_UPDATE(FROM_SLABS, VEC)                                                                                             \
+  hipLaunchKernelGGL((fos::fista_update_kernel<FROM_SLABS, VEC>), dim3(f->nupd), dim3(256), 0, p->stream, slabs, nslabs, gsrc,  \
+                     (int)p->n, f->x_cur, f->x_prev, f->scal, prm, part, host_beta, beta_val, x_hist, y_next, beta_next,       \
+                     slab_stride, y_mode, y_slot)
+  if (slabs) { if (p->vec4) FOS_UPDATE(true, true); else FOS_UPDATE(true, false); }
+  else { if (p->vec4) FOS_UPDATE(false, true); else FOS_UPDATE(false, false); }
+#undef FOS_UPDATE
+  LAUNCH_CHECK();
+  return FOS_OK;
 }
 
-// y source of a plain-run iteration: the fp32 vector the previous update kernel wrote, or (first iteration after a
-// reset / split-mode call) the fp64 state with the host's beta.  Both give bit-identical y.
+static int launch_update_from_slabs(fos_fista* f, double* part, int host_beta, double beta_val,
+                                    double* x_hist = nullptr, float* y_next = nullptr, double beta_next = 0.0,
+                                    const float* slabs = nullptr, int64_t slab_stride = 0, int nslabs = 0,
+                                    int y_mode = fos::YOUT_VECTOR, int y_slot = 0) {
+  fos_problem* p = f->p;
+  return launch_update(f, slabs ? slabs : p->slabs, nslabs ? nslabs : p->nslabs, fos::GradSrc{nullptr, nullptr}, f->prm, part,
+                       host_beta, beta_val, x_hist, y_next, beta_next, slab_stride ? slab_stride : p->slab_stride, y_mode, y_slot);
+}
+
+// y source of a plain-run iteration: the fp32 vector the previous update kernel wrote, or the fp64 state with the host's beta
 static YSource plain_source(fos_fista* f) {
   if (f->y_valid) return YSource{f->ynext, nullptr, nullptr, nullptr, &f->scal->stopped, 0.0, nullptr};
   return YSource{nullptr, f->x_cur, f->x_prev, nullptr, &f->scal->stopped, f->h_beta, nullptr};
 }
 
-// Bring the device scalars up to date after plain split-mode updates (their bookkeeping is deferred so that a
-// sharded run pays two launches + one collective per iteration).  n_rr = 0: rr was written by slab_reduce.
-static int flush_pending(fos_fista* f) {
-  if (!f->pending) return FOS_OK;
-  fos_problem* p = f->p;
-  const size_t psz = (size_t)f->nupd * 4;
-  const long long last = f->h_k - 1;
-  const double* cur = f->part2 + (size_t)(last & 1) * psz;
-  const double* prev = f->plain_count >= 2 ? f->part2 + (size_t)((last - 1) & 1) * psz : nullptr;
-  hipLaunchKernelGGL(fos::fista_finalize_plain_kernel, dim3(1), dim3(64), 0, p->stream, cur, prev, f->nupd, p->rr_part, 0,
-                     f->scal, f->h_t, f->h_beta, f->h_k);
+// ---- The host mirror of the momentum scalars (struct fos_fista, fos_internal.hpp): its only writers ----------------------
+static double* part2_slot(const fos_fista* f, long long k) { return f->part2 + (size_t)(k & 1) * f->nupd * 4; }
+
+// The closing fista_finalize_plain_kernel of plain iterations: step partials (nparts x 4) of the last iteration (cur) and of
+// the one before it (prev; null: none), rr partials (n_rr = 0: rr was written already), momentum and count from the mirror.
+static int finish_plain(fos_fista* f, const double* cur, const double* prev, int nparts, const double* rr, int n_rr) {
+  hipLaunchKernelGGL(fos::fista_finalize_plain_kernel, dim3(1), dim3(64), 0, f->p->stream, cur, prev, nparts, rr, n_rr, f->scal,
+                     f->h_t, f->h_beta, f->h_k);
   LAUNCH_CHECK();
   f->pending = false;
   return FOS_OK;
+}
+
+// ... of plain iterations whose partials sit in part2
+static int finish_part2(fos_fista* f, int n_rr) {
+  return finish_plain(f, part2_slot(f, f->h_k - 1), f->plain_count >= 2 ? part2_slot(f, f->h_k - 2) : nullptr, f->nupd,
+                      f->p->rr_part, n_rr);
+}
+
+static int flush_pending(fos_fista* f) { return f->pending ? finish_part2(f, 0) : FOS_OK; }
+
+// Start of a plain run: flush (unless the run closes the pending iterations itself), then the mirror valid - read back once
+// after device-held state.  *stopped: the state machine has stopped; the caller decides what that means for its run.
+static int begin_plain(fos_fista* f, bool* stopped, bool flush = true) {
+  *stopped = false;
+  int rc = flush ? flush_pending(f) : FOS_OK;
+  if (rc || f->host_valid) return rc;
+  fos_fista_status st;
+  if ((rc = fos_fista_status_get(f, &st))) return rc;
+  *stopped = st.stopped != FOS_STOP_NONE;
+  f->h_t = st.t_prev; f->h_beta = st.beta; f->h_k = st.k;
+  f->host_valid = true;
+  return FOS_OK;
+}
+
+// One plain iteration k = h_k: beta_k of its y, beta_{k+1} of the next y, its part2 slot.  ynext: its update leaves y_{k+1}
+// there.
+struct PlainStep { double beta, beta_next; double* part; };
+static PlainStep advance_plain(fos_fista* f, bool ynext) {
+  PlainStep s{f->h_beta, 0.0, part2_slot(f, f->h_k)};
+  host_momentum(f->prm, f->h_k, &f->h_t, &f->h_beta);
+  s.beta_next = f->h_beta;
+  f->h_k += 1;
+  f->plain_count += 1;
+  f->y_valid = ynext;
+  f->pending = true;
+  return s;
+}
+
+// The momentum of `iters` plain iterations run in one launch: beta_k for y_k, then beta_{k+1} ... beta_{k+iters} -> p->fz_beta.
+// The mirror moves on by iters; *before is where it stood (restore_momentum).
+struct Momentum { double t, beta; long long k; };
+static int momentum_sequence(fos_fista* f, int iters, Momentum* before) {
+  fos_problem* p = f->p;
+  int rc = grow(&p->fz_beta_cap, iters + 1, sizeof(double), &p->fz_beta);
+  if (rc) return rc;
+  *before = Momentum{f->h_t, f->h_beta, f->h_k};
+  std::vector<double> betas((size_t)iters + 1);
+  betas[0] = f->h_beta;
+  for (int k = 0; k < iters; ++k) {
+    host_momentum(f->prm, f->h_k, &f->h_t, &f->h_beta);
+    betas[(size_t)k + 1] = f->h_beta;
+    f->h_k += 1;
+  }
+  HIP_TRY(hipMemcpyAsync(p->fz_beta, betas.data(), betas.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));          // (the host vector must outlive the copy)
+  return FOS_OK;
+}
+
+static void restore_momentum(fos_fista* f, const Momentum& m) {
+  f->h_t = m.t; f->h_beta = m.beta; f->h_k = m.k;
+}
+
+// ynext must hold y_{h_k}
+static int ensure_y(fos_fista* f) {
+  if (f->y_valid) return FOS_OK;
+  fos_problem* p = f->p;
+  hipLaunchKernelGGL(fos::form_y_kernel, dim3(grid_1d(p->n, 256, 256)), dim3(256), 0, p->stream, f->x_cur, f->x_prev, f->h_beta,
+                     f->ynext, p->n);
+  LAUNCH_CHECK();
+  f->y_valid = true;
+  return FOS_OK;
+}
+
+// The next plain iteration starts a new run of part2 partials, and forms its y from the fp64 state unless keep_y.
+static void restart_plain(fos_fista* f, bool keep_y = false) {
+  f->plain_count = 0;
+  if (!keep_y) f->y_valid = false;
+}
+
+// t, beta and k advance on the device only from here on
+static void hand_to_device(fos_fista* f) {
+  f->host_valid = false;
+  restart_plain(f);
 }
 
 static bool plain_run(const fos_fista* f) {
@@ -281,18 +367,6 @@ static int launch_grad_norm_stop(fos_fista* f) {
   return FOS_OK;
 }
 
-static int refresh_host_scalars(fos_fista* f, bool* stopped) {
-  *stopped = false;
-  if (f->host_valid) return FOS_OK;
-  fos_fista_status st;
-  int rc = fos_fista_status_get(f, &st);      // synchronises once after split-mode / device-driven calls
-  if (rc) return rc;
-  *stopped = st.stopped != FOS_STOP_NONE;
-  f->h_t = st.t_prev; f->h_beta = st.beta; f->h_k = st.k;
-  f->host_valid = true;
-  return FOS_OK;
-}
-
 // Whole run in ONE launch of ONE workgroup (resident.hpp): A, b and the iterate state stay in LDS.
 static int run_resident(fos_fista* f, int iters, double* x_hist, double* hist, fos::ResidentOpts opt = fos::ResidentOpts{}) {
   fos_problem* p = f->p;
@@ -308,9 +382,7 @@ static int run_resident(fos_fista* f, int iters, double* x_hist, double* hist, f
   else { if (small) FOS_RS_LAUNCH(fos::bf16_t, true); else FOS_RS_LAUNCH(fos::bf16_t, false); }
 #undef FOS_RS_LAUNCH
   LAUNCH_CHECK();
-  f->host_valid = false;                       // t, beta, k now live on the device only
-  f->y_valid = false;
-  f->plain_count = 0;
+  hand_to_device(f);
   return FOS_OK;
 }
 
@@ -354,27 +426,24 @@ int fos_fista_run_history(fos_fista* f, int iters, double* x_hist, double* hist,
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_history: needs a plain run on the fused path with a DUAL kernel");
   if (iters == 0) return FOS_OK;
   bool stopped = false;
-  int rc = refresh_host_scalars(f, &stopped);
+  int rc = begin_plain(f, &stopped);
   if (rc) return rc;
   if (stopped) return fail(FOS_ERR_STATE, "fos_fista_run_history: solver already stopped");
   const int nwg = p->nwg;
+  const size_t psz = (size_t)f->nupd * 4;
   double* rr2_slots = reinterpret_cast<double*>(work);                 // (iters + 1) x nwg
   double* part_slots = rr2_slots + (size_t)(iters + 1) * nwg;          // iters x nupd x 4
   double* saved_rr2 = p->rr2_part;
   int n_rr = 0;
-  if ((rc = flush_pending(f))) return rc;
-  f->y_valid = false;      // the DUAL pass needs x_k itself, so it always rebuilds y from the fp64 state
-  f->plain_count = 0;
   for (int it = 0; it < iters; ++it) {
+    // the DUAL pass needs x_k itself, so it always forms y from the fp64 state
     YSource ys{nullptr, f->x_cur, f->x_prev, nullptr, &f->scal->stopped, f->h_beta, nullptr};
     p->rr2_part = rr2_slots + (size_t)it * nwg;                        // slot it = residual of the iterate BEFORE it
     rc = launch_pass(p, ys, p->b, true, &n_rr, true);
     p->rr2_part = saved_rr2;
     if (rc) return rc;
-    launch_update_from_slabs(f, part_slots + (size_t)it * f->nupd * 4, 1, f->h_beta, x_hist + (size_t)it * p->n);
-    LAUNCH_CHECK();
-    host_momentum(f->prm, f->h_k, &f->h_t, &f->h_beta);
-    f->h_k += 1;
+    const PlainStep s = advance_plain(f, false);
+    if ((rc = launch_update_from_slabs(f, part_slots + it * psz, 1, s.beta, x_hist + (size_t)it * p->n))) return rc;
   }
   // closing residual pass: ||A x_last - b||^2 -> slot iters (written by the residual-only kernel into rr_part)
   hipLaunchKernelGGL(fos::cast_f64_f32_kernel, dim3(grid_1d(p->n, 256, 1024)), dim3(256), 0, p->stream, f->x_cur, p->ybuf,
@@ -391,13 +460,10 @@ int fos_fista_run_history(fos_fista* f, int iters, double* x_hist, double* hist,
   hipLaunchKernelGGL(fos::history_fold_kernel, dim3(iters), dim3(64), 0, p->stream, rr2_slots, nwg, part_slots, f->nupd,
                      hist);
   LAUNCH_CHECK();
-  // device scalars: step norms of the last two iterations, momentum from the host
-  const double* cur = part_slots + (size_t)(iters - 1) * f->nupd * 4;
-  const double* prev = iters >= 2 ? part_slots + (size_t)(iters - 2) * f->nupd * 4 : nullptr;
-  hipLaunchKernelGGL(fos::fista_finalize_plain_kernel, dim3(1), dim3(64), 0, p->stream, cur, prev, f->nupd, p->rr_part,
-                     nwg, f->scal, f->h_t, f->h_beta, f->h_k);
-  LAUNCH_CHECK();
-  return FOS_OK;
+  rc = finish_plain(f, part_slots + (iters - 1) * psz, iters >= 2 ? part_slots + (iters - 2) * psz : nullptr, f->nupd,
+                    p->rr_part, nwg);
+  restart_plain(f);
+  return rc;
 }
 
 int fos_fista_run(fos_fista* f, int iters) {
@@ -453,39 +519,21 @@ int fos_fista_run(fos_fista* f, int iters) {
   }
   if (plain_run(f)) {
     bool stopped = false;
-    int rc0 = refresh_host_scalars(f, &stopped);
-    if (rc0) return rc0;
-    if (stopped) return FOS_OK;
-    const size_t psz = (size_t)f->nupd * 4;
+    int rc = begin_plain(f, &stopped, false);   // pending split-mode iterations close with this run's bookkeeping
+    if (rc || stopped) return rc;
     int n_rr = 0;
     for (int it = 0; it < iters; ++it) {
-      int rc;
       if ((rc = launch_pass(p, plain_source(f), p->b, true, &n_rr))) return rc;
-      const double beta_k = f->h_beta;
-      host_momentum(f->prm, f->h_k, &f->h_t, &f->h_beta);          // beta_{k+1}
-      launch_update_from_slabs(f, f->part2 + (size_t)(f->h_k & 1) * psz, 1, beta_k, nullptr, f->ynext, f->h_beta);
-      LAUNCH_CHECK();
-      f->y_valid = true;
-      f->h_k += 1;
-      f->plain_count += 1;
+      const PlainStep s = advance_plain(f, true);
+      if ((rc = launch_update_from_slabs(f, s.part, 1, s.beta, nullptr, f->ynext, s.beta_next))) return rc;
     }
-    f->pending = false;
-    const long long last = f->h_k - 1;
-    const double* cur = f->part2 + (size_t)(last & 1) * psz;
-    const double* prev = f->plain_count >= 2 ? f->part2 + (size_t)((last - 1) & 1) * psz : nullptr;
-    hipLaunchKernelGGL(fos::fista_finalize_plain_kernel, dim3(1), dim3(64), 0, p->stream, cur, prev, f->nupd, p->rr_part,
-                       n_rr, f->scal, f->h_t, f->h_beta, f->h_k);
-    LAUNCH_CHECK();
-    return FOS_OK;
+    return finish_part2(f, n_rr);
   }
-  f->host_valid = false;
-  f->y_valid = false;
-  f->plain_count = 0;
+  hand_to_device(f);
   for (int it = 0; it < iters; ++it) {
     int n_rr = 0, rc;
     if ((rc = launch_pass(p, fista_source(f), p->b, true, &n_rr))) return rc;
-    launch_update_from_slabs(f, p->part, 0, 0.0);
-    LAUNCH_CHECK();
+    if ((rc = launch_update_from_slabs(f, p->part, 0, 0.0))) return rc;
     if ((rc = launch_finalize(f, n_rr))) return rc;
   }
   return FOS_OK;
@@ -510,59 +558,25 @@ int fos_fista_run_fused(fos_fista* f, int iters) {
   if (!plain_run(f) || f->precise || f->prm.tau_from_state)
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_fused: plain runs only (no adaptive restart, tolerances, device-held step)");
   if (iters == 0) return FOS_OK;
-  int rc = flush_pending(f);
-  if (rc) return rc;
   bool stopped = false;
-  if ((rc = refresh_host_scalars(f, &stopped))) return rc;
-  if (stopped) return FOS_OK;
+  int rc = begin_plain(f, &stopped);
+  if (rc || stopped) return rc;
   // workspace: G slabs (the planner's are reused when it planned G workgroups), barrier words, beta sequence, partials
-  if (G > p->slab_cap) {
-    if (p->slabs) (void)hipFree(p->slabs);
-    p->slabs = nullptr; p->slab_cap = 0;
-    HIP_TRY(hipMalloc(&p->slabs, (size_t)G * p->n * sizeof(float)));
-    p->slab_cap = G;
-  }
-  if (G > p->rr_cap) {
-    if (p->rr_part) (void)hipFree(p->rr_part);
-    if (p->rr2_part) (void)hipFree(p->rr2_part);
-    p->rr_part = p->rr2_part = nullptr; p->rr_cap = 0;
-    HIP_TRY(hipMalloc(&p->rr_part, (size_t)G * sizeof(double)));
-    HIP_TRY(hipMalloc(&p->rr2_part, (size_t)G * sizeof(double)));
-    p->rr_cap = G;
-  }
+  if ((rc = grow(&p->slab_cap, G, (size_t)p->n * sizeof(float), &p->slabs))) return rc;
+  if ((rc = grow(&p->rr_cap, G, sizeof(double), &p->rr_part, &p->rr2_part))) return rc;
   if (!p->fz_bar) {
     HIP_TRY(hipMalloc(&p->fz_bar, fos::FZ_BAR_WORDS * sizeof(unsigned)));
     HIP_TRY(hipMemsetAsync(p->fz_bar, 0, fos::FZ_BAR_WORDS * sizeof(unsigned), p->stream));
     HIP_TRY(hipMalloc(&p->fz_part, (size_t)2 * G * 4 * sizeof(double)));
   }
-  if (iters + 1 > p->fz_beta_cap) {
-    if (p->fz_beta) (void)hipFree(p->fz_beta);
-    p->fz_beta = nullptr; p->fz_beta_cap = 0;
-    HIP_TRY(hipMalloc(&p->fz_beta, (size_t)(iters + 1) * sizeof(double)));
-    p->fz_beta_cap = iters + 1;
-  }
-  if (!f->y_valid) {
-    hipLaunchKernelGGL(fos::form_y_kernel, dim3(grid_1d(p->n, 256, 256)), dim3(256), 0, p->stream, f->x_cur, f->x_prev, f->h_beta,
-                       f->ynext, p->n);
-    LAUNCH_CHECK();
-    f->y_valid = true;
-  }
-  // the momentum sequence of a plain run does not depend on the data: beta[k] for y_k, beta[k + 1] ... beta[iters]
-  std::vector<double> betas((size_t)iters + 1);
-  betas[0] = f->h_beta;
-  const long long k0 = f->h_k;
-  for (int k = 0; k < iters; ++k) {
-    host_momentum(f->prm, f->h_k, &f->h_t, &f->h_beta);
-    betas[(size_t)k + 1] = f->h_beta;
-    f->h_k += 1;
-  }
-  HIP_TRY(hipMemcpyAsync(p->fz_beta, betas.data(), betas.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));          // (the host vector must outlive the copy)
+  if ((rc = ensure_y(f))) return rc;
+  Momentum before;
+  if ((rc = momentum_sequence(f, iters, &before))) return rc;
   fos::FusedArgs a{};
   a.A = (const float*)p->A; a.lda = p->lda; a.b = p->b; a.m = p->m; a.n = (int)p->n;
   a.rows_per_wg = ((p->m + G - 1) / G + fos::FZ_ROWS - 1) / fos::FZ_ROWS * fos::FZ_ROWS;
   a.slabs = p->slabs; a.y = f->ynext; a.x_cur = f->x_cur; a.x_prev = f->x_prev; a.beta = p->fz_beta; a.part = p->fz_part;
-  a.rr_part = p->rr_part; a.bar = p->fz_bar; a.iters = iters; a.prox_kind = f->prm.prox_kind; a.k0 = k0;
+  a.rr_part = p->rr_part; a.bar = p->fz_bar; a.iters = iters; a.prox_kind = f->prm.prox_kind; a.k0 = before.k;
   a.tau = f->prm.tau; a.alpha1 = f->prm.alpha1; a.alpha2 = f->prm.alpha2;
   a.timeout_ticks = 100000000ull * 2ull;           // 2 s of the 100 MHz wall clock per wait
   a.stamps = p->fz_stamps;
@@ -576,15 +590,10 @@ int fos_fista_run_fused(fos_fista* f, int iters) {
   }
   if (rc) return rc;
   if ((rc = prof_mark(p, false))) return rc;
-  f->pending = false;
-  f->plain_count += iters;
   const long long last = f->h_k - 1;
-  const double* cur = p->fz_part + (size_t)(last & 1) * G * 4;
   const double* prev = iters >= 2 ? p->fz_part + (size_t)((last - 1) & 1) * G * 4 : nullptr;
-  hipLaunchKernelGGL(fos::fista_finalize_plain_kernel, dim3(1), dim3(64), 0, p->stream, cur, prev, G, p->rr_part, G, f->scal,
-                     f->h_t, f->h_beta, f->h_k);
-  LAUNCH_CHECK();
-  f->plain_count = 0;                              // part2 of the two-launch path starts afresh
+  if ((rc = finish_plain(f, p->fz_part + (size_t)(last & 1) * G * 4, prev, G, p->rr_part, G))) return rc;
+  restart_plain(f, true);                          // the kernel leaves y_{k+iters} in ynext
   // a grid-wide wait that ran out leaves the state invalid: report it (synchronises)
   unsigned bad = 0;
   HIP_TRY(hipMemcpyAsync(&bad, p->fz_bar + fos::FZ_LINE, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
@@ -607,13 +616,9 @@ int fos_fista_run_chip(fos_fista* f, int iters) {
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_chip: no gradient-norm rule, fp64 split gradient or device-held step (backtracking)");
   const bool ctrl = !plain_run(f);
   if (iters == 0) return FOS_OK;
-  int rc = flush_pending(f);
-  if (rc) return rc;
   bool stopped = false;
-  if (!ctrl) {
-    if ((rc = refresh_host_scalars(f, &stopped))) return rc;
-    if (stopped) return FOS_OK;
-  }
+  int rc = ctrl ? flush_pending(f) : begin_plain(f, &stopped);
+  if (rc || stopped) return rc;
   // about 1024 rows (four per thread) per workgroup, at most what its LDS holds: the barrier, not the pass, is the cost, and it
   // grows with the number of workgroups (tools/bench_chip.py: 100000 x 5 took 11.9 us per iteration on 256 workgroups)
   int64_t G = std::max<int64_t>(1, std::min<int64_t>(p->ncu, (p->m + 1023) / 1024));
@@ -626,23 +631,8 @@ int fos_fista_run_chip(fos_fista* f, int iters) {
     HIP_TRY(hipMalloc(&p->cr_bar, fos::FZ_BAR_WORDS * sizeof(unsigned)));
     HIP_TRY(hipMemsetAsync(p->cr_bar, 0, fos::FZ_BAR_WORDS * sizeof(unsigned), p->stream));
   }
-  if (iters + 1 > p->fz_beta_cap) {
-    if (p->fz_beta) (void)hipFree(p->fz_beta);
-    p->fz_beta = nullptr; p->fz_beta_cap = 0;
-    HIP_TRY(hipMalloc(&p->fz_beta, (size_t)(iters + 1) * sizeof(double)));
-    p->fz_beta_cap = iters + 1;
-  }
-  std::vector<double> betas((size_t)iters + 1);
-  betas[0] = f->h_beta;
-  const long long k_before = f->h_k;
-  const double t_before = f->h_t, beta_before = f->h_beta;
-  for (int k = 0; k < iters; ++k) {
-    host_momentum(f->prm, f->h_k, &f->h_t, &f->h_beta);
-    betas[(size_t)k + 1] = f->h_beta;
-    f->h_k += 1;
-  }
-  HIP_TRY(hipMemcpyAsync(p->fz_beta, betas.data(), betas.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));          // (the host vector must outlive the copy)
+  Momentum before;
+  if ((rc = momentum_sequence(f, iters, &before))) return rc;
   double* stats = p->cr_part + (size_t)2 * p->ncu * 17;
   fos::ChipArgs a{};
   a.A = (const float*)p->A; a.lda = p->lda; a.b = p->b; a.m = p->m; a.n = (int)p->n; a.rows_per_wg = rpw;
@@ -664,85 +654,56 @@ int fos_fista_run_chip(fos_fista* f, int iters) {
   HIP_TRY(hipMemcpyAsync(&bad, p->cr_bar + fos::FZ_LINE, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   if (bad) {
-    f->h_k = k_before; f->h_t = t_before; f->h_beta = beta_before;
+    restore_momentum(f, before);
     HIP_TRY(hipMemsetAsync(p->cr_bar, 0, fos::FZ_BAR_WORDS * sizeof(unsigned), p->stream));
     return fail(FOS_ERR_STATE, "fos_fista_run_chip: a grid-wide wait timed out (workgroups not co-resident); the state is "
                                "the one before the call");
   }
-  f->pending = false;
-  f->y_valid = false;                              // the fp32 y vector of the two-launch path is not maintained here
-  f->plain_count = 0;
-  if (ctrl) {                                      // the kernel advanced FistaScalars itself; the host's mirrors are stale
-    f->host_valid = false;
-    f->h_k = k_before; f->h_t = t_before; f->h_beta = beta_before;
+  if (ctrl) {                                      // the kernel advanced FistaScalars itself
+    hand_to_device(f);
     return FOS_OK;
   }
-  hipLaunchKernelGGL(fos::fista_finalize_plain_kernel, dim3(1), dim3(64), 0, p->stream, stats, iters >= 2 ? stats + 4 : (const double*)nullptr,
-                     1, stats + 8, 1, f->scal, f->h_t, f->h_beta, f->h_k);
-  LAUNCH_CHECK();
-  return FOS_OK;
+  restart_plain(f);                                // ynext is not maintained here
+  return finish_plain(f, stats, iters >= 2 ? stats + 4 : nullptr, 1, stats + 8, 1);
+}
+
+// The arguments of fista_update_multi_kernel: every state machine's buffers and weights; plain runs also take its next
+// momentum step (controlled runs take beta from the device scalars).
+static fos::MultiUpdate multi_update(fos_fista* const* fs, int nv, bool controlled) {
+  fos::MultiUpdate mu{};
+  for (int v = 0; v < nv; ++v) {
+    fos_fista* f = fs[v];
+    mu.x_cur[v] = f->x_cur; mu.x_prev[v] = f->x_prev; mu.scal[v] = f->scal; mu.part[v] = f->part2;
+    mu.alpha1[v] = f->prm.alpha1; mu.alpha2[v] = f->prm.alpha2; mu.tau[v] = f->prm.tau;
+    if (!controlled) {
+      const PlainStep s = advance_plain(f, false);
+      mu.part[v] = s.part; mu.beta[v] = s.beta; mu.beta_next[v] = s.beta_next;
+    }
+  }
+  return mu;
 }
 
 // Up to 16 state machines in lockstep on the matrix cores (gram_batch.hpp): per iteration and per row panel, product 1
-// (R = A_panel Y - b, from HBM) and product 2 (G += R^T A_panel, the panel again from the Infinity Cache), then one
-// update kernel per state machine, which leaves its y_{k+1} in the candidate block of the next product 1.
+// (R = A_panel Y - b, from HBM) and product 2 (G += R^T A_panel, the panel again from the Infinity Cache), then the updates,
+// which leave every y_{k+1} in the candidate block of the next product 1.  The layout: plan_multi_mfma (fos_plan.hip).
+// same_family: the state machines differ in weights and steps only (a regularisation path does) - one update launch for all.
 // b16 (several right-hand sides, unsharded): product 1 subtracts column j of this m x 16 block from candidate column j
 // instead of the problem's b; always the two-product form (the planner's cluster layout, if any, is left as it is).
-static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controlled = false, const float* b16 = nullptr) {
+static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controlled, bool same_family,
+                          const float* b16 = nullptr) {
   fos_problem* p = fs[0]->p;
-  int rc = ensure_batch_workspace(p);
-  if (rc) return rc;
-  const bool is_bf16 = p->dtype == FOS_BF16;
-  const int64_t esz = is_bf16 ? 2 : 4;
-  // One-read form (cluster_pass.hpp): fp32, 2049..16384 columns in strips of 1024 -> 4, 8 or 16 members per cluster, all
-  // CUs busy, at least 8 panels per cluster; FOS_PLAN_CLUSTER / FOS_PLAN_NO_CLUSTER force it on (where served) / off.
-  // Planner default (profiles/r03_cluster_crossover.md, 16 weights, us per iteration, two products -> one read): the
-  // one-read form wins where every member of a cluster has a full 1024-column strip and the matrix is large -
-  // 131072 x 4096 826 -> 640, 524288 x 4096 3306 -> 2407, 65536 x 8192 670 -> 643, 262144 x 8192 2668 -> 2430 - ties at
-  // 32768 x 8192 and loses with idle members (6144 columns +10 %, 3072 +5 %) and at 16 members (131072 x 16384 +5 %).
-  const int cs_need = (int)((p->n + fos::CP_W - 1) / fos::CP_W);
-  const bool cluster_wins = (p->n == 4096 || p->n == 8192) && p->m * p->n >= (1ll << 29) && !p->comm;
-  const bool want_cluster = p->cp_mode == 1 || (p->cp_mode == 0 && cluster_wins);
-  if (!p->rbuf16 && want_cluster && !is_bf16 && p->ncu % 8 == 0) {
-    const int cs = cs_need <= 2 ? 0 : cs_need <= 4 ? 4 : cs_need <= 8 ? 8 : cs_need <= 16 ? 16 : 0;
-    if (cs && (p->ncu / 8) % cs == 0 && p->m >= (int64_t)(p->ncu / cs) * fos::CP_ROWS * 8) {
-      p->cp_cs = cs;
-      p->cp_clusters = p->ncu / cs;
-      p->cp_rows_per_cluster = ((p->m + p->cp_clusters - 1) / p->cp_clusters + fos::CP_ROWS - 1) / fos::CP_ROWS * fos::CP_ROWS;
-      HIP_TRY(hipMalloc(&p->cp_xchg, (size_t)p->ncu * fos::CP_SLOTS * 256 * sizeof(float)));
-      HIP_TRY(hipMalloc(&p->cp_flags, (size_t)p->ncu * fos::CP_FLAG_STRIDE * sizeof(unsigned)));
-      HIP_TRY(hipMemsetAsync(p->cp_flags, 0, (size_t)p->ncu * fos::CP_FLAG_STRIDE * sizeof(unsigned), p->stream));
-      HIP_TRY(hipMalloc(&p->cp_error, sizeof(int)));
-      HIP_TRY(hipMemsetAsync(p->cp_error, 0, sizeof(int), p->stream));
-    }
-  }
   const bool cols = p->col_sharded;
   if (cols && !controlled) return fail(FOS_ERR_STATE, "run_multi_mfma: a column-sharded lockstep is device-controlled");
+  int rc = ensure_batch_workspace(p);
+  if (rc) return rc;
   if (cols && !p->mfold) HIP_TRY(hipMalloc(&p->mfold, (size_t)fos::BT_NV * 4 * sizeof(double)));
-  if (!p->rbuf16) {
-    // Panel: product 1 gives a workgroup 64-128 whole rows, so it needs >= 128 * CUs * 2 rows to fill the chip; row
-    // splits of product 2: enough (strip, split) workgroups for two per CU.  (A panel that fits the Infinity Cache
-    // - ~3000 rows at n = 8192 - would need a split-K product 1; see DESIGN.md "Multi-lambda".)
-    const int64_t rows = 256 * (int64_t)p->ncu;
-    p->panel_rows = std::min<int64_t>(rows, (p->m + 255) / 256 * 256);
-    if (cols && p->comm->kind != 0) {          // mesh transport: a panel's 16 residual columns are one message
-      const int64_t fit = (int64_t)(p->comm->cap_bytes / (fos::BT_NV * sizeof(float))) / 256 * 256;
-      if (fit < 256) return fail(FOS_ERR_ARG, "fos_fista_run_multi: the communicator's inbox rows hold less than one 256-row "
-                                              "panel of 16 residual columns (16 KiB)");
-      p->panel_rows = std::min<int64_t>(p->panel_rows, fit);
-    }
-    const int64_t strips = (p->n + (is_bf16 ? fos::GQ_COLS : fos::GB_COLS) - 1) / (is_bf16 ? fos::GQ_COLS : fos::GB_COLS);
-    int64_t splits = std::max<int64_t>(1, (2 * (int64_t)p->ncu + strips - 1) / strips);
-    splits = std::min<int64_t>(splits, std::max<int64_t>(1, p->panel_rows / 256));
-    p->gram_rows_per_split = ((p->panel_rows + splits - 1) / splits + fos::GB_ROWS - 1) / fos::GB_ROWS * fos::GB_ROWS;
-    p->gram_splits = (int)((p->panel_rows + p->gram_rows_per_split - 1) / p->gram_rows_per_split);
-    if (p->cp_cs) p->gram_splits = p->cp_clusters;      // one slab set per cluster
-    HIP_TRY(hipMalloc(&p->rbuf16, (size_t)p->panel_rows * fos::BT_NV * sizeof(float)));
-    HIP_TRY(hipMalloc(&p->slabs16, (size_t)p->gram_splits * fos::BT_NV * p->n * sizeof(float)));
-  }
+  if ((rc = plan_multi_mfma(p))) return rc;
+  const bool is_bf16 = p->dtype == FOS_BF16;
+  const int64_t esz = is_bf16 ? 2 : 4;
+  const int y_mode = is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP;
   // row splits of product 2: the planned ones, or - a B-block run on a problem planned for the cluster form, whose slab
   // count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated
-  const bool use_cluster = p->cp_cs && !b16;
+  bool use_cluster = p->cp_cs && !b16;
   int g_splits = p->gram_splits;
   if (p->cp_cs && b16) {
     g_splits = (int)((p->panel_rows + p->gram_rows_per_split - 1) / p->gram_rows_per_split);
@@ -760,51 +721,37 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
     for (int v = 0; v < nv; ++v) {
       fos_fista* f = fs[v];
       if ((rc = flush_pending(f))) return rc;
-      f->host_valid = false; f->y_valid = false; f->plain_count = 0;
+      hand_to_device(f);
       mc.scal[v] = f->scal; mc.part[v] = f->part2; mc.x_cur[v] = f->x_cur; mc.x_prev[v] = f->x_prev;
       mc.adaptive_restart[v] = f->prm.adaptive_restart; mc.restart_threshold[v] = f->prm.restart_threshold;
       mc.tol_step[v] = f->prm.tol_step; mc.tol_ratio[v] = f->prm.tol_ratio;
     }
     hipLaunchKernelGGL(fos::form_y_multi_kernel, dim3(grid_1d(p->n, 256, 64), nv), dim3(256), 0, p->stream, mc, (int)p->n, p->xp,
-                       is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP, 1);
+                       y_mode, 1);
     LAUNCH_CHECK();
   }
   for (int v = 0; v < nv && !controlled; ++v) {
     fos_fista* f = fs[v];
-    if ((rc = flush_pending(f))) return rc;
     bool stopped = false;
-    if ((rc = refresh_host_scalars(f, &stopped))) return rc;
+    if ((rc = begin_plain(f, &stopped))) return rc;
     if (stopped) return fail(FOS_ERR_STATE, "fos_fista_run_multi: a handle has already stopped");
     hipLaunchKernelGGL(fos::form_y_block_kernel, dim3(grid_1d(p->n, 256, 256)), dim3(256), 0, p->stream, f->x_cur, f->x_prev,
                        f->h_beta, (int)p->n, v, is_bf16 ? (float*)nullptr : p->xp,
                        is_bf16 ? (unsigned short*)p->xp : (unsigned short*)nullptr);
     LAUNCH_CHECK();
-    f->y_valid = false;              // the fp32 y vector of the single-vector path is not maintained here
-    f->plain_count = 0;
+    restart_plain(f);                // y lives in the candidate block; part2 partials are counted from this run on
   }
-  const size_t psz = (size_t)fs[0]->nupd * 4;
   const int64_t strips = (p->n + (is_bf16 ? fos::GQ_COLS : fos::GB_COLS) - 1) / (is_bf16 ? fos::GQ_COLS : fos::GB_COLS);
-  // one update launch for all state machines when they differ in weights and steps only (a regularisation path does)
-  bool same_family = true;
-  for (int v = 1; v < nv; ++v) {
-    const fos::FistaParams &a = fs[0]->prm, &c = fs[v]->prm;
-    same_family = same_family && a.mode == c.mode && a.prox_kind == c.prox_kind && a.delta == c.delta;
-  }
   for (int it = 0; it < iters; ++it) {
     if ((rc = prof_mark(p, true))) return rc;
-    if (use_cluster) {
-      if ((rc = launch_cluster_pass(p))) {
-        if (p->cp_mode == 1 || it > 0) return rc;
-        (void)hipGetLastError();                 // planner's own choice refused (cooperative launch): two products instead
-        p->cp_cs = 0;
-        p->cp_mode = 2;
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        (void)hipFree(p->rbuf16); (void)hipFree(p->slabs16);       // sized for the cluster form: re-planned by the re-entry
-        p->rbuf16 = p->slabs16 = nullptr;
-        return run_multi_mfma(fs, nv, iters, controlled, b16);
-      }
-    } else
-    for (int64_t row0 = 0, panel = 0; row0 < p->m; row0 += p->panel_rows, ++panel) {
+    if (use_cluster && (rc = launch_cluster_pass(p))) {
+      if (p->cp_mode == 1 || it > 0) return rc;
+      (void)hipGetLastError();                   // planner's own choice refused (cooperative launch): two products instead
+      if ((rc = plan_multi_mfma(p, true))) return rc;
+      use_cluster = false;
+      g_splits = p->gram_splits;
+    }
+    for (int64_t row0 = 0, panel = 0; !use_cluster && row0 < p->m; row0 += p->panel_rows, ++panel) {
       const int64_t rows = std::min<int64_t>(p->panel_rows, p->m - row0);
       const char* Ap = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz;
       int nwg1 = 0;
@@ -831,16 +778,20 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
     // row-sharded problem: the 16 partial gradients (all row splits) are summed over the ranks before the updates
     // (column-sharded: the gradient block is local)
     if (!cols && (rc = reduce_across(p, p->slabs16, (size_t)g_splits * fos::BT_NV * p->n, false))) return rc;
-    if (controlled) {                            // update (device beta) -> bookkeeping of all weights -> their y_{k+1}
-      fos::MultiUpdate mu{};
-      for (int v = 0; v < nv; ++v) {
-        fos_fista* f = fs[v];
-        mu.x_cur[v] = f->x_cur; mu.x_prev[v] = f->x_prev; mu.scal[v] = f->scal; mu.part[v] = f->part2;
-        mu.alpha1[v] = f->prm.alpha1; mu.alpha2[v] = f->prm.alpha2; mu.tau[v] = f->prm.tau;
-      }
-      hipLaunchKernelGGL(fos::fista_update_multi_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->slabs16,
-                         g_splits, (int)p->n, mu, fs[0]->prm, p->xp, is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP, 0);
+    if (controlled || same_family) {             // one launch updates all state machines
+      const fos::MultiUpdate mu = multi_update(fs, nv, controlled);
+      hipLaunchKernelGGL(fos::fista_update_multi_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->slabs16, g_splits,
+                         (int)p->n, mu, fs[0]->prm, p->xp, y_mode, controlled ? 0 : 1);
       LAUNCH_CHECK();
+    } else {
+      for (int v = 0; v < nv; ++v) {
+        const PlainStep s = advance_plain(fs[v], false);
+        if ((rc = launch_update_from_slabs(fs[v], s.part, 1, s.beta, nullptr, p->xp, s.beta_next, p->slabs16 + (size_t)v * p->n,
+                                           (int64_t)fos::BT_NV * p->n, g_splits, y_mode, v)))
+          return rc;
+      }
+    }
+    if (controlled) {                            // bookkeeping of all weights (device beta) -> their y_{k+1}
       if (cols) {                                // step norms, ||x||^2, ||x||_1 are sums over the column blocks of all ranks
         hipLaunchKernelGGL(fold4_multi_kernel, dim3(nv), dim3(64), 0, p->stream, mc, fs[0]->nupd, p->mfold);
         LAUNCH_CHECK();
@@ -852,36 +803,8 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
         hipLaunchKernelGGL(fos::fista_finalize_multi_kernel, dim3(nv), dim3(64), 0, p->stream, mc, fs[0]->nupd, fs[0]->prm);
       LAUNCH_CHECK();
       hipLaunchKernelGGL(fos::form_y_multi_kernel, dim3(grid_1d(p->n, 256, 64), nv), dim3(256), 0, p->stream, mc, (int)p->n, p->xp,
-                         is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP, 0);
+                         y_mode, 0);
       LAUNCH_CHECK();
-    } else if (same_family) {                    // one launch updates all state machines
-      fos::MultiUpdate mu{};
-      for (int v = 0; v < nv; ++v) {
-        fos_fista* f = fs[v];
-        mu.x_cur[v] = f->x_cur; mu.x_prev[v] = f->x_prev; mu.scal[v] = f->scal;
-        mu.part[v] = f->part2 + (size_t)(f->h_k & 1) * psz;
-        mu.beta[v] = f->h_beta;
-        host_momentum(f->prm, f->h_k, &f->h_t, &f->h_beta);
-        mu.beta_next[v] = f->h_beta;
-        mu.alpha1[v] = f->prm.alpha1; mu.alpha2[v] = f->prm.alpha2; mu.tau[v] = f->prm.tau;
-        f->h_k += 1;
-        f->plain_count += 1;
-      }
-      hipLaunchKernelGGL(fos::fista_update_multi_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->slabs16,
-                         g_splits, (int)p->n, mu, fs[0]->prm, p->xp, is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP);
-      LAUNCH_CHECK();
-    } else {
-      for (int v = 0; v < nv; ++v) {
-        fos_fista* f = fs[v];
-        const double beta_k = f->h_beta;
-        host_momentum(f->prm, f->h_k, &f->h_t, &f->h_beta);
-        launch_update_from_slabs(f, f->part2 + (size_t)(f->h_k & 1) * psz, 1, beta_k, nullptr, p->xp, f->h_beta,
-                                 p->slabs16 + (size_t)v * p->n, (int64_t)fos::BT_NV * p->n, g_splits,
-                                 is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP, v);
-        LAUNCH_CHECK();
-        f->h_k += 1;
-        f->plain_count += 1;
-      }
     }
   }
   if (use_cluster) {     // a cluster member that waited out its bound parked itself and raised the flag: the sums are invalid
@@ -892,15 +815,8 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
                                         "(results invalid); rerun with FOS_PLAN_NO_CLUSTER");
   }
   for (int v = 0; v < nv && !controlled; ++v) {
-    fos_fista* f = fs[v];
-    f->pending = false;
-    const long long last = f->h_k - 1;
-    const double* cur = f->part2 + (size_t)(last & 1) * psz;
-    const double* prev = f->plain_count >= 2 ? f->part2 + (size_t)((last - 1) & 1) * psz : nullptr;
-    hipLaunchKernelGGL(fos::fista_finalize_plain_kernel, dim3(1), dim3(64), 0, p->stream, cur, prev, f->nupd, p->rr_part, 0,
-                       f->scal, f->h_t, f->h_beta, f->h_k);
-    LAUNCH_CHECK();
-    f->plain_count = 0;              // part2 of the next single-vector run starts afresh
+    if ((rc = finish_part2(fs[v], 0))) return rc;
+    restart_plain(fs[v]);            // the next single-vector run counts its part2 partials afresh
   }
   return FOS_OK;
 }
@@ -918,7 +834,6 @@ static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, in
   }
   // B is staged once per call, after the kernel choice and only when there are iterations to run
   auto stage = [&]() { return rhs ? stage_b16(p, B, ldb, nv) : FOS_OK; };
-  const float* b16 = nullptr;                    // p->b16 once staged
   bool all_plain = true, controllable = true, same_family = true;
   for (int v = 0; v < nv; ++v) {
     all_plain = all_plain && plain_run(fs[v]);
@@ -936,13 +851,13 @@ static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, in
       return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi: a column-sharded lockstep serves one family without the "
                                        "gradient-norm rule / fp64 gradient / persisted step");
     if (iters == 0) return FOS_OK;
-    return run_multi_mfma(fs, nv, iters, true);
+    return run_multi_mfma(fs, nv, iters, true, true);
   }
   if (!all_plain && controllable && same_family && shape_ok && p->entry != wide_entry(p->dtype) && (nv >= 3 || p->comm)) {
     if (iters == 0) return FOS_OK;
     int rc = stage();
     if (rc) return rc;
-    return run_multi_mfma(fs, nv, iters, true, rhs ? p->b16 : nullptr);
+    return run_multi_mfma(fs, nv, iters, true, true, rhs ? p->b16 : nullptr);
   }
   const bool streaming = shape_ok && all_plain;
   // (a sharded problem takes the matrix-core pass for any number of weights: its 16 gradients are one 16 x n all-reduce)
@@ -953,79 +868,41 @@ static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, in
     if (iters == 0) return FOS_OK;
     int rc = stage();
     if (rc) return rc;
-    return run_multi_mfma(fs, nv, iters, false, rhs ? p->b16 : nullptr);   // 5..16 weights, n up to 16384, fp32 and bf16
+    return run_multi_mfma(fs, nv, iters, false, same_family, rhs ? p->b16 : nullptr);   // 5..16 weights, n up to 16384, fp32 and bf16
   }
   if (!fn) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi: no multi-vector kernel for this shape / configuration");
   if (iters == 0) return FOS_OK;
-  {
-    int rc = stage();
-    if (rc) return rc;
-    b16 = rhs ? p->b16 : nullptr;
-  }
+  int rc = stage();
+  if (rc) return rc;
   // workspace: nv interleaved slab sets and rr partials per workgroup
   const int nwg = p->nwg;
-  if (nwg * nv > p->slab_cap) {
-    if (p->slabs) (void)hipFree(p->slabs);
-    p->slabs = nullptr;
-    p->slab_cap = 0;
-    HIP_TRY(hipMalloc(&p->slabs, (size_t)nwg * nv * p->n * sizeof(float)));
-    p->slab_cap = nwg * nv;
-  }
-  if (nwg * nv > p->rr_cap) {
-    if (p->rr_part) (void)hipFree(p->rr_part);
-    if (p->rr2_part) (void)hipFree(p->rr2_part);
-    p->rr_part = p->rr2_part = nullptr;
-    p->rr_cap = 0;
-    HIP_TRY(hipMalloc(&p->rr_part, (size_t)nwg * nv * sizeof(double)));
-    HIP_TRY(hipMalloc(&p->rr2_part, (size_t)nwg * nv * sizeof(double)));
-    p->rr_cap = nwg * nv;
-  }
+  if ((rc = grow(&p->slab_cap, nwg * nv, (size_t)p->n * sizeof(float), &p->slabs))) return rc;
+  if ((rc = grow(&p->rr_cap, nwg * nv, sizeof(double), &p->rr_part, &p->rr2_part))) return rc;
   fos::MultiY ys{};
   ys.stopped = nullptr;
   for (int v = 0; v < nv; ++v) {
     fos_fista* f = fs[v];
-    int rc = flush_pending(f);
-    if (rc) return rc;
     bool stopped = false;
-    if ((rc = refresh_host_scalars(f, &stopped))) return rc;
+    if ((rc = begin_plain(f, &stopped))) return rc;
     if (stopped) return fail(FOS_ERR_STATE, "fos_fista_run_multi: a handle has already stopped");
-    if (!f->y_valid) {
-      hipLaunchKernelGGL(fos::form_y_kernel, dim3(grid_1d(p->n, 256, 256)), dim3(256), 0, p->stream, f->x_cur, f->x_prev,
-                         f->h_beta, f->ynext, p->n);
-      LAUNCH_CHECK();
-      f->y_valid = true;
-    }
+    if ((rc = ensure_y(f))) return rc;
     ys.y[v] = f->ynext;
   }
   for (int v = nv; v < 4; ++v) ys.y[v] = ys.y[0];
-  const size_t psz = (size_t)fs[0]->nupd * 4;
   for (int it = 0; it < iters; ++it) {
-    int rc = prof_mark(p, true);
-    if (rc) return rc;
-    fn((const float*)p->A, p->lda, rhs ? b16 : p->b, p->m, (int)p->n, ys, p->rows_per_wg, p->slabs, p->rr_part, nwg, p->stream);
+    if ((rc = prof_mark(p, true))) return rc;
+    fn((const float*)p->A, p->lda, rhs ? p->b16 : p->b, p->m, (int)p->n, ys, p->rows_per_wg, p->slabs, p->rr_part, nwg, p->stream);
     LAUNCH_CHECK();
     if ((rc = prof_mark(p, false))) return rc;
     for (int v = 0; v < nv; ++v) {
-      fos_fista* f = fs[v];
-      const double beta_k = f->h_beta;
-      host_momentum(f->prm, f->h_k, &f->h_t, &f->h_beta);
-      launch_update_from_slabs(f, f->part2 + (size_t)(f->h_k & 1) * psz, 1, beta_k, nullptr, f->ynext, f->h_beta,
-                               p->slabs + (size_t)v * p->n, (int64_t)nv * p->n);
-      LAUNCH_CHECK();
-      f->h_k += 1;
-      f->plain_count += 1;
+      const PlainStep s = advance_plain(fs[v], true);
+      if ((rc = launch_update_from_slabs(fs[v], s.part, 1, s.beta, nullptr, fs[v]->ynext, s.beta_next, p->slabs + (size_t)v * p->n,
+                                         (int64_t)nv * p->n)))
+        return rc;
     }
   }
-  for (int v = 0; v < nv; ++v) {
-    fos_fista* f = fs[v];
-    f->pending = false;
-    const long long last = f->h_k - 1;
-    const double* cur = f->part2 + (size_t)(last & 1) * psz;
-    const double* prev = f->plain_count >= 2 ? f->part2 + (size_t)((last - 1) & 1) * psz : nullptr;
-    hipLaunchKernelGGL(fos::fista_finalize_plain_kernel, dim3(1), dim3(64), 0, p->stream, cur, prev, f->nupd, p->rr_part, 0,
-                       f->scal, f->h_t, f->h_beta, f->h_k);
-    LAUNCH_CHECK();
-  }
+  for (int v = 0; v < nv; ++v)
+    if ((rc = finish_part2(fs[v], 0))) return rc;
   return FOS_OK;
 }
 
@@ -1093,40 +970,14 @@ int fos_fista_grad_dual(fos_fista* f) {
 int fos_fista_update(fos_fista* f) {
   if (!f) return fail(FOS_ERR_ARG, "fos_fista_update: null");
   fos_problem* p = f->p;
-  const bool plain = plain_run(f) && f->host_valid && !p->col_sharded;
-  double* part = p->part;
-  int host_beta = 0;
-  double beta_k = 0.0, beta_next = 0.0;
-  float* y_next = nullptr;
-  if (plain) {
+  if (plain_run(f) && f->host_valid && !p->col_sharded) {
     // host-driven momentum (see fos_fista_run): no per-iteration bookkeeping launch, y handed on as one fp32 vector
-    beta_k = f->h_beta;
-    host_momentum(f->prm, f->h_k, &f->h_t, &f->h_beta);
-    beta_next = f->h_beta;
-    part = f->part2 + (size_t)(f->h_k & 1) * (size_t)f->nupd * 4;
-    host_beta = 1;
-    y_next = f->ynext;
+    const PlainStep s = advance_plain(f, true);
+    return launch_update(f, nullptr, 0, grad_src(f), f->prm, s.part, 1, s.beta, nullptr, f->ynext, s.beta_next);
   }
-  if (p->vec4)
-    hipLaunchKernelGGL((fos::fista_update_kernel<false, true>), dim3(f->nupd), dim3(256), 0, p->stream,
-                       (const float*)nullptr, 0, grad_src(f), (int)p->n, f->x_cur, f->x_prev, f->scal, f->prm, part, host_beta,
-                       beta_k, (double*)nullptr, y_next, beta_next);
-  else
-    hipLaunchKernelGGL((fos::fista_update_kernel<false, false>), dim3(f->nupd), dim3(256), 0, p->stream,
-                       (const float*)nullptr, 0, grad_src(f), (int)p->n, f->x_cur, f->x_prev, f->scal, f->prm, part, host_beta,
-                       beta_k, (double*)nullptr, y_next, beta_next);
-  LAUNCH_CHECK();
-  if (plain) {
-    f->h_k += 1;
-    f->plain_count += 1;
-    f->y_valid = true;
-    f->pending = true;
-    return FOS_OK;
-  }
-  f->host_valid = false;
-  f->y_valid = false;
-  f->plain_count = 0;
-  return launch_finalize(f, 0);
+  hand_to_device(f);
+  int rc = launch_update(f, nullptr, 0, grad_src(f), f->prm, p->part, 0, 0.0, nullptr, nullptr, 0.0);
+  return rc ? rc : launch_finalize(f, 0);
 }
 
 int fos_fista_trial(fos_fista* f, double t, int with_residual, double out8[8]) {
@@ -1193,9 +1044,7 @@ static int run_device_driven(fos_fista* f, int iters, bool backtracking, double 
       f->tau_on_device = true;
     }
   }
-  f->host_valid = false;                       // t_k, beta_k depend on nothing the host knows any more
-  f->y_valid = false;
-  f->plain_count = 0;
+  hand_to_device(f);
   fos::FistaParams prm_dev = f->prm;
   prm_dev.tau_from_state = backtracking ? 1 : 0;
   const bool record = hist != nullptr;
@@ -1218,15 +1067,7 @@ static int run_device_driven(fos_fista* f, int iters, bool backtracking, double 
     }
     // update (with the step the decision left in FistaScalars::tau), then the scalar bookkeeping / history row
     double* xrow = x_hist ? x_hist + (size_t)it * p->n : nullptr;
-    if (p->vec4)
-      hipLaunchKernelGGL((fos::fista_update_kernel<false, true>), dim3(f->nupd), dim3(256), 0, p->stream,
-                         (const float*)nullptr, 0, grad_src(f), (int)p->n, f->x_cur, f->x_prev, f->scal, prm_dev, p->part, 0,
-                         0.0, xrow, (float*)nullptr, 0.0);
-    else
-      hipLaunchKernelGGL((fos::fista_update_kernel<false, false>), dim3(f->nupd), dim3(256), 0, p->stream,
-                         (const float*)nullptr, 0, grad_src(f), (int)p->n, f->x_cur, f->x_prev, f->scal, prm_dev, p->part, 0,
-                         0.0, xrow, (float*)nullptr, 0.0);
-    LAUNCH_CHECK();
+    if ((rc = launch_update(f, nullptr, 0, grad_src(f), prm_dev, p->part, 0, 0.0, xrow, nullptr, 0.0))) return rc;
     if ((rc = launch_finalize(f, 0, record ? hist + (size_t)it * 4 : nullptr))) return rc;
   }
   return FOS_OK;

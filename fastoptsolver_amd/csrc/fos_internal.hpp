@@ -52,6 +52,24 @@ inline int fail(int code, const std::string& msg) {
     if (e_ != hipSuccess) return fail(FOS_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e_)); \
   } while (0)
 
+// Device buffers that grow with demand: when `need` exceeds *cap, a (and b, sized alike) are freed and reallocated to exactly
+// need * unit bytes.  A failed allocation leaves *cap = 0, so the next call tries again.
+template <class T>
+int grow(int* cap, int64_t need, size_t unit, T** a, T** b = nullptr) {
+  if (need <= *cap) return FOS_OK;
+  T** bufs[] = {a, b};
+  for (T** q : bufs)
+    if (q && *q) {
+      (void)hipFree(*q);
+      *q = nullptr;
+    }
+  *cap = 0;
+  for (T** q : bufs)
+    if (q) HIP_TRY(hipMalloc(q, (size_t)need * unit));
+  *cap = (int)need;
+  return FOS_OK;
+}
+
 
 using fos::YSource;
 
@@ -218,18 +236,31 @@ struct fos_problem {
   int64_t prof_launches = 0;
 };
 
+// The momentum scalars t_k, beta_k and the count k live in FistaScalars on the device.  Plain runs (no adaptive restart, no
+// stopping tolerance) follow a momentum sequence that does not depend on the data, so the host keeps a mirror of them and
+// passes beta_k to the kernels by value; the scalar bookkeeping then runs once per call instead of once per iteration.
+//   host_valid   h_t, h_beta, h_k are t_k, beta_k, k.  False once a run with data-dependent control (device-driven,
+//                resident, controlled lockstep, non-plain split mode) has advanced the device scalars; the next plain run
+//                reads them back once (one synchronisation).
+//   pending      plain iterations have run whose bookkeeping (fista_finalize_plain_kernel) has not: the device scalars are
+//                behind the mirror.  Every other entry point flushes first; a plain fos_fista_run closes them with its own
+//                iterations.
+//   plain_count  consecutive plain iterations whose step partials sit in part2 (slot k & 1); the closing bookkeeping reads the
+//                previous step from part2 only when there are two.
+//   y_valid      ynext holds y_{h_k} in fp32 (written by the previous update); otherwise the next pass forms y from x_k,
+//                x_{k-1} and h_beta - bit-identical either way.
+// fos_fista.hip assigns these fields only in its mirror helpers (begin_plain ... hand_to_device) and in create / reset.
 struct fos_fista {
   fos_problem* p = nullptr;
   fos::FistaParams prm{};
-  // host mirror of the momentum scalars, valid while only plain fos_fista_run calls advance the state
   bool host_valid = false;
   double h_t = 1.0, h_beta = 0.0;
   long long h_k = 0;
   double* part2 = nullptr;           // ping-pong partials for plain runs: 2 * nupd * 4 doubles
   float* ynext = nullptr;            // plain runs: y_{k+1} in fp32 written by the update kernel
-  bool y_valid = false;              // ynext holds y for iteration h_k
-  bool pending = false;              // plain split-mode updates whose scalar bookkeeping has not run yet
-  long long plain_count = 0;         // consecutive plain iterations whose partials sit in part2
+  bool y_valid = false;
+  bool pending = false;
+  long long plain_count = 0;
   double *x_cur = nullptr, *x_prev = nullptr;   // fp64 iterate state
   float* dlt = nullptr;                         // trial difference vector x_tmp - y_k (fp32)
   fos::FistaScalars* scal = nullptr;
@@ -254,6 +285,10 @@ int epc_of(int dtype);
 int grid_1d(int64_t n, int per_block, int cap);
 void plan_fused(fos_problem* p, const MenuEntry* e, int nwg_hint);
 void apply_plan(fos_problem* p, unsigned flags);
+// Layout of the matrix-core lockstep (run_multi_mfma), planned on first use: the one-read cluster form or two products per row
+// panel; fills cp_*, panel_rows, gram_* and allocates their buffers.  no_cluster: the cluster launch was refused - two
+// products from now on.
+int plan_multi_mfma(fos_problem* p, bool no_cluster = false);
 int ensure_workspace(fos_problem* p);
 int ensure_batch_workspace(fos_problem* p);
 int ensure_dd(fos_problem* p);

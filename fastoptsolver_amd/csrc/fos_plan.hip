@@ -345,24 +345,10 @@ void plan_fallback(fos_problem* p) {
 }
 
 int ensure_workspace(fos_problem* p) {
-  const int need_slabs = p->nslabs;
-  if (need_slabs > p->slab_cap) {
-    if (p->slabs) (void)hipFree(p->slabs);
-    p->slabs = nullptr;
-    p->slab_cap = 0;
-    HIP_TRY(hipMalloc(&p->slabs, (size_t)need_slabs * (p->slab_stride ? p->slab_stride : p->n) * sizeof(float)));
-    p->slab_cap = need_slabs;
-  }
+  int rc = grow(&p->slab_cap, p->nslabs, (size_t)(p->slab_stride ? p->slab_stride : p->n) * sizeof(float), &p->slabs);
+  if (rc) return rc;
   const int need_rr = std::max(std::max(p->nwg, p->colblock ? 256 : 1), std::max(p->resid_grid, 1));
-  if (need_rr > p->rr_cap) {
-    if (p->rr_part) (void)hipFree(p->rr_part);
-    if (p->rr2_part) (void)hipFree(p->rr2_part);
-    p->rr_part = p->rr2_part = nullptr;
-    p->rr_cap = 0;
-    HIP_TRY(hipMalloc(&p->rr_part, (size_t)need_rr * sizeof(double)));
-    HIP_TRY(hipMalloc(&p->rr2_part, (size_t)need_rr * sizeof(double)));
-    p->rr_cap = need_rr;
-  }
+  if ((rc = grow(&p->rr_cap, need_rr, sizeof(double), &p->rr_part, &p->rr2_part))) return rc;
   if (p->path == 1 && p->rvec == nullptr) HIP_TRY(hipMalloc(&p->rvec, (size_t)p->m * sizeof(double)));
   if (p->colblock && p->rneg == nullptr) {
     HIP_TRY(hipMalloc(&p->rneg, (size_t)p->m * sizeof(float)));
@@ -867,6 +853,61 @@ void apply_plan(fos_problem* p, unsigned flags) {
       p->colblock = true;
     } else plan_fallback(p);
   } else plan_fallback(p);
+}
+
+// Up to 16 state machines in lockstep on the matrix cores (run_multi_mfma).
+// One-read form (cluster_pass.hpp): fp32, 2049..16384 columns in strips of 1024 -> 4, 8 or 16 members per cluster, all CUs
+// busy, at least 8 panels per cluster; FOS_PLAN_CLUSTER / FOS_PLAN_NO_CLUSTER force it on (where served) / off.
+// Planner default (profiles/r03_cluster_crossover.md, 16 weights, us per iteration, two products -> one read): the one-read
+// form wins where every member of a cluster has a full 1024-column strip and the matrix is large - 131072 x 4096 826 -> 640,
+// 524288 x 4096 3306 -> 2407, 65536 x 8192 670 -> 643, 262144 x 8192 2668 -> 2430 - ties at 32768 x 8192 and loses with
+// idle members (6144 columns +10 %, 3072 +5 %) and at 16 members (131072 x 16384 +5 %).
+int plan_multi_mfma(fos_problem* p, bool no_cluster) {
+  if (no_cluster) {
+    p->cp_cs = 0;
+    p->cp_mode = 2;
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    (void)hipFree(p->rbuf16); (void)hipFree(p->slabs16);       // sized for the cluster form
+    p->rbuf16 = p->slabs16 = nullptr;
+  }
+  if (p->rbuf16) return FOS_OK;
+  const bool is_bf16 = p->dtype == FOS_BF16;
+  const int cs_need = (int)((p->n + fos::CP_W - 1) / fos::CP_W);
+  const bool cluster_wins = (p->n == 4096 || p->n == 8192) && p->m * p->n >= (1ll << 29) && !p->comm;
+  const bool want_cluster = p->cp_mode == 1 || (p->cp_mode == 0 && cluster_wins);
+  if (want_cluster && !is_bf16 && p->ncu % 8 == 0) {
+    const int cs = cs_need <= 2 ? 0 : cs_need <= 4 ? 4 : cs_need <= 8 ? 8 : cs_need <= 16 ? 16 : 0;
+    if (cs && (p->ncu / 8) % cs == 0 && p->m >= (int64_t)(p->ncu / cs) * fos::CP_ROWS * 8) {
+      p->cp_cs = cs;
+      p->cp_clusters = p->ncu / cs;
+      p->cp_rows_per_cluster = ((p->m + p->cp_clusters - 1) / p->cp_clusters + fos::CP_ROWS - 1) / fos::CP_ROWS * fos::CP_ROWS;
+      HIP_TRY(hipMalloc(&p->cp_xchg, (size_t)p->ncu * fos::CP_SLOTS * 256 * sizeof(float)));
+      HIP_TRY(hipMalloc(&p->cp_flags, (size_t)p->ncu * fos::CP_FLAG_STRIDE * sizeof(unsigned)));
+      HIP_TRY(hipMemsetAsync(p->cp_flags, 0, (size_t)p->ncu * fos::CP_FLAG_STRIDE * sizeof(unsigned), p->stream));
+      HIP_TRY(hipMalloc(&p->cp_error, sizeof(int)));
+      HIP_TRY(hipMemsetAsync(p->cp_error, 0, sizeof(int), p->stream));
+    }
+  }
+  // Panel: product 1 gives a workgroup 64-128 whole rows, so it needs >= 128 * CUs * 2 rows to fill the chip; row splits of
+  // product 2: enough (strip, split) workgroups for two per CU.  (A panel that fits the Infinity Cache - ~3000 rows at
+  // n = 8192 - would need a split-K product 1; see DESIGN.md "Multi-lambda".)
+  const int64_t rows = 256 * (int64_t)p->ncu;
+  p->panel_rows = std::min<int64_t>(rows, (p->m + 255) / 256 * 256);
+  if (p->col_sharded && p->comm->kind != 0) {          // mesh transport: a panel's 16 residual columns are one message
+    const int64_t fit = (int64_t)(p->comm->cap_bytes / (fos::BT_NV * sizeof(float))) / 256 * 256;
+    if (fit < 256) return fail(FOS_ERR_ARG, "fos_fista_run_multi: the communicator's inbox rows hold less than one 256-row "
+                                            "panel of 16 residual columns (16 KiB)");
+    p->panel_rows = std::min<int64_t>(p->panel_rows, fit);
+  }
+  const int64_t strips = (p->n + (is_bf16 ? fos::GQ_COLS : fos::GB_COLS) - 1) / (is_bf16 ? fos::GQ_COLS : fos::GB_COLS);
+  int64_t splits = std::max<int64_t>(1, (2 * (int64_t)p->ncu + strips - 1) / strips);
+  splits = std::min<int64_t>(splits, std::max<int64_t>(1, p->panel_rows / 256));
+  p->gram_rows_per_split = ((p->panel_rows + splits - 1) / splits + fos::GB_ROWS - 1) / fos::GB_ROWS * fos::GB_ROWS;
+  p->gram_splits = (int)((p->panel_rows + p->gram_rows_per_split - 1) / p->gram_rows_per_split);
+  if (p->cp_cs) p->gram_splits = p->cp_clusters;      // one slab set per cluster
+  HIP_TRY(hipMalloc(&p->rbuf16, (size_t)p->panel_rows * fos::BT_NV * sizeof(float)));
+  HIP_TRY(hipMalloc(&p->slabs16, (size_t)p->gram_splits * fos::BT_NV * p->n * sizeof(float)));
+  return FOS_OK;
 }
 
 // ---- fp64-accumulating pass (L-BFGS fg) -----------------------------------------------------------------------------
@@ -1510,13 +1551,8 @@ int fos_power_iter(fos_problem* p, float* v_inout, int n_iter, double tol, doubl
   if (!p || !v_inout || !L_out || n_iter <= 0) return fail(FOS_ERR_ARG, "fos_power_iter: bad argument");
   if (p->col_sharded)
     return fail(FOS_ERR_UNSUPPORTED, "fos_power_iter: column-sharded problems normalise over the ranks (see _lipschitz_cols)");
-  if (n_iter + 1 > p->lhist_cap) {             // L after every step (+ the norm of v0): sized by the caller's n_iter
-    if (p->lhist) (void)hipFree(p->lhist);
-    p->lhist = nullptr;
-    p->lhist_cap = 0;
-    HIP_TRY(hipMalloc(&p->lhist, (size_t)(n_iter + 1) * sizeof(double)));
-    p->lhist_cap = n_iter + 1;
-  }
+  // L after every step (+ the norm of v0): sized by the caller's n_iter
+  if (int rc = grow(&p->lhist_cap, n_iter + 1, sizeof(double), &p->lhist)) return rc;
   double* Lh = p->lhist;        // n_iter + 1 slots
   if (p->resident) {
     // all iterations in one launch; the break rule (:57) is evaluated on the device

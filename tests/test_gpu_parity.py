@@ -1238,6 +1238,78 @@ def test_resident_loop_and_split_entry_points_share_one_state(fos):
         assert _data.rel(st.x_tensor().cpu().numpy(), x_ref) < TOL, mode
 
 
+@pytest.mark.parametrize("mode", ["fista", "delta"])
+def test_plain_run_forms_share_one_momentum_state(fos, mode):
+    """A streaming plan driven through a mix of entry points - plain run, grad()/update() leaving their bookkeeping
+    pending, status(), the recorded DUAL run, plain run again - is the uninterrupted 18-iteration run and the oracle."""
+    from fastoptsolver_amd import _core, _lib
+    A, b, fx = _data.problem("aligned")
+    lam = float(np.max(np.abs(A.T @ b)))
+    L = float(fx["aligned/L"])
+    a1, a2 = 0.1 * lam, 0.5
+    prob = fos.prepare(A, b)
+    plan = prob.plan()
+    assert plan["resident"] == 0 and plan["path"] == 0, plan
+    md, delta = (_lib.MODE_FISTA, 0.0) if mode == "fista" else (_lib.MODE_DELTA, 3.0)
+
+    def handle():
+        st = _core.Fista(prob)
+        st.reset(1.0 / (L + a2), a1, a2, mode=md, prox_kind=_lib.PROX_L1, delta=delta)
+        return st
+
+    mixed, whole = handle(), handle()
+    mixed.run(5)
+    for _ in range(3):
+        mixed.grad()
+        mixed.update()
+    assert int(mixed.status().k) == 8
+    assert mixed.run_history(4) is not None
+    mixed.run(6)
+    whole.run(18)
+    assert int(mixed.status().k) == 18 and int(whole.status().k) == 18
+    x_mixed, x_whole = mixed.x_tensor().cpu().numpy(), whole.x_tensor().cpu().numpy()
+    if mode == "fista":
+        x_ref = orc.fista(A, b, "elasticnet", a1, a2, max_iter=18, L=L)
+    else:
+        x_ref = orc.fista_delta(A, b, "elasticnet", a1, a2, delta, max_iter=18, L=L)
+    assert _data.rel(x_mixed, x_whole) < 1e-6
+    assert _data.rel(x_mixed, x_ref) < TOL
+
+
+@pytest.mark.parametrize("m,n", [(4096, 512), (2000, 128)])
+def test_lockstep_continues_single_runs(fos, m, n):
+    """Four handles run 3 iterations on their own, then 5 in lockstep: each equals its own uninterrupted 8-iteration run.
+    4096 x 512 takes the VALU multi-vector kernel, 2000 x 128 (chunk-per-lane rows) the matrix-core form."""
+    from fastoptsolver_amd import _core, _lib
+    A, b, _ = _data.synth(m, n, 91 + n)
+    At = torch.as_tensor(A.astype(np.float32)).cuda()
+    A = At.to(torch.float64).cpu().numpy()
+    b = b.astype(np.float32).astype(np.float64)
+    prob = fos.prepare(At, b.astype(np.float32))
+    plan = prob.plan()
+    assert plan["path"] == 0 and plan["resident"] == 0 and plan["tall"] == (n <= 128), plan   # tall: no VALU multi kernel
+    lam = float(np.max(np.abs(A.T @ b)))
+    L = float(np.linalg.norm(A, 2) ** 2)
+    alphas = [(lam * 0.3 * 0.6 ** i, 0.5 if i % 2 else 0.0) for i in range(4)]
+
+    def handle(a1, a2):
+        st = _core.Fista(prob)
+        st.reset(1.0 / (L + a2), a1, a2, mode=_lib.MODE_FISTA, prox_kind=_lib.PROX_L1)
+        return st
+
+    hs = [handle(a1, a2) for a1, a2 in alphas]
+    for st in hs:
+        st.run(3)
+    assert _core.run_multi(hs, 5)
+    for (a1, a2), st in zip(alphas, hs):
+        one = handle(a1, a2)
+        one.run(8)
+        assert int(st.status().k) == 8
+        x = st.x_tensor().cpu().numpy()
+        assert _data.rel(x, one.x_tensor().cpu().numpy()) < 1e-6, (a1, a2)
+        assert _data.rel(x, orc.fista(A, b, "elasticnet", a1, a2, max_iter=8, L=L)) < TOL, (a1, a2)
+
+
 def test_resident_run_reports_stops_steps_and_counts(fos):
     from fastoptsolver_amd import _core, _lib
     A, b, fx = _data.problem("tiny")
