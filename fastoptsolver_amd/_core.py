@@ -580,3 +580,67 @@ def run_multi_rhs(handles, B, iters):
         return False
     _lib.check(rc, "fos_fista_run_multi_rhs")
     return True
+
+
+# ---- batches of small problems (fos_fista_run_batch / fos_power_iter_batch) -------------------------------------------
+RS_MAX_N, RS_MAX_M, RS_MAX_A = 64, 4096, 10240        # csrc/resident.hpp
+
+
+def resident_fits(m, n):
+    """The LDS-resident limits of csrc/resident.hpp (resident_fits): n <= 64, m <= 4096, m * (n | 1) <= 10240."""
+    return 1 <= n <= RS_MAX_N and 1 <= m <= RS_MAX_M and m * (n | 1) <= RS_MAX_A
+
+
+def batch_items(shapes):
+    """ctypes array of fos_batch_item from (a_offset, lda, b_offset, m, n) tuples."""
+    arr = (_lib.BatchItem * max(len(shapes), 1))()
+    for i, (ao, lda, bo, m, n) in enumerate(shapes):
+        arr[i].a_offset, arr[i].lda, arr[i].b_offset, arr[i].m, arr[i].n = int(ao), int(lda), int(bo), int(m), int(n)
+    return arr
+
+
+def power_iter_batch(A, dtype, shapes, V, n_iter=100, tol=1e-6):
+    """fos_power_iter of every problem in one launch: A a device buffer of the problems' elements (dtype "f32" / "bf16"),
+    shapes (a_offset, lda, b_offset, m, n) per problem, V (P x ldv float32 device) the start vectors (overwritten).
+    Returns (L, iterations) as host lists.  Synchronises."""
+    lib = _lib.load()
+    P = len(shapes)
+    if P == 0:
+        return [], []
+    dev = A.device
+    L = torch.empty(P, dtype=torch.float64, device=dev)
+    used = torch.empty(P, dtype=torch.int32, device=dev)
+    work = torch.empty((P * C.sizeof(_lib.BatchItem) + 7) // 8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.fos_power_iter_batch(ptr(A), _lib.FOS_BF16 if dtype == "bf16" else _lib.FOS_F32, batch_items(shapes),
+                                            P, ptr(V), int(V.stride(0)), int(n_iter), float(tol), ptr(L), ptr(used),
+                                            ptr(work), stream_ptr()), "fos_power_iter_batch")
+        return L.cpu().tolist(), used.cpu().tolist()
+
+
+def run_batch(A, dtype, B, shapes, params, iters, *, backtracking=False, eta=0.5, armijo_c=1e-2, ldx, record=False):
+    """fos_fista_run_batch: every problem from x = 0 for up to `iters` iterations, one workgroup each.  A / B: device
+    buffers of the problems' elements / right-hand sides; shapes (a_offset, lda, b_offset, m, n) and params (FistaParams)
+    per problem.  Returns dict of device tensors x [P, ldx], done [P], stopped [P], tau [P], ls [P, iters], taus [P, iters]
+    (and with record: x_hist [P, iters, ldx], hist [P, iters, 4]).  Enqueues only."""
+    lib = _lib.load()
+    P, dev, it1 = len(shapes), A.device, max(int(iters), 1)
+    out = dict(x=torch.zeros(P, ldx, dtype=torch.float64, device=dev),
+               done=torch.zeros(P, dtype=torch.int32, device=dev), stopped=torch.zeros(P, dtype=torch.int32, device=dev),
+               tau=torch.zeros(P, dtype=torch.float64, device=dev),
+               ls=torch.zeros(P, it1, dtype=torch.int32, device=dev), taus=torch.zeros(P, it1, dtype=torch.float64, device=dev))
+    if record:
+        out["x_hist"] = torch.zeros(P, it1, ldx, dtype=torch.float64, device=dev)
+        out["hist"] = torch.zeros(P, it1, 4, dtype=torch.float64, device=dev)
+    if P == 0:
+        return out
+    prm = (_lib.FistaParams * P)(*params)
+    work = torch.empty((lib.fos_fista_batch_workspace(P, int(ldx)) + 7) // 8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.fos_fista_run_batch(ptr(A), _lib.FOS_BF16 if dtype == "bf16" else _lib.FOS_F32, ptr(B),
+                                           batch_items(shapes), prm, P, int(iters), int(bool(backtracking)), float(eta),
+                                           float(armijo_c), int(ldx), ptr(out["x"]), ptr(out["done"]), ptr(out["stopped"]),
+                                           ptr(out["tau"]), ptr(out["ls"]), ptr(out["taus"]), ptr(out.get("hist")),
+                                           ptr(out.get("x_hist")), ptr(work), stream_ptr()), "fos_fista_run_batch")
+    out["_work"] = work              # alive until the caller has synchronised
+    return out

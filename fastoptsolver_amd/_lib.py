@@ -30,6 +30,11 @@ class LbfgsResult(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class BatchItem(C.Structure):
+    """fos_batch_item: one problem of a batch (offsets in elements)."""
+    _fields_ = [("a_offset", C.c_int64), ("lda", C.c_int64), ("b_offset", C.c_int64), ("m", C.c_int32), ("n", C.c_int32)]
+
+
 LS_FG, LS_CONVERGENCE, LS_WARNING, LS_ERROR = 0, 1, 2, 3
 
 
@@ -126,6 +131,10 @@ SIGNATURES = {
     "fos_gemv_pair_dd_multi": (_i32, [_vp, _vp, _i32, _i64, _vp, _i64, _f64, _vp, _vp]),
     "fos_lbfgs_minimize_multi": (_i32, [_vp, _i32, _vp, _i64, _f64, _i32, _f64, _vp, _i64, C.POINTER(_f64),
                                         C.POINTER(C.c_float), _i32, C.POINTER(_i32), C.POINTER(LbfgsResult)]),
+    "fos_fista_batch_workspace": (_i64, [_i32, _i64]),
+    "fos_fista_run_batch": (_i32, [_vp, _i32, _vp, C.POINTER(BatchItem), C.POINTER(FistaParams), _i32, _i32, _i32, _f64,
+                                   _f64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fos_power_iter_batch": (_i32, [_vp, _i32, C.POINTER(BatchItem), _i32, _vp, _i64, _i32, _f64, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1159,4 +1159,76 @@ int fos_fista_get_x(fos_fista* f, double* dst) {
 double* fos_fista_x(fos_fista* f) { return f ? f->x_cur : nullptr; }
 float* fos_fista_gbuf(fos_fista* f) { return f ? f->p->gbuf : nullptr; }
 
+// ---- batches of small problems: one workgroup per problem, one launch per SMALL class (resident_batch.hpp) ----------
+int64_t fos_fista_batch_workspace(int count, int64_t ldx) {
+  if (count < 0 || ldx < 1) return -1;
+  return (int64_t)count * ((int64_t)sizeof(fos::ResidentBatchDesc) + (int64_t)sizeof(fos::FistaScalars) +
+                           ldx * (int64_t)sizeof(double));
+}
+
+int fos_fista_run_batch(const void* A, int a_dtype, const float* b, const fos_batch_item* items, const fos_fista_params* prm,
+                        int count, int iters, int backtracking, double eta, double armijo_c, int64_t ldx, double* x_out,
+                        int32_t* iters_done, int32_t* stopped, double* tau_out, int32_t* ls_iters, double* tau_hist,
+                        double* hist, double* x_hist, void* work, void* stream) {
+  if (count < 0 || iters < 0 || (backtracking && !(eta > 0.0 && eta < 1.0)) || (a_dtype != FOS_F32 && a_dtype != FOS_BF16))
+    return fail(FOS_ERR_ARG, "fos_fista_run_batch: bad argument (count < 0, iters < 0, eta outside (0, 1) or a_dtype)");
+  if (count == 0) return FOS_OK;
+  if (!A || !b || !items || !prm || !x_out || !iters_done || !stopped || !tau_out || !work || ldx < 1)
+    return fail(FOS_ERR_ARG, "fos_fista_run_batch: bad argument (null pointer or ldx < 1)");
+  if (int rc = check_batch_items("fos_fista_run_batch", items, count, ldx)) return rc;
+  int n_small = 0;
+  for (int i = 0; i < count; ++i) {
+    const fos_fista_params& q = prm[i];
+    if (q.mode < 0 || q.mode > 2 || q.prox_kind < 0 || q.prox_kind > 1 || !(q.tau > 0.0) || q.tol_grad < 0.0 ||
+        q.tol_step < 0.0 || q.tol_ratio < 0.0)
+      return fail(FOS_ERR_ARG, "fos_fista_run_batch: bad argument (prm " + std::to_string(i) +
+                                   ": mode / prox_kind / tau / tolerance)");
+    n_small += items[i].n <= fos::RS_CHUNK && items[i].m <= fos::RS_SMALL_M;
+  }
+  // SMALL problems (rows of A in registers: run_resident's rule) at [0, n_small), the others after them, each class one
+  // launch over its own range
+  std::vector<fos::ResidentBatchDesc> d(count);
+  for (int i = 0, s = 0, l = n_small; i < count; ++i) {
+    const fos_batch_item& it = items[i];
+    fos::ResidentBatchDesc& e = d[it.n <= fos::RS_CHUNK && it.m <= fos::RS_SMALL_M ? s++ : l++];
+    e.a_offset = it.a_offset;
+    e.lda = it.lda;
+    e.b_offset = it.b_offset;
+    e.m = it.m;
+    e.n = it.n;
+    e.idx = i;
+    e.pad_ = 0;
+    to_dev_params(&prm[i], &e.prm);
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  auto* desc = reinterpret_cast<fos::ResidentBatchDesc*>(work);
+  fos::ResidentBatchOut o{};
+  o.ldx = ldx;
+  o.x_out = x_out;
+  o.iters_done = iters_done;
+  o.stopped = stopped;
+  o.tau_final = tau_out;
+  o.ls_out = ls_iters;
+  o.tau_out = tau_hist;
+  o.hist = hist;
+  o.x_hist = x_hist;
+  o.scal = reinterpret_cast<fos::FistaScalars*>(desc + count);
+  o.x_prev = reinterpret_cast<double*>(o.scal + count);
+  HIP_TRY(hipMemcpyAsync(desc, d.data(), (size_t)count * sizeof(fos::ResidentBatchDesc), hipMemcpyHostToDevice, st));
+#define FOS_RSB_LAUNCH(T, SMALL, G, D)                                                                                   \
+  hipLaunchKernelGGL((fos::fista_resident_batch_kernel<T, SMALL>), dim3(G), dim3(fos::RS_THREADS), 0, st,               \
+                     (const T*)A, b, D, iters, backtracking ? 1 : 0, eta, armijo_c, o)
+  const int n_large = count - n_small;
+  if (a_dtype == FOS_F32) {
+    if (n_small) FOS_RSB_LAUNCH(float, true, n_small, desc);
+    if (n_large) FOS_RSB_LAUNCH(float, false, n_large, desc + n_small);
+  } else {
+    if (n_small) FOS_RSB_LAUNCH(fos::bf16_t, true, n_small, desc);
+    if (n_large) FOS_RSB_LAUNCH(fos::bf16_t, false, n_large, desc + n_small);
+  }
+#undef FOS_RSB_LAUNCH
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
 }  // extern "C"

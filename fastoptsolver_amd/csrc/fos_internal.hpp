@@ -30,6 +30,7 @@
 #include "lbfgs_kernels.hpp"
 #include "reduce_update.hpp"
 #include "resident.hpp"
+#include "resident_batch.hpp"
 
 
 namespace fosapi {
@@ -324,5 +325,21 @@ int pair_dd_multi(fos_problem* p, const fos::DdMultiCols& c, int ncols, unsigned
 int comm_allreduce(fos_comm* c, void* buf, size_t count, bool f64, hipStream_t st);
 // sum `count` floats / doubles over the ranks of a sharded problem, in place, on the handle's stream (no-op otherwise)
 int reduce_across(fos_problem* p, void* buf, size_t count, bool f64);
+
+// ---- batches of small problems (fos_fista_run_batch, fos_power_iter_batch) -------------------------------------------
+// The descriptor checks both entry points make before any HIP call: FOS_ERR_ARG for a negative offset, lda < n or n > ld
+// (ld: the caller's stride of the per-problem n-vectors), FOS_ERR_UNSUPPORTED outside the LDS-resident limits.
+inline int check_batch_items(const char* fn, const fos_batch_item* items, int count, int64_t ld) {
+  for (int i = 0; i < count; ++i) {
+    const fos_batch_item& it = items[i];
+    if (it.a_offset < 0 || it.b_offset < 0 || it.n < 1 || it.m < 1 || it.lda < it.n || it.n > ld)
+      return fail(FOS_ERR_ARG, std::string(fn) + ": bad argument (item " + std::to_string(i) +
+                                   ": negative offset, empty shape, lda < n or n > the vector stride)");
+    if (!fos::resident_fits(it.m, it.n))
+      return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": item " + std::to_string(i) +
+                                           " does not fit the LDS-resident loop (n <= 64, m <= 4096, m * (n | 1) <= 10240)");
+  }
+  return FOS_OK;
+}
 
 }  // namespace fosapi

@@ -1647,4 +1647,26 @@ int fos_prox_elastic_net_vec(const float* v, const float* tau, float alpha1, flo
   return FOS_OK;
 }
 
+// One power iteration per problem of a batch, one workgroup each (resident_batch.hpp).
+int fos_power_iter_batch(const void* A, int a_dtype, const fos_batch_item* items, int count, float* v_inout, int64_t ldv,
+                         int n_iter, double tol, double* L_out, int32_t* iters_used, void* work, void* stream) {
+  if (count < 0 || n_iter < 1 || (a_dtype != FOS_F32 && a_dtype != FOS_BF16))
+    return fail(FOS_ERR_ARG, "fos_power_iter_batch: bad argument (count < 0, n_iter < 1 or a_dtype)");
+  if (count == 0) return FOS_OK;
+  if (!A || !items || !v_inout || !L_out || !iters_used || !work || ldv < 1)
+    return fail(FOS_ERR_ARG, "fos_power_iter_batch: bad argument (null pointer or ldv < 1)");
+  if (int rc = check_batch_items("fos_power_iter_batch", items, count, ldv)) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  auto* dev_items = reinterpret_cast<fos_batch_item*>(work);
+  HIP_TRY(hipMemcpyAsync(dev_items, items, (size_t)count * sizeof(fos_batch_item), hipMemcpyHostToDevice, st));
+  if (a_dtype == FOS_F32)
+    hipLaunchKernelGGL(fos::power_resident_batch_kernel<float>, dim3(count), dim3(fos::RS_THREADS), 0, st,
+                       (const float*)A, dev_items, v_inout, ldv, n_iter, tol, L_out, iters_used);
+  else
+    hipLaunchKernelGGL(fos::power_resident_batch_kernel<fos::bf16_t>, dim3(count), dim3(fos::RS_THREADS), 0, st,
+                       (const fos::bf16_t*)A, dev_items, v_inout, ldv, n_iter, tol, L_out, iters_used);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
 }  // extern "C"

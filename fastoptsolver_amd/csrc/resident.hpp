@@ -49,13 +49,14 @@ inline bool resident_fits(int64_t m, int64_t n) {
 // x_hist (nullable): iters x n doubles.  Iterations after a stop are not executed (state untouched, rows not written).
 // SMALL (n <= RS_CHUNK): every thread keeps its rows of A and b in registers and the loop reads LDS only for the
 // n-vectors - the shape of the reference's own problems (n = 5).
+// The body is a device function of one workgroup and one problem: the one-problem kernel below and the batch kernel
+// (resident_batch.hpp, one workgroup per problem) both run it.  ldxh: row stride of x_hist (n for the one-problem form).
 template <typename T, bool SMALL>
-__global__ __launch_bounds__(RS_THREADS) void fista_resident_kernel(const T* __restrict__ A, int64_t lda,
-                                                                   const float* __restrict__ b, int m, int n,
-                                                                   double* __restrict__ x_cur, double* __restrict__ x_prev,
-                                                                   FistaScalars* __restrict__ scal, FistaParams prm,
-                                                                   int iters, double* __restrict__ x_hist,
-                                                                   double* __restrict__ hist, ResidentOpts opt) {
+__device__ __forceinline__ void fista_resident_run(const T* __restrict__ A, int64_t lda, const float* __restrict__ b, int m,
+                                                   int n, double* __restrict__ x_cur, double* __restrict__ x_prev,
+                                                   FistaScalars* __restrict__ scal, FistaParams prm, int iters,
+                                                   double* __restrict__ x_hist, int64_t ldxh, double* __restrict__ hist,
+                                                   ResidentOpts opt) {
   __shared__ float a_s[RS_MAX_A];
   __shared__ float b_s[RS_MAX_M];
   __shared__ double y_s[RS_MAX_N], xc_s[RS_MAX_N], xp_s[RS_MAX_N], g_s[RS_MAX_N], tmp_s[RS_MAX_N];
@@ -296,7 +297,7 @@ __global__ __launch_bounds__(RS_THREADS) void fista_resident_kernel(const T* __r
         xp_s[lane] = xc;
         xc_s[lane] = xn;
         y_s[lane] = form_y(xn, xc, beta);
-        if (x_hist != nullptr) x_hist[(int64_t)it * n + lane] = xn;
+        if (x_hist != nullptr) x_hist[(int64_t)it * ldxh + lane] = xn;
       }
       if (lane == 0) {
         stop_s = stop;
@@ -336,6 +337,16 @@ __global__ __launch_bounds__(RS_THREADS) void fista_resident_kernel(const T* __r
     scal->stopped = stop;
     scal->restarts = restarts;
   }
+}
+
+template <typename T, bool SMALL>
+__global__ __launch_bounds__(RS_THREADS) void fista_resident_kernel(const T* __restrict__ A, int64_t lda,
+                                                                   const float* __restrict__ b, int m, int n,
+                                                                   double* __restrict__ x_cur, double* __restrict__ x_prev,
+                                                                   FistaScalars* __restrict__ scal, FistaParams prm,
+                                                                   int iters, double* __restrict__ x_hist,
+                                                                   double* __restrict__ hist, ResidentOpts opt) {
+  fista_resident_run<T, SMALL>(A, lda, b, m, n, x_cur, x_prev, scal, prm, iters, x_hist, n, hist, opt);
 }
 
 // One gradient of a small problem in one launch, all in fp64 on the fp32-stored A (L-BFGS fg, lbfgs.py:43-54):
@@ -400,10 +411,12 @@ __global__ __launch_bounds__(RS_THREADS) void gemv_pair_resident_kernel(const T*
 
 // Power iteration (iterative_solvers.py:45-60) in the same resident form: v normalised start vector in, L sequence out.
 // Lout: n_iter doubles (L after each step); iters_used: index of the step at which |L - prev| < tol fired (+1), or n_iter.
+// L_hist (nullable): n_iter doubles, L after each step; L_final (nullable): 1 double, L of the last step taken.
 template <typename T>
-__global__ __launch_bounds__(RS_THREADS) void power_resident_kernel(const T* __restrict__ A, int64_t lda, int m, int n,
-                                                                   float* __restrict__ v_inout, int n_iter, double tol,
-                                                                   double* __restrict__ L_out, int* __restrict__ iters_used) {
+__device__ __forceinline__ void power_resident_run(const T* __restrict__ A, int64_t lda, int m, int n,
+                                                   float* __restrict__ v_inout, int n_iter, double tol,
+                                                   double* __restrict__ L_hist, double* __restrict__ L_final,
+                                                   int* __restrict__ iters_used) {
   __shared__ float a_s[RS_MAX_A];
   __shared__ double v_s[RS_MAX_N], w_s[RS_MAX_N];
   __shared__ double red[RS_WAVES][RS_CHUNK + 1];
@@ -468,13 +481,23 @@ __global__ __launch_bounds__(RS_THREADS) void power_resident_kernel(const T* __r
     L = sqrt(s);
     __syncthreads();
     if (tid < n) v_s[tid] = w_s[tid] / L;
-    if (tid == 0) L_out[it] = L;
+    if (tid == 0 && L_hist != nullptr) L_hist[it] = L;
     __syncthreads();
     if (fabs(L - prev) < tol) { used = it + 1; break; }
     prev = L;
   }
   if (tid < n) v_inout[tid] = (float)v_s[tid];
-  if (tid == 0) *iters_used = used;
+  if (tid == 0) {
+    *iters_used = used;
+    if (L_final != nullptr) *L_final = L;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(RS_THREADS) void power_resident_kernel(const T* __restrict__ A, int64_t lda, int m, int n,
+                                                                   float* __restrict__ v_inout, int n_iter, double tol,
+                                                                   double* __restrict__ L_out, int* __restrict__ iters_used) {
+  power_resident_run<T>(A, lda, m, n, v_inout, n_iter, tol, L_out, nullptr, iters_used);
 }
 
 }  // namespace fos

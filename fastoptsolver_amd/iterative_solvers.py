@@ -10,8 +10,10 @@ accumulate in fp32), ``check_every=`` (how often the host polls the device stop 
 """
 from __future__ import annotations
 
+import functools
 import math
 import time
+import types
 
 import numpy as np
 import torch
@@ -87,7 +89,18 @@ def estimate_lipschitz(A, n_iter: int = 100, tol: float = 1e-6, *, group=None) -
 
     Row-sharded problems: with a ``Comm`` attached to the problem the kernels' all-reduce makes this the power
     iteration of the whole matrix as it stands; ``group=`` (a torch.distributed group, split-form sharding) sums
-    w over the ranks here.  Every rank must draw the same v0 (seed the global stream identically)."""
+    w over the ranks here.  Every rank must draw the same v0 (seed the global stream identically).
+    A batch (a 3-D A or a sequence of matrices) gives a length-P float64 ndarray: the draws of P single calls, in
+    problem order, and one power iteration per problem in one launch."""
+    if _is_batch(A):
+        if group is not None:
+            raise ValueError("a batch (3-D A or a sequence of matrices) cannot be combined with group=")
+        mats = list(A) if isinstance(A, (list, tuple)) else [A[i] for i in range(int(A.shape[0]))]
+        for i, Ai in enumerate(mats):
+            if _ndim(Ai) != 2:
+                raise ValueError(f"batch member {i}: A must be 2-D")
+        L, _ = _batch_lipschitz(mats, [None] * len(mats), None, n_iter, tol)
+        return np.asarray(L, dtype=np.float64)
     prob = _core.prepare(A)
     v0 = np.random.randn(prob.n)
     if group is not None:
@@ -657,7 +670,7 @@ def _solve_targets(A, B, *, delta, alpha1, alpha2, backtracking, eta, t_init_fac
     estimated once.  Groups of up to 16 columns advance in lockstep on one read of A per iteration
     (fos_fista_run_multi_rhs); what the lockstep does not serve - shapes without a multi-vector kernel, a last group of
     one column, backtracking, fista's gradient-norm rule (tol > 0) - runs column by column on sibling problems that borrow
-    the same device A."""
+    the same device A.  A that fits one CU's LDS (the resident plan): every column in one launch, one workgroup each."""
     if sharded:
         raise ValueError("a 2-D b (several targets) cannot be combined with comm= / group= / cols=")
     if return_history:
@@ -685,6 +698,25 @@ def _solve_targets(A, B, *, delta, alpha1, alpha2, backtracking, eta, t_init_fac
             backtracking=backtracking, eta=eta, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio, adaptive_restart=restart,
             restart_threshold=restart_threshold, grad_tol_check=delta is None, check_every=check_every)).x_tensor()
 
+    if prob.plan()["resident"]:
+        # A fits one CU's LDS: all k columns in ONE launch, one workgroup per column on the shared A (fos_fista_run_batch),
+        # each computing what the column's own single-target run computes - backtracking and tol > 0 included
+        m, n_dev = prob.m, prob.n_dev
+        prm = _lib.FistaParams(tau=tau, alpha1=alpha1, alpha2=alpha2, delta=delta or 0.0, restart_threshold=restart_threshold,
+                               tol_step=tol if tol > 0.0 else 0.0, tol_ratio=tol_ratio if tol_ratio > 0.0 else 0.0,
+                               tol_grad=tol if (delta is None and tol > 0.0) else 0.0, mode=mode, prox_kind=_lib.PROX_L1,
+                               adaptive_restart=int(restart), reserved=0)
+        cols = types.SimpleNamespace(shapes=[(m, prob.n)] * k, likes=[None] * k, device=prob.device, ldx=n_dev)
+        group = dict(idx=list(range(k)), A=prob.A, B=Bt.t().contiguous(),          # (k, m): column j at j*m
+                     items=[(0, prob.lda, j * m, m, n_dev) for j in range(k)])
+        xs, metrics = [None] * k, [None] * k
+        _run_batch_group(cols, prob.dtype, group, list(range(k)), [prm] * k, max_iter, backtracking, eta, False, delta,
+                         None, xs, None, metrics)
+        for g_t, l_t, l_i in metrics:
+            grad_call_times.extend(g_t)
+            ls_call_times.extend(l_t)
+            ls_call_iters.extend(l_i)
+        return _core.from_device_vec(torch.stack(xs, dim=1), like)
     X = torch.zeros(prob.n, k, dtype=torch.float64, device=prob.device)
     width = 4 if k <= 4 else 16            # up to 4: the multi-vector VALU pass where the shape has one; else matrix cores
     for g0 in range(0, k, width):
@@ -711,6 +743,233 @@ def _solve_targets(A, B, *, delta, alpha1, alpha2, backtracking, eta, t_init_fac
 
 
 # ---------------------------------------------------------------------
+# Batches of small independent problems: fista(A, b) / fista_delta(A, b) with a 3-D A or a sequence of matrices (extension)
+# ---------------------------------------------------------------------
+def _is_batch(A):
+    """A batch call: a 3-D A (P, m, n) or a list / tuple of 2-D matrices.  A 2-D A with a 2-D b stays multi-target."""
+    if isinstance(A, (list, tuple)):
+        return True
+    return not isinstance(A, _core.Problem) and len(getattr(A, "shape", ())) == 3
+
+
+def _ndim(x):
+    return len(x.shape) if hasattr(x, "shape") else np.ndim(x)
+
+
+def _batch_members(A, b, sharded):
+    """The problems of a batch call as (matrices, vectors) - 2-D / 1-D host or device objects, not yet converted - after
+    the checks that refuse a call before any device work."""
+    if sharded:
+        raise ValueError("a batch (3-D A or a sequence of matrices) cannot be combined with comm= / group= / cols=")
+    if b is None:
+        raise ValueError("a batch needs b: (P, m) for a 3-D A, a sequence of vectors for a sequence of matrices")
+    if not isinstance(b, (list, tuple)) and _ndim(b) == 3:
+        raise ValueError("b must not be 3-D: a batch takes one right-hand side per problem")
+    mats = list(A) if isinstance(A, (list, tuple)) else [A[i] for i in range(int(A.shape[0]))]
+    if isinstance(b, (list, tuple)):
+        vecs = list(b)
+    elif _ndim(b) == 2:
+        vecs = [b[i] for i in range(int(b.shape[0]))]
+    else:
+        raise ValueError("a batch needs one right-hand side per problem: b of shape (P, m) or a sequence of vectors")
+    if len(mats) != len(vecs):
+        raise ValueError(f"a batch of {len(mats)} matrices needs as many right-hand sides (got {len(vecs)})")
+    for i, (Ai, bi) in enumerate(zip(mats, vecs)):
+        if _ndim(Ai) != 2:
+            raise ValueError(f"batch member {i}: A must be 2-D")
+        if _ndim(bi) != 1 or (bi.shape[0] if hasattr(bi, "shape") else len(bi)) != Ai.shape[0]:
+            raise ValueError(f"batch member {i}: b must be a vector of m = {Ai.shape[0]} entries")
+    return mats, vecs
+
+
+def _batch_L(L, P):
+    if L is None:
+        return None
+    vals = [float(v) for v in L] if isinstance(L, (list, tuple, np.ndarray)) or _core.is_tensor(L) else [float(L)] * P
+    if len(vals) != P:
+        raise ValueError(f"L= needs one value per problem ({P}) or a scalar")
+    return vals
+
+
+class _Batch:
+    """The members of a batch bound to the device: every problem within the LDS-resident limits (resident.hpp) gets its
+    slice of one device buffer of A elements (per storage dtype) and of one of right-hand sides, converted exactly as
+    Problem / to_device_vec convert a single call's inputs; the others keep their host / device objects and run one by
+    one through the single path."""
+
+    def __init__(self, mats, vecs, dtype):
+        self.mats, self.vecs, self.P = mats, vecs, len(mats)
+        self.likes = [_core.Like(Ai) for Ai in mats]
+        self.shapes = [(int(Ai.shape[0]), int(Ai.shape[1])) for Ai in mats]
+        self.kinds = []                          # per problem: "f32" / "bf16"
+        for Ai in mats:
+            bf16 = (dtype in ("bf16", torch.bfloat16)) or (dtype is None and _core.is_tensor(Ai) and Ai.dtype == torch.bfloat16)
+            self.kinds.append("bf16" if bf16 else "f32")
+        self.fits = [_core.resident_fits(m, n) for m, n in self.shapes]
+        self.groups = {}                         # dtype -> dict(idx, A, B, items)
+        if any(self.fits):
+            _core.require_gpu()
+            self.device = next((Ai.device for Ai in mats if _core.is_tensor(Ai) and Ai.is_cuda),
+                               torch.device("cuda", torch.cuda.current_device()))
+        for kind in ("f32", "bf16"):
+            idx = [i for i in range(self.P) if self.fits[i] and self.kinds[i] == kind]
+            if idx:
+                self.groups[kind] = self._bind(idx, torch.bfloat16 if kind == "bf16" else torch.float32)
+        self.ldx = max([n for (m, n), ok in zip(self.shapes, self.fits) if ok] or [1])
+
+    def _bind(self, idx, tdtype):
+        dev = self.device
+        a_off, b_off, items, ao, bo = [], [], [], 0, 0
+        for i in idx:
+            m, n = self.shapes[i]
+            items.append((ao, n, bo, m, n))
+            a_off.append(ao)
+            b_off.append(bo)
+            ao += m * n
+            bo += m
+        Abuf = torch.empty(max(ao, 1), dtype=tdtype, device=dev)
+        Bbuf = torch.empty(max(bo, 1), dtype=torch.float32, device=dev)
+        for i, o, q in zip(idx, a_off, b_off):
+            m, n = self.shapes[i]
+            Ai, dst = self.mats[i], Abuf[o:o + m * n].view(m, n)
+            if _core.is_tensor(Ai):
+                At = Ai.detach()
+                if At.is_cuda:
+                    dst.copy_(At.to(device=dev, dtype=tdtype))           # Problem: At.to(device, dtype).contiguous()
+                else:
+                    _core.upload_matrix(At, dst)
+            else:
+                _core.upload_matrix(torch.from_numpy(np.asarray(Ai)), dst)
+            if self.vecs[i] is not None:
+                Bbuf[q:q + m].copy_(_core.to_device_vec(self.vecs[i], dev))
+        return dict(idx=idx, A=Abuf, B=Bbuf, items=items)
+
+    def problem(self, i):
+        """The single path's Problem of member i (members outside the resident limits)."""
+        return _core.Problem(self.mats[i], self.vecs[i], self.kinds[i] if self.kinds[i] == "bf16" else None)
+
+
+def _batch_lipschitz(mats, vecs, dtype, n_iter=100, tol=1e-6, batch=None):
+    """estimate_lipschitz of every member (ref:45-60): np.random.randn(n_i) drawn in problem order, as P single calls
+    would draw them; one batched power iteration for the resident members, Problem.power_iter for the others."""
+    bt = batch if batch is not None else _Batch(mats, vecs, dtype)
+    v0s = [np.random.randn(n) for (m, n) in bt.shapes]
+    L = [0.0] * bt.P
+    for kind, g in bt.groups.items():
+        V = torch.zeros(len(g["idx"]), bt.ldx, dtype=torch.float32, device=bt.device)
+        for r, i in enumerate(g["idx"]):
+            V[r, : bt.shapes[i][1]] = _core.to_device_vec(v0s[i], bt.device)      # Problem.vec_in's conversion
+        Ls, _ = _core.power_iter_batch(g["A"], kind, g["items"], V, n_iter=n_iter, tol=tol)
+        for i, Li in zip(g["idx"], Ls):
+            L[i] = Li
+    probs = {}
+    for i in range(bt.P):
+        if not bt.fits[i]:
+            probs[i] = bt.problem(i)
+            L[i] = probs[i].power_iter(v0s[i], n_iter=n_iter, tol=tol)[0]
+    return L, probs
+
+
+def _solve_batch(A, b, *, delta, reg_type, alpha1, alpha2, backtracking, eta, t_init_factor, max_iter, tol, tol_ratio,
+                 adaptive_restart, restart_threshold, return_history, L, dtype, sharded):
+    """X[i] = fista(A[i], b[i], ...) (fista_delta when `delta` is given) for every member, the resident ones in one
+    launch (one workgroup per problem, fos_fista_run_batch), the others one by one through the single path."""
+    mats, vecs = _batch_members(A, b, sharded)
+    P = len(mats)
+    L_given = _batch_L(L, P)
+    bt = _Batch(mats, vecs, dtype)
+    if L_given is None:
+        L_vals, probs = _batch_lipschitz(mats, vecs, dtype, batch=bt)
+    else:
+        L_vals, probs = L_given, {}
+    mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
+    obj = _objective_by_alpha(alpha1, alpha2) if delta is None else _objective_by_reg(reg_type, alpha1, alpha2)
+    a2_smooth = alpha2 if alpha2 > 0 else 0.0
+    taus = [t_init_factor / (Li + a2_smooth) for Li in L_vals]
+    xs, hists = [None] * P, [None] * P
+    metrics = [([], [], []) for _ in range(P)]       # per problem: grad times, ls times, ls iters
+    prm_of = lambda i: _lib.FistaParams(                                               # noqa: E731 (what _drive resets)
+        tau=taus[i], alpha1=alpha1, alpha2=alpha2, delta=delta or 0.0, restart_threshold=restart_threshold,
+        tol_step=tol if tol > 0.0 else 0.0, tol_ratio=tol_ratio if tol_ratio > 0.0 else 0.0,
+        tol_grad=tol if (delta is None and tol > 0.0) else 0.0, mode=mode, prox_kind=_lib.PROX_L1,
+        adaptive_restart=int(bool(adaptive_restart) and delta is None), reserved=0)
+    for kind, g in bt.groups.items():
+        idx = g["idx"]
+        # the device-side x history is bounded like the single path's chunks: split the batch where it would exceed it
+        per = max(1, _HISTORY_CHUNK_BYTES // (8 * max(max_iter, 1) * bt.ldx)) if return_history else len(idx)
+        for c0 in range(0, len(idx), per):
+            sub = list(range(c0, min(len(idx), c0 + per)))
+            _run_batch_group(bt, kind, g, sub, [prm_of(idx[r]) for r in sub], max_iter, backtracking, eta,
+                             return_history, delta, obj, xs, hists, metrics)
+    for i in range(P):
+        if bt.fits[i]:
+            continue
+        prob = probs.get(i) or bt.problem(i)
+        fn = fista if delta is None else functools.partial(fista_delta, delta=delta)
+        kw = dict(backtracking=backtracking, eta=eta, t_init_factor=t_init_factor, max_iter=max_iter, tol=tol,
+                  tol_ratio=tol_ratio, return_history=return_history, L=L_vals[i])
+        if delta is None:
+            kw.update(adaptive_restart=adaptive_restart, restart_threshold=restart_threshold)
+        res = fn(prob, None, reg_type, alpha1, alpha2, **kw)
+        xs[i], hists[i] = (res if return_history else (res, None))
+        metrics[i] = (list(grad_call_times), list(ls_call_times), list(ls_call_iters))
+    reset_metrics()
+    for g_t, l_t, l_i in metrics:
+        grad_call_times.extend(g_t)
+        ls_call_times.extend(l_t)
+        ls_call_iters.extend(l_i)
+    if isinstance(A, (list, tuple)):
+        X = xs
+    elif _core.is_tensor(A):                 # each row is the single call's result (a tensor of that kind): stacked
+        like = _core.Like(A)
+        X = torch.stack(xs) if P else torch.zeros(0, int(A.shape[2]), dtype=like.dtype, device=like.device)
+    else:
+        X = np.stack(xs) if P else np.zeros((0, int(A.shape[2])))
+    return (X, hists) if return_history else X
+
+
+def _run_batch_group(bt, kind, g, sub, params, max_iter, backtracking, eta, record, delta, obj, xs, hists, metrics):
+    """One fos_fista_run_batch launch (two for a ragged batch) over the members g["idx"][r], r in sub; results, history
+    and each member's metric lists go into xs / hists / metrics at the members' places."""
+    idx = [g["idx"][r] for r in sub]
+    items = [g["items"][r] for r in sub]
+    t0 = time.perf_counter()
+    ev0 = torch.cuda.Event(enable_timing=True)
+    ev1 = torch.cuda.Event(enable_timing=True)
+    with torch.cuda.device(bt.device):
+        ev0.record()
+        out = _core.run_batch(g["A"], kind, g["B"], items, params, max_iter, backtracking=backtracking, eta=eta,
+                              armijo_c=C, ldx=bt.ldx, record=record)
+        ev1.record()
+        ev1.synchronize()
+    wall = time.perf_counter() - t0
+    done = out["done"].cpu().tolist()
+    stopped = out["stopped"].cpu().tolist()
+    ls = out["ls"].cpu().tolist() if backtracking else None
+    xs_dev = out["x"]
+    # one gradient per completed iteration plus the one whose norm ended the run (_Run.resident); the device does not time
+    # its phases: the launch's time in equal shares over the gradients, the searches' wall time over the searches
+    ngrad = [k + (1 if s == _lib.STOP_GRAD else 0) for k, s in zip(done, stopped)]
+    g_share = ev0.elapsed_time(ev1) * 1e-3 / max(sum(ngrad), 1)
+    l_share = wall / max(sum(done), 1)
+    hs = out["hist"].cpu().numpy() if record else None
+    for r, i in enumerate(idx):
+        n, like, k = bt.shapes[i][1], bt.likes[i], done[r]
+        xs[i] = xs_dev[r, :n] if like is None else _core.from_device_vec(xs_dev[r, :n], like)
+        metrics[i] = ([g_share] * ngrad[r], [l_share] * k if backtracking else [],
+                      [int(v) for v in ls[r][:k]] if backtracking else [])
+        if record:
+            xh = out["x_hist"][r, :k, :n]
+            rows = [_core.from_device_vec(xh[t], like) for t in range(k)] if like.tensor else list(xh.cpu().numpy())
+            h = {"x": [] if delta is not None else [_core.from_device_vec(torch.zeros(n, dtype=torch.float64,
+                                                                                       device=bt.device), like)],
+                 "obj": []}
+            h["x"].extend(rows)
+            h["obj"].extend(obj(float(q[0]), float(q[2]), float(q[1])) for q in hs[r, :k])
+            hists[i] = h
+
+
+# ---------------------------------------------------------------------
 # FISTA                                                        ref:132-245
 # ---------------------------------------------------------------------
 def fista(A, b, reg_type: str, alpha1: float, alpha2: float, backtracking: bool = False, eta: float = 0.5,
@@ -727,6 +986,12 @@ def fista(A, b, reg_type: str, alpha1: float, alpha2: float, backtracking: bool 
     Several targets: a 2-D ``b`` of shape (m, k), k >= 2, returns x of shape (n, k) whose column j is
     ``fista(A, b[:, j], ...)`` with the same L (estimated once); up to 16 columns share each read of A."""
     reset_metrics()
+    if _is_batch(A):
+        return _solve_batch(A, b, delta=None, reg_type=reg_type, alpha1=alpha1, alpha2=alpha2, backtracking=backtracking,
+                            eta=eta, t_init_factor=t_init_factor, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio,
+                            adaptive_restart=adaptive_restart, restart_threshold=restart_threshold,
+                            return_history=return_history, L=L, dtype=dtype,
+                            sharded=any(v is not None for v in (comm, group, cols)))
     B = _targets(A, b)
     if B is not None:
         return _solve_targets(A, B, delta=None, alpha1=alpha1, alpha2=alpha2, backtracking=backtracking, eta=eta,
@@ -768,6 +1033,11 @@ def fista_delta(A, b, reg_type: str, alpha1: float, alpha2: float, delta: float,
     reset_metrics()
     # Course requirement: delta > 2 for convergence guarantee                   ref:268
     assert delta > 2, "In FISTA-Δ, delta must be > 2 for convergence (course requirement)"
+    if _is_batch(A):             # a batch of independent problems: see fista
+        return _solve_batch(A, b, delta=delta, reg_type=reg_type, alpha1=alpha1, alpha2=alpha2, backtracking=backtracking,
+                            eta=eta, t_init_factor=t_init_factor, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio,
+                            adaptive_restart=False, restart_threshold=1.0, return_history=return_history, L=L,
+                            dtype=dtype, sharded=any(v is not None for v in (comm, group, cols)))
     B = _targets(A, b)
     if B is not None:            # several targets: see fista
         return _solve_targets(A, B, delta=delta, alpha1=alpha1, alpha2=alpha2, backtracking=backtracking, eta=eta,

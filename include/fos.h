@@ -468,6 +468,44 @@ int fos_lbfgs_minimize_multi(fos_problem* p, int nv, const float* B, int64_t ldb
                              double* X, int64_t ldx, double* hist, float* round_ms, int round_cap, int* rounds,
                              fos_lbfgs_result* res);
 
+/* Batches of small independent problems (extension): one workgroup per problem runs the LDS-resident loop of
+ * fos_fista_run_resident on its own A, b and parameters, all problems in ONE launch (two when the batch mixes problems
+ * with n <= 8 and m <= 2048, whose rows of A live in registers, with the others).  Problem i computes exactly what
+ * fos_fista_run_resident computes for it on a fresh handle: the same kernel body, the same arithmetic.
+ *   A         device, elements of a_dtype (FOS_F32 / FOS_BF16); problem i's matrix is m x n, row-major, at A + a_offset with
+ *             leading dimension lda (several targets on one A: every item has the same a_offset)
+ *   b         device floats; problem i's m-vector at b + b_offset
+ *   items     HOST, count descriptors (offsets in elements)                                                          */
+typedef struct fos_batch_item {
+  int64_t a_offset, lda, b_offset;
+  int32_t m, n;
+} fos_batch_item;
+/* Bytes of device workspace fos_fista_run_batch needs for `count` problems with iterate stride ldx (8-byte aligned). */
+int64_t fos_fista_batch_workspace(int count, int64_t ldx);
+/* Run every problem of the batch from the reference's initial state (x = 0, t = 1, beta = 0, k = 0) for up to `iters`
+ * iterations with every option of fos_fista_run_resident: prm[i] (HOST, count entries) is problem i's fos_fista_params
+ * (its own tau, weights, mode, restart, step / ratio / gradient-norm stops: tol_grad plays fos_fista_run_resident's
+ * grad_tol); backtracking / eta / armijo_c are shared.  Device outputs, problem i at:
+ *   x_out      + i*ldx        n doubles: the solution (ldx >= every n)
+ *   iters_done / stopped / tau_out [i]: iterations completed, STOP_* code, step after the last search
+ *   ls_iters / tau_hist + i*iters, hist + i*iters*4, x_hist + i*iters*ldx (row t of problem i at + t*ldx): the nullable
+ *   per-iteration records of fos_fista_run_resident
+ *   work       fos_fista_batch_workspace(count, ldx) bytes: the descriptors and each problem's state (caller-owned)
+ * Checked before any HIP call: FOS_ERR_ARG for null pointers, count < 0, iters < 0, backtracking with eta outside (0, 1),
+ * an item with n > ldx, a negative offset, lda < n or a bad fos_fista_params; FOS_ERR_UNSUPPORTED for an item outside the
+ * LDS-resident limits (n <= 64, m <= 4096, m * (n | 1) <= 10240).  The host arrays are copied once; they may be reused
+ * when the call returns.  Enqueues only. */
+int fos_fista_run_batch(const void* A, int a_dtype, const float* b, const fos_batch_item* items, const fos_fista_params* prm,
+                        int count, int iters, int backtracking, double eta, double armijo_c, int64_t ldx, double* x_out,
+                        int32_t* iters_done, int32_t* stopped, double* tau_out, int32_t* ls_iters, double* tau_hist,
+                        double* hist, double* x_hist, void* work, void* stream);
+/* fos_power_iter of every problem of the batch in one launch (b_offset unused): problem i's start vector at
+ * v_inout + i*ldv (device, n floats; the normalised last iterate comes back there), L_out[i] and iters_used[i] (device).
+ * work: count * sizeof(fos_batch_item) bytes of device memory (caller-owned).  Same argument checks as fos_fista_run_batch
+ * (n_iter < 1, ldv < n: FOS_ERR_ARG).  Enqueues only. */
+int fos_power_iter_batch(const void* A, int a_dtype, const fos_batch_item* items, int count, float* v_inout, int64_t ldv,
+                         int n_iter, double tol, double* L_out, int32_t* iters_used, void* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
