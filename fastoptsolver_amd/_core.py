@@ -26,14 +26,23 @@ def is_tensor(x):
     return isinstance(x, torch.Tensor)
 
 
-def to_device_vec(x, device=None):
-    """1-D float32 contiguous CUDA tensor from ndarray / tensor."""
+def to_device(x, device=None, dtype=torch.float32):
+    """Contiguous CUDA tensor (float32 unless told otherwise) of the same shape from an ndarray / tensor of any rank."""
     if is_tensor(x):
         t = x.detach()
     else:
         t = torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-    return t.to(device=dev, dtype=torch.float32).contiguous()
+    return t.to(device=dev, dtype=dtype).contiguous()
+
+
+to_device_vec = to_device       # the name for a vector
+
+
+def stores_bf16(A, dtype=None):
+    """Whether the device copy of A is kept in bf16: asked for by `dtype`, or A arrives as a bf16 tensor and nothing else was
+    asked for."""
+    return (dtype in ("bf16", torch.bfloat16)) or (dtype is None and is_tensor(A) and A.dtype == torch.bfloat16)
 
 
 UPLOAD_CHUNK_BYTES = 256 << 20
@@ -102,7 +111,7 @@ class Problem:
         require_gpu()
         lib = _lib.load()
         self.like = Like(A)
-        want_bf16 = (dtype in ("bf16", torch.bfloat16)) or (dtype is None and is_tensor(A) and A.dtype == torch.bfloat16)
+        want_bf16 = stores_bf16(A, dtype)
         tdtype = torch.bfloat16 if want_bf16 else torch.float32
         gran = 8 if want_bf16 else 4
         dev = A.device if is_tensor(A) and A.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -191,8 +200,7 @@ class Problem:
     # ---- user-length <-> device-length vectors ------------------------------------------------------------
     def vec_in(self, x, dtype=torch.float32):
         """1-D device tensor of the kernel's length n_dev (zero beyond n) from a user vector of length n or n_dev."""
-        t = x.detach() if is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
-        t = t.to(device=self.device, dtype=dtype).contiguous()
+        t = to_device(x, self.device, dtype)
         if t.numel() == self.n_dev:
             return t
         if t.numel() != self.n:
@@ -311,9 +319,8 @@ class Problem:
         Xf[: X.shape[0], :nv] = X
         with self.ctx():
             rc = self.lib.fos_residual_batch_rhs(self.h, ptr(Xf), nv, ptr(B), int(B.stride(0)), ptr(self.scratch))
-        if rc == -4:
+        if not _lib.served(rc, "fos_residual_batch_rhs"):
             return None
-        _lib.check(rc, "fos_residual_batch_rhs")
         return self.scratch[:nv].cpu().tolist()
 
     def power_iter(self, v0, n_iter=100, tol=1e-6):
@@ -395,20 +402,14 @@ class Fista:
         cores, the owned slice of the iterate resident in LDS).  False when this problem / configuration is not served."""
         with self.prob.ctx():
             rc = self.lib.fos_fista_run_fused(self.h, int(iters))
-        if rc == -4:
-            return False
-        _lib.check(rc, "fos_fista_run_fused")
-        return True
+        return _lib.served(rc, "fos_fista_run_fused")
 
     def run_chip(self, iters):
         """`iters` plain iterations in ONE launch with A resident in the LDS of up to all CUs and one grid-wide barrier per
         iteration (fos_fista_run_chip: tall-skinny fp32 problems, n <= 16).  False when not served."""
         with self.prob.ctx():
             rc = self.lib.fos_fista_run_chip(self.h, int(iters))
-        if rc == -4:
-            return False
-        _lib.check(rc, "fos_fista_run_chip")
-        return True
+        return _lib.served(rc, "fos_fista_run_chip")
 
     def run_history(self, iters):
         """Device-resident history run: (x_hist [iters, n] float64, hist [iters, 4] float64 =
@@ -421,9 +422,8 @@ class Fista:
         work = torch.empty(max(1, (nbytes + 7) // 8), dtype=torch.float64, device=dev)
         with self.prob.ctx():
             rc = self.lib.fos_fista_run_history(self.h, int(iters), ptr(xh), ptr(hist), ptr(work))
-        if rc == -4:
+        if not _lib.served(rc, "fos_fista_run_history"):
             return None
-        _lib.check(rc, "fos_fista_run_history")
         self._keep = work            # stays alive until the stream has consumed it (next sync)
         return self.prob.vec_out(xh), hist
 
@@ -445,9 +445,8 @@ class Fista:
             rc = self.lib.fos_fista_run_resident(self.h, iters, 1 if backtracking else 0, float(eta), float(armijo_c),
                                                  float(grad_tol), ptr(xh), ptr(hist), ptr(ls), ptr(taus),
                                                  C.byref(done), C.byref(tau))
-        if rc == -4:
+        if not _lib.served(rc, "fos_fista_run_resident"):
             return None
-        _lib.check(rc, "fos_fista_run_resident")
         k = int(done.value)
         out = dict(done=k, tau=float(tau.value), ls=ls[:k].cpu().tolist(), taus=taus[:k].cpu().tolist())
         if record:
@@ -465,9 +464,8 @@ class Fista:
         with self.prob.ctx():
             rc = self.lib.fos_fista_run_backtracking(self.h, int(iters), float(eta), float(armijo_c), float(grad_eps),
                                                      ptr(ls), ptr(taus))
-        if rc == -4:
+        if not _lib.served(rc, "fos_fista_run_backtracking"):
             return None
-        _lib.check(rc, "fos_fista_run_backtracking")
         return ls, taus
 
     def run_recorded(self, iters, backtracking, eta, armijo_c, grad_eps, want_rr=True):
@@ -485,9 +483,8 @@ class Fista:
                                                  float(grad_eps), ptr(rec["x"]), ptr(rec["hist"]),
                                                  ptr(rec["rr_seen"] if want_rr else None),
                                                  ptr(rec["ls"]), ptr(rec["taus"]))
-        if rc == -4:
+        if not _lib.served(rc, "fos_fista_run_recorded"):
             return None
-        _lib.check(rc, "fos_fista_run_recorded")
         return rec
 
     def resume_after_stall(self):
@@ -522,9 +519,8 @@ class Fista:
         out = (C.c_double * (8 * nv))()
         with self.prob.ctx():
             rc = self.lib.fos_fista_trial_batch(self.h, float(t), float(eta), int(nv), out)
-        if rc == -4:
+        if not _lib.served(rc, "fos_fista_trial_batch"):
             return None
-        _lib.check(rc, "fos_fista_trial_batch")
         keys = ("gd", "dd", "nnz", "gnorm2", "y2", "q", "rr_y")
         return [dict(zip(keys, out[8 * j: 8 * j + 7])) for j in range(nv)]
 
@@ -562,10 +558,7 @@ def run_multi(handles, iters):
     arr = (C.c_void_p * len(handles))(*[h.h for h in handles])
     with handles[0].prob.ctx():
         rc = lib.fos_fista_run_multi(arr, len(handles), int(iters))
-    if rc == -4:
-        return False
-    _lib.check(rc, "fos_fista_run_multi")
-    return True
+    return _lib.served(rc, "fos_fista_run_multi")
 
 
 def run_multi_rhs(handles, B, iters):
@@ -576,10 +569,7 @@ def run_multi_rhs(handles, B, iters):
     arr = (C.c_void_p * len(handles))(*[h.h for h in handles])
     with handles[0].prob.ctx():
         rc = lib.fos_fista_run_multi_rhs(arr, len(handles), ptr(B), int(B.stride(0)), int(iters))
-    if rc == -4:
-        return False
-    _lib.check(rc, "fos_fista_run_multi_rhs")
-    return True
+    return _lib.served(rc, "fos_fista_run_multi_rhs")
 
 
 # ---- batches of small problems (fos_fista_run_batch / fos_power_iter_batch) -------------------------------------------

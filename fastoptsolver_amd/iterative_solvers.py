@@ -10,10 +10,9 @@ accumulate in fp32), ``check_every=`` (how often the host polls the device stop 
 """
 from __future__ import annotations
 
-import functools
+import collections
 import math
 import time
-import types
 
 import numpy as np
 import torch
@@ -165,103 +164,178 @@ def _armijo_accepts(tr, t_k, smooth_a2, grad_eps=8.0 * _EPS32):
 # ---------------------------------------------------------------------
 # shared FISTA / FISTA-Δ / fused-ISTA driver
 # ---------------------------------------------------------------------
-class _Run:
-    """One solver run: the state machine, what the caller asked for, and the metric / history sinks.  Each execution
-    strategy is a method that returns True when it ran the whole job and False when this problem / plan has no such form
-    (the dispatcher `_drive` then tries the next one)."""
+def _pos(v):
+    """A tolerance for which non-positive means "off", as the device takes it."""
+    return v if v > 0.0 else 0.0
 
-    def __init__(self, prob, like, st, *, tau, eta, max_iter, tol, tol_ratio, backtracking, grad_tol_check, history,
-                 history_obj, log, check_every, reducer, smooth_a2, grad_eps, batch_trials):
-        self.prob, self.like, self.st = prob, like, st
+
+def _params(tau, alpha1, alpha2, *, mode, prox_kind=_lib.PROX_L1, delta=None, tol=0.0, tol_ratio=0.0, grad_rule=False,
+            adaptive_restart=False, restart_threshold=1.0):
+    """The fields of fos_fista_params from the solvers' arguments, under the names `_core.Fista.reset` and
+    `_lib.FistaParams` take them.  `tol` is the step stop and, where `grad_rule` says so, the gradient-norm rule (ref:179) as
+    well; momentum restarts exist for FISTA only.  Tolerances reach the device as given: a caller for which a non-positive
+    one means "off" passes `_pos(tol)`."""
+    prm = dict(tau=float(tau), alpha1=float(alpha1), alpha2=float(alpha2), delta=float(delta or 0.0),
+               restart_threshold=float(restart_threshold), tol_step=float(tol), tol_ratio=float(tol_ratio), mode=int(mode),
+               prox_kind=int(prox_kind), adaptive_restart=int(bool(adaptive_restart) and mode == _lib.MODE_FISTA))
+    if grad_rule:                   # absent means 0.0, off: stand-in states without the rule (CPU tests) never meet the field
+        prm["tol_grad"] = float(tol)
+    return prm
+
+
+def _new_state(prob, prm):
+    st = _core.Fista(prob)
+    st.reset(**prm)
+    return st
+
+
+def _shares(n, seconds, of=None):
+    """n of the `of` (default: n) equal shares of `seconds`: the device does not time the phases of a launch."""
+    return [seconds / max(n if of is None else of, 1)] * n
+
+
+def _ngrad(done, stopped):
+    """One gradient per completed iteration, plus the one whose norm ended the run (ref:173-180)."""
+    return done + (1 if stopped == _lib.STOP_GRAD else 0)
+
+
+class _Records:
+    """What a run leaves to its caller besides x: the `history` of fista / fista_delta (ref:224-232, :319-322), the `log` of
+    ista (ref:117-120) and the entries of the metric lists.  The execution strategies hand over what the device recorded;
+    the conversion to the caller's kind, the objective and the shares of the timings are decided here."""
+
+    def __init__(self, like, history=None, obj=None, log=None, timer=_EventTimer):
+        self.like, self.history, self.obj, self.log = like, history, obj, log
+        self.timer = timer(grad_call_times)
+        self.recording = history is not None or log is not None
+        self.objectives = history is not None
+        self.owed = []          # (||x||_1, ||x||_2^2) of recorded iterates whose ||A x - b||^2 is not known yet
+
+    def _rows(self, xs):
+        """[k, n] device block -> k rows of the caller's kind: tensors row by row, ndarrays out of one copy to the host."""
+        if self.like.tensor:
+            return [_core.from_device_vec(xs[i], self.like) for i in range(xs.shape[0])]
+        return list(xs.cpu().numpy())
+
+    def block(self, xs, hs, taus=None, rr_known=True):
+        """k iterations recorded on the device: xs [k, n] device rows, hs [k, 4] host rows {||A x - b||^2, ||x||_1, ||x||_2^2,
+        ||dx||^2}, taus the steps used (host list or device tensor; the log only).  rr_known=False: hs[:, 0] is not filled,
+        the residuals come later through settle()."""
+        rows = self._rows(xs)
+        if self.history is not None:
+            self.history["x"].extend(rows)
+            if rr_known:
+                self.history["obj"].extend(self.obj(float(r[0]), float(r[2]), float(r[1])) for r in hs)
+            else:
+                self.owed.extend((float(r[1]), float(r[2])) for r in hs)
+        if self.log is not None:                            # ista's log (ref:117-120): x, the step used, ||dx||
+            self.log["x"].extend(rows)
+            self.log["t"].extend(taus.cpu().tolist() if _core.is_tensor(taus) else taus)
+            self.log["delta"].extend(float(math.sqrt(r[3])) for r in hs)
+
+    def one(self, x, s, tau):
+        """The iteration the host finished itself: the device iterate, its status (norms, step length), the step used."""
+        row = _core.from_device_vec(x, self.like)
+        if self.history is not None:
+            self.history["x"].append(row)
+            self.owed.append((s.xnorm1, s.xnorm2))
+        if self.log is not None:
+            self.log["x"].append(row)
+            self.log["t"].append(tau)
+            self.log["delta"].append(s.this_step)
+
+    def settle(self, rrs, norms=None):
+        """||A x - b||^2 of the oldest iterates still owed their objective: f(x after iteration t) is seen by iteration
+        t + 1's gradient pass, or by a closing residual pass (which brings `norms` of its own)."""
+        self.history["obj"].extend(self.obj(rr, x2, x1) for rr, (x1, x2) in zip(rrs, norms or self.owed))
+        del self.owed[:len(rrs)]
+
+    def gradients(self, n=None):
+        """The run's own timer bracketed its launches: resolve it, and keep the `n` gradient passes that belong to the run
+        (None: all that were counted)."""
+        self.timer.flush()
+        if n is not None:
+            del grad_call_times[n:]
+
+    def searches(self, shrinks, seconds):
+        """One Armijo search per entry of `shrinks` (ref:183-197) in `seconds` of wall time together."""
+        ls_call_iters.extend(int(v) for v in shrinks)
+        ls_call_times.extend(_shares(len(shrinks), seconds))
+
+
+class _Run:
+    """One solver run: the state machine, what the caller asked for, and the record sink.  Each execution strategy is a
+    method that returns True when it ran the whole job and False when this problem / plan has no such form (the dispatcher
+    `_drive` then tries the next one)."""
+
+    def __init__(self, prob, st, rec, *, tau, eta, max_iter, tol, tol_ratio, backtracking, grad_tol_check, check_every,
+                 reducer, smooth_a2, grad_eps, batch_trials):
+        self.prob, self.st, self.rec = prob, st, rec
         self.tau, self.eta, self.max_iter, self.tol, self.tol_ratio = tau, eta, max_iter, tol, tol_ratio
         self.backtracking, self.grad_tol_check = backtracking, grad_tol_check
-        self.history, self.history_obj, self.log = history, history_obj, log
         self.check_every, self.reducer = check_every, reducer
         self.smooth_a2, self.grad_eps, self.use_batch = smooth_a2, grad_eps, batch_trials
-        self.gtimer = getattr(st, "make_timer", _EventTimer)(grad_call_times)     # stand-in states bring a host timer
-        self.recording = history is not None or log is not None
-        # ista passes x0 itself as `like`
-        self.as_tensor = like.tensor if hasattr(like, "tensor") else _core.is_tensor(like)
 
     # ---- 1. nothing needs the host per iteration: enqueue everything, poll for stops -------------------------------
     def enqueue_only(self):
-        st, gtimer = self.st, self.gtimer
+        st, rec = self.st, self.rec
         stops_possible = self.tol > 0.0 or self.tol_ratio > 0.0
         chunk = self.max_iter if not stops_possible else max(1, int(self.check_every or 8))
         done = 0
         while done < self.max_iter:
             todo = min(chunk, self.max_iter - done)
-            ev = gtimer.start()
+            ev = rec.timer.start()
             st.run(todo)
-            gtimer.stop(ev, todo)
+            rec.timer.stop(ev, todo)
             done += todo
             if stops_possible and st.status().stopped != _lib.STOP_NONE:
                 break
-        gtimer.flush()
+        rec.gradients()
         if stops_possible:
-            # only the iterations that really ran count as gradient calls, plus the gradient whose norm ended the run
+            # only the iterations that really ran count as gradient calls
             s_end = st.status()
-            del grad_call_times[int(s_end.k) + (1 if s_end.stopped == _lib.STOP_GRAD else 0):]
+            rec.gradients(_ngrad(int(s_end.k), s_end.stopped))
         return True
 
     # ---- 2. small problems (A fits one CU's LDS): every host-driven feature - backtracking, gradient-norm stop, history,
     #         ISTA log - runs inside ONE launch of the LDS-resident loop; the host only unpacks what the device recorded
     def resident(self):
-        st, gtimer, like = self.st, self.gtimer, self.like
-        ev = gtimer.start()
+        st, rec = self.st, self.rec
+        ev = rec.timer.start()
         ls_t0 = time.perf_counter()
         res = st.run_resident(self.max_iter, backtracking=self.backtracking, eta=self.eta, armijo_c=C,
                               grad_tol=self.tol if (self.grad_tol_check and self.tol > 0.0) else 0.0,
-                              record=self.recording)
+                              record=rec.recording)
         if res is None:
-            gtimer.pending.clear()
+            rec.timer.pending.clear()
             return False
-        k = res["done"]
-        # one gradient per completed iteration, plus the one whose norm ended the run (ref:173-180)
-        ngrad = k + (1 if st.status().stopped == _lib.STOP_GRAD else 0)
-        gtimer.stop(ev, max(ngrad, 1))
-        gtimer.flush()
-        del grad_call_times[ngrad:]
+        ngrad = _ngrad(res["done"], st.status().stopped)
+        rec.timer.stop(ev, max(ngrad, 1))
+        rec.gradients(ngrad)
         if self.backtracking:                                    # ref:183-197: one search per completed iteration
-            share = (time.perf_counter() - ls_t0) / max(k, 1)
-            ls_call_iters.extend(int(v) for v in res["ls"])
-            ls_call_times.extend([share] * k)                    # the device does not time its phases: equal shares
-        if self.recording:
-            hs = res["hist"].cpu().numpy()
-            xs = res["x"]
-            rows = [_core.from_device_vec(xs[i], like) for i in range(k)] if self.as_tensor else list(xs.cpu().numpy())
-            if self.history is not None:
-                self.history["x"].extend(rows)
-                self.history["obj"].extend(self.history_obj(float(r[0]), float(r[2]), float(r[1])) for r in hs)
-            if self.log is not None:
-                self.log["x"].extend(rows)
-                self.log["t"].extend(res["taus"])
-                self.log["delta"].extend(float(math.sqrt(r[3])) for r in hs)
+            rec.searches(res["ls"], time.perf_counter() - ls_t0)
+        if rec.recording:
+            rec.block(res["x"], res["hist"].cpu().numpy(), res["taus"])
         return True
 
     # ---- 3. history of a PLAIN run without any per-iteration host round trip: x and the objective ingredients are
     #         recorded on the device by the same two kernels of the plain run and read back once (ref:224-232, :319-322)
     def history_plain(self):
-        st, gtimer, prob, like, history = self.st, self.gtimer, self.prob, self.like, self.history
-        chunk = max(1, min(self.max_iter, _HISTORY_CHUNK_BYTES // (8 * prob.n_dev)))    # bound the device-side x history
+        st, rec = self.st, self.rec
+        chunk = max(1, min(self.max_iter, _HISTORY_CHUNK_BYTES // (8 * self.prob.n_dev)))   # bound the device-side x history
         done = 0
         while done < self.max_iter:
             todo = min(chunk, self.max_iter - done)
-            ev = gtimer.start()
-            rec = st.run_history(todo)
-            if rec is None:
-                gtimer.pending.clear()
+            ev = rec.timer.start()
+            out = st.run_history(todo)
+            if out is None:
+                rec.timer.pending.clear()
                 return False
-            gtimer.stop(ev, todo)
-            xh, hs = rec
-            hs = hs.cpu().numpy()
-            if like.tensor:
-                history["x"].extend(_core.from_device_vec(xh[i], like) for i in range(todo))
-            else:
-                history["x"].extend(list(xh.cpu().numpy()))
-            history["obj"].extend(self.history_obj(float(r[0]), float(r[2]), float(r[1])) for r in hs)
+            rec.timer.stop(ev, todo)
+            xh, hs = out
+            rec.block(xh, hs.cpu().numpy())
             done += todo
-        gtimer.flush()
+        rec.gradients()
         return True
 
     # ---- the Armijo search on the host (ref:183-197 / :298-312 / :92-108): used by the host-driven loop and to finish a
@@ -294,76 +368,58 @@ class _Run:
     # The host polls every `check_every` iterations for stops and for a parked search, which it finishes itself before
     # handing the loop back to the device.
     def device_driven(self):
-        st, gtimer, prob, like = self.st, self.gtimer, self.prob, self.like
-        history, log, backtracking, recording = self.history, self.log, self.backtracking, self.recording
+        st, rec, prob, backtracking, recording = self.st, self.rec, self.prob, self.backtracking, self.rec.recording
         cap = _HISTORY_CHUNK_BYTES // (8 * prob.n_dev) if recording else self.max_iter
         chunk = max(1, min(int(self.check_every or (16 if recording else 8)), cap))
         done, started_total, ls_t0 = 0, 0, time.perf_counter()
-        rr_seen, norms = [], []                # rr_seen[t]: residual of the iterate iteration t started from
+        rr_seen, shrinks = [], []              # rr_seen[t]: residual of the iterate iteration t started from
         while done < self.max_iter:
             todo = min(chunk, self.max_iter - done)
-            ev = gtimer.start()
+            ev = rec.timer.start()
             if recording:
-                rec = st.run_recorded(todo, backtracking, self.eta, C, self.grad_eps, want_rr=history is not None)
+                out = st.run_recorded(todo, backtracking, self.eta, C, self.grad_eps, want_rr=rec.objectives)
             else:
                 pair = st.run_backtracking(todo, self.eta, C, self.grad_eps)
-                rec = None if pair is None else dict(ls=pair[0], taus=pair[1])
-            if rec is None:                                   # this plan has no candidate pass: the host drives
-                gtimer.pending.clear()
+                out = None if pair is None else dict(ls=pair[0], taus=pair[1])
+            if out is None:                                   # this plan has no candidate pass: the host drives
+                rec.timer.pending.clear()
                 return False
             s = st.status()                                   # synchronises: k, stop / stall flag
             ran = int(s.k) - done
             stalled = s.stopped == _lib.STOP_LS_STALL
             started = ran + (1 if (stalled or s.stopped == _lib.STOP_GRAD) else 0)
-            gtimer.stop(ev, max(started, 1))
+            rec.timer.stop(ev, max(started, 1))
             started_total += started
             if backtracking:
-                ls_call_iters.extend(int(v) for v in rec["ls"][:ran].cpu().tolist())
+                shrinks.extend(out["ls"][:ran].cpu().tolist())
             if recording:
-                if history is not None:
-                    rr_seen.extend(rec["rr_seen"][:started].cpu().tolist())
-                hs = rec["hist"][:ran].cpu().numpy()
-                xh = prob.vec_out(rec["x"][:ran])
-                rows = [_core.from_device_vec(xh[i], like) for i in range(ran)] if self.as_tensor else list(xh.cpu().numpy())
-                if history is not None:
-                    history["x"].extend(rows)
-                if log is not None:                            # ista's log (ref:117-120): x, the step used, ||dx||
-                    log["x"].extend(rows)
-                    log["t"].extend(rec["taus"][:ran].cpu().tolist() if backtracking else [self.tau] * ran)
-                    log["delta"].extend(float(math.sqrt(r[3])) for r in hs)
-                norms.extend((float(r[1]), float(r[2])) for r in hs)
+                if rec.objectives:
+                    rr_seen.extend(out["rr_seen"][:started].cpu().tolist())
+                rec.block(prob.vec_out(out["x"][:ran]), out["hist"][:ran].cpu().numpy(),
+                          out["taus"][:ran] if backtracking else [self.tau] * ran, rr_known=False)
             done += ran
             if stalled:                                       # finish this iteration's search on the host
                 tau = st.resume_after_stall()
                 tau, steps = self.search_on_host(tau, _BATCH)
                 self.tau = tau
-                ls_call_iters.append(steps)
+                shrinks.append(steps)
                 st.set_tau(tau)
                 st.update()
                 s = st.status()
                 if recording:
-                    row = _core.from_device_vec(st.x_tensor(), like)
-                    if history is not None:
-                        history["x"].append(row)
-                    if log is not None:
-                        log["x"].append(row)
-                        log["t"].append(tau)
-                        log["delta"].append(s.this_step)
-                    norms.append((s.xnorm1, s.xnorm2))
+                    rec.one(st.x_tensor(), s, tau)
                 done += 1
             if s.stopped != _lib.STOP_NONE:
                 break
-        gtimer.flush()
-        del grad_call_times[started_total:]
+        rec.gradients(started_total)
         if backtracking:
-            share = (time.perf_counter() - ls_t0) / max(len(ls_call_iters), 1)
-            ls_call_times.extend([share] * len(ls_call_iters))    # the device does not time its phases: equal shares
+            rec.searches(shrinks, time.perf_counter() - ls_t0)
         # f(x after iteration t) needs ||A x - b||^2 of that iterate: seen by iteration t + 1, or by a closing pass
-        if history is not None:
+        if rec.objectives:
             rr_of = rr_seen[1:done + 1]
             if len(rr_of) < done:
                 rr_of.append(prob.residual_objective(st.x_tensor())[0])
-            history["obj"].extend(self.history_obj(rr, x2, x1) for rr, (x1, x2) in zip(rr_of, norms))
+            rec.settle(rr_of)
         return True
 
     # ---- 5. the host drives every iteration: split-form sharding over torch.distributed (the all-reduce sits between
@@ -372,55 +428,44 @@ class _Run:
     # pass of iteration k also returns ||A x_k - b||^2, so f(x_k) is appended one iteration late and only the very last
     # iterate needs a residual pass of its own.
     def host_driven(self):
-        st, gtimer, prob, like, reducer = self.st, self.gtimer, self.prob, self.like, self.reducer
-        history, log, tol, tol_ratio = self.history, self.log, self.tol, self.tol_ratio
+        st, rec, prob, reducer, tol, tol_ratio = self.st, self.rec, self.prob, self.reducer, self.tol, self.tol_ratio
 
         def rr_x_of(status):         # ||A x_k - b||^2 over ALL rows (split-form sharding: summed here)
             return reducer.sum([status.rr_x])[0] if reducer is not None else status.rr_x
 
-        owed = None                  # (||x||_1, ||x||_2^2) of the newest iterate whose objective is not recorded yet
         for _ in range(self.max_iter):
-            ev = gtimer.start()
-            st.grad(dual=owed is not None)                        # ref:173-175 (alpha2*y is added by the consumers)
+            ev = rec.timer.start()
+            st.grad(dual=bool(rec.owed))                          # ref:173-175 (alpha2*y is added by the consumers)
             if reducer is not None:
                 reducer.grad()
-            gtimer.stop(ev)
+            rec.timer.stop(ev)
             if self.grad_tol_check and tol > 0.0:                 # ref:179
                 if math.sqrt(st.trial(self.tau, with_residual=False)["gnorm2"]) < tol:
-                    if owed is not None:
-                        history["obj"].append(self.history_obj(rr_x_of(st.status()), owed[1], owed[0]))
-                        owed = None
+                    if rec.owed:
+                        rec.settle([rr_x_of(st.status())])
                     break
             if self.backtracking:                                 # ref:183-197 / ref:298-312 / ref:92-108
                 ls_t0 = time.perf_counter()
-                t_k, bt_steps = self.search_on_host(self.tau, 0)
-                ls_call_times.append(time.perf_counter() - ls_t0)
-                ls_call_iters.append(bt_steps)
-                self.tau = t_k
+                self.tau, bt_steps = self.search_on_host(self.tau, 0)
+                rec.searches([bt_steps], time.perf_counter() - ls_t0)
                 st.set_tau(self.tau)
             st.update()                                           # ref:200-221
-            if self.recording:
+            if rec.recording:
                 xk = st.x_tensor()
                 s = st.status()
-                if history is not None:
-                    if owed is not None:
-                        history["obj"].append(self.history_obj(rr_x_of(s), owed[1], owed[0]))
-                    history["x"].append(_core.from_device_vec(xk, like))
-                    owed = (s.xnorm1, s.xnorm2)
-                if log is not None:
-                    log["x"].append(_core.from_device_vec(xk, like))
-                    log["t"].append(self.tau)
-                    log["delta"].append(s.this_step)
+                if rec.owed:
+                    rec.settle([rr_x_of(s)])
+                rec.one(xk, s, self.tau)
             else:
                 s = st.status() if (tol > 0.0 or tol_ratio > 0.0) else None
             if s is not None and s.stopped != _lib.STOP_NONE:     # ref:238, :242
                 break
-        if owed is not None:
+        if rec.owed:
             rr, x2, x1 = prob.residual_objective(st.x_tensor())
             if reducer is not None:
                 rr = reducer.sum([rr])[0]
-            history["obj"].append(self.history_obj(rr, x2, x1))
-        gtimer.flush()
+            rec.settle([rr], [(x1, x2)])
+        rec.gradients()
         return True
 
 
@@ -430,7 +475,10 @@ def _drive(prob, like, *, mode, prox_kind, alpha1, alpha2, tau, delta=0.0, backt
            batch_trials=True, reducer=None, state=None):
     """Run the state machine with the first execution strategy of `_Run` that serves this configuration: device-driven
     wherever nothing needs a per-iteration host decision, host-driven otherwise (split-form sharding, ref:179 / :183-197 /
-    :224-232 on plans without the device forms)."""
+    :224-232 on plans without the device forms).  `like`: a `_core.Like` or the caller's own array.
+    batch_trials=False: the searches of a streaming problem run in the host-driven loop with one candidate per pass over A
+    (fos_fista_trial) - the sequential search that tests and tools hold the 16-candidate one against."""
+    like = like if isinstance(like, _core.Like) else _core.Like(like)
     st = state if state is not None else _core.Fista(prob)      # `state`: a stand-in with the same interface (CPU tests)
     x0_dev = None if x0 is None else _core.to_device_vec(x0, prob.device).double()   # padded by Fista.reset
     # reducer: split-form sharding - the all-reduce sits between the gradient and the update, so the host drives
@@ -439,9 +487,9 @@ def _drive(prob, like, *, mode, prox_kind, alpha1, alpha2, tau, delta=0.0, backt
     # between grad() and update() when the host drives anyway
     device_loop = reducer is None                               # every such configuration has an enqueue-only form
     dev_grad_stop = grad_tol_check and tol > 0.0 and (not host_needed or device_loop)
-    st.reset(tau, alpha1, alpha2, mode=mode, prox_kind=prox_kind, delta=delta, adaptive_restart=adaptive_restart,
-             restart_threshold=restart_threshold, tol_step=tol if tol > 0.0 else 0.0,
-             tol_ratio=tol_ratio if tol_ratio > 0.0 else 0.0, x0=x0_dev, **({"tol_grad": tol} if dev_grad_stop else {}))
+    prm = _params(tau, alpha1, alpha2, mode=mode, prox_kind=prox_kind, delta=delta, tol=_pos(tol), tol_ratio=_pos(tol_ratio),
+                  grad_rule=dev_grad_stop, adaptive_restart=adaptive_restart, restart_threshold=restart_threshold)
+    st.reset(x0=x0_dev, **prm)
     # Backtracking decides on a cancelling sum (grad.dlt): take the gradient from the fp64-accumulating pass then; in
     # split-form sharding the state machine keeps it in a tensor of ours and the reducer sums the n + 1 doubles
     grad_eps = 8.0 * _EPS32
@@ -453,23 +501,56 @@ def _drive(prob, like, *, mode, prox_kind, alpha1, alpha2, tau, delta=0.0, backt
             st.set_precise(True, own_buffer=True)
             reducer.gbuf64 = st.gbuf64
             grad_eps = 64.0 * _EPS64
-    run = _Run(prob, like, st, tau=tau, eta=eta, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio, backtracking=backtracking,
-               grad_tol_check=grad_tol_check, history=history, history_obj=history_obj, log=log, check_every=check_every,
-               reducer=reducer, smooth_a2=alpha2 if (prox_kind == _lib.PROX_L1 and alpha2 > 0) else 0.0,
-               grad_eps=grad_eps, batch_trials=batch_trials)
+    rec = _Records(like, history, history_obj, log, timer=getattr(st, "make_timer", _EventTimer))   # stand-in states bring a host timer
+    run = _Run(prob, st, rec, tau=tau, eta=eta, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio, backtracking=backtracking,
+               grad_tol_check=grad_tol_check, check_every=check_every, reducer=reducer,
+               smooth_a2=alpha2 if (prox_kind == _lib.PROX_L1 and alpha2 > 0) else 0.0, grad_eps=grad_eps,
+               batch_trials=batch_trials)
     if not host_needed:
         run.enqueue_only()
         return st
     on_device = reducer is None and max_iter > 0
     if on_device and run.resident():
         return st
-    plain = not (mode == _lib.MODE_FISTA and adaptive_restart) and tol == 0.0 and tol_ratio == 0.0
+    plain = not prm["adaptive_restart"] and tol == 0.0 and tol_ratio == 0.0
     if on_device and history is not None and log is None and not backtracking and plain and run.history_plain():
         return st
-    if on_device and hasattr(st, "run_recorded") and (run.recording or backtracking) and run.device_driven():
+    if on_device and batch_trials and hasattr(st, "run_recorded") and (rec.recording or backtracking) and run.device_driven():
         return st
     run.host_driven()
     return st
+
+
+def _tau(L, alpha2, t_init_factor):
+    """First step: t_init_factor / L, the ridge term being part of the smooth function (ref:156-158)."""
+    return t_init_factor / (L + (alpha2 if alpha2 > 0 else 0.0))
+
+
+class _Loop(collections.namedtuple("_Loop", "delta alpha1 alpha2 backtracking eta t_init_factor max_iter tol tol_ratio "
+                                            "adaptive_restart restart_threshold")):
+    """The arguments of the reference's loop as fista (delta None) and fista_delta take them, and what follows from them
+    alone: every form of a call - single, several targets, batch - hands them on as they are."""
+    __slots__ = ()
+
+    @property
+    def mode(self):
+        return _lib.MODE_FISTA if self.delta is None else _lib.MODE_DELTA
+
+    def tau(self, L):
+        return _tau(L, self.alpha2, self.t_init_factor)
+
+    def params(self, tau):
+        """`_params` of a run that starts from x = 0 and carries all its stopping rules on the device (lockstep and batch
+        launches): fista's tol is also the gradient-norm rule, fista_delta's a step stop only."""
+        return _params(tau, self.alpha1, self.alpha2, mode=self.mode, delta=self.delta, tol=_pos(self.tol),
+                       tol_ratio=_pos(self.tol_ratio), grad_rule=self.delta is None, adaptive_restart=self.adaptive_restart,
+                       restart_threshold=self.restart_threshold)
+
+    def drive(self, prob, like, tau, **kw):
+        return _drive(prob, like, mode=self.mode, prox_kind=_lib.PROX_L1, alpha1=self.alpha1, alpha2=self.alpha2, tau=tau,
+                      delta=self.delta, backtracking=self.backtracking, eta=self.eta, max_iter=self.max_iter, tol=self.tol,
+                      tol_ratio=self.tol_ratio, adaptive_restart=self.adaptive_restart,
+                      restart_threshold=self.restart_threshold, grad_tol_check=self.delta is None, **kw)
 
 
 def _objective_by_alpha(alpha1, alpha2):
@@ -651,94 +732,69 @@ def _targets(A, b):
     return None if shape[0] * shape[1] == m else b
 
 
-def _metrics_apart(fn):
-    """Run `fn` (one single-target solve) against empty metric lists, then put the earlier entries back in front: the
-    solve's own bookkeeping indexes the lists from their start."""
+def _metrics_of(fn):
+    """Run `fn` (one sub-solve) against empty metric lists - its own bookkeeping indexes them from their start - and return
+    (its result, the three lists it recorded); the earlier entries are back in place afterwards."""
     lists = (grad_call_times, ls_call_times, ls_call_iters)
     saved = [list(v) for v in lists]
     reset_metrics()
     try:
-        return fn()
+        return fn(), tuple(list(v) for v in lists)
     finally:
         for v, old in zip(lists, saved):
-            v[:0] = old
+            v[:] = old
 
 
-def _solve_targets(A, B, *, delta, alpha1, alpha2, backtracking, eta, t_init_factor, max_iter, tol, tol_ratio,
-                   adaptive_restart, restart_threshold, L, dtype, check_every, sharded, return_history):
+def _metrics_add(recorded):
+    for v, new in zip((grad_call_times, ls_call_times, ls_call_iters), recorded):
+        v.extend(new)
+
+
+def _solve_targets(A, B, lp, L, dtype, check_every):
     """X[:, j] = fista(A, B[:, j], ...) (fista_delta when `delta` is given) for every column j, with A bound once and L
     estimated once.  Groups of up to 16 columns advance in lockstep on one read of A per iteration
     (fos_fista_run_multi_rhs); what the lockstep does not serve - shapes without a multi-vector kernel, a last group of
     one column, backtracking, fista's gradient-norm rule (tol > 0) - runs column by column on sibling problems that borrow
     the same device A.  A that fits one CU's LDS (the resident plan): every column in one launch, one workgroup each."""
-    if sharded:
-        raise ValueError("a 2-D b (several targets) cannot be combined with comm= / group= / cols=")
-    if return_history:
-        raise ValueError("return_history=True is not available with a 2-D b (several targets)")
     prob = _core.prepare(A, None, dtype)
     like = prob.like
-    Bt = B.detach() if _core.is_tensor(B) else torch.from_numpy(np.ascontiguousarray(np.asarray(B)))
-    Bt = Bt.to(device=prob.device, dtype=torch.float32).contiguous()
+    Bt = _core.to_device(B, prob.device)
     if Bt.shape[0] != prob.m:
         raise ValueError("b must have m rows")
     k = int(Bt.shape[1])
-    L_val = float(L) if L is not None else estimate_lipschitz(prob)                    # once for all columns
-    if alpha2 > 0:
-        L_val += alpha2
-    tau = t_init_factor / L_val
-    mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
-    restart = bool(adaptive_restart) and delta is None
+    tau = lp.tau(_lipschitz(prob, L))                                                  # once for all columns
+    prm = lp.params(tau)
     # fista's tol is also the gradient-norm rule, which sits before the update; fista_delta's is a step stop only
-    lockstep = not backtracking and (tol == 0.0 or delta is not None)
-
-    def one(j):
-        sib = prob.sibling(Bt[:, j].contiguous())
-        return _metrics_apart(lambda: _drive(
-            sib, like, mode=mode, prox_kind=_lib.PROX_L1, alpha1=alpha1, alpha2=alpha2, tau=tau, delta=delta or 0.0,
-            backtracking=backtracking, eta=eta, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio, adaptive_restart=restart,
-            restart_threshold=restart_threshold, grad_tol_check=delta is None, check_every=check_every)).x_tensor()
+    lockstep = not lp.backtracking and (lp.tol == 0.0 or lp.delta is not None)
 
     if prob.plan()["resident"]:
         # A fits one CU's LDS: all k columns in ONE launch, one workgroup per column on the shared A (fos_fista_run_batch),
         # each computing what the column's own single-target run computes - backtracking and tol > 0 included
-        m, n_dev = prob.m, prob.n_dev
-        prm = _lib.FistaParams(tau=tau, alpha1=alpha1, alpha2=alpha2, delta=delta or 0.0, restart_threshold=restart_threshold,
-                               tol_step=tol if tol > 0.0 else 0.0, tol_ratio=tol_ratio if tol_ratio > 0.0 else 0.0,
-                               tol_grad=tol if (delta is None and tol > 0.0) else 0.0, mode=mode, prox_kind=_lib.PROX_L1,
-                               adaptive_restart=int(restart), reserved=0)
-        cols = types.SimpleNamespace(shapes=[(m, prob.n)] * k, likes=[None] * k, device=prob.device, ldx=n_dev)
-        group = dict(idx=list(range(k)), A=prob.A, B=Bt.t().contiguous(),          # (k, m): column j at j*m
-                     items=[(0, prob.lda, j * m, m, n_dev) for j in range(k)])
-        xs, metrics = [None] * k, [None] * k
-        _run_batch_group(cols, prob.dtype, group, list(range(k)), [prm] * k, max_iter, backtracking, eta, False, delta,
-                         None, xs, None, metrics)
-        for g_t, l_t, l_i in metrics:
-            grad_call_times.extend(g_t)
-            ls_call_times.extend(l_t)
-            ls_call_iters.extend(l_i)
+        bt = _Batch.targets(prob, Bt)
+        xs = []
+        for x, _, recorded in _run_batch_group(bt, prob.dtype, range(k), [_lib.FistaParams(**prm)] * k, lp):
+            xs.append(x)
+            _metrics_add(recorded)
         return _core.from_device_vec(torch.stack(xs, dim=1), like)
     X = torch.zeros(prob.n, k, dtype=torch.float64, device=prob.device)
     width = 4 if k <= 4 else 16            # up to 4: the multi-vector VALU pass where the shape has one; else matrix cores
     for g0 in range(0, k, width):
         g1 = min(k, g0 + width)
         if lockstep and g1 - g0 >= 2:
-            handles = []
-            for _ in range(g0, g1):
-                st = _core.Fista(prob)
-                st.reset(tau, alpha1, alpha2, mode=mode, delta=delta or 0.0, adaptive_restart=restart,
-                         restart_threshold=restart_threshold, tol_step=tol if tol > 0.0 else 0.0,
-                         tol_ratio=tol_ratio if tol_ratio > 0.0 else 0.0)
-                handles.append(st)
+            handles = [_new_state(prob, prm) for _ in range(g0, g1)]
             gtimer = _EventTimer(grad_call_times)
             ev = gtimer.start()
-            if _core.run_multi_rhs(handles, Bt[:, g0:g1], max_iter):
-                gtimer.stop(ev, max_iter)                  # one gradient per lockstep iteration, as fista_path counts
+            if _core.run_multi_rhs(handles, Bt[:, g0:g1], lp.max_iter):
+                gtimer.stop(ev, lp.max_iter)                  # one gradient per lockstep iteration, as fista_path counts
                 gtimer.flush()
                 for j, st in zip(range(g0, g1), handles):
                     X[:, j] = st.x_tensor()
                 continue
         for j in range(g0, g1):
-            X[:, j] = one(j)
+            st, recorded = _metrics_of(lambda: lp.drive(prob.sibling(Bt[:, j].contiguous()), like, tau,
+                                                        check_every=check_every))
+            _metrics_add(recorded)
+            X[:, j] = st.x_tensor()
     return _core.from_device_vec(X, like)
 
 
@@ -756,11 +812,9 @@ def _ndim(x):
     return len(x.shape) if hasattr(x, "shape") else np.ndim(x)
 
 
-def _batch_members(A, b, sharded):
+def _batch_members(A, b):
     """The problems of a batch call as (matrices, vectors) - 2-D / 1-D host or device objects, not yet converted - after
     the checks that refuse a call before any device work."""
-    if sharded:
-        raise ValueError("a batch (3-D A or a sequence of matrices) cannot be combined with comm= / group= / cols=")
     if b is None:
         raise ValueError("a batch needs b: (P, m) for a 3-D A, a sequence of vectors for a sequence of matrices")
     if not isinstance(b, (list, tuple)) and _ndim(b) == 3:
@@ -801,10 +855,7 @@ class _Batch:
         self.mats, self.vecs, self.P = mats, vecs, len(mats)
         self.likes = [_core.Like(Ai) for Ai in mats]
         self.shapes = [(int(Ai.shape[0]), int(Ai.shape[1])) for Ai in mats]
-        self.kinds = []                          # per problem: "f32" / "bf16"
-        for Ai in mats:
-            bf16 = (dtype in ("bf16", torch.bfloat16)) or (dtype is None and _core.is_tensor(Ai) and Ai.dtype == torch.bfloat16)
-            self.kinds.append("bf16" if bf16 else "f32")
+        self.kinds = ["bf16" if _core.stores_bf16(Ai, dtype) else "f32" for Ai in mats]
         self.fits = [_core.resident_fits(m, n) for m, n in self.shapes]
         self.groups = {}                         # dtype -> dict(idx, A, B, items)
         if any(self.fits):
@@ -816,6 +867,16 @@ class _Batch:
             if idx:
                 self.groups[kind] = self._bind(idx, torch.bfloat16 if kind == "bf16" else torch.float32)
         self.ldx = max([n for (m, n), ok in zip(self.shapes, self.fits) if ok] or [1])
+
+    @classmethod
+    def targets(cls, prob, Bt):
+        """One bound A within the resident limits with the k columns of Bt (m x k, device) as right-hand sides: k members
+        on the same elements, whose results stay on the device (likes None)."""
+        bt, k, m = cls.__new__(cls), int(Bt.shape[1]), prob.m
+        bt.P, bt.shapes, bt.likes, bt.device, bt.ldx = k, [(m, prob.n)] * k, [None] * k, prob.device, prob.n_dev
+        bt.groups = {prob.dtype: dict(idx=list(range(k)), A=prob.A, B=Bt.t().contiguous(),     # (k, m): column j at j*m
+                                      items=[(0, prob.lda, j * m, m, prob.n_dev) for j in range(k)])}
+        return bt
 
     def _bind(self, idx, tdtype):
         dev = self.device
@@ -846,7 +907,7 @@ class _Batch:
 
     def problem(self, i):
         """The single path's Problem of member i (members outside the resident limits)."""
-        return _core.Problem(self.mats[i], self.vecs[i], self.kinds[i] if self.kinds[i] == "bf16" else None)
+        return _core.Problem(self.mats[i], self.vecs[i], "bf16" if self.kinds[i] == "bf16" else None)
 
 
 def _batch_lipschitz(mats, vecs, dtype, n_iter=100, tol=1e-6, batch=None):
@@ -870,11 +931,10 @@ def _batch_lipschitz(mats, vecs, dtype, n_iter=100, tol=1e-6, batch=None):
     return L, probs
 
 
-def _solve_batch(A, b, *, delta, reg_type, alpha1, alpha2, backtracking, eta, t_init_factor, max_iter, tol, tol_ratio,
-                 adaptive_restart, restart_threshold, return_history, L, dtype, sharded):
+def _solve_batch(A, b, reg_type, lp, return_history, L, dtype):
     """X[i] = fista(A[i], b[i], ...) (fista_delta when `delta` is given) for every member, the resident ones in one
     launch (one workgroup per problem, fos_fista_run_batch), the others one by one through the single path."""
-    mats, vecs = _batch_members(A, b, sharded)
+    mats, vecs = _batch_members(A, b)
     P = len(mats)
     L_given = _batch_L(L, P)
     bt = _Batch(mats, vecs, dtype)
@@ -882,42 +942,27 @@ def _solve_batch(A, b, *, delta, reg_type, alpha1, alpha2, backtracking, eta, t_
         L_vals, probs = _batch_lipschitz(mats, vecs, dtype, batch=bt)
     else:
         L_vals, probs = L_given, {}
-    mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
-    obj = _objective_by_alpha(alpha1, alpha2) if delta is None else _objective_by_reg(reg_type, alpha1, alpha2)
-    a2_smooth = alpha2 if alpha2 > 0 else 0.0
-    taus = [t_init_factor / (Li + a2_smooth) for Li in L_vals]
-    xs, hists = [None] * P, [None] * P
-    metrics = [([], [], []) for _ in range(P)]       # per problem: grad times, ls times, ls iters
-    prm_of = lambda i: _lib.FistaParams(                                               # noqa: E731 (what _drive resets)
-        tau=taus[i], alpha1=alpha1, alpha2=alpha2, delta=delta or 0.0, restart_threshold=restart_threshold,
-        tol_step=tol if tol > 0.0 else 0.0, tol_ratio=tol_ratio if tol_ratio > 0.0 else 0.0,
-        tol_grad=tol if (delta is None and tol > 0.0) else 0.0, mode=mode, prox_kind=_lib.PROX_L1,
-        adaptive_restart=int(bool(adaptive_restart) and delta is None), reserved=0)
+    obj = (_objective_by_alpha(lp.alpha1, lp.alpha2) if lp.delta is None
+           else _objective_by_reg(reg_type, lp.alpha1, lp.alpha2))
+    fields = lp.params(1.0)                          # the members' parameters differ in the first step only
+    results = [None] * P                             # per problem: (x, history or None, the metric entries it recorded)
     for kind, g in bt.groups.items():
         idx = g["idx"]
         # the device-side x history is bounded like the single path's chunks: split the batch where it would exceed it
-        per = max(1, _HISTORY_CHUNK_BYTES // (8 * max(max_iter, 1) * bt.ldx)) if return_history else len(idx)
+        per = max(1, _HISTORY_CHUNK_BYTES // (8 * max(lp.max_iter, 1) * bt.ldx)) if return_history else len(idx)
         for c0 in range(0, len(idx), per):
-            sub = list(range(c0, min(len(idx), c0 + per)))
-            _run_batch_group(bt, kind, g, sub, [prm_of(idx[r]) for r in sub], max_iter, backtracking, eta,
-                             return_history, delta, obj, xs, hists, metrics)
+            sub = range(c0, min(len(idx), c0 + per))
+            params = [_lib.FistaParams(**dict(fields, tau=lp.tau(L_vals[idx[r]]))) for r in sub]
+            for r, res in zip(sub, _run_batch_group(bt, kind, sub, params, lp, return_history, obj)):
+                results[idx[r]] = res
     for i in range(P):
-        if bt.fits[i]:
-            continue
-        prob = probs.get(i) or bt.problem(i)
-        fn = fista if delta is None else functools.partial(fista_delta, delta=delta)
-        kw = dict(backtracking=backtracking, eta=eta, t_init_factor=t_init_factor, max_iter=max_iter, tol=tol,
-                  tol_ratio=tol_ratio, return_history=return_history, L=L_vals[i])
-        if delta is None:
-            kw.update(adaptive_restart=adaptive_restart, restart_threshold=restart_threshold)
-        res = fn(prob, None, reg_type, alpha1, alpha2, **kw)
-        xs[i], hists[i] = (res if return_history else (res, None))
-        metrics[i] = (list(grad_call_times), list(ls_call_times), list(ls_call_iters))
-    reset_metrics()
-    for g_t, l_t, l_i in metrics:
-        grad_call_times.extend(g_t)
-        ls_call_times.extend(l_t)
-        ls_call_iters.extend(l_i)
+        if not bt.fits[i]:
+            res, recorded = _metrics_of(lambda: _solve_one(probs.get(i) or bt.problem(i), None, reg_type, lp, return_history,
+                                                           L_vals[i]))
+            results[i] = (res if return_history else (res, None)) + (recorded,)
+    for _, _, recorded in results:
+        _metrics_add(recorded)
+    xs, hists = [r[0] for r in results], [r[1] for r in results]
     if isinstance(A, (list, tuple)):
         X = xs
     elif _core.is_tensor(A):                 # each row is the single call's result (a tensor of that kind): stacked
@@ -928,9 +973,10 @@ def _solve_batch(A, b, *, delta, reg_type, alpha1, alpha2, backtracking, eta, t_
     return (X, hists) if return_history else X
 
 
-def _run_batch_group(bt, kind, g, sub, params, max_iter, backtracking, eta, record, delta, obj, xs, hists, metrics):
-    """One fos_fista_run_batch launch (two for a ragged batch) over the members g["idx"][r], r in sub; results, history
-    and each member's metric lists go into xs / hists / metrics at the members' places."""
+def _run_batch_group(bt, kind, sub, params, lp, record=False, obj=None):
+    """One fos_fista_run_batch launch (two for a ragged batch) over the members r in `sub` of the group bt.groups[kind].
+    Per member: (x, its history or None, the three metric lists it recorded)."""
+    g, backtracking = bt.groups[kind], lp.backtracking
     idx = [g["idx"][r] for r in sub]
     items = [g["items"][r] for r in sub]
     t0 = time.perf_counter()
@@ -938,7 +984,7 @@ def _run_batch_group(bt, kind, g, sub, params, max_iter, backtracking, eta, reco
     ev1 = torch.cuda.Event(enable_timing=True)
     with torch.cuda.device(bt.device):
         ev0.record()
-        out = _core.run_batch(g["A"], kind, g["B"], items, params, max_iter, backtracking=backtracking, eta=eta,
+        out = _core.run_batch(g["A"], kind, g["B"], items, params, lp.max_iter, backtracking=backtracking, eta=lp.eta,
                               armijo_c=C, ldx=bt.ldx, record=record)
         ev1.record()
         ev1.synchronize()
@@ -947,31 +993,74 @@ def _run_batch_group(bt, kind, g, sub, params, max_iter, backtracking, eta, reco
     stopped = out["stopped"].cpu().tolist()
     ls = out["ls"].cpu().tolist() if backtracking else None
     xs_dev = out["x"]
-    # one gradient per completed iteration plus the one whose norm ended the run (_Run.resident); the device does not time
-    # its phases: the launch's time in equal shares over the gradients, the searches' wall time over the searches
-    ngrad = [k + (1 if s == _lib.STOP_GRAD else 0) for k, s in zip(done, stopped)]
-    g_share = ev0.elapsed_time(ev1) * 1e-3 / max(sum(ngrad), 1)
-    l_share = wall / max(sum(done), 1)
+    # the launch's time in equal shares over the gradients of all its members, the searches' wall time over all its searches
+    ngrad = [_ngrad(k, s) for k, s in zip(done, stopped)]
+    dev_s, ngrad_all, done_all = ev0.elapsed_time(ev1) * 1e-3, sum(ngrad), sum(done)
     hs = out["hist"].cpu().numpy() if record else None
+    results = []
     for r, i in enumerate(idx):
         n, like, k = bt.shapes[i][1], bt.likes[i], done[r]
-        xs[i] = xs_dev[r, :n] if like is None else _core.from_device_vec(xs_dev[r, :n], like)
-        metrics[i] = ([g_share] * ngrad[r], [l_share] * k if backtracking else [],
-                      [int(v) for v in ls[r][:k]] if backtracking else [])
+        x = xs_dev[r, :n] if like is None else _core.from_device_vec(xs_dev[r, :n], like)     # None: stays on the device
+        h = None
         if record:
-            xh = out["x_hist"][r, :k, :n]
-            rows = [_core.from_device_vec(xh[t], like) for t in range(k)] if like.tensor else list(xh.cpu().numpy())
-            h = {"x": [] if delta is not None else [_core.from_device_vec(torch.zeros(n, dtype=torch.float64,
-                                                                                       device=bt.device), like)],
-                 "obj": []}
-            h["x"].extend(rows)
-            h["obj"].extend(obj(float(q[0]), float(q[2]), float(q[1])) for q in hs[r, :k])
-            hists[i] = h
+            zero = torch.zeros(n, dtype=torch.float64, device=bt.device)
+            h = {"x": [_core.from_device_vec(zero, like)] if lp.delta is None else [], "obj": []}   # ref:160 / ref:279
+            _Records(like, h, obj).block(out["x_hist"][r, :k, :n], hs[r, :k])
+        results.append((x, h, (_shares(ngrad[r], dev_s, ngrad_all), _shares(k, wall, done_all) if backtracking else [],
+                               [int(v) for v in ls[r][:k]] if backtracking else [])))
+    return results
 
 
 # ---------------------------------------------------------------------
 # FISTA                                                        ref:132-245
+# FISTA-Δ                                                      ref:251-344
 # ---------------------------------------------------------------------
+def _lipschitz(prob, L, *, comm=None, cols=None, group=None):
+    """L as the caller gave it, or estimated the way the problem is sharded (ref:155 / :273): one power iteration, one draw
+    from the global NumPy stream."""
+    if L is not None:
+        return float(L)
+    if cols is not None:
+        return _lipschitz_cols(prob, comm, cols)
+    return estimate_lipschitz(prob, group=group)
+
+
+def _solve(A, b, reg_type, lp, return_history, L, dtype, check_every, comm, group, cols):
+    """The front end of fista and fista_delta: a batch, several targets or one problem, sharded or not."""
+    reset_metrics()
+    batch = _is_batch(A)
+    B = None if batch else _targets(A, b)
+    if batch or B is not None:
+        if any(v is not None for v in (comm, group, cols)):
+            what = "a batch (3-D A or a sequence of matrices)" if batch else "a 2-D b (several targets)"
+            raise ValueError(f"{what} cannot be combined with comm= / group= / cols=")
+        if batch:
+            return _solve_batch(A, b, reg_type, lp, return_history, L, dtype)
+        if return_history:
+            raise ValueError("return_history=True is not available with a 2-D b (several targets)")
+        return _solve_targets(A, B, lp, L, dtype, check_every)
+    prob, reducer = _sharded_problem(A, b, dtype, comm, group, cols)
+    return _solve_one(prob, reducer, reg_type, lp, return_history, L, check_every, comm, cols, group)
+
+
+def _solve_one(prob, reducer, reg_type, lp, return_history, L, check_every=None, comm=None, cols=None, group=None):
+    """One problem bound to the device: fista (ref:132-245), or fista_delta (ref:251-344) when `delta` is given.  The two
+    differ in the momentum rule, in fista's gradient-norm stop and restarts, and in what the history holds."""
+    like = prob.like
+    L_val = _lipschitz(prob, L, comm=comm, cols=cols, group=group if reducer is not None else None)
+    history = obj = None
+    if lp.delta is None:
+        obj = _objective_by_alpha(lp.alpha1, lp.alpha2)
+        if return_history:
+            zero = torch.zeros(prob.n, dtype=torch.float64, device=prob.device)
+            history = {"x": [_core.from_device_vec(zero, like)], "obj": []}      # ref:160
+    elif return_history:
+        history, obj = {"x": [], "obj": []}, _objective_by_reg(reg_type, lp.alpha1, lp.alpha2)   # ref:279 (no x0 entry)
+    st = lp.drive(prob, like, lp.tau(L_val), history=history, history_obj=obj, check_every=check_every, reducer=reducer)
+    x_k = _core.from_device_vec(st.x_tensor(), like)
+    return (x_k, history) if return_history else x_k
+
+
 def fista(A, b, reg_type: str, alpha1: float, alpha2: float, backtracking: bool = False, eta: float = 0.5,
           t_init_factor: float = 1.0, max_iter: int = 500, tol: float = 0.0, tol_ratio: float = 0.0,
           adaptive_restart: bool = False, restart_threshold: float = 1.0, return_history: bool = False,
@@ -985,47 +1074,11 @@ def fista(A, b, reg_type: str, alpha1: float, alpha2: float, backtracking: bool 
     an m-vector per iteration (backtracking: plus ONE all-reduce of the 16 candidates' m-vectors per search).
     Several targets: a 2-D ``b`` of shape (m, k), k >= 2, returns x of shape (n, k) whose column j is
     ``fista(A, b[:, j], ...)`` with the same L (estimated once); up to 16 columns share each read of A."""
-    reset_metrics()
-    if _is_batch(A):
-        return _solve_batch(A, b, delta=None, reg_type=reg_type, alpha1=alpha1, alpha2=alpha2, backtracking=backtracking,
-                            eta=eta, t_init_factor=t_init_factor, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio,
-                            adaptive_restart=adaptive_restart, restart_threshold=restart_threshold,
-                            return_history=return_history, L=L, dtype=dtype,
-                            sharded=any(v is not None for v in (comm, group, cols)))
-    B = _targets(A, b)
-    if B is not None:
-        return _solve_targets(A, B, delta=None, alpha1=alpha1, alpha2=alpha2, backtracking=backtracking, eta=eta,
-                              t_init_factor=t_init_factor, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio,
-                              adaptive_restart=adaptive_restart, restart_threshold=restart_threshold, L=L, dtype=dtype,
-                              check_every=check_every, sharded=any(v is not None for v in (comm, group, cols)),
-                              return_history=return_history)
-    prob, reducer = _sharded_problem(A, b, dtype, comm, group, cols)
-    like = prob.like
-    if L is not None:
-        L_val = float(L)
-    elif cols is not None:
-        L_val = _lipschitz_cols(prob, comm, cols)
-    else:
-        L_val = estimate_lipschitz(prob, group=group if reducer is not None else None)                        # ref:155
-    if alpha2 > 0:                                                            # ref:156-157
-        L_val += alpha2
-    tau = t_init_factor / L_val                                               # ref:158
-    history = None
-    if return_history:
-        zero = torch.zeros(prob.n, dtype=torch.float64, device=prob.device)
-        history = {"x": [_core.from_device_vec(zero, like)], "obj": []}      # ref:160
-    st = _drive(prob, like, mode=_lib.MODE_FISTA, prox_kind=_lib.PROX_L1, alpha1=alpha1, alpha2=alpha2, tau=tau,
-                backtracking=backtracking, eta=eta, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio,
-                adaptive_restart=adaptive_restart, restart_threshold=restart_threshold, grad_tol_check=True,
-                history=history, history_obj=_objective_by_alpha(alpha1, alpha2), check_every=check_every,
-                reducer=reducer)
-    x_k = _core.from_device_vec(st.x_tensor(), like)
-    return (x_k, history) if return_history else x_k
+    lp = _Loop(None, alpha1, alpha2, backtracking, eta, t_init_factor, max_iter, tol, tol_ratio, adaptive_restart,
+               restart_threshold)
+    return _solve(A, b, reg_type, lp, return_history, L, dtype, check_every, comm, group, cols)
 
 
-# ---------------------------------------------------------------------
-# FISTA-Δ                                                      ref:251-344
-# ---------------------------------------------------------------------
 def fista_delta(A, b, reg_type: str, alpha1: float, alpha2: float, delta: float, backtracking: bool = False,
                 eta: float = 0.5, t_init_factor: float = 1.0, max_iter: int = 500, tol: float = 0.0,
                 tol_ratio: float = 0.0, return_history: bool = False, *, L=None, dtype=None, check_every=None,
@@ -1033,35 +1086,8 @@ def fista_delta(A, b, reg_type: str, alpha1: float, alpha2: float, delta: float,
     reset_metrics()
     # Course requirement: delta > 2 for convergence guarantee                   ref:268
     assert delta > 2, "In FISTA-Δ, delta must be > 2 for convergence (course requirement)"
-    if _is_batch(A):             # a batch of independent problems: see fista
-        return _solve_batch(A, b, delta=delta, reg_type=reg_type, alpha1=alpha1, alpha2=alpha2, backtracking=backtracking,
-                            eta=eta, t_init_factor=t_init_factor, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio,
-                            adaptive_restart=False, restart_threshold=1.0, return_history=return_history, L=L,
-                            dtype=dtype, sharded=any(v is not None for v in (comm, group, cols)))
-    B = _targets(A, b)
-    if B is not None:            # several targets: see fista
-        return _solve_targets(A, B, delta=delta, alpha1=alpha1, alpha2=alpha2, backtracking=backtracking, eta=eta,
-                              t_init_factor=t_init_factor, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio,
-                              adaptive_restart=False, restart_threshold=1.0, L=L, dtype=dtype, check_every=check_every,
-                              sharded=any(v is not None for v in (comm, group, cols)), return_history=return_history)
-    prob, reducer = _sharded_problem(A, b, dtype, comm, group, cols)
-    like = prob.like
-    if L is not None:
-        L_val = float(L)
-    elif cols is not None:
-        L_val = _lipschitz_cols(prob, comm, cols)
-    else:
-        L_val = estimate_lipschitz(prob, group=group if reducer is not None else None)                        # ref:273
-    if alpha2 > 0:
-        L_val += alpha2
-    tau = t_init_factor / L_val
-    history = {"x": [], "obj": []} if return_history else None               # ref:279 (no x0 entry)
-    obj = _objective_by_reg(reg_type, alpha1, alpha2) if return_history else None
-    st = _drive(prob, like, mode=_lib.MODE_DELTA, prox_kind=_lib.PROX_L1, alpha1=alpha1, alpha2=alpha2, tau=tau,
-                delta=delta, backtracking=backtracking, eta=eta, max_iter=max_iter, tol=tol, tol_ratio=tol_ratio,
-                grad_tol_check=False, history=history, history_obj=obj, check_every=check_every, reducer=reducer)
-    x_k = _core.from_device_vec(st.x_tensor(), like)
-    return (x_k, history) if return_history else x_k
+    lp = _Loop(delta, alpha1, alpha2, backtracking, eta, t_init_factor, max_iter, tol, tol_ratio, False, 1.0)
+    return _solve(A, b, reg_type, lp, return_history, L, dtype, check_every, comm, group, cols)
 
 
 # ---------------------------------------------------------------------
@@ -1092,18 +1118,12 @@ def fista_path(A, b, alphas, t_init_factor: float = 1.0, max_iter: int = 500, *,
         assert delta > 2, "In FISTA-Δ, delta must be > 2 for convergence (course requirement)"
     prob, _ = _sharded_problem(A, b, dtype, comm, None, cols)    # comm: A, b are this rank's rows (matrix-core pass, one
     like = prob.like                                             # all-reduce of the 16 gradients per iteration)
-    if L is not None:
-        L_val = float(L)
-    else:
-        L_val = _lipschitz_cols(prob, comm, cols) if cols is not None else estimate_lipschitz(prob)
+    L_val = _lipschitz(prob, L, comm=comm, cols=cols)
     mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
-    handles = []
-    for a1, a2 in alphas:
-        st = _core.Fista(prob)
-        st.reset(t_init_factor / (L_val + (a2 if a2 > 0 else 0.0)), a1, a2, mode=mode, delta=delta or 0.0,
-                 adaptive_restart=bool(adaptive_restart) and delta is None, restart_threshold=restart_threshold,
-                 tol_step=tol, tol_ratio=tol_ratio, tol_grad=tol if delta is None else 0.0)
-        handles.append(st)
+    # the tolerances go to the device as given: a negative one is refused there (fos_fista_reset), not read as "off"
+    handles = [_new_state(prob, _params(_tau(L_val, a2, t_init_factor), a1, a2, mode=mode, delta=delta, tol=tol,
+                                        tol_ratio=tol_ratio, grad_rule=delta is None, adaptive_restart=adaptive_restart,
+                                        restart_threshold=restart_threshold)) for a1, a2 in alphas]
     gtimer = _EventTimer(grad_call_times)
     # up to 4 weights: the multi-vector VALU pass where the shape has one; up to 16: the matrix-core pass
     width = 4 if len(handles) <= 4 and cols is None else 16

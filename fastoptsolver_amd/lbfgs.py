@@ -19,7 +19,7 @@ import torch.distributed as dist
 
 from . import _core, _lib
 from ._linesearch import LineSearch
-from .iterative_solvers import _EventTimer, _metrics_apart, _targets, grad_call_times, reset_metrics
+from .iterative_solvers import _EventTimer, _metrics_add, _metrics_of, _targets, grad_call_times, reset_metrics
 
 _M, _FACTR, _MAXLS = 10, 1e7, 20
 _EPS = float(np.finfo(np.float64).eps)
@@ -160,7 +160,8 @@ class LBFGSSolver:
 
     def _fit_native(self, ops):
         """The whole iteration under the C ABI (fos_lbfgs_minimize: what SciPy's compiled optimiser is to lbfgs.py:64):
-        line search and memory logic in C++ on the host, every vector on the device, six scalars read per fg."""
+        line search and memory logic in C++ on the host, every vector on the device, six scalars read per fg.
+        Returns the run as a dict: nit, nfev, task, f, history (list), x and iterates ([nit, n] or None) on the device."""
         import ctypes as C
         prob, n = ops.prob, ops.n
         a2 = float(self.alpha2) if self.reg_type in ("ridge", "elasticnet") else 0.0   # lbfgs.py:49-51
@@ -175,16 +176,12 @@ class LBFGSSolver:
         with prob.ctx():
             _lib.check(ops.lib.fos_lbfgs_minimize(prob.h, a2, max_iter, float(self.tol), _core.ptr(x), hist,
                                                   _core.ptr(iterates), fg_ms, cap, C.byref(res)), "fos_lbfgs_minimize")
-        self.nit_, self.nfev_, self.task_ = int(res.nit), int(res.nfev), self._TASKS[res.task]
-        grad_call_times.extend(float(fg_ms[i]) * 1e-3 for i in range(min(self.nfev_, cap)))
+        nit, nfev = int(res.nit), int(res.nfev)
+        grad_call_times.extend(float(fg_ms[i]) * 1e-3 for i in range(min(nfev, cap)))
         l1 = self.reg_type in ("lasso", "elasticnet")
-        self.history_.extend(hist[2 * k] + (self.alpha1 * hist[2 * k + 1] if l1 else 0.0) for k in range(self.nit_))
-        # one conversion (and one copy to the host for ndarray callers) for all iterates; the list holds its rows
-        self.iterates_ = list(ops.to_caller(iterates[: self.nit_])) if keep and self.nit_ else []
-        self.x_ = ops.to_caller(x)                                                    # lbfgs.py:71
-        self.final_obj_ = float(res.f)                                                # lbfgs.py:72
-        self._x_dev = x
-        return self
+        return dict(nit=nit, nfev=nfev, task=self._TASKS[res.task], f=float(res.f), x=x,
+                    history=[hist[2 * k] + (self.alpha1 * hist[2 * k + 1] if l1 else 0.0) for k in range(nit)],
+                    iterates=iterates[:nit] if keep and nit else None)
 
     _LOCKSTEP_MIN, _GROUP = 3, 16         # fos_fista_run_multi's convention: the shared pass pays from three columns on
 
@@ -196,8 +193,7 @@ class LBFGSSolver:
         import ctypes as C
         prob = _core.prepare(A, None)
         lib = _lib.load()
-        Bt = B.detach() if _core.is_tensor(B) else torch.from_numpy(np.ascontiguousarray(np.asarray(B)))
-        Bt = Bt.to(device=prob.device, dtype=torch.float32)
+        Bt = _core.to_device(B, prob.device)
         if Bt.shape[0] != prob.m:
             raise ValueError("b must have m rows")
         k, n = int(Bt.shape[1]), prob.n_dev
@@ -209,12 +205,10 @@ class LBFGSSolver:
         task, fobj, hist_out = [None] * k, np.zeros(k, dtype=np.float64), [[] for _ in range(k)]
 
         def one(j):
-            solo = LBFGSSolver.__new__(LBFGSSolver)
-            solo.reg_type, solo.alpha1, solo.alpha2 = self.reg_type, self.alpha1, self.alpha2
-            solo.max_iter, solo.tol, solo.history_ = self.max_iter, self.tol, []
-            _metrics_apart(lambda: solo._fit_native(_HipOps(prob.sibling(Bt[:, j].contiguous()), None)))
-            X[j] = solo._x_dev
-            nit[j], nfev[j], task[j], fobj[j], hist_out[j] = solo.nit_, solo.nfev_, solo.task_, solo.final_obj_, solo.history_
+            r, recorded = _metrics_of(lambda: self._fit_native(_HipOps(prob.sibling(Bt[:, j].contiguous()), None)))
+            _metrics_add(recorded)
+            X[j] = r["x"]
+            nit[j], nfev[j], task[j], fobj[j], hist_out[j] = r["nit"], r["nfev"], r["task"], r["f"], r["history"]
 
         for g0 in range(0, k, self._GROUP):
             g1 = min(k, g0 + self._GROUP)
@@ -230,7 +224,7 @@ class LBFGSSolver:
                 with prob.ctx():
                     rc = lib.fos_lbfgs_minimize_multi(prob.h, nv, _core.ptr(Bg), nv, a2, max_iter, float(self.tol),
                                                       _core.ptr(X[g0:g1]), n, hist, round_ms, cap, C.byref(rounds), res)
-                if rc == 0:
+                if _lib.served(rc, "fos_lbfgs_minimize_multi"):
                     r = int(rounds.value)
                     times = [float(round_ms[i]) * 1e-3 for i in range(min(r, cap))]
                     grad_call_times.extend(times + [times[-1] if times else 0.0] * (r - len(times)))   # one per round
@@ -240,8 +234,6 @@ class LBFGSSolver:
                         hist_out[j] = [hist[h0 + 2 * i] + (self.alpha1 * hist[h0 + 2 * i + 1] if l1 else 0.0)
                                        for i in range(nit[j])]
                     continue
-                if rc != -4:                                  # anything but FOS_ERR_UNSUPPORTED is an error
-                    _lib.check(rc, "fos_lbfgs_minimize_multi")
             for j in range(g0, g1):
                 one(j)
         self.x_ = _core.from_device_vec(X[:, : prob.n].t().contiguous(), prob.like)
@@ -276,7 +268,15 @@ class LBFGSSolver:
             prob, _ = _sharded_problem(A, b, None, comm, None, cols)
             ops = _HipColOps(prob, comm)
         if ops is None and (group is None or dist.get_world_size(group) == 1):
-            return self._fit_native(_HipOps(A, b, comm))
+            ops = _HipOps(A, b, comm)
+            r = self._fit_native(ops)
+            self.nit_, self.nfev_, self.task_ = r["nit"], r["nfev"], r["task"]
+            self.history_.extend(r["history"])
+            # one conversion (and one copy to the host for ndarray callers) for all iterates; the list holds its rows
+            self.iterates_ = list(ops.to_caller(r["iterates"])) if r["iterates"] is not None else []
+            self.x_ = ops.to_caller(r["x"])                                               # lbfgs.py:71
+            self.final_obj_ = r["f"]                                                      # lbfgs.py:72
+            return self
         ops = ops if ops is not None else _HipOps(A, b, comm)
         sharded = comm is None and group is not None and dist.get_world_size(group) > 1
         a2 = float(self.alpha2) if self.reg_type in ("ridge", "elasticnet") else 0.0   # lbfgs.py:49-51

@@ -1,8 +1,7 @@
 """MI355X drop-in for the reference's ``objective_functions.py`` (one residual pass over A, kernel K5)."""
-import numpy as np
-import torch
-
 from . import _core
+from .iterative_solvers import _objective_by_reg, _targets
+from .operators import vec_stats
 
 
 def compute_objective(x, A, b, reg_type, alpha1, alpha2):
@@ -10,34 +9,17 @@ def compute_objective(x, A, b, reg_type, alpha1, alpha2):
     objective_functions.py:3-30; ValueError for any other reg_type (:28).
     Several targets: with x of shape (n, k) and b of shape (m, k), k >= 2, the sum over the columns (½‖AX−B‖²_F plus the
     regulariser of X): 16 residual norms per pass over A on the matrix cores where the shape has that pass."""
-    if reg_type not in ("lasso", "ridge", "elasticnet"):
-        raise ValueError(f"Unsupported reg_type='{reg_type}'")
-    from .iterative_solvers import _targets
+    value = _objective_by_reg(reg_type, alpha1, alpha2)
     if _targets(A, b) is not None:
-        return _objective_targets(x, A, b, reg_type, alpha1, alpha2)
+        return _objective_targets(x, A, b, value)
     prob = _core.as_problem(A, b)
     xt = _core.to_device_vec(x, prob.device)
-    rr, x2, x1 = prob.residual_objective(xt)
-    return _value(reg_type, alpha1, alpha2, rr, x2, x1)
+    return value(*prob.residual_objective(xt))
 
 
-def _value(reg_type, alpha1, alpha2, rr, x2, x1):
-    g = 0.5 * rr
-    if reg_type in ("ridge", "elasticnet"):
-        g += 0.5 * alpha2 * x2
-    h = alpha1 * x1 if reg_type in ("lasso", "elasticnet") else 0.0
-    return g + h
-
-
-def _as_device_block(M, device):
-    t = M.detach() if _core.is_tensor(M) else torch.from_numpy(np.ascontiguousarray(np.asarray(M)))
-    return t.to(device=device, dtype=torch.float32).contiguous()
-
-
-def _objective_targets(X, A, B, reg_type, alpha1, alpha2):
-    from .operators import vec_stats
+def _objective_targets(X, A, B, value):
     prob = _core.prepare(A)
-    Bt, Xt = _as_device_block(B, prob.device), _as_device_block(X, prob.device)
+    Bt, Xt = _core.to_device(B, prob.device), _core.to_device(X, prob.device)
     k = int(Bt.shape[1])
     if Bt.shape[0] != prob.m:
         raise ValueError("b must have m rows")
@@ -54,5 +36,5 @@ def _objective_targets(X, A, B, reg_type, alpha1, alpha2):
             else:
                 st = vec_stats(xj, None, None)
                 rr, x2, x1 = rrs[i], st[0], st[4]
-            total += _value(reg_type, alpha1, alpha2, rr, x2, x1)
+            total += value(rr, x2, x1)
     return total

@@ -400,3 +400,61 @@ def orc_ls_total(A, b, a1, a2, c, L):
     else:
         _, met = orc.fista(A, b, "elasticnet", a1, a2, **kw)
     return met["ls_iters_total"]
+
+
+# --------------------------------------------------------------------------------------------------
+# the record sink of the solver runs (iterative_solvers._Records): it receives tensors and makes no device call, so its
+# bookkeeping - rows of the caller's kind, objectives now or one pass late, the log, the metric shares - is checked here
+# --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tensor_caller", [False, True])
+def test_record_sink_bookkeeping(tensor_caller):
+    from fastoptsolver_amd import _core, iterative_solvers as its
+    its.reset_metrics()
+    like = _core.Like(torch.zeros(1, dtype=torch.float32) if tensor_caller else np.zeros(1))
+    a1, a2 = 0.3, 0.2
+    history, log = {"x": ["x0"], "obj": []}, {"x": [], "t": [], "delta": []}
+    rec = its._Records(like, history, its._objective_by_alpha(a1, a2), log, timer=_HostTimer)
+    assert rec.recording and rec.objectives
+    xs = torch.arange(12, dtype=torch.float64).reshape(3, 4)
+    hs = np.array([[8.0, 1.0, 2.0, 9.0], [6.0, 1.5, 2.5, 4.0], [4.0, 2.0, 3.0, 1.0]])     # rr, ||x||_1, ||x||_2^2, ||dx||^2
+    rec.block(xs, hs, taus=torch.tensor([0.5, 0.25, 0.25], dtype=torch.float64))
+    rec.block(xs[:2] + 100.0, hs[:2], taus=[0.125, 0.125], rr_known=False)           # residuals come one pass late
+    assert len(history["obj"]) == 3 and len(rec.owed) == 2
+    rec.settle([5.0])
+    s = _Status()
+    s.xnorm1, s.xnorm2, s.this_step = 7.0, 11.0, 0.75
+    rec.one(torch.full((4,), -1.0, dtype=torch.float64), s, 0.0625)
+    rec.settle([3.0])
+    rec.settle([2.0], [(70.0, 110.0)])                     # a closing residual pass brings its own norms
+    assert rec.owed == []
+    f = lambda rr, x1, x2: 0.5 * rr + 0.5 * a2 * x2 + a1 * x1                        # noqa: E731
+    assert history["obj"] == [f(8.0, 1.0, 2.0), f(6.0, 1.5, 2.5), f(4.0, 2.0, 3.0), f(5.0, 1.0, 2.0), f(3.0, 1.5, 2.5),
+                              f(2.0, 70.0, 110.0)]
+    assert history["x"][0] == "x0" and len(history["x"]) == 7 and len(log["x"]) == 6
+    want = [xs[0], xs[1], xs[2], xs[0] + 100.0, xs[1] + 100.0, torch.full((4,), -1.0, dtype=torch.float64)]
+    for got, ref, logged in zip(history["x"][1:], want, log["x"]):
+        if tensor_caller:
+            assert isinstance(got, torch.Tensor) and got.dtype == torch.float32 and got.device.type == "cpu"
+            assert torch.equal(got, ref.float())
+        else:
+            assert isinstance(got, np.ndarray) and got.dtype == np.float64 and np.array_equal(got, ref.numpy())
+        assert logged is got                                # one conversion serves history and log
+    assert log["t"] == [0.5, 0.25, 0.25, 0.125, 0.125, 0.0625]
+    assert log["delta"] == [3.0, 2.0, 1.0, 3.0, 2.0, 0.75]
+    # metrics: the searches' wall time in equal shares, the timer's count trimmed to the gradients that belong to the run
+    rec.searches([1, 0, 3], 3.0)
+    rec.searches([2], 0.25)
+    assert (its.ls_call_times, its.ls_call_iters) == ([1.0, 1.0, 1.0, 0.25], [1, 0, 3, 2])
+    rec.timer.stop(None, 5)
+    rec.gradients(4)
+    assert its.get_metrics()["grad_num_calls"] == 4
+    rec.timer.stop(None, 2)
+    rec.gradients()
+    assert its.get_metrics()["grad_num_calls"] == 6
+    assert its._shares(2, 1.0, 4) == [0.25, 0.25] and its._shares(0, 1.0) == []       # members of a batch launch
+    # a sink without history or log records metrics only
+    plain = its._Records(like)
+    assert not plain.recording and not plain.objectives
+    plain.searches([4, 4], 2.0)
+    assert its.get_metrics()["ls_iters_total"] == 14 and its.get_metrics()["ls_num_calls"] == 6
+    its.reset_metrics()
