@@ -63,3 +63,22 @@ def fp32_pass_tolerances(A, y, b, g_ref, rr_ref):
     g_tol = 2e-6 * float(np.linalg.norm(g_ref)) + float(np.linalg.norm(A, 2) if m * n <= 1 << 16 else np.linalg.norm(A)) * dr
     rr_tol = 5e-6 * rr_ref + 2.0 * r_norm * dr + dr * dr
     return g_tol, rr_tol
+
+
+def fp32_pass_tolerances_cols(A, Y, B, G_ref, rr_ref):
+    """fp32_pass_tolerances for every column of Y (n x k) at once: the same two bounds, as arrays of k entries (|A| is formed
+    once for the block).  B: None, one b (m) for all columns or a block (m x k); G_ref (n x k), rr_ref (k)."""
+    A = np.asarray(A, dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    m, n = A.shape
+    eps32 = float(np.finfo(np.float32).eps)
+    ab = np.abs(A) @ np.abs(Y)
+    if B is not None:
+        B = np.abs(np.asarray(B, dtype=np.float64))
+        ab = ab + (B if B.ndim == 2 else B[:, None])
+    dr = 4.0 * eps32 * np.linalg.norm(ab, axis=0)
+    rr_ref = np.asarray(rr_ref, dtype=np.float64)
+    g_tol = 2e-6 * np.linalg.norm(np.asarray(G_ref, dtype=np.float64), axis=0) + \
+        float(np.linalg.norm(A, 2) if m * n <= 1 << 16 else np.linalg.norm(A)) * dr
+    rr_tol = 5e-6 * rr_ref + 2.0 * np.sqrt(rr_ref) * dr + dr * dr
+    return g_tol, rr_tol

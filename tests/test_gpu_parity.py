@@ -846,6 +846,8 @@ def test_residual_batch_mfma_vs_oracle(fos, m, n, nv):
         R = A.astype(np.float64) @ X.astype(np.float64) - (b.astype(np.float64)[:, None] if use_b else 0.0)
         want = (R ** 2).sum(axis=0)
         assert np.allclose(got, want, rtol=TOL), (use_b, got, want)
+        _, rr_tol = _data.fp32_pass_tolerances_cols(A, X, b if use_b else None, np.zeros((n, nv)), want)     # per column
+        assert (np.abs(np.asarray(got) - want) <= rr_tol).all(), (use_b, got, want, rr_tol)
 
 
 @pytest.mark.parametrize("m,n,nv", [(64, 16, 16), (1000, 512, 5), (777, 136, 3), (4099, 8192, 16), (130, 16384, 9), (1, 8, 1),
@@ -864,7 +866,10 @@ def test_residual_batch_mfma_bf16_vs_oracle(fos, m, n, nv):
     for use_b in (True, False):
         got = prob.residual_batch(X, use_b=use_b)
         R = Aq @ X.astype(np.float64) - (b.astype(np.float64)[:, None] if use_b else 0.0)
-        assert np.allclose(got, (R ** 2).sum(axis=0), rtol=TOL), (use_b, got)
+        want = (R ** 2).sum(axis=0)
+        assert np.allclose(got, want, rtol=TOL), (use_b, got)
+        _, rr_tol = _data.fp32_pass_tolerances_cols(Aq, X, b if use_b else None, np.zeros((n, nv)), want)    # per column
+        assert (np.abs(np.asarray(got) - want) <= rr_tol).all(), (use_b, got, want, rr_tol)
 
 
 def test_bf16_backtracking_uses_mfma_batch_and_matches_oracle(fos):
