@@ -48,28 +48,18 @@ int fos_fista_create(fos_problem* p, fos_fista** out) {
   if (!p || !out) return fail(FOS_ERR_ARG, "fos_fista_create: null");
   fos_fista* f = new fos_fista();
   f->p = p;
-  const size_t nb = (size_t)p->n * sizeof(double);
-  hipError_t he = hipMalloc(&f->x_cur, nb);
-  if (he == hipSuccess) he = hipMalloc(&f->x_prev, nb);
-  if (he == hipSuccess) he = hipMalloc(&f->dlt, (size_t)p->n * sizeof(float));
-  if (he == hipSuccess) he = hipMalloc(&f->scal, sizeof(fos::FistaScalars));
-  if (he == hipSuccess) he = hipMalloc(&f->out5, 8 * sizeof(double));
   f->nupd = (int)((p->n + fos::RCOLS - 1) / fos::RCOLS);
-  if (he == hipSuccess) he = hipMalloc(&f->part2, (size_t)2 * f->nupd * 4 * sizeof(double));
-  if (he == hipSuccess) he = hipMalloc(&f->ynext, (size_t)p->n * sizeof(float));
-  if (he != hipSuccess) {
-    fos_fista_destroy(f);
-    return fail(FOS_ERR_HIP, std::string("fos_fista_create: ") + hipGetErrorString(he));
+  int rc;
+  if ((rc = f->x_cur.reserve(p->n)) || (rc = f->x_prev.reserve(p->n)) || (rc = f->dlt.reserve(p->n)) || (rc = f->scal.reserve(1)) ||
+      (rc = f->out5.reserve(8)) || (rc = f->part2.reserve((size_t)2 * f->nupd * 4)) || (rc = f->ynext.reserve(p->n))) {
+    delete f;
+    return rc;
   }
   *out = f;
   return FOS_OK;
 }
 
 int fos_fista_destroy(fos_fista* f) {
-  if (!f) return FOS_OK;
-  void* bufs[] = {f->x_cur, f->x_prev, f->dlt, f->scal, f->out5, f->part2, f->ynext, f->gbuf64_owned ? f->gbuf64 : nullptr, f->folded};
-  for (void* q : bufs)
-    if (q) (void)hipFree(q);
   delete f;
   return FOS_OK;
 }
@@ -131,8 +121,8 @@ static fos::GradSrc grad_src(const fos_fista* f) {
 int fos_fista_set_precise(fos_fista* f, int on) {
   if (!f) return fail(FOS_ERR_ARG, "fos_fista_set_precise: null");
   if (on && !f->gbuf64) {
-    HIP_TRY(hipMalloc(&f->gbuf64, (size_t)(f->p->n + 4) * sizeof(double)));
-    f->gbuf64_owned = true;
+    if (int rc = f->gbuf64_own.reserve(f->p->n + 4)) return rc;
+    f->gbuf64 = f->gbuf64_own;
   }
   f->precise = on != 0;
   return FOS_OK;
@@ -141,9 +131,8 @@ int fos_fista_set_precise(fos_fista* f, int on) {
 int fos_fista_set_gbuf64(fos_fista* f, double* buf) {
   if (!f) return fail(FOS_ERR_ARG, "fos_fista_set_gbuf64: null");
   if (buf && (reinterpret_cast<uintptr_t>(buf) & 15u)) return fail(FOS_ERR_ARG, "fos_fista_set_gbuf64: misaligned");
-  if (f->gbuf64 && f->gbuf64_owned) (void)hipFree(f->gbuf64);
+  f->gbuf64_own.reset();
   f->gbuf64 = buf;
-  f->gbuf64_owned = false;
   if (!buf) f->precise = false;
   return FOS_OK;
 }
@@ -183,19 +172,19 @@ __global__ __launch_bounds__(64) void fold4_multi_kernel(fos::MultiControl mc, i
 
 static int launch_finalize(fos_fista* f, int n_rr, double* hist_row = nullptr) {
   fos_problem* p = f->p;
-  const double* part = p->part;
+  const double* part = p->ws.part;
   int nparts = f->nupd;
   if (p->col_sharded) {
     // x is partitioned over the ranks: step norms, ||grad||^2, ||x||_1, ||x||^2 are sums over ALL column blocks
-    if (!f->folded) HIP_TRY(hipMalloc(&f->folded, 8 * sizeof(double)));
-    hipLaunchKernelGGL(fold4_kernel, dim3(1), dim3(64), 0, p->stream, p->part, f->nupd, f->folded, (const int*)nullptr);   // re-derived after a stop: the in-place all-reduce below must never see its own result
+    if (int rc = f->folded.reserve(8)) return rc;
+    hipLaunchKernelGGL(fold4_kernel, dim3(1), dim3(64), 0, p->stream, p->ws.part, f->nupd, f->folded, (const int*)nullptr);   // re-derived after a stop: the in-place all-reduce below must never see its own result
     LAUNCH_CHECK();
     int rc = reduce_across(p, f->folded, 4, true);
     if (rc) return rc;
     part = f->folded;
     nparts = 1;
   }
-  hipLaunchKernelGGL(fos::fista_finalize_kernel, dim3(1), dim3(64), 0, p->stream, part, nparts, p->rr_part, n_rr,
+  hipLaunchKernelGGL(fos::fista_finalize_kernel, dim3(1), dim3(64), 0, p->stream, part, nparts, p->pass.rr_part, n_rr,
                      f->scal, f->prm, hist_row);
   LAUNCH_CHECK();
   return FOS_OK;
@@ -224,8 +213,8 @@ static int launch_update(fos_fista* f, const float* slabs, int nslabs, fos::Grad
   hipLaunchKernelGGL((fos::fista_update_kernel<FROM_SLABS, VEC>), dim3(f->nupd), dim3(256), 0, p->stream, slabs, nslabs, gsrc,  \
                      (int)p->n, f->x_cur, f->x_prev, f->scal, prm, part, host_beta, beta_val, x_hist, y_next, beta_next,       \
                      slab_stride, y_mode, y_slot)
-  if (slabs) { if (p->vec4) FOS_UPDATE(true, true); else FOS_UPDATE(true, false); }
-  else { if (p->vec4) FOS_UPDATE(false, true); else FOS_UPDATE(false, false); }
+  if (slabs) { if (p->pass.vec4) FOS_UPDATE(true, true); else FOS_UPDATE(true, false); }
+  else { if (p->pass.vec4) FOS_UPDATE(false, true); else FOS_UPDATE(false, false); }
 #undef FOS_UPDATE
   LAUNCH_CHECK();
   return FOS_OK;
@@ -236,8 +225,8 @@ static int launch_update_from_slabs(fos_fista* f, double* part, int host_beta, d
                                     const float* slabs = nullptr, int64_t slab_stride = 0, int nslabs = 0,
                                     int y_mode = fos::YOUT_VECTOR, int y_slot = 0) {
   fos_problem* p = f->p;
-  return launch_update(f, slabs ? slabs : p->slabs, nslabs ? nslabs : p->nslabs, fos::GradSrc{nullptr, nullptr}, f->prm, part,
-                       host_beta, beta_val, x_hist, y_next, beta_next, slab_stride ? slab_stride : p->slab_stride, y_mode, y_slot);
+  return launch_update(f, slabs ? slabs : p->pass.slabs, nslabs ? nslabs : p->pass.nslabs, fos::GradSrc{nullptr, nullptr}, f->prm, part,
+                       host_beta, beta_val, x_hist, y_next, beta_next, slab_stride ? slab_stride : p->pass.slab_stride, y_mode, y_slot);
 }
 
 // y source of a plain-run iteration: the fp32 vector the previous update kernel wrote, or the fp64 state with the host's beta
@@ -262,7 +251,7 @@ static int finish_plain(fos_fista* f, const double* cur, const double* prev, int
 // ... of plain iterations whose partials sit in part2
 static int finish_part2(fos_fista* f, int n_rr) {
   return finish_plain(f, part2_slot(f, f->h_k - 1), f->plain_count >= 2 ? part2_slot(f, f->h_k - 2) : nullptr, f->nupd,
-                      f->p->rr_part, n_rr);
+                      f->p->pass.rr_part, n_rr);
 }
 
 static int flush_pending(fos_fista* f) { return f->pending ? finish_part2(f, 0) : FOS_OK; }
@@ -295,13 +284,12 @@ static PlainStep advance_plain(fos_fista* f, bool ynext) {
   return s;
 }
 
-// The momentum of `iters` plain iterations run in one launch: beta_k for y_k, then beta_{k+1} ... beta_{k+iters} -> p->fz_beta.
+// The momentum of `iters` plain iterations run in one launch: beta_k for y_k, then beta_{k+1} ... beta_{k+iters} -> p->ws.fz_beta.
 // The mirror moves on by iters; *before is where it stood (restore_momentum).
 struct Momentum { double t, beta; long long k; };
 static int momentum_sequence(fos_fista* f, int iters, Momentum* before) {
   fos_problem* p = f->p;
-  int rc = grow(&p->fz_beta_cap, iters + 1, sizeof(double), &p->fz_beta);
-  if (rc) return rc;
+  if (int rc = p->ws.fz_beta.reserve((size_t)iters + 1)) return rc;
   *before = Momentum{f->h_t, f->h_beta, f->h_k};
   std::vector<double> betas((size_t)iters + 1);
   betas[0] = f->h_beta;
@@ -310,7 +298,7 @@ static int momentum_sequence(fos_fista* f, int iters, Momentum* before) {
     betas[(size_t)k + 1] = f->h_beta;
     f->h_k += 1;
   }
-  HIP_TRY(hipMemcpyAsync(p->fz_beta, betas.data(), betas.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipMemcpyAsync(p->ws.fz_beta, betas.data(), betas.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));          // (the host vector must outlive the copy)
   return FOS_OK;
 }
@@ -351,7 +339,7 @@ static bool plain_run(const fos_fista* f) {
 static int launch_grad_norm_stop(fos_fista* f) {
   fos_problem* p = f->p;
   if (p->col_sharded) {                        // ||grad||^2 = sum over the column blocks of all ranks
-    if (!f->folded) HIP_TRY(hipMalloc(&f->folded, 8 * sizeof(double)));
+    if (int rc = f->folded.reserve(8)) return rc;
     hipLaunchKernelGGL(fos::grad_norm_stop_kernel, dim3(1), dim3(1024), 0, p->stream, grad_src(f), (int)p->n, f->x_cur,
                        f->x_prev, f->scal, f->prm, f->folded + 4);
     LAUNCH_CHECK();
@@ -392,12 +380,12 @@ int fos_fista_run_resident(fos_fista* f, int iters, int backtracking, double eta
   if (!f || iters < 0 || !iters_done || !tau_out || (backtracking && !(eta > 0.0 && eta < 1.0)))
     return fail(FOS_ERR_ARG, "fos_fista_run_resident: bad argument");
   fos_problem* p = f->p;
-  if (!p->resident) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_resident: problem does not fit the LDS-resident loop");
+  if (!p->pass.resident) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_resident: problem does not fit the LDS-resident loop");
   *iters_done = 0;
   *tau_out = f->prm.tau;
   if (iters == 0) return FOS_OK;
-  double* tau_dev = p->dscal + 241;
-  int* done_dev = reinterpret_cast<int*>(p->dscal + 242);
+  double* tau_dev = p->ws.dscal + 241;
+  int* done_dev = reinterpret_cast<int*>(p->ws.dscal + 242);
   fos::ResidentOpts opt{backtracking ? 1 : 0, eta, armijo_c, grad_tol, ls_iters, tau_hist, tau_dev, done_dev};
   int rc = run_resident(f, iters, x_hist, hist, opt);
   if (rc) return rc;
@@ -414,54 +402,47 @@ int fos_fista_run_resident(fos_fista* f, int iters, int backtracking, double eta
 
 int64_t fos_fista_history_workspace(fos_fista* f, int iters) {
   if (!f || iters < 0) return -1;
-  return ((int64_t)(iters + 1) * f->p->nwg + (int64_t)iters * f->nupd * 4) * (int64_t)sizeof(double);
+  return ((int64_t)(iters + 1) * f->p->pass.nwg + (int64_t)iters * f->nupd * 4) * (int64_t)sizeof(double);
 }
 
 int fos_fista_run_history(fos_fista* f, int iters, double* x_hist, double* hist, void* work) {
   if (!f || iters < 0 || (iters > 0 && (!x_hist || !hist || !work)))
     return fail(FOS_ERR_ARG, "fos_fista_run_history: bad argument");
   fos_problem* p = f->p;
-  if (plain_run(f) && p->resident) return iters == 0 ? FOS_OK : run_resident(f, iters, x_hist, hist);
-  if (!plain_run(f) || p->path != 0 || p->colblock || p->entry->dual == nullptr || p->comm != nullptr)
+  if (plain_run(f) && p->pass.resident) return iters == 0 ? FOS_OK : run_resident(f, iters, x_hist, hist);
+  if (!plain_run(f) || p->pass.path != 0 || p->pass.colblock || p->pass.entry->dual == nullptr || p->comm != nullptr)
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_history: needs a plain run on the fused path with a DUAL kernel");
   if (iters == 0) return FOS_OK;
   bool stopped = false;
   int rc = begin_plain(f, &stopped);
   if (rc) return rc;
   if (stopped) return fail(FOS_ERR_STATE, "fos_fista_run_history: solver already stopped");
-  const int nwg = p->nwg;
+  const int nwg = p->pass.nwg;
   const size_t psz = (size_t)f->nupd * 4;
   double* rr2_slots = reinterpret_cast<double*>(work);                 // (iters + 1) x nwg
   double* part_slots = rr2_slots + (size_t)(iters + 1) * nwg;          // iters x nupd x 4
-  double* saved_rr2 = p->rr2_part;
   int n_rr = 0;
   for (int it = 0; it < iters; ++it) {
     // the DUAL pass needs x_k itself, so it always forms y from the fp64 state
     YSource ys{nullptr, f->x_cur, f->x_prev, nullptr, &f->scal->stopped, f->h_beta, nullptr};
-    p->rr2_part = rr2_slots + (size_t)it * nwg;                        // slot it = residual of the iterate BEFORE it
-    rc = launch_pass(p, ys, p->b, true, &n_rr, true);
-    p->rr2_part = saved_rr2;
-    if (rc) return rc;
+    // slot it = residual of the iterate BEFORE it
+    if ((rc = launch_pass(p, ys, p->b, true, &n_rr, true, rr2_slots + (size_t)it * nwg))) return rc;
     const PlainStep s = advance_plain(f, false);
     if ((rc = launch_update_from_slabs(f, part_slots + it * psz, 1, s.beta, x_hist + (size_t)it * p->n))) return rc;
   }
   // closing residual pass: ||A x_last - b||^2 -> slot iters (written by the residual-only kernel into rr_part)
-  hipLaunchKernelGGL(fos::cast_f64_f32_kernel, dim3(grid_1d(p->n, 256, 1024)), dim3(256), 0, p->stream, f->x_cur, p->ybuf,
+  hipLaunchKernelGGL(fos::cast_f64_f32_kernel, dim3(grid_1d(p->n, 256, 1024)), dim3(256), 0, p->stream, f->x_cur, p->ws.ybuf,
                      p->n);
   LAUNCH_CHECK();
   {
-    YSource ys{p->ybuf, nullptr, nullptr, nullptr, nullptr};
-    double* saved_rr = p->rr_part;
-    p->rr_part = rr2_slots + (size_t)iters * nwg;
-    rc = launch_pass(p, ys, p->b, false, &n_rr);
-    p->rr_part = saved_rr;
-    if (rc) return rc;
+    YSource ys{p->ws.ybuf, nullptr, nullptr, nullptr, nullptr};
+    if ((rc = launch_pass(p, ys, p->b, false, &n_rr, false, rr2_slots + (size_t)iters * nwg))) return rc;
   }
   hipLaunchKernelGGL(fos::history_fold_kernel, dim3(iters), dim3(64), 0, p->stream, rr2_slots, nwg, part_slots, f->nupd,
                      hist);
   LAUNCH_CHECK();
   rc = finish_plain(f, part_slots + (iters - 1) * psz, iters >= 2 ? part_slots + (iters - 2) * psz : nullptr, f->nupd,
-                    p->rr_part, nwg);
+                    p->pass.rr_part, nwg);
   restart_plain(f);
   return rc;
 }
@@ -470,7 +451,7 @@ int fos_fista_run(fos_fista* f, int iters) {
   if (!f || iters < 0) return fail(FOS_ERR_ARG, "fos_fista_run: bad argument");
   fos_problem* p = f->p;
   if (iters == 0) return FOS_OK;
-  if (p->resident) return run_resident(f, iters, nullptr, nullptr);
+  if (p->pass.resident) return run_resident(f, iters, nullptr, nullptr);
   // Tall-skinny runs without backtracking / history: A in the LDS of up to all CUs, one grid barrier per iteration
   // (chip_resident.hpp); adaptive restart and the step / ratio stops are decided on the device by every workgroup alike.  The
   // planner's own region is where the plain loop measured at least 1.4x ahead of the two launches below (tools/bench_chip.py:
@@ -533,7 +514,7 @@ int fos_fista_run(fos_fista* f, int iters) {
   for (int it = 0; it < iters; ++it) {
     int n_rr = 0, rc;
     if ((rc = launch_pass(p, fista_source(f), p->b, true, &n_rr))) return rc;
-    if ((rc = launch_update_from_slabs(f, p->part, 0, 0.0))) return rc;
+    if ((rc = launch_update_from_slabs(f, p->ws.part, 0, 0.0))) return rc;
     if ((rc = launch_finalize(f, n_rr))) return rc;
   }
   return FOS_OK;
@@ -551,7 +532,7 @@ int fos_fista_run_fused(fos_fista* f, int iters) {
   if (!f || iters < 0) return fail(FOS_ERR_ARG, "fos_fista_run_fused: bad argument");
   fos_problem* p = f->p;
   const int G = p->ncu;
-  if (p->dtype != FOS_F32 || p->path != 0 || p->tall || p->colblock || p->resident || p->comm || p->n % 2048 != 0 ||
+  if (p->dtype != FOS_F32 || p->pass.path != 0 || p->pass.tall || p->pass.colblock || p->pass.resident || p->comm || p->n % 2048 != 0 ||
       p->n > 8192 || p->lda % 4 != 0 || (reinterpret_cast<uintptr_t>(p->A) & 15u) || p->m < 8 * (int64_t)G ||
       (p->n + G - 1) / G > fos::FZ_OWN_MAX)
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_fused: fp32 A, n in {2048, 4096, 6144, 8192}, aligned rows, m >= 8 x CUs, unsharded");
@@ -562,12 +543,12 @@ int fos_fista_run_fused(fos_fista* f, int iters) {
   int rc = begin_plain(f, &stopped);
   if (rc || stopped) return rc;
   // workspace: G slabs (the planner's are reused when it planned G workgroups), barrier words, beta sequence, partials
-  if ((rc = grow(&p->slab_cap, G, (size_t)p->n * sizeof(float), &p->slabs))) return rc;
-  if ((rc = grow(&p->rr_cap, G, sizeof(double), &p->rr_part, &p->rr2_part))) return rc;
-  if (!p->fz_bar) {
-    HIP_TRY(hipMalloc(&p->fz_bar, fos::FZ_BAR_WORDS * sizeof(unsigned)));
-    HIP_TRY(hipMemsetAsync(p->fz_bar, 0, fos::FZ_BAR_WORDS * sizeof(unsigned), p->stream));
-    HIP_TRY(hipMalloc(&p->fz_part, (size_t)2 * G * 4 * sizeof(double)));
+  if ((rc = p->pass.slabs.reserve((size_t)G * p->n)) || (rc = p->pass.rr_part.reserve(G)) || (rc = p->pass.rr2_part.reserve(G)))
+    return rc;
+  if (!p->ws.fz_part) {
+    if ((rc = p->ws.fz_bar.reserve(fos::FZ_BAR_WORDS))) return rc;
+    HIP_TRY(hipMemsetAsync(p->ws.fz_bar, 0, fos::FZ_BAR_WORDS * sizeof(unsigned), p->stream));
+    if ((rc = p->ws.fz_part.reserve((size_t)2 * G * 4))) return rc;
   }
   if ((rc = ensure_y(f))) return rc;
   Momentum before;
@@ -575,8 +556,8 @@ int fos_fista_run_fused(fos_fista* f, int iters) {
   fos::FusedArgs a{};
   a.A = (const float*)p->A; a.lda = p->lda; a.b = p->b; a.m = p->m; a.n = (int)p->n;
   a.rows_per_wg = ((p->m + G - 1) / G + fos::FZ_ROWS - 1) / fos::FZ_ROWS * fos::FZ_ROWS;
-  a.slabs = p->slabs; a.y = f->ynext; a.x_cur = f->x_cur; a.x_prev = f->x_prev; a.beta = p->fz_beta; a.part = p->fz_part;
-  a.rr_part = p->rr_part; a.bar = p->fz_bar; a.iters = iters; a.prox_kind = f->prm.prox_kind; a.k0 = before.k;
+  a.slabs = p->pass.slabs; a.y = f->ynext; a.x_cur = f->x_cur; a.x_prev = f->x_prev; a.beta = p->ws.fz_beta; a.part = p->ws.fz_part;
+  a.rr_part = p->pass.rr_part; a.bar = p->ws.fz_bar; a.iters = iters; a.prox_kind = f->prm.prox_kind; a.k0 = before.k;
   a.tau = f->prm.tau; a.alpha1 = f->prm.alpha1; a.alpha2 = f->prm.alpha2;
   a.timeout_ticks = 100000000ull * 2ull;           // 2 s of the 100 MHz wall clock per wait
   a.stamps = p->fz_stamps;
@@ -591,12 +572,12 @@ int fos_fista_run_fused(fos_fista* f, int iters) {
   if (rc) return rc;
   if ((rc = prof_mark(p, false))) return rc;
   const long long last = f->h_k - 1;
-  const double* prev = iters >= 2 ? p->fz_part + (size_t)((last - 1) & 1) * G * 4 : nullptr;
-  if ((rc = finish_plain(f, p->fz_part + (size_t)(last & 1) * G * 4, prev, G, p->rr_part, G))) return rc;
+  const double* prev = iters >= 2 ? p->ws.fz_part + (size_t)((last - 1) & 1) * G * 4 : nullptr;
+  if ((rc = finish_plain(f, p->ws.fz_part + (size_t)(last & 1) * G * 4, prev, G, p->pass.rr_part, G))) return rc;
   restart_plain(f, true);                          // the kernel leaves y_{k+iters} in ynext
   // a grid-wide wait that ran out leaves the state invalid: report it (synchronises)
   unsigned bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, p->fz_bar + fos::FZ_LINE, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipMemcpyAsync(&bad, p->ws.fz_bar + fos::FZ_LINE, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   if (bad) return fail(FOS_ERR_STATE, "fos_fista_run_fused: a grid-wide wait timed out (workgroups not co-resident?); state invalid");
   return FOS_OK;
@@ -626,18 +607,18 @@ int fos_fista_run_chip(fos_fista* f, int iters) {
   int64_t rpw = (p->m + G - 1) / G;
   if (rpw > cap) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_chip: rows per workgroup exceed the LDS budget");
   G = (p->m + rpw - 1) / rpw;
-  if (!p->cr_part) {
-    HIP_TRY(hipMalloc(&p->cr_part, ((size_t)2 * p->ncu * 17 + 16) * sizeof(double)));
-    HIP_TRY(hipMalloc(&p->cr_bar, fos::FZ_BAR_WORDS * sizeof(unsigned)));
-    HIP_TRY(hipMemsetAsync(p->cr_bar, 0, fos::FZ_BAR_WORDS * sizeof(unsigned), p->stream));
+  if (!p->ws.cr_part) {
+    if ((rc = p->ws.cr_bar.reserve(fos::FZ_BAR_WORDS))) return rc;
+    HIP_TRY(hipMemsetAsync(p->ws.cr_bar, 0, fos::FZ_BAR_WORDS * sizeof(unsigned), p->stream));
+    if ((rc = p->ws.cr_part.reserve((size_t)2 * p->ncu * 17 + 16))) return rc;
   }
   Momentum before;
   if ((rc = momentum_sequence(f, iters, &before))) return rc;
-  double* stats = p->cr_part + (size_t)2 * p->ncu * 17;
+  double* stats = p->ws.cr_part + (size_t)2 * p->ncu * 17;
   fos::ChipArgs a{};
   a.A = (const float*)p->A; a.lda = p->lda; a.b = p->b; a.m = p->m; a.n = (int)p->n; a.rows_per_wg = rpw;
-  a.part = p->cr_part; a.x_cur = f->x_cur; a.x_prev = f->x_prev; a.beta = p->fz_beta; a.stats = stats; a.rr_out = stats + 8;
-  a.bar = p->cr_bar; a.iters = iters; a.prox_kind = f->prm.prox_kind;
+  a.part = p->ws.cr_part; a.x_cur = f->x_cur; a.x_prev = f->x_prev; a.beta = p->ws.fz_beta; a.stats = stats; a.rr_out = stats + 8;
+  a.bar = p->ws.cr_bar; a.iters = iters; a.prox_kind = f->prm.prox_kind;
   a.tau = f->prm.tau; a.alpha1 = f->prm.alpha1; a.alpha2 = f->prm.alpha2;
   a.timeout_ticks = 100000000ull * 2ull;
   if ((rc = prof_mark(p, true))) return rc;
@@ -651,11 +632,11 @@ int fos_fista_run_chip(fos_fista* f, int iters) {
   // launch BEFORE anything is written back: the iterate on the device is the one the call started from.  The handle's
   // momentum counters are put back, the barrier words cleared, and the caller is told - it can run the two-launch loop.
   unsigned bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, p->cr_bar + fos::FZ_LINE, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipMemcpyAsync(&bad, p->ws.cr_bar + fos::FZ_LINE, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   if (bad) {
     restore_momentum(f, before);
-    HIP_TRY(hipMemsetAsync(p->cr_bar, 0, fos::FZ_BAR_WORDS * sizeof(unsigned), p->stream));
+    HIP_TRY(hipMemsetAsync(p->ws.cr_bar, 0, fos::FZ_BAR_WORDS * sizeof(unsigned), p->stream));
     return fail(FOS_ERR_STATE, "fos_fista_run_chip: a grid-wide wait timed out (workgroups not co-resident); the state is "
                                "the one before the call");
   }
@@ -696,24 +677,24 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
   if (cols && !controlled) return fail(FOS_ERR_STATE, "run_multi_mfma: a column-sharded lockstep is device-controlled");
   int rc = ensure_batch_workspace(p);
   if (rc) return rc;
-  if (cols && !p->mfold) HIP_TRY(hipMalloc(&p->mfold, (size_t)fos::BT_NV * 4 * sizeof(double)));
+  if (cols && (rc = p->ws.mfold.reserve((size_t)fos::BT_NV * 4))) return rc;
   if ((rc = plan_multi_mfma(p))) return rc;
   const bool is_bf16 = p->dtype == FOS_BF16;
   const int64_t esz = is_bf16 ? 2 : 4;
   const int y_mode = is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP;
   // row splits of product 2: the planned ones, or - a B-block run on a problem planned for the cluster form, whose slab
   // count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated
-  bool use_cluster = p->cp_cs && !b16;
-  int g_splits = p->gram_splits;
-  if (p->cp_cs && b16) {
-    g_splits = (int)((p->panel_rows + p->gram_rows_per_split - 1) / p->gram_rows_per_split);
-    if (g_splits > p->gram_splits)
+  bool use_cluster = p->multi.cp_cs && !b16;
+  int g_splits = p->multi.gram_splits;
+  if (p->multi.cp_cs && b16) {
+    g_splits = (int)((p->multi.panel_rows + p->multi.gram_rows_per_split - 1) / p->multi.gram_rows_per_split);
+    if (g_splits > p->multi.gram_splits)
       return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs: the cluster layout of this problem has too few slabs "
                                        "for the two-product form");
   }
   // candidate block: zero everywhere (padding columns, unused slots), then y_k of every state machine
   const size_t per_entry = is_bf16 ? 3 * sizeof(unsigned short) : sizeof(float);
-  HIP_TRY(hipMemsetAsync(p->xp, 0, (size_t)p->n_pad * fos::BT_NV * per_entry, p->stream));
+  HIP_TRY(hipMemsetAsync(p->cand.xp, 0, (size_t)p->cand.n_pad * fos::BT_NV * per_entry, p->stream));
   // Controlled run (adaptive restart / step or ratio tolerance on any weight): momentum and stops are decided on the
   // device per state machine, every iteration; a stopped weight is a masked column of the block.
   fos::MultiControl mc{};
@@ -726,7 +707,7 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
       mc.adaptive_restart[v] = f->prm.adaptive_restart; mc.restart_threshold[v] = f->prm.restart_threshold;
       mc.tol_step[v] = f->prm.tol_step; mc.tol_ratio[v] = f->prm.tol_ratio;
     }
-    hipLaunchKernelGGL(fos::form_y_multi_kernel, dim3(grid_1d(p->n, 256, 64), nv), dim3(256), 0, p->stream, mc, (int)p->n, p->xp,
+    hipLaunchKernelGGL(fos::form_y_multi_kernel, dim3(grid_1d(p->n, 256, 64), nv), dim3(256), 0, p->stream, mc, (int)p->n, p->cand.xp,
                        y_mode, 1);
     LAUNCH_CHECK();
   }
@@ -736,8 +717,8 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
     if ((rc = begin_plain(f, &stopped))) return rc;
     if (stopped) return fail(FOS_ERR_STATE, "fos_fista_run_multi: a handle has already stopped");
     hipLaunchKernelGGL(fos::form_y_block_kernel, dim3(grid_1d(p->n, 256, 256)), dim3(256), 0, p->stream, f->x_cur, f->x_prev,
-                       f->h_beta, (int)p->n, v, is_bf16 ? (float*)nullptr : p->xp,
-                       is_bf16 ? (unsigned short*)p->xp : (unsigned short*)nullptr);
+                       f->h_beta, (int)p->n, v, is_bf16 ? (float*)nullptr : p->cand.xp,
+                       is_bf16 ? (unsigned short*)p->cand.xp.get() : (unsigned short*)nullptr);
     LAUNCH_CHECK();
     restart_plain(f);                // y lives in the candidate block; part2 partials are counted from this run on
   }
@@ -747,29 +728,30 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
     if (use_cluster && (rc = launch_cluster_pass(p))) {
       if (p->cp_mode == 1 || it > 0) return rc;
       (void)hipGetLastError();                   // planner's own choice refused (cooperative launch): two products instead
-      if ((rc = plan_multi_mfma(p, true))) return rc;
+      p->cp_mode = 2;
+      if ((rc = invalidate(p, IN_CLUSTER)) || (rc = plan_multi_mfma(p))) return rc;
       use_cluster = false;
-      g_splits = p->gram_splits;
+      g_splits = p->multi.gram_splits;
     }
-    for (int64_t row0 = 0, panel = 0; !use_cluster && row0 < p->m; row0 += p->panel_rows, ++panel) {
-      const int64_t rows = std::min<int64_t>(p->panel_rows, p->m - row0);
+    for (int64_t row0 = 0, panel = 0; !use_cluster && row0 < p->m; row0 += p->multi.panel_rows, ++panel) {
+      const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
       const char* Ap = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz;
       int nwg1 = 0;
       // column-sharded: b enters the sum over the ranks once (rank 0); R = sum_p A_p Y_p - b is the ONE exchange per panel
       const float* bp = b16 ? b16 + row0 * fos::BT_NV : (p->b && !(cols && p->comm->rank != 0)) ? p->b + row0 : nullptr;
-      if ((rc = launch_batch_product(p, Ap, bp, rows, 1, p->rbuf16, &nwg1, nullptr, b16 != nullptr))) return rc;
-      if (cols && (rc = reduce_across(p, p->rbuf16, (size_t)rows * fos::BT_NV, false))) return rc;
+      if ((rc = launch_batch_product(p, Ap, bp, rows, 1, p->multi.rbuf16, &nwg1, nullptr, b16 != nullptr))) return rc;
+      if (cols && (rc = reduce_across(p, p->multi.rbuf16, (size_t)rows * fos::BT_NV, false))) return rc;
       const dim3 grid((unsigned)strips, (unsigned)g_splits);
 #define FOS_GRAM(T, ACC)                                                                                                  \
   hipLaunchKernelGGL((fos::gram_batch_mfma_kernel<T, ACC>), grid, dim3(fos::GB_THREADS), 0, p->stream, (const T*)Ap, p->lda, \
-                     rows, (int)p->n, p->rbuf16, p->gram_rows_per_split, p->slabs16, p->n)
+                     rows, (int)p->n, p->multi.rbuf16, p->multi.gram_rows_per_split, p->multi.slabs16, p->n)
       if (is_bf16) {
         if (panel)
           hipLaunchKernelGGL(fos::gram_batch_mfma_bf16_kernel<true>, grid, dim3(fos::GB_THREADS), 0, p->stream,
-                             (const fos::bf16_t*)Ap, p->lda, rows, (int)p->n, p->rbuf16, p->gram_rows_per_split, p->slabs16, p->n);
+                             (const fos::bf16_t*)Ap, p->lda, rows, (int)p->n, p->multi.rbuf16, p->multi.gram_rows_per_split, p->multi.slabs16, p->n);
         else
           hipLaunchKernelGGL(fos::gram_batch_mfma_bf16_kernel<false>, grid, dim3(fos::GB_THREADS), 0, p->stream,
-                             (const fos::bf16_t*)Ap, p->lda, rows, (int)p->n, p->rbuf16, p->gram_rows_per_split, p->slabs16, p->n);
+                             (const fos::bf16_t*)Ap, p->lda, rows, (int)p->n, p->multi.rbuf16, p->multi.gram_rows_per_split, p->multi.slabs16, p->n);
       } else { if (panel) FOS_GRAM(float, true); else FOS_GRAM(float, false); }
 #undef FOS_GRAM
       LAUNCH_CHECK();
@@ -777,39 +759,39 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
     if ((rc = prof_mark(p, false))) return rc;
     // row-sharded problem: the 16 partial gradients (all row splits) are summed over the ranks before the updates
     // (column-sharded: the gradient block is local)
-    if (!cols && (rc = reduce_across(p, p->slabs16, (size_t)g_splits * fos::BT_NV * p->n, false))) return rc;
+    if (!cols && (rc = reduce_across(p, p->multi.slabs16, (size_t)g_splits * fos::BT_NV * p->n, false))) return rc;
     if (controlled || same_family) {             // one launch updates all state machines
       const fos::MultiUpdate mu = multi_update(fs, nv, controlled);
-      hipLaunchKernelGGL(fos::fista_update_multi_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->slabs16, g_splits,
-                         (int)p->n, mu, fs[0]->prm, p->xp, y_mode, controlled ? 0 : 1);
+      hipLaunchKernelGGL(fos::fista_update_multi_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->multi.slabs16, g_splits,
+                         (int)p->n, mu, fs[0]->prm, p->cand.xp, y_mode, controlled ? 0 : 1);
       LAUNCH_CHECK();
     } else {
       for (int v = 0; v < nv; ++v) {
         const PlainStep s = advance_plain(fs[v], false);
-        if ((rc = launch_update_from_slabs(fs[v], s.part, 1, s.beta, nullptr, p->xp, s.beta_next, p->slabs16 + (size_t)v * p->n,
+        if ((rc = launch_update_from_slabs(fs[v], s.part, 1, s.beta, nullptr, p->cand.xp, s.beta_next, p->multi.slabs16 + (size_t)v * p->n,
                                            (int64_t)fos::BT_NV * p->n, g_splits, y_mode, v)))
           return rc;
       }
     }
     if (controlled) {                            // bookkeeping of all weights (device beta) -> their y_{k+1}
       if (cols) {                                // step norms, ||x||^2, ||x||_1 are sums over the column blocks of all ranks
-        hipLaunchKernelGGL(fold4_multi_kernel, dim3(nv), dim3(64), 0, p->stream, mc, fs[0]->nupd, p->mfold);
+        hipLaunchKernelGGL(fold4_multi_kernel, dim3(nv), dim3(64), 0, p->stream, mc, fs[0]->nupd, p->ws.mfold);
         LAUNCH_CHECK();
-        if ((rc = reduce_across(p, p->mfold, (size_t)nv * 4, true))) return rc;
+        if ((rc = reduce_across(p, p->ws.mfold, (size_t)nv * 4, true))) return rc;
         fos::MultiControl mf = mc;
-        for (int v = 0; v < nv; ++v) mf.part[v] = p->mfold + (size_t)v * 4;
+        for (int v = 0; v < nv; ++v) mf.part[v] = p->ws.mfold + (size_t)v * 4;
         hipLaunchKernelGGL(fos::fista_finalize_multi_kernel, dim3(nv), dim3(64), 0, p->stream, mf, 1, fs[0]->prm);
       } else
         hipLaunchKernelGGL(fos::fista_finalize_multi_kernel, dim3(nv), dim3(64), 0, p->stream, mc, fs[0]->nupd, fs[0]->prm);
       LAUNCH_CHECK();
-      hipLaunchKernelGGL(fos::form_y_multi_kernel, dim3(grid_1d(p->n, 256, 64), nv), dim3(256), 0, p->stream, mc, (int)p->n, p->xp,
+      hipLaunchKernelGGL(fos::form_y_multi_kernel, dim3(grid_1d(p->n, 256, 64), nv), dim3(256), 0, p->stream, mc, (int)p->n, p->cand.xp,
                          y_mode, 0);
       LAUNCH_CHECK();
     }
   }
   if (use_cluster) {     // a cluster member that waited out its bound parked itself and raised the flag: the sums are invalid
     int bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, p->cp_error, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(&bad, p->multi.cp_error, sizeof(int), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     if (bad) return fail(FOS_ERR_STATE, "fos_fista_run_multi: the one-read cluster pass timed out waiting for a member "
                                         "(results invalid); rerun with FOS_PLAN_NO_CLUSTER");
@@ -822,7 +804,7 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
 }
 
 // The lockstep dispatcher of fos_fista_run_multi (B == nullptr: the problem's b) and fos_fista_run_multi_rhs (B: column v of
-// the caller's m x nv block for state machine v, staged once per call into the m x 16 block p->b16).  Arguments are checked.
+// the caller's m x nv block for state machine v, staged once per call into the m x 16 block p->ws.b16).  Arguments are checked.
 static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, int64_t ldb) {
   fos_problem* p = fs[0]->p;
   const bool rhs = B != nullptr;
@@ -843,7 +825,7 @@ static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, in
     const fos::FistaParams &a = fs[0]->prm, &c = fs[v]->prm;
     same_family = same_family && a.mode == c.mode && a.prox_kind == c.prox_kind && a.delta == c.delta;
   }
-  const bool shape_ok = batch_supported(p) && !p->colblock && !p->resident && !p->col_sharded;
+  const bool shape_ok = batch_supported(p) && !p->pass.colblock && !p->pass.resident && !p->col_sharded;
   // Column-sharded (very wide A): the two products per panel with ONE exchange of the panel's 16 residual columns between
   // them; always device-controlled (step norms are sums over the ranks).  The matrix-core kernels tile any width.
   if (p->col_sharded) {
@@ -853,31 +835,32 @@ static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, in
     if (iters == 0) return FOS_OK;
     return run_multi_mfma(fs, nv, iters, true, true);
   }
-  if (!all_plain && controllable && same_family && shape_ok && p->entry != wide_entry(p->dtype) && (nv >= 3 || p->comm)) {
+  if (!all_plain && controllable && same_family && shape_ok && p->pass.entry != wide_entry(p->dtype) && (nv >= 3 || p->comm)) {
     if (iters == 0) return FOS_OK;
     int rc = stage();
     if (rc) return rc;
-    return run_multi_mfma(fs, nv, iters, true, true, rhs ? p->b16 : nullptr);
+    return run_multi_mfma(fs, nv, iters, true, true, rhs ? p->ws.b16 : nullptr);
   }
   const bool streaming = shape_ok && all_plain;
   // (a sharded problem takes the matrix-core pass for any number of weights: its 16 gradients are one 16 x n all-reduce)
-  MultiLaunch fn = (streaming && !p->tall && !p->comm && p->dtype == FOS_F32 && p->entry != wide_entry(p->dtype)) ? find_multi(p->n, nv, rhs) : nullptr;
+  MultiLaunch fn = (streaming && !p->pass.tall && !p->comm && p->dtype == FOS_F32 && p->pass.entry != wide_entry(p->dtype)) ? find_multi(p->n, nv, rhs) : nullptr;
   // the two-product pass costs about two single-vector passes per iteration whatever the number of weights: it pays
   // from three weights on (profiles/r02_multilambda.md); two weights without a VALU multi-vector kernel run one by one
-  if (!fn && streaming && p->entry != wide_entry(p->dtype) && (nv >= 3 || p->comm)) {
+  if (!fn && streaming && p->pass.entry != wide_entry(p->dtype) && (nv >= 3 || p->comm)) {
     if (iters == 0) return FOS_OK;
     int rc = stage();
     if (rc) return rc;
-    return run_multi_mfma(fs, nv, iters, false, same_family, rhs ? p->b16 : nullptr);   // 5..16 weights, n up to 16384, fp32 and bf16
+    return run_multi_mfma(fs, nv, iters, false, same_family, rhs ? p->ws.b16 : nullptr);   // 5..16 weights, n up to 16384, fp32 and bf16
   }
   if (!fn) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi: no multi-vector kernel for this shape / configuration");
   if (iters == 0) return FOS_OK;
   int rc = stage();
   if (rc) return rc;
   // workspace: nv interleaved slab sets and rr partials per workgroup
-  const int nwg = p->nwg;
-  if ((rc = grow(&p->slab_cap, nwg * nv, (size_t)p->n * sizeof(float), &p->slabs))) return rc;
-  if ((rc = grow(&p->rr_cap, nwg * nv, sizeof(double), &p->rr_part, &p->rr2_part))) return rc;
+  const int nwg = p->pass.nwg;
+  if ((rc = p->pass.slabs.reserve((size_t)nwg * nv * p->n)) || (rc = p->pass.rr_part.reserve((size_t)nwg * nv)) ||
+      (rc = p->pass.rr2_part.reserve((size_t)nwg * nv)))
+    return rc;
   fos::MultiY ys{};
   ys.stopped = nullptr;
   for (int v = 0; v < nv; ++v) {
@@ -891,12 +874,12 @@ static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, in
   for (int v = nv; v < 4; ++v) ys.y[v] = ys.y[0];
   for (int it = 0; it < iters; ++it) {
     if ((rc = prof_mark(p, true))) return rc;
-    fn((const float*)p->A, p->lda, rhs ? p->b16 : p->b, p->m, (int)p->n, ys, p->rows_per_wg, p->slabs, p->rr_part, nwg, p->stream);
+    fn((const float*)p->A, p->lda, rhs ? p->ws.b16 : p->b, p->m, (int)p->n, ys, p->pass.rows_per_wg, p->pass.slabs, p->pass.rr_part, nwg, p->stream);
     LAUNCH_CHECK();
     if ((rc = prof_mark(p, false))) return rc;
     for (int v = 0; v < nv; ++v) {
       const PlainStep s = advance_plain(fs[v], true);
-      if ((rc = launch_update_from_slabs(fs[v], s.part, 1, s.beta, nullptr, fs[v]->ynext, s.beta_next, p->slabs + (size_t)v * p->n,
+      if ((rc = launch_update_from_slabs(fs[v], s.part, 1, s.beta, nullptr, fs[v]->ynext, s.beta_next, p->pass.slabs + (size_t)v * p->n,
                                          (int64_t)nv * p->n)))
         return rc;
     }
@@ -925,7 +908,7 @@ int fos_fista_grad(fos_fista* f) {
   if (!f) return fail(FOS_ERR_ARG, "fos_fista_grad: null");
   fos_problem* p = f->p;
   int n_rr = 0, rc;
-  if (f->precise && !p->resident) {
+  if (f->precise && !p->pass.resident) {
     // fp64-accumulating pass at the unrounded y_k = x_k + beta (x_k - x_{k-1}); alpha2*y is added by the consumers
     YSource ys = (plain_run(f) && f->host_valid)
                      ? YSource{nullptr, f->x_cur, f->x_prev, nullptr, &f->scal->stopped, f->h_beta, nullptr}
@@ -946,21 +929,21 @@ int fos_fista_grad_dual(fos_fista* f) {
   fos_problem* p = f->p;
   int n_rr = 0, rc;
   if ((rc = flush_pending(f))) return rc;
-  if (p->path == 0 && !p->colblock && p->entry->dual != nullptr && !(f->precise && !p->resident)) {
+  if (p->pass.path == 0 && !p->pass.colblock && p->pass.entry->dual != nullptr && !(f->precise && !p->pass.resident)) {
     if ((rc = launch_pass(p, fista_source(f), p->b, true, &n_rr, true))) return rc;
     if ((rc = launch_slab_reduce(p, n_rr, p->gbuf, &f->scal->rr, &f->scal->stopped))) return rc;
-    hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->rr2_part, n_rr, 1,
+    hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->pass.rr2_part, n_rr, 1,
                        &f->scal->rr_x);
     LAUNCH_CHECK();
     return p->col_sharded ? FOS_OK : reduce_across(p, &f->scal->rr_x, 1, true);
   }
   // no DUAL instantiation (fallback path / wide geometries): a separate residual pass on x_k, then the gradient
-  hipLaunchKernelGGL(fos::cast_f64_f32_kernel, dim3(grid_1d(p->n, 256, 1024)), dim3(256), 0, p->stream, f->x_cur, p->ybuf,
+  hipLaunchKernelGGL(fos::cast_f64_f32_kernel, dim3(grid_1d(p->n, 256, 1024)), dim3(256), 0, p->stream, f->x_cur, p->ws.ybuf,
                      p->n);
   LAUNCH_CHECK();
-  YSource ys{p->ybuf, nullptr, nullptr, nullptr, &f->scal->stopped};
+  YSource ys{p->ws.ybuf, nullptr, nullptr, nullptr, &f->scal->stopped};
   if ((rc = launch_pass(p, ys, p->b, false, &n_rr))) return rc;
-  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->rr_part, n_rr, 1,
+  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->pass.rr_part, n_rr, 1,
                      &f->scal->rr_x);
   LAUNCH_CHECK();
   if (!p->col_sharded && (rc = reduce_across(p, &f->scal->rr_x, 1, true))) return rc;
@@ -976,7 +959,7 @@ int fos_fista_update(fos_fista* f) {
     return launch_update(f, nullptr, 0, grad_src(f), f->prm, s.part, 1, s.beta, nullptr, f->ynext, s.beta_next);
   }
   hand_to_device(f);
-  int rc = launch_update(f, nullptr, 0, grad_src(f), f->prm, p->part, 0, 0.0, nullptr, nullptr, 0.0);
+  int rc = launch_update(f, nullptr, 0, grad_src(f), f->prm, p->ws.part, 0, 0.0, nullptr, nullptr, 0.0);
   return rc ? rc : launch_finalize(f, 0);
 }
 
@@ -988,8 +971,8 @@ int fos_fista_trial(fos_fista* f, double t, int with_residual, double out8[8]) {
   const int grid = grid_1d(p->n, 256, 256);
   HIP_TRY(hipMemsetAsync(f->out5, 0, 8 * sizeof(double), p->stream));
   hipLaunchKernelGGL(fos::fista_trial_kernel, dim3(grid), dim3(256), 0, p->stream, grad_src(f), (int)p->n, f->x_cur,
-                     f->x_prev, f->scal, f->prm, t, f->dlt, p->part);
-  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->part, grid, fos::TRIAL_W, f->out5);
+                     f->x_prev, f->scal, f->prm, t, f->dlt, p->ws.part);
+  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->ws.part, grid, fos::TRIAL_W, f->out5);
   LAUNCH_CHECK();
   // rr(y_k) was produced by fos_fista_grad; copy it before the trial pass reuses the partial buffer
   HIP_TRY(hipMemcpyAsync(f->out5 + 6, &f->scal->rr, sizeof(double), hipMemcpyDeviceToDevice, p->stream));
@@ -997,7 +980,7 @@ int fos_fista_trial(fos_fista* f, double t, int with_residual, double out8[8]) {
     YSource ys{f->dlt, nullptr, nullptr, nullptr, nullptr};
     int n_rr = 0, rc;
     if ((rc = launch_pass(p, ys, nullptr, false, &n_rr))) return rc;        // ||A dlt||^2  (b = 0)
-    hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->rr_part, n_rr, 1, f->out5 + 5);
+    hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->pass.rr_part, n_rr, 1, f->out5 + 5);
     LAUNCH_CHECK();
     if ((rc = reduce_across(p, f->out5 + 5, 1, true))) return rc;
   }
@@ -1010,22 +993,22 @@ int fos_fista_trial(fos_fista* f, double t, int with_residual, double out8[8]) {
 // core pass ||A dlt_j||^2 -> bt_out[64..80).  t_from_state: t is FistaScalars::tau on the device (no host value).
 static int enqueue_trial_batch(fos_fista* f, double t, double eta, int nv, int t_from_state) {
   fos_problem* p = f->p;
-  const int grid = grid_1d(p->n_pad, 256, 64);
+  const int grid = grid_1d(p->cand.n_pad, 256, 64);
   const int* stopped = t_from_state ? &f->scal->stopped : nullptr;
   if (p->dtype == FOS_BF16)
     hipLaunchKernelGGL(fos::fista_trial_batch_bf16_kernel, dim3(grid), dim3(256), 0, p->stream, grad_src(f), (int)p->n,
-                       (int)p->n_pad, f->x_cur, f->x_prev, f->scal, f->prm, t, eta, nv, (unsigned short*)p->xp, p->part,
+                       (int)p->cand.n_pad, f->x_cur, f->x_prev, f->scal, f->prm, t, eta, nv, (unsigned short*)p->cand.xp.get(), p->ws.part,
                        t_from_state);
   else
     hipLaunchKernelGGL(fos::fista_trial_batch_kernel, dim3(grid), dim3(256), 0, p->stream, grad_src(f), (int)p->n,
-                       (int)p->n_pad, f->x_cur, f->x_prev, f->scal, f->prm, t, eta, nv, p->xp, p->part, t_from_state);
-  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->part, grid, fos::BT_W, p->bt_out);
+                       (int)p->cand.n_pad, f->x_cur, f->x_prev, f->scal, f->prm, t, eta, nv, p->cand.xp, p->ws.part, t_from_state);
+  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->ws.part, grid, fos::BT_W, p->cand.bt_out);
   LAUNCH_CHECK();
   if (p->col_sharded) {              // grad.dlt_j, ||dlt_j||^2, the counts, ||grad||^2, ||y||^2 are sums over the column blocks
-    int rc = reduce_across(p, p->bt_out, fos::BT_W, true);
+    int rc = reduce_across(p, p->cand.bt_out, fos::BT_W, true);
     if (rc) return rc;
   }
-  return launch_residual_batch(p, 0, p->bt_out + 64, stopped);
+  return launch_residual_batch(p, 0, p->cand.bt_out + 64, stopped);
 }
 
 // Device-driven iterations with data-dependent control - Armijo search, adaptive restart, the stopping rules - and,
@@ -1061,13 +1044,13 @@ static int run_device_driven(fos_fista* f, int iters, bool backtracking, double 
     if (f->prm.tol_grad > 0.0 && (rc = launch_grad_norm_stop(f))) return rc;   // :179
     if (backtracking) {
       if ((rc = enqueue_trial_batch(f, 0.0, eta, fos::BT_NV, 1))) return rc;   // :187-191 for 16 candidates
-      hipLaunchKernelGGL(fos::armijo_decide_kernel, dim3(1), dim3(1), 0, p->stream, p->bt_out, f->scal, f->prm, eta,
+      hipLaunchKernelGGL(fos::armijo_decide_kernel, dim3(1), dim3(1), 0, p->stream, p->cand.bt_out, f->scal, f->prm, eta,
                          armijo_c, grad_eps, fos::BT_NV, ls_iters, tau_hist, (long long)it);
       LAUNCH_CHECK();
     }
     // update (with the step the decision left in FistaScalars::tau), then the scalar bookkeeping / history row
     double* xrow = x_hist ? x_hist + (size_t)it * p->n : nullptr;
-    if ((rc = launch_update(f, nullptr, 0, grad_src(f), prm_dev, p->part, 0, 0.0, xrow, nullptr, 0.0))) return rc;
+    if ((rc = launch_update(f, nullptr, 0, grad_src(f), prm_dev, p->ws.part, 0, 0.0, xrow, nullptr, 0.0))) return rc;
     if ((rc = launch_finalize(f, 0, record ? hist + (size_t)it * 4 : nullptr))) return rc;
   }
   return FOS_OK;
@@ -1078,7 +1061,7 @@ int fos_fista_run_backtracking(fos_fista* f, int iters, double eta, double armij
   if (!f || iters < 0 || !(eta > 0.0 && eta < 1.0) || !(grad_eps >= 0.0))
     return fail(FOS_ERR_ARG, "fos_fista_run_backtracking: bad argument");
   fos_problem* p = f->p;
-  if (!batch_supported(p) || p->resident)
+  if (!batch_supported(p) || p->pass.resident)
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_backtracking: needs the matrix-core candidate pass (streaming plans)");
   if (iters == 0) return FOS_OK;
   return run_device_driven(f, iters, true, eta, armijo_c, grad_eps, ls_iters, tau_hist, nullptr, nullptr, nullptr);
@@ -1090,7 +1073,7 @@ int fos_fista_run_recorded(fos_fista* f, int iters, int backtracking, double eta
       (backtracking && (!(eta > 0.0 && eta < 1.0) || !(grad_eps >= 0.0))))
     return fail(FOS_ERR_ARG, "fos_fista_run_recorded: bad argument");
   fos_problem* p = f->p;
-  if (p->resident || (backtracking && !batch_supported(p)))
+  if (p->pass.resident || (backtracking && !batch_supported(p)))
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_recorded: resident problems record inside their one launch; "
                                      "backtracking needs the matrix-core candidate pass");
   if (iters == 0) return FOS_OK;
@@ -1119,9 +1102,9 @@ int fos_fista_trial_batch(fos_fista* f, double t, double eta, int nv, double* ou
   int rc = ensure_batch_workspace(p);
   if (rc) return rc;
   if ((rc = enqueue_trial_batch(f, t, eta, nv, 0))) return rc;
-  HIP_TRY(hipMemcpyAsync(p->bt_out + 100, &f->scal->rr, sizeof(double), hipMemcpyDeviceToDevice, p->stream));
+  HIP_TRY(hipMemcpyAsync(p->cand.bt_out + 100, &f->scal->rr, sizeof(double), hipMemcpyDeviceToDevice, p->stream));
   double h[128];
-  HIP_TRY(hipMemcpyAsync(h, p->bt_out, 128 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipMemcpyAsync(h, p->cand.bt_out, 128 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   for (int j = 0; j < nv; ++j) {
     double* o = out + 8 * j;

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <chrono>
 #include <vector>
@@ -53,24 +54,53 @@ inline int fail(int code, const std::string& msg) {
     if (e_ != hipSuccess) return fail(FOS_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e_)); \
   } while (0)
 
-// Device buffers that grow with demand: when `need` exceeds *cap, a (and b, sized alike) are freed and reallocated to exactly
-// need * unit bytes.  A failed allocation leaves *cap = 0, so the next call tries again.
-template <class T>
-int grow(int* cap, int64_t need, size_t unit, T** a, T** b = nullptr) {
-  if (need <= *cap) return FOS_OK;
-  T** bufs[] = {a, b};
-  for (T** q : bufs)
-    if (q && *q) {
-      (void)hipFree(*q);
-      *q = nullptr;
+// The one owner of an allocation the library makes: freed once (in the destructor or in reset(), with a plain hipFree, which
+// waits for the device), sized in BYTES.  Every device buffer of a handle is a DevBuf member; a raw pointer member is memory
+// that belongs to the caller.  Converts to the raw pointer for kernel arguments.  PINNED: host memory the device can write.
+template <class T, bool PINNED = false>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : ptr_(o.ptr_), bytes_(o.bytes_) { o.ptr_ = nullptr; o.bytes_ = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      std::swap(ptr_, o.ptr_);
+      std::swap(bytes_, o.bytes_);
     }
-  *cap = 0;
-  for (T** q : bufs)
-    if (q) HIP_TRY(hipMalloc(q, (size_t)need * unit));
-  *cap = (int)need;
-  return FOS_OK;
-}
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  void reset() {
+    if (ptr_) (void)(PINNED ? hipHostFree(ptr_) : hipFree(ptr_));
+    ptr_ = nullptr;
+    bytes_ = 0;
+  }
+  // Room for `count` elements: a no-op when the buffer is large enough, otherwise freed and allocated to exactly
+  // count * sizeof(T) bytes (contents are not kept).  A failed allocation leaves the buffer empty: the next call tries again.
+  int reserve(size_t count) {
+    const size_t need = count * sizeof(T);
+    if (ptr_ && need <= bytes_) return FOS_OK;
+    reset();
+    const hipError_t e = PINNED ? hipHostMalloc(&ptr_, need) : hipMalloc(&ptr_, need);
+    if (e != hipSuccess) {
+      ptr_ = nullptr;
+      return fail(FOS_ERR_HIP, std::string(PINNED ? "hipHostMalloc(" : "hipMalloc(") + std::to_string(need) + " bytes): " +
+                                   hipGetErrorString(e));
+    }
+    bytes_ = need;
+    return FOS_OK;
+  }
+  T* get() const { return ptr_; }
+  operator T*() const { return ptr_; }
+  T* operator->() const { return ptr_; }
 
+ private:
+  T* ptr_ = nullptr;
+  size_t bytes_ = 0;
+};
+template <class T>
+using PinnedBuf = DevBuf<T, true>;
 
 using fos::YSource;
 
@@ -100,55 +130,39 @@ typedef void (*MultiLaunch)(const float* A, int64_t lda, const float* b, int64_t
 using fosapi::MenuEntry;
 using fosapi::DdEntry;
 
-// Device + pinned workspace of fos_lbfgs_minimize, cached on the problem handle: round 2 allocated it per fit (7 hipMalloc +
-// hipHostMalloc + 2 events per fg, and the hipFree's at the end drain the device) inside an 8 ms fit.
+using fosapi::DevBuf;
+using fosapi::PinnedBuf;
+
+// Device + pinned workspace of fos_lbfgs_minimize, cached on the problem handle (allocating per fit cost more than an 8 ms
+// fit's iterations, and the frees at its end drain the device).  Complete only when n is set.
 struct LbfgsWork {
   int64_t n = 0;
-  double *g = nullptr, *g_old = nullptr, *d = nullptr, *x_old = nullptr, *S = nullptr, *Y = nullptr, *vl = nullptr;
-  double* host = nullptr;              // pinned: 16 doubles
-  unsigned long long* t_start = nullptr;   // device: wall-clock stamp taken in front of an evaluation
+  DevBuf<double> g, g_old, d, x_old, S, Y, vl;
+  PinnedBuf<double> host;              // 16 doubles
+  DevBuf<unsigned long long> t_start;  // wall-clock stamp taken in front of an evaluation
   double ticks_per_ms = 1e5;           // hipDeviceAttributeWallClockRate (kHz)
   bool pass_stamps = false;           // the pass kernel of this plan stamps its own start (dd_pass_stamps)
-  ~LbfgsWork() {
-    void* bufs[] = {g, g_old, d, x_old, S, Y, vl, t_start};
-    for (void* q : bufs)
-      if (q) (void)hipFree(q);
-    if (host) (void)hipHostFree(host);
-  }
 };
 
 // Device + pinned workspace of fos_lbfgs_minimize_multi (16 columns, column-contiguous), cached like LbfgsWork.
 struct LbfgsMultiWork {
   int64_t n = 0;
-  double *g = nullptr;                 // [2][16][n]: the two gradient buffers of every column (current / previous)
-  double *d = nullptr, *x_old = nullptr, *S = nullptr, *Y = nullptr, *vl = nullptr, *rr = nullptr;
-  double* host = nullptr;              // pinned: 16 columns x 16 doubles, then the sequence number
-  unsigned* count = nullptr;           // device: workgroups of the statistics launch that have reported
-  unsigned long long* t_start = nullptr;
+  DevBuf<double> g;                    // [2][16][n]: the two gradient buffers of every column (current / previous)
+  DevBuf<double> d, x_old, S, Y, vl, rr;
+  PinnedBuf<double> host;              // 16 columns x 16 doubles, then the sequence number
+  DevBuf<unsigned> count;              // workgroups of the statistics launch that have reported
+  DevBuf<unsigned long long> t_start;
   double ticks_per_ms = 1e5;
-  ~LbfgsMultiWork() {
-    void* bufs[] = {g, d, x_old, S, Y, vl, rr, count, t_start};
-    for (void* q : bufs)
-      if (q) (void)hipFree(q);
-    if (host) (void)hipHostFree(host);
-  }
 };
 
-struct fos_problem {
-  const void* A = nullptr;
-  const float* b = nullptr;
-  int64_t m = 0, n = 0, lda = 0;
-  int dtype = FOS_F32;
-  hipStream_t stream = nullptr;
-  int ncu = 256;
-  fos_comm* comm = nullptr;          // row-sharded problem: sums of partial results go through it (comm.hpp)
-  LbfgsWork* lbfgs = nullptr;        // fos_lbfgs_minimize workspace, allocated by the first fit
-  LbfgsMultiWork* lbfgs_multi = nullptr;   // fos_lbfgs_minimize_multi workspace
-  bool col_sharded = false;          // comm splits the COLUMNS instead: this rank holds A[:, its columns], x is partitioned
-  unsigned plan_flags = 0;           // FOS_PLAN_* given to fos_problem_replan
-  bool allow_resident = true;
-  bool il = false;                   // rows dealt round-robin to the workgroups (FOS_PLAN_INTERLEAVE / planner default for big rows)
-  // plan
+// The plan of a problem handle, in groups: each holds the numbers of ONE decision and the buffers that decision sizes, names
+// the inputs it was derived from, and is cleared as a whole by reset().  fosapi::invalidate (fos_plan.hip) is the one place
+// that decides which groups an entry point resets; a group is rebuilt by its planner function on the next use.
+
+// fp32 pass.  From: shape, layout (lda, alignment of A), plan flags, fos_problem_tune, comm (resident), column sharding.
+// Filled by apply_plan / plan_cols (plan_fused, plan_tall, plan_fallback, plan_resident), buffers by ensure_workspace; the
+// fused step and the multi-vector VALU pass reserve more slabs / partials for their own grids.
+struct PassPlan {
   int path = 0;                      // 0 fused, 1 two-pass fallback
   bool resident = false;             // small enough for the single-launch LDS-resident loop (resident.hpp)
   bool tall = false;                 // n <= 64: row-per-thread single pass (gemv_tall.hpp); no alignment requirements
@@ -156,77 +170,125 @@ struct fos_problem {
   // columns through the streaming kernel in two phases, r = A y - b block by block, then A^T r block by block
   bool colblock = false;
   int64_t cb_width = 0;
-  float* rneg = nullptr;             // m floats: the negated residual between the two phases
-  float* zeros = nullptr;            // cb_width floats of zeros (phase 2 runs the same kernel with y = 0, b = -r)
   int64_t slab_stride = 0;           // floats between slab rows (0 = n); the tall pass pads rows to a multiple of 4
+  bool vec4 = false;                 // n % 4 == 0: float4 epilogues
   const MenuEntry* entry = nullptr;
   int nwg = 0;                       // workgroups of the fused kernel
   int nslabs = 0;
   int64_t rows_per_wg = 0;
   int resid_grid = 0;                // fallback pass-1 grid
-  bool vec4 = false;                 // n % 4 == 0: float4 epilogues
-  // workspace
-  int slab_cap = 0, rr_cap = 0;
-  float* slabs = nullptr;
-  double* rr_part = nullptr;
-  double* rr2_part = nullptr;        // DUAL pass: partials of ||A x_k - b||^2
-  double* rvec = nullptr;            // fallback: residual (m doubles)
-  float* gbuf = nullptr;             // n + 4 floats (internal, or caller-owned after fos_problem_set_gbuf)
-  float* gbuf_own = nullptr;
-  // fp64-accumulating pass (fos_gemv_pair_dd): own geometry and fp64 slabs, allocated on first use
-  const DdEntry* dd_entry = nullptr;
-  int dd_nwg = 0;
-  int dd_nwg_hint = 0;               // fos_problem_tune_dd: workgroups of the streaming fp64 pass (0 = planner)
-  int64_t dd_rows_per_wg = 0;
-  double* slabs_dd = nullptr;
-  double* rr_dd = nullptr;
-  int dd_two_pass_chunks = 0;        // > 0: this shape runs the fp64 two-pass kernels for the dd pass
-  float* ybuf = nullptr;             // n floats: aligned copy of a caller vector when needed
-  double* dscal = nullptr;           // 256 device doubles (scalars)
-  double* lhist = nullptr;           // power iteration: L after every step (n_iter + 1 doubles, grown on demand)
-  int lhist_cap = 0;
-  double* part = nullptr;            // partial sums of the small kernels
-  int part_cap = 0;
-  // batched (MFMA) residual: permuted candidate block, per-workgroup partials, folded results
-  float* xp = nullptr;
-  double* q_part = nullptr;
-  double* bt_out = nullptr;          // 128 doubles
-  int64_t n_pad = 0;
-  // multi-lambda pass on the matrix cores (gram_batch.hpp): residual panel and the 16 gradient slab sets
-  float* rbuf16 = nullptr;           // panel_rows x 16 floats
-  float* rcols16 = nullptr;          // column-sharded candidate pass: m x 16 partial residuals (summed over the ranks)
-  float* b16 = nullptr;              // several right-hand sides: m x 16 zero-padded block of the caller's B (stage_b16)
-  double* cr_part = nullptr;         // chip-resident loop (chip_resident.hpp): [2][G][17] partials + [8] step sums + [1] rr
-  unsigned* cr_bar = nullptr;
-  unsigned long long* fz_stamps = nullptr;   // caller-owned (fos_problem_set_fused_stamps), [ncu][8]
-  double* mfold = nullptr;           // column-sharded lockstep: 16 x 4 folded step partials (summed over the ranks)
-  float* slabs16 = nullptr;          // splits x 16 x n floats
+  DevBuf<float> slabs;
+  DevBuf<double> rr_part;
+  DevBuf<double> rr2_part;           // DUAL pass: partials of ||A x_k - b||^2
+  DevBuf<double> rvec;               // two-pass forms (this one and the fp64 pass's): residual (m doubles)
+  DevBuf<float> rneg;                // m floats: the negated residual between the two column-block phases
+  DevBuf<float> zeros;               // cb_width floats of zeros (phase 2 runs the same kernel with y = 0, b = -r)
+  void reset() { *this = PassPlan{}; }
+};
+
+// fp64-accumulating pass (fos_gemv_pair_dd).  From: the fp32 pass group (tall plans share its grid and slab stride; resident
+// plans need nothing), dd_nwg_hint, column sharding.  Filled by ensure_dd on first use.
+struct DdPlan {
+  bool planned = false;
+  const DdEntry* entry = nullptr;    // streaming geometry; null: tall (the fp32 pass's entry) or two-pass
+  int nwg = 0;
+  int64_t rows_per_wg = 0;
+  int two_pass_chunks = 0;           // > 0: this shape runs the fp64 two-pass kernels for the dd pass
+  DevBuf<double> slabs;
+  DevBuf<double> rr;
+  void reset() { *this = DdPlan{}; }
+};
+
+// Multi-weight lockstep on the matrix cores (gram_batch.hpp; one-read form: cluster_pass.hpp).  From: shape, cp_mode, comm,
+// col_sharded, the communicator's inbox size.  Filled by plan_multi_mfma on first use.
+struct MultiPlan {
+  bool planned = false;
   int64_t panel_rows = 0;
   int gram_splits = 0;
   int64_t gram_rows_per_split = 0;
-  // fp64 multi-point pass on the matrix cores (gram_batch_dd.hpp, fos_gemv_pair_dd_multi): staged points, residual panel,
-  // slab sets and product-1 partials of all panels; geometry decided on first use
-  double* xd = nullptr;              // n_pad64 x 16 doubles (Xp layout)
-  double* rdd = nullptr;             // dm_panel_rows x 16 doubles
-  double* slabs_dd16 = nullptr;      // dm_splits x 16 x n doubles
-  double* qdd_part = nullptr;        // panels x 2 * ncu x 16 doubles
-  int64_t dm_n_pad = 0, dm_panel_rows = 0, dm_rows_per_split = 0;
-  int dm_splits = 0;
-  // one-read form of the same pass (cluster_pass.hpp): hand-off ring, flags, launch epoch
-  int cp_cs = 0, cp_clusters = 0;    // members per cluster (0: shape not served), clusters
+  int cp_cs = 0, cp_clusters = 0;    // members per cluster (0: two products per panel), clusters
   int64_t cp_rows_per_cluster = 0;
-  float* cp_xchg = nullptr;
-  unsigned* cp_flags = nullptr;
-  int* cp_error = nullptr;
-  unsigned cp_epoch = 1;
-  int cp_mode = 0;                   // 0: planner's choice, 1: FOS_PLAN_CLUSTER, 2: FOS_PLAN_NO_CLUSTER
+  DevBuf<float> rbuf16;              // residual panel: panel_rows x 16 floats
+  DevBuf<float> slabs16;             // the 16 gradient slab sets: splits x 16 x n floats
+  DevBuf<float> cp_xchg;             // one-read form: hand-off ring
+  DevBuf<unsigned> cp_flags;         // zeroed when allocated; fos_problem::cp_epoch keeps counting across a rebuild
+  DevBuf<int> cp_error;
+  void reset() { *this = MultiPlan{}; }
+};
+
+// fp64 multi-point pass on the matrix cores (gram_batch_dd.hpp, fos_gemv_pair_dd_multi).  From: shape, CU count.  Filled by
+// ensure_dd_multi on first use.
+struct DdMultiPlan {
+  bool planned = false;
+  int64_t n_pad = 0, panel_rows = 0, rows_per_split = 0;
+  int splits = 0;
+  DevBuf<double> xd;                 // staged points: n_pad x 16 doubles (Xp layout)
+  DevBuf<double> rdd;                // residual panel: panel_rows x 16 doubles
+  DevBuf<double> slabs;              // splits x 16 x n doubles
+  DevBuf<double> q_part;             // product-1 partials of all panels: panels x 2 * ncu x 16 doubles
+  void reset() { *this = DdMultiPlan{}; }
+};
+
+// Candidate block of the batched (MFMA) residual and of the lockstep.  From: shape, dtype, CU count.  Filled by
+// ensure_batch_workspace on first use.
+struct CandPlan {
+  bool planned = false;
+  int64_t n_pad = 0;
+  DevBuf<float> xp;                  // permuted candidate block (bf16 storage: three bf16 terms per entry)
+  DevBuf<double> q_part;             // per-workgroup partials
+  DevBuf<double> bt_out;             // folded results: 128 doubles
+  void reset() { *this = CandPlan{}; }
+};
+
+// Scratch sized by the shape and the CU count alone: nothing invalidates it.  gbuf_own ... part: fos_problem_create; the rest
+// on first use by the entry point named.
+struct Scratch {
+  DevBuf<float> gbuf_own;            // n + 4 floats
+  DevBuf<float> ybuf;                // n floats: aligned copy of a caller vector when needed
+  DevBuf<double> dscal;              // 256 device doubles (scalars)
+  DevBuf<double> part;               // partial sums of the small kernels
+  DevBuf<double> lhist;              // fos_power_iter: L after every step (n_iter + 1 doubles, grown on demand)
+  DevBuf<float> rcols16;             // column-sharded candidate pass: m x 16 partial residuals (summed over the ranks)
+  DevBuf<float> b16;                 // several right-hand sides: m x 16 zero-padded block of the caller's B (stage_b16)
+  DevBuf<double> mfold;              // column-sharded lockstep: 16 x 4 folded step partials (summed over the ranks)
+  DevBuf<double> cr_part;            // chip-resident loop (chip_resident.hpp): [2][G][17] partials + [8] step sums + [1] rr
+  DevBuf<unsigned> cr_bar;
   // fused persistent step (fused_step.hpp, fos_fista_run_fused): barrier words, per-workgroup partials, beta sequence
+  DevBuf<unsigned> fz_bar;
+  DevBuf<double> fz_part;
+  DevBuf<double> fz_beta;            // also the chip-resident loop's; iters + 1 doubles, grown on demand
+};
+
+struct fos_problem {
+  // the caller's: never freed here
+  const void* A = nullptr;
+  const float* b = nullptr;
+  float* gbuf = nullptr;             // n + 4 floats: ws.gbuf_own, or the caller's after fos_problem_set_gbuf
+  unsigned long long* fz_stamps = nullptr;   // fos_problem_set_fused_stamps, [ncu][8]
+  fos_comm* comm = nullptr;          // row-sharded problem: sums of partial results go through it (comm.hpp)
+  int64_t m = 0, n = 0, lda = 0;
+  int dtype = FOS_F32;
+  hipStream_t stream = nullptr;
+  int ncu = 256;
+  // inputs of the plan groups besides the shape (set by the entry point named; see fosapi::invalidate)
+  bool col_sharded = false;          // comm splits the COLUMNS instead: this rank holds A[:, its columns], x is partitioned
+  unsigned plan_flags = 0;           // FOS_PLAN_* given to fos_problem_replan
+  bool allow_resident = true;
+  bool il = false;                   // rows dealt round-robin to the workgroups (FOS_PLAN_INTERLEAVE / planner default for big rows)
+  int dd_nwg_hint = 0;               // fos_problem_tune_dd: workgroups of the streaming fp64 pass (0 = planner)
+  int cp_mode = 0;                   // 0: planner's choice, 1: FOS_PLAN_CLUSTER, 2: FOS_PLAN_NO_CLUSTER
   int chip_mode = 0;                 // 0: planner (fos_fista_run_chip where it measured ahead), 1: FOS_PLAN_CHIP_RESIDENT, 2: never
   bool fused_on = false;             // FOS_PLAN_FUSED_MFMA: plain fos_fista_run calls take fos_fista_run_fused where served
-  unsigned* fz_bar = nullptr;
-  double* fz_part = nullptr;
-  double* fz_beta = nullptr;
-  int fz_beta_cap = 0;
+  unsigned cp_epoch = 1;             // launch epoch of the one-read cluster pass
+  // decisions and the workspace they size
+  PassPlan pass;
+  DdPlan dd;
+  MultiPlan multi;
+  DdMultiPlan dm;
+  CandPlan cand;
+  Scratch ws;
+  std::unique_ptr<LbfgsWork> lbfgs;              // fos_lbfgs_minimize workspace, allocated by the first fit
+  std::unique_ptr<LbfgsMultiWork> lbfgs_multi;   // fos_lbfgs_minimize_multi workspace
   // optional kernel timing (fos_problem_profile)
   int profiling = 0;                 // 0 off, N: bracket every N-th launch of the A pass
   int64_t prof_seq = 0;
@@ -257,22 +319,22 @@ struct fos_fista {
   bool host_valid = false;
   double h_t = 1.0, h_beta = 0.0;
   long long h_k = 0;
-  double* part2 = nullptr;           // ping-pong partials for plain runs: 2 * nupd * 4 doubles
-  float* ynext = nullptr;            // plain runs: y_{k+1} in fp32 written by the update kernel
+  DevBuf<double> part2;              // ping-pong partials for plain runs: 2 * nupd * 4 doubles
+  DevBuf<float> ynext;               // plain runs: y_{k+1} in fp32 written by the update kernel
   bool y_valid = false;
   bool pending = false;
   long long plain_count = 0;
-  double *x_cur = nullptr, *x_prev = nullptr;   // fp64 iterate state
-  float* dlt = nullptr;                         // trial difference vector x_tmp - y_k (fp32)
-  fos::FistaScalars* scal = nullptr;
+  DevBuf<double> x_cur, x_prev;      // fp64 iterate state
+  DevBuf<float> dlt;                 // trial difference vector x_tmp - y_k (fp32)
+  DevBuf<fos::FistaScalars> scal;
   // precise mode (fos_fista_set_precise): the split-form gradient comes from the fp64-accumulating pass at the unrounded
   // fp64 y_k, so that the Armijo comparison g(x_tmp) <= g(y) + C grad.dlt is decided on fp64-accurate terms
   bool precise = false;
-  double* folded = nullptr;          // column-sharded: the 4 update sums of an iteration, folded and summed over the ranks
+  DevBuf<double> folded;             // column-sharded: the 4 update sums of an iteration, folded and summed over the ranks
   bool tau_on_device = false;        // FistaScalars::tau is authoritative (device-driven backtracking ran since the last set_tau / reset)
-  double* gbuf64 = nullptr;          // n + 4 doubles: [gradient ; ||r||^2]
-  bool gbuf64_owned = false;         // allocated by fos_fista_set_precise (false: the caller's, fos_fista_set_gbuf64)
-  double* out5 = nullptr;            // device
+  double* gbuf64 = nullptr;          // n + 4 doubles: [gradient ; ||r||^2] - gbuf64_own, or the caller's (fos_fista_set_gbuf64)
+  DevBuf<double> gbuf64_own;         // allocated by fos_fista_set_precise when the caller gave none
+  DevBuf<double> out5;
   int nupd = 0;                      // workgroups of the update kernel
 };
 
@@ -286,10 +348,19 @@ int epc_of(int dtype);
 int grid_1d(int64_t n, int per_block, int cap);
 void plan_fused(fos_problem* p, const MenuEntry* e, int nwg_hint);
 void apply_plan(fos_problem* p, unsigned flags);
+// An input of the plan changed: reset every group derived from it (the groups and their inputs: fos_problem above).  Each
+// group is rebuilt by its planner function on the next use.
+enum PlanInput : unsigned {
+  IN_PLAN = 1,       // plan flags, column sharding: the fp32 pass is planned anew
+  IN_TUNE = 2,       // fos_problem_tune: the fp32 pass's geometry or grid
+  IN_TUNE_DD = 4,    // fos_problem_tune_dd
+  IN_COMM = 8,       // a communicator attached or detached
+  IN_CLUSTER = 16,   // the runtime refused the one-read cluster launch: cp_mode is now "never"
+};
+int invalidate(fos_problem* p, unsigned changed);
 // Layout of the matrix-core lockstep (run_multi_mfma), planned on first use: the one-read cluster form or two products per row
-// panel; fills cp_*, panel_rows, gram_* and allocates their buffers.  no_cluster: the cluster launch was refused - two
-// products from now on.
-int plan_multi_mfma(fos_problem* p, bool no_cluster = false);
+// panel; fills the MultiPlan group.
+int plan_multi_mfma(fos_problem* p);
 int ensure_workspace(fos_problem* p);
 int ensure_batch_workspace(fos_problem* p);
 int ensure_dd(fos_problem* p);
@@ -301,7 +372,10 @@ MultiLaunch find_multi(int64_t n, int nv, bool bblock = false);
 // several right-hand sides: the caller's B (m x nv, leading dimension ldb) -> p->b16, zero beyond column nv
 int stage_b16(fos_problem* p, const float* B, int64_t ldb, int nv);
 // Enqueue the A pass for `ys`.  with_g: also produce the slabs (A^T r).  *n_rr: number of rr partials written.
-int launch_pass(fos_problem* p, const YSource& ys, const float* b, bool with_g, int* n_rr, bool dual = false);
+// rr_to (single-pass streaming plans only; the caller checks): the caller's nwg doubles that take the partials of ||A y - b||^2
+// - of ||A x_k - b||^2 for a DUAL pass - instead of the handle's own.
+int launch_pass(fos_problem* p, const YSource& ys, const float* b, bool with_g, int* n_rr, bool dual = false,
+                double* rr_to = nullptr);
 // slabs -> gbuf[0..n], summed over the ranks when the problem is row-sharded; rr_out (nullable) = the global ||r||^2
 int launch_slab_reduce(fos_problem* p, int n_rr, float* gbuf, double* rr_out, const int* stopped);
 // Product 1 on `rows` rows starting at A / b: q_part[wg][16] partial squared norms, rout (nullable): the residuals

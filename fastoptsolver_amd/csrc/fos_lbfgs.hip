@@ -135,18 +135,14 @@ int fos_lbfgs_minimize(fos_problem* p, double alpha2, int max_iter, double pgtol
   const size_t nb = (size_t)n * sizeof(double);
   hipStream_t st = p->stream;
   if (p->lbfgs == nullptr || p->lbfgs->n != n) {
-    delete p->lbfgs;
-    p->lbfgs = new LbfgsWork();
+    p->lbfgs.reset(new LbfgsWork());
     LbfgsWork& nw = *p->lbfgs;
-    HIP_TRY(hipMalloc(&nw.g, nb + 8 * sizeof(double)));
-    HIP_TRY(hipMalloc(&nw.g_old, nb + 8 * sizeof(double)));
-    HIP_TRY(hipMalloc(&nw.d, nb));
-    HIP_TRY(hipMalloc(&nw.x_old, nb));
-    HIP_TRY(hipMalloc(&nw.S, nb * M));
-    HIP_TRY(hipMalloc(&nw.Y, nb * M));
-    HIP_TRY(hipMalloc(&nw.vl, (size_t)fos_lbfgs_direction_work(n) * sizeof(double)));
-    HIP_TRY(hipHostMalloc(&nw.host, 16 * sizeof(double)));
-    HIP_TRY(hipMalloc(&nw.t_start, sizeof(unsigned long long)));
+    const size_t un = (size_t)n;
+    int rc;
+    if ((rc = nw.g.reserve(un + 8)) || (rc = nw.g_old.reserve(un + 8)) || (rc = nw.d.reserve(un)) || (rc = nw.x_old.reserve(un)) ||
+        (rc = nw.S.reserve(un * M)) || (rc = nw.Y.reserve(un * M)) || (rc = nw.vl.reserve(fos_lbfgs_direction_work(n))) ||
+        (rc = nw.host.reserve(16)) || (rc = nw.t_start.reserve(1)))
+      return rc;
     int dev = 0, khz = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && khz > 0) nw.ticks_per_ms = (double)khz;
@@ -193,11 +189,11 @@ int fos_lbfgs_minimize(fos_problem* p, double alpha2, int max_iter, double pgtol
       hipLaunchKernelGGL(fos::stamp_kernel, dim3(1), dim3(1), 0, st, w.t_start);
       LAUNCH_CHECK();
     }
-    int rc = gemv_pair_dd_stamped(p, xv, alpha2, gv, (timed && w.pass_stamps) ? w.t_start : nullptr, nullptr);
+    int rc = gemv_pair_dd_stamped(p, xv, alpha2, gv, (timed && w.pass_stamps) ? w.t_start.get() : nullptr, nullptr);
     if (rc) return rc;
     seq += 1;
     hipLaunchKernelGGL((fos::vec_stats_kernel<double, double>), dim3(1), dim3(fos::LB_THREADS), 0, st, xv, (const double*)gv,
-                       dv, n, host_dev, (const double*)(gv + n), flag_dev, seq, timed ? w.t_start : nullptr);
+                       dv, n, host_dev, (const double*)(gv + n), flag_dev, seq, timed ? w.t_start.get() : nullptr);
     LAUNCH_CHECK();
     return FOS_OK;
   };
@@ -341,20 +337,16 @@ int fos_lbfgs_minimize_multi(fos_problem* p, int nv, const float* B, int64_t ldb
   const int64_t vlw = fos_lbfgs_direction_work(n);
   hipStream_t st = p->stream;
   if (p->lbfgs_multi == nullptr || p->lbfgs_multi->n != n) {
-    delete p->lbfgs_multi;
-    p->lbfgs_multi = new LbfgsMultiWork();
+    p->lbfgs_multi.reset(new LbfgsMultiWork());
     LbfgsMultiWork& nw = *p->lbfgs_multi;
-    HIP_TRY(hipMalloc(&nw.g, 2 * NV * nb));
-    HIP_TRY(hipMalloc(&nw.d, NV * nb));
-    HIP_TRY(hipMalloc(&nw.x_old, NV * nb));
-    HIP_TRY(hipMalloc(&nw.S, (size_t)NV * M * nb));
-    HIP_TRY(hipMalloc(&nw.Y, (size_t)NV * M * nb));
-    HIP_TRY(hipMalloc(&nw.vl, (size_t)NV * vlw * sizeof(double)));
-    HIP_TRY(hipMalloc(&nw.rr, NV * sizeof(double)));
-    HIP_TRY(hipMalloc(&nw.count, sizeof(unsigned)));
+    const size_t un = (size_t)n;
+    int rc;
+    if ((rc = nw.g.reserve(2 * NV * un)) || (rc = nw.d.reserve(NV * un)) || (rc = nw.x_old.reserve(NV * un)) ||
+        (rc = nw.S.reserve(NV * M * un)) || (rc = nw.Y.reserve(NV * M * un)) || (rc = nw.vl.reserve((size_t)NV * vlw)) ||
+        (rc = nw.rr.reserve(NV)) || (rc = nw.count.reserve(1)) || (rc = nw.host.reserve(NV * SLOTS + 8)) ||
+        (rc = nw.t_start.reserve(1)))
+      return rc;
     HIP_TRY(hipMemsetAsync(nw.count, 0, sizeof(unsigned), st));
-    HIP_TRY(hipHostMalloc(&nw.host, (NV * SLOTS + 8) * sizeof(double)));
-    HIP_TRY(hipMalloc(&nw.t_start, sizeof(unsigned long long)));
     int dev = 0, khz = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && khz > 0) nw.ticks_per_ms = (double)khz;
@@ -412,7 +404,7 @@ int fos_lbfgs_minimize_multi(fos_problem* p, int nv, const float* B, int64_t ldb
       hipLaunchKernelGGL(fos::stamp_kernel, dim3(1), dim3(1), 0, st, w.t_start);
       LAUNCH_CHECK();
     }
-    int rc2 = pair_dd_multi(p, pc, k, live, alpha2, p->b16);
+    int rc2 = pair_dd_multi(p, pc, k, live, alpha2, p->ws.b16);
     if (rc2) return rc2;
     seq += 1;
     hipLaunchKernelGGL(fos::vec_stats_multi_kernel, dim3(1, k), dim3(fos::LB_THREADS), 0, st, sc, n, w.count, flag_dev, seq,

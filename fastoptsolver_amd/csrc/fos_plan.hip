@@ -278,8 +278,8 @@ int grid_1d(int64_t n, int per_block, int cap) {
 
 
 void plan_fused(fos_problem* p, const MenuEntry* e, int nwg_hint) {
-  p->entry = e;
-  p->path = 0;
+  p->pass.entry = e;
+  p->pass.path = 0;
   int64_t m = p->m;
   // Workgroups per CU (profiles/r02_sweep_wgs.log): one for the wide geometries, whose register tiles already hold
   // 64-96 KiB of rows in flight per CU; two for the 256-thread geometries with 1-2 chunks per thread (1048576 x 1024:
@@ -304,18 +304,18 @@ void plan_fused(fos_problem* p, const MenuEntry* e, int nwg_hint) {
   const int64_t row_bytes = p->n * (p->dtype == FOS_F32 ? 4 : 2);
   const int64_t min_rows = std::max<int64_t>(2 * (int64_t)e->r, (32768 + row_bytes - 1) / row_bytes);
   if (m < (int64_t)nwg * min_rows) nwg = (int)std::max<int64_t>(1, m / min_rows);
-  p->rows_per_wg = (m + nwg - 1) / nwg;
-  p->nwg = (int)((m + p->rows_per_wg - 1) / p->rows_per_wg);
-  p->nslabs = p->nwg;
+  p->pass.rows_per_wg = (m + nwg - 1) / nwg;
+  p->pass.nwg = (int)((m + p->pass.rows_per_wg - 1) / p->pass.rows_per_wg);
+  p->pass.nslabs = p->pass.nwg;
 }
 
 // Row-per-thread pass: every thread gets at least 4 rows when m allows, at most 4 workgroups per CU.
 void plan_tall(fos_problem* p, const MenuEntry* e) {
-  p->entry = e;
-  p->path = 0;
-  p->tall = true;
-  p->slab_stride = fos::tall_slab_stride((int)p->n);
-  p->vec4 = true;                    // padded slab rows: the float4 epilogues serve ragged n as well
+  p->pass.entry = e;
+  p->pass.path = 0;
+  p->pass.tall = true;
+  p->pass.slab_stride = fos::tall_slab_stride((int)p->n);
+  p->pass.vec4 = true;                    // padded slab rows: the float4 epilogues serve ragged n as well
   // 4 workgroups per CU for the row-per-thread forms (profiles/r02_sweep_wgs.log)
   // (round 3, whole-step sweep tools/wg_sweep.py: the chunk-per-lane form wants 2 workgroups per CU when its rows fill the
   //  lanes - 2000000 x 64: 102.7 -> 89.6 us, 4000000 x 32: 93.3 -> 89.5 us - and 4 when a fifth or more of them idle -
@@ -329,31 +329,31 @@ void plan_tall(fos_problem* p, const MenuEntry* e) {
   // 10.9 us per iteration, 10000 x 100: 14.6 -> 11.6 us, 30000 x 100: 16.8 -> 13.1 us; profiles/r03_wg_sweep.txt)
   const int64_t by_rows = std::max<int64_t>(p->m / rows_min, std::min<int64_t>(p->ncu, p->m / 64));
   int64_t nwg = std::max<int64_t>(1, std::min<int64_t>(per_cu * (int64_t)p->ncu, by_rows));
-  p->rows_per_wg = ((p->m + nwg - 1) / nwg + 3) / 4 * 4;     // a multiple of 4 rows: 16-byte aligned block starts (staged copy)
-  p->nwg = (int)((p->m + p->rows_per_wg - 1) / p->rows_per_wg);
-  p->nslabs = p->nwg;
+  p->pass.rows_per_wg = ((p->m + nwg - 1) / nwg + 3) / 4 * 4;     // a multiple of 4 rows: 16-byte aligned block starts (staged copy)
+  p->pass.nwg = (int)((p->m + p->pass.rows_per_wg - 1) / p->pass.rows_per_wg);
+  p->pass.nslabs = p->pass.nwg;
 }
 
 void plan_fallback(fos_problem* p) {
-  p->entry = nullptr;
-  p->path = 1;
+  p->pass.entry = nullptr;
+  p->pass.path = 1;
   int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(64, p->m / 64));
-  p->rows_per_wg = (p->m + chunks - 1) / chunks;
-  p->nslabs = (int)((p->m + p->rows_per_wg - 1) / p->rows_per_wg);
-  p->nwg = p->nslabs;
-  p->resid_grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (p->m + 3) / 4));
+  p->pass.rows_per_wg = (p->m + chunks - 1) / chunks;
+  p->pass.nslabs = (int)((p->m + p->pass.rows_per_wg - 1) / p->pass.rows_per_wg);
+  p->pass.nwg = p->pass.nslabs;
+  p->pass.resid_grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (p->m + 3) / 4));
 }
 
 int ensure_workspace(fos_problem* p) {
-  int rc = grow(&p->slab_cap, p->nslabs, (size_t)(p->slab_stride ? p->slab_stride : p->n) * sizeof(float), &p->slabs);
+  PassPlan& w = p->pass;
+  int rc = w.slabs.reserve((size_t)w.nslabs * (w.slab_stride ? w.slab_stride : p->n));
   if (rc) return rc;
-  const int need_rr = std::max(std::max(p->nwg, p->colblock ? 256 : 1), std::max(p->resid_grid, 1));
-  if ((rc = grow(&p->rr_cap, need_rr, sizeof(double), &p->rr_part, &p->rr2_part))) return rc;
-  if (p->path == 1 && p->rvec == nullptr) HIP_TRY(hipMalloc(&p->rvec, (size_t)p->m * sizeof(double)));
-  if (p->colblock && p->rneg == nullptr) {
-    HIP_TRY(hipMalloc(&p->rneg, (size_t)p->m * sizeof(float)));
-    HIP_TRY(hipMalloc(&p->zeros, (size_t)p->cb_width * sizeof(float)));
-    HIP_TRY(hipMemset(p->zeros, 0, (size_t)p->cb_width * sizeof(float)));
+  const int need_rr = std::max(std::max(w.nwg, w.colblock ? 256 : 1), std::max(w.resid_grid, 1));
+  if ((rc = w.rr_part.reserve(need_rr)) || (rc = w.rr2_part.reserve(need_rr))) return rc;
+  if (w.path == 1 && (rc = w.rvec.reserve(p->m))) return rc;
+  if (w.colblock && !w.zeros) {
+    if ((rc = w.rneg.reserve(p->m)) || (rc = w.zeros.reserve(w.cb_width))) return rc;
+    HIP_TRY(hipMemset(w.zeros, 0, (size_t)w.cb_width * sizeof(float)));
   }
   return FOS_OK;
 }
@@ -396,11 +396,11 @@ int prof_mark(fos_problem* p, bool start) {
 }
 
 // Enqueue the A pass for `ys`.  with_g: also produce the slabs (A^T r).  Returns number of rr partials.
-int launch_pass_inner(fos_problem* p, const YSource& ys, const float* b, bool with_g, int* n_rr, bool dual);
-int launch_pass(fos_problem* p, const YSource& ys, const float* b, bool with_g, int* n_rr, bool dual) {
+int launch_pass_inner(fos_problem* p, const YSource& ys, const float* b, bool with_g, int* n_rr, bool dual, double* rr_to);
+int launch_pass(fos_problem* p, const YSource& ys, const float* b, bool with_g, int* n_rr, bool dual, double* rr_to) {
   int rc = prof_mark(p, true);
   if (rc) return rc;
-  if ((rc = launch_pass_inner(p, ys, b, with_g, n_rr, dual))) return rc;
+  if ((rc = launch_pass_inner(p, ys, b, with_g, n_rr, dual, rr_to))) return rc;
   return prof_mark(p, false);
 }
 
@@ -424,11 +424,37 @@ __global__ __launch_bounds__(256) void unsum_if_stopped_kernel(float* __restrict
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) v[i] *= scale;
 }
 
+// The two-pass form (ragged / misaligned layouts, column-sharded fp64 pass), for the fp32 pass and the fp64 pass alike.
+// Pass 1: r = A y - b into pass.rvec (fp64) and `grid` partials of ||r||^2 into rr.
+int launch_residual_rows(fos_problem* p, const YSource& ys, const float* b, int grid, double* rr) {
+  if (p->dtype == FOS_F32)
+    hipLaunchKernelGGL(fos::residual_rows_kernel<float>, dim3(grid), dim3(256), 0, p->stream, (const float*)p->A, p->lda, b,
+                       p->m, (int)p->n, ys, p->pass.rvec, rr);
+  else
+    hipLaunchKernelGGL(fos::residual_rows_kernel<fos::bf16_t>, dim3(grid), dim3(256), 0, p->stream, (const fos::bf16_t*)p->A,
+                       p->lda, b, p->m, (int)p->n, ys, p->pass.rvec, rr);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+// Pass 2: slab c = A[rows of chunk c]^T r, `chunks` chunks of rows_per_chunk rows, float or double slabs.
+template <typename ACC>
+int launch_transpose_rows(fos_problem* p, const int* stopped, int chunks, int64_t rows_per_chunk, ACC* slabs) {
+  const dim3 grid((unsigned)((p->n + 255) / 256), (unsigned)chunks);
+  if (p->dtype == FOS_F32)
+    hipLaunchKernelGGL((fos::transpose_rows_kernel<float, ACC>), grid, dim3(256), 0, p->stream, (const float*)p->A, p->lda, p->m,
+                       (int)p->n, p->pass.rvec, stopped, rows_per_chunk, slabs);
+  else
+    hipLaunchKernelGGL((fos::transpose_rows_kernel<fos::bf16_t, ACC>), grid, dim3(256), 0, p->stream, (const fos::bf16_t*)p->A,
+                       p->lda, p->m, (int)p->n, p->pass.rvec, stopped, rows_per_chunk, slabs);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
 // Column blocks (rows wider than any single-pass kernel): phase 1 accumulates the negated residual block by block with the
 // residual-only form of the streaming kernel, phase 2 is the SAME with-gradient kernel per block with y = 0 and b = -r
 // (its row "dot" is then exactly r_i), writing its columns of full-width slabs.  A is read twice, at streaming speed.
 int launch_pass_colblock(fos_problem* p, const YSource& ys, const float* b, bool with_g, int* n_rr) {
-  const int64_t W = p->cb_width, esz = p->dtype == FOS_F32 ? 4 : 2;
+  const int64_t W = p->pass.cb_width, esz = p->dtype == FOS_F32 ? 4 : 2;
   const int nblk = (int)((p->n + W - 1) / W);
   const char* Ab = reinterpret_cast<const char*>(p->A);
   for (int cb = 0; cb < nblk; ++cb) {
@@ -438,25 +464,25 @@ int launch_pass_colblock(fos_problem* p, const YSource& ys, const float* b, bool
     if (ys.y) yb.y = ys.y + c0;
     if (ys.x_cur) { yb.x_cur = ys.x_cur + c0; yb.x_prev = ys.x_prev + c0; }
     if (ys.yd) yb.yd = ys.yd + c0;
-    yb.res_out = p->rneg;
+    yb.res_out = p->pass.rneg;
     yb.res_accum = cb > 0;
     // column-sharded: b enters the sum over the ranks once (rank 0)
     const float* b_here = (cb == 0 && !(p->col_sharded && p->comm->rank != 0)) ? b : nullptr;
-    p->entry->resid_only_cb(Ab + c0 * esz, p->lda, b_here, p->m, nb, yb, p->rows_per_wg, p->slabs, p->rr2_part,
-                            p->rr2_part, p->nwg, p->stream);
+    p->pass.entry->resid_only_cb(Ab + c0 * esz, p->lda, b_here, p->m, nb, yb, p->pass.rows_per_wg, p->pass.slabs, p->pass.rr2_part,
+                            p->pass.rr2_part, p->pass.nwg, p->stream);
     LAUNCH_CHECK();
   }
   if (p->col_sharded) {              // r = sum over the column blocks of ALL ranks: the one m-vector exchange
     if (ys.stopped != nullptr) {     // after a stop the passes above were no-ops and rneg still holds the last SUM: divide
-      hipLaunchKernelGGL(unsum_if_stopped_kernel, dim3(grid_1d(p->m, 256, 1024)), dim3(256), 0, p->stream, p->rneg, p->m,   // it back
+      hipLaunchKernelGGL(unsum_if_stopped_kernel, dim3(grid_1d(p->m, 256, 1024)), dim3(256), 0, p->stream, p->pass.rneg, p->m,   // it back
                          1.0f / (float)p->comm->nranks, ys.stopped);
       LAUNCH_CHECK();
     }
-    int rc = reduce_across(p, p->rneg, (size_t)p->m, false);
+    int rc = reduce_across(p, p->pass.rneg, (size_t)p->m, false);
     if (rc) return rc;
   }
   if (!with_g) {
-    hipLaunchKernelGGL(sumsq_partials_kernel, dim3(256), dim3(256), 0, p->stream, p->rneg, p->m, p->rr_part, ys.stopped);
+    hipLaunchKernelGGL(sumsq_partials_kernel, dim3(256), dim3(256), 0, p->stream, p->pass.rneg, p->m, p->pass.rr_part, ys.stopped);
     LAUNCH_CHECK();
     *n_rr = 256;
     return FOS_OK;
@@ -464,51 +490,35 @@ int launch_pass_colblock(fos_problem* p, const YSource& ys, const float* b, bool
   for (int cb = 0; cb < nblk; ++cb) {
     const int64_t c0 = cb * W;
     const int nb = (int)std::min<int64_t>(W, p->n - c0);
-    YSource yz{p->zeros, nullptr, nullptr, nullptr, ys.stopped};
+    YSource yz{p->pass.zeros, nullptr, nullptr, nullptr, ys.stopped};
     yz.slab_stride = p->n;
-    p->entry->with_g_cb(Ab + c0 * esz, p->lda, p->rneg, p->m, nb, yz, p->rows_per_wg, p->slabs + c0, cb == 0 ? p->rr_part : p->rr2_part,
-                        p->rr2_part, p->nwg, p->stream);
+    p->pass.entry->with_g_cb(Ab + c0 * esz, p->lda, p->pass.rneg, p->m, nb, yz, p->pass.rows_per_wg, p->pass.slabs + c0, cb == 0 ? p->pass.rr_part : p->pass.rr2_part,
+                        p->pass.rr2_part, p->pass.nwg, p->stream);
     LAUNCH_CHECK();
   }
-  *n_rr = p->nwg;
+  *n_rr = p->pass.nwg;
   return FOS_OK;
 }
 
-int launch_pass_inner(fos_problem* p, const YSource& ys, const float* b, bool with_g, int* n_rr, bool dual) {
-  if (p->path == 0 && p->colblock) return launch_pass_colblock(p, ys, b, with_g, n_rr);
-  if (p->path == 0) {
-    FusedLaunch fn = dual ? p->entry->dual : (with_g ? p->entry->with_g : p->entry->resid_only);
+int launch_pass_inner(fos_problem* p, const YSource& ys, const float* b, bool with_g, int* n_rr, bool dual, double* rr_to) {
+  if (p->pass.path == 0 && p->pass.colblock) return launch_pass_colblock(p, ys, b, with_g, n_rr);
+  if (p->pass.path == 0) {
+    FusedLaunch fn = dual ? p->pass.entry->dual : (with_g ? p->pass.entry->with_g : p->pass.entry->resid_only);
     if (p->il) {
-      FusedLaunch fi = dual ? p->entry->dual_il : (with_g ? p->entry->with_g_il : p->entry->resid_only_il);
+      FusedLaunch fi = dual ? p->pass.entry->dual_il : (with_g ? p->pass.entry->with_g_il : p->pass.entry->resid_only_il);
       if (fi) fn = fi;
     }
-    fn(p->A, p->lda, b, p->m, (int)p->n, ys, p->rows_per_wg, p->slabs, p->rr_part, p->rr2_part, p->nwg, p->stream);
+    fn(p->A, p->lda, b, p->m, (int)p->n, ys, p->pass.rows_per_wg, p->pass.slabs, rr_to && !dual ? rr_to : p->pass.rr_part.get(),
+       rr_to && dual ? rr_to : p->pass.rr2_part.get(), p->pass.nwg, p->stream);
     LAUNCH_CHECK();
-    *n_rr = p->nwg;
+    *n_rr = p->pass.nwg;
     return FOS_OK;
   }
-  if (p->dtype == FOS_F32)
-    hipLaunchKernelGGL(fos::residual_rows_kernel<float>, dim3(p->resid_grid), dim3(256), 0, p->stream,
-                       (const float*)p->A, p->lda, b, p->m, (int)p->n, ys, p->rvec, p->rr_part);
-  else
-    hipLaunchKernelGGL(fos::residual_rows_kernel<fos::bf16_t>, dim3(p->resid_grid), dim3(256), 0, p->stream,
-                       (const fos::bf16_t*)p->A, p->lda, b, p->m, (int)p->n, ys, p->rvec, p->rr_part);
-  LAUNCH_CHECK();
-  *n_rr = p->resid_grid;
-  if (with_g) {
-    dim3 grid((unsigned)((p->n + 255) / 256), (unsigned)p->nslabs);
-    if (p->dtype == FOS_F32)
-      hipLaunchKernelGGL(fos::transpose_rows_kernel<float>, grid, dim3(256), 0, p->stream, (const float*)p->A, p->lda,
-                         p->m, (int)p->n, p->rvec, ys.stopped, p->rows_per_wg, p->slabs);
-    else
-      hipLaunchKernelGGL(fos::transpose_rows_kernel<fos::bf16_t>, grid, dim3(256), 0, p->stream,
-                         (const fos::bf16_t*)p->A, p->lda, p->m, (int)p->n, p->rvec, ys.stopped, p->rows_per_wg,
-                         p->slabs);
-    LAUNCH_CHECK();
-  }
-  return FOS_OK;
+  int rc = launch_residual_rows(p, ys, b, p->pass.resid_grid, p->pass.rr_part);
+  if (rc) return rc;
+  *n_rr = p->pass.resid_grid;
+  return with_g ? launch_transpose_rows<float>(p, ys.stopped, p->pass.nslabs, p->pass.rows_per_wg, p->pass.slabs.get()) : FOS_OK;
 }
-
 
 
 __global__ void rr_from_gbuf_kernel(const float* __restrict__ gbuf, int n, double* __restrict__ rr_out, const int* stopped) {
@@ -538,12 +548,12 @@ int launch_slab_reduce(fos_problem* p, int n_rr, float* gbuf, double* rr_out, co
 
 int launch_slab_reduce_local(fos_problem* p, int n_rr, float* gbuf, double* rr_out, const int* stopped) {
   const int grid = (int)((p->n + fos::RCOLS - 1) / fos::RCOLS);
-  if (p->vec4)
-    hipLaunchKernelGGL(fos::slab_reduce_kernel<true>, dim3(grid), dim3(256), 0, p->stream, p->slabs, p->nslabs,
-                       (int)p->n, p->rr_part, n_rr, gbuf, rr_out, stopped, p->slab_stride);
+  if (p->pass.vec4)
+    hipLaunchKernelGGL(fos::slab_reduce_kernel<true>, dim3(grid), dim3(256), 0, p->stream, p->pass.slabs, p->pass.nslabs,
+                       (int)p->n, p->pass.rr_part, n_rr, gbuf, rr_out, stopped, p->pass.slab_stride);
   else
-    hipLaunchKernelGGL(fos::slab_reduce_kernel<false>, dim3(grid), dim3(256), 0, p->stream, p->slabs, p->nslabs,
-                       (int)p->n, p->rr_part, n_rr, gbuf, rr_out, stopped);
+    hipLaunchKernelGGL(fos::slab_reduce_kernel<false>, dim3(grid), dim3(256), 0, p->stream, p->pass.slabs, p->pass.nslabs,
+                       (int)p->n, p->pass.rr_part, n_rr, gbuf, rr_out, stopped);
   LAUNCH_CHECK();
   return FOS_OK;
 }
@@ -554,14 +564,16 @@ __global__ void xp_pack_kernel(const float* __restrict__ X, int n, int n_pad, in
 }
 
 int ensure_batch_workspace(fos_problem* p) {
-  if (p->xp && p->q_part && p->bt_out) return FOS_OK;     // all three or nothing: a failed attempt is retried cleanly
+  if (p->cand.planned) return FOS_OK;
   const int64_t tile_cols = p->dtype == FOS_BF16 ? fos::BQ_COLS : fos::BT_COLS;
-  p->n_pad = (p->n + tile_cols - 1) / tile_cols * tile_cols;
+  p->cand.n_pad = (p->n + tile_cols - 1) / tile_cols * tile_cols;
   // fp32: Xp, one float per (column, candidate); bf16: Xq, three bf16 terms per (column, candidate)
   const size_t per_entry = p->dtype == FOS_BF16 ? 3 * sizeof(unsigned short) : sizeof(float);
-  if (!p->xp) HIP_TRY(hipMalloc(&p->xp, (size_t)p->n_pad * fos::BT_NV * per_entry));
-  if (!p->q_part) HIP_TRY(hipMalloc(&p->q_part, (size_t)(3 * p->ncu + 8) * fos::BT_NV * sizeof(double)));
-  if (!p->bt_out) HIP_TRY(hipMalloc(&p->bt_out, 128 * sizeof(double)));
+  int rc;
+  if ((rc = p->cand.xp.reserve((size_t)p->cand.n_pad * fos::BT_NV * per_entry / sizeof(float))) ||
+      (rc = p->cand.q_part.reserve((size_t)(3 * p->ncu + 8) * fos::BT_NV)) || (rc = p->cand.bt_out.reserve(128)))
+    return rc;
+  p->cand.planned = true;
   return FOS_OK;
 }
 
@@ -608,17 +620,17 @@ int launch_batch_product(fos_problem* p, const void* A, const float* b, int64_t 
   if (is_bf16)
     hipLaunchKernelGGL(bblock ? (rout ? vq.fn_store_rhs : vq.fn_rhs) : (rout ? vq.fn_store : vq.fn), dim3((unsigned)nwg),
                        dim3(fos::BT_THREADS), 0, p->stream, (const fos::bf16_t*)A, p->lda, b, (use_b && b) ? 1 : 0,
-                       rows_total, (int)p->n, (const unsigned short*)p->xp, gpw, p->q_part, rout, stopped);
+                       rows_total, (int)p->n, (const unsigned short*)p->cand.xp.get(), gpw, p->cand.q_part, rout, stopped);
   else
     hipLaunchKernelGGL(bblock ? (rout ? vf.fn_store_rhs : vf.fn_rhs) : (rout ? vf.fn_store : vf.fn), dim3((unsigned)nwg),
                        dim3(fos::BT_THREADS), 0, p->stream, (const float*)A, p->lda, b, (use_b && b) ? 1 : 0, rows_total,
-                       (int)p->n, p->xp, gpw, p->q_part, rout, stopped);
+                       (int)p->n, p->cand.xp, gpw, p->cand.q_part, rout, stopped);
   LAUNCH_CHECK();
   *nwg_out = (int)nwg;
   return FOS_OK;
 }
 
-// q[j] = ||A Xp_j - use_b*b||^2 -> out16 (device); Xp already in p->xp.
+// q[j] = ||A Xp_j - use_b*b||^2 -> out16 (device); Xp already in p->cand.xp.
 // q[j] = sum_i R[i][j]^2 of an m x 16 residual block (column-sharded candidate pass, after the sum over the ranks)
 __global__ __launch_bounds__(256) void colnorms16_partials_kernel(const float* __restrict__ R, int64_t m, double* __restrict__ part,
                                                                  const int* stopped) {
@@ -650,26 +662,26 @@ int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* s
   if (p->col_sharded) {
     // Column-sharded: ||A dlt_j||^2 = ||sum_p A_p dlt_{j,p}||^2.  Every rank's product 1 keeps its partial residuals
     // (m x 16 floats), ONE all-reduce sums the blocks of all 16 candidates (4 MiB at m = 65536), the column norms follow.
-    if (!p->rcols16) HIP_TRY(hipMalloc(&p->rcols16, (size_t)p->m * fos::BT_NV * sizeof(float)));
+    if ((rc = p->ws.rcols16.reserve((size_t)p->m * fos::BT_NV))) return rc;
     const float* b_here = p->comm->rank == 0 ? p->b : nullptr;
-    if ((rc = launch_batch_product(p, p->A, b_here, p->m, use_b, p->rcols16, &nwg, stopped))) return rc;
+    if ((rc = launch_batch_product(p, p->A, b_here, p->m, use_b, p->ws.rcols16, &nwg, stopped))) return rc;
     if ((rc = prof_mark(p, false))) return rc;
     if (stopped != nullptr) {        // a no-op product leaves the last SUM in place: divide it back before the in-place all-reduce
       hipLaunchKernelGGL(unsum16_if_stopped_kernel, dim3(grid_1d(p->m * fos::BT_NV, 256, 1024)), dim3(256), 0, p->stream,
-                         p->rcols16, p->m * fos::BT_NV, 1.0f / (float)p->comm->nranks, stopped);
+                         p->ws.rcols16, p->m * fos::BT_NV, 1.0f / (float)p->comm->nranks, stopped);
       LAUNCH_CHECK();
     }
-    if ((rc = reduce_across(p, p->rcols16, (size_t)p->m * fos::BT_NV, false))) return rc;
+    if ((rc = reduce_across(p, p->ws.rcols16, (size_t)p->m * fos::BT_NV, false))) return rc;
     const int g = grid_1d(p->m, 16 * 16, 3 * p->ncu);
-    hipLaunchKernelGGL(colnorms16_partials_kernel, dim3(g), dim3(256), 0, p->stream, p->rcols16, p->m, p->q_part, stopped);
+    hipLaunchKernelGGL(colnorms16_partials_kernel, dim3(g), dim3(256), 0, p->stream, p->ws.rcols16, p->m, p->cand.q_part, stopped);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->q_part, g, fos::BT_NV, out16);
+    hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->cand.q_part, g, fos::BT_NV, out16);
     LAUNCH_CHECK();
     return FOS_OK;
   }
   if ((rc = launch_batch_product(p, p->A, b16 ? b16 : p->b, p->m, use_b, nullptr, &nwg, stopped, b16 != nullptr))) return rc;
   if ((rc = prof_mark(p, false))) return rc;
-  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->q_part, (int)nwg, fos::BT_NV, out16);
+  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->cand.q_part, (int)nwg, fos::BT_NV, out16);
   LAUNCH_CHECK();
   return reduce_across(p, out16, fos::BT_NV, true);      // sharded: ||A dlt_j||^2 = sum over the row blocks
 }
@@ -697,22 +709,22 @@ MultiLaunch find_multi(int64_t n, int nv, bool bblock) {
 }
 
 int stage_b16(fos_problem* p, const float* B, int64_t ldb, int nv) {
-  if (!p->b16) HIP_TRY(hipMalloc(&p->b16, (size_t)p->m * fos::BT_NV * sizeof(float)));
+  if (int rc = p->ws.b16.reserve((size_t)p->m * fos::BT_NV)) return rc;
   hipLaunchKernelGGL(fos::stage_b16_kernel, dim3(grid_1d(p->m * fos::BT_NV, 256, 4 * p->ncu)), dim3(256), 0, p->stream, B,
-                     ldb, nv, p->m, p->b16);
+                     ldb, nv, p->m, p->ws.b16);
   LAUNCH_CHECK();
   return FOS_OK;
 }
 
 // The matrix-core passes (16 candidates / 16 weights) need the aligned layout only - not a streaming plan: rows of 65..128
-// columns run the chunk-per-lane pass (p->tall) and keep them; n <= 64 may be ragged / misaligned and does not.
-bool batch_supported(const fos_problem* p) { return p->path == 0 && (!p->tall || p->n > fos::TL_MAX_N); }   // fp32: f32 MFMA; bf16: 3-term bf16 MFMA
+// columns run the chunk-per-lane pass (p->pass.tall) and keep them; n <= 64 may be ragged / misaligned and does not.
+bool batch_supported(const fos_problem* p) { return p->pass.path == 0 && (!p->pass.tall || p->n > fos::TL_MAX_N); }   // fp32: f32 MFMA; bf16: 3-term bf16 MFMA
 
 // ---- fp64 multi-point pass on the matrix cores (gram_batch_dd.hpp) ---------------------------------------------------
 // The shapes of the fp32 matrix-core pair (run_multi_mfma): the aligned layout, fp32 and bf16, up to 16384 columns, any
 // number of row panels; not the two-pass / LDS-resident / n <= 64 plans, column blocks, the y-in-LDS rows or sharding.
 bool pair_dd_multi_supported(const fos_problem* p) {
-  return batch_supported(p) && !p->colblock && !p->resident && !p->col_sharded && !p->comm && p->entry != wide_entry(p->dtype) &&
+  return batch_supported(p) && !p->pass.colblock && !p->pass.resident && !p->col_sharded && !p->comm && p->pass.entry != wide_entry(p->dtype) &&
          p->n <= 16384;
 }
 
@@ -720,21 +732,22 @@ bool pair_dd_multi_supported(const fos_problem* p) {
 // workgroup groups of 64 rows, at most two workgroups per CU (51 KiB of LDS each for fp32).
 constexpr int DM_P1_PER_CU = 2;
 int ensure_dd_multi(fos_problem* p) {
-  if (p->xd && p->rdd && p->slabs_dd16 && p->qdd_part) return FOS_OK;
+  if (p->dm.planned) return FOS_OK;
   const int64_t n = p->n;
-  p->dm_n_pad = (n + fos::DM_COLS - 1) / fos::DM_COLS * fos::DM_COLS;
-  p->dm_panel_rows = std::min<int64_t>(256 * (int64_t)p->ncu, (p->m + 255) / 256 * 256);
+  p->dm.n_pad = (n + fos::DM_COLS - 1) / fos::DM_COLS * fos::DM_COLS;
+  p->dm.panel_rows = std::min<int64_t>(256 * (int64_t)p->ncu, (p->m + 255) / 256 * 256);
   const int64_t strips = (n + fos::DM_COLS - 1) / fos::DM_COLS;
   int64_t splits = std::max<int64_t>(1, (2 * (int64_t)p->ncu + strips - 1) / strips);
-  splits = std::min<int64_t>(splits, std::max<int64_t>(1, p->dm_panel_rows / 256));
-  p->dm_rows_per_split = ((p->dm_panel_rows + splits - 1) / splits + fos::DM_ROWS - 1) / fos::DM_ROWS * fos::DM_ROWS;
-  p->dm_splits = (int)((p->dm_panel_rows + p->dm_rows_per_split - 1) / p->dm_rows_per_split);
-  const int64_t panels = (p->m + p->dm_panel_rows - 1) / p->dm_panel_rows;
-  if (!p->xd) HIP_TRY(hipMalloc(&p->xd, (size_t)p->dm_n_pad * fos::BT_NV * sizeof(double)));
-  if (!p->rdd) HIP_TRY(hipMalloc(&p->rdd, (size_t)p->dm_panel_rows * fos::BT_NV * sizeof(double)));
-  if (!p->slabs_dd16) HIP_TRY(hipMalloc(&p->slabs_dd16, (size_t)p->dm_splits * fos::BT_NV * n * sizeof(double)));
-  if (!p->qdd_part)
-    HIP_TRY(hipMalloc(&p->qdd_part, (size_t)panels * DM_P1_PER_CU * p->ncu * fos::BT_NV * sizeof(double)));
+  splits = std::min<int64_t>(splits, std::max<int64_t>(1, p->dm.panel_rows / 256));
+  p->dm.rows_per_split = ((p->dm.panel_rows + splits - 1) / splits + fos::DM_ROWS - 1) / fos::DM_ROWS * fos::DM_ROWS;
+  p->dm.splits = (int)((p->dm.panel_rows + p->dm.rows_per_split - 1) / p->dm.rows_per_split);
+  const int64_t panels = (p->m + p->dm.panel_rows - 1) / p->dm.panel_rows;
+  int rc;
+  if ((rc = p->dm.xd.reserve((size_t)p->dm.n_pad * fos::BT_NV)) || (rc = p->dm.rdd.reserve((size_t)p->dm.panel_rows * fos::BT_NV)) ||
+      (rc = p->dm.slabs.reserve((size_t)p->dm.splits * fos::BT_NV * n)) ||
+      (rc = p->dm.q_part.reserve((size_t)panels * DM_P1_PER_CU * p->ncu * fos::BT_NV)))
+    return rc;
+  p->dm.planned = true;
   return FOS_OK;
 }
 
@@ -743,14 +756,14 @@ int ensure_dd_multi(fos_problem* p) {
 template <typename T>
 int run_pair_dd_multi(fos_problem* p, const fos::DdMultiCols& c, int ncols, unsigned live, double alpha2, const float* b16) {
   const int64_t n = p->n, esz = sizeof(T);
-  hipLaunchKernelGGL(fos::xd_pack_kernel, dim3(grid_1d(p->dm_n_pad * fos::BT_NV, 256, 4 * p->ncu)), dim3(256), 0, p->stream, c,
-                     live, (int)n, (int)p->dm_n_pad, p->xd);
+  hipLaunchKernelGGL(fos::xd_pack_kernel, dim3(grid_1d(p->dm.n_pad * fos::BT_NV, 256, 4 * p->ncu)), dim3(256), 0, p->stream, c,
+                     live, (int)n, (int)p->dm.n_pad, p->dm.xd);
   LAUNCH_CHECK();
   const int64_t strips = (n + fos::DM_COLS - 1) / fos::DM_COLS;
   int64_t nparts = 0;
   int rc;
-  for (int64_t row0 = 0, panel = 0; row0 < p->m; row0 += p->dm_panel_rows, ++panel) {
-    const int64_t rows = std::min<int64_t>(p->dm_panel_rows, p->m - row0);
+  for (int64_t row0 = 0, panel = 0; row0 < p->m; row0 += p->dm.panel_rows, ++panel) {
+    const int64_t rows = std::min<int64_t>(p->dm.panel_rows, p->m - row0);
     const T* Ap = reinterpret_cast<const T*>(reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz);
     const int64_t ngroups = (rows + fos::DM_ROWS - 1) / fos::DM_ROWS;
     int64_t nwg = std::min<int64_t>(ngroups, DM_P1_PER_CU * (int64_t)p->ncu);
@@ -758,24 +771,24 @@ int run_pair_dd_multi(fos_problem* p, const fos::DdMultiCols& c, int ncols, unsi
     nwg = (ngroups + gpw - 1) / gpw;
     if ((rc = prof_mark(p, true))) return rc;
     hipLaunchKernelGGL(fos::residual_dd_mfma_kernel<T>, dim3((unsigned)nwg), dim3(fos::DM_THREADS), 0, p->stream, Ap, p->lda,
-                       b16 + row0 * fos::BT_NV, rows, (int)n, (const double*)p->xd, gpw, p->qdd_part + nparts * fos::BT_NV,
-                       p->rdd);
+                       b16 + row0 * fos::BT_NV, rows, (int)n, (const double*)p->dm.xd, gpw, p->dm.q_part + nparts * fos::BT_NV,
+                       p->dm.rdd);
     LAUNCH_CHECK();
     if ((rc = prof_mark(p, false))) return rc;
     nparts += nwg;
-    const dim3 grid((unsigned)strips, (unsigned)p->dm_splits);
+    const dim3 grid((unsigned)strips, (unsigned)p->dm.splits);
     if ((rc = prof_mark(p, true))) return rc;
     if (panel)
       hipLaunchKernelGGL((fos::gram_dd_mfma_kernel<T, true>), grid, dim3(fos::DM_THREADS), 0, p->stream, Ap, p->lda, rows,
-                         (int)n, (const double*)p->rdd, p->dm_rows_per_split, p->slabs_dd16, n);
+                         (int)n, (const double*)p->dm.rdd, p->dm.rows_per_split, p->dm.slabs, n);
     else
       hipLaunchKernelGGL((fos::gram_dd_mfma_kernel<T, false>), grid, dim3(fos::DM_THREADS), 0, p->stream, Ap, p->lda, rows,
-                         (int)n, (const double*)p->rdd, p->dm_rows_per_split, p->slabs_dd16, n);
+                         (int)n, (const double*)p->dm.rdd, p->dm.rows_per_split, p->dm.slabs, n);
     LAUNCH_CHECK();
     if ((rc = prof_mark(p, false))) return rc;
   }
   hipLaunchKernelGGL(fos::pair_dd_multi_finish_kernel, dim3(grid_1d(n, 256, 64), ncols), dim3(256), 0, p->stream,
-                     (const double*)p->slabs_dd16, p->dm_splits, (int)n, (const double*)p->qdd_part, (int)nparts, alpha2, c);
+                     (const double*)p->dm.slabs, p->dm.splits, (int)n, (const double*)p->dm.q_part, (int)nparts, alpha2, c);
   LAUNCH_CHECK();
   return FOS_OK;
 }
@@ -806,8 +819,8 @@ int aligned_vec(fos_problem* p, const float* v, const float** out) {
     *out = v;
     return FOS_OK;
   }
-  HIP_TRY(hipMemcpyAsync(p->ybuf, v, (size_t)p->n * sizeof(float), hipMemcpyDeviceToDevice, p->stream));
-  *out = p->ybuf;
+  HIP_TRY(hipMemcpyAsync(p->ws.ybuf, v, (size_t)p->n * sizeof(float), hipMemcpyDeviceToDevice, p->stream));
+  *out = p->ws.ybuf;
   return FOS_OK;
 }
 
@@ -824,35 +837,56 @@ bool il_default(const fos_problem* p) {
   return bytes >= (12ll << 30);
 }
 
-// Choose the kernel family for this problem; `flags` (FOS_PLAN_*) switch individual families off (fos_problem_replan).
+// the streaming kernels' layout: whole 16-byte chunks per row, rows and the matrix 16-byte aligned
+bool vec_layout(const fos_problem* p) {
+  const int epc = epc_of(p->dtype);
+  return (p->n % epc == 0) && (p->lda % epc == 0) && ((reinterpret_cast<uintptr_t>(p->A) & 15u) == 0);
+}
+// the one-workgroup resident loop has no exchange step
+void plan_resident(fos_problem* p) { p->pass.resident = fos::resident_fits(p->m, p->n) && p->allow_resident && p->comm == nullptr; }
+// The two-phase column-block plan: blocks of equal width (a multiple of 64 columns, at most the widest streaming geometry).
+// Null where no streaming geometry with a column-block form covers that width.
+const MenuEntry* colblock_entry(const fos_problem* p, int64_t* width) {
+  const int64_t cap = 16384, blocks = (p->n + cap - 1) / cap;
+  *width = ((p->n + blocks - 1) / blocks + 63) / 64 * 64;
+  const MenuEntry* ce = default_entry(p->dtype, *width);
+  return ce && ce->with_g_cb && ce->resid_only_cb ? ce : nullptr;
+}
+void plan_colblock(fos_problem* p, const MenuEntry* ce, int64_t width) {
+  plan_fused(p, ce, 0);
+  p->pass.colblock = true;
+  p->pass.cb_width = width;
+}
+
+// Choose the kernel family for this problem (a fresh PassPlan); `flags` (FOS_PLAN_*) switch individual families off
+// (fos_problem_replan).
 void apply_plan(fos_problem* p, unsigned flags) {
-  const int64_t m = p->m, n = p->n;
+  const int64_t n = p->n;
   p->plan_flags = flags;
-  p->tall = false;
-  p->colblock = false;
-  p->slab_stride = 0;
-  p->vec4 = (n % 4 == 0);
+  p->pass.vec4 = (n % 4 == 0);
   p->allow_resident = !(flags & FOS_PLAN_NO_RESIDENT);
   p->il = (flags & FOS_PLAN_INTERLEAVE) ? true : (flags & FOS_PLAN_NO_INTERLEAVE) ? false : il_default(p);
-  p->resident = fos::resident_fits(m, n) && p->allow_resident && p->comm == nullptr;
-  const int epc = epc_of(p->dtype);
-  const bool vec_ok = (n % epc == 0) && (p->lda % epc == 0) && ((reinterpret_cast<uintptr_t>(p->A) & 15u) == 0);
+  plan_resident(p);
+  const bool vec_ok = vec_layout(p);
+  int64_t cb_width = 0;
   const MenuEntry* e = vec_ok ? default_entry(p->dtype, n) : nullptr;
   if ((n <= fos::TL_MAX_N || (n <= tlr_max_n(p->dtype) && vec_ok)) && !(flags & FOS_PLAN_NO_TALL))
     plan_tall(p, tall_entry(p->dtype, n, p->lda, p->A));
   else if (e) plan_fused(p, e, 0);
   else if (vec_ok && n <= fos::WD_MAX_N && !(flags & FOS_PLAN_NO_WIDE)) plan_fused(p, wide_entry(p->dtype), 0);
-  else if (vec_ok && !(flags & FOS_PLAN_NO_COLBLOCK)) {
-    // column blocks of equal width (a multiple of 64 columns, at most the widest streaming geometry)
-    const int64_t cap = 16384;
-    const int64_t blocks = (n + cap - 1) / cap;
-    p->cb_width = ((n + blocks - 1) / blocks + 63) / 64 * 64;
-    const MenuEntry* ce = default_entry(p->dtype, p->cb_width);
-    if (ce && ce->with_g_cb && ce->resid_only_cb) {
-      plan_fused(p, ce, 0);
-      p->colblock = true;
-    } else plan_fallback(p);
-  } else plan_fallback(p);
+  else if (const MenuEntry* ce = (vec_ok && !(flags & FOS_PLAN_NO_COLBLOCK)) ? colblock_entry(p, &cb_width) : nullptr)
+    plan_colblock(p, ce, cb_width);
+  else plan_fallback(p);
+}
+
+int invalidate(fos_problem* p, unsigned changed) {
+  // these two follow launches of the same call or tuning loop: the stream drains before their buffers go
+  if (changed & (IN_TUNE_DD | IN_CLUSTER)) HIP_TRY(hipStreamSynchronize(p->stream));
+  if (changed & IN_PLAN) p->pass.reset();
+  if (changed & IN_COMM) plan_resident(p);
+  if (changed & (IN_PLAN | IN_TUNE | IN_TUNE_DD | IN_COMM)) p->dd.reset();
+  if (changed & (IN_PLAN | IN_COMM | IN_CLUSTER)) p->multi.reset();
+  return FOS_OK;
 }
 
 // Up to 16 state machines in lockstep on the matrix cores (run_multi_mfma).
@@ -862,15 +896,9 @@ void apply_plan(fos_problem* p, unsigned flags) {
 // form wins where every member of a cluster has a full 1024-column strip and the matrix is large - 131072 x 4096 826 -> 640,
 // 524288 x 4096 3306 -> 2407, 65536 x 8192 670 -> 643, 262144 x 8192 2668 -> 2430 - ties at 32768 x 8192 and loses with
 // idle members (6144 columns +10 %, 3072 +5 %) and at 16 members (131072 x 16384 +5 %).
-int plan_multi_mfma(fos_problem* p, bool no_cluster) {
-  if (no_cluster) {
-    p->cp_cs = 0;
-    p->cp_mode = 2;
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    (void)hipFree(p->rbuf16); (void)hipFree(p->slabs16);       // sized for the cluster form
-    p->rbuf16 = p->slabs16 = nullptr;
-  }
-  if (p->rbuf16) return FOS_OK;
+int plan_multi_mfma(fos_problem* p) {
+  if (p->multi.planned) return FOS_OK;
+  int rc;
   const bool is_bf16 = p->dtype == FOS_BF16;
   const int cs_need = (int)((p->n + fos::CP_W - 1) / fos::CP_W);
   const bool cluster_wins = (p->n == 4096 || p->n == 8192) && p->m * p->n >= (1ll << 29) && !p->comm;
@@ -878,35 +906,37 @@ int plan_multi_mfma(fos_problem* p, bool no_cluster) {
   if (want_cluster && !is_bf16 && p->ncu % 8 == 0) {
     const int cs = cs_need <= 2 ? 0 : cs_need <= 4 ? 4 : cs_need <= 8 ? 8 : cs_need <= 16 ? 16 : 0;
     if (cs && (p->ncu / 8) % cs == 0 && p->m >= (int64_t)(p->ncu / cs) * fos::CP_ROWS * 8) {
-      p->cp_cs = cs;
-      p->cp_clusters = p->ncu / cs;
-      p->cp_rows_per_cluster = ((p->m + p->cp_clusters - 1) / p->cp_clusters + fos::CP_ROWS - 1) / fos::CP_ROWS * fos::CP_ROWS;
-      HIP_TRY(hipMalloc(&p->cp_xchg, (size_t)p->ncu * fos::CP_SLOTS * 256 * sizeof(float)));
-      HIP_TRY(hipMalloc(&p->cp_flags, (size_t)p->ncu * fos::CP_FLAG_STRIDE * sizeof(unsigned)));
-      HIP_TRY(hipMemsetAsync(p->cp_flags, 0, (size_t)p->ncu * fos::CP_FLAG_STRIDE * sizeof(unsigned), p->stream));
-      HIP_TRY(hipMalloc(&p->cp_error, sizeof(int)));
-      HIP_TRY(hipMemsetAsync(p->cp_error, 0, sizeof(int), p->stream));
+      p->multi.cp_cs = cs;
+      p->multi.cp_clusters = p->ncu / cs;
+      p->multi.cp_rows_per_cluster = ((p->m + p->multi.cp_clusters - 1) / p->multi.cp_clusters + fos::CP_ROWS - 1) / fos::CP_ROWS * fos::CP_ROWS;
+      if ((rc = p->multi.cp_xchg.reserve((size_t)p->ncu * fos::CP_SLOTS * 256)) ||
+          (rc = p->multi.cp_flags.reserve((size_t)p->ncu * fos::CP_FLAG_STRIDE)) || (rc = p->multi.cp_error.reserve(1)))
+        return rc;
+      HIP_TRY(hipMemsetAsync(p->multi.cp_flags, 0, (size_t)p->ncu * fos::CP_FLAG_STRIDE * sizeof(unsigned), p->stream));
+      HIP_TRY(hipMemsetAsync(p->multi.cp_error, 0, sizeof(int), p->stream));
     }
   }
   // Panel: product 1 gives a workgroup 64-128 whole rows, so it needs >= 128 * CUs * 2 rows to fill the chip; row splits of
   // product 2: enough (strip, split) workgroups for two per CU.  (A panel that fits the Infinity Cache - ~3000 rows at
   // n = 8192 - would need a split-K product 1; see DESIGN.md "Multi-lambda".)
   const int64_t rows = 256 * (int64_t)p->ncu;
-  p->panel_rows = std::min<int64_t>(rows, (p->m + 255) / 256 * 256);
+  p->multi.panel_rows = std::min<int64_t>(rows, (p->m + 255) / 256 * 256);
   if (p->col_sharded && p->comm->kind != 0) {          // mesh transport: a panel's 16 residual columns are one message
     const int64_t fit = (int64_t)(p->comm->cap_bytes / (fos::BT_NV * sizeof(float))) / 256 * 256;
     if (fit < 256) return fail(FOS_ERR_ARG, "fos_fista_run_multi: the communicator's inbox rows hold less than one 256-row "
                                             "panel of 16 residual columns (16 KiB)");
-    p->panel_rows = std::min<int64_t>(p->panel_rows, fit);
+    p->multi.panel_rows = std::min<int64_t>(p->multi.panel_rows, fit);
   }
   const int64_t strips = (p->n + (is_bf16 ? fos::GQ_COLS : fos::GB_COLS) - 1) / (is_bf16 ? fos::GQ_COLS : fos::GB_COLS);
   int64_t splits = std::max<int64_t>(1, (2 * (int64_t)p->ncu + strips - 1) / strips);
-  splits = std::min<int64_t>(splits, std::max<int64_t>(1, p->panel_rows / 256));
-  p->gram_rows_per_split = ((p->panel_rows + splits - 1) / splits + fos::GB_ROWS - 1) / fos::GB_ROWS * fos::GB_ROWS;
-  p->gram_splits = (int)((p->panel_rows + p->gram_rows_per_split - 1) / p->gram_rows_per_split);
-  if (p->cp_cs) p->gram_splits = p->cp_clusters;      // one slab set per cluster
-  HIP_TRY(hipMalloc(&p->rbuf16, (size_t)p->panel_rows * fos::BT_NV * sizeof(float)));
-  HIP_TRY(hipMalloc(&p->slabs16, (size_t)p->gram_splits * fos::BT_NV * p->n * sizeof(float)));
+  splits = std::min<int64_t>(splits, std::max<int64_t>(1, p->multi.panel_rows / 256));
+  p->multi.gram_rows_per_split = ((p->multi.panel_rows + splits - 1) / splits + fos::GB_ROWS - 1) / fos::GB_ROWS * fos::GB_ROWS;
+  p->multi.gram_splits = (int)((p->multi.panel_rows + p->multi.gram_rows_per_split - 1) / p->multi.gram_rows_per_split);
+  if (p->multi.cp_cs) p->multi.gram_splits = p->multi.cp_clusters;      // one slab set per cluster
+  if ((rc = p->multi.rbuf16.reserve((size_t)p->multi.panel_rows * fos::BT_NV)) ||
+      (rc = p->multi.slabs16.reserve((size_t)p->multi.gram_splits * fos::BT_NV * p->n)))
+    return rc;
+  p->multi.planned = true;
   return FOS_OK;
 }
 
@@ -915,19 +945,20 @@ int plan_multi_mfma(fos_problem* p, bool no_cluster) {
 // they are (they accumulate in fp64 anyway), streaming shapes get the ACC = double instantiation of gemv_pair_kernel,
 // everything else (ragged / misaligned layouts, rows wider than the dd menu) the fp64 two-pass kernels.
 int ensure_dd(fos_problem* p) {
-  if (p->slabs_dd || p->resident) return FOS_OK;
+  if (p->dd.planned || p->pass.resident) return FOS_OK;
+  int rc;
   int nslabs = 0;
   int64_t stride = p->n;
   int n_rr = 0;
-  if (p->tall) {
-    nslabs = p->nwg; stride = p->slab_stride; n_rr = p->nwg;
+  if (p->pass.tall) {
+    nslabs = p->pass.nwg; stride = p->pass.slab_stride; n_rr = p->pass.nwg;
   } else {
     const DdEntry* e = nullptr;
-    if (p->path == 0 && !p->col_sharded)      // column-sharded: the two-pass form, r all-reduced between the passes
+    if (p->pass.path == 0 && !p->col_sharded)      // column-sharded: the two-pass form, r all-reduced between the passes
       for (const auto& c : kDdMenu)
         if (c.dtype == p->dtype && (int64_t)c.threads * c.k * epc_of(p->dtype) >= p->n) { e = &c; break; }
     if (e) {
-      p->dd_entry = e;
+      p->dd.entry = e;
       // fp64 form: two workgroups per CU for the 256-thread geometries (they hold 2 waves per SIMD at most 256 VGPRs
       // each); four for the one-chunk geometry (76 VGPRs; 1048576 x 1024: 723 -> 660 us = 81 % of 8 TB/s, tools/dd_bench;
       // the two-chunk geometry is best at two: 524288 x 2048 87.5 % against 82 %)
@@ -946,20 +977,20 @@ int ensure_dd(fos_problem* p) {
       const int64_t min_rows = std::max<int64_t>(2 * (int64_t)e->r, (65536 + row_bytes - 1) / row_bytes);   // fp64 slabs
       if (p->dd_nwg_hint > 0) nwg = p->dd_nwg_hint;
       if (p->m < (int64_t)nwg * min_rows) nwg = (int)std::max<int64_t>(1, p->m / min_rows);
-      p->dd_rows_per_wg = (p->m + nwg - 1) / nwg;
-      p->dd_nwg = (int)((p->m + p->dd_rows_per_wg - 1) / p->dd_rows_per_wg);
-      nslabs = p->dd_nwg; n_rr = p->dd_nwg;
+      p->dd.rows_per_wg = (p->m + nwg - 1) / nwg;
+      p->dd.nwg = (int)((p->m + p->dd.rows_per_wg - 1) / p->dd.rows_per_wg);
+      nslabs = p->dd.nwg; n_rr = p->dd.nwg;
     } else {
       const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(64, p->m / 64));
-      p->dd_rows_per_wg = (p->m + chunks - 1) / chunks;
-      p->dd_two_pass_chunks = (int)((p->m + p->dd_rows_per_wg - 1) / p->dd_rows_per_wg);
-      p->dd_nwg = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (p->m + 3) / 4));      // pass-1 grid
-      nslabs = p->dd_two_pass_chunks; n_rr = p->dd_nwg;
-      if (p->rvec == nullptr) HIP_TRY(hipMalloc(&p->rvec, (size_t)p->m * sizeof(double)));
+      p->dd.rows_per_wg = (p->m + chunks - 1) / chunks;
+      p->dd.two_pass_chunks = (int)((p->m + p->dd.rows_per_wg - 1) / p->dd.rows_per_wg);
+      p->dd.nwg = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (p->m + 3) / 4));      // pass-1 grid
+      nslabs = p->dd.two_pass_chunks; n_rr = p->dd.nwg;
+      if ((rc = p->pass.rvec.reserve(p->m))) return rc;
     }
   }
-  HIP_TRY(hipMalloc(&p->rr_dd, (size_t)std::max(n_rr, 1) * sizeof(double)));
-  HIP_TRY(hipMalloc(&p->slabs_dd, (size_t)nslabs * stride * sizeof(double)));
+  if ((rc = p->dd.rr.reserve(std::max(n_rr, 1))) || (rc = p->dd.slabs.reserve((size_t)nslabs * stride))) return rc;
+  p->dd.planned = true;
   return FOS_OK;
 }
 
@@ -971,22 +1002,22 @@ int launch_cluster_pass_cs(fos_problem* p) {
   static std::atomic<uint64_t> done{0};
   if (raise_dynamic_lds(kern, fos::CP_LDS_BYTES, done)) return fail(FOS_ERR_HIP, "cluster pass: dynamic LDS size refused");
   const float* A = (const float*)p->A;
-  int64_t lda = p->lda, m = p->m, rpc = p->cp_rows_per_cluster, n_stride = p->n;
-  int n = (int)p->n, n_pad = (int)p->n_pad, xcd_aware = 1;
+  int64_t lda = p->lda, m = p->m, rpc = p->multi.cp_rows_per_cluster, n_stride = p->n;
+  int n = (int)p->n, n_pad = (int)p->cand.n_pad, xcd_aware = 1;
   const float* b = p->b;
-  const float* xp = p->xp;
+  const float* xp = p->cand.xp;
   unsigned epoch = p->cp_epoch;
   // A PLAIN launch: #CUs workgroups with > 80 KiB of LDS each are co-resident by grid size - all a cooperative launch
   // would check (MI355X_MICROARCH.md "coop-launch") - every wait in the kernel is bounded, and a process that used
   // hipLaunchCooperativeKernel dies in rocprofv3's exit handler (tools/exit_probe.py, round 3).
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p->cp_clusters * CS)), dim3(fos::CP_THREADS), (unsigned)fos::CP_LDS_BYTES, p->stream, A,
-                     lda, b, m, n, n_pad, xp, rpc, xcd_aware, p->cp_xchg, p->cp_flags, epoch, p->slabs16, n_stride, p->cp_error);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(p->multi.cp_clusters * CS)), dim3(fos::CP_THREADS), (unsigned)fos::CP_LDS_BYTES, p->stream, A,
+                     lda, b, m, n, n_pad, xp, rpc, xcd_aware, p->multi.cp_xchg, p->multi.cp_flags, epoch, p->multi.slabs16, n_stride, p->multi.cp_error);
   LAUNCH_CHECK();
   p->cp_epoch += (unsigned)(rpc / fos::CP_ROWS) + 16u;
   return FOS_OK;
 }
 int launch_cluster_pass(fos_problem* p) {
-  switch (p->cp_cs) {
+  switch (p->multi.cp_cs) {
     case 4: return launch_cluster_pass_cs<4>(p);
     case 8: return launch_cluster_pass_cs<8>(p);
     case 16: return launch_cluster_pass_cs<16>(p);
@@ -1071,20 +1102,13 @@ int fos_problem_create(fos_problem** out, const void* A, int64_t m, int64_t n, i
   }
   p->ncu = prop.multiProcessorCount;
   apply_plan(p, 0);
-  int rc = ensure_workspace(p);
-  if (rc == FOS_OK) {
-    hipError_t he = hipMalloc(&p->gbuf_own, (size_t)(n + 4) * sizeof(float));
-    p->gbuf = p->gbuf_own;
-    if (he == hipSuccess) he = hipMalloc(&p->ybuf, (size_t)n * sizeof(float));
-    if (he == hipSuccess) he = hipMalloc(&p->dscal, 256 * sizeof(double));
-    p->part_cap = std::max(1024, (int)((n + fos::RCOLS - 1) / fos::RCOLS)) * 4;
-    if (he == hipSuccess) he = hipMalloc(&p->part, (size_t)p->part_cap * sizeof(double));
-    if (he != hipSuccess) rc = fail(FOS_ERR_HIP, std::string("fos_problem_create: ") + hipGetErrorString(he));
-  }
-  if (rc != FOS_OK) {
-    fos_problem_destroy(p);
+  int rc;
+  if ((rc = ensure_workspace(p)) || (rc = p->ws.gbuf_own.reserve(n + 4)) || (rc = p->ws.ybuf.reserve(n)) ||
+      (rc = p->ws.dscal.reserve(256)) || (rc = p->ws.part.reserve(std::max<size_t>(1024, (n + fos::RCOLS - 1) / fos::RCOLS) * 4))) {
+    delete p;
     return rc;
   }
+  p->gbuf = p->ws.gbuf_own;
   *out = p;
   return FOS_OK;
 }
@@ -1092,33 +1116,22 @@ int fos_problem_create(fos_problem** out, const void* A, int64_t m, int64_t n, i
 int fos_problem_set_comm(fos_problem* p, fos_comm* c) {
   if (!p) return fail(FOS_ERR_ARG, "fos_problem_set_comm: null");
   p->comm = c;
-  if (c) p->resident = false;        // the one-workgroup resident loop has no exchange step
-  else p->resident = fos::resident_fits(p->m, p->n) && p->allow_resident;
-  return FOS_OK;
+  return invalidate(p, IN_COMM);
 }
 
 int fos_problem_set_comm_cols(fos_problem* p, fos_comm* c) {
   if (!p || !c) return fail(FOS_ERR_ARG, "fos_problem_set_comm_cols: null");
-  const int epc = epc_of(p->dtype);
-  const bool vec_ok = (p->n % epc == 0) && (p->lda % epc == 0) && ((reinterpret_cast<uintptr_t>(p->A) & 15u) == 0);
-  if (!vec_ok || p->n <= tlr_max_n(p->dtype))
+  if (!vec_layout(p) || p->n <= tlr_max_n(p->dtype))
     return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_comm_cols: needs the streaming layout (aligned, more than 32 chunks of 16 bytes per row and rank)");
   // the two-phase column-block plan, whatever the width: r = sum_p A_p y_p - b is exchanged between the phases
-  void* drop[] = {p->slabs, p->rr_part, p->rr2_part};
-  for (void* q : drop)
-    if (q) (void)hipFree(q);
-  p->slabs = nullptr; p->rr_part = p->rr2_part = nullptr;
-  p->slab_cap = p->rr_cap = 0;
-  p->tall = false; p->slab_stride = 0; p->vec4 = true; p->resident = false;
-  const int64_t blocks = (p->n + 16383) / 16384;
-  p->cb_width = ((p->n + blocks - 1) / blocks + 63) / 64 * 64;
-  const MenuEntry* ce = default_entry(p->dtype, p->cb_width);
-  if (!ce || !ce->with_g_cb || !ce->resid_only_cb)
-    return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_comm_cols: no column-block kernel for this block width");
-  plan_fused(p, ce, 0);
-  p->colblock = true;
+  int64_t cb_width = 0;
+  const MenuEntry* ce = colblock_entry(p, &cb_width);
+  if (!ce) return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_comm_cols: no column-block kernel for this block width");
   p->comm = c;
   p->col_sharded = true;
+  if (int rc = invalidate(p, IN_PLAN | IN_COMM)) return rc;
+  p->pass.vec4 = true;
+  plan_colblock(p, ce, cb_width);
   return ensure_workspace(p);
 }
 
@@ -1144,26 +1157,13 @@ int fos_problem_replan(fos_problem* p, unsigned flags) {
                            FOS_PLAN_INTERLEAVE | FOS_PLAN_NO_INTERLEAVE | FOS_PLAN_NO_CLUSTER | FOS_PLAN_FUSED_MFMA |
                            FOS_PLAN_CHIP_RESIDENT | FOS_PLAN_NO_CHIP_RESIDENT))
     return fail(FOS_ERR_ARG, "fos_problem_replan: unknown flag");
-  // the multi-lambda workspace follows its own plan (one-read cluster form or two products): rebuilt on first use
-  {
-    void* multi[] = {p->rbuf16, p->slabs16, p->cp_xchg, p->cp_flags, p->cp_error};
-    for (void* q : multi)
-      if (q) (void)hipFree(q);
-    p->rbuf16 = p->slabs16 = p->cp_xchg = nullptr; p->cp_flags = nullptr; p->cp_error = nullptr;
-    p->cp_cs = p->cp_clusters = 0;
-    p->cp_mode = (flags & FOS_PLAN_CLUSTER) ? 1 : (flags & FOS_PLAN_NO_CLUSTER) ? 2 : 0;
-    p->fused_on = (flags & FOS_PLAN_FUSED_MFMA) != 0;
-    p->chip_mode = (flags & FOS_PLAN_CHIP_RESIDENT) ? 1 : (flags & FOS_PLAN_NO_CHIP_RESIDENT) ? 2 : 0;
-    flags &= ~(unsigned)(FOS_PLAN_CLUSTER | FOS_PLAN_NO_CLUSTER | FOS_PLAN_FUSED_MFMA | FOS_PLAN_CHIP_RESIDENT |
-                         FOS_PLAN_NO_CHIP_RESIDENT);
-  }
-  // workspace sized for the old plan (slab stride, fp64 slabs) is dropped and rebuilt
-  void* drop[] = {p->slabs, p->rr_part, p->rr2_part, p->slabs_dd, p->rr_dd};
-  for (void* q : drop)
-    if (q) (void)hipFree(q);
-  p->slabs = nullptr; p->rr_part = p->rr2_part = nullptr; p->slabs_dd = nullptr; p->rr_dd = nullptr;
-  p->slab_cap = p->rr_cap = 0;
-  p->dd_entry = nullptr; p->dd_two_pass_chunks = 0;
+  p->cp_mode = (flags & FOS_PLAN_CLUSTER) ? 1 : (flags & FOS_PLAN_NO_CLUSTER) ? 2 : 0;
+  p->fused_on = (flags & FOS_PLAN_FUSED_MFMA) != 0;
+  p->chip_mode = (flags & FOS_PLAN_CHIP_RESIDENT) ? 1 : (flags & FOS_PLAN_NO_CHIP_RESIDENT) ? 2 : 0;
+  flags &= ~(unsigned)(FOS_PLAN_CLUSTER | FOS_PLAN_NO_CLUSTER | FOS_PLAN_FUSED_MFMA | FOS_PLAN_CHIP_RESIDENT |
+                       FOS_PLAN_NO_CHIP_RESIDENT);
+  int rc = invalidate(p, IN_PLAN);
+  if (rc) return rc;
   apply_plan(p, flags);
   return ensure_workspace(p);
 }
@@ -1177,8 +1177,8 @@ int fos_stream_read_probe(const void* buf, size_t bytes, int launches, void* str
   HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
   const size_t n16 = bytes / 16;
   const int grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)ncu, (n16 + 4095) / 4096));
-  float* sink = nullptr;
-  HIP_TRY(hipMalloc(&sink, (size_t)grid * 8 * sizeof(float)));
+  DevBuf<float> sink;
+  if (int rc = sink.reserve((size_t)grid * 8)) return rc;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   hipError_t e = hipEventCreate(&e0);
   if (e == hipSuccess) e = hipEventCreate(&e1);
@@ -1189,10 +1189,10 @@ int fos_stream_read_probe(const void* buf, size_t bytes, int launches, void* str
   for (int order = 0; order < 3 && e == hipSuccess; ++order) {
     void (*kern)(const fos::f32x4*, size_t, float*) =
         order == 0 ? stream_read_kernel<0> : order == 1 ? stream_read_kernel<1> : stream_read_kernel<2>;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, st, (const fos::f32x4*)buf, n16, sink);      // warm-up
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, st, (const fos::f32x4*)buf, n16, sink.get());      // warm-up
     e = hipEventRecord(e0, st);
     for (int i = 0; i < launches && e == hipSuccess; ++i) {
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, st, (const fos::f32x4*)buf, n16, sink);
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, st, (const fos::f32x4*)buf, n16, sink.get());
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(e1, st);
@@ -1203,7 +1203,6 @@ int fos_stream_read_probe(const void* buf, size_t bytes, int launches, void* str
   }
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(sink);
   if (e != hipSuccess) return fail(FOS_ERR_HIP, std::string("fos_stream_read_probe: ") + hipGetErrorString(e));
   const double us = (double)ms * 1e3 / launches;
   *gbps_out = (double)bytes / (us * 1e-6) / 1e9;
@@ -1233,27 +1232,20 @@ int fos_problem_profile_read(fos_problem* p, double* ms_total, int64_t* launches
 int fos_problem_destroy(fos_problem* p) {
   if (!p) return FOS_OK;
   for (hipEvent_t e : p->ev_pool) (void)hipEventDestroy(e);
-  void* bufs[] = {p->slabs, p->rr_part, p->rr2_part, p->rvec, p->gbuf_own, p->ybuf, p->dscal, p->part, p->xp, p->q_part, p->bt_out,
-                  p->slabs_dd, p->rr_dd, p->lhist, p->rbuf16, p->rcols16, p->b16, p->mfold, p->cr_part, p->cr_bar, p->slabs16, p->rneg, p->zeros, p->cp_xchg, p->cp_flags, p->fz_bar, p->fz_part, p->fz_beta,
-                  p->cp_error, p->xd, p->rdd, p->slabs_dd16, p->qdd_part};
-  for (void* q : bufs)
-    if (q) (void)hipFree(q);
-  delete p->lbfgs;
-  delete p->lbfgs_multi;
   delete p;
   return FOS_OK;
 }
 
 int fos_problem_plan(const fos_problem* p, int32_t plan[8]) {
   if (!p || !plan) return fail(FOS_ERR_ARG, "fos_problem_plan: null");
-  plan[0] = p->path;
-  plan[1] = p->entry ? p->entry->threads : 256;
-  plan[2] = p->entry ? p->entry->k : 0;
-  plan[3] = p->entry ? p->entry->r : 0;
-  plan[4] = p->nwg;
-  plan[5] = p->nslabs;
-  plan[6] = (p->path == 0 ? 1 : 0) | (p->resident ? 2 : 0) | (p->tall ? 4 : 0) | (p->colblock ? 8 : 0) | (p->cp_cs ? 16 : 0) |
-            ((p->il && p->entry && p->entry->with_g_il && p->path == 0 && !p->colblock && !p->tall) ? 32 : 0) |
+  plan[0] = p->pass.path;
+  plan[1] = p->pass.entry ? p->pass.entry->threads : 256;
+  plan[2] = p->pass.entry ? p->pass.entry->k : 0;
+  plan[3] = p->pass.entry ? p->pass.entry->r : 0;
+  plan[4] = p->pass.nwg;
+  plan[5] = p->pass.nslabs;
+  plan[6] = (p->pass.path == 0 ? 1 : 0) | (p->pass.resident ? 2 : 0) | (p->pass.tall ? 4 : 0) | (p->pass.colblock ? 8 : 0) | (p->multi.cp_cs ? 16 : 0) |
+            ((p->il && p->pass.entry && p->pass.entry->with_g_il && p->pass.path == 0 && !p->pass.colblock && !p->pass.tall) ? 32 : 0) |
             (p->fused_on ? 64 : 0) | (p->chip_mode == 1 ? 128 : 0);
   plan[7] = p->ncu;
   return FOS_OK;
@@ -1261,37 +1253,34 @@ int fos_problem_plan(const fos_problem* p, int32_t plan[8]) {
 
 int fos_problem_tune(fos_problem* p, int threads, int chunks, int rows, int workgroups) {
   if (!p) return fail(FOS_ERR_ARG, "fos_problem_tune: null");
-  if (p->path == 0 && p->tall && workgroups > 0) {        // row-per-thread pass: only the workgroup count is tunable
-    p->rows_per_wg = ((p->m + workgroups - 1) / workgroups + 3) / 4 * 4;
-    p->nwg = (int)((p->m + p->rows_per_wg - 1) / p->rows_per_wg);
-    p->nslabs = p->nwg;
+  if (p->pass.path == 0 && p->pass.tall && workgroups > 0) {        // row-per-thread pass: only the workgroup count is tunable
+    p->pass.rows_per_wg = ((p->m + workgroups - 1) / workgroups + 3) / 4 * 4;
+    p->pass.nwg = (int)((p->m + p->pass.rows_per_wg - 1) / p->pass.rows_per_wg);
+    p->pass.nslabs = p->pass.nwg;
+    if (int rc = invalidate(p, IN_TUNE)) return rc;
     return ensure_workspace(p);
   }
-  if (p->path != 0 || p->tall || p->colblock)
+  if (p->pass.path != 0 || p->pass.tall || p->pass.colblock)
     return fail(FOS_ERR_UNSUPPORTED, "fos_problem_tune: only the streaming single-pass kernel has a geometry menu");
   const MenuEntry* e = find_entry(p->dtype, threads, chunks, rows);
   if (!e || (int64_t)e->threads * e->k * epc_of(p->dtype) < p->n)
     return fail(FOS_ERR_UNSUPPORTED, "fos_problem_tune: geometry not instantiated or too narrow for n");
   plan_fused(p, e, workgroups);
+  if (int rc = invalidate(p, IN_TUNE)) return rc;
   return ensure_workspace(p);
 }
 
 int fos_problem_tune_dd(fos_problem* p, int workgroups) {
   if (!p || workgroups < 0) return fail(FOS_ERR_ARG, "fos_problem_tune_dd: bad argument");
-  if (p->tall || p->resident) return fail(FOS_ERR_UNSUPPORTED, "fos_problem_tune_dd: the tall / resident plans share the fp32 pass's grid");
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  if (p->slabs_dd) (void)hipFree(p->slabs_dd);
-  if (p->rr_dd) (void)hipFree(p->rr_dd);
-  p->slabs_dd = nullptr; p->rr_dd = nullptr;
-  p->dd_entry = nullptr; p->dd_two_pass_chunks = 0;
+  if (p->pass.tall || p->pass.resident) return fail(FOS_ERR_UNSUPPORTED, "fos_problem_tune_dd: the tall / resident plans share the fp32 pass's grid");
   p->dd_nwg_hint = workgroups;
-  return FOS_OK;                                   // re-planned on the next fp64 pass (ensure_dd)
+  return invalidate(p, IN_TUNE_DD);                // re-planned on the next fp64 pass (ensure_dd)
 }
 
 int fos_problem_set_gbuf(fos_problem* p, float* gbuf) {
   if (!p) return fail(FOS_ERR_ARG, "fos_problem_set_gbuf: null");
   if (gbuf && (reinterpret_cast<uintptr_t>(gbuf) & 15u)) return fail(FOS_ERR_ARG, "fos_problem_set_gbuf: misaligned");
-  p->gbuf = gbuf ? gbuf : p->gbuf_own;
+  p->gbuf = gbuf ? gbuf : p->ws.gbuf_own;
   return FOS_OK;
 }
 
@@ -1312,7 +1301,7 @@ int fos_gemv_pair(fos_problem* p, const float* y, float alpha2, float* grad, dou
 
 int fos_gemv_pair_f64(fos_problem* p, const double* y, double alpha2, float* grad, double* rr_out) {
   if (!p || !y || !grad) return fail(FOS_ERR_ARG, "fos_gemv_pair_f64: null");
-  if (p->resident) {                           // small problem: one launch, fp64 throughout (resident.hpp)
+  if (p->pass.resident) {                           // small problem: one launch, fp64 throughout (resident.hpp)
     if (p->dtype == FOS_F32)
       hipLaunchKernelGGL(fos::gemv_pair_resident_kernel<float>, dim3(1), dim3(fos::RS_THREADS), 0, p->stream,
                          (const float*)p->A, p->lda, p->b, (int)p->m, (int)p->n, y, alpha2, grad, rr_out);
@@ -1355,33 +1344,20 @@ __global__ __launch_bounds__(256) void unsum_f64_if_stopped_kernel(double* __res
 // the local block; alpha2*y_p is local.  out[0..n) is this rank's block of the gradient, out[n] the global ||r||^2.
 static int launch_pass_dd_cols(fos_problem* p, const YSource& ys, double alpha2, const double* l2vec, double* out) {
   const float* b_here = p->comm->rank == 0 ? p->b : nullptr;
-  const dim3 grid((unsigned)((p->n + 255) / 256), (unsigned)p->dd_two_pass_chunks);
-  if (p->dtype == FOS_F32)
-    hipLaunchKernelGGL(fos::residual_rows_kernel<float>, dim3(p->dd_nwg), dim3(256), 0, p->stream, (const float*)p->A, p->lda,
-                       b_here, p->m, (int)p->n, ys, p->rvec, p->rr_dd);
-  else
-    hipLaunchKernelGGL(fos::residual_rows_kernel<fos::bf16_t>, dim3(p->dd_nwg), dim3(256), 0, p->stream,
-                       (const fos::bf16_t*)p->A, p->lda, b_here, p->m, (int)p->n, ys, p->rvec, p->rr_dd);
-  LAUNCH_CHECK();
+  int rc = launch_residual_rows(p, ys, b_here, p->dd.nwg, p->dd.rr);
+  if (rc) return rc;
   if (ys.stopped != nullptr) {       // after a stop pass 1 was a no-op and rvec still holds the last SUM: divide it back
-    hipLaunchKernelGGL(unsum_f64_if_stopped_kernel, dim3(grid_1d(p->m, 256, 1024)), dim3(256), 0, p->stream, p->rvec, p->m,
+    hipLaunchKernelGGL(unsum_f64_if_stopped_kernel, dim3(grid_1d(p->m, 256, 1024)), dim3(256), 0, p->stream, p->pass.rvec, p->m,
                        1.0 / (double)p->comm->nranks, ys.stopped);
     LAUNCH_CHECK();
   }
-  int rc = reduce_across(p, p->rvec, (size_t)p->m, true);
-  if (rc) return rc;
-  const int n_rr = std::min(p->dd_nwg, 256);
-  hipLaunchKernelGGL(sumsq_f64_partials_kernel, dim3(n_rr), dim3(256), 0, p->stream, p->rvec, p->m, p->rr_dd, ys.stopped);
+  if ((rc = reduce_across(p, p->pass.rvec, (size_t)p->m, true))) return rc;
+  const int n_rr = std::min(p->dd.nwg, 256);
+  hipLaunchKernelGGL(sumsq_f64_partials_kernel, dim3(n_rr), dim3(256), 0, p->stream, p->pass.rvec, p->m, p->dd.rr, ys.stopped);
   LAUNCH_CHECK();
-  if (p->dtype == FOS_F32)
-    hipLaunchKernelGGL((fos::transpose_rows_kernel<float, double>), grid, dim3(256), 0, p->stream, (const float*)p->A, p->lda,
-                       p->m, (int)p->n, p->rvec, ys.stopped, p->dd_rows_per_wg, p->slabs_dd);
-  else
-    hipLaunchKernelGGL((fos::transpose_rows_kernel<fos::bf16_t, double>), grid, dim3(256), 0, p->stream,
-                       (const fos::bf16_t*)p->A, p->lda, p->m, (int)p->n, p->rvec, ys.stopped, p->dd_rows_per_wg, p->slabs_dd);
-  LAUNCH_CHECK();
+  if ((rc = launch_transpose_rows<double>(p, ys.stopped, p->dd.two_pass_chunks, p->dd.rows_per_wg, p->dd.slabs.get()))) return rc;
   hipLaunchKernelGGL(fos::slab_reduce_dd_kernel, dim3((unsigned)((p->n + fos::SRD_COLS - 1) / fos::SRD_COLS)),
-                     dim3(fos::SRD_THREADS), 0, p->stream, p->slabs_dd, p->dd_two_pass_chunks, (int)p->n, (int64_t)p->n, p->rr_dd,
+                     dim3(fos::SRD_THREADS), 0, p->stream, p->dd.slabs, p->dd.two_pass_chunks, (int)p->n, (int64_t)p->n, p->dd.rr,
                      n_rr, alpha2, l2vec, out, ys.stopped);
   LAUNCH_CHECK();
   return FOS_OK;
@@ -1396,41 +1372,30 @@ int fosapi::launch_pass_dd(fos_problem* p, const YSource& ys, double alpha2, con
     if ((rc = launch_pass_dd_cols(p, ys, alpha2, l2vec, out))) return rc;
     return prof_mark(p, false);
   }
-  if (rc) return rc;
   int nslabs = 0, n_rr = 0;
   int64_t stride = p->n;
   if ((rc = prof_mark(p, true))) return rc;
-  if (p->tall) {
-    p->entry->dd(p->A, p->lda, p->b, p->m, (int)p->n, ys, p->rows_per_wg, p->slabs_dd, p->rr_dd, p->nwg, p->stream);
-    nslabs = n_rr = p->nwg;
-    stride = p->slab_stride;
-  } else if (p->dd_entry) {
-    (p->il && p->dd_entry->fn_il ? p->dd_entry->fn_il : p->dd_entry->fn)(p->A, p->lda, p->b, p->m, (int)p->n, ys, p->dd_rows_per_wg, p->slabs_dd, p->rr_dd, p->dd_nwg, p->stream);
-    nslabs = n_rr = p->dd_nwg;
+  if (p->pass.tall) {
+    p->pass.entry->dd(p->A, p->lda, p->b, p->m, (int)p->n, ys, p->pass.rows_per_wg, p->dd.slabs, p->dd.rr, p->pass.nwg, p->stream);
+    nslabs = n_rr = p->pass.nwg;
+    stride = p->pass.slab_stride;
+  } else if (p->dd.entry) {
+    (p->il && p->dd.entry->fn_il ? p->dd.entry->fn_il : p->dd.entry->fn)(p->A, p->lda, p->b, p->m, (int)p->n, ys, p->dd.rows_per_wg, p->dd.slabs, p->dd.rr, p->dd.nwg, p->stream);
+    nslabs = n_rr = p->dd.nwg;
   } else {
-    dim3 grid((unsigned)((p->n + 255) / 256), (unsigned)p->dd_two_pass_chunks);
-    if (p->dtype == FOS_F32) {
-      hipLaunchKernelGGL(fos::residual_rows_kernel<float>, dim3(p->dd_nwg), dim3(256), 0, p->stream, (const float*)p->A,
-                         p->lda, p->b, p->m, (int)p->n, ys, p->rvec, p->rr_dd);
-      hipLaunchKernelGGL((fos::transpose_rows_kernel<float, double>), grid, dim3(256), 0, p->stream, (const float*)p->A,
-                         p->lda, p->m, (int)p->n, p->rvec, ys.stopped, p->dd_rows_per_wg, p->slabs_dd);
-    } else {
-      hipLaunchKernelGGL(fos::residual_rows_kernel<fos::bf16_t>, dim3(p->dd_nwg), dim3(256), 0, p->stream,
-                         (const fos::bf16_t*)p->A, p->lda, p->b, p->m, (int)p->n, ys, p->rvec, p->rr_dd);
-      hipLaunchKernelGGL((fos::transpose_rows_kernel<fos::bf16_t, double>), grid, dim3(256), 0, p->stream,
-                         (const fos::bf16_t*)p->A, p->lda, p->m, (int)p->n, p->rvec, ys.stopped, p->dd_rows_per_wg,
-                         p->slabs_dd);
-    }
-    nslabs = p->dd_two_pass_chunks;
-    n_rr = p->dd_nwg;
+    if ((rc = launch_residual_rows(p, ys, p->b, p->dd.nwg, p->dd.rr)) ||
+        (rc = launch_transpose_rows<double>(p, ys.stopped, p->dd.two_pass_chunks, p->dd.rows_per_wg, p->dd.slabs.get())))
+      return rc;
+    nslabs = p->dd.two_pass_chunks;
+    n_rr = p->dd.nwg;
   }
   LAUNCH_CHECK();
   if ((rc = prof_mark(p, false))) return rc;
   // sharded: alpha2*x enters the sum over the ranks exactly once (rank 0 adds it to its partial)
   const double a2_here = (p->comm && p->comm->rank != 0) ? 0.0 : alpha2;
   hipLaunchKernelGGL(fos::slab_reduce_dd_kernel, dim3((unsigned)((p->n + fos::SRD_COLS - 1) / fos::SRD_COLS)),
-                     dim3(fos::SRD_THREADS), 0, p->stream, p->slabs_dd,
-                     nslabs, (int)p->n, stride, p->rr_dd, n_rr, a2_here, l2vec, out, p->comm ? nullptr : ys.stopped);
+                     dim3(fos::SRD_THREADS), 0, p->stream, p->dd.slabs,
+                     nslabs, (int)p->n, stride, p->dd.rr, n_rr, a2_here, l2vec, out, p->comm ? nullptr : ys.stopped);
   LAUNCH_CHECK();
   return reduce_across(p, out, (size_t)p->n + 1, true);      // (sharded: re-derived after a stop, see launch_slab_reduce)
 }
@@ -1447,7 +1412,7 @@ int fosapi::gemv_pair_dd_stamped(fos_problem* p, const double* x, double alpha2,
                                  bool* stamped) {
   if (stamped) *stamped = false;
   if (!p || !x || !grad_rr) return fail(FOS_ERR_ARG, "fos_gemv_pair_dd: null");
-  if (p->resident) {                           // small problem: one launch, fp64 throughout (resident.hpp)
+  if (p->pass.resident) {                           // small problem: one launch, fp64 throughout (resident.hpp)
     if (p->dtype == FOS_F32)
       hipLaunchKernelGGL((fos::gemv_pair_resident_kernel<float, double>), dim3(1), dim3(fos::RS_THREADS), 0, p->stream,
                          (const float*)p->A, p->lda, p->b, (int)p->m, (int)p->n, x, alpha2, grad_rr, grad_rr + p->n);
@@ -1471,10 +1436,10 @@ int fosapi::gemv_pair_dd_stamped(fos_problem* p, const double* x, double alpha2,
 // whether the kernel behind fos_gemv_pair_dd on this plan writes YSource::t_stamp (the streaming fp64 kernel does)
 int fosapi::dd_pass_stamps(fos_problem* p, bool* yes) {
   *yes = false;
-  if (p->resident) return FOS_OK;
+  if (p->pass.resident) return FOS_OK;
   int rc = ensure_dd(p);
   if (rc) return rc;
-  *yes = p->dd_entry != nullptr && !p->tall && !p->col_sharded;
+  *yes = p->dd.entry != nullptr && !p->pass.tall && !p->col_sharded;
   return FOS_OK;
 }
 extern "C" {
@@ -1487,7 +1452,7 @@ int fos_residual_objective(fos_problem* p, const float* x, double* out3) {
   YSource ys{xa, nullptr, nullptr, nullptr, nullptr};
   int n_rr = 0;
   if ((rc = launch_pass(p, ys, p->b, false, &n_rr))) return rc;
-  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->rr_part, n_rr, 1, out3);
+  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->pass.rr_part, n_rr, 1, out3);
   LAUNCH_CHECK();
   if (!p->col_sharded && (rc = reduce_across(p, out3, 1, true))) return rc;
   hipLaunchKernelGGL(fos::vec_norms_kernel, dim3(1), dim3(fos::LB_THREADS), 0, p->stream, xa, p->n, out3 + 1);
@@ -1502,11 +1467,11 @@ int fos_residual_batch(fos_problem* p, const float* X, int nv, int use_b, double
   int rc = ensure_batch_workspace(p);
   if (rc) return rc;
   if (p->dtype == FOS_BF16)
-    hipLaunchKernelGGL(fos::xq_pack_kernel, dim3(grid_1d(p->n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
-                       (int)p->n_pad, nv, (unsigned short*)p->xp);
+    hipLaunchKernelGGL(fos::xq_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
+                       (int)p->cand.n_pad, nv, (unsigned short*)p->cand.xp.get());
   else
-    hipLaunchKernelGGL(xp_pack_kernel, dim3(grid_1d(p->n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
-                       (int)p->n_pad, nv, p->xp);
+    hipLaunchKernelGGL(xp_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
+                       (int)p->cand.n_pad, nv, p->cand.xp);
   LAUNCH_CHECK();
   return launch_residual_batch(p, use_b, out16);
 }
@@ -1520,13 +1485,13 @@ int fos_residual_batch_rhs(fos_problem* p, const float* X, int nv, const float* 
   if (rc) return rc;
   if ((rc = stage_b16(p, B, ldb, nv))) return rc;
   if (p->dtype == FOS_BF16)
-    hipLaunchKernelGGL(fos::xq_pack_kernel, dim3(grid_1d(p->n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
-                       (int)p->n_pad, nv, (unsigned short*)p->xp);
+    hipLaunchKernelGGL(fos::xq_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
+                       (int)p->cand.n_pad, nv, (unsigned short*)p->cand.xp.get());
   else
-    hipLaunchKernelGGL(xp_pack_kernel, dim3(grid_1d(p->n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
-                       (int)p->n_pad, nv, p->xp);
+    hipLaunchKernelGGL(xp_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
+                       (int)p->cand.n_pad, nv, p->cand.xp);
   LAUNCH_CHECK();
-  return launch_residual_batch(p, 1, out16, nullptr, p->b16);
+  return launch_residual_batch(p, 1, out16, nullptr, p->ws.b16);
 }
 
 int fos_gemv_pair_dd_multi(fos_problem* p, const double* X, int nv, int64_t ldx, const float* B, int64_t ldb, double alpha2,
@@ -1544,7 +1509,7 @@ int fos_gemv_pair_dd_multi(fos_problem* p, const double* X, int nv, int64_t ldx,
   }
   int rc = stage_b16(p, B, ldb, nv);
   if (rc) return rc;
-  return pair_dd_multi(p, c, nv, (1u << nv) - 1u, alpha2, p->b16);
+  return pair_dd_multi(p, c, nv, (1u << nv) - 1u, alpha2, p->ws.b16);
 }
 
 int fos_power_iter(fos_problem* p, float* v_inout, int n_iter, double tol, double* L_out, int* iters_out) {
@@ -1552,11 +1517,11 @@ int fos_power_iter(fos_problem* p, float* v_inout, int n_iter, double tol, doubl
   if (p->col_sharded)
     return fail(FOS_ERR_UNSUPPORTED, "fos_power_iter: column-sharded problems normalise over the ranks (see _lipschitz_cols)");
   // L after every step (+ the norm of v0): sized by the caller's n_iter
-  if (int rc = grow(&p->lhist_cap, n_iter + 1, sizeof(double), &p->lhist)) return rc;
-  double* Lh = p->lhist;        // n_iter + 1 slots
-  if (p->resident) {
+  if (int rc = p->ws.lhist.reserve((size_t)n_iter + 1)) return rc;
+  double* Lh = p->ws.lhist;        // n_iter + 1 slots
+  if (p->pass.resident) {
     // all iterations in one launch; the break rule (:57) is evaluated on the device
-    int* used_dev = reinterpret_cast<int*>(p->dscal + 240);
+    int* used_dev = reinterpret_cast<int*>(p->ws.dscal + 240);
     if (p->dtype == FOS_F32)
       hipLaunchKernelGGL(fos::power_resident_kernel<float>, dim3(1), dim3(fos::RS_THREADS), 0, p->stream,
                          (const float*)p->A, p->lda, (int)p->m, (int)p->n, v_inout, n_iter, tol, Lh, used_dev);
@@ -1574,7 +1539,7 @@ int fos_power_iter(fos_problem* p, float* v_inout, int n_iter, double tol, doubl
     if (iters_out) *iters_out = used;
     return FOS_OK;
   }
-  float* v = p->ybuf;
+  float* v = p->ws.ybuf;
   // v = v0 / ||v0||   (iterative_solvers.py:51)
   hipLaunchKernelGGL(fos::power_normalize_kernel, dim3(1), dim3(1024), 0, p->stream, v_inout, (int)p->n, v, Lh + n_iter);
   LAUNCH_CHECK();

@@ -1658,10 +1658,11 @@ def test_handles_release_their_device_memory(fos):
     multi-lambda panels, L-BFGS workspace, persistent-step barriers) goes back with the handle: device memory in use after
     40 rounds of create -> every solver family -> destroy equals the level after the first round."""
     import gc
-    from fastoptsolver_amd import _core
+    from fastoptsolver_amd import _core, _lib
     A, b, _ = _data.synth(3000, 2048, 77)
     At = torch.as_tensor(A.astype(np.float32)).cuda()
     bt = b.astype(np.float32)
+    B3 = np.stack([bt, 0.5 * bt, -bt], axis=1)
     L = float(np.linalg.norm(A, 2) ** 2)
     lam = float(np.max(np.abs(A.T @ b)))
 
@@ -1673,9 +1674,19 @@ def test_handles_release_their_device_memory(fos):
         fos.fista_path(prob, None, [(0.1 * lam * 0.8 ** i, 0.0) for i in range(6)], max_iter=4, L=L)
         fos.fista_path(prob, None, [(0.1 * lam * 0.8 ** i, 0.0) for i in range(3)], max_iter=4, L=L, adaptive_restart=True)
         fos.LBFGSSolver("ridge", 0.0, 1.0, max_iter=3).fit(prob, None)
+        fos.LBFGSSolver("ridge", 0.0, 1.0, max_iter=3).fit(prob, B3)
         st = _core.Fista(prob); st.reset(1.0 / L, 0.1 * lam, 0.0)
         assert st.run_fused(3)
-        del st, prob
+        del st
+        # every group is reset and built again before the handle goes: re-plan, tune both passes, run the families again
+        prob.replan(cluster=False)
+        prob.tune(256, 2, 4, 300)
+        _lib.check(prob.lib.fos_problem_tune_dd(prob.h, 200), "fos_problem_tune_dd")
+        fos.fista(prob, None, "elasticnet", 0.1 * lam, 0.5, max_iter=5, L=L, backtracking=True)
+        fos.fista_path(prob, None, [(0.1 * lam * 0.8 ** i, 0.0) for i in range(6)], max_iter=4, L=L)
+        fos.LBFGSSolver("ridge", 0.0, 1.0, max_iter=3).fit(prob, None)
+        fos.LBFGSSolver("ridge", 0.0, 1.0, max_iter=3).fit(prob, B3)
+        del prob
         gc.collect()
         torch.cuda.synchronize()
 
@@ -1685,6 +1696,134 @@ def test_handles_release_their_device_memory(fos):
         one_round()
     free1, _ = torch.cuda.mem_get_info()
     assert free0 - free1 < (8 << 20), f"device memory in use grew by {(free0 - free1) / 2 ** 20:.1f} MiB over 40 rounds"
+
+
+# --------------------------------------------------------------------------------------------------
+# Re-planning, tuning and attaching a communicator AFTER the first pass: the groups of the plan that were derived from
+# the changed input are rebuilt (fos_internal.hpp: invalidate).  Each order is checked against the fp64 oracle at the
+# tolerance of the neighbouring tests of the same pass, and bit for bit against a fresh handle brought into the same
+# state before its first pass.
+# --------------------------------------------------------------------------------------------------
+def _pair_dd(prob, xd):
+    from fastoptsolver_amd import _core, _lib
+    out = torch.zeros(prob.n_dev + 1, dtype=torch.float64, device="cuda")
+    _lib.check(prob.lib.fos_gemv_pair_dd(prob.h, _core.ptr(xd), 0.37, _core.ptr(out)), "fos_gemv_pair_dd")
+    return out
+
+
+@pytest.mark.parametrize("m,n", [(40000, 100), (20001, 7)])
+def test_tune_after_an_fp64_pass_on_tall_plans(fos, m, n):
+    """Tall plans share the fp32 pass's grid with the fp64 pass: fos_problem_tune(0, 0, 0, workgroups) after the first
+    fos_gemv_pair_dd, with more and with fewer workgroups than planned, re-sizes the fp64 slabs with the grid.
+    40000 x 100 takes the chunk-per-lane pass, 20001 x 7 the row-per-thread pass (more rows than the resident loop)."""
+    rng = np.random.default_rng(m + n)
+    A = rng.standard_normal((m, n)).astype(np.float32)
+    b = rng.standard_normal(m).astype(np.float32)
+    x = rng.standard_normal(n) * (1.0 + 1e-9 * rng.standard_normal(n))
+    At, xd, yd = torch.as_tensor(A).cuda(), _dev(x, torch.float64), _dev(x.astype(np.float32))
+    g_ref, rr_ref = orc.gram_gradient(A.astype(np.float64), x, b.astype(np.float64), 0.37)
+    g32_ref, _ = orc.gram_gradient(A.astype(np.float64), x.astype(np.float32).astype(np.float64), b.astype(np.float64), 0.37)
+    prob = fos.prepare(At, b, pad=False)
+    plan = prob.plan()
+    assert plan["tall"] == 1 and plan["resident"] == 0, plan
+    planned = plan["workgroups"]
+
+    def check(out, g32, where):
+        got = out.cpu().numpy()
+        assert _data.rel(got[:n], g_ref) < 1e-12, where
+        assert got[n] == pytest.approx(rr_ref, rel=1e-12), where
+        assert _data.rel(g32.cpu().numpy(), g32_ref) < 1e-6, where          # test_tall_skinny_gemv_pair's bounds
+
+    check(_pair_dd(prob, xd), prob.gemv_pair(yd, alpha2=0.37), ("planned", plan))
+    for wg in (2 * planned + 3, max(1, 2 * planned // 3)):
+        prob.tune(0, 0, 0, wg)
+        assert prob.plan()["workgroups"] != planned
+        out, g32 = _pair_dd(prob, xd), prob.gemv_pair(yd, alpha2=0.37)
+        check(out, g32, (wg, prob.plan()))
+        fresh = fos.prepare(At, b, pad=False)
+        fresh.tune(0, 0, 0, wg)
+        assert fresh.plan() == prob.plan()
+        assert torch.equal(_pair_dd(fresh, xd), out), wg
+        assert torch.equal(fresh.gemv_pair(yd, alpha2=0.37), g32), wg
+
+
+def _six_weights(fos, m, n, seed):
+    A, b, _ = _data.synth(m, n, seed)
+    At = torch.as_tensor(A.astype(np.float32)).cuda()
+    A = At.to(torch.float64).cpu().numpy()
+    b = b.astype(np.float32).astype(np.float64)
+    lam = float(np.max(np.abs(A.T @ b)))
+    L = float(np.linalg.norm(A, "fro") ** 2)
+    alphas = [(lam * 0.4 * 0.7 ** i, 0.5 if i % 3 == 1 else 0.0) for i in range(6)]
+    refs = [orc.fista(A, b, "elasticnet", a1, a2, max_iter=15, L=L) for a1, a2 in alphas]
+    return At, b.astype(np.float32), alphas, L, refs
+
+
+def _check_path(xs, refs, same_as=None):
+    for i, (x, x_ref) in enumerate(zip(xs, refs)):
+        assert _data.rel(_np(x), x_ref) < TOL, i
+        if same_as is not None:
+            assert np.array_equal(_np(x), _np(same_as[i])), i
+
+
+def test_replan_after_a_lockstep_run(fos):
+    """A 6-weight path on the matrix cores in the one-read cluster form, then replan(cluster=False): the panel, the slab
+    sets and the hand-off ring of the cluster layout go, the two-product layout is planned on the next run."""
+    At, b, alphas, L, refs = _six_weights(fos, 8200, 4096, 5)
+    prob = fos.prepare(At, b)
+    prob.replan(cluster=True)
+    _check_path(fos.fista_path(prob, None, alphas, max_iter=15, L=L), refs)
+    assert prob.plan()["cluster"] == 1
+    prob.replan(cluster=False)
+    xs = fos.fista_path(prob, None, alphas, max_iter=15, L=L)
+    assert prob.plan()["cluster"] == 0
+    fresh = fos.prepare(At, b)
+    fresh.replan(cluster=False)
+    _check_path(xs, refs, same_as=fos.fista_path(fresh, None, alphas, max_iter=15, L=L))
+
+
+def test_set_comm_after_a_lockstep_run(fos):
+    """A 6-weight path, then a one-rank communicator attached with set_comm: the lockstep layout is planned again with
+    the communicator in view (no one-read form, whose launch has no exchange step)."""
+    from fastoptsolver_amd import distributed as fd
+    At, b, alphas, L, refs = _six_weights(fos, 3000, 2048, 6)
+    comm = fd.Comm.solo()
+    prob = fos.prepare(At, b)
+    _check_path(fos.fista_path(prob, None, alphas, max_iter=15, L=L), refs)
+    xs = fos.fista_path(prob, None, alphas, max_iter=15, L=L, comm=comm)
+    assert prob.comm is comm
+    fresh = fos.prepare(At, b)
+    _check_path(xs, refs, same_as=fos.fista_path(fresh, None, alphas, max_iter=15, L=L, comm=comm))
+
+
+def test_set_comm_cols_after_an_fp64_pass(fos):
+    """A streaming plan runs fos_gemv_pair_dd on its fp64 geometry, then becomes the one block of a column-sharded problem
+    (one-rank communicator): the fp64 pass is planned again and takes the two-pass form with the residual exchange."""
+    from fastoptsolver_amd import distributed as fd
+    m, n = 600, 1024
+    rng = np.random.default_rng(23)
+    A = rng.standard_normal((m, n)).astype(np.float32)
+    b = rng.standard_normal(m).astype(np.float32)
+    x = rng.standard_normal(n) * (1.0 + 1e-9 * rng.standard_normal(n))
+    At, xd = torch.as_tensor(A).cuda(), _dev(x, torch.float64)
+    g_ref, rr_ref = orc.gram_gradient(A.astype(np.float64), x, b.astype(np.float64), 0.37)
+    comm = fd.Comm.solo()
+
+    def check(out, where):
+        got = out.cpu().numpy()
+        assert _data.rel(got[:n], g_ref) < 1e-12, where
+        assert got[n] == pytest.approx(rr_ref, rel=1e-12), where
+
+    prob = fos.prepare(At, b, pad=False)
+    assert (prob.plan()["path"], prob.plan()["tall"], prob.plan()["colblock"]) == (0, 0, 0)
+    check(_pair_dd(prob, xd), prob.plan())
+    prob.set_comm_cols(comm)
+    assert prob.plan()["colblock"] == 1
+    out = _pair_dd(prob, xd)
+    check(out, prob.plan())
+    fresh = fos.prepare(At, b, pad=False)
+    fresh.set_comm_cols(comm)
+    assert torch.equal(_pair_dd(fresh, xd), out)
 
 
 def test_distinct_handles_from_distinct_threads(fos):

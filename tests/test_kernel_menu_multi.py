@@ -108,8 +108,8 @@ def test_thresholds_match_the_source():
     split = re.findall(r"if\s*\(\s*n\s*<=\s*(\d+)\s*\)\s*return\s*\(\s*bblock\s*\?\s*(\w+)\s*:\s*(\w+)\s*\)", find)
     assert [(int(c), a, b) for c, a, b in split] == [(mm.VALU_CAP[256], "small_rhs", "small"), (mm.VALU_CAP[512], "big_rhs", "big")]
     assert re.search(r"const\s+int\s+variant\s*=\s*rows_total\s*>=\s*%d\s*\*\s*\(int64_t\)\s*p->ncu\s*\?\s*1\s*:\s*0" % mm.RB2_ROWS_PER_CU, tp)
-    assert re.search(r"const\s+int64_t\s+rows\s*=\s*%d\s*\*\s*\(int64_t\)\s*p->ncu\s*;\s*p->panel_rows\s*=\s*std::min<int64_t>\(rows,\s*\(p->m\s*\+\s*255\)\s*/\s*256\s*\*\s*256\)" % mm.PANEL_ROWS_PER_CU, tp)
-    assert re.search(r"p->dm_panel_rows\s*=\s*std::min<int64_t>\(%d\s*\*\s*\(int64_t\)\s*p->ncu,\s*\(p->m\s*\+\s*255\)\s*/\s*256\s*\*\s*256\)" % mm.PANEL_ROWS_PER_CU, tp)
+    assert re.search(r"const\s+int64_t\s+rows\s*=\s*%d\s*\*\s*\(int64_t\)\s*p->ncu\s*;\s*p->multi\.panel_rows\s*=\s*std::min<int64_t>\(rows,\s*\(p->m\s*\+\s*255\)\s*/\s*256\s*\*\s*256\)" % mm.PANEL_ROWS_PER_CU, tp)
+    assert re.search(r"p->dm\.panel_rows\s*=\s*std::min<int64_t>\(%d\s*\*\s*\(int64_t\)\s*p->ncu,\s*\(p->m\s*\+\s*255\)\s*/\s*256\s*\*\s*256\)" % mm.PANEL_ROWS_PER_CU, tp)
     assert re.search(r"cs_need\s*<=\s*2\s*\?\s*0\s*:\s*cs_need\s*<=\s*4\s*\?\s*4\s*:\s*cs_need\s*<=\s*8\s*\?\s*8\s*:\s*cs_need\s*<=\s*16\s*\?\s*16\s*:\s*0", tp)
     assert re.search(r"\(p->ncu\s*/\s*8\)\s*%\s*cs\s*==\s*0\s*&&\s*p->m\s*>=\s*\(int64_t\)\(p->ncu\s*/\s*cs\)\s*\*\s*fos::CP_ROWS\s*\*\s*"
                      + str(mm.CP_MIN_PANELS), tp)
