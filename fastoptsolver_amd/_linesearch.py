@@ -14,7 +14,9 @@ def _cubic_min(a, fa, da, c, fc, dc, clamp_sqrt=False):
     rad = (theta / scale) ** 2 - (da / scale) * (dc / scale)
     if clamp_sqrt:
         rad = max(0.0, rad)
-    return theta, scale * math.sqrt(rad)
+    # a negative radicand (values that no smooth function takes: an overflowed f next to finite ones) gives NaN, as
+    # std::sqrt does in the native search, instead of raising
+    return theta, scale * (math.sqrt(rad) if rad >= 0.0 else float("nan"))
 
 
 def next_trial(iv, stp, f, d):

@@ -111,7 +111,7 @@ int fos_vec_stats_dd(const double* x, const double* g, const double* d, int64_t 
 int fos_vec_axpby_dd(double a, const double* x, double b, const double* y, double* out, int64_t n, void* stream) {
   if (!x || !out || n <= 0 || (b != 0.0 && !y)) return fail(FOS_ERR_ARG, "fos_vec_axpby_dd: bad argument");
   hipLaunchKernelGGL(fos::vec_axpby_f64_kernel<double>, dim3(grid_1d(n, 256, 1024)), dim3(256), 0, (hipStream_t)stream, a,
-                     x, b, b != 0.0 ? y : nullptr, out, n);
+                     x, b, y, out, n);                // a given y takes part even when b == 0 (0 * inf is NaN, as in NumPy)
   LAUNCH_CHECK();
   return FOS_OK;
 }
@@ -207,8 +207,8 @@ int fos_lbfgs_minimize(fos_problem* p, double alpha2, int max_iter, double pgtol
     xnorm1 = w.host[4];
   };
   auto axpby = [&](double a, const double* xv, double b, const double* yv, double* out) {
-    hipLaunchKernelGGL(fos::vec_axpby_f64_kernel<double>, dim3(ax_grid), dim3(256), 0, st, a, xv, b, b != 0.0 ? yv : nullptr,
-                       out, n);
+    // y always takes part: with stp = 0 and an infinite d, NumPy's stp * d + x_old is NaN, not x_old (the search must see it)
+    hipLaunchKernelGGL(fos::vec_axpby_f64_kernel<double>, dim3(ax_grid), dim3(256), 0, st, a, xv, b, yv, out, n);
   };
   auto finish = [&](double f, double gmax, int nit, int task) -> int {
     res->f = f; res->gmax = gmax; res->nit = nit; res->nfev = nfev; res->task = task; res->reserved = 0;
@@ -290,7 +290,8 @@ int fos_lbfgs_minimize(fos_problem* p, double alpha2, int max_iter, double pgtol
       continue;
     }
     stp = stp_used;
-    if (hist) { hist[2 * nit] = f; hist[2 * nit + 1] = xnorm1; }
+    const bool recorded = nit < max_iter;      // max_iter = 0 still runs one iteration (as SciPy does): it is not recorded
+    if (hist && recorded) { hist[2 * nit] = f; hist[2 * nit + 1] = xnorm1; }
     {                                           // record the iterate; keep the pair only if its curvature is positive
       const double sy = (gd1 - gd0) * stp;
       const bool keep_pair = sy > EPS * (-gd0 * stp);
@@ -300,11 +301,12 @@ int fos_lbfgs_minimize(fos_problem* p, double alpha2, int max_iter, double pgtol
         if (hist_n == M) head = (head + 1) % M;
         else hist_n += 1;
       }
-      if (keep_pair || iterates) {
+      double* iter_out = (iterates && recorded) ? iterates + (size_t)nit * n : nullptr;
+      if (keep_pair || iter_out) {
         hipLaunchKernelGGL(fos::lbfgs_store_pair_kernel, dim3(ax_grid), dim3(256), 0, st, stp, (const double*)w.d,
                            (const double*)g, (const double*)g_old, keep_pair ? w.S + (size_t)slot * n : nullptr,
                            keep_pair ? w.Y + (size_t)slot * n : nullptr, (const double*)x,
-                           iterates ? iterates + (size_t)nit * n : nullptr, n);
+                           iter_out, n);
         LAUNCH_CHECK();
       }
     }

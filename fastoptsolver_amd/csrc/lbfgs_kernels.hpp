@@ -47,6 +47,18 @@ __device__ inline void block_sum_bcast(double (&v)[NV], double (*lds)[LB_THREADS
   for (int i = 0; i < NV; ++i) v[i] += dpp_fetch<0x140, 0xF>(v[i]);     // row_mirror
 }
 
+// a*b and a+b, each rounded once and never contracted into an fma.  (__dmul_rn / __dadd_rn are plain operators in HIP's
+// headers and hipcc contracts across them by default: the trial points x_old + stp*d were fma results, one rounding short
+// of NumPy's `stp * d + x_old`.  The pragma takes the `contract` flag off these two instructions, inlined or not.)
+__device__ __forceinline__ double mul_rn(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ double add_rn(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
 // Four consecutive elements of a float / double vector (16-byte aligned for float, 32-byte for double).
 __device__ inline void load4(const float* p, double (&o)[4]) {
   const f32x4 t = *reinterpret_cast<const f32x4*>(p);
@@ -420,7 +432,7 @@ __device__ __forceinline__ void lbfgs_combine_body(const double* __restrict__ g,
     if (x_step != nullptr) {
       const double xo = x_step[col];
       x_old[col] = xo;
-      x_step[col] = __dadd_rn(__dmul_rn(1.0, -acc), xo);
+      x_step[col] = add_rn(mul_rn(1.0, -acc), xo);
     }
   }
 }
@@ -434,8 +446,12 @@ static __global__ __launch_bounds__(VL_THREADS) void lbfgs_combine_kernel(const 
   lbfgs_combine_body(g, S, Y, hist, head, cap, n, partial, nparts, d_out, gd_out, x_step, x_old, blockIdx.x);
 }
 
-// out5 = { x.x, g.d, d.d, max|g|, ||x||_1 }; any pointer may be NULL (its entries are then 0).  XT: float or double
-// iterate.  With `extra` the scalar *extra rides along as out5[5] (the ||r||^2 of the evaluation: one host read for all).
+// max(a, b) of two non-negative numbers that keeps a NaN (fmax drops it: an all-NaN gradient then had max|g| = 0 and the
+// optimiser reported convergence).  For finite operands the result is fmax's, bit for bit.
+__device__ inline double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
+
+// out5 = { x.x, g.d, d.d, max|g|, ||x||_1 }; any pointer may be NULL (its entries are then 0); a NaN anywhere in g makes
+// max|g| NaN.  XT: float or double iterate.  With `extra` the scalar *extra rides along as out5[5] (the ||r||^2 of the evaluation: one host read for all).
 // The sums of vec_stats_kernel; thread 0 writes out5 (and out5[5] = *extra, out5[9] = t_now - *t_start when given).
 template <typename XT, typename GT>
 __device__ __forceinline__ void vec_stats_body(const XT* __restrict__ x, const GT* __restrict__ g, const GT* __restrict__ d,
@@ -449,17 +465,17 @@ __device__ __forceinline__ void vec_stats_body(const XT* __restrict__ x, const G
     x1 += fabs(xv);
     gd += gv * dv;
     dd += dv * dv;
-    gm = fmax(gm, fabs(gv));
+    gm = nan_max(gm, fabs(gv));
   }
   xx = wave_sum(xx); gd = wave_sum(gd); dd = wave_sum(dd); x1 = wave_sum(x1);
 #pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) gm = fmax(gm, __shfl_xor(gm, off, 64));
+  for (int off = 32; off >= 1; off >>= 1) gm = nan_max(gm, __shfl_xor(gm, off, 64));
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) { lds[0][wave] = xx; lds[1][wave] = gd; lds[2][wave] = dd; lds[3][wave] = gm; lds[4][wave] = x1; }
   __syncthreads();
   if (threadIdx.x == 0) {
     double a = 0.0, b = 0.0, c = 0.0, e = 0.0, f = 0.0;
-    for (int i = 0; i < 16; ++i) { a += lds[0][i]; b += lds[1][i]; c += lds[2][i]; e = fmax(e, lds[3][i]); f += lds[4][i]; }
+    for (int i = 0; i < 16; ++i) { a += lds[0][i]; b += lds[1][i]; c += lds[2][i]; e = nan_max(e, lds[3][i]); f += lds[4][i]; }
     out5[0] = a; out5[1] = b; out5[2] = c; out5[3] = e; out5[4] = f;
     if (extra != nullptr) out5[5] = *extra;
     if (t_start != nullptr) out5[9] = (double)(t_now - *t_start);
@@ -532,8 +548,8 @@ __global__ __launch_bounds__(256) void vec_axpby_f64_kernel(double a, const doub
                                                             const YT* __restrict__ y, double* __restrict__ out,
                                                             int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    double v = __dmul_rn(a, x[i]);
-    if (y != nullptr) v = __dadd_rn(__dmul_rn(b, (double)y[i]), v);
+    double v = mul_rn(a, x[i]);
+    if (y != nullptr) v = add_rn(mul_rn(b, (double)y[i]), v);
     out[i] = v;
   }
 }
@@ -544,7 +560,7 @@ static __global__ __launch_bounds__(256) void lbfgs_first_trial_kernel(double* _
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const double xo = x[i];
     x_old[i] = xo;
-    x[i] = __dadd_rn(__dmul_rn(stp, d[i]), xo);
+    x[i] = add_rn(mul_rn(stp, d[i]), xo);
   }
 }
 
@@ -558,8 +574,8 @@ static __global__ __launch_bounds__(256) void lbfgs_store_pair_kernel(double stp
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     if (iter_out != nullptr) iter_out[i] = x[i];
     if (s_out != nullptr) {
-      s_out[i] = __dmul_rn(stp, d[i]);
-      y_out[i] = __dadd_rn(g[i], -g_old[i]);
+      s_out[i] = mul_rn(stp, d[i]);
+      y_out[i] = add_rn(g[i], -g_old[i]);
     }
   }
 }
@@ -615,7 +631,7 @@ static __global__ __launch_bounds__(256) void lbfgs_first_trial_multi_kernel(LbM
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const double xo = x[i];
     x_old[i] = xo;
-    x[i] = __dadd_rn(__dmul_rn(stp, d[i]), xo);
+    x[i] = add_rn(mul_rn(stp, d[i]), xo);
   }
 }
 
@@ -627,8 +643,8 @@ static __global__ __launch_bounds__(256) void lbfgs_step_multi_kernel(LbMulti c,
   const double* __restrict__ d = c.d[v];
   const double stp = c.stp[v];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    double w = __dmul_rn(1.0, x_old[i]);
-    w = __dadd_rn(__dmul_rn(stp, d[i]), w);
+    double w = mul_rn(1.0, x_old[i]);
+    w = add_rn(mul_rn(stp, d[i]), w);
     x[i] = w;
   }
 }
@@ -643,8 +659,8 @@ static __global__ __launch_bounds__(256) void lbfgs_store_pair_multi_kernel(LbMu
   double* __restrict__ y_out = c.y_out[v];
   const double stp = c.stp[v];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    s_out[i] = __dmul_rn(stp, d[i]);
-    y_out[i] = __dadd_rn(g[i], -g_old[i]);
+    s_out[i] = mul_rn(stp, d[i]);
+    y_out[i] = add_rn(g[i], -g_old[i]);
   }
 }
 

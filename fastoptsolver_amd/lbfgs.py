@@ -25,6 +25,11 @@ _M, _FACTR, _MAXLS = 10, 1e7, 20
 _EPS = float(np.finfo(np.float64).eps)
 
 
+def _nan_max(values):
+    """max of the ranks' max|g| that keeps a NaN, as the statistics kernel does (Python's max drops or keeps it by position)."""
+    return float("nan") if any(v != v for v in values) else max(values)
+
+
 class _HipOps:
     """The device primitives of one fit: fp64 K2 pass, fp64 two-loop K4, fp64 n-vector kernels.  No CPU fallback."""
 
@@ -79,7 +84,7 @@ class _HipOps:
 
     def _axpby(self, a, x, b, y, out):
         with torch.cuda.device(self.dev):
-            _lib.check(self.lib.fos_vec_axpby_dd(float(a), _core.ptr(x), float(b), _core.ptr(y if b != 0.0 else None),
+            _lib.check(self.lib.fos_vec_axpby_dd(float(a), _core.ptr(x), float(b), _core.ptr(y),
                                                  _core.ptr(out), self.n, _core.stream_ptr()), "fos_vec_axpby_dd")
         return out
 
@@ -121,7 +126,7 @@ class _HipColOps(_HipOps):
             xc[4 + self.comm.rank] = s[3]                                   # max|g|: one slot per rank
             self.comm.allreduce(xc)
             h = xc.cpu().tolist()
-        return [h[0], h[1], h[2], max(h[4:]), h[3], float(self.rr.cpu())]
+        return [h[0], h[1], h[2], _nan_max(h[4:]), h[3], float(self.rr.cpu())]
 
     def direction(self, g, S, Y, hist, head):
         d = torch.empty(self.n, dtype=torch.float64, device=self.dev)
@@ -165,11 +170,13 @@ class LBFGSSolver:
         import ctypes as C
         prob, n = ops.prob, ops.n
         a2 = float(self.alpha2) if self.reg_type in ("ridge", "elasticnet") else 0.0   # lbfgs.py:49-51
-        max_iter = int(self.max_iter)
+        # max_iter = 0 runs one iteration, as SciPy's maxiter = 0 does: the same run as max_iter = 1.  The ABI records at
+        # most max_iter iterations, so the limit is passed as 1 and the buffers hold the iteration that runs.
+        max_iter = max(int(self.max_iter), 1)
         x = ops.new_x()                                                              # lbfgs.py:63
-        hist = (C.c_double * max(2 * max_iter, 1))()
+        hist = (C.c_double * (2 * max_iter))()
         keep = max_iter * n * 8 <= (1 << 30)                  # iterates_ (an extension) only while they fit 1 GiB
-        iterates = torch.empty(max(max_iter, 1), n, dtype=torch.float64, device=ops.dev) if keep else None
+        iterates = torch.empty(max_iter, n, dtype=torch.float64, device=ops.dev) if keep else None
         cap = 21 * max_iter + 2
         fg_ms = (C.c_float * cap)()
         res = _lib.LbfgsResult()
@@ -198,7 +205,7 @@ class LBFGSSolver:
             raise ValueError("b must have m rows")
         k, n = int(Bt.shape[1]), prob.n_dev
         a2 = float(self.alpha2) if self.reg_type in ("ridge", "elasticnet") else 0.0   # lbfgs.py:49-51
-        max_iter = int(self.max_iter)
+        max_iter = max(int(self.max_iter), 1)             # 0 runs one iteration, like 1 (see _fit_native)
         l1 = self.reg_type in ("lasso", "elasticnet")
         X = torch.zeros(k, n, dtype=torch.float64, device=prob.device)        # row j: the iterate of column j
         nit, nfev = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int64)
@@ -216,7 +223,7 @@ class LBFGSSolver:
             if nv >= self._LOCKSTEP_MIN:
                 Bg = Bt[:, g0:g1].contiguous()
                 hstride = 2 * max_iter
-                hist = (C.c_double * max(nv * hstride, 1))()
+                hist = (C.c_double * (nv * hstride))()
                 cap = 22 * max_iter + 64
                 round_ms = (C.c_float * cap)()
                 rounds = C.c_int(0)

@@ -375,7 +375,8 @@ float* fos_fista_gbuf(fos_fista* f);     /* device pointer to gbuf (n+1 floats),
  * slot (head + i) % cap holds the i-th oldest pair.  One launch. */
 int fos_lbfgs_two_loop(const float* g, const float* S, const float* Y, int hist, int head, int cap, int64_t n,
                        float* d_out, void* stream);
-/* out5 (device doubles) = { x.x, g.d, d.d, max|g|, ||x||_1 } in one launch; x, g, d may each be NULL. */
+/* out5 (device doubles) = { x.x, g.d, d.d, max|g|, ||x||_1 } in one launch; x, g, d may each be NULL.  A NaN in g makes
+ * max|g| NaN (so that "max|g| <= pgtol" fails on it), in every form of this function. */
 int fos_vec_stats(const float* x, const float* g, const float* d, int64_t n, double* out5, void* stream);
 /* out = a*x + b*y (y may be NULL when b == 0). */
 int fos_vec_axpby(double a, const float* x, double b, const float* y, float* out, int64_t n, void* stream);
@@ -404,7 +405,8 @@ int fos_lbfgs_direction_dd(const double* g, const double* S, const double* Y, in
                            double* d_out, double* gd_out, double* work, int64_t work_doubles, void* stream);
 int fos_vec_stats_dd(const double* x, const double* g, const double* d, int64_t n, double* out5, void* stream);
 /* out = a*x + b*y with the two products and the sum rounded separately (no fma contraction): bit for bit NumPy's
- * `stp * d + x_old`, `g - g_old`, `stp * d` (oracle lbfgs_minimize). */
+ * `stp * d + x_old`, `g - g_old`, `stp * d` (oracle lbfgs_minimize).  y may be NULL when b == 0 (out = a*x); a y that is
+ * given takes part whatever b is (0 * inf is NaN, as in NumPy). */
 int fos_vec_axpby_dd(double a, const double* x, double b, const double* y, double* out, int64_t n, void* stream);
 
 /* ---- the optimiser itself: what scipy.optimize.fmin_l_bfgs_b is to lbfgs.py:64 --------------------------------------
@@ -432,6 +434,8 @@ double fos_linesearch_step(fos_linesearch* ls, double stp, double f, double d);
  *   hist      host, 2*max_iter doubles (nullable): after iteration k, hist[2k] = loss of fg at x_k, hist[2k+1] = ||x_k||_1
  *             (the callback's compute_objective(x_k) = loss + alpha1*||x_k||_1 without an extra pass)   lbfgs.py:56-61
  *   iterates  device, max_iter*n doubles (nullable): x_k after every iteration
+ *             max_iter = 0 still runs ONE iteration (SciPy's maxiter = 0 does: nit = 1, task 2); it is not recorded - nothing
+ *             is ever written beyond 2*max_iter doubles of hist or max_iter*n doubles of iterates
  *   fg_ms     host, fg_cap floats (nullable): device milliseconds of every fg evaluation (get_metrics)
  * task: 0 |proj g| <= pgtol, 1 relative reduction of f <= factr*epsmch, 2 iteration limit, 3 abnormal termination in
  * the line search.  Works on sharded problems (fos_problem_set_comm).  Synchronises. */
@@ -458,7 +462,8 @@ int fos_gemv_pair_dd_multi(fos_problem* p, const double* X, int nv, int64_t ldx,
  * unfinished fits take their next evaluation in ONE fos_gemv_pair_dd_multi pass (a round), so A is read about
  * max_j nfev_j times instead of sum_j nfev_j.  One host round trip per round (plus one in the first iteration).
  *   X         device, n x nv doubles, column j at X + j*ldx (ldx >= n): start points in, solutions out
- *   hist      host, nv x 2*max_iter doubles (nullable): fit j's pairs (loss, ||x||_1) at hist + j*2*max_iter
+ *   hist      host, nv x 2*max_iter doubles (nullable): fit j's pairs (loss, ||x||_1) at hist + j*2*max_iter (max_iter = 0:
+ *             one iteration runs, nothing is recorded)
  *   round_ms  host, round_cap floats (nullable): device milliseconds of every round's pass
  *   rounds    host (nullable): number of rounds (passes over A) of the call
  *   res       host, nv results

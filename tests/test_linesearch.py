@@ -80,3 +80,92 @@ def test_native_line_search_equals_the_python_one():
     st = _lib.LineSearchState()
     lib.fos_linesearch_begin(C.byref(st), 1.0, 1.0, 0.5)
     assert st.status == _lib.LS_ERROR
+
+
+# ---- non-finite values of f and f' -------------------------------------------------------------------------------------
+# What the drivers meet on data with a NaN or an Inf in it: the optimiser then lives on the search's answers alone (20
+# evaluations at most, MAXLS), so the three restatements must give the same steps and the same status on them too.
+_NAN, _INF = float("nan"), float("inf")
+_SPOILED = [(_NAN, _NAN), (_INF, _NAN), (_INF, _INF), (_INF, -_INF), (_NAN, 1.0), (_NAN, -1.0), (1.0, _NAN), (-_INF, -1.0),
+            (_INF, 1.0), (_INF, -1.0)]
+
+
+def _same(a, b):
+    return (a != a and b != b) or a == b
+
+
+def _scripted(begin, step, status, stp0, f0, d0, phi, dphi, after, bad, sticky):
+    """Steps of a search whose evaluation number `after` (and every later one when `sticky`) returns `bad`."""
+    stp = begin(stp0, f0, d0)
+    seq = [stp]
+    if status() != "FG":
+        return seq, status()
+    for k in range(20):
+        f, d = (bad if (k == after or (sticky and k > after)) else (float(phi(stp)), float(dphi(stp))))
+        try:
+            stp = step(stp, f, d)
+        except ValueError:                # the oracle's math.sqrt refuses a negative radicand: compared up to here
+            return seq, "RAISED"
+        seq.append(stp)
+        if status() != "FG":
+            break
+    return seq, status()
+
+
+def _three_ways(stp0, f0, d0, phi, dphi, after, bad, sticky):
+    import ctypes as C
+    from fastoptsolver_amd import _lib
+    lib = _lib.load()
+    names = {_lib.LS_FG: "FG", _lib.LS_CONVERGENCE: "CONVERGENCE", _lib.LS_WARNING: "WARNING", _lib.LS_ERROR: "ERROR"}
+    ls = LineSearch()
+    ls.status = "FG"
+    py = _scripted(ls.begin, ls.step, lambda: ls.status, stp0, f0, d0, phi, dphi, after, bad, sticky)
+    mt = orc.MoreThuente()
+    ref = _scripted(mt.start, mt.advance, lambda: "FG" if mt.task in ("START", "FG") else mt.task, stp0, f0, d0, phi, dphi, after, bad, sticky)
+    st = _lib.LineSearchState()
+    cc = _scripted(lambda s, f, d: lib.fos_linesearch_begin(C.byref(st), s, f, d),
+                   lambda s, f, d: lib.fos_linesearch_step(C.byref(st), s, f, d), lambda: names[st.status], stp0, f0, d0, phi,
+                   dphi, after, bad, sticky)
+    return py, ref, cc
+
+
+def test_non_finite_values_give_the_same_steps_in_all_three_searches():
+    rng = np.random.default_rng(7)
+    checked = raised = 0
+    for trial in range(60):
+        phi, dphi = _functions(rng)
+        if dphi(0.0) >= 0:
+            continue
+        stp0 = float(rng.choice([1.0, 0.01, 25.0]))
+        for after in (0, 1, 2):
+            for bad in _SPOILED:
+                for sticky in (False, True):
+                    py, ref, cc = _three_ways(stp0, float(phi(0.0)), float(dphi(0.0)), phi, dphi, after, bad, sticky)
+                    where = (trial, after, bad, sticky, py, ref, cc)
+                    assert len(py[0]) == len(cc[0]) and py[1] != "RAISED", where
+                    assert all(_same(a, b) for a, b in zip(py[0], cc[0])), where             # bit for bit
+                    assert py[1].startswith(cc[1]), where
+                    assert all(_same(a, b) or a == pytest.approx(b, rel=1e-14) for a, b in zip(py[0], ref[0])), where
+                    checked += 1
+                    if ref[1] == "RAISED":          # values no function takes (an Inf between finite ones): a prefix only
+                        assert len(ref[0]) <= len(py[0]) and py[0][len(ref[0])] != py[0][len(ref[0])], where
+                        raised += 1
+                        continue
+                    assert len(py[0]) == len(ref[0]) and ref[1].startswith(py[1].split(":")[0]), where
+    assert checked > 1000 and raised < checked // 10, (checked, raised)
+
+
+def test_non_finite_start_values():
+    """f(0), f'(0) and the first step as a fit on spoiled data hands them over: an all-NaN gradient gives f'(0) = NaN and a
+    first step 1/||d|| = NaN, an infinite one f'(0) = -Inf and a first step of 0."""
+    phi, dphi = (lambda t: _NAN), (lambda t: _NAN)
+    for stp0, f0, d0 in ((_NAN, _NAN, _NAN), (0.0, _INF, -_INF), (_NAN, 1.0, _NAN), (1.0, _NAN, -1.0), (1.0, _INF, -1.0),
+                         (1e10, 1.0, -_INF), (1.0, 1.0, _INF)):
+        py, ref, cc = _three_ways(stp0, f0, d0, phi, dphi, 99, (_NAN, _NAN), False)
+        where = (stp0, f0, d0, py, ref, cc)
+        assert len(py[0]) == len(ref[0]) == len(cc[0]), where
+        assert all(_same(a, b) for a, b in zip(py[0], cc[0])) and all(_same(a, b) for a, b in zip(py[0], ref[0])), where
+        assert ref[1].startswith(py[1].split(":")[0]) and py[1].startswith(cc[1]), where
+    # the search never ends by itself on NaN values: the drivers' limit of 20 evaluations is what ends it
+    py, ref, cc = _three_ways(_NAN, _NAN, _NAN, phi, dphi, 99, (_NAN, _NAN), False)
+    assert py[1] == ref[1] == cc[1] == "FG" and len(py[0]) == 21
