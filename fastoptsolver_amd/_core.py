@@ -323,6 +323,20 @@ class Problem:
             return None
         return self.scratch[:nv].cpu().tolist()
 
+    def residual_batch_folds(self, X, fold_ids, held):
+        """Held-out squared errors: sum over the rows i with fold_ids[i] == held[j] of (A_i . X_j - b_i)^2 for the nv <= 16
+        columns of X (n x nv) in one MFMA pass (fos_residual_batch_folds); fold_ids: `fold_ids_tensor`, held: nv ints
+        (-1: no row).  Host list, or None where the shape has no such pass.  Synchronises."""
+        X = torch.as_tensor(X, device=self.device, dtype=torch.float32)
+        nv = X.shape[1]
+        Xf = torch.zeros(self.n_dev, 16, dtype=torch.float32, device=self.device)
+        Xf[: X.shape[0], :nv] = X
+        with self.ctx():
+            rc = self.lib.fos_residual_batch_folds(self.h, ptr(Xf), nv, ptr(fold_ids), (C.c_int32 * nv)(*held), ptr(self.scratch))
+        if not _lib.served(rc, "fos_residual_batch_folds"):
+            return None
+        return self.scratch[:nv].cpu().tolist()
+
     def power_iter(self, v0, n_iter=100, tol=1e-6):
         v = self.vec_in(v0).clone()
         L = C.c_double()
@@ -570,6 +584,27 @@ def run_multi_rhs(handles, B, iters):
     with handles[0].prob.ctx():
         rc = lib.fos_fista_run_multi_rhs(arr, len(handles), ptr(B), int(B.stride(0)), int(iters))
     return _lib.served(rc, "fos_fista_run_multi_rhs")
+
+
+def fold_ids_tensor(ids, device):
+    """The fold id of every row (0..254) as the uint8 device tensor the fold kernels read: padded with zeros to a multiple of
+    4 entries (they fetch the ids of 4 rows with one 32-bit load; the allocation is aligned far beyond 4 bytes)."""
+    ids = np.ascontiguousarray(np.asarray(ids), dtype=np.uint8)
+    out = torch.zeros((ids.shape[0] + 3) // 4 * 4, dtype=torch.uint8, device=device)
+    out[: ids.shape[0]] = torch.from_numpy(ids).to(device)
+    return out
+
+
+def run_multi_folds(handles, fold_ids, held, iters):
+    """Advance up to 16 Fista handles of one Problem in lockstep, handle v fitting the rows whose fold id differs from held[v]
+    (-1: all rows) (fos_fista_run_multi_folds); fold_ids: `fold_ids_tensor`.  Returns False when this shape / configuration
+    is not served (callers then gather the rows fold by fold)."""
+    lib = handles[0].lib
+    nv = len(handles)
+    arr = (C.c_void_p * nv)(*[h.h for h in handles])
+    with handles[0].prob.ctx():
+        rc = lib.fos_fista_run_multi_folds(arr, nv, int(iters), ptr(fold_ids), (C.c_int32 * nv)(*held))
+    return _lib.served(rc, "fos_fista_run_multi_folds")
 
 
 # ---- batches of small problems (fos_fista_run_batch / fos_power_iter_batch) -------------------------------------------

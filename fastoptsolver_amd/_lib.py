@@ -84,6 +84,7 @@ SIGNATURES = {
     "fos_residual_objective": (_i32, [_vp, _vp, _vp]),
     "fos_residual_batch": (_i32, [_vp, _vp, _i32, _i32, _vp]),
     "fos_residual_batch_rhs": (_i32, [_vp, _vp, _i32, _vp, _i64, _vp]),
+    "fos_residual_batch_folds": (_i32, [_vp, _vp, _i32, _vp, C.POINTER(_i32), _vp]),
     "fos_power_iter": (_i32, [_vp, _vp, _i32, _f64, C.POINTER(_f64), C.POINTER(_i32)]),
     "fos_prox_l1": (_i32, [_vp, _f32, _vp, _i64, _vp]),
     "fos_prox_l1_vec": (_i32, [_vp, _vp, _vp, _i64, _vp]),
@@ -101,6 +102,7 @@ SIGNATURES = {
     "fos_fista_run_resident": (_i32, [_vp, _i32, _i32, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fos_fista_run_multi": (_i32, [C.POINTER(_vp), _i32, _i32]),
     "fos_fista_run_multi_rhs": (_i32, [C.POINTER(_vp), _i32, _vp, _i64, _i32]),
+    "fos_fista_run_multi_folds": (_i32, [C.POINTER(_vp), _i32, _i32, _vp, C.POINTER(_i32)]),
     "fos_fista_run_fused": (_i32, [_vp, _i32]),
     "fos_fista_grad": (_i32, [_vp]),
     "fos_fista_grad_dual": (_i32, [_vp]),

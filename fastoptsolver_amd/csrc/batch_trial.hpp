@@ -97,13 +97,50 @@ static __global__ __launch_bounds__(256) void fista_trial_batch_kernel(GradSrc g
         (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
+// Fold mode of product 1's epilogue (K-fold cross-validation in lockstep, fos_fista_run_multi_folds): every row carries a
+// fold id, every candidate column the id of the fold it holds out.  TRAIN zeroes column j's residual on the rows of its
+// held-out fold (the column fits the other rows: product 2 and the updates see a masked R and need not know), HELD zeroes
+// it everywhere else (q_part is the held-out squared error).  The mask sits before qsum and before the rout store.
+constexpr int FOLD_OFF = 0, FOLD_TRAIN = 1, FOLD_HELD = 2;
+// The 16 held-out fold ids, by value.  Row ids are 0..254; -1 (the byte 255) matches no row: a TRAIN column keeps every
+// row, a HELD column none.
+struct alignas(4) FoldHeld { int8_t id[BT_NV]; };
+// The held id of candidate j as the unsigned byte the row ids are compared with (constant indices only: the struct stays
+// in scalar registers).
+__device__ __forceinline__ unsigned fold_held_of(const FoldHeld& h, int j) {
+  unsigned w[4];
+  __builtin_memcpy(w, &h, sizeof(w));
+  const int q = j >> 2;
+  const unsigned ws = q == 0 ? w[0] : q == 1 ? w[1] : q == 2 ? w[2] : w[3];
+  return (ws >> (8 * (j & 3))) & 0xffu;
+}
+// A lane's 4 consecutive rows start at a multiple of 4: one aligned 32-bit load fetches their fold ids (fold_of_row is
+// 4-byte aligned and readable up to m rounded up to 4).  Row r of the group is byte r.  A group past the last row (its
+// rows are skipped) reads the last group's ids: the load stays unconditional and in bounds.
+__device__ __forceinline__ unsigned fold_ids_of(const uint8_t* __restrict__ fold_of_row, int64_t row0, int64_t m) {
+  const int64_t last = (m - 1) & ~(int64_t)3;
+  return *reinterpret_cast<const uint32_t*>(fold_of_row + (row0 < m ? row0 : last));
+}
+// The ids have arrived before the epilogue ends, also for a lane none of whose rows exist (it never reads them): without
+// this the load is still pending where the tile loop resumes and the compiler drains every tile in flight there
+// (a full vmcnt(0) in the steady state instead of the counted one).
+__device__ __forceinline__ void fold_ids_settle(unsigned ids4) { asm volatile("" ::"v"(ids4)); }
+template <int FOLD>
+__device__ __forceinline__ float fold_mask(float v, unsigned ids4, int r, unsigned held) {
+  if constexpr (FOLD == FOLD_OFF) return v;
+  const bool is_held = ((ids4 >> (8 * r)) & 0xffu) == held;
+  return (FOLD == FOLD_TRAIN ? is_held : !is_held) ? 0.f : v;
+}
+
 // q_part[wg][j] = sum over this workgroup's rows of (A_i . X_j - use_b * b_i)^2.
 // Requirements (host-checked): n % 4 == 0, lda % 4 == 0, A 16-byte aligned, Xp zero-padded to n_pad = 64*ceil(n/64).
 // STORE_R = true (multi-lambda gradient, gram_batch.hpp): the residuals themselves, rout[row][16 candidates] fp32,
 // are kept for the second product G = A^T R.
 // BBLOCK = true (several right-hand sides): b is the m x 16 block B16 and column j subtracts its own B16[row][j] - 16
 // lanes read one contiguous 64-byte row, the pattern of the rout store beside it.
-template <int RB, bool STORE_R = false, bool BBLOCK = false>
+// FOLD (FOLD_TRAIN / FOLD_HELD): the epilogue masks v by fold_of_row[row] (indexed by the row within the launch) against
+// held.id[candidate], see above; the tile loop is the same.
+template <int RB, bool STORE_R = false, bool BBLOCK = false, int FOLD = FOLD_OFF>
 __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const float* __restrict__ A, int64_t lda,
                                                                         const float* __restrict__ b, int use_b,
                                                                         int64_t m, int n,
@@ -111,7 +148,9 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const f
                                                                         int64_t groups_per_wg,
                                                                         double* __restrict__ q_part,
                                                                         float* __restrict__ rout = nullptr,
-                                                                        const int* __restrict__ stopped = nullptr) {
+                                                                        const int* __restrict__ stopped = nullptr,
+                                                                        const uint8_t* __restrict__ fold_of_row = nullptr,
+                                                                        FoldHeld held = FoldHeld{}) {
   if (stopped != nullptr && *stopped != 0) return;          // parked pipeline (solver stopped / line search stalled)
   constexpr int ROWS = BT_ROWS * RB;              // RB 16-row blocks per wave share each candidate fragment read
   constexpr int A_LOADS = BT_A_LOADS * RB;
@@ -163,6 +202,7 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const f
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) { acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f}; acc_odd[rb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
   double qsum = 0.0;                              // this lane's candidate j = lane & 15, its 4 rows per row block
+  const unsigned held_id = FOLD != FOLD_OFF ? fold_held_of(held, lane & 15) : 0u;
   auto compute_tile = [&](int buf, int64_t t) {
 #pragma unroll
     for (int sub = 0; sub < BT_COLS / 16; ++sub) {
@@ -183,6 +223,8 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const f
       for (int rb = 0; rb < RB; ++rb) {
         acc[rb] += acc_odd[rb];
         const int64_t row0 = (g_lo + t / ktiles) * ROWS + 16 * (wave * RB + rb) + 4 * (lane >> 4);
+        unsigned ids4 = 0u;
+        if constexpr (FOLD != FOLD_OFF) ids4 = fold_ids_of(fold_of_row, row0, m);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int64_t row = row0 + r;
@@ -193,10 +235,12 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const f
             } else {
               if (use_b) v -= b[row];
             }
+            v = fold_mask<FOLD>(v, ids4, r, held_id);
             qsum += (double)v * (double)v;
             if constexpr (STORE_R) rout[row * BT_NV + (lane & 15)] = v;      // 16 lanes: one 64-byte row of R
           }
         }
+        if constexpr (FOLD != FOLD_OFF) fold_ids_settle(ids4);
         acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
         acc_odd[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
@@ -338,12 +382,13 @@ static __global__ void xq_pack_kernel(const float* __restrict__ X, int n, int n_
 // RB = 16-row blocks per wave (the candidate fragments read from LDS are reused for RB row blocks: X is 96 bytes per
 // column against 32 bytes of A per row block, so LDS traffic per byte of A falls with RB); COLS = bf16 columns per tile.
 // Requirements: n % 8 == 0, lda % 8 == 0, A 16-byte aligned, Xq zero-padded to n_pad (a multiple of 128).
-// BBLOCK: b is the m x 16 right-hand-side block, as in residual_batch_mfma_kernel.
-template <int RB, int COLS, bool STORE_R = false, bool BBLOCK = false>
+// BBLOCK: b is the m x 16 right-hand-side block, FOLD: the fold mask of the epilogue, both as in residual_batch_mfma_kernel.
+template <int RB, int COLS, bool STORE_R = false, bool BBLOCK = false, int FOLD = FOLD_OFF>
 __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_bf16_kernel(
     const bf16_t* __restrict__ A, int64_t lda, const float* __restrict__ b, int use_b, int64_t m, int n,
     const unsigned short* __restrict__ xq, int64_t groups_per_wg, double* __restrict__ q_part,
-    float* __restrict__ rout = nullptr, const int* __restrict__ stopped = nullptr) {
+    float* __restrict__ rout = nullptr, const int* __restrict__ stopped = nullptr,
+    const uint8_t* __restrict__ fold_of_row = nullptr, FoldHeld held = FoldHeld{}) {
   if (stopped != nullptr && *stopped != 0) return;
   constexpr int ROWS = 64 * RB;
   constexpr int STRIDE = COLS + 8;
@@ -402,6 +447,7 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_bf16_kernel(
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) { acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f}; acc_odd[rb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
   double qsum = 0.0;
+  const unsigned held_id = FOLD != FOLD_OFF ? fold_held_of(held, lane & 15) : 0u;
   auto compute_tile = [&](int buf, int64_t t) {
 #pragma unroll
     for (int ks = 0; ks < COLS / 32; ++ks) {
@@ -423,6 +469,8 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_bf16_kernel(
       for (int rb = 0; rb < RB; ++rb) {
         acc[rb] += acc_odd[rb];
         const int64_t row0 = (g_lo + t / ktiles) * ROWS + 16 * (wave * RB + rb) + 4 * (lane >> 4);
+        unsigned ids4 = 0u;
+        if constexpr (FOLD != FOLD_OFF) ids4 = fold_ids_of(fold_of_row, row0, m);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int64_t row = row0 + r;
@@ -433,10 +481,12 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_bf16_kernel(
             } else {
               if (use_b) v -= b[row];
             }
+            v = fold_mask<FOLD>(v, ids4, r, held_id);
             qsum += (double)v * (double)v;
             if constexpr (STORE_R) rout[row * BT_NV + (lane & 15)] = v;
           }
         }
+        if constexpr (FOLD != FOLD_OFF) fold_ids_settle(ids4);
         acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
         acc_odd[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
       }

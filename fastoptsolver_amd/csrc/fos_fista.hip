@@ -670,8 +670,12 @@ static fos::MultiUpdate multi_update(fos_fista* const* fs, int nv, bool controll
 // same_family: the state machines differ in weights and steps only (a regularisation path does) - one update launch for all.
 // b16 (several right-hand sides, unsharded): product 1 subtracts column j of this m x 16 block from candidate column j
 // instead of the problem's b; always the two-product form (the planner's cluster layout, if any, is left as it is).
+// fold_of_row / held (K-fold cross-validation, unsharded, the problem's own b): product 1 zeroes column j's residual on the
+// rows of the fold it holds out (batch_trial.hpp FOLD_TRAIN), so state machine j fits the other rows; the two-product form
+// likewise.  Product 2 and the updates see a masked R and are the same launches.
 static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controlled, bool same_family,
-                          const float* b16 = nullptr) {
+                          const float* b16 = nullptr, const uint8_t* fold_of_row = nullptr,
+                          const fos::FoldHeld* held = nullptr) {
   fos_problem* p = fs[0]->p;
   const bool cols = p->col_sharded;
   if (cols && !controlled) return fail(FOS_ERR_STATE, "run_multi_mfma: a column-sharded lockstep is device-controlled");
@@ -684,13 +688,14 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
   const int y_mode = is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP;
   // row splits of product 2: the planned ones, or - a B-block run on a problem planned for the cluster form, whose slab
   // count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated
-  bool use_cluster = p->multi.cp_cs && !b16;
+  const bool two_products = b16 || fold_of_row;
+  bool use_cluster = p->multi.cp_cs && !two_products;
   int g_splits = p->multi.gram_splits;
-  if (p->multi.cp_cs && b16) {
+  if (p->multi.cp_cs && two_products) {
     g_splits = (int)((p->multi.panel_rows + p->multi.gram_rows_per_split - 1) / p->multi.gram_rows_per_split);
     if (g_splits > p->multi.gram_splits)
-      return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs: the cluster layout of this problem has too few slabs "
-                                       "for the two-product form");
+      return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs / _folds: the cluster layout of this problem has too few "
+                                       "slabs for the two-product form");
   }
   // candidate block: zero everywhere (padding columns, unused slots), then y_k of every state machine
   const size_t per_entry = is_bf16 ? 3 * sizeof(unsigned short) : sizeof(float);
@@ -739,7 +744,11 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
       int nwg1 = 0;
       // column-sharded: b enters the sum over the ranks once (rank 0); R = sum_p A_p Y_p - b is the ONE exchange per panel
       const float* bp = b16 ? b16 + row0 * fos::BT_NV : (p->b && !(cols && p->comm->rank != 0)) ? p->b + row0 : nullptr;
-      if ((rc = launch_batch_product(p, Ap, bp, rows, 1, p->multi.rbuf16, &nwg1, nullptr, b16 != nullptr))) return rc;
+      if (fold_of_row)               // the ids are offset with the panel as b is (panel rows are a multiple of 256)
+        rc = launch_batch_product_folds(p, Ap, p->b + row0, rows, p->multi.rbuf16, &nwg1, fold_of_row + row0, *held);
+      else
+        rc = launch_batch_product(p, Ap, bp, rows, 1, p->multi.rbuf16, &nwg1, nullptr, b16 != nullptr);
+      if (rc) return rc;
       if (cols && (rc = reduce_across(p, p->multi.rbuf16, (size_t)rows * fos::BT_NV, false))) return rc;
       const dim3 grid((unsigned)strips, (unsigned)g_splits);
 #define FOS_GRAM(T, ACC)                                                                                                  \
@@ -902,6 +911,36 @@ int fos_fista_run_multi_rhs(fos_fista* const* fs, int nv, const float* B, int64_
   for (int v = 0; v < nv; ++v)
     if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi_rhs: handles must share one problem");
   return run_multi(fs, nv, iters, B, ldb);
+}
+
+int fos_fista_run_multi_folds(fos_fista* const* fs, int nv, int iters, const uint8_t* fold_of_row, const int32_t* held) {
+  fos::FoldHeld hb{};
+  if (!fs || !fold_of_row || !held || nv < 1 || nv > fos::BT_NV || iters < 0 || ((uintptr_t)fold_of_row & 3) != 0 ||
+      !fold_held_block(held, nv, &hb))
+    return fail(FOS_ERR_ARG, "fos_fista_run_multi_folds: bad argument (null pointer, nv outside 1..16, iters < 0, fold_of_row "
+                             "not 4-byte aligned or a held id outside -1..254)");
+  for (int v = 0; v < nv; ++v)
+    if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi_folds: handles must share one problem");
+  fos_problem* p = fs[0]->p;
+  if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the problem has no b of its own");
+  if (p->comm || p->col_sharded)
+    return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: row- or column-sharded problems are not served");
+  if (!pair_dd_multi_supported(p))
+    return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the shape has no matrix-core pair");
+  bool all_plain = true, same_family = true;
+  for (int v = 0; v < nv; ++v) {
+    if (fs[v]->prm.tol_grad != 0.0 || fs[v]->precise || fs[v]->prm.tau_from_state)
+      return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: no gradient-norm rule, fp64 split gradient or device-held step");
+    all_plain = all_plain && plain_run(fs[v]);
+    const fos::FistaParams &a = fs[0]->prm, &c = fs[v]->prm;
+    same_family = same_family && a.mode == c.mode && a.prox_kind == c.prox_kind && a.delta == c.delta;
+  }
+  // device control (adaptive restart, step / ratio stops) is one update launch for all state machines: one family
+  if (!all_plain && !same_family)
+    return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: a device-controlled lockstep serves one family");
+  if (iters == 0) return FOS_OK;
+  // always the two matrix-core products, for any number of state machines: the alternative is a copy of A per fold
+  return run_multi_mfma(fs, nv, iters, !all_plain, same_family, nullptr, fold_of_row, &hb);
 }
 
 int fos_fista_grad(fos_fista* f) {

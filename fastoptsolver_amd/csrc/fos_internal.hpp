@@ -382,6 +382,14 @@ int launch_slab_reduce(fos_problem* p, int n_rr, float* gbuf, double* rr_out, co
 // (bblock: b is the rows x 16 right-hand-side block, column j subtracts its own b[row * 16 + j])
 int launch_batch_product(fos_problem* p, const void* A, const float* b, int64_t rows_total, int use_b, float* rout, int* nwg_out,
                          const int* stopped = nullptr, bool bblock = false);
+// held (HOST, nv entries, each -1..254) -> the by-value block of the fold kernels, the slots beyond nv set to -1 (in either
+// mode such a column is all zero: its candidate is).  False when an entry is out of range.
+bool fold_held_block(const int32_t* held, int nv, fos::FoldHeld* out);
+// Product 1 with the fold mask of K-fold cross-validation (batch_trial.hpp FOLD_TRAIN / FOLD_HELD) on `rows` rows starting at
+// A / b / fold_of_row; geometry and outputs as launch_batch_product.  rout given: the train-store form (R zero on every
+// column's held-out rows); rout null: the held-out residual form (q_part = held-out squared errors).
+int launch_batch_product_folds(fos_problem* p, const void* A, const float* b, int64_t rows_total, float* rout, int* nwg_out,
+                               const uint8_t* fold_of_row, const fos::FoldHeld& held);
 // q[j] = ||A Xp_j - use_b*b||^2 -> out16 (device); Xp already in p->xp.  b16 (unsharded only): subtract its column j instead
 int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* stopped = nullptr, const float* b16 = nullptr);
 int launch_cluster_pass(fos_problem* p);

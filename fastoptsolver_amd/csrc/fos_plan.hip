@@ -582,7 +582,7 @@ int ensure_batch_workspace(fos_problem* p) {
 // <4,64> 170.4 us.  The 128-row tile halves the LDS re-reads of the candidate fragments per byte of A; the 64-row
 // tile is kept for short problems, where it gives twice as many workgroups.
 typedef void (*Bf16Batch)(const fos::bf16_t*, int64_t, const float*, int, int64_t, int, const unsigned short*, int64_t, double*,
-                          float*, const int*);
+                          float*, const int*, const uint8_t*, fos::FoldHeld);
 // fn_store: also keeps R (gram_batch.hpp); fn_rhs / fn_store_rhs: the same with a right-hand side per column (B16 block)
 struct Bf16BatchVariant { Bf16Batch fn, fn_store; int rows; int wg_per_cu; Bf16Batch fn_rhs, fn_store_rhs; };
 const Bf16BatchVariant kBf16Batch[] = {
@@ -593,7 +593,7 @@ const Bf16BatchVariant kBf16Batch[] = {
 };
 
 typedef void (*F32Batch)(const float*, int64_t, const float*, int, int64_t, int, const float*, int64_t, double*, float*,
-                         const int*);
+                         const int*, const uint8_t*, fos::FoldHeld);
 struct F32BatchVariant { F32Batch fn, fn_store; int rows; int wg_per_cu; F32Batch fn_rhs, fn_store_rhs; };
 // fp32, measured at 65536 x 8192: <1> 64-row tile 368-395 us, <2> 128-row tile 335.7 us (80 % of HBM), <4> 336.8 us.
 const F32BatchVariant kF32Batch[] = {
@@ -603,10 +603,25 @@ const F32BatchVariant kF32Batch[] = {
      fos::residual_batch_mfma_kernel<2, false, true>, fos::residual_batch_mfma_kernel<2, true, true>},
 };
 
-// Product 1 on `rows` rows starting at A / b: q_part[wg][16] partial squared norms, rout (nullable): the residuals.
-// Returns the number of workgroups (rows of q_part).
-int launch_batch_product(fos_problem* p, const void* A, const float* b, int64_t rows_total, int use_b, float* rout, int* nwg_out,
-                         const int* stopped, bool bblock) {
+// The fold forms of product 1 (K-fold cross-validation in lockstep), one entry per tile variant of the tables above:
+// store_train keeps R with every column zero on its held-out rows, resid_held sums the held-out squared errors.
+struct Bf16FoldVariant { Bf16Batch store_train, resid_held; };
+const Bf16FoldVariant kBf16Folds[] = {
+    {fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_TRAIN>,
+     fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_HELD>},
+    {fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_TRAIN>,
+     fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_HELD>},
+};
+struct F32FoldVariant { F32Batch store_train, resid_held; };
+const F32FoldVariant kF32Folds[] = {
+    {fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_TRAIN>, fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_HELD>},
+    {fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_TRAIN>, fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_HELD>},
+};
+
+// The grid of product 1 on `rows_total` rows: the tile variant (0: 64-row tile, 1: 128-row tile), the row groups per
+// workgroup and the number of workgroups (rows of q_part).
+struct BatchGrid { int variant; int64_t gpw, nwg; };
+static BatchGrid batch_grid(const fos_problem* p, int64_t rows_total) {
   const bool is_bf16 = p->dtype == FOS_BF16;
   const int variant = rows_total >= 128 * (int64_t)p->ncu ? 1 : 0;
   const int rows = is_bf16 ? kBf16Batch[variant].rows : kF32Batch[variant].rows;
@@ -615,18 +630,54 @@ int launch_batch_product(fos_problem* p, const void* A, const float* b, int64_t 
   int64_t nwg = std::min<int64_t>(ngroups, per_cu * (int64_t)p->ncu);
   const int64_t gpw = (ngroups + nwg - 1) / nwg;
   nwg = (ngroups + gpw - 1) / gpw;
-  const Bf16BatchVariant& vq = kBf16Batch[variant];
-  const F32BatchVariant& vf = kF32Batch[variant];
-  if (is_bf16)
-    hipLaunchKernelGGL(bblock ? (rout ? vq.fn_store_rhs : vq.fn_rhs) : (rout ? vq.fn_store : vq.fn), dim3((unsigned)nwg),
+  return {variant, gpw, nwg};
+}
+
+// Product 1 on `rows` rows starting at A / b: q_part[wg][16] partial squared norms, rout (nullable): the residuals.
+// Returns the number of workgroups (rows of q_part).
+int launch_batch_product(fos_problem* p, const void* A, const float* b, int64_t rows_total, int use_b, float* rout, int* nwg_out,
+                         const int* stopped, bool bblock) {
+  const BatchGrid g = batch_grid(p, rows_total);
+  const Bf16BatchVariant& vq = kBf16Batch[g.variant];
+  const F32BatchVariant& vf = kF32Batch[g.variant];
+  if (p->dtype == FOS_BF16)
+    hipLaunchKernelGGL(bblock ? (rout ? vq.fn_store_rhs : vq.fn_rhs) : (rout ? vq.fn_store : vq.fn), dim3((unsigned)g.nwg),
                        dim3(fos::BT_THREADS), 0, p->stream, (const fos::bf16_t*)A, p->lda, b, (use_b && b) ? 1 : 0,
-                       rows_total, (int)p->n, (const unsigned short*)p->cand.xp.get(), gpw, p->cand.q_part, rout, stopped);
+                       rows_total, (int)p->n, (const unsigned short*)p->cand.xp.get(), g.gpw, p->cand.q_part, rout, stopped,
+                       (const uint8_t*)nullptr, fos::FoldHeld{});
   else
-    hipLaunchKernelGGL(bblock ? (rout ? vf.fn_store_rhs : vf.fn_rhs) : (rout ? vf.fn_store : vf.fn), dim3((unsigned)nwg),
+    hipLaunchKernelGGL(bblock ? (rout ? vf.fn_store_rhs : vf.fn_rhs) : (rout ? vf.fn_store : vf.fn), dim3((unsigned)g.nwg),
                        dim3(fos::BT_THREADS), 0, p->stream, (const float*)A, p->lda, b, (use_b && b) ? 1 : 0, rows_total,
-                       (int)p->n, p->cand.xp, gpw, p->cand.q_part, rout, stopped);
+                       (int)p->n, p->cand.xp, g.gpw, p->cand.q_part, rout, stopped, (const uint8_t*)nullptr, fos::FoldHeld{});
   LAUNCH_CHECK();
-  *nwg_out = (int)nwg;
+  *nwg_out = (int)g.nwg;
+  return FOS_OK;
+}
+
+bool fold_held_block(const int32_t* held, int nv, fos::FoldHeld* out) {
+  for (int j = 0; j < fos::BT_NV; ++j) {
+    const int32_t h = j < nv ? held[j] : -1;
+    if (h < -1 || h > 254) return false;
+    out->id[j] = (int8_t)h;                        // -1 is the byte 255, which no row carries
+  }
+  return true;
+}
+
+int launch_batch_product_folds(fos_problem* p, const void* A, const float* b, int64_t rows_total, float* rout, int* nwg_out,
+                               const uint8_t* fold_of_row, const fos::FoldHeld& held) {
+  const BatchGrid g = batch_grid(p, rows_total);
+  const Bf16FoldVariant& vq = kBf16Folds[g.variant];
+  const F32FoldVariant& vf = kF32Folds[g.variant];
+  if (p->dtype == FOS_BF16)
+    hipLaunchKernelGGL(rout ? vq.store_train : vq.resid_held, dim3((unsigned)g.nwg), dim3(fos::BT_THREADS), 0, p->stream,
+                       (const fos::bf16_t*)A, p->lda, b, 1, rows_total, (int)p->n, (const unsigned short*)p->cand.xp.get(), g.gpw,
+                       p->cand.q_part, rout, (const int*)nullptr, fold_of_row, held);
+  else
+    hipLaunchKernelGGL(rout ? vf.store_train : vf.resid_held, dim3((unsigned)g.nwg), dim3(fos::BT_THREADS), 0, p->stream,
+                       (const float*)A, p->lda, b, 1, rows_total, (int)p->n, p->cand.xp, g.gpw, p->cand.q_part, rout,
+                       (const int*)nullptr, fold_of_row, held);
+  LAUNCH_CHECK();
+  *nwg_out = (int)g.nwg;
   return FOS_OK;
 }
 
@@ -1492,6 +1543,35 @@ int fos_residual_batch_rhs(fos_problem* p, const float* X, int nv, const float* 
                        (int)p->cand.n_pad, nv, p->cand.xp);
   LAUNCH_CHECK();
   return launch_residual_batch(p, 1, out16, nullptr, p->ws.b16);
+}
+
+int fos_residual_batch_folds(fos_problem* p, const float* X, int nv, const uint8_t* fold_of_row, const int32_t* held,
+                             double* out16) {
+  fos::FoldHeld hb{};
+  if (!p || !X || !fold_of_row || !held || !out16 || nv < 1 || nv > fos::BT_NV || ((uintptr_t)fold_of_row & 3) != 0 ||
+      !fold_held_block(held, nv, &hb))
+    return fail(FOS_ERR_ARG, "fos_residual_batch_folds: bad argument (null pointer, nv outside 1..16, fold_of_row not 4-byte "
+                             "aligned or a held id outside -1..254)");
+  if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: the problem has no b of its own");
+  if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: sharded problems are not served");
+  if (!pair_dd_multi_supported(p))
+    return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: the shape has no matrix-core pair");
+  int rc = ensure_batch_workspace(p);
+  if (rc) return rc;
+  if (p->dtype == FOS_BF16)
+    hipLaunchKernelGGL(fos::xq_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
+                       (int)p->cand.n_pad, nv, (unsigned short*)p->cand.xp.get());
+  else
+    hipLaunchKernelGGL(xp_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
+                       (int)p->cand.n_pad, nv, p->cand.xp);
+  LAUNCH_CHECK();
+  if ((rc = prof_mark(p, true))) return rc;
+  int nwg = 0;
+  if ((rc = launch_batch_product_folds(p, p->A, p->b, p->m, nullptr, &nwg, fold_of_row, hb))) return rc;
+  if ((rc = prof_mark(p, false))) return rc;
+  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->cand.q_part, nwg, fos::BT_NV, out16);
+  LAUNCH_CHECK();
+  return FOS_OK;
 }
 
 int fos_gemv_pair_dd_multi(fos_problem* p, const double* X, int nv, int64_t ldx, const float* B, int64_t ldb, double alpha2,

@@ -69,13 +69,19 @@ class _EventTimer:
         ev1.record()
         self.pending.append((ev0, ev1, count))
 
+    def recount(self, count):
+        """The pair stopped last covered `count` units after all (a device-side stop ended the run early)."""
+        ev0, ev1, _ = self.pending[-1]
+        self.pending[-1] = (ev0, ev1, count)
+
     def flush(self):
         if not self.pending:
             return
         self.pending[-1][1].synchronize()
         for ev0, ev1, count in self.pending:
-            dt = ev0.elapsed_time(ev1) * 1e-3 / count
-            self.sink.extend([dt] * count)
+            if count > 0:
+                dt = ev0.elapsed_time(ev1) * 1e-3 / count
+                self.sink.extend([dt] * count)
         self.pending.clear()
 
 
@@ -1093,6 +1099,24 @@ def fista_delta(A, b, reg_type: str, alpha1: float, alpha2: float, delta: float,
 # ---------------------------------------------------------------------
 # Regularisation path (extension)
 # ---------------------------------------------------------------------
+def _run_path(prob, prms, max_iter, cols=None):
+    """One state machine per parameter set on `prob`, advanced max_iter iterations in lockstep groups (fos_fista_run_multi;
+    what it does not serve runs one by one); one grad_call_times entry per lockstep iteration per group.  The handles."""
+    handles = [_new_state(prob, prm) for prm in prms]
+    gtimer = _EventTimer(grad_call_times)
+    # up to 4 weights: the multi-vector VALU pass where the shape has one; up to 16: the matrix-core pass
+    width = 4 if len(handles) <= 4 and cols is None else 16
+    for i in range(0, len(handles), width):
+        group = handles[i:i + width]
+        ev = gtimer.start()
+        if len(group) == 1 or not _core.run_multi(group, max_iter):
+            for st in group:
+                st.run(max_iter)
+        gtimer.stop(ev, max_iter)
+    gtimer.flush()
+    return handles
+
+
 def fista_path(A, b, alphas, t_init_factor: float = 1.0, max_iter: int = 500, *, delta=None, L=None, dtype=None,
                comm=None, cols=None, tol: float = 0.0, tol_ratio: float = 0.0, adaptive_restart: bool = False,
                restart_threshold: float = 1.0, return_info: bool = False):
@@ -1121,22 +1145,170 @@ def fista_path(A, b, alphas, t_init_factor: float = 1.0, max_iter: int = 500, *,
     L_val = _lipschitz(prob, L, comm=comm, cols=cols)
     mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
     # the tolerances go to the device as given: a negative one is refused there (fos_fista_reset), not read as "off"
-    handles = [_new_state(prob, _params(_tau(L_val, a2, t_init_factor), a1, a2, mode=mode, delta=delta, tol=tol,
-                                        tol_ratio=tol_ratio, grad_rule=delta is None, adaptive_restart=adaptive_restart,
-                                        restart_threshold=restart_threshold)) for a1, a2 in alphas]
-    gtimer = _EventTimer(grad_call_times)
-    # up to 4 weights: the multi-vector VALU pass where the shape has one; up to 16: the matrix-core pass
-    width = 4 if len(handles) <= 4 and cols is None else 16
-    for i in range(0, len(handles), width):
-        group = handles[i:i + width]
-        ev = gtimer.start()
-        if len(group) == 1 or not _core.run_multi(group, max_iter):
-            for st in group:
-                st.run(max_iter)
-        gtimer.stop(ev, max_iter)
-    gtimer.flush()
+    handles = _run_path(prob, [_params(_tau(L_val, a2, t_init_factor), a1, a2, mode=mode, delta=delta, tol=tol,
+                                       tol_ratio=tol_ratio, grad_rule=delta is None, adaptive_restart=adaptive_restart,
+                                       restart_threshold=restart_threshold) for a1, a2 in alphas], max_iter, cols)
     xs = [_core.from_device_vec(st.x_tensor(), like) for st in handles]
     if return_info:
         stats = [st.status() for st in handles]
         return xs, [(int(s.k), int(s.stopped)) for s in stats]
     return xs
+
+
+# ---------------------------------------------------------------------
+# K-fold cross-validation of a regularisation path (extension)
+# ---------------------------------------------------------------------
+CVResult = collections.namedtuple("CVResult", "alphas mse mean_mse best x coefs info")
+
+CV_MAX_FOLDS = 255                       # fold ids are bytes 0..254 on the device; 255 stands for "no fold"
+
+
+def _cv_folds(folds, m):
+    """The fold id of every row (uint8 ndarray of length m) and the fold sizes, from `folds` as fista_cv takes it: an int
+    K >= 2 (contiguous blocks, the first m % K folds one row longer) or an integer array of m ids 0..K-1, K <= 255.
+    ValueError for anything else and for an empty fold; no device work."""
+    if isinstance(folds, (int, np.integer)) and not isinstance(folds, (bool, np.bool_)):
+        K = int(folds)
+        if K < 2 or K > CV_MAX_FOLDS:
+            raise ValueError(f"folds: an int K needs 2 <= K <= {CV_MAX_FOLDS}, got {K}")
+        if K > m:
+            raise ValueError(f"folds: {K} folds of {m} rows leave a fold empty")
+        sizes = np.array([m // K + (1 if f < m % K else 0) for f in range(K)], dtype=np.int64)
+        return np.repeat(np.arange(K, dtype=np.uint8), sizes), sizes
+    arr = folds.detach().cpu().numpy() if _core.is_tensor(folds) else np.asarray(folds)
+    if arr.ndim != 1 or arr.shape[0] != m:
+        raise ValueError(f"folds: an int K or one fold id per row ({m}) expected, got shape {arr.shape}")
+    if arr.dtype.kind not in "iu":
+        raise ValueError("folds: integer fold ids expected")
+    if arr.min() < 0 or arr.max() > CV_MAX_FOLDS - 1:
+        raise ValueError(f"folds: ids must lie in 0..{CV_MAX_FOLDS - 1}")
+    sizes = np.bincount(arr.astype(np.int64), minlength=int(arr.max()) + 1)
+    if len(sizes) < 2:
+        raise ValueError("folds: at least two folds are needed")
+    if (sizes == 0).any():
+        raise ValueError(f"folds: fold {int(np.argmin(sizes))} is empty")
+    return arr.astype(np.uint8), sizes.astype(np.int64)
+
+
+def _cv_lockstep(prob, ids, K, prms, max_iter):
+    """Every (fold, weight) pair as a column of the masked lockstep on the one bound A: groups of up to 16 columns,
+    fold-major, each one fos_fista_run_multi_folds call and one fos_residual_batch_folds pass.  (x n x K x L float64 device,
+    held-out SSE K x L, info) or None where the entry point does not serve the problem (decided on the first group)."""
+    La = len(prms)
+    cols = [(f, a) for f in range(K) for a in range(La)]
+    ids_dev = _core.fold_ids_tensor(ids, prob.device)
+    X = torch.zeros(prob.n, K, La, dtype=torch.float64, device=prob.device)
+    sse = np.zeros((K, La))
+    info = [[None] * La for _ in range(K)]
+    gtimer = _EventTimer(grad_call_times)
+    for g0 in range(0, len(cols), 16):
+        grp = cols[g0:g0 + 16]
+        held = [f for f, _ in grp]
+        handles = [_new_state(prob, prms[a]) for _, a in grp]
+        ev = gtimer.start()
+        if not _core.run_multi_folds(handles, ids_dev, held, max_iter):
+            if g0 == 0:
+                return None
+            raise _lib.FosError("fos_fista_run_multi_folds refused a later group of a problem it served")
+        gtimer.stop(ev, max_iter)
+        stats = [st.status() for st in handles]
+        gtimer.recount(max(int(s.k) for s in stats))             # the lockstep iterations actually run
+        xg = torch.stack([st.x_tensor() for st in handles], dim=1)
+        q = prob.residual_batch_folds(xg, ids_dev, held)
+        for j, (f, a) in enumerate(grp):
+            X[:, f, a] = xg[:, j]
+            sse[f, a] = q[j]
+            info[f][a] = (int(stats[j].k), int(stats[j].stopped))
+    gtimer.flush()
+    return X, sse, info
+
+
+def _cv_fold_by_fold(prob, ids, K, prms, max_iter):
+    """The slow path, for what the masked lockstep refuses: per fold the training rows gathered into a device copy (one
+    fold's copy alive at a time), the path run on the copy, the held-out rows gathered and scored with
+    fos_residual_objective.  Same results, K copies and K times the reads."""
+    La = len(prms)
+    idt = torch.from_numpy(ids.astype(np.int64)).to(prob.device)
+    X = torch.zeros(prob.n, K, La, dtype=torch.float64, device=prob.device)
+    sse = np.zeros((K, La))
+    info = [[None] * La for _ in range(K)]
+    for f in range(K):
+        rows = torch.nonzero(idt != f).squeeze(1)
+        sub = _core.Problem(prob.A.index_select(0, rows), prob.b.index_select(0, rows), prob.dtype)
+        handles, recorded = _metrics_of(lambda: _run_path(sub, prms, max_iter))
+        _metrics_add(recorded)
+        del sub
+        rows = torch.nonzero(idt == f).squeeze(1)
+        held = _core.Problem(prob.A.index_select(0, rows), prob.b.index_select(0, rows), prob.dtype)
+        for a, st in enumerate(handles):
+            x = st.x_tensor()
+            s = st.status()
+            X[:, f, a] = x[: prob.n]
+            sse[f, a] = held.residual_objective(x)[0]
+            info[f][a] = (int(s.k), int(s.stopped))
+        del handles, held
+    return X, sse, info
+
+
+def fista_cv(A, b, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int = 500, *, delta=None, L=None, dtype=None,
+             tol_ratio: float = 0.0, adaptive_restart: bool = False, restart_threshold: float = 1.0, refit: bool = True,
+             return_coefs: bool = False):
+    """K-fold cross-validation of a regularisation path: which of ``alphas`` (``(alpha1, alpha2)`` pairs, as in
+    ``fista_path``) predicts held-out rows best.
+
+    ``folds``: an int K >= 2 - contiguous blocks of rows, the first ``m % K`` folds one row longer - or an integer array
+    with one fold id 0..K-1 per row, K <= 255 (shuffled or stratified splits are such arrays).  Every fold must be
+    non-empty; anything else raises ValueError before any device work.
+
+    All K x L fits (K folds, L weights) advance in lockstep on the ONE device copy of A: fit (f, a) is column
+    ``f * L + a`` of the matrix-core pass of ``fista_path`` whose residual is zero on the rows of fold f, so it solves the
+    problem of the other rows; up to 16 columns share each read of A (fos_fista_run_multi_folds) and no row is ever
+    gathered.  The held-out squared errors of a group come from one further pass with the complementary mask.
+
+    ``L`` is estimated once, on the whole A, unless given (one power iteration, one draw from the global NumPy stream, like
+    ``fista_path``) and used for every fold: lambda_max(A_train^T A_train) <= lambda_max(A^T A), so the step 1 / L is valid
+    for every training set.  Contract: ``coefs[:, f, a]`` is what ``fista(A[train_f], b[train_f], ..., alpha1, alpha2, L=L)``
+    returns (``fista_delta`` with ``delta``) for that L, with the same ``t_init_factor``, ``max_iter``, ``tol_ratio``,
+    ``adaptive_restart`` and ``restart_threshold``; momentum restarts and the ratio stop are decided per column on the device.
+    There is no ``tol`` (the gradient-norm rule), no backtracking and no sharding here.
+
+    Returns ``CVResult(alphas, mse, mean_mse, best, x, coefs, info)``: ``mse[f, a]`` the held-out mean squared error
+    (K x L float64 ndarray), ``mean_mse`` its mean over the folds, ``best`` the argmin (first on ties), ``x`` the fit on ALL
+    rows at ``alphas[best]`` with the same L and parameters (``refit=True``; else None), ``coefs`` the n x K x L fits
+    (``return_coefs=True``; else None), ``info[f][a] = (iterations, stop_code)``.  ``grad_call_times`` gets one entry per
+    lockstep iteration actually run per group of columns.
+
+    The slow path: problems the lockstep does not serve (A that fits one CU's LDS, n <= 64, ragged or misaligned rows,
+    rows wider than 16384 columns) run fold by fold on gathered device copies of the training rows, one copy alive at a
+    time - the same results at K copies and K times the reads of A."""
+    reset_metrics()
+    if delta is not None:
+        assert delta > 2, "In FISTA-Δ, delta must be > 2 for convergence (course requirement)"
+    alphas = [(float(a1), float(a2)) for a1, a2 in alphas]
+    if not alphas:
+        raise ValueError("alphas: at least one (alpha1, alpha2) pair is needed")
+    m = A.m if isinstance(A, _core.Problem) else int(A.shape[0] if hasattr(A, "shape") else np.shape(A)[0])
+    ids, sizes = _cv_folds(folds, m)
+    K = len(sizes)
+    prob = _core.as_problem(A, b, dtype)
+    if prob.b is None:
+        raise ValueError("fista_cv needs b")
+    like = prob.like
+    L_val = _lipschitz(prob, L)
+    mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
+    prms = [_params(_tau(L_val, a2, t_init_factor), a1, a2, mode=mode, delta=delta, tol_ratio=tol_ratio,
+                    adaptive_restart=adaptive_restart, restart_threshold=restart_threshold) for a1, a2 in alphas]
+    out = _cv_lockstep(prob, ids, K, prms, max_iter)
+    if out is None:
+        out = _cv_fold_by_fold(prob, ids, K, prms, max_iter)
+    X, sse, info = out
+    mse = sse / sizes[:, None].astype(np.float64)
+    mean_mse = mse.mean(axis=0)
+    best = int(np.argmin(mean_mse))
+    x = None
+    if refit:
+        st = _new_state(prob, prms[best])
+        st.run(max_iter)
+        x = _core.from_device_vec(st.x_tensor(), like)
+    coefs = _core.from_device_vec(X, like) if return_coefs else None
+    return CVResult(alphas, mse, mean_mse, best, x, coefs, info)

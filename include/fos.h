@@ -211,6 +211,13 @@ int fos_residual_batch(fos_problem* p, const float* X, int nv, int use_b, double
  * b is not used.  One pass over A; B is staged into an m x 16 zero-padded block first.  FOS_ERR_ARG (checked before any HIP
  * call): null p / X / B / out16, nv outside 1..16, ldb < nv.  FOS_ERR_UNSUPPORTED on fallback-path and sharded problems. */
 int fos_residual_batch_rhs(fos_problem* p, const float* X, int nv, const float* B, int64_t ldb, double* out16);
+/* Held-out squared errors: out16[j] (device doubles) = sum over the rows i with fold_of_row[i] == held[j] of
+ * (A_i . X_j - b_i)^2 for the nv <= 16 columns of X (layout of fos_residual_batch); held[j] = -1: no row, 0.  One pass
+ * over A.  fold_of_row (device) and held (host) as for fos_fista_run_multi_folds, and the same FOS_ERR_ARG (null p / X /
+ * fold_of_row / held / out16, nv outside 1..16, a misaligned fold_of_row, a held entry outside -1..254; checked before
+ * any HIP call) and FOS_ERR_UNSUPPORTED cases (no b, sharded, shapes without the matrix-core pair). */
+int fos_residual_batch_folds(fos_problem* p, const float* X, int nv, const uint8_t* fold_of_row, const int32_t* held,
+                             double* out16);
 
 /* Power iteration, iterative_solvers.py:45-60.  v_inout: start vector (n floats, need not be normalised),
  * overwritten with the last iterate.  Any n_iter >= 1.  Synchronises; *L_out and *iters_out are host values. */
@@ -292,6 +299,20 @@ int fos_fista_run_multi(fos_fista* const* fs, int nv, int iters);
  * the multi-vector VALU pass subtracts B[i][v] for vector v).  FOS_ERR_ARG (checked before any HIP call): null fs / B,
  * nv outside 1..16, ldb < nv, iters < 0, handles on different problems.  Enqueues only (like fos_fista_run_multi). */
 int fos_fista_run_multi_rhs(fos_fista* const* fs, int nv, const float* B, int64_t ldb, int iters);
+/* K-fold cross-validation in lockstep: nv <= 16 state machines on ONE problem (its own b) advance `iters` iterations in
+ * lockstep, state machine v fitting the rows i with fold_of_row[i] != held[v] (held[v] = -1: all rows).  The matrix-core
+ * pass of fos_fista_run_multi with one change: product 1 zeroes column v's residual on the rows it holds out, so there is
+ * no copy of A and K folds x L weights cost ceil(K L / 16) reads of A per iteration.  fold_of_row: DEVICE, m fold ids
+ * 0..254, 4-byte aligned and readable up to m rounded up to 4 (the kernels fetch the ids of 4 rows with one 32-bit load);
+ * held: HOST, nv entries.  Always the two-product form (never the one-read cluster form or the multi-vector VALU pass),
+ * for any nv in 1..16; plain and device-controlled runs (adaptive restart, step / ratio stops per state machine, a
+ * stopped one becomes a masked column) as in fos_fista_run_multi; results equal fos_fista_run on the gathered rows
+ * (1e-6).  FOS_ERR_ARG (checked before any HIP call): null fs / fold_of_row / held, nv outside 1..16, iters < 0, a
+ * misaligned fold_of_row, a held entry outside -1..254, handles on different problems.  FOS_ERR_UNSUPPORTED (nothing
+ * run): a problem without its own b, row- or column-sharded problems, shapes without the matrix-core pair (LDS-resident,
+ * n <= 64, column-block, y-in-LDS rows, two-pass), a handle with the gradient-norm rule (tol_grad), the fp64 split
+ * gradient or a device-held step, device control over mixed families.  Enqueues only. */
+int fos_fista_run_multi_folds(fos_fista* const* fs, int nv, int iters, const uint8_t* fold_of_row, const int32_t* held);
 /* BASELINE north_star's literal step, opt-in: `iters` plain iterations in ONE persistent launch - A staged through LDS
  * in 4-row panels, the row dots A y on v_mfma_f32_4x4x1_16B_f32, A^T r on the VALU from the staged tile, a grid-wide
  * barrier, then prox + momentum by the workgroup that OWNS the columns, whose slice of x_k, x_{k-1} stays in its LDS for
