@@ -257,7 +257,8 @@ static int finish_part2(fos_fista* f, int n_rr) {
 static int flush_pending(fos_fista* f) { return f->pending ? finish_part2(f, 0) : FOS_OK; }
 
 // Start of a plain run: flush (unless the run closes the pending iterations itself), then the mirror valid - read back once
-// after device-held state.  *stopped: the state machine has stopped; the caller decides what that means for its run.
+// after device-held state.  *stopped: the state machine has stopped; the caller decides what that means for its run.  The
+// mirror of a stopped state stays invalid, so every later plain call asks again: a valid mirror says "not stopped".
 static int begin_plain(fos_fista* f, bool* stopped, bool flush = true) {
   *stopped = false;
   int rc = flush ? flush_pending(f) : FOS_OK;
@@ -265,6 +266,7 @@ static int begin_plain(fos_fista* f, bool* stopped, bool flush = true) {
   fos_fista_status st;
   if ((rc = fos_fista_status_get(f, &st))) return rc;
   *stopped = st.stopped != FOS_STOP_NONE;
+  if (*stopped) return FOS_OK;
   f->h_t = st.t_prev; f->h_beta = st.beta; f->h_k = st.k;
   f->host_valid = true;
   return FOS_OK;

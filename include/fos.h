@@ -247,6 +247,14 @@ int fos_fista_set_precise(fos_fista* f, int on);
 /* Precise mode with a CALLER-OWNED gradient buffer (n + 4 doubles, 16-byte aligned; NULL returns to fp32): split-form
  * sharding sums [gradient ; ||r||^2] (n + 1 doubles) over the ranks itself, between fos_fista_grad and the consumers. */
 int fos_fista_set_gbuf64(fos_fista* f, double* buf);
+/* A STOPPED handle (fos_fista_status.stopped != FOS_STOP_NONE: a stopping rule fired, or a device search parked itself with
+ * FOS_STOP_LS_STALL) stays where it is until fos_fista_reset - or fos_fista_resume_after_stall for a parked search: every
+ * entry point below that would advance it returns FOS_OK (or its usual FOS_ERR_UNSUPPORTED) and leaves x_k, k and the
+ * stop code untouched, whatever ran on the handle before and in whatever order the entry points are mixed - fos_fista_run,
+ * _run_fused, _run_chip, _run_resident (*iters_done = 0), _grad / _grad_dual + _update, _run_recorded,
+ * _run_backtracking, and the device-controlled lockstep, where a stopped handle is a masked column.  Two kinds of call
+ * report it instead, before anything is run: fos_fista_run_history (its caller expects `iters` rows) and the PLAIN
+ * lockstep of fos_fista_run_multi / _run_multi_rhs / _run_multi_folds (no masked columns there) return FOS_ERR_STATE. */
 /* Enqueue `iters` full iterations (gradient, prox, momentum, restart and stop logic all on the device;
  * no host round trip).  Iterations after a device-side stop are no-ops.  :170-242, :289-342 */
 int fos_fista_run(fos_fista* f, int iters);
