@@ -46,6 +46,9 @@ def stores_bf16(A, dtype=None):
 
 
 UPLOAD_CHUNK_BYTES = 256 << 20
+LOSSES = {"squared": _lib.LOSS_SQUARED, "logistic": _lib.LOSS_LOGISTIC}
+LOGIT_MAX_N = 16384                      # device columns the matrix-core pair serves (csrc/fos_plan.hip pair_dd_multi_supported)
+LOGIT_MIN_N = {"f32": 68, "bf16": 72}    # the narrowest streaming width: 64 columns plus one 16-byte chunk
 
 
 def upload_matrix(src, out):
@@ -101,13 +104,19 @@ class Problem:
     Build it once with ``prepare(A, b)`` and pass it wherever the solvers take ``A`` to avoid re-uploading A.
     """
 
-    def __init__(self, A, b=None, dtype=None, pad=None):
-        """pad: zero-pad the columns of the device copy of A to the fused kernel's granularity (4 fp32 / 8 bf16
+    def __init__(self, A, b=None, dtype=None, pad=None, loss="squared"):
+        """loss: "squared" (b is the target of 0.5 ||Ax - b||^2) or "logistic" (b holds labels in [0, 1]; the data term is the
+        log-loss, served by `logistic_path` / `logistic_cv` / `logistic_objective` only: fos_problem_set_loss).
+        pad: zero-pad the columns of the device copy of A to the fused kernel's granularity (4 fp32 / 8 bf16
         elements, 16-byte aligned rows) so that a ragged n or a misaligned view still gets the single-pass kernel
         (4x faster than the two-pass path at 65536 x 8190).  Zero columns stay exactly zero through gradient and
         prox, and every vector is padded / trimmed here, so callers never see them.  None = only for problems large
         enough for it to matter (m*n >= 2^20: the padded single pass is 3-14x faster from there on); small ragged problems
-        keep the fp64-accumulating two-pass path."""
+        keep the fp64-accumulating two-pass path.  A logistic problem runs on the matrix-core pair alone, so for it None means
+        always: rows are padded to the granularity, and to 68 fp32 / 72 bf16 columns when n <= 64 - every shape up to 16384
+        device columns is served; more raise ValueError."""
+        if loss not in LOSSES:
+            raise ValueError(f"loss: one of {sorted(LOSSES)} expected, got {loss!r}")
         require_gpu()
         lib = _lib.load()
         self.like = Like(A)
@@ -127,10 +136,11 @@ class Problem:
         fused_ok = borrowable and n % gran == 0 and (At.stride(0) % gran == 0 or m == 1) and At.data_ptr() % 16 == 0
         if pad is None:
             # n <= 64 runs the row-per-thread kernel, which takes ragged / misaligned rows as they are
-            pad = (not fused_ok) and m * n >= (1 << 20) and n > 64
+            pad = loss == "logistic" or ((not fused_ok) and m * n >= (1 << 20) and n > 64)
         n_dev = n
-        if pad and not fused_ok:
-            n_dev = (n + gran - 1) // gran * gran
+        n_min = LOGIT_MIN_N["bf16" if want_bf16 else "f32"] if loss == "logistic" and n <= 64 else 0
+        if pad and (not fused_ok or n < n_min):
+            n_dev = max((n + gran - 1) // gran * gran, n_min)
             Ap = torch.zeros(m, n_dev, dtype=tdtype, device=dev)
             if At.is_cuda:
                 Ap[:, :n].copy_(At)                  # one strided device copy
@@ -147,6 +157,9 @@ class Problem:
         self.lda = int(At.stride(0)) if self.m > 1 else self.n_dev
         self.device = At.device
         self.dtype = "bf16" if want_bf16 else "f32"
+        self.loss = loss
+        if loss == "logistic" and n_dev > LOGIT_MAX_N:
+            raise ValueError(f"a logistic problem is limited to {LOGIT_MAX_N} device columns, got {n_dev}")
         self._bind(b, lib)
 
     def sibling(self, b):
@@ -155,7 +168,7 @@ class Problem:
         sib = Problem.__new__(Problem)
         sib.like = self.like
         sib.A, sib.m, sib.n, sib.n_dev, sib.lda = self.A, self.m, self.n, self.n_dev, self.lda
-        sib.device, sib.dtype = self.device, self.dtype
+        sib.device, sib.dtype, sib.loss = self.device, self.dtype, self.loss
         sib._bind(b, self.lib)
         return sib
 
@@ -165,6 +178,11 @@ class Problem:
         self.b = None if b is None else to_device_vec(b, self.device)
         if self.b is not None and self.b.numel() != self.m:
             raise ValueError("b must have m entries")
+        if self.loss == "logistic":
+            if self.b is None:
+                raise ValueError("a logistic problem needs its labels")
+            if not bool((torch.isfinite(self.b) & (self.b >= 0) & (self.b <= 1)).all()):     # once, on the device
+                raise ValueError("logistic labels must be finite and lie in [0, 1]")
         self.gbuf = torch.zeros(self.n_dev + 4, dtype=torch.float32, device=self.device)
         self.scratch = torch.zeros(32, dtype=torch.float64, device=self.device)
         h = C.c_void_p()
@@ -175,6 +193,8 @@ class Problem:
             self.h = h
             self._stream = torch.cuda.current_stream(self.device).cuda_stream
             _lib.check(lib.fos_problem_set_gbuf(self.h, ptr(self.gbuf)), "fos_problem_set_gbuf")
+            if self.loss != "squared":
+                _lib.check(lib.fos_problem_set_loss(self.h, LOSSES[self.loss]), "fos_problem_set_loss")
         self.lib = lib
 
     def __del__(self):
@@ -347,9 +367,15 @@ class Problem:
         return L.value, it.value, self.vec_out(v)
 
 
-def prepare(A, b=None, dtype=None, pad=None):
-    """Upload/bind A (and b) once; the result can be passed as ``A`` to every solver (``b`` may then be None)."""
-    return A if isinstance(A, Problem) else Problem(A, b, dtype, pad)
+def prepare(A, b=None, dtype=None, pad=None, *, loss="squared"):
+    """Upload/bind A (and b) once; the result can be passed as ``A`` to every solver (``b`` may then be None).
+    ``loss="logistic"``: b holds labels in [0, 1] and the handle is one for ``logistic_path`` / ``logistic_cv`` /
+    ``logistic_objective`` (see ``Problem``); a handle that is passed in keeps the loss it was prepared with."""
+    if isinstance(A, Problem):
+        if loss == "logistic" and A.loss != "logistic":
+            raise ValueError("this Problem was prepared for the squared loss")
+        return A
+    return Problem(A, b, dtype, pad, loss)
 
 
 def as_problem(A, b, dtype=None):

@@ -132,6 +132,19 @@ __device__ __forceinline__ float fold_mask(float v, unsigned ids4, int r, unsign
   return (FOLD == FOLD_TRAIN ? is_held : !is_held) ? 0.f : v;
 }
 
+// Loss of product 1's epilogue.  SQUARED: R = A Y - b, q = sum R^2.  LOGISTIC (labels b in [0, 1], z = a_i . y_j):
+// R = sigma(z) - b, the derivative of the log-loss l(z, b) = log(1 + e^z) - b z, and q = sum l.  Everything downstream
+// (product 2, the slab sums, the updates) sees only R.
+constexpr int LOSS_SQUARED = 0, LOSS_LOGISTIC = 1;
+// sigma(z) - b -> *v and l(z, b) -> *l without overflow at either end: e = exp(-|z|) <= 1, sigma = 1 / (1 + e) or e / (1 + e),
+// log(1 + e^z) = max(z, 0) + log1p(e).  The accurate expf / log1pf (a few ulp), not the fast forms.
+__device__ __forceinline__ void logistic_terms(float z, float label, float* v, float* l) {
+  const float e = expf(-fabsf(z));
+  const float p = z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+  *v = p - label;
+  *l = fmaxf(z, 0.f) - label * z + log1pf(e);
+}
+
 // q_part[wg][j] = sum over this workgroup's rows of (A_i . X_j - use_b * b_i)^2.
 // Requirements (host-checked): n % 4 == 0, lda % 4 == 0, A 16-byte aligned, Xp zero-padded to n_pad = 64*ceil(n/64).
 // STORE_R = true (multi-lambda gradient, gram_batch.hpp): the residuals themselves, rout[row][16 candidates] fp32,
@@ -140,7 +153,9 @@ __device__ __forceinline__ float fold_mask(float v, unsigned ids4, int r, unsign
 // lanes read one contiguous 64-byte row, the pattern of the rout store beside it.
 // FOLD (FOLD_TRAIN / FOLD_HELD): the epilogue masks v by fold_of_row[row] (indexed by the row within the launch) against
 // held.id[candidate], see above; the tile loop is the same.
-template <int RB, bool STORE_R = false, bool BBLOCK = false, int FOLD = FOLD_OFF>
+// LOSS (LOSS_LOGISTIC): the epilogue forms sigma(A_i . X_j) - b_i and sums the log-loss instead (logistic_terms above; b is
+// the label vector, use_b is 1, BBLOCK false); the fold mask applies to both; the tile loop is the same.
+template <int RB, bool STORE_R = false, bool BBLOCK = false, int FOLD = FOLD_OFF, int LOSS = LOSS_SQUARED>
 __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const float* __restrict__ A, int64_t lda,
                                                                         const float* __restrict__ b, int use_b,
                                                                         int64_t m, int n,
@@ -230,13 +245,22 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const f
           const int64_t row = row0 + r;
           if (row < m) {
             float v = acc[rb][r];
-            if constexpr (BBLOCK) {
-              if (use_b) v -= b[row * BT_NV + (lane & 15)];
+            if constexpr (LOSS == LOSS_LOGISTIC) {
+              static_assert(!BBLOCK, "the logistic epilogue reads one label vector");
+              float l;
+              logistic_terms(v, b[row], &v, &l);
+              v = fold_mask<FOLD>(v, ids4, r, held_id);
+              l = fold_mask<FOLD>(l, ids4, r, held_id);
+              qsum += (double)l;
             } else {
-              if (use_b) v -= b[row];
+              if constexpr (BBLOCK) {
+                if (use_b) v -= b[row * BT_NV + (lane & 15)];
+              } else {
+                if (use_b) v -= b[row];
+              }
+              v = fold_mask<FOLD>(v, ids4, r, held_id);
+              qsum += (double)v * (double)v;
             }
-            v = fold_mask<FOLD>(v, ids4, r, held_id);
-            qsum += (double)v * (double)v;
             if constexpr (STORE_R) rout[row * BT_NV + (lane & 15)] = v;      // 16 lanes: one 64-byte row of R
           }
         }
@@ -382,8 +406,9 @@ static __global__ void xq_pack_kernel(const float* __restrict__ X, int n, int n_
 // RB = 16-row blocks per wave (the candidate fragments read from LDS are reused for RB row blocks: X is 96 bytes per
 // column against 32 bytes of A per row block, so LDS traffic per byte of A falls with RB); COLS = bf16 columns per tile.
 // Requirements: n % 8 == 0, lda % 8 == 0, A 16-byte aligned, Xq zero-padded to n_pad (a multiple of 128).
-// BBLOCK: b is the m x 16 right-hand-side block, FOLD: the fold mask of the epilogue, both as in residual_batch_mfma_kernel.
-template <int RB, int COLS, bool STORE_R = false, bool BBLOCK = false, int FOLD = FOLD_OFF>
+// BBLOCK: b is the m x 16 right-hand-side block, FOLD: the fold mask of the epilogue, LOSS: the logistic epilogue, all as in
+// residual_batch_mfma_kernel.
+template <int RB, int COLS, bool STORE_R = false, bool BBLOCK = false, int FOLD = FOLD_OFF, int LOSS = LOSS_SQUARED>
 __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_bf16_kernel(
     const bf16_t* __restrict__ A, int64_t lda, const float* __restrict__ b, int use_b, int64_t m, int n,
     const unsigned short* __restrict__ xq, int64_t groups_per_wg, double* __restrict__ q_part,
@@ -476,13 +501,22 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_bf16_kernel(
           const int64_t row = row0 + r;
           if (row < m) {
             float v = acc[rb][r];
-            if constexpr (BBLOCK) {
-              if (use_b) v -= b[row * BT_NV + (lane & 15)];
+            if constexpr (LOSS == LOSS_LOGISTIC) {
+              static_assert(!BBLOCK, "the logistic epilogue reads one label vector");
+              float l;
+              logistic_terms(v, b[row], &v, &l);
+              v = fold_mask<FOLD>(v, ids4, r, held_id);
+              l = fold_mask<FOLD>(l, ids4, r, held_id);
+              qsum += (double)l;
             } else {
-              if (use_b) v -= b[row];
+              if constexpr (BBLOCK) {
+                if (use_b) v -= b[row * BT_NV + (lane & 15)];
+              } else {
+                if (use_b) v -= b[row];
+              }
+              v = fold_mask<FOLD>(v, ids4, r, held_id);
+              qsum += (double)v * (double)v;
             }
-            v = fold_mask<FOLD>(v, ids4, r, held_id);
-            qsum += (double)v * (double)v;
             if constexpr (STORE_R) rout[row * BT_NV + (lane & 15)] = v;
           }
         }

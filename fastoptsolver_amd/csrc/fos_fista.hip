@@ -381,6 +381,7 @@ int fos_fista_run_resident(fos_fista* f, int iters, int backtracking, double eta
                            double* tau_out) {
   if (!f || iters < 0 || !iters_done || !tau_out || (backtracking && !(eta > 0.0 && eta < 1.0)))
     return fail(FOS_ERR_ARG, "fos_fista_run_resident: bad argument");
+  if (int rc_ = need_squared(f->p, "fos_fista_run_resident")) return rc_;
   fos_problem* p = f->p;
   if (!p->pass.resident) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_resident: problem does not fit the LDS-resident loop");
   *iters_done = 0;
@@ -410,6 +411,7 @@ int64_t fos_fista_history_workspace(fos_fista* f, int iters) {
 int fos_fista_run_history(fos_fista* f, int iters, double* x_hist, double* hist, void* work) {
   if (!f || iters < 0 || (iters > 0 && (!x_hist || !hist || !work)))
     return fail(FOS_ERR_ARG, "fos_fista_run_history: bad argument");
+  if (int rc_ = need_squared(f->p, "fos_fista_run_history")) return rc_;
   fos_problem* p = f->p;
   if (plain_run(f) && p->pass.resident) return iters == 0 ? FOS_OK : run_resident(f, iters, x_hist, hist);
   if (!plain_run(f) || p->pass.path != 0 || p->pass.colblock || p->pass.entry->dual == nullptr || p->comm != nullptr)
@@ -451,6 +453,7 @@ int fos_fista_run_history(fos_fista* f, int iters, double* x_hist, double* hist,
 
 int fos_fista_run(fos_fista* f, int iters) {
   if (!f || iters < 0) return fail(FOS_ERR_ARG, "fos_fista_run: bad argument");
+  if (int rc_ = need_squared(f->p, "fos_fista_run")) return rc_;
   fos_problem* p = f->p;
   if (iters == 0) return FOS_OK;
   if (p->pass.resident) return run_resident(f, iters, nullptr, nullptr);
@@ -532,6 +535,7 @@ int fos_problem_set_fused_stamps(fos_problem* p, unsigned long long* stamps) {
 // BASELINE north_star's literal design, opt-in (the two-launch VALU step measures faster).  Plain runs only.
 int fos_fista_run_fused(fos_fista* f, int iters) {
   if (!f || iters < 0) return fail(FOS_ERR_ARG, "fos_fista_run_fused: bad argument");
+  if (int rc_ = need_squared(f->p, "fos_fista_run_fused")) return rc_;
   fos_problem* p = f->p;
   const int G = p->ncu;
   if (p->dtype != FOS_F32 || p->pass.path != 0 || p->pass.tall || p->pass.colblock || p->pass.resident || p->comm || p->n % 2048 != 0 ||
@@ -588,6 +592,7 @@ int fos_fista_run_fused(fos_fista* f, int iters) {
 // Tall-skinny plain runs with A resident in the LDS of up to all CUs, one grid barrier per iteration (chip_resident.hpp). Opt-in.
 int fos_fista_run_chip(fos_fista* f, int iters) {
   if (!f || iters < 0) return fail(FOS_ERR_ARG, "fos_fista_run_chip: bad argument");
+  if (int rc_ = need_squared(f->p, "fos_fista_run_chip")) return rc_;
   fos_problem* p = f->p;
   const int nc = p->n <= 8 ? 8 : 16;
   const int64_t cap = fos::cr_rows_cap(nc);
@@ -675,6 +680,8 @@ static fos::MultiUpdate multi_update(fos_fista* const* fs, int nv, bool controll
 // fold_of_row / held (K-fold cross-validation, unsharded, the problem's own b): product 1 zeroes column j's residual on the
 // rows of the fold it holds out (batch_trial.hpp FOLD_TRAIN), so state machine j fits the other rows; the two-product form
 // likewise.  Product 2 and the updates see a masked R and are the same launches.
+// A logistic problem (fos_problem_set_loss): product 1 is the logistic form, R = sigma(A_panel Y) - b with or without the fold
+// mask (launch_batch_product_logit); the two-product form as well, and everything after product 1 is the same.
 static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controlled, bool same_family,
                           const float* b16 = nullptr, const uint8_t* fold_of_row = nullptr,
                           const fos::FoldHeld* held = nullptr) {
@@ -690,14 +697,15 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
   const int y_mode = is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP;
   // row splits of product 2: the planned ones, or - a B-block run on a problem planned for the cluster form, whose slab
   // count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated
-  const bool two_products = b16 || fold_of_row;
+  const bool logit = p->loss == FOS_LOSS_LOGISTIC;
+  const bool two_products = b16 || fold_of_row || logit;
   bool use_cluster = p->multi.cp_cs && !two_products;
   int g_splits = p->multi.gram_splits;
   if (p->multi.cp_cs && two_products) {
     g_splits = (int)((p->multi.panel_rows + p->multi.gram_rows_per_split - 1) / p->multi.gram_rows_per_split);
     if (g_splits > p->multi.gram_splits)
-      return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs / _folds: the cluster layout of this problem has too few "
-                                       "slabs for the two-product form");
+      return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs / _folds / logistic loss: the cluster layout of this problem "
+                                       "has too few slabs for the two-product form");
   }
   // candidate block: zero everywhere (padding columns, unused slots), then y_k of every state machine
   const size_t per_entry = is_bf16 ? 3 * sizeof(unsigned short) : sizeof(float);
@@ -746,7 +754,9 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
       int nwg1 = 0;
       // column-sharded: b enters the sum over the ranks once (rank 0); R = sum_p A_p Y_p - b is the ONE exchange per panel
       const float* bp = b16 ? b16 + row0 * fos::BT_NV : (p->b && !(cols && p->comm->rank != 0)) ? p->b + row0 : nullptr;
-      if (fold_of_row)               // the ids are offset with the panel as b is (panel rows are a multiple of 256)
+      if (logit)                     // labels and fold ids are offset with the panel
+        rc = launch_batch_product_logit(p, Ap, p->b + row0, rows, p->multi.rbuf16, &nwg1, fold_of_row ? fold_of_row + row0 : nullptr, held);
+      else if (fold_of_row)          // the ids are offset with the panel as b is (panel rows are a multiple of 256)
         rc = launch_batch_product_folds(p, Ap, p->b + row0, rows, p->multi.rbuf16, &nwg1, fold_of_row + row0, *held);
       else
         rc = launch_batch_product(p, Ap, bp, rows, 1, p->multi.rbuf16, &nwg1, nullptr, b16 != nullptr);
@@ -816,9 +826,38 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
 
 // The lockstep dispatcher of fos_fista_run_multi (B == nullptr: the problem's b) and fos_fista_run_multi_rhs (B: column v of
 // the caller's m x nv block for state machine v, staged once per call into the m x 16 block p->ws.b16).  Arguments are checked.
+// The checks the masked and the logistic lockstep share: no gradient-norm rule, fp64 split gradient or device-held step, and
+// device control (adaptive restart, step / ratio stops) only for one family - it is one update launch for all state machines.
+static int lockstep_forms(fos_fista* const* fs, int nv, const char* fn, bool* all_plain, bool* same_family) {
+  *all_plain = *same_family = true;
+  for (int v = 0; v < nv; ++v) {
+    if (fs[v]->prm.tol_grad != 0.0 || fs[v]->precise || fs[v]->prm.tau_from_state)
+      return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": no gradient-norm rule, fp64 split gradient or device-held step");
+    *all_plain = *all_plain && plain_run(fs[v]);
+    const fos::FistaParams &a = fs[0]->prm, &c = fs[v]->prm;
+    *same_family = *same_family && a.mode == c.mode && a.prox_kind == c.prox_kind && a.delta == c.delta;
+  }
+  if (!*all_plain && !*same_family) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": a device-controlled lockstep serves one family");
+  return FOS_OK;
+}
+
+// A logistic problem: always the two matrix-core products, for any number of state machines (one included - there is no
+// single-vector logistic pass), never the cluster form or the VALU multi-vector pass.
+static int run_multi_logit(fos_fista* const* fs, int nv, int iters, const uint8_t* fold_of_row, const fos::FoldHeld* held,
+                           const char* fn) {
+  fos_problem* p = fs[0]->p;
+  if (!p->b || p->comm || p->col_sharded || !pair_dd_multi_supported(p))
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the logistic loss needs b, an unsharded problem and the matrix-core pair");
+  bool all_plain, same_family;
+  if (int rc = lockstep_forms(fs, nv, fn, &all_plain, &same_family)) return rc;
+  if (iters == 0) return FOS_OK;
+  return run_multi_mfma(fs, nv, iters, !all_plain, same_family, nullptr, fold_of_row, held);
+}
+
 static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, int64_t ldb) {
   fos_problem* p = fs[0]->p;
   const bool rhs = B != nullptr;
+  if (p->loss == FOS_LOSS_LOGISTIC) return run_multi_logit(fs, nv, iters, nullptr, nullptr, "fos_fista_run_multi");
   if (rhs && (p->comm || p->col_sharded))
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs: row- or column-sharded problems are not served");
   if (nv == 1) {
@@ -912,6 +951,7 @@ int fos_fista_run_multi_rhs(fos_fista* const* fs, int nv, const float* B, int64_
     return fail(FOS_ERR_ARG, "fos_fista_run_multi_rhs: bad argument (null pointer, nv outside 1..16, ldb < nv or iters < 0)");
   for (int v = 0; v < nv; ++v)
     if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi_rhs: handles must share one problem");
+  if (int rc_ = need_squared(fs[0]->p, "fos_fista_run_multi_rhs")) return rc_;
   return run_multi(fs, nv, iters, B, ldb);
 }
 
@@ -924,22 +964,14 @@ int fos_fista_run_multi_folds(fos_fista* const* fs, int nv, int iters, const uin
   for (int v = 0; v < nv; ++v)
     if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi_folds: handles must share one problem");
   fos_problem* p = fs[0]->p;
+  if (p->loss == FOS_LOSS_LOGISTIC) return run_multi_logit(fs, nv, iters, fold_of_row, &hb, "fos_fista_run_multi_folds");
   if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the problem has no b of its own");
   if (p->comm || p->col_sharded)
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: row- or column-sharded problems are not served");
   if (!pair_dd_multi_supported(p))
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the shape has no matrix-core pair");
-  bool all_plain = true, same_family = true;
-  for (int v = 0; v < nv; ++v) {
-    if (fs[v]->prm.tol_grad != 0.0 || fs[v]->precise || fs[v]->prm.tau_from_state)
-      return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: no gradient-norm rule, fp64 split gradient or device-held step");
-    all_plain = all_plain && plain_run(fs[v]);
-    const fos::FistaParams &a = fs[0]->prm, &c = fs[v]->prm;
-    same_family = same_family && a.mode == c.mode && a.prox_kind == c.prox_kind && a.delta == c.delta;
-  }
-  // device control (adaptive restart, step / ratio stops) is one update launch for all state machines: one family
-  if (!all_plain && !same_family)
-    return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: a device-controlled lockstep serves one family");
+  bool all_plain, same_family;
+  if (int rc = lockstep_forms(fs, nv, "fos_fista_run_multi_folds", &all_plain, &same_family)) return rc;
   if (iters == 0) return FOS_OK;
   // always the two matrix-core products, for any number of state machines: the alternative is a copy of A per fold
   return run_multi_mfma(fs, nv, iters, !all_plain, same_family, nullptr, fold_of_row, &hb);
@@ -947,6 +979,7 @@ int fos_fista_run_multi_folds(fos_fista* const* fs, int nv, int iters, const uin
 
 int fos_fista_grad(fos_fista* f) {
   if (!f) return fail(FOS_ERR_ARG, "fos_fista_grad: null");
+  if (int rc_ = need_squared(f->p, "fos_fista_grad")) return rc_;
   fos_problem* p = f->p;
   int n_rr = 0, rc;
   if (f->precise && !p->pass.resident) {
@@ -967,6 +1000,7 @@ int fos_fista_grad(fos_fista* f) {
 
 int fos_fista_grad_dual(fos_fista* f) {
   if (!f) return fail(FOS_ERR_ARG, "fos_fista_grad_dual: null");
+  if (int rc_ = need_squared(f->p, "fos_fista_grad_dual")) return rc_;
   fos_problem* p = f->p;
   int n_rr = 0, rc;
   if ((rc = flush_pending(f))) return rc;
@@ -993,6 +1027,7 @@ int fos_fista_grad_dual(fos_fista* f) {
 
 int fos_fista_update(fos_fista* f) {
   if (!f) return fail(FOS_ERR_ARG, "fos_fista_update: null");
+  if (int rc_ = need_squared(f->p, "fos_fista_update")) return rc_;
   fos_problem* p = f->p;
   if (plain_run(f) && f->host_valid && !p->col_sharded) {
     // host-driven momentum (see fos_fista_run): no per-iteration bookkeeping launch, y handed on as one fp32 vector
@@ -1006,6 +1041,7 @@ int fos_fista_update(fos_fista* f) {
 
 int fos_fista_trial(fos_fista* f, double t, int with_residual, double out8[8]) {
   if (!f || !out8 || !(t > 0.0)) return fail(FOS_ERR_ARG, "fos_fista_trial: bad argument");
+  if (int rc_ = need_squared(f->p, "fos_fista_trial")) return rc_;
   fos_problem* p = f->p;
   if (p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_trial: no column-sharded form (||A dlt||^2 needs an m-vector exchange per candidate)");
   { int rcf = flush_pending(f); if (rcf) return rcf; }
@@ -1101,6 +1137,7 @@ int fos_fista_run_backtracking(fos_fista* f, int iters, double eta, double armij
                                double* tau_hist) {
   if (!f || iters < 0 || !(eta > 0.0 && eta < 1.0) || !(grad_eps >= 0.0))
     return fail(FOS_ERR_ARG, "fos_fista_run_backtracking: bad argument");
+  if (int rc_ = need_squared(f->p, "fos_fista_run_backtracking")) return rc_;
   fos_problem* p = f->p;
   if (!batch_supported(p) || p->pass.resident)
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_backtracking: needs the matrix-core candidate pass (streaming plans)");
@@ -1113,6 +1150,7 @@ int fos_fista_run_recorded(fos_fista* f, int iters, int backtracking, double eta
   if (!f || iters < 0 || (iters > 0 && (!x_hist || !hist)) ||
       (backtracking && (!(eta > 0.0 && eta < 1.0) || !(grad_eps >= 0.0))))
     return fail(FOS_ERR_ARG, "fos_fista_run_recorded: bad argument");
+  if (int rc_ = need_squared(f->p, "fos_fista_run_recorded")) return rc_;
   fos_problem* p = f->p;
   if (p->pass.resident || (backtracking && !batch_supported(p)))
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_recorded: resident problems record inside their one launch; "
@@ -1123,6 +1161,7 @@ int fos_fista_run_recorded(fos_fista* f, int iters, int backtracking, double eta
 
 int fos_fista_resume_after_stall(fos_fista* f, double* tau_out) {
   if (!f || !tau_out) return fail(FOS_ERR_ARG, "fos_fista_resume_after_stall: null");
+  if (int rc_ = need_squared(f->p, "fos_fista_resume_after_stall")) return rc_;
   fos_problem* p = f->p;
   fos::FistaScalars h;
   HIP_TRY(hipMemcpyAsync(&h, f->scal, sizeof(h), hipMemcpyDeviceToHost, p->stream));
@@ -1137,6 +1176,7 @@ int fos_fista_resume_after_stall(fos_fista* f, double* tau_out) {
 int fos_fista_trial_batch(fos_fista* f, double t, double eta, int nv, double* out) {
   if (!f || !out || !(t > 0.0) || !(eta > 0.0) || nv < 1 || nv > fos::BT_NV)
     return fail(FOS_ERR_ARG, "fos_fista_trial_batch: bad argument");
+  if (int rc_ = need_squared(f->p, "fos_fista_trial_batch")) return rc_;
   fos_problem* p = f->p;
   { int rcf = flush_pending(f); if (rcf) return rcf; }
   if (!batch_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_trial_batch: needs the fused path");

@@ -268,6 +268,7 @@ struct fos_problem {
   fos_comm* comm = nullptr;          // row-sharded problem: sums of partial results go through it (comm.hpp)
   int64_t m = 0, n = 0, lda = 0;
   int dtype = FOS_F32;
+  int loss = FOS_LOSS_SQUARED;       // fos_problem_set_loss: what b means to the matrix-core lockstep (no buffer depends on it)
   hipStream_t stream = nullptr;
   int ncu = 256;
   // inputs of the plan groups besides the shape (set by the entry point named; see fosapi::invalidate)
@@ -390,6 +391,13 @@ bool fold_held_block(const int32_t* held, int nv, fos::FoldHeld* out);
 // column's held-out rows); rout null: the held-out residual form (q_part = held-out squared errors).
 int launch_batch_product_folds(fos_problem* p, const void* A, const float* b, int64_t rows_total, float* rout, int* nwg_out,
                                const uint8_t* fold_of_row, const fos::FoldHeld& held);
+// Product 1 of a logistic problem (kF32Logit / kBf16Logit): rout = sigma(A Y) - b when given, q_part = log-loss partials;
+// fold_of_row / held (both or neither): the masked forms as launch_batch_product_folds.
+int launch_batch_product_logit(fos_problem* p, const void* A, const float* b, int64_t rows_total, float* rout, int* nwg_out,
+                               const uint8_t* fold_of_row, const fos::FoldHeld* held);
+// The one guard of the entry points that form a residual, gradient or objective with b as a squared-loss target: refuses a
+// logistic problem (FOS_ERR_UNSUPPORTED) before any launch or change of handle state.
+int need_squared(const fos_problem* p, const char* fn);
 // q[j] = ||A Xp_j - use_b*b||^2 -> out16 (device); Xp already in p->xp.  b16 (unsharded only): subtract its column j instead
 int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* stopped = nullptr, const float* b16 = nullptr);
 int launch_cluster_pass(fos_problem* p);

@@ -81,7 +81,9 @@ int fos_lbfgs_direction_dd(const double* g, const double* S, const double* Y, in
 // the coefficient recursion is then replicated and every rank combines its own block of d.  g.d and d.d come out global.
 int fos_lbfgs_direction_cols(fos_problem* p, const double* g, const double* S, const double* Y, int hist, int head, int cap,
                              double* d_out, double* gd_out, double* work, int64_t work_doubles) {
-  if (!p || !p->col_sharded || !g || !d_out || !work || hist < 0 || cap < hist || (hist > 0 && (!S || !Y)) || head < 0 ||
+  if (!p) return fail(FOS_ERR_ARG, "fos_lbfgs_direction_cols: bad argument (null problem)");
+  if (int rc_ = need_squared(p, "fos_lbfgs_direction_cols")) return rc_;
+  if (!p->col_sharded || !g || !d_out || !work || hist < 0 || cap < hist || (hist > 0 && (!S || !Y)) || head < 0 ||
       (cap > 0 && head >= cap) || work_doubles < (int64_t)fos::VL_MAXPARTS * fos::VL_PSTRIDE)
     return fail(FOS_ERR_ARG, "fos_lbfgs_direction_cols: bad argument (needs a column-sharded problem and 64 x 256 doubles of work)");
   if (hist > fos::VL_MAXH) return fail(FOS_ERR_UNSUPPORTED, "fos_lbfgs_direction_cols: at most 10 pairs");
@@ -126,6 +128,7 @@ double fos_linesearch_step(fos_linesearch* ls, double stp, double f, double d) {
 int fos_lbfgs_minimize(fos_problem* p, double alpha2, int max_iter, double pgtol, double* x, double* hist,
                        double* iterates, float* fg_ms, int fg_cap, fos_lbfgs_result* res) {
   if (!p || !x || !res || max_iter < 0) return fail(FOS_ERR_ARG, "fos_lbfgs_minimize: bad argument");
+  if (int rc_ = need_squared(p, "fos_lbfgs_minimize")) return rc_;
   if (p->col_sharded)
     return fail(FOS_ERR_UNSUPPORTED, "fos_lbfgs_minimize: a column-sharded problem partitions the iterate - every scalar of "
                                      "the iteration is a sum over the ranks; use the driver above the ABI (LBFGSSolver.fit(cols=))");
@@ -329,6 +332,7 @@ int fos_lbfgs_minimize_multi(fos_problem* p, int nv, const float* B, int64_t ldb
     return fail(FOS_ERR_ARG, "fos_lbfgs_minimize_multi: bad argument (null pointer, nv outside 2..16, ldb < nv, ldx < n or "
                              "max_iter < 0)");
   if (ldx < p->n) return fail(FOS_ERR_ARG, "fos_lbfgs_minimize_multi: bad argument (ldx < n)");
+  if (int rc_ = need_squared(p, "fos_lbfgs_minimize_multi")) return rc_;
   if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_lbfgs_minimize_multi: sharded problems are not served");
   if (!pair_dd_multi_supported(p))
     return fail(FOS_ERR_UNSUPPORTED, "fos_lbfgs_minimize_multi: no multi-point fp64 pass for this shape (fit the columns one by one)");

@@ -618,6 +618,32 @@ const F32FoldVariant kF32Folds[] = {
     {fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_TRAIN>, fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_HELD>},
 };
 
+// The logistic forms of product 1 (the problem's loss is FOS_LOSS_LOGISTIC: b holds labels in [0, 1]), one entry per tile
+// variant of the tables above: store keeps R = sigma(A Y) - b for product 2, resid only sums the log-loss; train_store /
+// held_resid are the two with the fold masks of cross-validation.
+struct Bf16LogitVariant { Bf16Batch store, resid, train_store, held_resid; };
+const Bf16LogitVariant kBf16Logit[] = {
+    {fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
+     fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
+     fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC>,
+     fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC>},
+    {fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
+     fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
+     fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC>,
+     fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC>},
+};
+struct F32LogitVariant { F32Batch store, resid, train_store, held_resid; };
+const F32LogitVariant kF32Logit[] = {
+    {fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
+     fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
+     fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC>,
+     fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC>},
+    {fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
+     fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
+     fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC>,
+     fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC>},
+};
+
 // The grid of product 1 on `rows_total` rows: the tile variant (0: 64-row tile, 1: 128-row tile), the row groups per
 // workgroup and the number of workgroups (rows of q_part).
 struct BatchGrid { int variant; int64_t gpw, nwg; };
@@ -654,6 +680,13 @@ int launch_batch_product(fos_problem* p, const void* A, const float* b, int64_t 
   return FOS_OK;
 }
 
+int need_squared(const fos_problem* p, const char* fn) {
+  if (p && p->loss != FOS_LOSS_SQUARED)
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": not served on a logistic problem (fos_problem_set_loss); the logistic "
+                                     "loss runs through fos_fista_run_multi / _run_multi_folds and fos_residual_batch / _folds");
+  return FOS_OK;
+}
+
 bool fold_held_block(const int32_t* held, int nv, fos::FoldHeld* out) {
   for (int j = 0; j < fos::BT_NV; ++j) {
     const int32_t h = j < nv ? held[j] : -1;
@@ -676,6 +709,28 @@ int launch_batch_product_folds(fos_problem* p, const void* A, const float* b, in
     hipLaunchKernelGGL(rout ? vf.store_train : vf.resid_held, dim3((unsigned)g.nwg), dim3(fos::BT_THREADS), 0, p->stream,
                        (const float*)A, p->lda, b, 1, rows_total, (int)p->n, p->cand.xp, g.gpw, p->cand.q_part, rout,
                        (const int*)nullptr, fold_of_row, held);
+  LAUNCH_CHECK();
+  *nwg_out = (int)g.nwg;
+  return FOS_OK;
+}
+
+// Product 1 of a logistic problem on `rows` rows starting at A / b (the labels): R = sigma(A Y) - b into rout when given,
+// q_part[wg][16] the partial log-loss sums.  fold_of_row / held given: the masked forms, train-store with rout, heldout-resid
+// without.  Geometry as launch_batch_product.
+int launch_batch_product_logit(fos_problem* p, const void* A, const float* b, int64_t rows_total, float* rout, int* nwg_out,
+                               const uint8_t* fold_of_row, const fos::FoldHeld* held) {
+  const BatchGrid g = batch_grid(p, rows_total);
+  const Bf16LogitVariant& vq = kBf16Logit[g.variant];
+  const F32LogitVariant& vf = kF32Logit[g.variant];
+  const fos::FoldHeld hb = held ? *held : fos::FoldHeld{};
+  if (p->dtype == FOS_BF16)
+    hipLaunchKernelGGL(fold_of_row ? (rout ? vq.train_store : vq.held_resid) : (rout ? vq.store : vq.resid), dim3((unsigned)g.nwg),
+                       dim3(fos::BT_THREADS), 0, p->stream, (const fos::bf16_t*)A, p->lda, b, 1, rows_total, (int)p->n,
+                       (const unsigned short*)p->cand.xp.get(), g.gpw, p->cand.q_part, rout, (const int*)nullptr, fold_of_row, hb);
+  else
+    hipLaunchKernelGGL(fold_of_row ? (rout ? vf.train_store : vf.held_resid) : (rout ? vf.store : vf.resid), dim3((unsigned)g.nwg),
+                       dim3(fos::BT_THREADS), 0, p->stream, (const float*)A, p->lda, b, 1, rows_total, (int)p->n, p->cand.xp, g.gpw,
+                       p->cand.q_part, rout, (const int*)nullptr, fold_of_row, hb);
   LAUNCH_CHECK();
   *nwg_out = (int)g.nwg;
   return FOS_OK;
@@ -1164,14 +1219,36 @@ int fos_problem_create(fos_problem** out, const void* A, int64_t m, int64_t n, i
   return FOS_OK;
 }
 
+int fos_problem_set_loss(fos_problem* p, int loss) {
+  if (!p) return fail(FOS_ERR_ARG, "fos_problem_set_loss: null");
+  if (loss != FOS_LOSS_SQUARED && loss != FOS_LOSS_LOGISTIC) return fail(FOS_ERR_ARG, "fos_problem_set_loss: unknown loss");
+  if (loss == FOS_LOSS_LOGISTIC) {
+    if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_loss: a logistic problem needs b (the labels)");
+    if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_loss: sharded problems are not served");
+    if (!pair_dd_multi_supported(p))
+      return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_loss: the logistic loss runs on the matrix-core pair (aligned streaming "
+                                       "layout, 65..16384 columns)");
+  }
+  p->loss = loss;                    // no buffer depends on the loss: nothing to invalidate
+  return FOS_OK;
+}
+
+int fos_problem_get_loss(const fos_problem* p, int* loss) {
+  if (!p || !loss) return fail(FOS_ERR_ARG, "fos_problem_get_loss: null");
+  *loss = p->loss;
+  return FOS_OK;
+}
+
 int fos_problem_set_comm(fos_problem* p, fos_comm* c) {
   if (!p) return fail(FOS_ERR_ARG, "fos_problem_set_comm: null");
+  if (int rc_ = need_squared(p, "fos_problem_set_comm")) return rc_;
   p->comm = c;
   return invalidate(p, IN_COMM);
 }
 
 int fos_problem_set_comm_cols(fos_problem* p, fos_comm* c) {
   if (!p || !c) return fail(FOS_ERR_ARG, "fos_problem_set_comm_cols: null");
+  if (int rc_ = need_squared(p, "fos_problem_set_comm_cols")) return rc_;
   if (!vec_layout(p) || p->n <= tlr_max_n(p->dtype))
     return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_comm_cols: needs the streaming layout (aligned, more than 32 chunks of 16 bytes per row and rank)");
   // the two-phase column-block plan, whatever the width: r = sum_p A_p y_p - b is exchanged between the phases
@@ -1337,6 +1414,7 @@ int fos_problem_set_gbuf(fos_problem* p, float* gbuf) {
 
 int fos_gemv_pair(fos_problem* p, const float* y, float alpha2, float* grad, double* rr_out) {
   if (!p || !y || !grad) return fail(FOS_ERR_ARG, "fos_gemv_pair: null");
+  if (int rc_ = need_squared(p, "fos_gemv_pair")) return rc_;
   const float* ya = nullptr;
   int rc = aligned_vec(p, y, &ya);
   if (rc) return rc;
@@ -1352,6 +1430,7 @@ int fos_gemv_pair(fos_problem* p, const float* y, float alpha2, float* grad, dou
 
 int fos_gemv_pair_f64(fos_problem* p, const double* y, double alpha2, float* grad, double* rr_out) {
   if (!p || !y || !grad) return fail(FOS_ERR_ARG, "fos_gemv_pair_f64: null");
+  if (int rc_ = need_squared(p, "fos_gemv_pair_f64")) return rc_;
   if (p->pass.resident) {                           // small problem: one launch, fp64 throughout (resident.hpp)
     if (p->dtype == FOS_F32)
       hipLaunchKernelGGL(fos::gemv_pair_resident_kernel<float>, dim3(1), dim3(fos::RS_THREADS), 0, p->stream,
@@ -1453,6 +1532,8 @@ int fosapi::launch_pass_dd(fos_problem* p, const YSource& ys, double alpha2, con
 extern "C" {
 
 int fos_gemv_pair_dd(fos_problem* p, const double* x, double alpha2, double* grad_rr) {
+  if (!p || !x || !grad_rr) return fail(FOS_ERR_ARG, "fos_gemv_pair_dd: null");
+  if (int rc_ = need_squared(p, "fos_gemv_pair_dd")) return rc_;
   return fosapi::gemv_pair_dd_stamped(p, x, alpha2, grad_rr, nullptr, nullptr);
 }
 
@@ -1497,6 +1578,7 @@ extern "C" {
 
 int fos_residual_objective(fos_problem* p, const float* x, double* out3) {
   if (!p || !x || !out3) return fail(FOS_ERR_ARG, "fos_residual_objective: null");
+  if (int rc_ = need_squared(p, "fos_residual_objective")) return rc_;
   const float* xa = nullptr;
   int rc = aligned_vec(p, x, &xa);
   if (rc) return rc;
@@ -1512,8 +1594,34 @@ int fos_residual_objective(fos_problem* p, const float* x, double* out3) {
   return FOS_OK;
 }
 
+// fos_residual_batch / _folds on a logistic problem: out16[j] = sum of the log-loss of column j over all rows, or over the rows
+// of the fold it holds out.  Arguments are checked.
+static int residual_batch_logit(fos_problem* p, const char* fn, const float* X, int nv, double* out16, const uint8_t* fold_of_row,
+                                const fos::FoldHeld* held) {
+  if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the shape has no matrix-core pair");
+  int rc = ensure_batch_workspace(p);
+  if (rc) return rc;
+  if (p->dtype == FOS_BF16)
+    hipLaunchKernelGGL(fos::xq_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
+                       (int)p->cand.n_pad, nv, (unsigned short*)p->cand.xp.get());
+  else
+    hipLaunchKernelGGL(xp_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
+                       (int)p->cand.n_pad, nv, p->cand.xp);
+  LAUNCH_CHECK();
+  if ((rc = prof_mark(p, true))) return rc;
+  int nwg = 0;
+  if ((rc = launch_batch_product_logit(p, p->A, p->b, p->m, nullptr, &nwg, fold_of_row, held))) return rc;
+  if ((rc = prof_mark(p, false))) return rc;
+  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->cand.q_part, nwg, fos::BT_NV, out16);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
 int fos_residual_batch(fos_problem* p, const float* X, int nv, int use_b, double* out16) {
   if (!p || !X || !out16 || nv < 1 || nv > fos::BT_NV) return fail(FOS_ERR_ARG, "fos_residual_batch: bad argument");
+  if (!use_b)                        // ||A X_j||^2 is a squared-loss quantity
+    if (int rc = need_squared(p, "fos_residual_batch (use_b = 0)")) return rc;
+  if (p->loss == FOS_LOSS_LOGISTIC) return residual_batch_logit(p, "fos_residual_batch", X, nv, out16, nullptr, nullptr);
   if (!batch_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch: needs the fused path");
   int rc = ensure_batch_workspace(p);
   if (rc) return rc;
@@ -1530,6 +1638,7 @@ int fos_residual_batch(fos_problem* p, const float* X, int nv, int use_b, double
 int fos_residual_batch_rhs(fos_problem* p, const float* X, int nv, const float* B, int64_t ldb, double* out16) {
   if (!p || !X || !B || !out16 || nv < 1 || nv > fos::BT_NV || ldb < nv)
     return fail(FOS_ERR_ARG, "fos_residual_batch_rhs: bad argument (null pointer, nv outside 1..16 or ldb < nv)");
+  if (int rc_ = need_squared(p, "fos_residual_batch_rhs")) return rc_;
   if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_rhs: sharded problems are not served");
   if (!batch_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_rhs: needs the fused path");
   int rc = ensure_batch_workspace(p);
@@ -1554,6 +1663,7 @@ int fos_residual_batch_folds(fos_problem* p, const float* X, int nv, const uint8
                              "aligned or a held id outside -1..254)");
   if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: the problem has no b of its own");
   if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: sharded problems are not served");
+  if (p->loss == FOS_LOSS_LOGISTIC) return residual_batch_logit(p, "fos_residual_batch_folds", X, nv, out16, fold_of_row, &hb);
   if (!pair_dd_multi_supported(p))
     return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: the shape has no matrix-core pair");
   int rc = ensure_batch_workspace(p);
@@ -1579,6 +1689,7 @@ int fos_gemv_pair_dd_multi(fos_problem* p, const double* X, int nv, int64_t ldx,
   if (!p || !X || !B || !G || !rr || nv < 1 || nv > fos::BT_NV || ldb < nv || ldx < 1)
     return fail(FOS_ERR_ARG, "fos_gemv_pair_dd_multi: bad argument (null pointer, nv outside 1..16, ldb < nv or ldx < n)");
   if (ldx < p->n) return fail(FOS_ERR_ARG, "fos_gemv_pair_dd_multi: bad argument (ldx < n)");
+  if (int rc_ = need_squared(p, "fos_gemv_pair_dd_multi")) return rc_;
   if (!pair_dd_multi_supported(p)) return pair_dd_multi(p, fos::DdMultiCols{}, 0, 0u, alpha2, nullptr);
   fos::DdMultiCols c{};
   for (int j = 0; j < nv; ++j) {

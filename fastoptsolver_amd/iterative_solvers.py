@@ -1099,17 +1099,23 @@ def fista_delta(A, b, reg_type: str, alpha1: float, alpha2: float, delta: float,
 # ---------------------------------------------------------------------
 # Regularisation path (extension)
 # ---------------------------------------------------------------------
-def _run_path(prob, prms, max_iter, cols=None):
+def _run_path(prob, prms, max_iter, cols=None, lockstep_only=False):
     """One state machine per parameter set on `prob`, advanced max_iter iterations in lockstep groups (fos_fista_run_multi;
-    what it does not serve runs one by one); one grad_call_times entry per lockstep iteration per group.  The handles."""
+    what it does not serve runs one by one); one grad_call_times entry per lockstep iteration per group.  The handles.
+    lockstep_only (a logistic problem: the lockstep is its one form): groups of 16, a group of one included, and a refusal
+    raises."""
     handles = [_new_state(prob, prm) for prm in prms]
     gtimer = _EventTimer(grad_call_times)
     # up to 4 weights: the multi-vector VALU pass where the shape has one; up to 16: the matrix-core pass
-    width = 4 if len(handles) <= 4 and cols is None else 16
+    width = 4 if len(handles) <= 4 and cols is None and not lockstep_only else 16
     for i in range(0, len(handles), width):
         group = handles[i:i + width]
         ev = gtimer.start()
-        if len(group) == 1 or not _core.run_multi(group, max_iter):
+        if lockstep_only:
+            if not _core.run_multi(group, max_iter):
+                raise _lib.FosError("fos_fista_run_multi refused the lockstep: " +
+                                    prob.lib.fos_last_error().decode("utf-8", "replace"))
+        elif len(group) == 1 or not _core.run_multi(group, max_iter):
             for st in group:
                 st.run(max_iter)
         gtimer.stop(ev, max_iter)

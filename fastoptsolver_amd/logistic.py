@@ -1,0 +1,138 @@
+"""Sparse logistic regression on the matrix-core lockstep (extension; the reference has squared loss only).
+
+    minimise   sum_i log(1 + exp(a_i.x)) - y_i a_i.x  +  alpha1 ||x||_1  +  0.5 alpha2 ||x||^2 ,   labels y in [0, 1]
+
+The gradient of the data term is A^T (sigma(Ax) - y): the lockstep of ``fista_path`` / ``fista_cv`` with ONE line of product
+1's epilogue changed (csrc/batch_trial.hpp, LOSS_LOGISTIC) - product 2, the updates, the per-column restarts and stops on
+the device and the fold masks are the launches of the squared loss.  The loss belongs to the problem handle
+(``prepare(A, y, loss="logistic")``, fos_problem_set_loss); every entry point that would answer with a squared-loss quantity
+refuses such a handle.  An intercept is a constant column appended by the caller.
+"""
+from __future__ import annotations
+
+import collections
+
+import numpy as np
+import torch
+
+from . import _core, _lib
+from . import iterative_solvers as _its
+
+LogisticCVResult = collections.namedtuple("LogisticCVResult", "alphas logloss mean_logloss best x coefs info")
+
+
+def _check_path_args(alphas, delta):
+    alphas = [(float(a1), float(a2)) for a1, a2 in alphas]
+    if not alphas:
+        raise ValueError("alphas: at least one (alpha1, alpha2) pair is needed")
+    if delta is not None and not delta > 2:
+        raise ValueError("delta: FISTA-Δ needs delta > 2")
+    return alphas
+
+
+def _problem(A, y, dtype):
+    """The logistic handle on (A, y): a prepared one as it is, anything else bound (and padded) here."""
+    if isinstance(A, _core.Problem):
+        if A.loss != "logistic":
+            raise ValueError('A was prepared for the squared loss: use prepare(A, y, loss="logistic")')
+        return A
+    if y is None:
+        raise ValueError("the labels y are needed")
+    return _core.Problem(A, y, dtype, None, "logistic")
+
+
+def _params_of(prob, alphas, L, t_init_factor, delta, tol_ratio, adaptive_restart, restart_threshold):
+    """L of the logistic data term (lambda_max(A^T A) / 4 unless given) and one parameter set per weight."""
+    L_val = float(L) if L is not None else _its.estimate_lipschitz(prob) / 4.0
+    mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
+    return [_its._params(_its._tau(L_val, a2, t_init_factor), a1, a2, mode=mode, delta=delta, tol_ratio=tol_ratio,
+                         adaptive_restart=adaptive_restart, restart_threshold=restart_threshold) for a1, a2 in alphas]
+
+
+def logistic_path(A, y, alphas, t_init_factor: float = 1.0, max_iter: int = 500, *, delta=None, L=None, dtype=None,
+                  tol_ratio: float = 0.0, adaptive_restart: bool = False, restart_threshold: float = 1.0,
+                  return_info: bool = False):
+    """Sparse logistic regression of the labels ``y`` (in [0, 1]) on A for several weights at once.
+
+    ``alphas`` is a sequence of ``(alpha1, alpha2)`` pairs; the result is the list of solutions, one per pair, and with
+    ``return_info=True`` also ``[(iterations, stop_code), ...]``.  The pairs advance in lockstep groups of up to 16 columns
+    on the matrix cores (fos_fista_run_multi on a logistic problem): two GEMM-shaped products per iteration for the whole
+    group.  A single pair is a one-column lockstep - there is no one-read single-target logistic pass, so a single fit
+    reads A twice per iteration; that is accepted here.
+
+    ``L``, when not given, is ``estimate_lipschitz(A) / 4`` (one power iteration, one draw from the global NumPy stream, like
+    ``fista_path``): sigma' <= 1/4 bounds the Hessian A^T diag(sigma') A by A^T A / 4.  When given it is the constant of the
+    logistic data term and used as it is.  The step is ``t_init_factor / (L + alpha2)``.
+
+    Contract: each result is FISTA (FISTA-Δ with ``delta`` > 2) on the logistic objective from x0 = 0 with that step, under
+    the momentum, restart (``adaptive_restart`` / ``restart_threshold``) and ratio-stop (``tol_ratio``) rules of the
+    reference's loop, decided per column on the device.  There is no ``tol`` (the gradient-norm rule), no backtracking and
+    no sharding.  A: an array / tensor (zero-padded on the device so that every shape up to 16384 columns is served: see
+    ``prepare``) or a ``prepare(A, y, loss="logistic")`` handle (``y`` may then be None)."""
+    _its.reset_metrics()
+    alphas = _check_path_args(alphas, delta)
+    prob = _problem(A, y, dtype)
+    prms = _params_of(prob, alphas, L, t_init_factor, delta, tol_ratio, adaptive_restart, restart_threshold)
+    handles = _its._run_path(prob, prms, max_iter, lockstep_only=True)
+    xs = [_core.from_device_vec(st.x_tensor(), prob.like) for st in handles]
+    if return_info:
+        stats = [st.status() for st in handles]
+        return xs, [(int(s.k), int(s.stopped)) for s in stats]
+    return xs
+
+
+def logistic_cv(A, y, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int = 500, *, delta=None, L=None, dtype=None,
+                tol_ratio: float = 0.0, adaptive_restart: bool = False, restart_threshold: float = 1.0, refit: bool = True,
+                return_coefs: bool = False):
+    """K-fold cross-validation of a logistic regularisation path: ``fista_cv`` with the log-loss.
+
+    ``folds`` as in ``fista_cv`` (an int K >= 2 or one fold id per row), validated before any device work.  All K x L fits
+    are masked columns of the lockstep on the one device copy of A (fos_fista_run_multi_folds on a logistic problem); the
+    held-out log-losses of a group come from one further pass with the complementary mask.  ``L`` comes from the whole A
+    (``estimate_lipschitz(A) / 4`` unless given) and is valid for every training set: lambda_max(A_train^T A_train) <=
+    lambda_max(A^T A).  Contract: ``coefs[:, f, a]`` is what ``logistic_path(A[train_f], y[train_f], [alphas[a]], ..., L=L)``
+    returns.  No fold-by-fold slow path exists: padding makes every shape up to 16384 columns served, the rest raises.
+
+    Returns ``LogisticCVResult(alphas, logloss, mean_logloss, best, x, coefs, info)``: ``logloss[f, a]`` the held-out MEAN
+    log-loss (K x L float64 ndarray), ``mean_logloss`` its mean over the folds, ``best`` the argmin (first on ties), ``x``
+    the fit on all rows at ``alphas[best]`` (``refit=True``; else None), ``coefs`` the n x K x L fits
+    (``return_coefs=True``; else None), ``info[f][a] = (iterations, stop_code)``."""
+    _its.reset_metrics()
+    alphas = _check_path_args(alphas, delta)
+    m = A.m if isinstance(A, _core.Problem) else int(A.shape[0] if hasattr(A, "shape") else np.shape(A)[0])
+    ids, sizes = _its._cv_folds(folds, m)
+    K = len(sizes)
+    prob = _problem(A, y, dtype)
+    prms = _params_of(prob, alphas, L, t_init_factor, delta, tol_ratio, adaptive_restart, restart_threshold)
+    out = _its._cv_lockstep(prob, ids, K, prms, max_iter)
+    if out is None:
+        raise _lib.FosError("fos_fista_run_multi_folds refused the logistic lockstep: " +
+                            prob.lib.fos_last_error().decode("utf-8", "replace"))
+    X, total, info = out
+    logloss = total / sizes[:, None].astype(np.float64)
+    mean_logloss = logloss.mean(axis=0)
+    best = int(np.argmin(mean_logloss))
+    x = None
+    if refit:
+        st =_its._run_path(prob, [prms[best]], max_iter, lockstep_only=True)[0]
+        x = _core.from_device_vec(st.x_tensor(), prob.like)
+    coefs = _core.from_device_vec(X, prob.like) if return_coefs else None
+    return LogisticCVResult(alphas, logloss, mean_logloss, best, x, coefs, info)
+
+
+def logistic_objective(x, A, y, alpha1, alpha2):
+    """sum_i log(1 + exp(a_i.x)) - y_i a_i.x + alpha1 ||x||_1 + 0.5 alpha2 ||x||^2 with the data term from the device
+    (fos_residual_batch on a logistic problem; x is rounded to fp32 for the pass over A).  ``x``: a vector (returns a float) or
+    an n x k block (returns k float64 values), 16 columns per pass.  Synchronises."""
+    prob = _problem(A, y, None)
+    xt = x.detach() if _core.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=np.float64))
+    vector = xt.dim() == 1
+    X = (xt.reshape(-1, 1) if vector else xt).to(device=prob.device, dtype=torch.float64)
+    if X.dim() != 2 or X.shape[0] != prob.n:
+        raise ValueError(f"x: a vector of length {prob.n} or an {prob.n} x k block expected")
+    nll = []
+    for j0 in range(0, X.shape[1], 16):
+        nll += prob.residual_batch(X[:, j0:j0 + 16], use_b=True)
+    Xh = X.cpu().numpy()
+    val = np.asarray(nll, dtype=np.float64) + float(alpha1) * np.abs(Xh).sum(axis=0) + 0.5 * float(alpha2) * (Xh * Xh).sum(axis=0)
+    return float(val[0]) if vector else val

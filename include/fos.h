@@ -29,6 +29,7 @@ enum { FOS_OK = 0, FOS_ERR_ARG = -1, FOS_ERR_HIP = -2, FOS_ERR_STATE = -3, FOS_E
 enum { FOS_F32 = 0, FOS_BF16 = 1 };                    /* element type of A */
 enum { FOS_MODE_FISTA = 0, FOS_MODE_DELTA = 1, FOS_MODE_ISTA = 2 };
 enum { FOS_PROX_L1 = 0, FOS_PROX_ENET = 1 };
+enum { FOS_LOSS_SQUARED = 0, FOS_LOSS_LOGISTIC = 1 };  /* fos_problem_set_loss */
 enum { FOS_STOP_NONE = 0, FOS_STOP_STEP = 1, FOS_STOP_RATIO = 2, FOS_STOP_GRAD = 3, FOS_STOP_LS_STALL = 4 };
 
 enum { FOS_PLAN_NO_RESIDENT = 1, FOS_PLAN_NO_TALL = 2, FOS_PLAN_NO_WIDE = 4, FOS_PLAN_NO_COLBLOCK = 8,
@@ -120,6 +121,27 @@ int fos_problem_tune_dd(fos_problem* p, int workgroups);
 /* Use a caller-owned gradient buffer (n + 4 floats, 16-byte aligned) instead of the internal one, e.g. a
  * torch tensor that torch.distributed all-reduces between fos_fista_grad and fos_fista_update. */
 int fos_problem_set_gbuf(fos_problem* p, float* gbuf);
+/* The loss of the data term (FOS_LOSS_*; FOS_LOSS_SQUARED after fos_problem_create).  FOS_LOSS_LOGISTIC: b holds labels in
+ * [0, 1] and the data term is sum_i log(1 + exp(a_i.x)) - b_i a_i.x (sparse logistic regression; gradient A^T (sigma(Ax) - b),
+ * Lipschitz constant lambda_max(A^T A) / 4).  On a logistic problem
+ *   - fos_fista_run_multi (any nv in 1..16, one included) and fos_fista_run_multi_folds minimise the logistic objective: always
+ *     the two matrix-core products per iteration, plain or device-controlled; the gradient-norm rule, the fp64 split gradient
+ *     and a device-held step are refused (FOS_ERR_UNSUPPORTED), as fos_fista_run_multi_folds refuses them;
+ *   - fos_residual_batch with use_b = 1 gives out16[j] = sum_i l(a_i.X_j, b_i), the negative log-likelihood of column j, and
+ *     fos_residual_batch_folds the same sum over column j's held-out rows;
+ *   - the entry points that touch neither b nor a residual work as before: fos_power_iter, fos_problem_plan / _replan / _tune*,
+ *     fos_problem_profile*, fos_problem_set_stream / _set_gbuf, fos_fista_create / _destroy / _reset / _set_tau,
+ *     fos_fista_status_get / _get_x;
+ *   - every other entry point that forms a residual, gradient or objective with b returns FOS_ERR_UNSUPPORTED before any launch
+ *     or change of handle state: the single-vector passes (fos_gemv_pair*, fos_residual_objective, fos_fista_grad* / _update),
+ *     every single-handle run form, the trial, backtracking and recorded forms, fos_residual_batch with use_b = 0,
+ *     fos_residual_batch_rhs, fos_fista_run_multi_rhs, every fos_lbfgs_* entry point on the problem, and
+ *     fos_problem_set_comm / _set_comm_cols.
+ * FOS_ERR_ARG (checked before any HIP call): null p, an unknown loss.  FOS_ERR_UNSUPPORTED for FOS_LOSS_LOGISTIC on a problem
+ * without b, a sharded one, or a shape without the matrix-core pair (aligned streaming layout, 65..16384 columns).  No buffer
+ * depends on the loss; nothing is replanned. */
+int fos_problem_set_loss(fos_problem* p, int loss);
+int fos_problem_get_loss(const fos_problem* p, int* loss);
 
 /* ---- row-sharded problems (the reference is single-process) --------------------------------------------
  * One process per GPU; each rank binds ITS rows of A and b to a fos_problem and attaches a communicator.  From then on
