@@ -75,6 +75,19 @@ def upload_matrix(src, out):
     return out
 
 
+def checked_weights(w, m):
+    """Sample weights as a float64 tensor where they live: m entries, finite, >= 0 and not all zero - ValueError otherwise.
+    Checked once, before any device work of the problem."""
+    t = (w.detach() if is_tensor(w) else torch.from_numpy(np.array(w, dtype=np.float64))).to(torch.float64)
+    if t.dim() != 1 or t.numel() != m:
+        raise ValueError(f"sample_weight must have m = {m} entries, got shape {tuple(t.shape)}")
+    if not bool((torch.isfinite(t) & (t >= 0)).all()):
+        raise ValueError("sample_weight must be finite and >= 0")
+    if not bool((t > 0).any()):
+        raise ValueError("sample_weight must not be all zero")
+    return t
+
+
 class Like:
     """What the caller handed in (so results come back as the same kind) without keeping the object alive."""
 
@@ -104,7 +117,7 @@ class Problem:
     Build it once with ``prepare(A, b)`` and pass it wherever the solvers take ``A`` to avoid re-uploading A.
     """
 
-    def __init__(self, A, b=None, dtype=None, pad=None, loss="squared"):
+    def __init__(self, A, b=None, dtype=None, pad=None, loss="squared", sample_weight=None):
         """loss: "squared" (b is the target of 0.5 ||Ax - b||^2) or "logistic" (b holds labels in [0, 1]; the data term is the
         log-loss, served by `logistic_path` / `logistic_cv` / `logistic_objective` only: fos_problem_set_loss).
         pad: zero-pad the columns of the device copy of A to the fused kernel's granularity (4 fp32 / 8 bf16
@@ -114,9 +127,14 @@ class Problem:
         enough for it to matter (m*n >= 2^20: the padded single pass is 3-14x faster from there on); small ragged problems
         keep the fp64-accumulating two-pass path.  A logistic problem runs on the matrix-core pair alone, so for it None means
         always: rows are padded to the granularity, and to 68 fp32 / 72 bf16 columns when n <= 64 - every shape up to 16384
-        device columns is served; more raise ValueError."""
+        device columns is served; more raise ValueError.
+        sample_weight: m per-row weights w_i >= 0 of the data term (`prepare_weighted`; fos_row_weights_bind).  A weighted problem
+        runs on the matrix-core pair alone as a logistic one does and is padded by the same rules."""
         if loss not in LOSSES:
             raise ValueError(f"loss: one of {sorted(LOSSES)} expected, got {loss!r}")
+        pair_only = loss == "logistic" or sample_weight is not None      # served by the matrix-core pair alone
+        if sample_weight is not None:                                    # before any device work
+            sample_weight = checked_weights(sample_weight, int(A.shape[0] if hasattr(A, "shape") else np.shape(A)[0]))
         require_gpu()
         lib = _lib.load()
         self.like = Like(A)
@@ -136,9 +154,9 @@ class Problem:
         fused_ok = borrowable and n % gran == 0 and (At.stride(0) % gran == 0 or m == 1) and At.data_ptr() % 16 == 0
         if pad is None:
             # n <= 64 runs the row-per-thread kernel, which takes ragged / misaligned rows as they are
-            pad = loss == "logistic" or ((not fused_ok) and m * n >= (1 << 20) and n > 64)
+            pad = pair_only or ((not fused_ok) and m * n >= (1 << 20) and n > 64)
         n_dev = n
-        n_min = LOGIT_MIN_N["bf16" if want_bf16 else "f32"] if loss == "logistic" and n <= 64 else 0
+        n_min = LOGIT_MIN_N["bf16" if want_bf16 else "f32"] if pair_only and n <= 64 else 0
         if pad and (not fused_ok or n < n_min):
             n_dev = max((n + gran - 1) // gran * gran, n_min)
             Ap = torch.zeros(m, n_dev, dtype=tdtype, device=dev)
@@ -158,9 +176,15 @@ class Problem:
         self.device = At.device
         self.dtype = "bf16" if want_bf16 else "f32"
         self.loss = loss
-        if loss == "logistic" and n_dev > LOGIT_MAX_N:
-            raise ValueError(f"a logistic problem is limited to {LOGIT_MAX_N} device columns, got {n_dev}")
+        if pair_only and n_dev > LOGIT_MAX_N:
+            raise ValueError(f"a logistic or weighted problem is limited to {LOGIT_MAX_N} device columns, got {n_dev}")
+        self.sample_weight = None
         self._bind(b, lib)
+        if sample_weight is not None:
+            # zero-padded to a multiple of 4 entries: product 1 fetches the weights of 4 rows with one 16-byte load
+            buf = torch.zeros((m + 3) // 4 * 4, dtype=torch.float32, device=self.device)
+            buf[:m] = sample_weight.to(device=self.device, dtype=torch.float32)
+            self.set_sample_weight(buf[:m])
 
     def sibling(self, b):
         """Another handle on the SAME device A (borrowed as it is: no upload, no padding) with its own b - the column-by-column
@@ -168,8 +192,10 @@ class Problem:
         sib = Problem.__new__(Problem)
         sib.like = self.like
         sib.A, sib.m, sib.n, sib.n_dev, sib.lda = self.A, self.m, self.n, self.n_dev, self.lda
-        sib.device, sib.dtype, sib.loss = self.device, self.dtype, self.loss
+        sib.device, sib.dtype, sib.loss, sib.sample_weight = self.device, self.dtype, self.loss, None
         sib._bind(b, self.lib)
+        if self.sample_weight is not None:          # the rows are the same rows: a sibling of a weighted handle is weighted
+            sib.set_sample_weight(self.sample_weight)
         return sib
 
     def _bind(self, b, lib):
@@ -196,6 +222,13 @@ class Problem:
             if self.loss != "squared":
                 _lib.check(lib.fos_problem_set_loss(self.h, LOSSES[self.loss]), "fos_problem_set_loss")
         self.lib = lib
+
+    def set_sample_weight(self, w):
+        """Bind the fp32 device vector `w` (m checked weights, 16-byte aligned, readable up to m rounded up to 4) or, with None,
+        detach the weights (fos_row_weights_bind): the handle is an unweighted one again."""
+        with self.ctx():
+            _lib.check(self.lib.fos_row_weights_bind(ptr(w), self.h), "fos_row_weights_bind")
+        self.sample_weight = w
 
     def __del__(self):
         h = getattr(self, "h", None)
@@ -357,6 +390,18 @@ class Problem:
             return None
         return self.scratch[:nv].cpu().tolist()
 
+    def gram_apply(self, X):
+        """A^T W A X_j for the nv <= 16 columns of X (n x nv), W the bound weights or the identity (fos_gram_apply): an n x nv
+        float32 device tensor.  Enqueues only."""
+        X = torch.as_tensor(X, device=self.device, dtype=torch.float32)
+        nv = X.shape[1]
+        Xf = torch.zeros(self.n_dev, 16, dtype=torch.float32, device=self.device)
+        Xf[: X.shape[0], :nv] = X
+        G = torch.empty(nv, self.n_dev, dtype=torch.float32, device=self.device)
+        with self.ctx():
+            _lib.check(self.lib.fos_gram_apply(ptr(Xf), nv, self.h, ptr(G)), "fos_gram_apply")
+        return self.vec_out(G).t()
+
     def power_iter(self, v0, n_iter=100, tol=1e-6):
         v = self.vec_in(v0).clone()
         L = C.c_double()
@@ -376,6 +421,22 @@ def prepare(A, b=None, dtype=None, pad=None, *, loss="squared"):
             raise ValueError("this Problem was prepared for the squared loss")
         return A
     return Problem(A, b, dtype, pad, loss)
+
+
+def prepare_weighted(A, b, sample_weight, dtype=None, *, loss="squared"):
+    """``prepare`` with per-row sample weights w_i >= 0: the data term is sum_i w_i 0.5 (a_i.x - b_i)^2, or with
+    ``loss="logistic"`` sum_i w_i (log(1 + e^{a_i.x}) - b_i a_i.x).  The weights belong to the handle (``.sample_weight``, the
+    fp32 device vector): pass it as ``A`` (``b`` None) to ``fista_path`` / ``fista_cv`` (squared loss) or ``logistic_path`` /
+    ``logistic_cv`` / ``logistic_objective``, which then run on the matrix-core lockstep alone; ``estimate_lipschitz(handle)``
+    is lambda_max(A^T W A).  Padded as a logistic problem is; every solver that would answer with an unweighted quantity
+    refuses the handle.  ValueError for weights that are not m finite values >= 0 or are all zero."""
+    if isinstance(A, Problem):
+        raise ValueError("prepare_weighted binds an array or tensor; this is already a Problem")
+    if sample_weight is None:
+        raise ValueError("sample_weight is needed")
+    if b is None:
+        raise ValueError("a weighted problem needs b")
+    return Problem(A, b, dtype, None, loss, sample_weight=sample_weight)
 
 
 def as_problem(A, b, dtype=None):

@@ -63,6 +63,9 @@ SIGNATURES = {
     "fos_problem_set_stream": (_i32, [_vp, _vp]),
     "fos_problem_set_loss": (_i32, [_vp, _i32]),
     "fos_problem_get_loss": (_i32, [_vp, C.POINTER(_i32)]),
+    "fos_row_weights_bind": (_i32, [_vp, _vp]),
+    "fos_row_weights_get": (_i32, [C.POINTER(_vp), _vp]),
+    "fos_gram_apply": (_i32, [_vp, _i32, _vp, _vp]),
     "fos_problem_replan": (_i32, [_vp, C.c_uint]),
     "fos_comm_unique_id": (_i32, [C.c_char_p]),
     "fos_comm_create": (_i32, [C.POINTER(_vp), C.c_char_p, _i32, _i32]),

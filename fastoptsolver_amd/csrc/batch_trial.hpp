@@ -132,6 +132,17 @@ __device__ __forceinline__ float fold_mask(float v, unsigned ids4, int r, unsign
   return (FOLD == FOLD_TRAIN ? is_held : !is_held) ? 0.f : v;
 }
 
+// Per-row sample weights of product 1's epilogue (fos_row_weights_bind).  A lane's 4 consecutive rows start at a multiple of 4:
+// one aligned 16-byte load fetches their weights (row_weight is 16-byte aligned and readable up to m rounded up to 4; the 16
+// lanes of a row group read the same address).  A group past the last row reads the last group's weights, as fold_ids_of does:
+// the load stays unconditional and in bounds.
+__device__ __forceinline__ f32x4 row_weights_of(const float* __restrict__ row_weight, int64_t row0, int64_t m) {
+  const int64_t last = (m - 1) & ~(int64_t)3;
+  return *reinterpret_cast<const f32x4*>(row_weight + (row0 < m ? row0 : last));
+}
+// The weights have arrived before the epilogue ends (fold_ids_settle: the steady state keeps its counted vmcnt).
+__device__ __forceinline__ void row_weights_settle(const f32x4& w4) { asm volatile("" ::"v"(w4.x), "v"(w4.y), "v"(w4.z), "v"(w4.w)); }
+
 // Loss of product 1's epilogue.  SQUARED: R = A Y - b, q = sum R^2.  LOGISTIC (labels b in [0, 1], z = a_i . y_j):
 // R = sigma(z) - b, the derivative of the log-loss l(z, b) = log(1 + e^z) - b z, and q = sum l.  Everything downstream
 // (product 2, the slab sums, the updates) sees only R.
@@ -155,7 +166,9 @@ __device__ __forceinline__ void logistic_terms(float z, float label, float* v, f
 // held.id[candidate], see above; the tile loop is the same.
 // LOSS (LOSS_LOGISTIC): the epilogue forms sigma(A_i . X_j) - b_i and sums the log-loss instead (logistic_terms above; b is
 // the label vector, use_b is 1, BBLOCK false); the fold mask applies to both; the tile loop is the same.
-template <int RB, bool STORE_R = false, bool BBLOCK = false, int FOLD = FOLD_OFF, int LOSS = LOSS_SQUARED>
+// WEIGHT (row_weight[row] >= 0, BBLOCK false): the stored residual is w_i r_ij and the sum is sum_i w_i r_ij^2 (squared) or
+// sum_i w_i l_ij (logistic): the weight multiplies after the residual / the logistic pair is formed and before the fold mask.
+template <int RB, bool STORE_R = false, bool BBLOCK = false, int FOLD = FOLD_OFF, int LOSS = LOSS_SQUARED, bool WEIGHT = false>
 __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const float* __restrict__ A, int64_t lda,
                                                                         const float* __restrict__ b, int use_b,
                                                                         int64_t m, int n,
@@ -165,7 +178,8 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const f
                                                                         float* __restrict__ rout = nullptr,
                                                                         const int* __restrict__ stopped = nullptr,
                                                                         const uint8_t* __restrict__ fold_of_row = nullptr,
-                                                                        FoldHeld held = FoldHeld{}) {
+                                                                        FoldHeld held = FoldHeld{},
+                                                                        const float* __restrict__ row_weight = nullptr) {
   if (stopped != nullptr && *stopped != 0) return;          // parked pipeline (solver stopped / line search stalled)
   constexpr int ROWS = BT_ROWS * RB;              // RB 16-row blocks per wave share each candidate fragment read
   constexpr int A_LOADS = BT_A_LOADS * RB;
@@ -240,6 +254,11 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const f
         const int64_t row0 = (g_lo + t / ktiles) * ROWS + 16 * (wave * RB + rb) + 4 * (lane >> 4);
         unsigned ids4 = 0u;
         if constexpr (FOLD != FOLD_OFF) ids4 = fold_ids_of(fold_of_row, row0, m);
+        f32x4 w4 = f32x4{1.f, 1.f, 1.f, 1.f};
+        if constexpr (WEIGHT) {
+          static_assert(!BBLOCK, "the weighted epilogue is not combined with several right-hand sides");
+          w4 = row_weights_of(row_weight, row0, m);
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int64_t row = row0 + r;
@@ -249,6 +268,7 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const f
               static_assert(!BBLOCK, "the logistic epilogue reads one label vector");
               float l;
               logistic_terms(v, b[row], &v, &l);
+              if constexpr (WEIGHT) { v *= w4[r]; l *= w4[r]; }
               v = fold_mask<FOLD>(v, ids4, r, held_id);
               l = fold_mask<FOLD>(l, ids4, r, held_id);
               qsum += (double)l;
@@ -258,13 +278,20 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const f
               } else {
                 if (use_b) v -= b[row];
               }
-              v = fold_mask<FOLD>(v, ids4, r, held_id);
-              qsum += (double)v * (double)v;
+              if constexpr (WEIGHT) {
+                const float r_plain = v;                      // sum w r^2 = (w r) r: the weight enters the sum once
+                v = fold_mask<FOLD>(v * w4[r], ids4, r, held_id);
+                qsum += (double)v * (double)r_plain;
+              } else {
+                v = fold_mask<FOLD>(v, ids4, r, held_id);
+                qsum += (double)v * (double)v;
+              }
             }
             if constexpr (STORE_R) rout[row * BT_NV + (lane & 15)] = v;      // 16 lanes: one 64-byte row of R
           }
         }
         if constexpr (FOLD != FOLD_OFF) fold_ids_settle(ids4);
+        if constexpr (WEIGHT) row_weights_settle(w4);
         acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
         acc_odd[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
@@ -406,14 +433,16 @@ static __global__ void xq_pack_kernel(const float* __restrict__ X, int n, int n_
 // RB = 16-row blocks per wave (the candidate fragments read from LDS are reused for RB row blocks: X is 96 bytes per
 // column against 32 bytes of A per row block, so LDS traffic per byte of A falls with RB); COLS = bf16 columns per tile.
 // Requirements: n % 8 == 0, lda % 8 == 0, A 16-byte aligned, Xq zero-padded to n_pad (a multiple of 128).
-// BBLOCK: b is the m x 16 right-hand-side block, FOLD: the fold mask of the epilogue, LOSS: the logistic epilogue, all as in
-// residual_batch_mfma_kernel.
-template <int RB, int COLS, bool STORE_R = false, bool BBLOCK = false, int FOLD = FOLD_OFF, int LOSS = LOSS_SQUARED>
+// BBLOCK: b is the m x 16 right-hand-side block, FOLD: the fold mask of the epilogue, LOSS: the logistic epilogue, WEIGHT: the
+// per-row weights, all as in residual_batch_mfma_kernel.
+template <int RB, int COLS, bool STORE_R = false, bool BBLOCK = false, int FOLD = FOLD_OFF, int LOSS = LOSS_SQUARED,
+          bool WEIGHT = false>
 __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_bf16_kernel(
     const bf16_t* __restrict__ A, int64_t lda, const float* __restrict__ b, int use_b, int64_t m, int n,
     const unsigned short* __restrict__ xq, int64_t groups_per_wg, double* __restrict__ q_part,
     float* __restrict__ rout = nullptr, const int* __restrict__ stopped = nullptr,
-    const uint8_t* __restrict__ fold_of_row = nullptr, FoldHeld held = FoldHeld{}) {
+    const uint8_t* __restrict__ fold_of_row = nullptr, FoldHeld held = FoldHeld{},
+    const float* __restrict__ row_weight = nullptr) {
   if (stopped != nullptr && *stopped != 0) return;
   constexpr int ROWS = 64 * RB;
   constexpr int STRIDE = COLS + 8;
@@ -496,6 +525,11 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_bf16_kernel(
         const int64_t row0 = (g_lo + t / ktiles) * ROWS + 16 * (wave * RB + rb) + 4 * (lane >> 4);
         unsigned ids4 = 0u;
         if constexpr (FOLD != FOLD_OFF) ids4 = fold_ids_of(fold_of_row, row0, m);
+        f32x4 w4 = f32x4{1.f, 1.f, 1.f, 1.f};
+        if constexpr (WEIGHT) {
+          static_assert(!BBLOCK, "the weighted epilogue is not combined with several right-hand sides");
+          w4 = row_weights_of(row_weight, row0, m);
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int64_t row = row0 + r;
@@ -505,6 +539,7 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_bf16_kernel(
               static_assert(!BBLOCK, "the logistic epilogue reads one label vector");
               float l;
               logistic_terms(v, b[row], &v, &l);
+              if constexpr (WEIGHT) { v *= w4[r]; l *= w4[r]; }
               v = fold_mask<FOLD>(v, ids4, r, held_id);
               l = fold_mask<FOLD>(l, ids4, r, held_id);
               qsum += (double)l;
@@ -514,13 +549,20 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_bf16_kernel(
               } else {
                 if (use_b) v -= b[row];
               }
-              v = fold_mask<FOLD>(v, ids4, r, held_id);
-              qsum += (double)v * (double)v;
+              if constexpr (WEIGHT) {
+                const float r_plain = v;                      // sum w r^2 = (w r) r: the weight enters the sum once
+                v = fold_mask<FOLD>(v * w4[r], ids4, r, held_id);
+                qsum += (double)v * (double)r_plain;
+              } else {
+                v = fold_mask<FOLD>(v, ids4, r, held_id);
+                qsum += (double)v * (double)v;
+              }
             }
             if constexpr (STORE_R) rout[row * BT_NV + (lane & 15)] = v;
           }
         }
         if constexpr (FOLD != FOLD_OFF) fold_ids_settle(ids4);
+        if constexpr (WEIGHT) row_weights_settle(w4);
         acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
         acc_odd[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
       }

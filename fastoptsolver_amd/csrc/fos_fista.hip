@@ -682,6 +682,44 @@ static fos::MultiUpdate multi_update(fos_fista* const* fs, int nv, bool controll
 // likewise.  Product 2 and the updates see a masked R and are the same launches.
 // A logistic problem (fos_problem_set_loss): product 1 is the logistic form, R = sigma(A_panel Y) - b with or without the fold
 // mask (launch_batch_product_logit); the two-product form as well, and everything after product 1 is the same.
+// A problem with row weights (fos_row_weights_bind): product 1 is the weighted form of its loss, R = w (A_panel Y - b) or
+// w (sigma(A_panel Y) - b) (launch_batch_product_weighted); the two-product form, and everything after product 1 is the same.
+
+// Row splits of product 2 in the two-product form: the planned ones, or - on a problem planned for the cluster form, whose slab
+// count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated.
+static int two_product_splits(const fos_problem* p, int* g_splits) {
+  *g_splits = p->multi.gram_splits;
+  if (p->multi.cp_cs) {
+    *g_splits = (int)((p->multi.panel_rows + p->multi.gram_rows_per_split - 1) / p->multi.gram_rows_per_split);
+    if (*g_splits > p->multi.gram_splits)
+      return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs / _folds / logistic loss / row weights: the cluster layout of this "
+                                       "problem has too few slabs for the two-product form");
+  }
+  return FOS_OK;
+}
+
+// Product 2 of fos_gram_apply on one row panel (the launches of run_multi_mfma, whose own stay in its body): slabs16[split][16][n]
+// (+)= R_panel^T A_panel, the panel again from the Infinity Cache.
+static int launch_gram_panel(fos_problem* p, const char* Ap, int64_t rows, int g_splits, bool accumulate) {
+  const bool is_bf16 = p->dtype == FOS_BF16;
+  const int64_t strips = (p->n + (is_bf16 ? fos::GQ_COLS : fos::GB_COLS) - 1) / (is_bf16 ? fos::GQ_COLS : fos::GB_COLS);
+  const dim3 grid((unsigned)strips, (unsigned)g_splits);
+#define FOS_GRAM(T, ACC)                                                                                                  \
+  hipLaunchKernelGGL((fos::gram_batch_mfma_kernel<T, ACC>), grid, dim3(fos::GB_THREADS), 0, p->stream, (const T*)Ap, p->lda, \
+                     rows, (int)p->n, p->multi.rbuf16, p->multi.gram_rows_per_split, p->multi.slabs16, p->n)
+  if (is_bf16) {
+    if (accumulate)
+      hipLaunchKernelGGL(fos::gram_batch_mfma_bf16_kernel<true>, grid, dim3(fos::GB_THREADS), 0, p->stream,
+                         (const fos::bf16_t*)Ap, p->lda, rows, (int)p->n, p->multi.rbuf16, p->multi.gram_rows_per_split, p->multi.slabs16, p->n);
+    else
+      hipLaunchKernelGGL(fos::gram_batch_mfma_bf16_kernel<false>, grid, dim3(fos::GB_THREADS), 0, p->stream,
+                         (const fos::bf16_t*)Ap, p->lda, rows, (int)p->n, p->multi.rbuf16, p->multi.gram_rows_per_split, p->multi.slabs16, p->n);
+  } else { if (accumulate) FOS_GRAM(float, true); else FOS_GRAM(float, false); }
+#undef FOS_GRAM
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
 static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controlled, bool same_family,
                           const float* b16 = nullptr, const uint8_t* fold_of_row = nullptr,
                           const fos::FoldHeld* held = nullptr) {
@@ -698,15 +736,11 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
   // row splits of product 2: the planned ones, or - a B-block run on a problem planned for the cluster form, whose slab
   // count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated
   const bool logit = p->loss == FOS_LOSS_LOGISTIC;
-  const bool two_products = b16 || fold_of_row || logit;
+  const bool weighted = p->row_weight != nullptr;
+  const bool two_products = b16 || fold_of_row || logit || weighted;
   bool use_cluster = p->multi.cp_cs && !two_products;
   int g_splits = p->multi.gram_splits;
-  if (p->multi.cp_cs && two_products) {
-    g_splits = (int)((p->multi.panel_rows + p->multi.gram_rows_per_split - 1) / p->multi.gram_rows_per_split);
-    if (g_splits > p->multi.gram_splits)
-      return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs / _folds / logistic loss: the cluster layout of this problem "
-                                       "has too few slabs for the two-product form");
-  }
+  if (two_products && (rc = two_product_splits(p, &g_splits))) return rc;
   // candidate block: zero everywhere (padding columns, unused slots), then y_k of every state machine
   const size_t per_entry = is_bf16 ? 3 * sizeof(unsigned short) : sizeof(float);
   HIP_TRY(hipMemsetAsync(p->cand.xp, 0, (size_t)p->cand.n_pad * fos::BT_NV * per_entry, p->stream));
@@ -754,7 +788,10 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
       int nwg1 = 0;
       // column-sharded: b enters the sum over the ranks once (rank 0); R = sum_p A_p Y_p - b is the ONE exchange per panel
       const float* bp = b16 ? b16 + row0 * fos::BT_NV : (p->b && !(cols && p->comm->rank != 0)) ? p->b + row0 : nullptr;
-      if (logit)                     // labels and fold ids are offset with the panel
+      if (weighted)                  // labels, fold ids and weights are offset with the panel (panel rows are a multiple of 256)
+        rc = launch_batch_product_weighted(p, Ap, p->b + row0, 1, rows, p->multi.rbuf16, &nwg1, fold_of_row ? fold_of_row + row0 : nullptr,
+                                           held, p->row_weight + row0);
+      else if (logit)                // labels and fold ids are offset with the panel
         rc = launch_batch_product_logit(p, Ap, p->b + row0, rows, p->multi.rbuf16, &nwg1, fold_of_row ? fold_of_row + row0 : nullptr, held);
       else if (fold_of_row)          // the ids are offset with the panel as b is (panel rows are a multiple of 256)
         rc = launch_batch_product_folds(p, Ap, p->b + row0, rows, p->multi.rbuf16, &nwg1, fold_of_row + row0, *held);
@@ -841,13 +878,14 @@ static int lockstep_forms(fos_fista* const* fs, int nv, const char* fn, bool* al
   return FOS_OK;
 }
 
-// A logistic problem: always the two matrix-core products, for any number of state machines (one included - there is no
-// single-vector logistic pass), never the cluster form or the VALU multi-vector pass.
+// A logistic problem or one with row weights: always the two matrix-core products, for any number of state machines (one
+// included - there is no single-vector logistic or weighted pass), never the cluster form or the VALU multi-vector pass.
 static int run_multi_logit(fos_fista* const* fs, int nv, int iters, const uint8_t* fold_of_row, const fos::FoldHeld* held,
                            const char* fn) {
   fos_problem* p = fs[0]->p;
   if (!p->b || p->comm || p->col_sharded || !pair_dd_multi_supported(p))
-    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the logistic loss needs b, an unsharded problem and the matrix-core pair");
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the logistic loss and row weights need b, an unsharded problem and the "
+                                                         "matrix-core pair");
   bool all_plain, same_family;
   if (int rc = lockstep_forms(fs, nv, fn, &all_plain, &same_family)) return rc;
   if (iters == 0) return FOS_OK;
@@ -857,7 +895,7 @@ static int run_multi_logit(fos_fista* const* fs, int nv, int iters, const uint8_
 static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, int64_t ldb) {
   fos_problem* p = fs[0]->p;
   const bool rhs = B != nullptr;
-  if (p->loss == FOS_LOSS_LOGISTIC) return run_multi_logit(fs, nv, iters, nullptr, nullptr, "fos_fista_run_multi");
+  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight) return run_multi_logit(fs, nv, iters, nullptr, nullptr, "fos_fista_run_multi");
   if (rhs && (p->comm || p->col_sharded))
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs: row- or column-sharded problems are not served");
   if (nv == 1) {
@@ -964,7 +1002,8 @@ int fos_fista_run_multi_folds(fos_fista* const* fs, int nv, int iters, const uin
   for (int v = 0; v < nv; ++v)
     if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi_folds: handles must share one problem");
   fos_problem* p = fs[0]->p;
-  if (p->loss == FOS_LOSS_LOGISTIC) return run_multi_logit(fs, nv, iters, fold_of_row, &hb, "fos_fista_run_multi_folds");
+  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight)
+    return run_multi_logit(fs, nv, iters, fold_of_row, &hb, "fos_fista_run_multi_folds");
   if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the problem has no b of its own");
   if (p->comm || p->col_sharded)
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: row- or column-sharded problems are not served");
@@ -975,6 +1014,44 @@ int fos_fista_run_multi_folds(fos_fista* const* fs, int nv, int iters, const uin
   if (iters == 0) return FOS_OK;
   // always the two matrix-core products, for any number of state machines: the alternative is a copy of A per fold
   return run_multi_mfma(fs, nv, iters, !all_plain, same_family, nullptr, fold_of_row, &hb);
+}
+
+// G[j][c] = sum over the row splits of slabs16[split][j][c]: the slab sum of fos_gram_apply.
+static __global__ __launch_bounds__(256) void gram_slab_sum_kernel(const float* __restrict__ slabs, int splits, int64_t n, int nv,
+                                                                   float* __restrict__ G) {
+  const int64_t total = (int64_t)nv * n;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    float acc = 0.f;                 // i = j * n + c; a slab set is 16 x n floats
+    for (int s = 0; s < splits; ++s) acc += slabs[(int64_t)s * fos::BT_NV * n + i];
+    G[i] = acc;
+  }
+}
+
+int fos_gram_apply(const float* X, int nv, fos_problem* p, float* G) {
+  if (!X || !p || !G || nv < 1 || nv > fos::BT_NV) return fail(FOS_ERR_ARG, "fos_gram_apply: bad argument (null pointer or nv outside 1..16)");
+  if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_gram_apply: the shape has no matrix-core pair");
+  int rc = ensure_batch_workspace(p);
+  if (rc) return rc;
+  if ((rc = plan_multi_mfma(p))) return rc;
+  int g_splits = 0;
+  if ((rc = two_product_splits(p, &g_splits))) return rc;
+  const int64_t esz = p->dtype == FOS_BF16 ? 2 : 4;
+  if ((rc = pack_candidates(p, X, nv))) return rc;
+  for (int64_t row0 = 0, panel = 0; row0 < p->m; row0 += p->multi.panel_rows, ++panel) {
+    const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
+    const char* Ap = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz;
+    int nwg1 = 0;
+    if (p->row_weight)               // R = w (A_panel X): neither b nor the loss enters
+      rc = launch_batch_product_weighted(p, Ap, nullptr, 0, rows, p->multi.rbuf16, &nwg1, nullptr, nullptr, p->row_weight + row0);
+    else
+      rc = launch_batch_product(p, Ap, nullptr, rows, 0, p->multi.rbuf16, &nwg1);
+    if (rc) return rc;
+    if ((rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
+  }
+  hipLaunchKernelGGL(gram_slab_sum_kernel, dim3(grid_1d((int64_t)nv * p->n, 256, 1024)), dim3(256), 0, p->stream, p->multi.slabs16,
+                     g_splits, p->n, nv, G);
+  LAUNCH_CHECK();
+  return FOS_OK;
 }
 
 int fos_fista_grad(fos_fista* f) {

@@ -269,6 +269,7 @@ struct fos_problem {
   int64_t m = 0, n = 0, lda = 0;
   int dtype = FOS_F32;
   int loss = FOS_LOSS_SQUARED;       // fos_problem_set_loss: what b means to the matrix-core lockstep (no buffer depends on it)
+  const float* row_weight = nullptr; // fos_row_weights_bind: the caller's m per-row weights of the data term (borrowed; nullptr: none)
   hipStream_t stream = nullptr;
   int ncu = 256;
   // inputs of the plan groups besides the shape (set by the entry point named; see fosapi::invalidate)
@@ -370,6 +371,8 @@ int prof_mark(fos_problem* p, bool start);
 int aligned_vec(fos_problem* p, const float* v, const float** out);
 bool batch_supported(const fos_problem* p);
 MultiLaunch find_multi(int64_t n, int nv, bool bblock = false);
+// the caller's X (n x 16 floats, columns 0..nv-1) -> p->cand.xp in the layout product 1 reads (after ensure_batch_workspace)
+int pack_candidates(fos_problem* p, const float* X, int nv);
 // several right-hand sides: the caller's B (m x nv, leading dimension ldb) -> p->b16, zero beyond column nv
 int stage_b16(fos_problem* p, const float* B, int64_t ldb, int nv);
 // Enqueue the A pass for `ys`.  with_g: also produce the slabs (A^T r).  *n_rr: number of rr partials written.
@@ -395,8 +398,12 @@ int launch_batch_product_folds(fos_problem* p, const void* A, const float* b, in
 // fold_of_row / held (both or neither): the masked forms as launch_batch_product_folds.
 int launch_batch_product_logit(fos_problem* p, const void* A, const float* b, int64_t rows_total, float* rout, int* nwg_out,
                                const uint8_t* fold_of_row, const fos::FoldHeld* held);
-// The one guard of the entry points that form a residual, gradient or objective with b as a squared-loss target: refuses a
-// logistic problem (FOS_ERR_UNSUPPORTED) before any launch or change of handle state.
+// Product 1 of a problem with row weights (kF32Weighted / kBf16Weighted): the form of the problem's loss with R and the sums
+// weighted per row; fold_of_row / held as launch_batch_product_logit; use_b = 0: R = w (A Y) (fos_gram_apply).
+int launch_batch_product_weighted(fos_problem* p, const void* A, const float* b, int use_b, int64_t rows_total, float* rout,
+                                  int* nwg_out, const uint8_t* fold_of_row, const fos::FoldHeld* held, const float* row_weight);
+// The one guard of the entry points that form an unweighted squared-loss residual, gradient or objective: refuses a logistic
+// problem and a problem with row weights (FOS_ERR_UNSUPPORTED) before any launch or change of handle state.
 int need_squared(const fos_problem* p, const char* fn);
 // q[j] = ||A Xp_j - use_b*b||^2 -> out16 (device); Xp already in p->xp.  b16 (unsharded only): subtract its column j instead
 int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* stopped = nullptr, const float* b16 = nullptr);

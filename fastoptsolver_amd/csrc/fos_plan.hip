@@ -577,12 +577,24 @@ int ensure_batch_workspace(fos_problem* p) {
   return FOS_OK;
 }
 
+// The caller's X (n x 16 floats, row-major; columns 0..nv-1 used) -> the candidate block of product 1 (Xp, or Xq for bf16).
+int pack_candidates(fos_problem* p, const float* X, int nv) {
+  if (p->dtype == FOS_BF16)
+    hipLaunchKernelGGL(fos::xq_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
+                       (int)p->cand.n_pad, nv, (unsigned short*)p->cand.xp.get());
+  else
+    hipLaunchKernelGGL(xp_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
+                       (int)p->cand.n_pad, nv, p->cand.xp);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
 // bf16 variants of the batched kernel: (row blocks per wave, tile columns), rows per workgroup, workgroups per CU.
 // Measured at 65536 x 8192 (tools/bench_bq.py): <1,128> 208.6 us, <2,64> 213.5 us, <2,128> 166.6 us (80.6 % of HBM),
 // <4,64> 170.4 us.  The 128-row tile halves the LDS re-reads of the candidate fragments per byte of A; the 64-row
 // tile is kept for short problems, where it gives twice as many workgroups.
 typedef void (*Bf16Batch)(const fos::bf16_t*, int64_t, const float*, int, int64_t, int, const unsigned short*, int64_t, double*,
-                          float*, const int*, const uint8_t*, fos::FoldHeld);
+                          float*, const int*, const uint8_t*, fos::FoldHeld, const float*);
 // fn_store: also keeps R (gram_batch.hpp); fn_rhs / fn_store_rhs: the same with a right-hand side per column (B16 block)
 struct Bf16BatchVariant { Bf16Batch fn, fn_store; int rows; int wg_per_cu; Bf16Batch fn_rhs, fn_store_rhs; };
 const Bf16BatchVariant kBf16Batch[] = {
@@ -593,7 +605,7 @@ const Bf16BatchVariant kBf16Batch[] = {
 };
 
 typedef void (*F32Batch)(const float*, int64_t, const float*, int, int64_t, int, const float*, int64_t, double*, float*,
-                         const int*, const uint8_t*, fos::FoldHeld);
+                         const int*, const uint8_t*, fos::FoldHeld, const float*);
 struct F32BatchVariant { F32Batch fn, fn_store; int rows; int wg_per_cu; F32Batch fn_rhs, fn_store_rhs; };
 // fp32, measured at 65536 x 8192: <1> 64-row tile 368-395 us, <2> 128-row tile 335.7 us (80 % of HBM), <4> 336.8 us.
 const F32BatchVariant kF32Batch[] = {
@@ -644,6 +656,50 @@ const F32LogitVariant kF32Logit[] = {
      fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC>},
 };
 
+// The weighted forms of product 1 (per-row sample weights bound with fos_row_weights_bind), one entry per tile variant of the
+// tables above: form[loss] holds store / resid / train_store / held_resid as the logistic tables do, all with WEIGHT on -
+// R = w (A Y - b) or w (sigma(A Y) - b), q_part = sum w r^2 or sum w l.
+struct Bf16WeightedForms { Bf16Batch store, resid, train_store, held_resid; };
+struct Bf16WeightedVariant { Bf16WeightedForms form[2]; };
+const Bf16WeightedVariant kBf16Weighted[] = {
+    {{{fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
+      fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
+      fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_TRAIN, fos::LOSS_SQUARED, true>,
+      fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_HELD, fos::LOSS_SQUARED, true>},
+     {fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
+      fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
+      fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC, true>,
+      fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC, true>}}},
+    {{{fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
+      fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
+      fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_TRAIN, fos::LOSS_SQUARED, true>,
+      fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_HELD, fos::LOSS_SQUARED, true>},
+     {fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
+      fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
+      fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC, true>,
+      fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC, true>}}},
+};
+struct F32WeightedForms { F32Batch store, resid, train_store, held_resid; };
+struct F32WeightedVariant { F32WeightedForms form[2]; };
+const F32WeightedVariant kF32Weighted[] = {
+    {{{fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
+      fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
+      fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_TRAIN, fos::LOSS_SQUARED, true>,
+      fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_HELD, fos::LOSS_SQUARED, true>},
+     {fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
+      fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
+      fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC, true>,
+      fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC, true>}}},
+    {{{fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
+      fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
+      fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_TRAIN, fos::LOSS_SQUARED, true>,
+      fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_HELD, fos::LOSS_SQUARED, true>},
+     {fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
+      fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
+      fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC, true>,
+      fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC, true>}}},
+};
+
 // The grid of product 1 on `rows_total` rows: the tile variant (0: 64-row tile, 1: 128-row tile), the row groups per
 // workgroup and the number of workgroups (rows of q_part).
 struct BatchGrid { int variant; int64_t gpw, nwg; };
@@ -670,17 +726,22 @@ int launch_batch_product(fos_problem* p, const void* A, const float* b, int64_t 
     hipLaunchKernelGGL(bblock ? (rout ? vq.fn_store_rhs : vq.fn_rhs) : (rout ? vq.fn_store : vq.fn), dim3((unsigned)g.nwg),
                        dim3(fos::BT_THREADS), 0, p->stream, (const fos::bf16_t*)A, p->lda, b, (use_b && b) ? 1 : 0,
                        rows_total, (int)p->n, (const unsigned short*)p->cand.xp.get(), g.gpw, p->cand.q_part, rout, stopped,
-                       (const uint8_t*)nullptr, fos::FoldHeld{});
+                       (const uint8_t*)nullptr, fos::FoldHeld{}, (const float*)nullptr);
   else
     hipLaunchKernelGGL(bblock ? (rout ? vf.fn_store_rhs : vf.fn_rhs) : (rout ? vf.fn_store : vf.fn), dim3((unsigned)g.nwg),
                        dim3(fos::BT_THREADS), 0, p->stream, (const float*)A, p->lda, b, (use_b && b) ? 1 : 0, rows_total,
-                       (int)p->n, p->cand.xp, g.gpw, p->cand.q_part, rout, stopped, (const uint8_t*)nullptr, fos::FoldHeld{});
+                       (int)p->n, p->cand.xp, g.gpw, p->cand.q_part, rout, stopped, (const uint8_t*)nullptr, fos::FoldHeld{},
+                       (const float*)nullptr);
   LAUNCH_CHECK();
   *nwg_out = (int)g.nwg;
   return FOS_OK;
 }
 
 int need_squared(const fos_problem* p, const char* fn) {
+  if (p && p->row_weight != nullptr)
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": not served on a problem with row weights (fos_row_weights_bind); the "
+                                     "weighted squared and logistic losses run through fos_fista_run_multi / _run_multi_folds and fos_residual_batch / "
+                                     "_folds");
   if (p && p->loss != FOS_LOSS_SQUARED)
     return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": not served on a logistic problem (fos_problem_set_loss); the logistic "
                                      "loss runs through fos_fista_run_multi / _run_multi_folds and fos_residual_batch / _folds");
@@ -704,11 +765,11 @@ int launch_batch_product_folds(fos_problem* p, const void* A, const float* b, in
   if (p->dtype == FOS_BF16)
     hipLaunchKernelGGL(rout ? vq.store_train : vq.resid_held, dim3((unsigned)g.nwg), dim3(fos::BT_THREADS), 0, p->stream,
                        (const fos::bf16_t*)A, p->lda, b, 1, rows_total, (int)p->n, (const unsigned short*)p->cand.xp.get(), g.gpw,
-                       p->cand.q_part, rout, (const int*)nullptr, fold_of_row, held);
+                       p->cand.q_part, rout, (const int*)nullptr, fold_of_row, held, (const float*)nullptr);
   else
     hipLaunchKernelGGL(rout ? vf.store_train : vf.resid_held, dim3((unsigned)g.nwg), dim3(fos::BT_THREADS), 0, p->stream,
                        (const float*)A, p->lda, b, 1, rows_total, (int)p->n, p->cand.xp, g.gpw, p->cand.q_part, rout,
-                       (const int*)nullptr, fold_of_row, held);
+                       (const int*)nullptr, fold_of_row, held, (const float*)nullptr);
   LAUNCH_CHECK();
   *nwg_out = (int)g.nwg;
   return FOS_OK;
@@ -726,11 +787,36 @@ int launch_batch_product_logit(fos_problem* p, const void* A, const float* b, in
   if (p->dtype == FOS_BF16)
     hipLaunchKernelGGL(fold_of_row ? (rout ? vq.train_store : vq.held_resid) : (rout ? vq.store : vq.resid), dim3((unsigned)g.nwg),
                        dim3(fos::BT_THREADS), 0, p->stream, (const fos::bf16_t*)A, p->lda, b, 1, rows_total, (int)p->n,
-                       (const unsigned short*)p->cand.xp.get(), g.gpw, p->cand.q_part, rout, (const int*)nullptr, fold_of_row, hb);
+                       (const unsigned short*)p->cand.xp.get(), g.gpw, p->cand.q_part, rout, (const int*)nullptr, fold_of_row, hb,
+                       (const float*)nullptr);
   else
     hipLaunchKernelGGL(fold_of_row ? (rout ? vf.train_store : vf.held_resid) : (rout ? vf.store : vf.resid), dim3((unsigned)g.nwg),
                        dim3(fos::BT_THREADS), 0, p->stream, (const float*)A, p->lda, b, 1, rows_total, (int)p->n, p->cand.xp, g.gpw,
-                       p->cand.q_part, rout, (const int*)nullptr, fold_of_row, hb);
+                       p->cand.q_part, rout, (const int*)nullptr, fold_of_row, hb, (const float*)nullptr);
+  LAUNCH_CHECK();
+  *nwg_out = (int)g.nwg;
+  return FOS_OK;
+}
+
+// Product 1 of a problem with row weights on `rows` rows starting at A / b / row_weight (use_b = 0: R = w (A Y), the first
+// half of fos_gram_apply): the weighted form of the problem's loss, with the fold mask when fold_of_row / held are given.
+// Geometry as launch_batch_product.
+int launch_batch_product_weighted(fos_problem* p, const void* A, const float* b, int use_b, int64_t rows_total, float* rout,
+                                  int* nwg_out, const uint8_t* fold_of_row, const fos::FoldHeld* held, const float* row_weight) {
+  const BatchGrid g = batch_grid(p, rows_total);
+  const int loss = (use_b && p->loss == FOS_LOSS_LOGISTIC) ? 1 : 0;
+  const Bf16WeightedForms& vq = kBf16Weighted[g.variant].form[loss];
+  const F32WeightedForms& vf = kF32Weighted[g.variant].form[loss];
+  const fos::FoldHeld hb = held ? *held : fos::FoldHeld{};
+  if (p->dtype == FOS_BF16)
+    hipLaunchKernelGGL(fold_of_row ? (rout ? vq.train_store : vq.held_resid) : (rout ? vq.store : vq.resid), dim3((unsigned)g.nwg),
+                       dim3(fos::BT_THREADS), 0, p->stream, (const fos::bf16_t*)A, p->lda, b, (use_b && b) ? 1 : 0, rows_total,
+                       (int)p->n, (const unsigned short*)p->cand.xp.get(), g.gpw, p->cand.q_part, rout, (const int*)nullptr,
+                       fold_of_row, hb, row_weight);
+  else
+    hipLaunchKernelGGL(fold_of_row ? (rout ? vf.train_store : vf.held_resid) : (rout ? vf.store : vf.resid), dim3((unsigned)g.nwg),
+                       dim3(fos::BT_THREADS), 0, p->stream, (const float*)A, p->lda, b, (use_b && b) ? 1 : 0, rows_total, (int)p->n,
+                       p->cand.xp, g.gpw, p->cand.q_part, rout, (const int*)nullptr, fold_of_row, hb, row_weight);
   LAUNCH_CHECK();
   *nwg_out = (int)g.nwg;
   return FOS_OK;
@@ -1239,6 +1325,26 @@ int fos_problem_get_loss(const fos_problem* p, int* loss) {
   return FOS_OK;
 }
 
+int fos_row_weights_bind(const float* w, fos_problem* p) {
+  if (!p) return fail(FOS_ERR_ARG, "fos_row_weights_bind: null problem");
+  if (((uintptr_t)w & 15) != 0) return fail(FOS_ERR_ARG, "fos_row_weights_bind: the weights are not 16-byte aligned");
+  if (w) {
+    if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_row_weights_bind: a weighted problem needs b");
+    if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_row_weights_bind: sharded problems are not served");
+    if (!pair_dd_multi_supported(p))
+      return fail(FOS_ERR_UNSUPPORTED, "fos_row_weights_bind: row weights run on the matrix-core pair (aligned streaming layout, "
+                                       "65..16384 columns)");
+  }
+  p->row_weight = w;                 // no buffer depends on the weights: nothing to invalidate
+  return FOS_OK;
+}
+
+int fos_row_weights_get(const float** w_out, const fos_problem* p) {
+  if (!p || !w_out) return fail(FOS_ERR_ARG, "fos_row_weights_get: null");
+  *w_out = p->row_weight;
+  return FOS_OK;
+}
+
 int fos_problem_set_comm(fos_problem* p, fos_comm* c) {
   if (!p) return fail(FOS_ERR_ARG, "fos_problem_set_comm: null");
   if (int rc_ = need_squared(p, "fos_problem_set_comm")) return rc_;
@@ -1595,7 +1701,8 @@ int fos_residual_objective(fos_problem* p, const float* x, double* out3) {
 }
 
 // fos_residual_batch / _folds on a logistic problem: out16[j] = sum of the log-loss of column j over all rows, or over the rows
-// of the fold it holds out.  Arguments are checked.
+// of the fold it holds out.  Arguments are checked.  A problem with row weights of either loss comes here too: the sums are
+// sum w l or sum w r^2 (launch_batch_product_weighted).
 static int residual_batch_logit(fos_problem* p, const char* fn, const float* X, int nv, double* out16, const uint8_t* fold_of_row,
                                 const fos::FoldHeld* held) {
   if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the shape has no matrix-core pair");
@@ -1610,7 +1717,11 @@ static int residual_batch_logit(fos_problem* p, const char* fn, const float* X, 
   LAUNCH_CHECK();
   if ((rc = prof_mark(p, true))) return rc;
   int nwg = 0;
-  if ((rc = launch_batch_product_logit(p, p->A, p->b, p->m, nullptr, &nwg, fold_of_row, held))) return rc;
+  if (p->row_weight)
+    rc = launch_batch_product_weighted(p, p->A, p->b, 1, p->m, nullptr, &nwg, fold_of_row, held, p->row_weight);
+  else
+    rc = launch_batch_product_logit(p, p->A, p->b, p->m, nullptr, &nwg, fold_of_row, held);
+  if (rc) return rc;
   if ((rc = prof_mark(p, false))) return rc;
   hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->cand.q_part, nwg, fos::BT_NV, out16);
   LAUNCH_CHECK();
@@ -1621,7 +1732,7 @@ int fos_residual_batch(fos_problem* p, const float* X, int nv, int use_b, double
   if (!p || !X || !out16 || nv < 1 || nv > fos::BT_NV) return fail(FOS_ERR_ARG, "fos_residual_batch: bad argument");
   if (!use_b)                        // ||A X_j||^2 is a squared-loss quantity
     if (int rc = need_squared(p, "fos_residual_batch (use_b = 0)")) return rc;
-  if (p->loss == FOS_LOSS_LOGISTIC) return residual_batch_logit(p, "fos_residual_batch", X, nv, out16, nullptr, nullptr);
+  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight) return residual_batch_logit(p, "fos_residual_batch", X, nv, out16, nullptr, nullptr);
   if (!batch_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch: needs the fused path");
   int rc = ensure_batch_workspace(p);
   if (rc) return rc;
@@ -1663,7 +1774,8 @@ int fos_residual_batch_folds(fos_problem* p, const float* X, int nv, const uint8
                              "aligned or a held id outside -1..254)");
   if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: the problem has no b of its own");
   if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: sharded problems are not served");
-  if (p->loss == FOS_LOSS_LOGISTIC) return residual_batch_logit(p, "fos_residual_batch_folds", X, nv, out16, fold_of_row, &hb);
+  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight)
+    return residual_batch_logit(p, "fos_residual_batch_folds", X, nv, out16, fold_of_row, &hb);
   if (!pair_dd_multi_supported(p))
     return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: the shape has no matrix-core pair");
   int rc = ensure_batch_workspace(p);

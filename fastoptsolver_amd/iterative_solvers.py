@@ -96,7 +96,13 @@ def estimate_lipschitz(A, n_iter: int = 100, tol: float = 1e-6, *, group=None) -
     iteration of the whole matrix as it stands; ``group=`` (a torch.distributed group, split-form sharding) sums
     w over the ranks here.  Every rank must draw the same v0 (seed the global stream identically).
     A batch (a 3-D A or a sequence of matrices) gives a length-P float64 ndarray: the draws of P single calls, in
-    problem order, and one power iteration per problem in one launch."""
+    problem order, and one power iteration per problem in one launch.
+    A handle with sample weights (``prepare_weighted``): lambda_max(A^T W A), the same power iteration with one
+    fos_gram_apply per step and v kept in fp64 on the host."""
+    if _weighted(A):
+        if group is not None:
+            raise ValueError("a weighted handle cannot be combined with group=")
+        return _weighted_lipschitz(A, np.random.randn(A.n), n_iter, tol)
     if _is_batch(A):
         if group is not None:
             raise ValueError("a batch (3-D A or a sequence of matrices) cannot be combined with group=")
@@ -114,6 +120,27 @@ def estimate_lipschitz(A, n_iter: int = 100, tol: float = 1e-6, *, group=None) -
         return sharded_lipschitz(lambda v: bare.gemv_pair(v, 0.0), prob.n, prob.vec_in(v0)[: prob.n], n_iter, tol,
                                  group=group)
     L, _, _ = prob.power_iter(v0, n_iter=n_iter, tol=tol)
+    return L
+
+
+def _weighted(A):
+    """Whether A is a handle with sample weights bound (`prepare_weighted`): it runs on the matrix-core lockstep alone."""
+    return isinstance(A, _core.Problem) and A.sample_weight is not None
+
+
+def _weighted_lipschitz(prob, v0, n_iter=100, tol=1e-6):
+    """ref:45-60 on A^T W A: w = A^T (W (A v)) is one fos_gram_apply per step (v rounded to fp32 for the pass), the norms and v
+    itself stay in fp64 here.  max(w) lambda_max(A^T A) is not used: with class weights {1, r} it is loose by up to r."""
+    v = np.asarray(v0, dtype=np.float64)
+    v = v / np.linalg.norm(v)
+    prev, L = 0.0, 0.0
+    for _ in range(n_iter):
+        w = prob.gram_apply(torch.from_numpy(v).reshape(-1, 1))[:, 0].to("cpu", torch.float64).numpy()
+        L = float(np.linalg.norm(w))
+        v = w / L
+        if abs(L - prev) < tol:
+            break
+        prev = L
     return L
 
 
@@ -1026,6 +1053,8 @@ def _lipschitz(prob, L, *, comm=None, cols=None, group=None):
     from the global NumPy stream."""
     if L is not None:
         return float(L)
+    if _weighted(prob):              # lambda_max(A^T W A); sigma' <= 1/4 bounds the weighted logistic Hessian by a quarter of it
+        return estimate_lipschitz(prob) / (4.0 if prob.loss == "logistic" else 1.0)
     if cols is not None:
         return _lipschitz_cols(prob, comm, cols)
     return estimate_lipschitz(prob, group=group)
@@ -1102,8 +1131,8 @@ def fista_delta(A, b, reg_type: str, alpha1: float, alpha2: float, delta: float,
 def _run_path(prob, prms, max_iter, cols=None, lockstep_only=False):
     """One state machine per parameter set on `prob`, advanced max_iter iterations in lockstep groups (fos_fista_run_multi;
     what it does not serve runs one by one); one grad_call_times entry per lockstep iteration per group.  The handles.
-    lockstep_only (a logistic problem: the lockstep is its one form): groups of 16, a group of one included, and a refusal
-    raises."""
+    lockstep_only (a logistic or weighted problem: the lockstep is its one form): groups of 16, a group of one included, and a
+    refusal raises."""
     handles = [_new_state(prob, prm) for prm in prms]
     gtimer = _EventTimer(grad_call_times)
     # up to 4 weights: the multi-vector VALU pass where the shape has one; up to 16: the matrix-core pass
@@ -1146,6 +1175,9 @@ def fista_path(A, b, alphas, t_init_factor: float = 1.0, max_iter: int = 500, *,
     reset_metrics()
     if delta is not None:
         assert delta > 2, "In FISTA-Δ, delta must be > 2 for convergence (course requirement)"
+    weighted = _weighted(A)
+    if weighted and (tol != 0.0 or comm is not None or cols is not None):
+        raise ValueError("a handle with sample weights runs on the lockstep alone: no tol (the gradient-norm rule), comm= or cols=")
     prob, _ = _sharded_problem(A, b, dtype, comm, None, cols)    # comm: A, b are this rank's rows (matrix-core pass, one
     like = prob.like                                             # all-reduce of the 16 gradients per iteration)
     L_val = _lipschitz(prob, L, comm=comm, cols=cols)
@@ -1153,7 +1185,8 @@ def fista_path(A, b, alphas, t_init_factor: float = 1.0, max_iter: int = 500, *,
     # the tolerances go to the device as given: a negative one is refused there (fos_fista_reset), not read as "off"
     handles = _run_path(prob, [_params(_tau(L_val, a2, t_init_factor), a1, a2, mode=mode, delta=delta, tol=tol,
                                        tol_ratio=tol_ratio, grad_rule=delta is None, adaptive_restart=adaptive_restart,
-                                       restart_threshold=restart_threshold) for a1, a2 in alphas], max_iter, cols)
+                                       restart_threshold=restart_threshold) for a1, a2 in alphas], max_iter, cols,
+                        lockstep_only=weighted)
     xs = [_core.from_device_vec(st.x_tensor(), like) for st in handles]
     if return_info:
         stats = [st.status() for st in handles]
@@ -1194,6 +1227,16 @@ def _cv_folds(folds, m):
     if (sizes == 0).any():
         raise ValueError(f"folds: fold {int(np.argmin(sizes))} is empty")
     return arr.astype(np.uint8), sizes.astype(np.int64)
+
+
+def _cv_weight_sums(prob, ids, K):
+    """The weight sum of every fold of a weighted handle (float64, length K): the denominators of the held-out scores.
+    ValueError for a fold whose weights sum to zero - nothing could be scored on it - before any solver launch."""
+    w = prob.sample_weight.to("cpu", torch.float64).numpy()
+    sums = np.bincount(np.asarray(ids, dtype=np.int64), weights=w, minlength=K).astype(np.float64)
+    if (sums <= 0.0).any():
+        raise ValueError(f"folds: the sample weights of fold {int(np.argmin(sums))} sum to zero")
+    return sums
 
 
 def _cv_lockstep(prob, ids, K, prms, max_iter):
@@ -1286,7 +1329,11 @@ def fista_cv(A, b, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int = 
 
     The slow path: problems the lockstep does not serve (A that fits one CU's LDS, n <= 64, ragged or misaligned rows,
     rows wider than 16384 columns) run fold by fold on gathered device copies of the training rows, one copy alive at a
-    time - the same results at K copies and K times the reads of A."""
+    time - the same results at K copies and K times the reads of A.
+
+    A handle with sample weights (``prepare_weighted``): every fit minimises the weighted objective of its training rows,
+    ``mse[f, a]`` is the weighted held-out sum of squares over the held-out weight sum (a fold whose weights sum to zero is a
+    ValueError before any solver launch), the refit runs in the lockstep too, and a refusal raises - there is no slow path."""
     reset_metrics()
     if delta is not None:
         assert delta > 2, "In FISTA-Δ, delta must be > 2 for convergence (course requirement)"
@@ -1300,21 +1347,30 @@ def fista_cv(A, b, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int = 
     if prob.b is None:
         raise ValueError("fista_cv needs b")
     like = prob.like
+    weighted = _weighted(prob)
+    if weighted:
+        sizes = _cv_weight_sums(prob, ids, K)
     L_val = _lipschitz(prob, L)
     mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
     prms = [_params(_tau(L_val, a2, t_init_factor), a1, a2, mode=mode, delta=delta, tol_ratio=tol_ratio,
                     adaptive_restart=adaptive_restart, restart_threshold=restart_threshold) for a1, a2 in alphas]
     out = _cv_lockstep(prob, ids, K, prms, max_iter)
     if out is None:
+        if weighted:                 # no unweighted slow path may answer for a weighted handle
+            raise _lib.FosError("fos_fista_run_multi_folds refused the weighted lockstep: " +
+                                prob.lib.fos_last_error().decode("utf-8", "replace"))
         out = _cv_fold_by_fold(prob, ids, K, prms, max_iter)
     X, sse, info = out
-    mse = sse / sizes[:, None].astype(np.float64)
+    mse = sse / sizes[:, None].astype(np.float64)       # weighted: the held-out weighted sum over the held-out weight sum
     mean_mse = mse.mean(axis=0)
     best = int(np.argmin(mean_mse))
     x = None
     if refit:
-        st = _new_state(prob, prms[best])
-        st.run(max_iter)
+        if weighted:
+            st = _run_path(prob, [prms[best]], max_iter, lockstep_only=True)[0]
+        else:
+            st = _new_state(prob, prms[best])
+            st.run(max_iter)
         x = _core.from_device_vec(st.x_tensor(), like)
     coefs = _core.from_device_vec(X, like) if return_coefs else None
     return CVResult(alphas, mse, mean_mse, best, x, coefs, info)

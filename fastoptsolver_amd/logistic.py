@@ -7,6 +7,10 @@ The gradient of the data term is A^T (sigma(Ax) - y): the lockstep of ``fista_pa
 the device and the fold masks are the launches of the squared loss.  The loss belongs to the problem handle
 (``prepare(A, y, loss="logistic")``, fos_problem_set_loss); every entry point that would answer with a squared-loss quantity
 refuses such a handle.  An intercept is a constant column appended by the caller.
+
+Per-row sample weights (``prepare_weighted(A, y, w, loss="logistic")``, fos_row_weights_bind): the data term becomes
+sum_i w_i (log(1 + exp(a_i.x)) - y_i a_i.x); ``logistic_path`` / ``logistic_cv`` / ``logistic_objective`` take the handle as
+``A`` and answer with the weighted quantities, the held-out scores as weighted means.
 """
 from __future__ import annotations
 
@@ -42,8 +46,14 @@ def _problem(A, y, dtype):
 
 
 def _params_of(prob, alphas, L, t_init_factor, delta, tol_ratio, adaptive_restart, restart_threshold):
-    """L of the logistic data term (lambda_max(A^T A) / 4 unless given) and one parameter set per weight."""
-    L_val = float(L) if L is not None else _its.estimate_lipschitz(prob) / 4.0
+    """L of the logistic data term (lambda_max(A^T A) / 4 unless given; lambda_max(A^T W A) / 4 on a weighted handle) and one
+    parameter set per weight."""
+    if L is not None:
+        L_val = float(L)
+    elif _its._weighted(prob):       # a quarter of lambda_max(A^T W A)
+        L_val = _its._lipschitz(prob, None)
+    else:
+        L_val = _its.estimate_lipschitz(prob) / 4.0
     mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
     return [_its._params(_its._tau(L_val, a2, t_init_factor), a1, a2, mode=mode, delta=delta, tol_ratio=tol_ratio,
                          adaptive_restart=adaptive_restart, restart_threshold=restart_threshold) for a1, a2 in alphas]
@@ -103,10 +113,12 @@ def logistic_cv(A, y, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int
     ids, sizes = _its._cv_folds(folds, m)
     K = len(sizes)
     prob = _problem(A, y, dtype)
+    if _its._weighted(prob):         # weighted held-out sums over the held-out weight sums; a zero-weight fold raises here
+        sizes = _its._cv_weight_sums(prob, ids, K)
     prms = _params_of(prob, alphas, L, t_init_factor, delta, tol_ratio, adaptive_restart, restart_threshold)
     out = _its._cv_lockstep(prob, ids, K, prms, max_iter)
     if out is None:
-        raise _lib.FosError("fos_fista_run_multi_folds refused the logistic lockstep: " +
+        raise _lib.FosError("fos_fista_run_multi_folds refused the lockstep: " +
                             prob.lib.fos_last_error().decode("utf-8", "replace"))
     X, total, info = out
     logloss = total / sizes[:, None].astype(np.float64)

@@ -142,6 +142,28 @@ int fos_problem_set_gbuf(fos_problem* p, float* gbuf);
  * depends on the loss; nothing is replanned. */
 int fos_problem_set_loss(fos_problem* p, int loss);
 int fos_problem_get_loss(const fos_problem* p, int* loss);
+/* Per-row sample weights w_i >= 0 of the data term: sum_i w_i 0.5 (a_i.x - b_i)^2 (gradient A^T (w * (Ax - b))) or, on a
+ * logistic problem, sum_i w_i (log(1 + exp(a_i.x)) - b_i a_i.x) (gradient A^T (w * (sigma(Ax) - b))); the penalties are
+ * unchanged.  w: m floats on the device, borrowed, 16-byte aligned and readable up to m rounded up to 4 (product 1 fetches the
+ * weights of 4 rows with one load); NULL detaches.  The data pointer comes first, the handle second.  With weights bound
+ *   - fos_fista_run_multi (any nv in 1..16, one included) and fos_fista_run_multi_folds minimise the weighted objective of the
+ *     problem's loss: always the two matrix-core products per iteration, with the refusals of a logistic problem; product 1
+ *     stores R = w * r, everything after it is the same;
+ *   - fos_residual_batch with use_b = 1 gives out16[j] = sum_i w_i (a_i.X_j - b_i)^2 (the weighted log-loss sum on a logistic
+ *     problem) and fos_residual_batch_folds the same sum over column j's held-out rows;
+ *   - every entry point that refuses a logistic problem refuses this one too (FOS_ERR_UNSUPPORTED before any launch or change
+ *     of handle state, with a message of its own): a weighted handle is never answered with an unweighted quantity;
+ *   - the entry points that touch neither b nor a residual work as before.
+ * FOS_ERR_ARG (checked before any HIP call): null p, a misaligned w.  FOS_ERR_UNSUPPORTED under the conditions of
+ * fos_problem_set_loss(p, FOS_LOSS_LOGISTIC): no b, a sharded problem, a shape without the matrix-core pair.  No buffer depends
+ * on the weights; nothing is replanned.  fos_row_weights_get reads the bound pointer back (NULL: none). */
+int fos_row_weights_bind(const float* w, fos_problem* p);
+int fos_row_weights_get(const float** w_out, const fos_problem* p);
+/* G + j*n (n floats, device) = A^T W A X_j for the nv <= 16 columns of X (the layout of fos_residual_batch: n x 16 floats,
+ * row-major).  W: the bound row weights, the identity when none are bound; neither b nor the loss enters, so logistic and
+ * weighted problems are served.  Product 1 (R = w * (A X), kept), product 2 over every row panel, one slab sum.  Enqueues only.
+ * FOS_ERR_ARG: a null pointer, nv outside 1..16.  FOS_ERR_UNSUPPORTED where the matrix-core pair is not served. */
+int fos_gram_apply(const float* X, int nv, fos_problem* p, float* G);
 
 /* ---- row-sharded problems (the reference is single-process) --------------------------------------------
  * One process per GPU; each rank binds ITS rows of A and b to a fos_problem and attaches a communicator.  From then on
