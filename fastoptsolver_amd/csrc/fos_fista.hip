@@ -681,9 +681,9 @@ static fos::MultiUpdate multi_update(fos_fista* const* fs, int nv, bool controll
 // rows of the fold it holds out (batch_trial.hpp FOLD_TRAIN), so state machine j fits the other rows; the two-product form
 // likewise.  Product 2 and the updates see a masked R and are the same launches.
 // A logistic problem (fos_problem_set_loss): product 1 is the logistic form, R = sigma(A_panel Y) - b with or without the fold
-// mask (launch_batch_product_logit); the two-product form as well, and everything after product 1 is the same.
+// mask; the two-product form as well, and everything after product 1 is the same.
 // A problem with row weights (fos_row_weights_bind): product 1 is the weighted form of its loss, R = w (A_panel Y - b) or
-// w (sigma(A_panel Y) - b) (launch_batch_product_weighted); the two-product form, and everything after product 1 is the same.
+// w (sigma(A_panel Y) - b); the two-product form, and everything after product 1 is the same.
 
 // Row splits of product 2 in the two-product form: the planned ones, or - on a problem planned for the cluster form, whose slab
 // count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated.
@@ -698,8 +698,8 @@ static int two_product_splits(const fos_problem* p, int* g_splits) {
   return FOS_OK;
 }
 
-// Product 2 of fos_gram_apply on one row panel (the launches of run_multi_mfma, whose own stay in its body): slabs16[split][16][n]
-// (+)= R_panel^T A_panel, the panel again from the Infinity Cache.
+// Product 2 on one row panel (run_multi_mfma, fos_gram_apply): slabs16[split][16][n] (+)= R_panel^T A_panel, the panel again
+// from the Infinity Cache.
 static int launch_gram_panel(fos_problem* p, const char* Ap, int64_t rows, int g_splits, bool accumulate) {
   const bool is_bf16 = p->dtype == FOS_BF16;
   const int64_t strips = (p->n + (is_bf16 ? fos::GQ_COLS : fos::GB_COLS) - 1) / (is_bf16 ? fos::GQ_COLS : fos::GB_COLS);
@@ -771,7 +771,6 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
     LAUNCH_CHECK();
     restart_plain(f);                // y lives in the candidate block; part2 partials are counted from this run on
   }
-  const int64_t strips = (p->n + (is_bf16 ? fos::GQ_COLS : fos::GB_COLS) - 1) / (is_bf16 ? fos::GQ_COLS : fos::GB_COLS);
   for (int it = 0; it < iters; ++it) {
     if ((rc = prof_mark(p, true))) return rc;
     if (use_cluster && (rc = launch_cluster_pass(p))) {
@@ -788,31 +787,15 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
       int nwg1 = 0;
       // column-sharded: b enters the sum over the ranks once (rank 0); R = sum_p A_p Y_p - b is the ONE exchange per panel
       const float* bp = b16 ? b16 + row0 * fos::BT_NV : (p->b && !(cols && p->comm->rank != 0)) ? p->b + row0 : nullptr;
-      if (weighted)                  // labels, fold ids and weights are offset with the panel (panel rows are a multiple of 256)
-        rc = launch_batch_product_weighted(p, Ap, p->b + row0, 1, rows, p->multi.rbuf16, &nwg1, fold_of_row ? fold_of_row + row0 : nullptr,
-                                           held, p->row_weight + row0);
-      else if (logit)                // labels and fold ids are offset with the panel
-        rc = launch_batch_product_logit(p, Ap, p->b + row0, rows, p->multi.rbuf16, &nwg1, fold_of_row ? fold_of_row + row0 : nullptr, held);
-      else if (fold_of_row)          // the ids are offset with the panel as b is (panel rows are a multiple of 256)
-        rc = launch_batch_product_folds(p, Ap, p->b + row0, rows, p->multi.rbuf16, &nwg1, fold_of_row + row0, *held);
-      else
-        rc = launch_batch_product(p, Ap, bp, rows, 1, p->multi.rbuf16, &nwg1, nullptr, b16 != nullptr);
-      if (rc) return rc;
+      // a fold mask, the logistic loss and row weights read the problem's own b (the labels); fold ids and weights are offset
+      // with the panel as b is (panel rows are a multiple of 256)
+      BatchLaunch L{};
+      L.A = Ap; L.b = (fold_of_row || logit || weighted) ? p->b + row0 : bp; L.use_b = 1; L.rows = rows; L.rout = p->multi.rbuf16;
+      L.bblock = b16 != nullptr; L.fold_of_row = fold_of_row ? fold_of_row + row0 : nullptr; L.held = held;
+      L.row_weight = weighted ? p->row_weight + row0 : nullptr;
+      if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
       if (cols && (rc = reduce_across(p, p->multi.rbuf16, (size_t)rows * fos::BT_NV, false))) return rc;
-      const dim3 grid((unsigned)strips, (unsigned)g_splits);
-#define FOS_GRAM(T, ACC)                                                                                                  \
-  hipLaunchKernelGGL((fos::gram_batch_mfma_kernel<T, ACC>), grid, dim3(fos::GB_THREADS), 0, p->stream, (const T*)Ap, p->lda, \
-                     rows, (int)p->n, p->multi.rbuf16, p->multi.gram_rows_per_split, p->multi.slabs16, p->n)
-      if (is_bf16) {
-        if (panel)
-          hipLaunchKernelGGL(fos::gram_batch_mfma_bf16_kernel<true>, grid, dim3(fos::GB_THREADS), 0, p->stream,
-                             (const fos::bf16_t*)Ap, p->lda, rows, (int)p->n, p->multi.rbuf16, p->multi.gram_rows_per_split, p->multi.slabs16, p->n);
-        else
-          hipLaunchKernelGGL(fos::gram_batch_mfma_bf16_kernel<false>, grid, dim3(fos::GB_THREADS), 0, p->stream,
-                             (const fos::bf16_t*)Ap, p->lda, rows, (int)p->n, p->multi.rbuf16, p->multi.gram_rows_per_split, p->multi.slabs16, p->n);
-      } else { if (panel) FOS_GRAM(float, true); else FOS_GRAM(float, false); }
-#undef FOS_GRAM
-      LAUNCH_CHECK();
+      if ((rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
     }
     if ((rc = prof_mark(p, false))) return rc;
     // row-sharded problem: the 16 partial gradients (all row splits) are summed over the ranks before the updates
@@ -1041,11 +1024,9 @@ int fos_gram_apply(const float* X, int nv, fos_problem* p, float* G) {
     const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
     const char* Ap = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz;
     int nwg1 = 0;
-    if (p->row_weight)               // R = w (A_panel X): neither b nor the loss enters
-      rc = launch_batch_product_weighted(p, Ap, nullptr, 0, rows, p->multi.rbuf16, &nwg1, nullptr, nullptr, p->row_weight + row0);
-    else
-      rc = launch_batch_product(p, Ap, nullptr, rows, 0, p->multi.rbuf16, &nwg1);
-    if (rc) return rc;
+    BatchLaunch L{};                 // R = A_panel X, or w (A_panel X): neither b nor the loss enters
+    L.A = Ap; L.rows = rows; L.rout = p->multi.rbuf16; L.row_weight = p->row_weight ? p->row_weight + row0 : nullptr;
+    if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
     if ((rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
   }
   hipLaunchKernelGGL(gram_slab_sum_kernel, dim3(grid_1d((int64_t)nv * p->n, 256, 1024)), dim3(256), 0, p->stream, p->multi.slabs16,

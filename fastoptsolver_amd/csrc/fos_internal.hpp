@@ -382,26 +382,26 @@ int launch_pass(fos_problem* p, const YSource& ys, const float* b, bool with_g, 
                 double* rr_to = nullptr);
 // slabs -> gbuf[0..n], summed over the ranks when the problem is row-sharded; rr_out (nullable) = the global ||r||^2
 int launch_slab_reduce(fos_problem* p, int n_rr, float* gbuf, double* rr_out, const int* stopped);
-// Product 1 on `rows` rows starting at A / b: q_part[wg][16] partial squared norms, rout (nullable): the residuals
-// (bblock: b is the rows x 16 right-hand-side block, column j subtracts its own b[row * 16 + j])
-int launch_batch_product(fos_problem* p, const void* A, const float* b, int64_t rows_total, int use_b, float* rout, int* nwg_out,
-                         const int* stopped = nullptr, bool bblock = false);
 // held (HOST, nv entries, each -1..254) -> the by-value block of the fold kernels, the slots beyond nv set to -1 (in either
 // mode such a column is all zero: its candidate is).  False when an entry is out of range.
 bool fold_held_block(const int32_t* held, int nv, fos::FoldHeld* out);
-// Product 1 with the fold mask of K-fold cross-validation (batch_trial.hpp FOLD_TRAIN / FOLD_HELD) on `rows` rows starting at
-// A / b / fold_of_row; geometry and outputs as launch_batch_product.  rout given: the train-store form (R zero on every
-// column's held-out rows); rout null: the held-out residual form (q_part = held-out squared errors).
-int launch_batch_product_folds(fos_problem* p, const void* A, const float* b, int64_t rows_total, float* rout, int* nwg_out,
-                               const uint8_t* fold_of_row, const fos::FoldHeld& held);
-// Product 1 of a logistic problem (kF32Logit / kBf16Logit): rout = sigma(A Y) - b when given, q_part = log-loss partials;
-// fold_of_row / held (both or neither): the masked forms as launch_batch_product_folds.
-int launch_batch_product_logit(fos_problem* p, const void* A, const float* b, int64_t rows_total, float* rout, int* nwg_out,
-                               const uint8_t* fold_of_row, const fos::FoldHeld* held);
-// Product 1 of a problem with row weights (kF32Weighted / kBf16Weighted): the form of the problem's loss with R and the sums
-// weighted per row; fold_of_row / held as launch_batch_product_logit; use_b = 0: R = w (A Y) (fos_gram_apply).
-int launch_batch_product_weighted(fos_problem* p, const void* A, const float* b, int use_b, int64_t rows_total, float* rout,
-                                  int* nwg_out, const uint8_t* fold_of_row, const fos::FoldHeld* held, const float* row_weight);
+// What one launch of product 1 (batch_trial.hpp) can be given; a zero or null member is "off".  On `rows` rows starting at
+// A / b / fold_of_row / row_weight: q_part[wg][16] takes the partial sums of every column, rout (nullable) the residual block R.
+struct BatchLaunch {
+  const void* A;                 // fp32 or bf16, as the problem's dtype says
+  const float* b;                // subtracted when use_b is set (the labels of a logistic problem)
+  int use_b;                     // 0: R = A Y, the squared form on any problem (fos_gram_apply, the line search)
+  int64_t rows;
+  float* rout;
+  bool bblock;                   // b is the rows x 16 right-hand-side block: column j subtracts its own b[row * 16 + j]
+  const int* stopped;            // device flag: the launch is a no-op while it is set
+  const uint8_t* fold_of_row;    // the fold mask of K-fold cross-validation (with held; both or neither): with rout R is zero
+  const fos::FoldHeld* held;     // on every column's held-out rows (FOLD_TRAIN), without rout the sums run over them (FOLD_HELD)
+  const float* row_weight;       // R and the sums are weighted per row
+};
+// The one launcher of product 1: the form (STORE_R, BBLOCK, FOLD, LOSS, WEIGHT) follows from L and the problem's loss and is
+// looked up in the one table of launchable forms (fos_plan.hip kBatchForms); *nwg_out = the rows of q_part written.
+int launch_batch_product(fos_problem* p, const BatchLaunch& L, int* nwg_out);
 // The one guard of the entry points that form an unweighted squared-loss residual, gradient or objective: refuses a logistic
 // problem and a problem with row weights (FOS_ERR_UNSUPPORTED) before any launch or change of handle state.
 int need_squared(const fos_problem* p, const char* fn);

@@ -589,116 +589,55 @@ int pack_candidates(fos_problem* p, const float* X, int nv) {
   return FOS_OK;
 }
 
-// bf16 variants of the batched kernel: (row blocks per wave, tile columns), rows per workgroup, workgroups per CU.
-// Measured at 65536 x 8192 (tools/bench_bq.py): <1,128> 208.6 us, <2,64> 213.5 us, <2,128> 166.6 us (80.6 % of HBM),
-// <4,64> 170.4 us.  The 128-row tile halves the LDS re-reads of the candidate fragments per byte of A; the 64-row
-// tile is kept for short problems, where it gives twice as many workgroups.
+// Product 1 (batch_trial.hpp): the kernel pointers stay typed, so every instantiation is checked against its signature.
 typedef void (*Bf16Batch)(const fos::bf16_t*, int64_t, const float*, int, int64_t, int, const unsigned short*, int64_t, double*,
                           float*, const int*, const uint8_t*, fos::FoldHeld, const float*);
-// fn_store: also keeps R (gram_batch.hpp); fn_rhs / fn_store_rhs: the same with a right-hand side per column (B16 block)
-struct Bf16BatchVariant { Bf16Batch fn, fn_store; int rows; int wg_per_cu; Bf16Batch fn_rhs, fn_store_rhs; };
-const Bf16BatchVariant kBf16Batch[] = {
-    {fos::residual_batch_mfma_bf16_kernel<1, 128>, fos::residual_batch_mfma_bf16_kernel<1, 128, true>, 64, 2,
-     fos::residual_batch_mfma_bf16_kernel<1, 128, false, true>, fos::residual_batch_mfma_bf16_kernel<1, 128, true, true>},
-    {fos::residual_batch_mfma_bf16_kernel<2, 128>, fos::residual_batch_mfma_bf16_kernel<2, 128, true>, 128, 1,
-     fos::residual_batch_mfma_bf16_kernel<2, 128, false, true>, fos::residual_batch_mfma_bf16_kernel<2, 128, true, true>},
-};
-
 typedef void (*F32Batch)(const float*, int64_t, const float*, int, int64_t, int, const float*, int64_t, double*, float*,
                          const int*, const uint8_t*, fos::FoldHeld, const float*);
-struct F32BatchVariant { F32Batch fn, fn_store; int rows; int wg_per_cu; F32Batch fn_rhs, fn_store_rhs; };
+
+// The launchable forms of product 1, one line each: X(STORE_R, BBLOCK, FOLD, LOSS, WEIGHT).  STORE_R also keeps R
+// (gram_batch.hpp reads it); BBLOCK: a right-hand side per column (B16 block); FOLD_TRAIN keeps R with every column zero on its
+// held-out rows, FOLD_HELD sums over the held-out rows only (K-fold cross-validation in lockstep); LOSS_LOGISTIC: R =
+// sigma(A Y) - b and the log-loss sums (b holds labels in [0, 1]); WEIGHT: R and the sums weighted per row
+// (fos_row_weights_bind).  tests/_menu_product1.py reads this list and FOS_P1_ENTRY.
+#define FOS_P1_FORMS(X)                                  \
+  X(false, false, FOLD_OFF, LOSS_SQUARED, false)         \
+  X(true, false, FOLD_OFF, LOSS_SQUARED, false)          \
+  X(false, true, FOLD_OFF, LOSS_SQUARED, false)          \
+  X(true, true, FOLD_OFF, LOSS_SQUARED, false)           \
+  X(true, false, FOLD_TRAIN, LOSS_SQUARED, false)        \
+  X(false, false, FOLD_HELD, LOSS_SQUARED, false)        \
+  X(true, false, FOLD_OFF, LOSS_LOGISTIC, false)         \
+  X(false, false, FOLD_OFF, LOSS_LOGISTIC, false)        \
+  X(true, false, FOLD_TRAIN, LOSS_LOGISTIC, false)       \
+  X(false, false, FOLD_HELD, LOSS_LOGISTIC, false)       \
+  X(true, false, FOLD_OFF, LOSS_SQUARED, true)           \
+  X(false, false, FOLD_OFF, LOSS_SQUARED, true)          \
+  X(true, false, FOLD_TRAIN, LOSS_SQUARED, true)         \
+  X(false, false, FOLD_HELD, LOSS_SQUARED, true)         \
+  X(true, false, FOLD_OFF, LOSS_LOGISTIC, true)          \
+  X(false, false, FOLD_OFF, LOSS_LOGISTIC, true)         \
+  X(true, false, FOLD_TRAIN, LOSS_LOGISTIC, true)        \
+  X(false, false, FOLD_HELD, LOSS_LOGISTIC, true)
+
+// A form and the four kernels it stands for: fp32 and bf16 (column tile 128), each at RB 1 and RB 2 (index: tile variant).
+struct BatchForm { bool store, bblock; int fold, loss; bool weight; };
+struct BatchEntry { BatchForm form; F32Batch f32[2]; Bf16Batch bf16[2]; };
+#define FOS_P1_ENTRY(S, B, F, L, W)                                                                                               \
+  {{S, B, fos::F, fos::L, W},                                                                                                     \
+   {fos::residual_batch_mfma_kernel<1, S, B, fos::F, fos::L, W>, fos::residual_batch_mfma_kernel<2, S, B, fos::F, fos::L, W>},    \
+   {fos::residual_batch_mfma_bf16_kernel<1, 128, S, B, fos::F, fos::L, W>,                                                        \
+    fos::residual_batch_mfma_bf16_kernel<2, 128, S, B, fos::F, fos::L, W>}},
+const BatchEntry kBatchForms[] = {FOS_P1_FORMS(FOS_P1_ENTRY)};
+#undef FOS_P1_ENTRY
+
+// The two tile variants (row blocks per wave RB 1, 2): rows per workgroup, workgroups per CU for fp32 and for bf16.
+// bf16, measured at 65536 x 8192 (tools/bench_bq.py), <RB, tile columns>: <1,128> 208.6 us, <2,64> 213.5 us, <2,128> 166.6 us
+// (80.6 % of HBM), <4,64> 170.4 us.  The 128-row tile halves the LDS re-reads of the candidate fragments per byte of A; the
+// 64-row tile is kept for short problems, where it gives twice as many workgroups.
 // fp32, measured at 65536 x 8192: <1> 64-row tile 368-395 us, <2> 128-row tile 335.7 us (80 % of HBM), <4> 336.8 us.
-const F32BatchVariant kF32Batch[] = {
-    {fos::residual_batch_mfma_kernel<1>, fos::residual_batch_mfma_kernel<1, true>, 64, 3,
-     fos::residual_batch_mfma_kernel<1, false, true>, fos::residual_batch_mfma_kernel<1, true, true>},
-    {fos::residual_batch_mfma_kernel<2>, fos::residual_batch_mfma_kernel<2, true>, 128, 2,
-     fos::residual_batch_mfma_kernel<2, false, true>, fos::residual_batch_mfma_kernel<2, true, true>},
-};
-
-// The fold forms of product 1 (K-fold cross-validation in lockstep), one entry per tile variant of the tables above:
-// store_train keeps R with every column zero on its held-out rows, resid_held sums the held-out squared errors.
-struct Bf16FoldVariant { Bf16Batch store_train, resid_held; };
-const Bf16FoldVariant kBf16Folds[] = {
-    {fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_TRAIN>,
-     fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_HELD>},
-    {fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_TRAIN>,
-     fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_HELD>},
-};
-struct F32FoldVariant { F32Batch store_train, resid_held; };
-const F32FoldVariant kF32Folds[] = {
-    {fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_TRAIN>, fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_HELD>},
-    {fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_TRAIN>, fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_HELD>},
-};
-
-// The logistic forms of product 1 (the problem's loss is FOS_LOSS_LOGISTIC: b holds labels in [0, 1]), one entry per tile
-// variant of the tables above: store keeps R = sigma(A Y) - b for product 2, resid only sums the log-loss; train_store /
-// held_resid are the two with the fold masks of cross-validation.
-struct Bf16LogitVariant { Bf16Batch store, resid, train_store, held_resid; };
-const Bf16LogitVariant kBf16Logit[] = {
-    {fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
-     fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
-     fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC>,
-     fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC>},
-    {fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
-     fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
-     fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC>,
-     fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC>},
-};
-struct F32LogitVariant { F32Batch store, resid, train_store, held_resid; };
-const F32LogitVariant kF32Logit[] = {
-    {fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
-     fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
-     fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC>,
-     fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC>},
-    {fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
-     fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC>,
-     fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC>,
-     fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC>},
-};
-
-// The weighted forms of product 1 (per-row sample weights bound with fos_row_weights_bind), one entry per tile variant of the
-// tables above: form[loss] holds store / resid / train_store / held_resid as the logistic tables do, all with WEIGHT on -
-// R = w (A Y - b) or w (sigma(A Y) - b), q_part = sum w r^2 or sum w l.
-struct Bf16WeightedForms { Bf16Batch store, resid, train_store, held_resid; };
-struct Bf16WeightedVariant { Bf16WeightedForms form[2]; };
-const Bf16WeightedVariant kBf16Weighted[] = {
-    {{{fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
-      fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
-      fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_TRAIN, fos::LOSS_SQUARED, true>,
-      fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_HELD, fos::LOSS_SQUARED, true>},
-     {fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
-      fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
-      fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC, true>,
-      fos::residual_batch_mfma_bf16_kernel<1, 128, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC, true>}}},
-    {{{fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
-      fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
-      fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_TRAIN, fos::LOSS_SQUARED, true>,
-      fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_HELD, fos::LOSS_SQUARED, true>},
-     {fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
-      fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
-      fos::residual_batch_mfma_bf16_kernel<2, 128, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC, true>,
-      fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC, true>}}},
-};
-struct F32WeightedForms { F32Batch store, resid, train_store, held_resid; };
-struct F32WeightedVariant { F32WeightedForms form[2]; };
-const F32WeightedVariant kF32Weighted[] = {
-    {{{fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
-      fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
-      fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_TRAIN, fos::LOSS_SQUARED, true>,
-      fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_HELD, fos::LOSS_SQUARED, true>},
-     {fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
-      fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
-      fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC, true>,
-      fos::residual_batch_mfma_kernel<1, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC, true>}}},
-    {{{fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
-      fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_OFF, fos::LOSS_SQUARED, true>,
-      fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_TRAIN, fos::LOSS_SQUARED, true>,
-      fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_HELD, fos::LOSS_SQUARED, true>},
-     {fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
-      fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_OFF, fos::LOSS_LOGISTIC, true>,
-      fos::residual_batch_mfma_kernel<2, true, false, fos::FOLD_TRAIN, fos::LOSS_LOGISTIC, true>,
-      fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_HELD, fos::LOSS_LOGISTIC, true>}}},
-};
+struct BatchTile { int rows, f32_wg_per_cu, bf16_wg_per_cu; };
+const BatchTile kBatchTiles[2] = {{64, 3, 2}, {128, 2, 1}};
 
 // The grid of product 1 on `rows_total` rows: the tile variant (0: 64-row tile, 1: 128-row tile), the row groups per
 // workgroup and the number of workgroups (rows of q_part).
@@ -706,8 +645,8 @@ struct BatchGrid { int variant; int64_t gpw, nwg; };
 static BatchGrid batch_grid(const fos_problem* p, int64_t rows_total) {
   const bool is_bf16 = p->dtype == FOS_BF16;
   const int variant = rows_total >= 128 * (int64_t)p->ncu ? 1 : 0;
-  const int rows = is_bf16 ? kBf16Batch[variant].rows : kF32Batch[variant].rows;
-  const int per_cu = is_bf16 ? kBf16Batch[variant].wg_per_cu : kF32Batch[variant].wg_per_cu;
+  const int rows = kBatchTiles[variant].rows;
+  const int per_cu = is_bf16 ? kBatchTiles[variant].bf16_wg_per_cu : kBatchTiles[variant].f32_wg_per_cu;
   const int64_t ngroups = (rows_total + rows - 1) / rows;
   int64_t nwg = std::min<int64_t>(ngroups, per_cu * (int64_t)p->ncu);
   const int64_t gpw = (ngroups + nwg - 1) / nwg;
@@ -715,23 +654,28 @@ static BatchGrid batch_grid(const fos_problem* p, int64_t rows_total) {
   return {variant, gpw, nwg};
 }
 
-// Product 1 on `rows` rows starting at A / b: q_part[wg][16] partial squared norms, rout (nullable): the residuals.
-// Returns the number of workgroups (rows of q_part).
-int launch_batch_product(fos_problem* p, const void* A, const float* b, int64_t rows_total, int use_b, float* rout, int* nwg_out,
-                         const int* stopped, bool bblock) {
-  const BatchGrid g = batch_grid(p, rows_total);
-  const Bf16BatchVariant& vq = kBf16Batch[g.variant];
-  const F32BatchVariant& vf = kF32Batch[g.variant];
+// Product 1 (fos_internal.hpp BatchLaunch): the form follows from what the launch is given, and a form that is not in
+// kBatchForms (a right-hand-side block with a fold mask, say) is refused before any launch; no entry point asks for one.
+int launch_batch_product(fos_problem* p, const BatchLaunch& L, int* nwg_out) {
+  const BatchForm want{L.rout != nullptr, L.bblock, L.fold_of_row ? (L.rout ? fos::FOLD_TRAIN : fos::FOLD_HELD) : fos::FOLD_OFF,
+                       (L.use_b && p->loss == FOS_LOSS_LOGISTIC) ? fos::LOSS_LOGISTIC : fos::LOSS_SQUARED, L.row_weight != nullptr};
+  const BatchEntry* hit = std::find_if(std::begin(kBatchForms), std::end(kBatchForms), [&](const BatchEntry& c) {
+    return c.form.store == want.store && c.form.bblock == want.bblock && c.form.fold == want.fold && c.form.loss == want.loss &&
+           c.form.weight == want.weight;
+  });
+  if (hit == std::end(kBatchForms)) return fail(FOS_ERR_STATE, "launch_batch_product: product 1 has no such form");
+  const BatchEntry& e = *hit;
+  const BatchGrid g = batch_grid(p, L.rows);
+  const int use_b = (L.use_b && L.b) ? 1 : 0;
+  const fos::FoldHeld held = L.held ? *L.held : fos::FoldHeld{};
   if (p->dtype == FOS_BF16)
-    hipLaunchKernelGGL(bblock ? (rout ? vq.fn_store_rhs : vq.fn_rhs) : (rout ? vq.fn_store : vq.fn), dim3((unsigned)g.nwg),
-                       dim3(fos::BT_THREADS), 0, p->stream, (const fos::bf16_t*)A, p->lda, b, (use_b && b) ? 1 : 0,
-                       rows_total, (int)p->n, (const unsigned short*)p->cand.xp.get(), g.gpw, p->cand.q_part, rout, stopped,
-                       (const uint8_t*)nullptr, fos::FoldHeld{}, (const float*)nullptr);
+    hipLaunchKernelGGL(e.bf16[g.variant], dim3((unsigned)g.nwg), dim3(fos::BT_THREADS), 0, p->stream, (const fos::bf16_t*)L.A,
+                       p->lda, L.b, use_b, L.rows, (int)p->n, (const unsigned short*)p->cand.xp.get(), g.gpw, p->cand.q_part, L.rout,
+                       L.stopped, L.fold_of_row, held, L.row_weight);
   else
-    hipLaunchKernelGGL(bblock ? (rout ? vf.fn_store_rhs : vf.fn_rhs) : (rout ? vf.fn_store : vf.fn), dim3((unsigned)g.nwg),
-                       dim3(fos::BT_THREADS), 0, p->stream, (const float*)A, p->lda, b, (use_b && b) ? 1 : 0, rows_total,
-                       (int)p->n, p->cand.xp, g.gpw, p->cand.q_part, rout, stopped, (const uint8_t*)nullptr, fos::FoldHeld{},
-                       (const float*)nullptr);
+    hipLaunchKernelGGL(e.f32[g.variant], dim3((unsigned)g.nwg), dim3(fos::BT_THREADS), 0, p->stream, (const float*)L.A, p->lda,
+                       L.b, use_b, L.rows, (int)p->n, p->cand.xp, g.gpw, p->cand.q_part, L.rout, L.stopped, L.fold_of_row, held,
+                       L.row_weight);
   LAUNCH_CHECK();
   *nwg_out = (int)g.nwg;
   return FOS_OK;
@@ -757,72 +701,6 @@ bool fold_held_block(const int32_t* held, int nv, fos::FoldHeld* out) {
   return true;
 }
 
-int launch_batch_product_folds(fos_problem* p, const void* A, const float* b, int64_t rows_total, float* rout, int* nwg_out,
-                               const uint8_t* fold_of_row, const fos::FoldHeld& held) {
-  const BatchGrid g = batch_grid(p, rows_total);
-  const Bf16FoldVariant& vq = kBf16Folds[g.variant];
-  const F32FoldVariant& vf = kF32Folds[g.variant];
-  if (p->dtype == FOS_BF16)
-    hipLaunchKernelGGL(rout ? vq.store_train : vq.resid_held, dim3((unsigned)g.nwg), dim3(fos::BT_THREADS), 0, p->stream,
-                       (const fos::bf16_t*)A, p->lda, b, 1, rows_total, (int)p->n, (const unsigned short*)p->cand.xp.get(), g.gpw,
-                       p->cand.q_part, rout, (const int*)nullptr, fold_of_row, held, (const float*)nullptr);
-  else
-    hipLaunchKernelGGL(rout ? vf.store_train : vf.resid_held, dim3((unsigned)g.nwg), dim3(fos::BT_THREADS), 0, p->stream,
-                       (const float*)A, p->lda, b, 1, rows_total, (int)p->n, p->cand.xp, g.gpw, p->cand.q_part, rout,
-                       (const int*)nullptr, fold_of_row, held, (const float*)nullptr);
-  LAUNCH_CHECK();
-  *nwg_out = (int)g.nwg;
-  return FOS_OK;
-}
-
-// Product 1 of a logistic problem on `rows` rows starting at A / b (the labels): R = sigma(A Y) - b into rout when given,
-// q_part[wg][16] the partial log-loss sums.  fold_of_row / held given: the masked forms, train-store with rout, heldout-resid
-// without.  Geometry as launch_batch_product.
-int launch_batch_product_logit(fos_problem* p, const void* A, const float* b, int64_t rows_total, float* rout, int* nwg_out,
-                               const uint8_t* fold_of_row, const fos::FoldHeld* held) {
-  const BatchGrid g = batch_grid(p, rows_total);
-  const Bf16LogitVariant& vq = kBf16Logit[g.variant];
-  const F32LogitVariant& vf = kF32Logit[g.variant];
-  const fos::FoldHeld hb = held ? *held : fos::FoldHeld{};
-  if (p->dtype == FOS_BF16)
-    hipLaunchKernelGGL(fold_of_row ? (rout ? vq.train_store : vq.held_resid) : (rout ? vq.store : vq.resid), dim3((unsigned)g.nwg),
-                       dim3(fos::BT_THREADS), 0, p->stream, (const fos::bf16_t*)A, p->lda, b, 1, rows_total, (int)p->n,
-                       (const unsigned short*)p->cand.xp.get(), g.gpw, p->cand.q_part, rout, (const int*)nullptr, fold_of_row, hb,
-                       (const float*)nullptr);
-  else
-    hipLaunchKernelGGL(fold_of_row ? (rout ? vf.train_store : vf.held_resid) : (rout ? vf.store : vf.resid), dim3((unsigned)g.nwg),
-                       dim3(fos::BT_THREADS), 0, p->stream, (const float*)A, p->lda, b, 1, rows_total, (int)p->n, p->cand.xp, g.gpw,
-                       p->cand.q_part, rout, (const int*)nullptr, fold_of_row, hb, (const float*)nullptr);
-  LAUNCH_CHECK();
-  *nwg_out = (int)g.nwg;
-  return FOS_OK;
-}
-
-// Product 1 of a problem with row weights on `rows` rows starting at A / b / row_weight (use_b = 0: R = w (A Y), the first
-// half of fos_gram_apply): the weighted form of the problem's loss, with the fold mask when fold_of_row / held are given.
-// Geometry as launch_batch_product.
-int launch_batch_product_weighted(fos_problem* p, const void* A, const float* b, int use_b, int64_t rows_total, float* rout,
-                                  int* nwg_out, const uint8_t* fold_of_row, const fos::FoldHeld* held, const float* row_weight) {
-  const BatchGrid g = batch_grid(p, rows_total);
-  const int loss = (use_b && p->loss == FOS_LOSS_LOGISTIC) ? 1 : 0;
-  const Bf16WeightedForms& vq = kBf16Weighted[g.variant].form[loss];
-  const F32WeightedForms& vf = kF32Weighted[g.variant].form[loss];
-  const fos::FoldHeld hb = held ? *held : fos::FoldHeld{};
-  if (p->dtype == FOS_BF16)
-    hipLaunchKernelGGL(fold_of_row ? (rout ? vq.train_store : vq.held_resid) : (rout ? vq.store : vq.resid), dim3((unsigned)g.nwg),
-                       dim3(fos::BT_THREADS), 0, p->stream, (const fos::bf16_t*)A, p->lda, b, (use_b && b) ? 1 : 0, rows_total,
-                       (int)p->n, (const unsigned short*)p->cand.xp.get(), g.gpw, p->cand.q_part, rout, (const int*)nullptr,
-                       fold_of_row, hb, row_weight);
-  else
-    hipLaunchKernelGGL(fold_of_row ? (rout ? vf.train_store : vf.held_resid) : (rout ? vf.store : vf.resid), dim3((unsigned)g.nwg),
-                       dim3(fos::BT_THREADS), 0, p->stream, (const float*)A, p->lda, b, (use_b && b) ? 1 : 0, rows_total, (int)p->n,
-                       p->cand.xp, g.gpw, p->cand.q_part, rout, (const int*)nullptr, fold_of_row, hb, row_weight);
-  LAUNCH_CHECK();
-  *nwg_out = (int)g.nwg;
-  return FOS_OK;
-}
-
-// q[j] = ||A Xp_j - use_b*b||^2 -> out16 (device); Xp already in p->cand.xp.
 // q[j] = sum_i R[i][j]^2 of an m x 16 residual block (column-sharded candidate pass, after the sum over the ranks)
 __global__ __launch_bounds__(256) void colnorms16_partials_kernel(const float* __restrict__ R, int64_t m, double* __restrict__ part,
                                                                  const int* stopped) {
@@ -847,16 +725,33 @@ __global__ __launch_bounds__(256) void unsum16_if_stopped_kernel(float* __restri
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) v[i] *= scale;
 }
 
-int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* stopped, const float* b16) {
+// Product 1 without R on all rows of the problem (A, rows and rout of L are set here; the candidates are packed) ->
+// out16[j] (device) = the sum of q_part[.][j], summed over the ranks of a row-sharded problem.
+static int residual_batch_sums(fos_problem* p, BatchLaunch L, double* out16) {
+  L.A = p->A; L.rows = p->m; L.rout = nullptr;
   int rc = prof_mark(p, true);
   if (rc) return rc;
   int nwg = 0;
+  if ((rc = launch_batch_product(p, L, &nwg))) return rc;
+  if ((rc = prof_mark(p, false))) return rc;
+  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->cand.q_part, nwg, fos::BT_NV, out16);
+  LAUNCH_CHECK();
+  return reduce_across(p, out16, fos::BT_NV, true);      // sharded: ||A dlt_j||^2 = sum over the row blocks
+}
+
+// q[j] = ||A Xp_j - use_b*b||^2 -> out16 (device); Xp already in p->cand.xp.
+int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* stopped, const float* b16) {
+  BatchLaunch L{};
+  L.use_b = use_b; L.stopped = stopped;
   if (p->col_sharded) {
+    int rc = prof_mark(p, true);
+    if (rc) return rc;
+    int nwg = 0;
     // Column-sharded: ||A dlt_j||^2 = ||sum_p A_p dlt_{j,p}||^2.  Every rank's product 1 keeps its partial residuals
     // (m x 16 floats), ONE all-reduce sums the blocks of all 16 candidates (4 MiB at m = 65536), the column norms follow.
     if ((rc = p->ws.rcols16.reserve((size_t)p->m * fos::BT_NV))) return rc;
-    const float* b_here = p->comm->rank == 0 ? p->b : nullptr;
-    if ((rc = launch_batch_product(p, p->A, b_here, p->m, use_b, p->ws.rcols16, &nwg, stopped))) return rc;
+    L.A = p->A; L.b = p->comm->rank == 0 ? p->b : nullptr; L.rows = p->m; L.rout = p->ws.rcols16;
+    if ((rc = launch_batch_product(p, L, &nwg))) return rc;
     if ((rc = prof_mark(p, false))) return rc;
     if (stopped != nullptr) {        // a no-op product leaves the last SUM in place: divide it back before the in-place all-reduce
       hipLaunchKernelGGL(unsum16_if_stopped_kernel, dim3(grid_1d(p->m * fos::BT_NV, 256, 1024)), dim3(256), 0, p->stream,
@@ -871,11 +766,8 @@ int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* s
     LAUNCH_CHECK();
     return FOS_OK;
   }
-  if ((rc = launch_batch_product(p, p->A, b16 ? b16 : p->b, p->m, use_b, nullptr, &nwg, stopped, b16 != nullptr))) return rc;
-  if ((rc = prof_mark(p, false))) return rc;
-  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->cand.q_part, (int)nwg, fos::BT_NV, out16);
-  LAUNCH_CHECK();
-  return reduce_across(p, out16, fos::BT_NV, true);      // sharded: ||A dlt_j||^2 = sum over the row blocks
+  L.b = b16 ? b16 : p->b; L.bblock = b16 != nullptr;
+  return residual_batch_sums(p, L, out16);
 }
 
 // ---- multi-lambda lockstep run ----------------------------------------------------------------------------------
@@ -1700,49 +1592,29 @@ int fos_residual_objective(fos_problem* p, const float* x, double* out3) {
   return FOS_OK;
 }
 
-// fos_residual_batch / _folds on a logistic problem: out16[j] = sum of the log-loss of column j over all rows, or over the rows
-// of the fold it holds out.  Arguments are checked.  A problem with row weights of either loss comes here too: the sums are
-// sum w l or sum w r^2 (launch_batch_product_weighted).
-static int residual_batch_logit(fos_problem* p, const char* fn, const float* X, int nv, double* out16, const uint8_t* fold_of_row,
-                                const fos::FoldHeld* held) {
+// fos_residual_batch / _folds on the shapes of the matrix-core pair, in the form the problem and the fold mask ask for:
+// out16[j] = sum r^2 or the sum of the log-loss of column j, weighted per row on a problem with row weights, over all rows or
+// over the rows of the fold that column holds out.  Arguments are checked.
+static int residual_batch_pair(fos_problem* p, const char* fn, const float* X, int nv, double* out16, const uint8_t* fold_of_row,
+                               const fos::FoldHeld* held) {
   if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the shape has no matrix-core pair");
   int rc = ensure_batch_workspace(p);
   if (rc) return rc;
-  if (p->dtype == FOS_BF16)
-    hipLaunchKernelGGL(fos::xq_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
-                       (int)p->cand.n_pad, nv, (unsigned short*)p->cand.xp.get());
-  else
-    hipLaunchKernelGGL(xp_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
-                       (int)p->cand.n_pad, nv, p->cand.xp);
-  LAUNCH_CHECK();
-  if ((rc = prof_mark(p, true))) return rc;
-  int nwg = 0;
-  if (p->row_weight)
-    rc = launch_batch_product_weighted(p, p->A, p->b, 1, p->m, nullptr, &nwg, fold_of_row, held, p->row_weight);
-  else
-    rc = launch_batch_product_logit(p, p->A, p->b, p->m, nullptr, &nwg, fold_of_row, held);
-  if (rc) return rc;
-  if ((rc = prof_mark(p, false))) return rc;
-  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->cand.q_part, nwg, fos::BT_NV, out16);
-  LAUNCH_CHECK();
-  return FOS_OK;
+  if ((rc = pack_candidates(p, X, nv))) return rc;
+  BatchLaunch L{};
+  L.b = p->b; L.use_b = 1; L.fold_of_row = fold_of_row; L.held = held; L.row_weight = p->row_weight;
+  return residual_batch_sums(p, L, out16);
 }
 
 int fos_residual_batch(fos_problem* p, const float* X, int nv, int use_b, double* out16) {
   if (!p || !X || !out16 || nv < 1 || nv > fos::BT_NV) return fail(FOS_ERR_ARG, "fos_residual_batch: bad argument");
   if (!use_b)                        // ||A X_j||^2 is a squared-loss quantity
     if (int rc = need_squared(p, "fos_residual_batch (use_b = 0)")) return rc;
-  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight) return residual_batch_logit(p, "fos_residual_batch", X, nv, out16, nullptr, nullptr);
+  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight) return residual_batch_pair(p, "fos_residual_batch", X, nv, out16, nullptr, nullptr);
   if (!batch_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch: needs the fused path");
   int rc = ensure_batch_workspace(p);
   if (rc) return rc;
-  if (p->dtype == FOS_BF16)
-    hipLaunchKernelGGL(fos::xq_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
-                       (int)p->cand.n_pad, nv, (unsigned short*)p->cand.xp.get());
-  else
-    hipLaunchKernelGGL(xp_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
-                       (int)p->cand.n_pad, nv, p->cand.xp);
-  LAUNCH_CHECK();
+  if ((rc = pack_candidates(p, X, nv))) return rc;
   return launch_residual_batch(p, use_b, out16);
 }
 
@@ -1755,13 +1627,7 @@ int fos_residual_batch_rhs(fos_problem* p, const float* X, int nv, const float* 
   int rc = ensure_batch_workspace(p);
   if (rc) return rc;
   if ((rc = stage_b16(p, B, ldb, nv))) return rc;
-  if (p->dtype == FOS_BF16)
-    hipLaunchKernelGGL(fos::xq_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
-                       (int)p->cand.n_pad, nv, (unsigned short*)p->cand.xp.get());
-  else
-    hipLaunchKernelGGL(xp_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
-                       (int)p->cand.n_pad, nv, p->cand.xp);
-  LAUNCH_CHECK();
+  if ((rc = pack_candidates(p, X, nv))) return rc;
   return launch_residual_batch(p, 1, out16, nullptr, p->ws.b16);
 }
 
@@ -1774,26 +1640,7 @@ int fos_residual_batch_folds(fos_problem* p, const float* X, int nv, const uint8
                              "aligned or a held id outside -1..254)");
   if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: the problem has no b of its own");
   if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: sharded problems are not served");
-  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight)
-    return residual_batch_logit(p, "fos_residual_batch_folds", X, nv, out16, fold_of_row, &hb);
-  if (!pair_dd_multi_supported(p))
-    return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: the shape has no matrix-core pair");
-  int rc = ensure_batch_workspace(p);
-  if (rc) return rc;
-  if (p->dtype == FOS_BF16)
-    hipLaunchKernelGGL(fos::xq_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
-                       (int)p->cand.n_pad, nv, (unsigned short*)p->cand.xp.get());
-  else
-    hipLaunchKernelGGL(xp_pack_kernel, dim3(grid_1d(p->cand.n_pad, 256, 256)), dim3(256), 0, p->stream, X, (int)p->n,
-                       (int)p->cand.n_pad, nv, p->cand.xp);
-  LAUNCH_CHECK();
-  if ((rc = prof_mark(p, true))) return rc;
-  int nwg = 0;
-  if ((rc = launch_batch_product_folds(p, p->A, p->b, p->m, nullptr, &nwg, fold_of_row, hb))) return rc;
-  if ((rc = prof_mark(p, false))) return rc;
-  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->cand.q_part, nwg, fos::BT_NV, out16);
-  LAUNCH_CHECK();
-  return FOS_OK;
+  return residual_batch_pair(p, "fos_residual_batch_folds", X, nv, out16, fold_of_row, &hb);
 }
 
 int fos_gemv_pair_dd_multi(fos_problem* p, const double* X, int nv, int64_t ldx, const float* B, int64_t ldb, double alpha2,

@@ -2,7 +2,7 @@
 
 K-fold cross-validation in lockstep (fos_fista_run_multi_folds, fos_residual_batch_folds) launches product 1 with a fold
 mask in its epilogue: one row per launchable cell (table, dtype, geometry, variant) with the cases that reach it.
-tests/test_kernel_menu_cv.py keeps the set of cells in step with the launch tables kF32Folds / kBf16Folds of
+tests/test_kernel_menu_cv.py keeps the set of cells in step with the fold forms of the product-1 form list of
 csrc/fos_plan.hip and checks on the CPU that every case lands on its cell; tests/test_gpu_cv.py runs every case against the
 fp64 oracle on the gathered rows.
 

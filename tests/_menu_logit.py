@@ -2,7 +2,7 @@
 
 A logistic problem (fos_problem_set_loss) launches product 1 with the logistic epilogue, with or without a fold mask: one
 row per launchable cell (table, dtype, geometry, variant) with the cases that reach it.  tests/test_kernel_menu_logit.py
-keeps the set of cells in step with the launch tables kF32Logit / kBf16Logit of csrc/fos_plan.hip and checks on the CPU that
+keeps the set of cells in step with the logistic forms of the product-1 form list of csrc/fos_plan.hip and checks on the CPU that
 every case lands on its cell; tests/test_gpu_logit.py runs every case against the fp64 reference of tests/_logit.py.
 
 table  geometry  variant        instantiation, chosen by

@@ -2,7 +2,7 @@
 
 A problem with row weights (fos_row_weights_bind) launches product 1 with the weight in its epilogue, for either loss and with
 or without a fold mask: one row per launchable cell (table, dtype, geometry, variant) with the cases that reach it.
-tests/test_kernel_menu_weighted.py keeps the set of cells in step with the launch tables kF32Weighted / kBf16Weighted of
+tests/test_kernel_menu_weighted.py keeps the set of cells in step with the weighted forms of the product-1 form list of
 csrc/fos_plan.hip and checks on the CPU that every case lands on its cell; tests/test_gpu_weighted.py runs every case against
 the fp64 reference of tests/_weighted.py.
 

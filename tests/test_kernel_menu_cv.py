@@ -1,45 +1,16 @@
-"""CPU guard: the coverage table of the fold instantiations of product 1 (tests/_menu_cv.py) names every cell of the launch
-tables kF32Folds / kBf16Folds (csrc/fos_plan.hip), every case lands on the cells it is filed under, and the launcher picks
-the tile variant the table's route restates."""
-import os
+"""CPU guard: the coverage table of the fold instantiations of product 1 (tests/_menu_cv.py) names every unweighted squared
+form with a fold mask in the form list of csrc/fos_plan.hip (tests/_menu_product1.py reads it), every case lands on the cells it
+is filed under, and the launcher picks the tile variant the table's route restates."""
 import re
 
 import pytest
 
-from tests import _menu_cv as mc, _menu_multi as mm
-from tests.test_kernel_menu import _initialiser
-from tests.test_kernel_menu_multi import PLAN, _body, _text, CU_COUNTS
-
-FOLD = {"fos::FOLD_TRAIN": "train", "fos::FOLD_HELD": "heldout", "fos::FOLD_OFF": "off"}
-
-
-def parse(plan=PLAN):
-    """The set of (table, dtype, geometry, variant) cells the two fold tables instantiate."""
-    tp = _text(plan)
-    cells = set()
-    for name, kern, dtype, skip in (("kF32Folds", "residual_batch_mfma_kernel", "f32", 1),
-                                    ("kBf16Folds", "residual_batch_mfma_bf16_kernel", "bf16", 2)):
-        found = re.findall(kern + r"\s*<([^<>]*)>", _initialiser(tp, name))
-        assert found, name
-        for args in found:
-            a = [s.strip() for s in args.split(",")]
-            assert len(a) == skip + 3, (name, a)
-            if dtype == "bf16":
-                assert int(a[1]) == mm.TILE_COLS["bf16"], a
-            assert a[skip + 1] == "false", (name, a, "the fold forms read the problem's own b")
-            cells.add(("p1f", dtype, f"RB{int(a[0])}", FOLD[a[skip + 2]] + ("-store" if a[skip] == "true" else "-resid")))
-    return cells
-
-
-def _describe(cells):
-    return "\n  ".join("/".join(c) for c in sorted(cells))
+from tests import _menu_cv as mc, _menu_multi as mm, _menu_product1 as p1
+from tests.test_kernel_menu_multi import PLAN, CU_COUNTS
 
 
 def check_coverage(plan=PLAN):
-    src, table = parse(plan), mc.cells()
-    msg = [f"{what}:\n  {_describe(c)}" for what, c in (("cells without a row in tests/_menu_cv.py", src - table),
-                                                          ("rows without a cell in the source", table - src)) if c]
-    assert not msg, "\n".join(msg)
+    p1.check_coverage("p1f", mc.cells(), "tests/_menu_cv.py", plan)
 
 
 def test_table_covers_every_instantiated_cell():
@@ -47,24 +18,12 @@ def test_table_covers_every_instantiated_cell():
     assert len(mc.ROWS) == len(mc.cells()) == 2 * 2 * 2          # dtype x RB x {train-store, heldout-resid}
 
 
-def test_fold_cells_stay_out_of_the_unmasked_tables():
-    """kF32Batch / kBf16Batch hold no fold form: tests/test_kernel_menu_multi.py parses them for the unmasked cells."""
-    tp = _text(PLAN)
-    for name in ("kF32Batch", "kBf16Batch"):
-        assert "FOLD" not in _initialiser(tp, name), name
-
-
 def test_launcher_shares_the_grid_of_the_unmasked_product():
-    """The RB route of the table (mm.rb) is launch_batch_product's: both launchers take it from batch_grid."""
-    tp = _text(PLAN)
-    grid = _body(tp, r"static\s+BatchGrid\s+batch_grid\s*\([^)]*\)\s*(?=\{)")
-    assert re.search(r"const\s+int\s+variant\s*=\s*rows_total\s*>=\s*%d\s*\*\s*\(int64_t\)\s*p->ncu\s*\?\s*1\s*:\s*0" % mm.RB2_ROWS_PER_CU, grid)
-    for fn in ("launch_batch_product", "launch_batch_product_folds"):
-        body = _body(tp, r"int\s+" + fn + r"\s*\([^)]*\)\s*(?=\{)")
-        assert re.search(r"batch_grid\s*\(\s*p\s*,\s*rows_total\s*\)", body), fn
-    body = _body(tp, r"int\s+launch_batch_product_folds\s*\([^)]*\)\s*(?=\{)")
-    assert re.search(r"kBf16Folds\s*\[\s*g\.variant\s*\]", body) and re.search(r"kF32Folds\s*\[\s*g\.variant\s*\]", body)
-    assert len(re.findall(r"rout\s*\?\s*v[qf]\.store_train\s*:\s*v[qf]\.resid_held", body)) == 2
+    """The RB route of the table (mm.rb) is batch_grid's, for every form: one launcher, and the fold form follows from rout."""
+    body = p1.launcher()
+    assert re.search(r"L\.fold_of_row\s*\?\s*\(\s*L\.rout\s*\?\s*fos::FOLD_TRAIN\s*:\s*fos::FOLD_HELD\s*\)\s*:\s*fos::FOLD_OFF", body)
+    assert len(re.findall(r"L\.fold_of_row\s*,\s*held\s*,", body)) == 2                  # ids and held block reach both launches
+    assert re.search(r"const\s+fos::FoldHeld\s+held\s*=\s*L\.held\s*\?\s*\*L\.held\s*:\s*fos::FoldHeld\{\}", body)
 
 
 @pytest.mark.parametrize("cus", CU_COUNTS)
@@ -94,13 +53,14 @@ def test_guard_names_a_deleted_instantiation(tmp_path):
     with open(PLAN) as fh:
         text = fh.read()
     for old, new, cell in (
-            ("fos::residual_batch_mfma_kernel<2, false, false, fos::FOLD_HELD>}", "nullptr}", "p1f/f32/RB2/heldout-resid"),
-            ("    {fos::residual_batch_mfma_bf16_kernel<1, 128, true, false, fos::FOLD_TRAIN>,\n", "    {nullptr,\n",
-             "p1f/bf16/RB1/train-store"),
-            ("{fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_TRAIN>,", "{fos::residual_batch_mfma_kernel<1, true, false, fos::FOLD_HELD>,",
+            ("  X(false, false, FOLD_HELD, LOSS_SQUARED, false)        \\\n", "", "p1f/f32/RB2/heldout-resid"),
+            ("  X(true, false, FOLD_TRAIN, LOSS_SQUARED, false)        \\\n", "", "p1f/bf16/RB1/train-store"),
+            ("  X(true, false, FOLD_TRAIN, LOSS_SQUARED, false)        \\\n", "  X(true, false, FOLD_HELD, LOSS_SQUARED, false)         \\\n",
              "p1f/f32/RB1/heldout-store"),
-            ("     fos::residual_batch_mfma_bf16_kernel<2, 128, false, false, fos::FOLD_HELD>},\n",
-             "     fos::residual_batch_mfma_bf16_kernel<4, 128, false, false, fos::FOLD_HELD>},\n", "p1f/bf16/RB4/heldout-resid")):
+            ("    fos::residual_batch_mfma_bf16_kernel<2, 128, S, B, fos::F, fos::L, W>}},\n",
+             "    fos::residual_batch_mfma_bf16_kernel<4, 128, S, B, fos::F, fos::L, W>}},\n", "p1f/bf16/RB4/heldout-resid"),
+            ("{fos::residual_batch_mfma_kernel<1, S, B, fos::F, fos::L, W>,", "{fos::residual_batch_mfma_kernel<2, S, B, fos::F, fos::L, W>,",
+             "p1f/f32/RB1/train-store")):
         assert text.count(old) == 1, old
         fake = tmp_path / "fos_plan.hip"
         fake.write_text(text.replace(old, new))

@@ -1,39 +1,21 @@
 """CPU guard: the coverage table of the multi-vector kernels (tests/_menu_multi.py) names every instantiation the
 dispatchers can launch, and every case lands on the cell it is filed under.
 
-Parsed from csrc/fos_plan.hip and csrc/fos_fista.hip: the four arrays of find_multi, kF32Batch, kBf16Batch, kPairDdMulti
-(and the two product-2 launches of run_pair_dd_multi), the switch of launch_cluster_pass, the ACC pairs of the product-2
-launches of run_multi_mfma, and the thresholds the table's route functions restate (the 4096 / 8192 split, 128 x CUs and
-256 x CUs rows, the cluster's strip width and row count)."""
+Parsed from csrc/fos_plan.hip and csrc/fos_fista.hip: the four arrays of find_multi, the unmasked squared forms of the
+product-1 table (tests/_menu_product1.py), kPairDdMulti (and the two product-2 launches of run_pair_dd_multi), the switch of
+launch_cluster_pass, the ACC pairs of the product-2 launches of launch_gram_panel, and the thresholds the table's route
+functions restate (the 4096 / 8192 split, 128 x CUs and 256 x CUs rows, the cluster's strip width and row count)."""
 import os
 import re
 
 import numpy as np
 import pytest
 
-from tests import _data, _menu, _menu_multi as mm
+from tests import _data, _menu, _menu_cv, _menu_logit, _menu_multi as mm, _menu_product1 as p1, _menu_weighted
+from tests._menu_product1 import CSRC, FISTA, PLAN, _body, _text
 from tests.test_kernel_menu import _initialiser
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fastoptsolver_amd", "csrc")
-PLAN, FISTA = os.path.join(CSRC, "fos_plan.hip"), os.path.join(CSRC, "fos_fista.hip")
 CU_COUNTS = (256, 64, 128, 304)          # 304: (CUs / 8) % cs != 0 - no cluster form on such a device
-
-
-def _text(path):
-    with open(path) as fh:
-        return re.sub(r"//[^\n]*", "", fh.read())
-
-
-def _body(text, start):
-    """The brace-balanced body that follows the first match of `start` (which ends before its opening brace)."""
-    m = re.search(start, text)
-    assert m is not None, start
-    i = text.index("{", m.end())
-    depth, j = 1, i + 1
-    while depth:
-        depth += {"{": 1, "}": -1}.get(text[j], 0)
-        j += 1
-    return text[i + 1:j - 1]
 
 
 def _flag(args, i):
@@ -52,16 +34,9 @@ def parse(plan=PLAN, fista=FISTA):
         for args in re.findall(r"multi_launch\s*<([^<>]*)>", init):
             a = [s.strip() for s in args.split(",")]
             cells.add(("valu", "f32", f"{int(a[0])}x{int(a[1])}", f"nvec{int(a[2])}" + ("-B" if _flag(a, 3) else "")))
-    # product 1: kF32Batch <RB, STORE, BBLOCK>, kBf16Batch <RB, 128, STORE, BBLOCK>
-    for name, kern, dtype, skip in (("kF32Batch", "residual_batch_mfma_kernel", "f32", 1),
-                                    ("kBf16Batch", "residual_batch_mfma_bf16_kernel", "bf16", 2)):
-        for args in re.findall(kern + r"\s*<([^<>]*)>", _initialiser(tp, name)):
-            a = [s.strip() for s in args.split(",")]
-            if dtype == "bf16":
-                assert int(a[1]) == mm.TILE_COLS["bf16"], a
-            cells.add(("p1", dtype, f"RB{int(a[0])}", ("store" if _flag(a, skip) else "resid") + ("-B" if _flag(a, skip + 1) else "")))
-    # product 2 of the lockstep run
-    body = _body(tf, r"static\s+int\s+run_multi_mfma\s*\([^)]*\)\s*(?=\{)")
+    cells |= p1.cells(plan, "p1")
+    # product 2 of the lockstep run and of fos_gram_apply
+    body = _body(tf, r"static\s+int\s+launch_gram_panel\s*\([^)]*\)\s*(?=\{)")
     for acc in re.findall(r"FOS_GRAM\s*\(\s*float\s*,\s*(true|false)\s*\)", body):
         cells.add(("p2", "f32", "gram", "acc" if acc == "true" else "first"))
     for acc in re.findall(r"gram_batch_mfma_bf16_kernel\s*<\s*(true|false)\s*>", body):
@@ -73,11 +48,11 @@ def parse(plan=PLAN, fista=FISTA):
         cells.add(("cluster", "f32", f"cs{int(cs)}", "pass"))
     # the fp64 pair: one entry per storage type, each with product 1 and both forms of product 2
     run = _body(tp, r"int\s+run_pair_dd_multi\s*\([^)]*\)\s*(?=\{)")
-    p1 = re.findall(r"residual_dd_mfma_kernel\s*<\s*T\s*>", run)
+    dd_p1 = re.findall(r"residual_dd_mfma_kernel\s*<\s*T\s*>", run)
     accs = re.findall(r"gram_dd_mfma_kernel\s*<\s*T\s*,\s*(true|false)\s*>", run)
     for t in re.findall(r"run_pair_dd_multi\s*<\s*([\w:]+)\s*>", _initialiser(tp, "kPairDdMulti")):
         dtype = {"float": "f32", "fos::bf16_t": "bf16"}[t]
-        for _ in p1:
+        for _ in dd_p1:
             cells.add(("dd", dtype, "residual", "p1"))
         for acc in accs:
             cells.add(("dd", dtype, "gram", "acc" if acc == "true" else "first"))
@@ -98,6 +73,14 @@ def check_coverage(plan=PLAN, fista=FISTA):
 def test_table_covers_every_instantiated_cell():
     check_coverage()
     assert len(mm.ROWS) == len(mm.cells()) == 12 + 8 + 8 + 4 + 3 + 2 + 4
+
+
+def test_the_four_tables_share_out_the_product_1_cells():
+    """The p1 rows here and the tables of the fold, logistic and weighted forms are together the 72 kernels of the source."""
+    groups = {"p1": {c for c in mm.cells() if c[0] == "p1"}, "p1f": _menu_cv.cells(), "p1l": _menu_logit.cells(),
+              "p1w": _menu_weighted.cells()}
+    assert [len(groups[t]) for t in ("p1", "p1f", "p1l", "p1w")] == [16, 8, 16, 32]
+    p1.check_partition(groups)
 
 
 def test_thresholds_match_the_source():
@@ -205,8 +188,11 @@ def test_guard_names_a_deleted_instantiation(tmp_path):
         text = fh.read()
     for old, new, cell in (
             ("multi_launch<512, 4, 3>, ", "", "valu/f32/512x4/nvec3"),
-            ("     fos::residual_batch_mfma_bf16_kernel<2, 128, false, true>, fos::residual_batch_mfma_bf16_kernel<2, 128, true, true>},",
-             "     nullptr, nullptr},", "p1/bf16/RB2/resid-B"),
+            ("  X(false, true, FOLD_OFF, LOSS_SQUARED, false)          \\\n", "", "p1/bf16/RB2/resid-B"),
+            ("  X(true, true, FOLD_OFF, LOSS_SQUARED, false)           \\\n", "  X(true, true, FOLD_TRAIN, LOSS_SQUARED, false)         \\\n",
+             "p1/f32/RB1/store-B"),
+            ("fos::residual_batch_mfma_kernel<2, S, B, fos::F, fos::L, W>}", "fos::residual_batch_mfma_kernel<4, S, B, fos::F, fos::L, W>}",
+             "p1/f32/RB4/resid"),
             ("    case 16: return launch_cluster_pass_cs<16>(p);\n", "", "cluster/f32/cs16/pass"),
             ("    {FOS_BF16, run_pair_dd_multi<fos::bf16_t>},\n", "", "dd/bf16/gram/acc"),
             ("multi_launch<512, 4, 4, true>}", "multi_launch<512, 4, 4, true>, multi_launch<1024, 4, 4, true>}", "valu/f32/1024x4/nvec4-B")):
@@ -218,7 +204,7 @@ def test_guard_names_a_deleted_instantiation(tmp_path):
         assert cell in str(err.value), (cell, str(err.value))
     with open(FISTA) as fh:
         text = fh.read()
-    old = "if (panel) FOS_GRAM(float, true); else FOS_GRAM(float, false);"
+    old = "if (accumulate) FOS_GRAM(float, true); else FOS_GRAM(float, false);"
     assert text.count(old) == 1
     fake = tmp_path / "fos_fista.hip"
     fake.write_text(text.replace(old, "FOS_GRAM(float, false);"))
