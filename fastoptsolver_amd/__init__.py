@@ -1,6 +1,6 @@
 """fastoptsolver_amd — MI355X-native inner loops (FISTA / ISTA / FISTA-Δ / L-BFGS) behind the call signatures
 of ElBaldo1/FastOptSolver.  Hand-written HIP for gfx950 through a C ABI (include/fos.h); no CPU fallback."""
-from ._core import Problem, prepare, prepare_weighted                               # noqa: F401
+from ._core import Problem, prepare, prepare_weighted, prepare_penalized                               # noqa: F401
 from ._lib import FosError                                            # noqa: F401
 from .iterative_solvers import (CVResult, estimate_lipschitz, fista, fista_cv, fista_delta, fista_path,  # noqa: F401
                                 get_metrics, ista, reset_metrics)
@@ -12,4 +12,4 @@ from .prox_operators import prox_elastic_net, prox_l1                 # noqa: F4
 
 __all__ = ["fista", "fista_delta", "fista_path", "fista_cv", "CVResult", "ista", "estimate_lipschitz", "reset_metrics", "get_metrics", "LBFGSSolver",
            "compute_objective", "prox_l1", "prox_elastic_net", "LeastSquares", "L1Prox", "ElasticNetProx",
-           "prepare", "prepare_weighted", "Problem", "FosError", "logistic_path", "logistic_cv", "logistic_objective", "LogisticCVResult"]
+           "prepare", "prepare_weighted", "prepare_penalized", "Problem", "FosError", "logistic_path", "logistic_cv", "logistic_objective", "LogisticCVResult"]

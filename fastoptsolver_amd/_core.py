@@ -1,6 +1,7 @@
 """Device-side plumbing: tensors in, C-ABI handles out.  torch is used for device memory, streams and
 events only; every arithmetic operation on the hot path is a HIP kernel behind include/fos.h."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -88,6 +89,31 @@ def checked_weights(w, m):
     return t
 
 
+def checked_coord(penalty_factor, lower, upper, n):
+    """Per-coordinate penalty factors and box bounds as float64 ndarrays of length n (None stays None; scalars broadcast):
+    factors finite and >= 0, bounds not NaN with lower <= 0 <= upper (x0 = 0 stays feasible; -inf / +inf mean "no bound") -
+    ValueError otherwise.  Checked on the host, before any device work."""
+    def vec(v, name):
+        if v is None:
+            return None
+        a = np.asarray(v.detach().cpu().numpy() if is_tensor(v) else v, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(n, float(a))
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError(f"{name} must be a scalar or have n = {n} entries, got shape {a.shape}")
+        if np.isnan(a).any():
+            raise ValueError(f"{name} must not hold NaN")
+        return a
+    pf, lo, hi = vec(penalty_factor, "penalty_factor"), vec(lower, "lower"), vec(upper, "upper")
+    if pf is not None and not (np.isfinite(pf) & (pf >= 0)).all():
+        raise ValueError("penalty_factor must be finite and >= 0")
+    if lo is not None and (lo > 0).any():
+        raise ValueError("lower must be <= 0 (the start x0 = 0 has to be feasible)")
+    if hi is not None and (hi < 0).any():
+        raise ValueError("upper must be >= 0 (the start x0 = 0 has to be feasible)")
+    return pf, lo, hi
+
+
 class Like:
     """What the caller handed in (so results come back as the same kind) without keeping the object alive."""
 
@@ -130,9 +156,26 @@ class Problem:
         device columns is served; more raise ValueError.
         sample_weight: m per-row weights w_i >= 0 of the data term (`prepare_weighted`; fos_row_weights_bind).  A weighted problem
         runs on the matrix-core pair alone as a logistic one does and is padded by the same rules."""
+        self._setup(A, b, dtype, pad, loss, sample_weight)
+
+    @classmethod
+    def penalized(cls, A, b, penalty_factor=None, lower=None, upper=None, dtype=None, loss="squared", sample_weight=None):
+        """The handle of a problem with per-coordinate penalty factors and box bounds (`prepare_penalized`): __init__'s
+        parameter list is part of the interface and stays as it is, so this is the constructor that takes them."""
+        prob = cls.__new__(cls)
+        prob._setup(A, b, dtype, None, loss, sample_weight, penalty_factor, lower, upper)
+        return prob
+
+    def _setup(self, A, b, dtype, pad, loss, sample_weight, penalty_factor=None, lower=None, upper=None):
+        """__init__, and with penalty_factor / lower / upper (`prepare_penalized`; `set_penalty`, fos_coord_bind) the handle of a
+        problem with per-coordinate penalty factors and box bounds: it runs on the matrix-core pair alone too and is padded by
+        the rules of a logistic problem."""
         if loss not in LOSSES:
             raise ValueError(f"loss: one of {sorted(LOSSES)} expected, got {loss!r}")
-        pair_only = loss == "logistic" or sample_weight is not None      # served by the matrix-core pair alone
+        coord = any(v is not None for v in (penalty_factor, lower, upper))
+        pair_only = loss == "logistic" or sample_weight is not None or coord      # served by the matrix-core pair alone
+        if coord:                                                        # before any device work
+            coord = checked_coord(penalty_factor, lower, upper, int(A.shape[1] if hasattr(A, "shape") else np.shape(A)[1]))
         if sample_weight is not None:                                    # before any device work
             sample_weight = checked_weights(sample_weight, int(A.shape[0] if hasattr(A, "shape") else np.shape(A)[0]))
         require_gpu()
@@ -177,9 +220,14 @@ class Problem:
         self.dtype = "bf16" if want_bf16 else "f32"
         self.loss = loss
         if pair_only and n_dev > LOGIT_MAX_N:
-            raise ValueError(f"a logistic or weighted problem is limited to {LOGIT_MAX_N} device columns, got {n_dev}")
+            raise ValueError(f"a logistic or weighted problem, or one with penalty factors or bounds, is limited to {LOGIT_MAX_N} device columns, "
+                             f"got {n_dev}")
         self.sample_weight = None
+        self._coord = (None, None, None)
+        self.penalty_max = 1.0
         self._bind(b, lib)
+        if coord:
+            self._set_checked(*coord)
         if sample_weight is not None:
             # zero-padded to a multiple of 4 entries: product 1 fetches the weights of 4 rows with one 16-byte load
             buf = torch.zeros((m + 3) // 4 * 4, dtype=torch.float32, device=self.device)
@@ -193,7 +241,10 @@ class Problem:
         sib.like = self.like
         sib.A, sib.m, sib.n, sib.n_dev, sib.lda = self.A, self.m, self.n, self.n_dev, self.lda
         sib.device, sib.dtype, sib.loss, sib.sample_weight = self.device, self.dtype, self.loss, None
+        sib._coord, sib.penalty_max = (None, None, None), 1.0
         sib._bind(b, self.lib)
+        if self.has_coord:                          # the columns are the same columns: the device vectors are shared
+            sib._bind_coord(self._coord, self.penalty_max)
         if self.sample_weight is not None:          # the rows are the same rows: a sibling of a weighted handle is weighted
             sib.set_sample_weight(self.sample_weight)
         return sib
@@ -229,6 +280,45 @@ class Problem:
         with self.ctx():
             _lib.check(self.lib.fos_row_weights_bind(ptr(w), self.h), "fos_row_weights_bind")
         self.sample_weight = w
+
+    def set_penalty(self, penalty_factor=None, lower=None, upper=None):
+        """Per-coordinate penalty factors p_j >= 0 and box bounds lower_j <= 0 <= upper_j (fos_coord_bind): the penalties become
+        alpha1 sum_j p_j |x_j| + 0.5 alpha2 sum_j p_j x_j^2 and the solution is held to lower_j <= x_j <= upper_j.  Each is None
+        (factor 1, -inf, +inf), a scalar (``lower=0.0``: the non-negative lasso) or n values; factors are used as given, p_j = 0
+        is an unpenalised coordinate (an intercept column).  All None detaches.  Checked on the host before any device work
+        (ValueError: a wrong length, a non-finite or negative factor, NaN, lower > 0 or upper < 0).  The handle then runs on the
+        matrix-core lockstep alone (``fista_path`` / ``fista_cv`` / ``logistic_path`` / ``logistic_cv``) with the step
+        t_init_factor / (L + alpha2 * penalty_max); every other solver refuses it."""
+        self._set_checked(*checked_coord(penalty_factor, lower, upper, self.n))
+
+    def _set_checked(self, pf, lo, hi):
+        """set_penalty with what checked_coord returned."""
+        n4 = (self.n_dev + 3) // 4 * 4              # the update fetches the values of 4 coordinates with one 16-byte load
+
+        def dev(v, fill):
+            if v is None:
+                return None
+            buf = torch.full((n4,), fill, dtype=torch.float32, device=self.device)
+            buf[: self.n] = torch.from_numpy(v).to(device=self.device, dtype=torch.float32)
+            return buf
+        self._bind_coord((dev(pf, 1.0), dev(lo, -math.inf), dev(hi, math.inf)), 1.0 if pf is None else float(pf.max()))
+
+    def _bind_coord(self, bufs, penalty_max):
+        with self.ctx():
+            _lib.check(self.lib.fos_coord_bind(ptr(bufs[0]), ptr(bufs[1]), ptr(bufs[2]), self.h), "fos_coord_bind")
+        self._coord = tuple(bufs)                   # the device vectors live as long as the handle borrows them
+        self.penalty_max = float(penalty_max) if bufs[0] is not None else 1.0
+
+    @property
+    def has_coord(self):
+        return any(v is not None for v in self._coord)
+
+    def _coord_view(self, i):
+        return None if self._coord[i] is None else self._coord[i][: self.n]
+
+    penalty_factor = property(lambda self: self._coord_view(0), doc="the bound fp32 device factors (n), or None")
+    lower = property(lambda self: self._coord_view(1), doc="the bound fp32 device lower bounds (n), or None")
+    upper = property(lambda self: self._coord_view(2), doc="the bound fp32 device upper bounds (n), or None")
 
     def __del__(self):
         h = getattr(self, "h", None)
@@ -437,6 +527,30 @@ def prepare_weighted(A, b, sample_weight, dtype=None, *, loss="squared"):
     if b is None:
         raise ValueError("a weighted problem needs b")
     return Problem(A, b, dtype, None, loss, sample_weight=sample_weight)
+
+
+def prepare_penalized(A, b, penalty_factor=None, lower=None, upper=None, dtype=None, *, loss="squared", sample_weight=None):
+    """``prepare`` with per-coordinate penalty factors p_j >= 0 and box bounds lower_j <= 0 <= upper_j (glmnet's penalty.factor
+    and lower.limits / upper.limits, sklearn's positive=True): the objective is
+
+        data term + alpha1 sum_j p_j |x_j| + 0.5 alpha2 sum_j p_j x_j^2    subject to    lower_j <= x_j <= upper_j
+
+    with the squared or (``loss="logistic"``) the logistic data term, weighted per row with ``sample_weight``.  Each of the
+    three is None (factor 1, -inf, +inf), a scalar (``lower=0.0``: the non-negative lasso) or n values; the factor scales both
+    penalties and is used as given (no rescaling), p_j = 0 is an unpenalised coordinate - an intercept is a constant column
+    with factor 0.  The data belongs to the handle (``.penalty_factor`` / ``.lower`` / ``.upper``, fp32 device vectors;
+    ``.penalty_max``; ``Problem.set_penalty`` rebinds or detaches): pass it as ``A`` (``b`` None) to ``fista_path`` /
+    ``fista_cv`` (squared loss) or ``logistic_path`` / ``logistic_cv`` / ``logistic_objective``, which then run on the
+    matrix-core lockstep alone with the step t_init_factor / (L + alpha2 max_j p_j); every other solver refuses the handle.
+    Padded as a logistic problem is (at most 16384 device columns).  ValueError, before any device work, for a wrong length,
+    a non-finite or negative factor, NaN, lower > 0 or upper < 0."""
+    if isinstance(A, Problem):
+        raise ValueError("prepare_penalized binds an array or tensor; on a Problem use its set_penalty")
+    if b is None:
+        raise ValueError("a problem with penalty factors or bounds needs b")
+    if penalty_factor is None and lower is None and upper is None:
+        raise ValueError("penalty_factor, lower or upper is needed")
+    return Problem.penalized(A, b, penalty_factor, lower, upper, dtype, loss, sample_weight)
 
 
 def as_problem(A, b, dtype=None):

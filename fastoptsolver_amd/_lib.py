@@ -65,6 +65,8 @@ SIGNATURES = {
     "fos_problem_get_loss": (_i32, [_vp, C.POINTER(_i32)]),
     "fos_row_weights_bind": (_i32, [_vp, _vp]),
     "fos_row_weights_get": (_i32, [C.POINTER(_vp), _vp]),
+    "fos_coord_bind": (_i32, [_vp, _vp, _vp, _vp]),
+    "fos_coord_get": (_i32, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "fos_gram_apply": (_i32, [_vp, _i32, _vp, _vp]),
     "fos_problem_replan": (_i32, [_vp, C.c_uint]),
     "fos_comm_unique_id": (_i32, [C.c_char_p]),

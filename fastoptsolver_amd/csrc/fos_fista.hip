@@ -684,6 +684,9 @@ static fos::MultiUpdate multi_update(fos_fista* const* fs, int nv, bool controll
 // mask; the two-product form as well, and everything after product 1 is the same.
 // A problem with row weights (fos_row_weights_bind): product 1 is the weighted form of its loss, R = w (A_panel Y - b) or
 // w (sigma(A_panel Y) - b); the two-product form, and everything after product 1 is the same.
+// A problem with coordinate data (fos_coord_bind: penalty factors and box bounds): the two-product form as well; both products
+// are the launches they were and the two update launch sites take the coordinate kernels (reduce_update.hpp, COORD), which
+// scale the penalties per coordinate and clamp to the box.  Composes with the fold mask, the logistic loss and row weights.
 
 // Row splits of product 2 in the two-product form: the planned ones, or - on a problem planned for the cluster form, whose slab
 // count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated.
@@ -737,7 +740,9 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
   // count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated
   const bool logit = p->loss == FOS_LOSS_LOGISTIC;
   const bool weighted = p->row_weight != nullptr;
-  const bool two_products = b16 || fold_of_row || logit || weighted;
+  const bool coord = has_coord(p);   // fos_coord_bind: the two update launches below take the coordinate kernels
+  const fos::CoordData cd{p->coord_factor, p->coord_lo, p->coord_hi};
+  const bool two_products = b16 || fold_of_row || logit || weighted || coord;
   bool use_cluster = p->multi.cp_cs && !two_products;
   int g_splits = p->multi.gram_splits;
   if (two_products && (rc = two_product_splits(p, &g_splits))) return rc;
@@ -803,12 +808,23 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
     if (!cols && (rc = reduce_across(p, p->multi.slabs16, (size_t)g_splits * fos::BT_NV * p->n, false))) return rc;
     if (controlled || same_family) {             // one launch updates all state machines
       const fos::MultiUpdate mu = multi_update(fs, nv, controlled);
+      if (coord)
+        hipLaunchKernelGGL(fos::fista_update_multi_coord_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->multi.slabs16,
+                           g_splits, (int)p->n, mu, fs[0]->prm, p->cand.xp, y_mode, controlled ? 0 : 1, cd);
+      else
       hipLaunchKernelGGL(fos::fista_update_multi_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->multi.slabs16, g_splits,
                          (int)p->n, mu, fs[0]->prm, p->cand.xp, y_mode, controlled ? 0 : 1);
       LAUNCH_CHECK();
     } else {
       for (int v = 0; v < nv; ++v) {
         const PlainStep s = advance_plain(fs[v], false);
+        if (coord) {
+          hipLaunchKernelGGL(fos::fista_update_coord_kernel, dim3(fs[v]->nupd), dim3(256), 0, p->stream,
+                             p->multi.slabs16 + (size_t)v * p->n, g_splits, (int)p->n, fs[v]->x_cur, fs[v]->x_prev, fs[v]->scal,
+                             fs[v]->prm, s.part, 1, s.beta, p->cand.xp, s.beta_next, (int64_t)fos::BT_NV * p->n, y_mode, v, cd);
+          LAUNCH_CHECK();
+          continue;
+        }
         if ((rc = launch_update_from_slabs(fs[v], s.part, 1, s.beta, nullptr, p->cand.xp, s.beta_next, p->multi.slabs16 + (size_t)v * p->n,
                                            (int64_t)fos::BT_NV * p->n, g_splits, y_mode, v)))
           return rc;
@@ -861,13 +877,13 @@ static int lockstep_forms(fos_fista* const* fs, int nv, const char* fn, bool* al
   return FOS_OK;
 }
 
-// A logistic problem or one with row weights: always the two matrix-core products, for any number of state machines (one
+// A logistic problem, one with row weights or one with coordinate data: always the two matrix-core products, for any number of state machines (one
 // included - there is no single-vector logistic or weighted pass), never the cluster form or the VALU multi-vector pass.
 static int run_multi_logit(fos_fista* const* fs, int nv, int iters, const uint8_t* fold_of_row, const fos::FoldHeld* held,
                            const char* fn) {
   fos_problem* p = fs[0]->p;
   if (!p->b || p->comm || p->col_sharded || !pair_dd_multi_supported(p))
-    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the logistic loss and row weights need b, an unsharded problem and the "
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the logistic loss, row weights and penalty factors / bounds need b, an unsharded problem and the "
                                                          "matrix-core pair");
   bool all_plain, same_family;
   if (int rc = lockstep_forms(fs, nv, fn, &all_plain, &same_family)) return rc;
@@ -878,7 +894,8 @@ static int run_multi_logit(fos_fista* const* fs, int nv, int iters, const uint8_
 static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, int64_t ldb) {
   fos_problem* p = fs[0]->p;
   const bool rhs = B != nullptr;
-  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight) return run_multi_logit(fs, nv, iters, nullptr, nullptr, "fos_fista_run_multi");
+  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight || has_coord(p))
+    return run_multi_logit(fs, nv, iters, nullptr, nullptr, "fos_fista_run_multi");
   if (rhs && (p->comm || p->col_sharded))
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs: row- or column-sharded problems are not served");
   if (nv == 1) {
@@ -985,7 +1002,7 @@ int fos_fista_run_multi_folds(fos_fista* const* fs, int nv, int iters, const uin
   for (int v = 0; v < nv; ++v)
     if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi_folds: handles must share one problem");
   fos_problem* p = fs[0]->p;
-  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight)
+  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight || has_coord(p))
     return run_multi_logit(fs, nv, iters, fold_of_row, &hb, "fos_fista_run_multi_folds");
   if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the problem has no b of its own");
   if (p->comm || p->col_sharded)

@@ -270,6 +270,10 @@ struct fos_problem {
   int dtype = FOS_F32;
   int loss = FOS_LOSS_SQUARED;       // fos_problem_set_loss: what b means to the matrix-core lockstep (no buffer depends on it)
   const float* row_weight = nullptr; // fos_row_weights_bind: the caller's m per-row weights of the data term (borrowed; nullptr: none)
+  // fos_coord_bind: per-coordinate penalty factors and box bounds of the lockstep's update (borrowed; nullptr: 1, -inf, +inf)
+  const float* coord_factor = nullptr;
+  const float* coord_lo = nullptr;
+  const float* coord_hi = nullptr;
   hipStream_t stream = nullptr;
   int ncu = 256;
   // inputs of the plan groups besides the shape (set by the entry point named; see fosapi::invalidate)
@@ -405,6 +409,10 @@ int launch_batch_product(fos_problem* p, const BatchLaunch& L, int* nwg_out);
 // The one guard of the entry points that form an unweighted squared-loss residual, gradient or objective: refuses a logistic
 // problem and a problem with row weights (FOS_ERR_UNSUPPORTED) before any launch or change of handle state.
 int need_squared(const fos_problem* p, const char* fn);
+// Coordinate data (fos_coord_bind) is served by the update of the two-product lockstep alone: has_coord says whether any of
+// the three vectors is bound, coord_refusal is need_squared's third refusal (FOS_OK on a problem without coordinate data).
+inline bool has_coord(const fos_problem* p) { return p->coord_factor || p->coord_lo || p->coord_hi; }
+int coord_refusal(const fos_problem* p, const char* fn);
 // q[j] = ||A Xp_j - use_b*b||^2 -> out16 (device); Xp already in p->xp.  b16 (unsharded only): subtract its column j instead
 int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* stopped = nullptr, const float* b16 = nullptr);
 int launch_cluster_pass(fos_problem* p);

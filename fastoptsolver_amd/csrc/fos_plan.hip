@@ -681,6 +681,15 @@ int launch_batch_product(fos_problem* p, const BatchLaunch& L, int* nwg_out) {
   return FOS_OK;
 }
 
+// need_squared's refusal of a problem with coordinate data: only the update of the two-product lockstep applies the factors
+// and the bounds, so no other form may answer for such a problem.
+int coord_refusal(const fos_problem* p, const char* fn) {
+  if (p && has_coord(p))
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": not served on a problem with penalty factors or bounds (fos_coord_bind); "
+                                     "with the squared or the logistic loss they run through fos_fista_run_multi / _run_multi_folds");
+  return FOS_OK;
+}
+
 int need_squared(const fos_problem* p, const char* fn) {
   if (p && p->row_weight != nullptr)
     return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": not served on a problem with row weights (fos_row_weights_bind); the "
@@ -689,7 +698,7 @@ int need_squared(const fos_problem* p, const char* fn) {
   if (p && p->loss != FOS_LOSS_SQUARED)
     return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": not served on a logistic problem (fos_problem_set_loss); the logistic "
                                      "loss runs through fos_fista_run_multi / _run_multi_folds and fos_residual_batch / _folds");
-  return FOS_OK;
+  return coord_refusal(p, fn);
 }
 
 bool fold_held_block(const int32_t* held, int nv, fos::FoldHeld* out) {
@@ -1234,6 +1243,31 @@ int fos_row_weights_bind(const float* w, fos_problem* p) {
 int fos_row_weights_get(const float** w_out, const fos_problem* p) {
   if (!p || !w_out) return fail(FOS_ERR_ARG, "fos_row_weights_get: null");
   *w_out = p->row_weight;
+  return FOS_OK;
+}
+
+int fos_coord_bind(const float* penalty_factor, const float* lower, const float* upper, fos_problem* p) {
+  if (!p) return fail(FOS_ERR_ARG, "fos_coord_bind: null problem");
+  if ((((uintptr_t)penalty_factor | (uintptr_t)lower | (uintptr_t)upper) & 15) != 0)
+    return fail(FOS_ERR_ARG, "fos_coord_bind: a vector is not 16-byte aligned");
+  if (penalty_factor || lower || upper) {
+    if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_coord_bind: a problem with coordinate data needs b");
+    if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_coord_bind: sharded problems are not served");
+    if (!pair_dd_multi_supported(p))
+      return fail(FOS_ERR_UNSUPPORTED, "fos_coord_bind: penalty factors and bounds run on the matrix-core pair (aligned streaming "
+                                       "layout, 65..16384 columns)");
+  }
+  p->coord_factor = penalty_factor;  // no buffer depends on the coordinate data: nothing to invalidate
+  p->coord_lo = lower;
+  p->coord_hi = upper;
+  return FOS_OK;
+}
+
+int fos_coord_get(const float** penalty_factor, const float** lower, const float** upper, const fos_problem* p) {
+  if (!p || !penalty_factor || !lower || !upper) return fail(FOS_ERR_ARG, "fos_coord_get: null");
+  *penalty_factor = p->coord_factor;
+  *lower = p->coord_lo;
+  *upper = p->coord_hi;
   return FOS_OK;
 }
 

@@ -265,7 +265,21 @@ static __global__ __launch_bounds__(SRD_THREADS) void slab_reduce_dd_kernel(cons
 // otherwise take the (all-reduced) gradient from gbuf.  Writes x_prev <- x_k, x_k <- x_next in place and
 // per-workgroup partial sums  part[wg] = {sum d^2, sum g_full^2, sum |x_next|, sum x_next^2}.
 // ---------------------------------------------------------------------------------------------------------
-template <bool FROM_SLABS, bool VEC>
+// COORD (fos_coord_bind): per-coordinate penalty factors p_j >= 0 and box bounds lo_j <= 0 <= hi_j.  Both penalties are
+// scaled by p_j and the prox is followed by the clamp to [lo_j, hi_j] - the exact 1-D prox of penalty plus box (the penalty
+// is convex with its minimum at 0, which the box contains).  An owned quad fetches its factors and bounds with one 16-byte
+// load each (16-byte aligned, readable up to n rounded up to 4; a null pointer stands for 1, -inf, +inf) and widens them to
+// fp64.  alpha2 * p_j is formed first: p_j = 1 gives bitwise the products of the plain form.
+struct CoordData {
+  const float* factor;
+  const float* lo;
+  const float* hi;
+};
+
+// element e of a quad by selects: a register array indexed by the loop counter would live in scratch
+__device__ inline float quad_lane(const f32x4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+
+template <bool FROM_SLABS, bool VEC, bool COORD = false>
 __device__ inline void fista_update_body(const float* __restrict__ slabs, int nslabs,
                                                           GradSrc gsrc, int n,
                                                           double* __restrict__ x_cur, double* __restrict__ x_prev,
@@ -273,7 +287,9 @@ __device__ inline void fista_update_body(const float* __restrict__ slabs, int ns
                                                           double* __restrict__ part, int host_beta, double beta_val,
                                                           double* __restrict__ x_hist,
                                                           float* __restrict__ y_next, double beta_next,
-                                                          int64_t slab_stride, int y_mode, int y_slot) {
+                                                          int64_t slab_stride, int y_mode, int y_slot,
+                                                          CoordData cd = CoordData{nullptr, nullptr, nullptr}) {
+  static_assert(!COORD || VEC, "the coordinate form owns whole quads");
   if (scal->stopped != 0) return;
   __shared__ f32x4 lds[RG][RQ];
   __shared__ double dl[4 * 4];
@@ -304,14 +320,34 @@ __device__ inline void fista_update_body(const float* __restrict__ slabs, int ns
   const double tau = prm.tau_from_state ? scal->tau : prm.tau;
   const double thr = tau * prm.alpha1;
   const double shrink = 1.0 / (1.0 + tau * prm.alpha2);
+  f32x4 pf4 = {1.f, 1.f, 1.f, 1.f}, lo4 = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, hi4 = {INFINITY, INFINITY, INFINITY, INFINITY};
+  if constexpr (COORD) {
+    if (cnt > 0) {                                     // the quad's 12 floats: L2-resident vectors of at most 64 KiB each
+      if (cd.factor != nullptr) pf4 = *reinterpret_cast<const f32x4*>(cd.factor + col);
+      if (cd.lo != nullptr) lo4 = *reinterpret_cast<const f32x4*>(cd.lo + col);
+      if (cd.hi != nullptr) hi4 = *reinterpret_cast<const f32x4*>(cd.hi + col);
+    }
+  }
   for (int e = 0; e < cnt; ++e) {
     const double xc = x_cur[col + e], xp = x_prev[col + e];
     const double y = form_y(xc, xp, beta);
     double gf = g[e];
-    if (prm.prox_kind == PROX_L1 && prm.alpha2 > 0.0) gf += prm.alpha2 * y;
-    const double v = y - tau * gf;
-    double xn = prm.alpha1 > 0.0 ? soft_threshold(v, thr) : v;
-    if (prm.prox_kind == PROX_ENET) xn *= shrink;
+    double xn;
+    if constexpr (COORD) {
+      const double pe = (double)quad_lane(pf4, e), lo = (double)quad_lane(lo4, e), hi = (double)quad_lane(hi4, e);
+      const double a2p = prm.alpha2 * pe;
+      if (prm.prox_kind == PROX_L1 && prm.alpha2 > 0.0) gf += a2p * y;
+      const double v = y - tau * gf;
+      xn = prm.alpha1 > 0.0 ? soft_threshold(v, thr * pe) : v;
+      if (prm.prox_kind == PROX_ENET) xn *= 1.0 / (1.0 + tau * a2p);
+      xn = xn < lo ? lo : xn;                          // comparisons, not fmin / fmax: a NaN stays one
+      xn = xn > hi ? hi : xn;
+    } else {
+      if (prm.prox_kind == PROX_L1 && prm.alpha2 > 0.0) gf += prm.alpha2 * y;
+      const double v = y - tau * gf;
+      xn = prm.alpha1 > 0.0 ? soft_threshold(v, thr) : v;
+      if (prm.prox_kind == PROX_ENET) xn *= shrink;
+    }
     const double d = xn - xc;
     acc[0] += d * d;
     acc[1] += gf * gf;
@@ -360,6 +396,18 @@ __global__ __launch_bounds__(256) void fista_update_kernel(const float* __restri
                                      y_next, beta_next, slab_stride, y_mode, y_slot);
 }
 
+// The per-handle update of the two-product lockstep on a problem with coordinate data (fos_coord_bind): the slab form with
+// float4 epilogues, y_{k+1} into the handle's slot of the candidate block.
+static __global__ __launch_bounds__(256) void fista_update_coord_kernel(const float* __restrict__ slabs, int nslabs, int n,
+                                                                        double* __restrict__ x_cur, double* __restrict__ x_prev,
+                                                                        const FistaScalars* __restrict__ scal, FistaParams prm,
+                                                                        double* __restrict__ part, int host_beta, double beta_val,
+                                                                        float* __restrict__ y_next, double beta_next,
+                                                                        int64_t slab_stride, int y_mode, int y_slot, CoordData cd) {
+  fista_update_body<true, true, true>(slabs, nslabs, GradSrc{nullptr, nullptr}, n, x_cur, x_prev, scal, prm, part, host_beta,
+                                      beta_val, nullptr, y_next, beta_next, slab_stride, y_mode, y_slot, cd);
+}
+
 // The updates of up to 16 lockstep state machines in ONE launch (multi-lambda pass, gram_batch.hpp): blockIdx.y selects
 // the state machine; its slab set is slabs + y*n with slab stride 16*n, its y_{k+1} goes to slot y of the block.
 struct MultiUpdate {
@@ -381,6 +429,18 @@ static __global__ __launch_bounds__(256) void fista_update_multi_kernel(const fl
   fista_update_body<true, true>(slabs + (int64_t)v * n, nslabs, GradSrc{nullptr, nullptr}, n, mu.x_cur[v], mu.x_prev[v], mu.scal[v], prm,
                                 mu.part[v], host_beta, mu.beta[v], nullptr, host_beta ? y_block : nullptr, mu.beta_next[v],
                                 (int64_t)BT_NV * n, y_mode, v);
+}
+
+// ... on a problem with coordinate data: the factors and bounds belong to the columns of A, so all state machines share them
+static __global__ __launch_bounds__(256) void fista_update_multi_coord_kernel(const float* __restrict__ slabs, int nslabs, int n,
+                                                                      MultiUpdate mu, FistaParams prm0, float* __restrict__ y_block,
+                                                                      int y_mode, int host_beta, CoordData cd) {
+  const int v = blockIdx.y;
+  FistaParams prm = prm0;
+  prm.alpha1 = mu.alpha1[v]; prm.alpha2 = mu.alpha2[v]; prm.tau = mu.tau[v];
+  fista_update_body<true, true, true>(slabs + (int64_t)v * n, nslabs, GradSrc{nullptr, nullptr}, n, mu.x_cur[v], mu.x_prev[v],
+                                      mu.scal[v], prm, mu.part[v], host_beta, mu.beta[v], nullptr, host_beta ? y_block : nullptr,
+                                      mu.beta_next[v], (int64_t)BT_NV * n, y_mode, v, cd);
 }
 
 // One wave: fold the partials and advance the scalar state.  iterative_solvers.py:204-221, :235-242, :325-342.

@@ -128,6 +128,12 @@ def _weighted(A):
     return isinstance(A, _core.Problem) and A.sample_weight is not None
 
 
+def _has_coord(A):
+    """Whether A is a handle with penalty factors or bounds bound (`Problem.set_penalty`): it runs on the matrix-core lockstep
+    alone."""
+    return isinstance(A, _core.Problem) and A.has_coord
+
+
 def _weighted_lipschitz(prob, v0, n_iter=100, tol=1e-6):
     """ref:45-60 on A^T W A: w = A^T (W (A v)) is one fos_gram_apply per step (v rounded to fp32 for the pass), the norms and v
     itself stay in fp64 here.  max(w) lambda_max(A^T A) is not used: with class weights {1, r} it is loose by up to r."""
@@ -554,9 +560,10 @@ def _drive(prob, like, *, mode, prox_kind, alpha1, alpha2, tau, delta=0.0, backt
     return st
 
 
-def _tau(L, alpha2, t_init_factor):
-    """First step: t_init_factor / L, the ridge term being part of the smooth function (ref:156-158)."""
-    return t_init_factor / (L + (alpha2 if alpha2 > 0 else 0.0))
+def _tau(L, alpha2, t_init_factor, penalty_max=1.0):
+    """First step: t_init_factor / L, the ridge term being part of the smooth function (ref:156-158).  penalty_max: max_j p_j of
+    a handle with penalty factors - its ridge term 0.5 alpha2 sum_j p_j x_j^2 has the Lipschitz constant alpha2 max_j p_j."""
+    return t_init_factor / (L + (alpha2 * penalty_max if alpha2 > 0 else 0.0))
 
 
 class _Loop(collections.namedtuple("_Loop", "delta alpha1 alpha2 backtracking eta t_init_factor max_iter tol tol_ratio "
@@ -1171,19 +1178,25 @@ def fista_path(A, b, alphas, t_init_factor: float = 1.0, max_iter: int = 500, *,
     ``[(iterations, stop_code), ...]`` per weight.
     ``cols=(lo, hi, n_total)`` with ``comm=``: COLUMN sharding (A is this rank's columns, b whole, each returned x this
     rank's block) - the lockstep keeps ONE exchange per row panel, the panel's 16 residual columns between the two
-    products, plus 64 doubles of step norms per iteration."""
+    products, plus 64 doubles of step norms per iteration.
+    A handle with penalty factors or bounds (``prepare_penalized`` / ``Problem.set_penalty``): the objective is 0.5 ||Ax - b||^2
+    + alpha1 sum_j p_j |x_j| + 0.5 alpha2 sum_j p_j x_j^2 subject to lower_j <= x_j <= upper_j (``lower=0.0``: the non-negative
+    lasso; p_j = 0: an unpenalised coordinate).  Such a problem runs on the matrix-core lockstep alone, a single weight as a one-column lockstep, with the step t_init_factor / (L + alpha2 max_j p_j)
+    (L is the constant of the data term and does not depend on the constraints); ``tol``, ``comm=`` and ``cols=`` are
+    ValueErrors and a refusal raises."""
     reset_metrics()
     if delta is not None:
         assert delta > 2, "In FISTA-Δ, delta must be > 2 for convergence (course requirement)"
-    weighted = _weighted(A)
+    weighted = _weighted(A) or _has_coord(A)
     if weighted and (tol != 0.0 or comm is not None or cols is not None):
-        raise ValueError("a handle with sample weights runs on the lockstep alone: no tol (the gradient-norm rule), comm= or cols=")
+        raise ValueError("a handle with sample weights, penalty factors or bounds runs on the lockstep alone: no tol (the "
+                         "gradient-norm rule), comm= or cols=")
     prob, _ = _sharded_problem(A, b, dtype, comm, None, cols)    # comm: A, b are this rank's rows (matrix-core pass, one
     like = prob.like                                             # all-reduce of the 16 gradients per iteration)
     L_val = _lipschitz(prob, L, comm=comm, cols=cols)
     mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
     # the tolerances go to the device as given: a negative one is refused there (fos_fista_reset), not read as "off"
-    handles = _run_path(prob, [_params(_tau(L_val, a2, t_init_factor), a1, a2, mode=mode, delta=delta, tol=tol,
+    handles = _run_path(prob, [_params(_tau(L_val, a2, t_init_factor, prob.penalty_max), a1, a2, mode=mode, delta=delta, tol=tol,
                                        tol_ratio=tol_ratio, grad_rule=delta is None, adaptive_restart=adaptive_restart,
                                        restart_threshold=restart_threshold) for a1, a2 in alphas], max_iter, cols,
                         lockstep_only=weighted)
@@ -1333,7 +1346,11 @@ def fista_cv(A, b, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int = 
 
     A handle with sample weights (``prepare_weighted``): every fit minimises the weighted objective of its training rows,
     ``mse[f, a]`` is the weighted held-out sum of squares over the held-out weight sum (a fold whose weights sum to zero is a
-    ValueError before any solver launch), the refit runs in the lockstep too, and a refusal raises - there is no slow path."""
+    ValueError before any solver launch), the refit runs in the lockstep too, and a refusal raises - there is no slow path.
+
+    A handle with penalty factors or bounds (``prepare_penalized``), as in ``fista_path``: the constraints belong to
+    the coordinates, so every fold's fit carries them; the step is t_init_factor / (L + alpha2 max_j p_j); the refit runs in
+    the lockstep and a refusal raises - there is no slow path."""
     reset_metrics()
     if delta is not None:
         assert delta > 2, "In FISTA-Δ, delta must be > 2 for convergence (course requirement)"
@@ -1348,16 +1365,17 @@ def fista_cv(A, b, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int = 
         raise ValueError("fista_cv needs b")
     like = prob.like
     weighted = _weighted(prob)
+    lockstep_only = weighted or _has_coord(prob)
     if weighted:
         sizes = _cv_weight_sums(prob, ids, K)
     L_val = _lipschitz(prob, L)
     mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
-    prms = [_params(_tau(L_val, a2, t_init_factor), a1, a2, mode=mode, delta=delta, tol_ratio=tol_ratio,
+    prms = [_params(_tau(L_val, a2, t_init_factor, prob.penalty_max), a1, a2, mode=mode, delta=delta, tol_ratio=tol_ratio,
                     adaptive_restart=adaptive_restart, restart_threshold=restart_threshold) for a1, a2 in alphas]
     out = _cv_lockstep(prob, ids, K, prms, max_iter)
     if out is None:
-        if weighted:                 # no unweighted slow path may answer for a weighted handle
-            raise _lib.FosError("fos_fista_run_multi_folds refused the weighted lockstep: " +
+        if lockstep_only:            # no unweighted or unconstrained slow path may answer for such a handle
+            raise _lib.FosError("fos_fista_run_multi_folds refused the lockstep of a handle with sample weights, penalty factors or bounds: " +
                                 prob.lib.fos_last_error().decode("utf-8", "replace"))
         out = _cv_fold_by_fold(prob, ids, K, prms, max_iter)
     X, sse, info = out
@@ -1366,7 +1384,7 @@ def fista_cv(A, b, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int = 
     best = int(np.argmin(mean_mse))
     x = None
     if refit:
-        if weighted:
+        if lockstep_only:
             st = _run_path(prob, [prms[best]], max_iter, lockstep_only=True)[0]
         else:
             st = _new_state(prob, prms[best])

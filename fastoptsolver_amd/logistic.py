@@ -6,7 +6,13 @@ The gradient of the data term is A^T (sigma(Ax) - y): the lockstep of ``fista_pa
 1's epilogue changed (csrc/batch_trial.hpp, LOSS_LOGISTIC) - product 2, the updates, the per-column restarts and stops on
 the device and the fold masks are the launches of the squared loss.  The loss belongs to the problem handle
 (``prepare(A, y, loss="logistic")``, fos_problem_set_loss); every entry point that would answer with a squared-loss quantity
-refuses such a handle.  An intercept is a constant column appended by the caller.
+refuses such a handle.  An intercept is a constant column appended by the caller AND given the penalty factor 0
+(``prepare_penalized``): without the factor the column is shrunk like any other, which fits the wrong model whenever the classes
+are unbalanced.
+
+Per-coordinate penalty factors and box bounds (``prepare_penalized(A, y, penalty_factor, lower, upper, loss="logistic")``,
+``Problem.set_penalty``, fos_coord_bind): the penalties become alpha1 sum_j p_j |x_j| + 0.5 alpha2 sum_j p_j x_j^2 subject to lower_j <= x_j <= upper_j;
+the update kernel of the lockstep applies them per coordinate, the products over A are unchanged.
 
 Per-row sample weights (``prepare_weighted(A, y, w, loss="logistic")``, fos_row_weights_bind): the data term becomes
 sum_i w_i (log(1 + exp(a_i.x)) - y_i a_i.x); ``logistic_path`` / ``logistic_cv`` / ``logistic_objective`` take the handle as
@@ -55,7 +61,7 @@ def _params_of(prob, alphas, L, t_init_factor, delta, tol_ratio, adaptive_restar
     else:
         L_val = _its.estimate_lipschitz(prob) / 4.0
     mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
-    return [_its._params(_its._tau(L_val, a2, t_init_factor), a1, a2, mode=mode, delta=delta, tol_ratio=tol_ratio,
+    return [_its._params(_its._tau(L_val, a2, t_init_factor, prob.penalty_max), a1, a2, mode=mode, delta=delta, tol_ratio=tol_ratio,
                          adaptive_restart=adaptive_restart, restart_threshold=restart_threshold) for a1, a2 in alphas]
 
 
@@ -78,7 +84,12 @@ def logistic_path(A, y, alphas, t_init_factor: float = 1.0, max_iter: int = 500,
     the momentum, restart (``adaptive_restart`` / ``restart_threshold``) and ratio-stop (``tol_ratio``) rules of the
     reference's loop, decided per column on the device.  There is no ``tol`` (the gradient-norm rule), no backtracking and
     no sharding.  A: an array / tensor (zero-padded on the device so that every shape up to 16384 columns is served: see
-    ``prepare``) or a ``prepare(A, y, loss="logistic")`` handle (``y`` may then be None)."""
+    ``prepare``) or a ``prepare(A, y, loss="logistic")`` handle (``y`` may then be None).
+
+    A handle with penalty factors or bounds (``prepare_penalized(A, y, ..., loss="logistic")`` / ``Problem.set_penalty``):
+    per-coordinate factors p_j >= 0 of both penalties and box bounds lower_j <= 0 <= upper_j.  An intercept is a constant
+    column with factor 0.  The step is then ``t_init_factor / (L + alpha2 max_j
+    p_j)``; L does not depend on the constraints."""
     _its.reset_metrics()
     alphas = _check_path_args(alphas, delta)
     prob = _problem(A, y, dtype)
@@ -106,7 +117,10 @@ def logistic_cv(A, y, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int
     Returns ``LogisticCVResult(alphas, logloss, mean_logloss, best, x, coefs, info)``: ``logloss[f, a]`` the held-out MEAN
     log-loss (K x L float64 ndarray), ``mean_logloss`` its mean over the folds, ``best`` the argmin (first on ties), ``x``
     the fit on all rows at ``alphas[best]`` (``refit=True``; else None), ``coefs`` the n x K x L fits
-    (``return_coefs=True``; else None), ``info[f][a] = (iterations, stop_code)``."""
+    (``return_coefs=True``; else None), ``info[f][a] = (iterations, stop_code)``.
+
+    A handle with penalty factors or bounds, as in ``logistic_path``: every fold's fit carries them (they belong to the
+    coordinates, not the rows), with the step ``t_init_factor / (L + alpha2 max_j p_j)``."""
     _its.reset_metrics()
     alphas = _check_path_args(alphas, delta)
     m = A.m if isinstance(A, _core.Problem) else int(A.shape[0] if hasattr(A, "shape") else np.shape(A)[0])
@@ -135,7 +149,10 @@ def logistic_cv(A, y, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int
 def logistic_objective(x, A, y, alpha1, alpha2):
     """sum_i log(1 + exp(a_i.x)) - y_i a_i.x + alpha1 ||x||_1 + 0.5 alpha2 ||x||^2 with the data term from the device
     (fos_residual_batch on a logistic problem; x is rounded to fp32 for the pass over A).  ``x``: a vector (returns a float) or
-    an n x k block (returns k float64 values), 16 columns per pass.  Synchronises."""
+    an n x k block (returns k float64 values), 16 columns per pass.  Synchronises.
+    On a handle with penalty factors (``Problem.set_penalty``) the penalties are the factored ones, alpha1 sum_j p_j |x_j| +
+    0.5 alpha2 sum_j p_j x_j^2 (the fp32 factors as bound); the box is not checked - solver outputs lie inside it by
+    construction."""
     prob = _problem(A, y, None)
     xt = x.detach() if _core.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=np.float64))
     vector = xt.dim() == 1
@@ -146,5 +163,7 @@ def logistic_objective(x, A, y, alpha1, alpha2):
     for j0 in range(0, X.shape[1], 16):
         nll += prob.residual_batch(X[:, j0:j0 + 16], use_b=True)
     Xh = X.cpu().numpy()
-    val = np.asarray(nll, dtype=np.float64) + float(alpha1) * np.abs(Xh).sum(axis=0) + 0.5 * float(alpha2) * (Xh * Xh).sum(axis=0)
+    pf = np.ones(prob.n) if prob.penalty_factor is None else prob.penalty_factor.to("cpu", torch.float64).numpy()
+    val = (np.asarray(nll, dtype=np.float64) + float(alpha1) * (pf[:, None] * np.abs(Xh)).sum(axis=0) +
+           0.5 * float(alpha2) * (pf[:, None] * Xh * Xh).sum(axis=0))
     return float(val[0]) if vector else val

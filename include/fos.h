@@ -159,6 +159,30 @@ int fos_problem_get_loss(const fos_problem* p, int* loss);
  * on the weights; nothing is replanned.  fos_row_weights_get reads the bound pointer back (NULL: none). */
 int fos_row_weights_bind(const float* w, fos_problem* p);
 int fos_row_weights_get(const float** w_out, const fos_problem* p);
+/* Per-coordinate penalty factors p_j >= 0 and box bounds lower_j <= 0 <= upper_j (entries may be -inf / +inf): the objective is
+ *   data term (squared or logistic, weighted or not) + alpha1 sum_j p_j |x_j| + 0.5 alpha2 sum_j p_j x_j^2
+ *   subject to lower_j <= x_j <= upper_j .
+ * The factor scales both penalties and is used as given (p_j = 0: an unpenalised coordinate, e.g. the intercept column);
+ * lower <= 0 <= upper keeps x0 = 0 feasible.  Each vector: n floats on the device, borrowed, 16-byte aligned and readable up
+ * to n rounded up to 4 (the update fetches the values of 4 coordinates with one load); each may be NULL, which stands for
+ * factor 1, -inf and +inf; all three NULL detaches, which is always served.  The data pointers come first, the handle last.
+ * The values are not checked here (the Python layer checks them).  With any of the three bound
+ *   - fos_fista_run_multi (any nv in 1..16, one included) and fos_fista_run_multi_folds minimise the objective above: always
+ *     the two matrix-core products per iteration, with the refusals of a logistic problem; the products are unchanged and the
+ *     update applies, per coordinate and in fp64, the exact prox of penalty plus box: PROX_L1 adds (alpha2 p_j) y to the
+ *     gradient and thresholds at tau alpha1 p_j, PROX_ENET thresholds and divides by 1 + tau alpha2 p_j, then both clamp to
+ *     [lower_j, upper_j].  A valid step is tau <= 1 / (L + alpha2 max_j p_j) for PROX_L1.  Composes with the logistic loss and
+ *     with row weights;
+ *   - fos_residual_batch (use_b = 1) and fos_residual_batch_folds answer as before: the data term does not depend on the
+ *     coordinate data;
+ *   - every entry point that refuses a logistic problem refuses this one too (FOS_ERR_UNSUPPORTED before any launch or change
+ *     of handle state, with a message of its own): no form without the factors and bounds answers for such a problem;
+ *   - the entry points that touch neither b nor a residual work as before.
+ * FOS_ERR_ARG (checked before any HIP call): null p, a misaligned vector.  FOS_ERR_UNSUPPORTED under the conditions of
+ * fos_row_weights_bind: no b, a sharded problem, a shape without the matrix-core pair.  No buffer depends on the binding;
+ * nothing is replanned.  fos_coord_get reads the three bound pointers back (NULL: none). */
+int fos_coord_bind(const float* penalty_factor, const float* lower, const float* upper, fos_problem* p);
+int fos_coord_get(const float** penalty_factor, const float** lower, const float** upper, const fos_problem* p);
 /* G + j*n (n floats, device) = A^T W A X_j for the nv <= 16 columns of X (the layout of fos_residual_batch: n x 16 floats,
  * row-major).  W: the bound row weights, the identity when none are bound; neither b nor the loss enters, so logistic and
  * weighted problems are served.  Product 1 (R = w * (A X), kept), product 2 over every row panel, one slab sum.  Enqueues only.
