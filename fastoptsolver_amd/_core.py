@@ -493,6 +493,10 @@ class Problem:
         return self.vec_out(G).t()
 
     def power_iter(self, v0, n_iter=100, tol=1e-6):
+        """The reference's power iteration (ref:45-60) from v0 (n values, need not be normalised): ``(L, it, v)``.  On every
+        plan ``it`` is the step at which ``|L_k - L_{k-1}| < tol`` fired (``n_iter`` when it never did), ``L`` the norm of that
+        step and ``v`` (n floats on the device) the normalised iterate after exactly ``it`` steps (fos_power_iter).
+        Synchronises."""
         v = self.vec_in(v0).clone()
         L = C.c_double()
         it = C.c_int()

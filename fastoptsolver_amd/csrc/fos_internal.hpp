@@ -248,6 +248,7 @@ struct Scratch {
   DevBuf<double> dscal;              // 256 device doubles (scalars)
   DevBuf<double> part;               // partial sums of the small kernels
   DevBuf<double> lhist;              // fos_power_iter: L after every step (n_iter + 1 doubles, grown on demand)
+  DevBuf<float> vring;               // fos_power_iter, streaming plans: the iterates of the last 16 steps (16 x n rounded up to 4)
   DevBuf<float> rcols16;             // column-sharded candidate pass: m x 16 partial residuals (summed over the ranks)
   DevBuf<float> b16;                 // several right-hand sides: m x 16 zero-padded block of the caller's B (stage_b16)
   DevBuf<double> mfold;              // column-sharded lockstep: 16 x 4 folded step partials (summed over the ranks)

@@ -1723,26 +1723,33 @@ int fos_power_iter(fos_problem* p, float* v_inout, int n_iter, double tol, doubl
     if (iters_out) *iters_out = used;
     return FOS_OK;
   }
-  float* v = p->ws.ybuf;
+  // The iterate after step `it` lives in slot it % 16 of a ring of 16 vectors (16-byte aligned slots), so that the one
+  // the break rule selects is still there when the chunk that ran past it has been read back; v0 / ||v0|| takes the
+  // slot step 0 reads, the last one.
+  const int chunk = 16;
+  const size_t vstride = ((size_t)p->n + 3) & ~(size_t)3;
+  if (int rc = p->ws.vring.reserve((size_t)chunk * vstride)) return rc;
+  float* ring = p->ws.vring;
+  auto slot = [&](int it) { return ring + (size_t)((it + chunk) % chunk) * vstride; };
   // v = v0 / ||v0||   (iterative_solvers.py:51)
-  hipLaunchKernelGGL(fos::power_normalize_kernel, dim3(1), dim3(1024), 0, p->stream, v_inout, (int)p->n, v, Lh + n_iter);
+  hipLaunchKernelGGL(fos::power_normalize_kernel, dim3(1), dim3(1024), 0, p->stream, v_inout, (int)p->n, slot(-1),
+                     Lh + n_iter);
   LAUNCH_CHECK();
   // The reference breaks as soon as |L - prev| < tol (:57).  The iterations are enqueued in chunks; after each chunk
   // the L values are read back and the break rule is replayed on the host, so a matrix with a dominant eigenvalue
-  // stops after a chunk instead of running all n_iter passes (the answer is the same either way).
+  // stops after a chunk instead of running all n_iter passes (L, the step and v are those of the step that broke).
   std::vector<double> hL(n_iter);
-  const int chunk = 16;
   double prev = 0.0;
   int used = n_iter, done = 0;
   bool hit = false;
   while (done < n_iter && !hit) {
     const int todo = std::min(chunk, n_iter - done);
     for (int it = done; it < done + todo; ++it) {
-      YSource ys{v, nullptr, nullptr, nullptr, nullptr};
+      YSource ys{slot(it - 1), nullptr, nullptr, nullptr, nullptr};
       int n_rr = 0, rc;
       if ((rc = launch_pass(p, ys, nullptr, true, &n_rr))) return rc;                       // w = A^T (A v)   :54
       if ((rc = launch_slab_reduce(p, n_rr, p->gbuf, nullptr, nullptr))) return rc;
-      hipLaunchKernelGGL(fos::power_normalize_kernel, dim3(1), dim3(1024), 0, p->stream, p->gbuf, (int)p->n, v,
+      hipLaunchKernelGGL(fos::power_normalize_kernel, dim3(1), dim3(1024), 0, p->stream, p->gbuf, (int)p->n, slot(it),
                          Lh + it);                                                         // L = ||w||, v = w/L :55-56
       LAUNCH_CHECK();
     }
@@ -1754,7 +1761,8 @@ int fos_power_iter(fos_problem* p, float* v_inout, int n_iter, double tol, doubl
     }
     done += todo;
   }
-  HIP_TRY(hipMemcpyAsync(v_inout, v, (size_t)p->n * sizeof(float), hipMemcpyDeviceToDevice, p->stream));
+  // the iterate after `used` steps: the one L_out and iters_out belong to
+  HIP_TRY(hipMemcpyAsync(v_inout, slot(used - 1), (size_t)p->n * sizeof(float), hipMemcpyDeviceToDevice, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   *L_out = hL[used - 1];
   if (iters_out) *iters_out = used;

@@ -287,8 +287,13 @@ int fos_residual_batch_rhs(fos_problem* p, const float* X, int nv, const float* 
 int fos_residual_batch_folds(fos_problem* p, const float* X, int nv, const uint8_t* fold_of_row, const int32_t* held,
                              double* out16);
 
-/* Power iteration, iterative_solvers.py:45-60.  v_inout: start vector (n floats, need not be normalised),
- * overwritten with the last iterate.  Any n_iter >= 1.  Synchronises; *L_out and *iters_out are host values. */
+/* Power iteration, iterative_solvers.py:45-60.  v_inout: start vector (n floats, need not be normalised).  Any n_iter >= 1.
+ * Synchronises; *L_out and *iters_out are host values.
+ * One contract on every plan: *iters_out is the step k at which |L_k - L_{k-1}| < tol fired (L_0 = 0), or n_iter when it never
+ * did; *L_out is L_k; v_inout comes back as the normalised iterate after exactly those k steps, v_k = w_k / L_k (all NaN when
+ * L_k = 0).  The streaming plans enqueue 16 steps at a time and may have run past k; they keep the last 16 iterates and
+ * return the k-th.  FOS_ERR_ARG (before any launch, outputs untouched): null p / v_inout / L_out, n_iter < 1;
+ * FOS_ERR_UNSUPPORTED on a column-sharded problem. */
 int fos_power_iter(fos_problem* p, float* v_inout, int n_iter, double tol, double* L_out, int* iters_out);
 
 /* ---- stand-alone prox (K3), prox_operators.py:3-8 and :10-16 --------------------------------------- */
@@ -602,7 +607,9 @@ int fos_fista_run_batch(const void* A, int a_dtype, const float* b, const fos_ba
                         int32_t* iters_done, int32_t* stopped, double* tau_out, int32_t* ls_iters, double* tau_hist,
                         double* hist, double* x_hist, void* work, void* stream);
 /* fos_power_iter of every problem of the batch in one launch (b_offset unused): problem i's start vector at
- * v_inout + i*ldv (device, n floats; the normalised last iterate comes back there), L_out[i] and iters_used[i] (device).
+ * v_inout + i*ldv (device, n floats), L_out[i] and iters_used[i] (device).  The contract of fos_power_iter per problem:
+ * iters_used[i] is the step at which problem i's break rule fired (or n_iter), L_out[i] the L of that step, and the n floats
+ * at v_inout + i*ldv the normalised iterate after exactly that many steps; nothing else of v_inout is written.
  * work: count * sizeof(fos_batch_item) bytes of device memory (caller-owned).  Same argument checks as fos_fista_run_batch
  * (n_iter < 1, ldv < n: FOS_ERR_ARG).  Enqueues only. */
 int fos_power_iter_batch(const void* A, int a_dtype, const fos_batch_item* items, int count, float* v_inout, int64_t ldv,
