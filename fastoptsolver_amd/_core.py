@@ -47,7 +47,8 @@ def stores_bf16(A, dtype=None):
 
 
 UPLOAD_CHUNK_BYTES = 256 << 20
-LOSSES = {"squared": _lib.LOSS_SQUARED, "logistic": _lib.LOSS_LOGISTIC}
+LOSSES = {"squared": _lib.LOSS_SQUARED, "logistic": _lib.LOSS_LOGISTIC, "multinomial": _lib.LOSS_MULTINOMIAL}
+MAX_CLASSES = 16                         # a class group of the multinomial lockstep is C of its 16 columns
 LOGIT_MAX_N = 16384                      # device columns the matrix-core pair serves (csrc/fos_plan.hip pair_dd_multi_supported)
 LOGIT_MIN_N = {"f32": 68, "bf16": 72}    # the narrowest streaming width: 64 columns plus one 16-byte chunk
 
@@ -87,6 +88,37 @@ def checked_weights(w, m):
     if not bool((t > 0).any()):
         raise ValueError("sample_weight must not be all zero")
     return t
+
+
+def checked_labels(y, classes=None):
+    """The labels of a multinomial problem as a float64 ndarray and the number of classes C: one integral class index 0 .. C-1
+    per row, C given or (None) max(y) + 1, 2 <= C <= 16 - ValueError otherwise.  Checked on the host, before any device work."""
+    if y is None:
+        raise ValueError("a multinomial problem needs its labels")
+    a = np.asarray(y.detach().cpu().numpy() if is_tensor(y) else y)
+    if a.ndim != 1 or a.size == 0 or a.dtype.kind not in "iufb":
+        raise ValueError(f"multinomial labels: one class index per row expected, got shape {a.shape} and dtype {a.dtype}")
+    a = a.astype(np.float64)
+    if not np.isfinite(a).all() or (a != np.floor(a)).any() or a.min() < 0:
+        raise ValueError("multinomial labels must be integral class indices >= 0")
+    if classes is None:
+        classes = int(a.max()) + 1
+    elif isinstance(classes, (bool, np.bool_)) or not isinstance(classes, (int, np.integer)):
+        raise ValueError(f"classes: an int expected, got {classes!r}")
+    classes = int(classes)
+    if not 2 <= classes <= MAX_CLASSES:
+        raise ValueError(f"classes: 2 <= C <= {MAX_CLASSES} expected, got {classes}")
+    if a.max() > classes - 1:
+        raise ValueError(f"multinomial labels must lie in 0 .. {classes - 1}, got {int(a.max())}")
+    return a, classes
+
+
+def checked_class_groups(ncols, classes):
+    """The number of class groups that `ncols` lockstep columns of a C-class multinomial problem hold: ncols is a multiple of C
+    and at most 16 - ValueError otherwise, before any device work."""
+    if ncols < 1 or ncols > 16 or ncols % classes:
+        raise ValueError(f"a multinomial problem with {classes} classes takes a multiple of {classes} columns (at most 16), got {ncols}")
+    return ncols // classes
 
 
 def checked_coord(penalty_factor, lower, upper, n):
@@ -144,8 +176,11 @@ class Problem:
     """
 
     def __init__(self, A, b=None, dtype=None, pad=None, loss="squared", sample_weight=None):
-        """loss: "squared" (b is the target of 0.5 ||Ax - b||^2) or "logistic" (b holds labels in [0, 1]; the data term is the
-        log-loss, served by `logistic_path` / `logistic_cv` / `logistic_objective` only: fos_problem_set_loss).
+        """loss: "squared" (b is the target of 0.5 ||Ax - b||^2), "logistic" (b holds labels in [0, 1]; the data term is the
+        log-loss, served by `logistic_path` / `logistic_cv` / `logistic_objective` only: fos_problem_set_loss) or "multinomial"
+        (b holds class indices 0 .. C-1, C = max(b) + 1 - `Problem.multinomial` takes C; the data term is the softmax
+        cross-entropy, served by `multinomial_path` / `multinomial_cv` / `multinomial_objective` only: fos_problem_set_multinomial;
+        `.classes` is C, None on any other handle).
         pad: zero-pad the columns of the device copy of A to the fused kernel's granularity (4 fp32 / 8 bf16
         elements, 16-byte aligned rows) so that a ragged n or a misaligned view still gets the single-pass kernel
         (4x faster than the two-pass path at 65536 x 8190).  Zero columns stay exactly zero through gradient and
@@ -166,14 +201,29 @@ class Problem:
         prob._setup(A, b, dtype, None, loss, sample_weight, penalty_factor, lower, upper)
         return prob
 
-    def _setup(self, A, b, dtype, pad, loss, sample_weight, penalty_factor=None, lower=None, upper=None):
+    @classmethod
+    def multinomial(cls, A, y, classes=None, dtype=None, sample_weight=None, penalty_factor=None, lower=None, upper=None):
+        """The handle of a multinomial (softmax) problem with C = `classes` classes (None: max(y) + 1), with or without row
+        weights, penalty factors and bounds: the constructor that takes the number of classes (`prepare_multinomial`)."""
+        prob = cls.__new__(cls)
+        prob._setup(A, y, dtype, None, "multinomial", sample_weight, penalty_factor, lower, upper, classes)
+        return prob
+
+    def _setup(self, A, b, dtype, pad, loss, sample_weight, penalty_factor=None, lower=None, upper=None, classes=None):
         """__init__, and with penalty_factor / lower / upper (`prepare_penalized`; `set_penalty`, fos_coord_bind) the handle of a
         problem with per-coordinate penalty factors and box bounds: it runs on the matrix-core pair alone too and is padded by
         the rules of a logistic problem."""
         if loss not in LOSSES:
             raise ValueError(f"loss: one of {sorted(LOSSES)} expected, got {loss!r}")
         coord = any(v is not None for v in (penalty_factor, lower, upper))
-        pair_only = loss == "logistic" or sample_weight is not None or coord      # served by the matrix-core pair alone
+        pair_only = loss != "squared" or sample_weight is not None or coord       # served by the matrix-core pair alone
+        self.classes = None
+        if loss == "multinomial":                                        # before any device work
+            if isinstance(b, Problem) or isinstance(A, Problem):
+                raise ValueError("a multinomial problem binds an array or tensor")
+            b, self.classes = checked_labels(b, classes)
+        elif classes is not None:
+            raise ValueError('classes belongs to loss="multinomial"')
         if coord:                                                        # before any device work
             coord = checked_coord(penalty_factor, lower, upper, int(A.shape[1] if hasattr(A, "shape") else np.shape(A)[1]))
         if sample_weight is not None:                                    # before any device work
@@ -220,7 +270,7 @@ class Problem:
         self.dtype = "bf16" if want_bf16 else "f32"
         self.loss = loss
         if pair_only and n_dev > LOGIT_MAX_N:
-            raise ValueError(f"a logistic or weighted problem, or one with penalty factors or bounds, is limited to {LOGIT_MAX_N} device columns, "
+            raise ValueError(f"a logistic, multinomial or weighted problem, or one with penalty factors or bounds, is limited to {LOGIT_MAX_N} device columns, "
                              f"got {n_dev}")
         self.sample_weight = None
         self._coord = (None, None, None)
@@ -241,6 +291,9 @@ class Problem:
         sib.like = self.like
         sib.A, sib.m, sib.n, sib.n_dev, sib.lda = self.A, self.m, self.n, self.n_dev, self.lda
         sib.device, sib.dtype, sib.loss, sib.sample_weight = self.device, self.dtype, self.loss, None
+        sib.classes = self.classes
+        if self.loss == "multinomial":              # the sibling's own labels, checked against the same C on the host
+            b = checked_labels(b, self.classes)[0]
         sib._coord, sib.penalty_max = (None, None, None), 1.0
         sib._bind(b, self.lib)
         if self.has_coord:                          # the columns are the same columns: the device vectors are shared
@@ -270,7 +323,9 @@ class Problem:
             self.h = h
             self._stream = torch.cuda.current_stream(self.device).cuda_stream
             _lib.check(lib.fos_problem_set_gbuf(self.h, ptr(self.gbuf)), "fos_problem_set_gbuf")
-            if self.loss != "squared":
+            if self.loss == "multinomial":
+                _lib.check(lib.fos_problem_set_multinomial(int(self.classes), self.h), "fos_problem_set_multinomial")
+            elif self.loss != "squared":
                 _lib.check(lib.fos_problem_set_loss(self.h, LOSSES[self.loss]), "fos_problem_set_loss")
         self.lib = lib
 
@@ -442,7 +497,10 @@ class Problem:
         return float(v[0]), float(v[1]), float(v[2])
 
     def residual_batch(self, X, use_b=True):
-        """||A X_j - b||^2 for the <= 16 columns of X (n x nv) in one MFMA pass; host list.  Synchronises."""
+        """||A X_j - b||^2 for the <= 16 columns of X (n x nv) in one MFMA pass; host list.  Synchronises.  On a multinomial
+        handle (use_b) the columns are whole class groups and entry s * C is the loss sum of group s, the others 0."""
+        if self.classes and use_b:
+            checked_class_groups(int(X.shape[1]), self.classes)
         X = torch.as_tensor(X, device=self.device, dtype=torch.float32)
         nv = X.shape[1]
         Xf = torch.zeros(self.n_dev, 16, dtype=torch.float32, device=self.device)
@@ -509,10 +567,14 @@ class Problem:
 def prepare(A, b=None, dtype=None, pad=None, *, loss="squared"):
     """Upload/bind A (and b) once; the result can be passed as ``A`` to every solver (``b`` may then be None).
     ``loss="logistic"``: b holds labels in [0, 1] and the handle is one for ``logistic_path`` / ``logistic_cv`` /
-    ``logistic_objective`` (see ``Problem``); a handle that is passed in keeps the loss it was prepared with."""
+    ``logistic_objective`` (see ``Problem``); a handle that is passed in keeps the loss it was prepared with.
+    ``loss="multinomial"``: b holds one integral class index 0 .. C-1 per row with C = max(b) + 1 (2 <= C <= 16; checked on the
+    host before any device work) and the handle is one for ``multinomial_path`` / ``multinomial_cv`` / ``multinomial_objective``;
+    ``prepare_multinomial`` takes C explicitly (a class that no row carries).  ``prepare_weighted`` and ``prepare_penalized``
+    take the loss likewise."""
     if isinstance(A, Problem):
-        if loss == "logistic" and A.loss != "logistic":
-            raise ValueError("this Problem was prepared for the squared loss")
+        if loss != "squared" and A.loss != loss:
+            raise ValueError(f"this Problem was prepared for the {A.loss} loss")
         return A
     return Problem(A, b, dtype, pad, loss)
 
@@ -770,10 +832,18 @@ def stream_read_probe(t, launches=20):
     return gbps.value, us.value
 
 
+def _check_class_groups(handles):
+    """On a multinomial problem the handles are whole class groups (ValueError before any device work)."""
+    classes = getattr(handles[0].prob, "classes", None)
+    if classes:
+        checked_class_groups(len(handles), classes)
+
+
 def run_multi(handles, iters):
     """Advance up to 16 Fista handles of one Problem in lockstep (fos_fista_run_multi).
     Returns False when this shape / configuration has no multi-vector kernel (callers then run them one by one)."""
     lib = handles[0].lib
+    _check_class_groups(handles)
     arr = (C.c_void_p * len(handles))(*[h.h for h in handles])
     with handles[0].prob.ctx():
         rc = lib.fos_fista_run_multi(arr, len(handles), int(iters))
@@ -806,6 +876,7 @@ def run_multi_folds(handles, fold_ids, held, iters):
     is not served (callers then gather the rows fold by fold)."""
     lib = handles[0].lib
     nv = len(handles)
+    _check_class_groups(handles)
     arr = (C.c_void_p * nv)(*[h.h for h in handles])
     with handles[0].prob.ctx():
         rc = lib.fos_fista_run_multi_folds(arr, nv, int(iters), ptr(fold_ids), (C.c_int32 * nv)(*held))

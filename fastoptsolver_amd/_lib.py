@@ -10,6 +10,7 @@ FOS_F32, FOS_BF16 = 0, 1
 MODE_FISTA, MODE_DELTA, MODE_ISTA = 0, 1, 2
 PROX_L1, PROX_ENET = 0, 1
 LOSS_SQUARED, LOSS_LOGISTIC = 0, 1
+LOSS_MULTINOMIAL = 2          # set with fos_problem_set_multinomial (it takes the number of classes)
 STOP_NONE, STOP_STEP, STOP_RATIO, STOP_GRAD, STOP_LS_STALL = 0, 1, 2, 3, 4
 ERR_UNSUPPORTED = -4            # FOS_ERR_UNSUPPORTED: this problem / plan has no such form (callers take the next one)
 PLAN_NO_RESIDENT, PLAN_NO_TALL, PLAN_NO_WIDE, PLAN_NO_COLBLOCK, PLAN_CLUSTER, PLAN_INTERLEAVE, PLAN_NO_INTERLEAVE, PLAN_NO_CLUSTER, PLAN_FUSED_MFMA, PLAN_CHIP_RESIDENT, PLAN_NO_CHIP_RESIDENT = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024
@@ -63,6 +64,8 @@ SIGNATURES = {
     "fos_problem_set_stream": (_i32, [_vp, _vp]),
     "fos_problem_set_loss": (_i32, [_vp, _i32]),
     "fos_problem_get_loss": (_i32, [_vp, C.POINTER(_i32)]),
+    "fos_problem_set_multinomial": (_i32, [_i32, _vp]),
+    "fos_problem_get_classes": (_i32, [C.POINTER(_i32), _vp]),
     "fos_row_weights_bind": (_i32, [_vp, _vp]),
     "fos_row_weights_get": (_i32, [C.POINTER(_vp), _vp]),
     "fos_coord_bind": (_i32, [_vp, _vp, _vp, _vp]),

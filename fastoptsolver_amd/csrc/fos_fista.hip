@@ -687,6 +687,10 @@ static fos::MultiUpdate multi_update(fos_fista* const* fs, int nv, bool controll
 // A problem with coordinate data (fos_coord_bind: penalty factors and box bounds): the two-product form as well; both products
 // are the launches they were and the two update launch sites take the coordinate kernels (reduce_update.hpp, COORD), which
 // scale the penalties per coordinate and clamp to the box.  Composes with the fold mask, the logistic loss and row weights.
+// A multinomial problem (fos_problem_set_multinomial): the 16 columns are the class vectors of floor(16 / C) joint fits.
+// Product 1 is the plain storing form, R = A_panel Y (the logits; neither b nor a mask nor the weights enter it), the link
+// kernel (softmax_link.hpp) turns the panel into softmax(A_panel Y) - onehot(b) in place with the weights and the fold mask
+// applied, and everything after it is the same.  Plain runs only (run_multi_softmax).
 
 // Row splits of product 2 in the two-product form: the planned ones, or - on a problem planned for the cluster form, whose slab
 // count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated.
@@ -742,10 +746,11 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
   const bool weighted = p->row_weight != nullptr;
   const bool coord = has_coord(p);   // fos_coord_bind: the two update launches below take the coordinate kernels
   const fos::CoordData cd{p->coord_factor, p->coord_lo, p->coord_hi};
+  const bool softmax = p->loss == FOS_LOSS_MULTINOMIAL;      // the link kernel sits between the two products of every panel
   const bool two_products = b16 || fold_of_row || logit || weighted || coord;
-  bool use_cluster = p->multi.cp_cs && !two_products;
+  bool use_cluster = p->multi.cp_cs && !two_products && !softmax;
   int g_splits = p->multi.gram_splits;
-  if (two_products && (rc = two_product_splits(p, &g_splits))) return rc;
+  if ((two_products || softmax) && (rc = two_product_splits(p, &g_splits))) return rc;
   // candidate block: zero everywhere (padding columns, unused slots), then y_k of every state machine
   const size_t per_entry = is_bf16 ? 3 * sizeof(unsigned short) : sizeof(float);
   HIP_TRY(hipMemsetAsync(p->cand.xp, 0, (size_t)p->cand.n_pad * fos::BT_NV * per_entry, p->stream));
@@ -798,7 +803,11 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
       L.A = Ap; L.b = (fold_of_row || logit || weighted) ? p->b + row0 : bp; L.use_b = 1; L.rows = rows; L.rout = p->multi.rbuf16;
       L.bblock = b16 != nullptr; L.fold_of_row = fold_of_row ? fold_of_row + row0 : nullptr; L.held = held;
       L.row_weight = weighted ? p->row_weight + row0 : nullptr;
+      if (softmax) { L.b = nullptr; L.use_b = 0; L.fold_of_row = nullptr; L.held = nullptr; L.row_weight = nullptr; }     // the logits alone
       if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
+      if (softmax && (rc = launch_softmax_link(p, row0, rows, nv, fold_of_row ? fos::FOLD_TRAIN : fos::FOLD_OFF, fold_of_row, held,
+                                               p->cand.q_part, &nwg1)))
+        return rc;
       if (cols && (rc = reduce_across(p, p->multi.rbuf16, (size_t)rows * fos::BT_NV, false))) return rc;
       if ((rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
     }
@@ -891,9 +900,37 @@ static int run_multi_logit(fos_fista* const* fs, int nv, int iters, const uint8_
   return run_multi_mfma(fs, nv, iters, !all_plain, same_family, nullptr, fold_of_row, held);
 }
 
+// A multinomial problem: the two matrix-core products with the link kernel between them, for nv / C joint fits of C columns
+// each.  A stop or restart decided per column would break a joint fit, so only plain runs are served, and the columns of a
+// fit share their parameters (and the fold they hold out).
+static int run_multi_softmax(fos_fista* const* fs, int nv, int iters, const uint8_t* fold_of_row, const int32_t* held_ids,
+                             const fos::FoldHeld* held, const char* fn) {
+  fos_problem* p = fs[0]->p;
+  if (!p->b || p->comm || p->col_sharded || !pair_dd_multi_supported(p))
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the multinomial loss needs b, an unsharded problem and the matrix-core pair");
+  if (!softmax_groups_ok(p, nv, held_ids))
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": on a multinomial problem nv is a multiple of the classes and the handles of "
+                                                         "a class group hold out one fold");
+  bool all_plain, same_family;
+  if (int rc = lockstep_forms(fs, nv, fn, &all_plain, &same_family)) return rc;
+  if (!all_plain)
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": a multinomial problem is served plain runs only (no adaptive restart, no "
+                                                         "step or ratio tolerance: a rule decided per column would break the joint fit)");
+  for (int v = 0; v < nv; ++v) {
+    const fos::FistaParams &a = fs[v / p->classes * p->classes]->prm, &c = fs[v]->prm;
+    if (a.tau != c.tau || a.alpha1 != c.alpha1 || a.alpha2 != c.alpha2 || a.delta != c.delta || a.mode != c.mode ||
+        a.prox_kind != c.prox_kind)
+      return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the handles of a class group of a multinomial problem carry identical "
+                                                           "parameters");
+  }
+  if (iters == 0) return FOS_OK;
+  return run_multi_mfma(fs, nv, iters, false, same_family, nullptr, fold_of_row, held);
+}
+
 static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, int64_t ldb) {
   fos_problem* p = fs[0]->p;
   const bool rhs = B != nullptr;
+  if (p->loss == FOS_LOSS_MULTINOMIAL) return run_multi_softmax(fs, nv, iters, nullptr, nullptr, nullptr, "fos_fista_run_multi");
   if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight || has_coord(p))
     return run_multi_logit(fs, nv, iters, nullptr, nullptr, "fos_fista_run_multi");
   if (rhs && (p->comm || p->col_sharded))
@@ -1002,6 +1039,7 @@ int fos_fista_run_multi_folds(fos_fista* const* fs, int nv, int iters, const uin
   for (int v = 0; v < nv; ++v)
     if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi_folds: handles must share one problem");
   fos_problem* p = fs[0]->p;
+  if (p->loss == FOS_LOSS_MULTINOMIAL) return run_multi_softmax(fs, nv, iters, fold_of_row, held, &hb, "fos_fista_run_multi_folds");
   if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight || has_coord(p))
     return run_multi_logit(fs, nv, iters, fold_of_row, &hb, "fos_fista_run_multi_folds");
   if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the problem has no b of its own");

@@ -251,6 +251,7 @@ struct Scratch {
   DevBuf<float> vring;               // fos_power_iter, streaming plans: the iterates of the last 16 steps (16 x n rounded up to 4)
   DevBuf<float> rcols16;             // column-sharded candidate pass: m x 16 partial residuals (summed over the ranks)
   DevBuf<float> b16;                 // several right-hand sides: m x 16 zero-padded block of the caller's B (stage_b16)
+  DevBuf<double> link_part;          // multinomial fos_residual_batch / _folds: the link kernel's partials of all panels (panels x ncu x 16)
   DevBuf<double> mfold;              // column-sharded lockstep: 16 x 4 folded step partials (summed over the ranks)
   DevBuf<double> cr_part;            // chip-resident loop (chip_resident.hpp): [2][G][17] partials + [8] step sums + [1] rr
   DevBuf<unsigned> cr_bar;
@@ -269,7 +270,8 @@ struct fos_problem {
   fos_comm* comm = nullptr;          // row-sharded problem: sums of partial results go through it (comm.hpp)
   int64_t m = 0, n = 0, lda = 0;
   int dtype = FOS_F32;
-  int loss = FOS_LOSS_SQUARED;       // fos_problem_set_loss: what b means to the matrix-core lockstep (no buffer depends on it)
+  int loss = FOS_LOSS_SQUARED;       // fos_problem_set_loss / _set_multinomial: what b means to the matrix-core lockstep (no buffer depends on it)
+  int classes = 0;                   // fos_problem_set_multinomial: C of a multinomial problem (b holds class indices 0 .. C-1); 0 otherwise
   const float* row_weight = nullptr; // fos_row_weights_bind: the caller's m per-row weights of the data term (borrowed; nullptr: none)
   // fos_coord_bind: per-coordinate penalty factors and box bounds of the lockstep's update (borrowed; nullptr: 1, -inf, +inf)
   const float* coord_factor = nullptr;
@@ -407,6 +409,15 @@ struct BatchLaunch {
 // The one launcher of product 1: the form (STORE_R, BBLOCK, FOLD, LOSS, WEIGHT) follows from L and the problem's loss and is
 // looked up in the one table of launchable forms (fos_plan.hip kBatchForms); *nwg_out = the rows of q_part written.
 int launch_batch_product(fos_problem* p, const BatchLaunch& L, int* nwg_out);
+// The link kernel of a multinomial problem (softmax_link.hpp) on the `rows` rows of p->multi.rbuf16 that product 1 has just
+// filled with the logits of the panel starting at row0: R in place (not in the held-out form), q_part[wg][16] the loss sums of
+// the segments; labels, weights and fold ids are offset by row0 here.  fold: FOLD_OFF / FOLD_TRAIN / FOLD_HELD (fold_of_row and
+// held non-null unless FOLD_OFF).  *nwg_out = the rows of q_part written (at most p->ncu).
+int launch_softmax_link(fos_problem* p, int64_t row0, int64_t rows, int nv, int fold, const uint8_t* fold_of_row,
+                        const fos::FoldHeld* held, double* q_part, int* nwg_out);
+// Whether the nv columns split into whole class groups of a multinomial problem and (held non-null: HOST ids) every group
+// holds out one fold.
+bool softmax_groups_ok(const fos_problem* p, int nv, const int32_t* held);
 // The one guard of the entry points that form an unweighted squared-loss residual, gradient or objective: refuses a logistic
 // problem and a problem with row weights (FOS_ERR_UNSUPPORTED) before any launch or change of handle state.
 int need_squared(const fos_problem* p, const char* fn);

@@ -1,6 +1,7 @@
 // libfos_hip.so, translation unit 1 of 4 - planner, kernel menus and the problem-level entry points of the C ABI
 // (include/fos.h).  Host code only decides launch geometry and enqueues kernels; there is no CPU compute fallback.
 #include "fos_internal.hpp"
+#include "softmax_link.hpp"
 
 namespace fosapi {
 
@@ -696,7 +697,9 @@ int need_squared(const fos_problem* p, const char* fn) {
                                      "weighted squared and logistic losses run through fos_fista_run_multi / _run_multi_folds and fos_residual_batch / "
                                      "_folds");
   if (p && p->loss != FOS_LOSS_SQUARED)
-    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": not served on a logistic problem (fos_problem_set_loss); the logistic "
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + (p->loss == FOS_LOSS_MULTINOMIAL
+                                                             ? ": not served on a multinomial problem (fos_problem_set_multinomial); the multinomial "
+                                                             : ": not served on a logistic problem (fos_problem_set_loss); the logistic ") +
                                      "loss runs through fos_fista_run_multi / _run_multi_folds and fos_residual_batch / _folds");
   return coord_refusal(p, fn);
 }
@@ -708,6 +711,37 @@ bool fold_held_block(const int32_t* held, int nv, fos::FoldHeld* out) {
     out->id[j] = (int8_t)h;                        // -1 is the byte 255, which no row carries
   }
   return true;
+}
+
+bool softmax_groups_ok(const fos_problem* p, int nv, const int32_t* held) {
+  const int C = p->classes;
+  if (C < 2 || nv % C != 0) return false;
+  for (int j = 0; held && j < nv; ++j)
+    if (held[j] != held[j / C * C]) return false;
+  return true;
+}
+
+// The link kernel (softmax_link.hpp) behind product 1 on one row panel of a multinomial problem.  One thread per row: the
+// panel has at most 256 * ncu rows, so the grid is at most ncu workgroups and q_part (3 * ncu + 8 rows) holds its partials.
+int launch_softmax_link(fos_problem* p, int64_t row0, int64_t rows, int nv, int fold, const uint8_t* fold_of_row,
+                        const fos::FoldHeld* held, double* q_part, int* nwg_out) {
+  if (p->loss != FOS_LOSS_MULTINOMIAL || rows < 1 || rows > p->multi.panel_rows || !softmax_groups_ok(p, nv, nullptr) ||
+      ((fold != fos::FOLD_OFF) && (!fold_of_row || !held)))
+    return fail(FOS_ERR_STATE, "launch_softmax_link: not a panel of a multinomial problem");
+  const int nwg = (int)std::min<int64_t>((rows + fos::SL_THREADS - 1) / fos::SL_THREADS, p->ncu);
+  const fos::FoldHeld hb = held ? *held : fos::FoldHeld{};
+  const float* w = p->row_weight ? p->row_weight + row0 : nullptr;
+  const uint8_t* ids = fold != fos::FOLD_OFF ? fold_of_row + row0 : nullptr;
+#define FOS_LINK(F, W)                                                                                                          \
+  hipLaunchKernelGGL((fos::softmax_link_kernel<fos::F, W>), dim3(nwg), dim3(fos::SL_THREADS), 0, p->stream, p->multi.rbuf16.get(), \
+                     rows, p->b + row0, p->classes, nv, w, ids, hb, q_part, (const int*)nullptr)
+  if (fold == fos::FOLD_TRAIN) { if (w) FOS_LINK(FOLD_TRAIN, true); else FOS_LINK(FOLD_TRAIN, false); }
+  else if (fold == fos::FOLD_HELD) { if (w) FOS_LINK(FOLD_HELD, true); else FOS_LINK(FOLD_HELD, false); }
+  else { if (w) FOS_LINK(FOLD_OFF, true); else FOS_LINK(FOLD_OFF, false); }
+#undef FOS_LINK
+  LAUNCH_CHECK();
+  *nwg_out = nwg;
+  return FOS_OK;
 }
 
 // q[j] = sum_i R[i][j]^2 of an m x 16 residual block (column-sharded candidate pass, after the sum over the ranks)
@@ -1208,7 +1242,8 @@ int fos_problem_create(fos_problem** out, const void* A, int64_t m, int64_t n, i
 
 int fos_problem_set_loss(fos_problem* p, int loss) {
   if (!p) return fail(FOS_ERR_ARG, "fos_problem_set_loss: null");
-  if (loss != FOS_LOSS_SQUARED && loss != FOS_LOSS_LOGISTIC) return fail(FOS_ERR_ARG, "fos_problem_set_loss: unknown loss");
+  if (loss != FOS_LOSS_SQUARED && loss != FOS_LOSS_LOGISTIC)
+    return fail(FOS_ERR_ARG, "fos_problem_set_loss: unknown loss (the multinomial loss is set with fos_problem_set_multinomial)");
   if (loss == FOS_LOSS_LOGISTIC) {
     if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_loss: a logistic problem needs b (the labels)");
     if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_loss: sharded problems are not served");
@@ -1217,6 +1252,25 @@ int fos_problem_set_loss(fos_problem* p, int loss) {
                                        "layout, 65..16384 columns)");
   }
   p->loss = loss;                    // no buffer depends on the loss: nothing to invalidate
+  return FOS_OK;
+}
+
+int fos_problem_set_multinomial(int classes, fos_problem* p) {
+  if (!p) return fail(FOS_ERR_ARG, "fos_problem_set_multinomial: null problem");
+  if (classes < 2 || classes > fos::BT_NV) return fail(FOS_ERR_ARG, "fos_problem_set_multinomial: classes outside 2..16");
+  if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_multinomial: a multinomial problem needs b (the class of every row)");
+  if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_multinomial: sharded problems are not served");
+  if (!pair_dd_multi_supported(p))
+    return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_multinomial: the multinomial loss runs on the matrix-core pair (aligned "
+                                     "streaming layout, 65..16384 columns)");
+  p->loss = FOS_LOSS_MULTINOMIAL;    // no buffer depends on the loss or on the number of classes: nothing to invalidate
+  p->classes = classes;
+  return FOS_OK;
+}
+
+int fos_problem_get_classes(int* classes, const fos_problem* p) {
+  if (!p || !classes) return fail(FOS_ERR_ARG, "fos_problem_get_classes: null");
+  *classes = p->loss == FOS_LOSS_MULTINOMIAL ? p->classes : 0;
   return FOS_OK;
 }
 
@@ -1640,10 +1694,45 @@ static int residual_batch_pair(fos_problem* p, const char* fn, const float* X, i
   return residual_batch_sums(p, L, out16);
 }
 
+// fos_residual_batch / _folds on a multinomial problem: per row panel the storing product 1 in its plain form (the logits of
+// the panel in rbuf16), then the link kernel (softmax_link.hpp), whose partials of all panels fold into out16: out16[s * C] =
+// the loss sum of segment s, weighted per row on a problem with row weights, over all rows (held == nullptr) or over the rows
+// of the fold the segment holds out; 0 in the other entries.  Arguments are checked.
+static int residual_batch_softmax(fos_problem* p, const char* fn, const float* X, int nv, double* out16, const uint8_t* fold_of_row,
+                                  const fos::FoldHeld* held) {
+  if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the shape has no matrix-core pair");
+  int rc = ensure_batch_workspace(p);
+  if (rc) return rc;
+  if ((rc = plan_multi_mfma(p))) return rc;
+  const int64_t panels = (p->m + p->multi.panel_rows - 1) / p->multi.panel_rows;
+  if ((rc = p->ws.link_part.reserve((size_t)panels * p->ncu * fos::BT_NV))) return rc;
+  if ((rc = pack_candidates(p, X, nv))) return rc;
+  const int64_t esz = p->dtype == FOS_BF16 ? 2 : 4;
+  int nparts = 0;
+  for (int64_t row0 = 0; row0 < p->m; row0 += p->multi.panel_rows) {
+    const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
+    int nwg1 = 0, nwg = 0;
+    BatchLaunch L{};                 // Z = A_panel X: no b, no mask, no weights
+    L.A = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz; L.rows = rows; L.rout = p->multi.rbuf16;
+    if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
+    if ((rc = launch_softmax_link(p, row0, rows, nv, held ? fos::FOLD_HELD : fos::FOLD_OFF, fold_of_row, held,
+                                  p->ws.link_part + (size_t)nparts * fos::BT_NV, &nwg)))
+      return rc;
+    nparts += nwg;
+  }
+  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->ws.link_part, nparts, fos::BT_NV, out16);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
 int fos_residual_batch(fos_problem* p, const float* X, int nv, int use_b, double* out16) {
   if (!p || !X || !out16 || nv < 1 || nv > fos::BT_NV) return fail(FOS_ERR_ARG, "fos_residual_batch: bad argument");
   if (!use_b)                        // ||A X_j||^2 is a squared-loss quantity
     if (int rc = need_squared(p, "fos_residual_batch (use_b = 0)")) return rc;
+  if (p->loss == FOS_LOSS_MULTINOMIAL) {
+    if (!softmax_groups_ok(p, nv, nullptr)) return fail(FOS_ERR_ARG, "fos_residual_batch: on a multinomial problem nv is a multiple of the classes");
+    return residual_batch_softmax(p, "fos_residual_batch", X, nv, out16, nullptr, nullptr);
+  }
   if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight) return residual_batch_pair(p, "fos_residual_batch", X, nv, out16, nullptr, nullptr);
   if (!batch_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch: needs the fused path");
   int rc = ensure_batch_workspace(p);
@@ -1674,6 +1763,12 @@ int fos_residual_batch_folds(fos_problem* p, const float* X, int nv, const uint8
                              "aligned or a held id outside -1..254)");
   if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: the problem has no b of its own");
   if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch_folds: sharded problems are not served");
+  if (p->loss == FOS_LOSS_MULTINOMIAL) {
+    if (!softmax_groups_ok(p, nv, held))
+      return fail(FOS_ERR_ARG, "fos_residual_batch_folds: on a multinomial problem nv is a multiple of the classes and the columns of "
+                               "a class group hold out one fold");
+    return residual_batch_softmax(p, "fos_residual_batch_folds", X, nv, out16, fold_of_row, &hb);
+  }
   return residual_batch_pair(p, "fos_residual_batch_folds", X, nv, out16, fold_of_row, &hb);
 }
 

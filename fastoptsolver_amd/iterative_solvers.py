@@ -134,6 +134,14 @@ def _has_coord(A):
     return isinstance(A, _core.Problem) and A.has_coord
 
 
+def _refuse_multinomial(A, who):
+    """A multinomial handle (`prepare(..., loss="multinomial")`) belongs to multinomial_path / multinomial_cv /
+    multinomial_objective: its lockstep columns are class groups, which no squared-loss or logistic solver forms."""
+    if isinstance(A, _core.Problem) and A.loss == "multinomial":
+        raise ValueError(f"{who}: A was prepared for the multinomial loss: use multinomial_path / multinomial_cv / "
+                         "multinomial_objective")
+
+
 def _weighted_lipschitz(prob, v0, n_iter=100, tol=1e-6):
     """ref:45-60 on A^T W A: w = A^T (W (A v)) is one fos_gram_apply per step (v rounded to fp32 for the pass), the norms and v
     itself stay in fp64 here.  max(w) lambda_max(A^T A) is not used: with class weights {1, r} it is loose by up to r."""
@@ -1070,6 +1078,7 @@ def _lipschitz(prob, L, *, comm=None, cols=None, group=None):
 def _solve(A, b, reg_type, lp, return_history, L, dtype, check_every, comm, group, cols):
     """The front end of fista and fista_delta: a batch, several targets or one problem, sharded or not."""
     reset_metrics()
+    _refuse_multinomial(A, "fista / fista_delta")
     batch = _is_batch(A)
     B = None if batch else _targets(A, b)
     if batch or B is not None:
@@ -1185,6 +1194,7 @@ def fista_path(A, b, alphas, t_init_factor: float = 1.0, max_iter: int = 500, *,
     (L is the constant of the data term and does not depend on the constraints); ``tol``, ``comm=`` and ``cols=`` are
     ValueErrors and a refusal raises."""
     reset_metrics()
+    _refuse_multinomial(A, "fista_path")
     if delta is not None:
         assert delta > 2, "In FISTA-Δ, delta must be > 2 for convergence (course requirement)"
     weighted = _weighted(A) or _has_coord(A)
@@ -1352,6 +1362,7 @@ def fista_cv(A, b, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int = 
     the coordinates, so every fold's fit carries them; the step is t_init_factor / (L + alpha2 max_j p_j); the refit runs in
     the lockstep and a refusal raises - there is no slow path."""
     reset_metrics()
+    _refuse_multinomial(A, "fista_cv")
     if delta is not None:
         assert delta > 2, "In FISTA-Δ, delta must be > 2 for convergence (course requirement)"
     alphas = [(float(a1), float(a2)) for a1, a2 in alphas]

@@ -44,7 +44,7 @@ def _problem(A, y, dtype):
     """The logistic handle on (A, y): a prepared one as it is, anything else bound (and padded) here."""
     if isinstance(A, _core.Problem):
         if A.loss != "logistic":
-            raise ValueError('A was prepared for the squared loss: use prepare(A, y, loss="logistic")')
+            raise ValueError(f'A was prepared for the {A.loss} loss: use prepare(A, y, loss="logistic")')
         return A
     if y is None:
         raise ValueError("the labels y are needed")

@@ -1,0 +1,219 @@
+"""Sparse multinomial (softmax) regression on the matrix-core lockstep (extension; the reference has squared loss only).
+
+    minimise over X (n x C)   sum_i logsumexp_c(a_i.x_c) - a_i.x_{y_i}  +  alpha1 sum_c ||x_c||_1  +  0.5 alpha2 sum_c ||x_c||^2
+
+with labels y_i in {0, ..., C-1}, 2 <= C <= 16.  The gradient of class c is A^T (softmax(A X)_c - [y = c]).  The 16 candidate
+columns of the lockstep of ``fista_path`` hold the C class vectors of floor(16 / C) fits at once: product 1 computes all class
+logits in one read of A, a link kernel couples the C columns of every fit (csrc/softmax_link.hpp: softmax, one-hot, loss),
+product 2 computes all class gradients in the other read, and the updates, fold masks, row weights, penalty factors and bounds
+are the launches of every other lockstep.  The loss belongs to the problem handle (``prepare(A, y, loss="multinomial")``,
+``prepare_multinomial(A, y, classes=C)``; fos_problem_set_multinomial); every other solver refuses such a handle.
+
+This is the symmetric (over-parametrised) softmax model glmnet and scikit-learn fit: with alpha1 > 0 or alpha2 > 0 the penalty
+picks the solution.  A per-class intercept is a constant column with penalty factor 0 (``prepare_penalized``); rows weights
+(``prepare_weighted``) multiply the data term per row.
+
+The fits of a class group are one joint problem, so only plain runs exist: there is no ``tol_ratio``, ``adaptive_restart`` or
+``restart_threshold`` here - a stop or restart decided per column would break the fit.
+"""
+from __future__ import annotations
+
+import collections
+
+import numpy as np
+import torch
+
+from . import _core, _lib
+from . import iterative_solvers as _its
+from .logistic import _check_path_args
+
+MultinomialCVResult = collections.namedtuple("MultinomialCVResult", "alphas logloss mean_logloss best x coefs info")
+
+LOCKSTEP_COLUMNS = 16
+
+
+def pack_groups(count, classes):
+    """How `count` fits of a C-class model share the 16 lockstep columns: ``[(first, number), ...]``, floor(16 / C) fits per
+    group, the last group partial.  Fit i of a group owns columns ``i * C .. i * C + C - 1``.  Pure: no device work."""
+    classes = int(classes)
+    if not 2 <= classes <= _core.MAX_CLASSES:
+        raise ValueError(f"classes: 2 <= C <= {_core.MAX_CLASSES} expected, got {classes}")
+    if count < 0:
+        raise ValueError("count must be >= 0")
+    per = LOCKSTEP_COLUMNS // classes
+    return [(first, min(per, count - first)) for first in range(0, count, per)]
+
+
+def prepare_multinomial(A, y, classes=None, dtype=None, *, sample_weight=None, penalty_factor=None, lower=None, upper=None):
+    """``prepare(A, y, loss="multinomial")`` with the number of classes given: ``y`` holds one integral class index 0 .. C-1 per
+    row (``classes=None``: C = max(y) + 1), 2 <= C <= 16, checked on the host before any device work (ValueError).  With
+    ``sample_weight`` the handle is a weighted one (``prepare_weighted``), with ``penalty_factor`` / ``lower`` / ``upper`` one
+    with per-coefficient penalty factors and box bounds (``prepare_penalized``; they belong to the coefficient's row of X and
+    hold for every class).  Pass the handle as ``A`` (``y`` None) to ``multinomial_path`` / ``multinomial_cv`` /
+    ``multinomial_objective``; ``.classes`` is C."""
+    if isinstance(A, _core.Problem):
+        raise ValueError("prepare_multinomial binds an array or tensor; this is already a Problem")
+    return _core.Problem.multinomial(A, y, classes, dtype, sample_weight, penalty_factor, lower, upper)
+
+
+def _problem(A, y, classes, dtype):
+    """The multinomial handle on (A, y): a prepared one as it is, anything else bound (and padded) here."""
+    if isinstance(A, _core.Problem):
+        if A.loss != "multinomial":
+            raise ValueError(f'A was prepared for the {A.loss} loss: use prepare(A, y, loss="multinomial")')
+        if classes is not None and int(classes) != A.classes:
+            raise ValueError(f"classes = {classes}, but the handle was prepared with {A.classes} classes")
+        return A
+    return _core.Problem.multinomial(A, y, classes, dtype)
+
+
+def _lipschitz(prob, L):
+    """L of the multinomial data term: Boehning's bound, the softmax Hessian is <= 1/2 I (x) A^T A (A^T W A on a weighted
+    handle), so lambda_max / 2 unless given."""
+    return float(L) if L is not None else _its.estimate_lipschitz(prob) / 2.0
+
+
+def _params_of(prob, alphas, L, t_init_factor, delta):
+    L_val = _lipschitz(prob, L)
+    mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
+    return [_its._params(_its._tau(L_val, a2, t_init_factor, prob.penalty_max), a1, a2, mode=mode, delta=delta) for a1, a2 in alphas]
+
+
+def _class_handles(prob, prms):
+    """C state machines per parameter set, class-minor: the columns of one lockstep group."""
+    return [_its._new_state(prob, prm) for prm in prms for _ in range(prob.classes)]
+
+
+def _run_groups(prob, prms, max_iter):
+    """Every parameter set as a class group of the lockstep (fos_fista_run_multi on a multinomial problem), floor(16 / C) per
+    call: (X n x C x len(prms) float64 device, [(iterations, stop_code)]).  A refusal raises."""
+    C = prob.classes
+    X = torch.zeros(prob.n, C, len(prms), dtype=torch.float64, device=prob.device)
+    info = []
+    gtimer = _its._EventTimer(_its.grad_call_times)
+    for first, number in pack_groups(len(prms), C):
+        handles = _class_handles(prob, prms[first:first + number])
+        ev = gtimer.start()
+        if not _core.run_multi(handles, max_iter):
+            raise _lib.FosError("fos_fista_run_multi refused the multinomial lockstep: " +
+                                prob.lib.fos_last_error().decode("utf-8", "replace"))
+        gtimer.stop(ev, max_iter)
+        for i in range(number):
+            X[:, :, first + i] = torch.stack([st.x_tensor() for st in handles[i * C:(i + 1) * C]], dim=1)
+            s = handles[i * C].status()
+            info.append((int(s.k), int(s.stopped)))
+    gtimer.flush()
+    return X, info
+
+
+def multinomial_path(A, y, alphas, classes=None, t_init_factor: float = 1.0, max_iter: int = 500, *, delta=None, L=None,
+                     dtype=None, return_info: bool = False):
+    """Sparse multinomial regression of the class labels ``y`` (integers 0 .. C-1) on A for several weights at once.
+
+    ``alphas`` is a sequence of ``(alpha1, alpha2)`` pairs; the result is the list of n x C solutions, one per pair (column c
+    the coefficients of class c), and with ``return_info=True`` also ``[(iterations, stop_code), ...]``.  ``classes``: C, or
+    None for max(y) + 1 (a handle knows its own).  floor(16 / C) pairs advance per lockstep call (``pack_groups``); a call
+    reads A twice per iteration whatever the number of pairs and classes in it.
+
+    ``L``, when not given, is ``estimate_lipschitz(A) / 2`` (one power iteration, one draw from the global NumPy stream):
+    Boehning's bound, the Hessian of the softmax data term is <= 1/2 I (x) A^T A; on a weighted handle lambda_max(A^T W A) / 2.
+    The step is ``t_init_factor / (L + alpha2 max_j p_j)`` (p: the penalty factors of a ``prepare_penalized`` handle, else 1).
+
+    Contract: each result is FISTA (FISTA-Δ with ``delta`` > 2) on the multinomial objective over the stacked unknown from
+    X0 = 0 with that step for exactly ``max_iter`` iterations.  No stopping rule and no momentum restart: the columns of a fit
+    are one joint problem.  A: an array / tensor (padded on the device as a logistic problem is; at most 16384 device columns)
+    or a ``prepare(A, y, loss="multinomial")`` / ``prepare_multinomial`` handle (``y`` may then be None), weighted or penalised
+    handles included."""
+    _its.reset_metrics()
+    alphas = _check_path_args(alphas, delta)
+    prob = _problem(A, y, classes, dtype)
+    X, info = _run_groups(prob, _params_of(prob, alphas, L, t_init_factor, delta), max_iter)
+    xs = [_core.from_device_vec(X[:, :, a], prob.like) for a in range(len(alphas))]
+    return (xs, info) if return_info else xs
+
+
+def multinomial_cv(A, y, alphas, folds=5, classes=None, t_init_factor: float = 1.0, max_iter: int = 500, *, delta=None, L=None,
+                   dtype=None, refit: bool = True, return_coefs: bool = False):
+    """K-fold cross-validation of a multinomial regularisation path: ``fista_cv`` with the softmax cross-entropy.
+
+    ``folds`` as in ``fista_cv`` (an int K >= 2 or one fold id per row), validated before any device work.  Every (fold,
+    weight) pair is a class group of the masked lockstep on the one device copy of A (fos_fista_run_multi_folds on a
+    multinomial problem), floor(16 / C) pairs per call; the held-out losses of a call come from one further pass with the
+    complementary mask (fos_residual_batch_folds).  ``L`` comes from the whole A (``estimate_lipschitz(A) / 2`` unless given)
+    and is valid for every training set.  Contract: ``coefs[:, :, f, a]`` is what ``multinomial_path(A[train_f], y[train_f],
+    [alphas[a]], classes=C, ..., L=L)`` returns.
+
+    Returns ``MultinomialCVResult(alphas, logloss, mean_logloss, best, x, coefs, info)``: ``logloss[f, a]`` the held-out MEAN
+    cross-entropy (K x L float64 ndarray; on a weighted handle the weighted sum over the held-out weight sum), ``mean_logloss``
+    its mean over the folds, ``best`` the argmin (first on ties), ``x`` the n x C fit on all rows at ``alphas[best]``
+    (``refit=True``; else None), ``coefs`` the n x C x K x L fits (``return_coefs=True``; else None), ``info[f][a] =
+    (iterations, stop_code)``."""
+    _its.reset_metrics()
+    alphas = _check_path_args(alphas, delta)
+    m = A.m if isinstance(A, _core.Problem) else int(A.shape[0] if hasattr(A, "shape") else np.shape(A)[0])
+    ids, sizes = _its._cv_folds(folds, m)
+    K, La = len(sizes), len(alphas)
+    prob = _problem(A, y, classes, dtype)
+    C = prob.classes
+    if _its._weighted(prob):         # weighted held-out sums over the held-out weight sums; a zero-weight fold raises here
+        sizes = _its._cv_weight_sums(prob, ids, K)
+    prms = _params_of(prob, alphas, L, t_init_factor, delta)
+    pairs = [(f, a) for f in range(K) for a in range(La)]
+    ids_dev = _core.fold_ids_tensor(ids, prob.device)
+    X = torch.zeros(prob.n, C, K, La, dtype=torch.float64, device=prob.device)
+    total = np.zeros((K, La))
+    info = [[None] * La for _ in range(K)]
+    gtimer = _its._EventTimer(_its.grad_call_times)
+    for first, number in pack_groups(len(pairs), C):
+        grp = pairs[first:first + number]
+        held = [f for f, _ in grp for _ in range(C)]
+        handles = _class_handles(prob, [prms[a] for _, a in grp])
+        ev = gtimer.start()
+        if not _core.run_multi_folds(handles, ids_dev, held, max_iter):
+            raise _lib.FosError("fos_fista_run_multi_folds refused the multinomial lockstep: " +
+                                prob.lib.fos_last_error().decode("utf-8", "replace"))
+        gtimer.stop(ev, max_iter)
+        xg = torch.stack([st.x_tensor() for st in handles], dim=1)
+        q = prob.residual_batch_folds(xg, ids_dev, held)
+        if q is None:
+            raise _lib.FosError("fos_residual_batch_folds refused the multinomial problem: " +
+                                prob.lib.fos_last_error().decode("utf-8", "replace"))
+        for i, (f, a) in enumerate(grp):
+            X[:, :, f, a] = xg[:, i * C:(i + 1) * C]
+            total[f, a] = q[i * C]
+            s = handles[i * C].status()
+            info[f][a] = (int(s.k), int(s.stopped))
+    gtimer.flush()
+    logloss = total / sizes[:, None].astype(np.float64)
+    mean_logloss = logloss.mean(axis=0)
+    best = int(np.argmin(mean_logloss))
+    x = None
+    if refit:
+        x = _core.from_device_vec(_run_groups(prob, [prms[best]], max_iter)[0][:, :, 0], prob.like)
+    coefs = _core.from_device_vec(X, prob.like) if return_coefs else None
+    return MultinomialCVResult(alphas, logloss, mean_logloss, best, x, coefs, info)
+
+
+def multinomial_objective(X, A, y, alpha1, alpha2):
+    """sum_i logsumexp_c(a_i.x_c) - a_i.x_{y_i} + alpha1 sum |X| + 0.5 alpha2 sum X^2 with the data term from the device
+    (fos_residual_batch on a multinomial problem; X is rounded to fp32 for the pass over A; weighted per row on a weighted
+    handle).  ``X``: n x C (returns a float) or an n x C x k block (returns k float64 values), floor(16 / C) members per pass.
+    Synchronises.  On a handle with penalty factors the penalties are the factored ones, alpha1 sum_j p_j sum_c |x_jc| + 0.5
+    alpha2 sum_j p_j sum_c x_jc^2 (the fp32 factors as bound); the box is not checked."""
+    prob = _problem(A, y, None, None)
+    C = prob.classes
+    xt = X.detach() if _core.is_tensor(X) else torch.from_numpy(np.asarray(X, dtype=np.float64))
+    single = xt.dim() == 2
+    if xt.dim() not in (2, 3) or xt.shape[0] != prob.n or xt.shape[1] != C:
+        raise ValueError(f"X: an {prob.n} x {C} matrix or an {prob.n} x {C} x k block expected, got shape {tuple(xt.shape)}")
+    Xd = (xt.unsqueeze(2) if single else xt).to(device=prob.device, dtype=torch.float64)
+    k = Xd.shape[2]
+    nll = []
+    for first, number in pack_groups(k, C):
+        block = Xd[:, :, first:first + number].permute(0, 2, 1).reshape(prob.n, number * C)      # member-major, class-minor
+        nll += prob.residual_batch(block, use_b=True)[::C]
+    Xh = Xd.cpu().numpy()
+    pf = np.ones(prob.n) if prob.penalty_factor is None else prob.penalty_factor.to("cpu", torch.float64).numpy()
+    val = (np.asarray(nll, dtype=np.float64) + float(alpha1) * (pf[:, None, None] * np.abs(Xh)).sum(axis=(0, 1)) +
+           0.5 * float(alpha2) * (pf[:, None, None] * Xh * Xh).sum(axis=(0, 1)))
+    return float(val[0]) if single else val

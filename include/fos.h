@@ -29,7 +29,7 @@ enum { FOS_OK = 0, FOS_ERR_ARG = -1, FOS_ERR_HIP = -2, FOS_ERR_STATE = -3, FOS_E
 enum { FOS_F32 = 0, FOS_BF16 = 1 };                    /* element type of A */
 enum { FOS_MODE_FISTA = 0, FOS_MODE_DELTA = 1, FOS_MODE_ISTA = 2 };
 enum { FOS_PROX_L1 = 0, FOS_PROX_ENET = 1 };
-enum { FOS_LOSS_SQUARED = 0, FOS_LOSS_LOGISTIC = 1 };  /* fos_problem_set_loss */
+enum { FOS_LOSS_SQUARED = 0, FOS_LOSS_LOGISTIC = 1, FOS_LOSS_MULTINOMIAL = 2 };  /* fos_problem_set_loss, fos_problem_set_multinomial */
 enum { FOS_STOP_NONE = 0, FOS_STOP_STEP = 1, FOS_STOP_RATIO = 2, FOS_STOP_GRAD = 3, FOS_STOP_LS_STALL = 4 };
 
 enum { FOS_PLAN_NO_RESIDENT = 1, FOS_PLAN_NO_TALL = 2, FOS_PLAN_NO_WIDE = 4, FOS_PLAN_NO_COLBLOCK = 8,
@@ -137,11 +137,37 @@ int fos_problem_set_gbuf(fos_problem* p, float* gbuf);
  *     every single-handle run form, the trial, backtracking and recorded forms, fos_residual_batch with use_b = 0,
  *     fos_residual_batch_rhs, fos_fista_run_multi_rhs, every fos_lbfgs_* entry point on the problem, and
  *     fos_problem_set_comm / _set_comm_cols.
- * FOS_ERR_ARG (checked before any HIP call): null p, an unknown loss.  FOS_ERR_UNSUPPORTED for FOS_LOSS_LOGISTIC on a problem
+ * FOS_ERR_ARG (checked before any HIP call): null p, an unknown loss (FOS_LOSS_MULTINOMIAL is set with
+ * fos_problem_set_multinomial, which takes the number of classes).  FOS_ERR_UNSUPPORTED for FOS_LOSS_LOGISTIC on a problem
  * without b, a sharded one, or a shape without the matrix-core pair (aligned streaming layout, 65..16384 columns).  No buffer
  * depends on the loss; nothing is replanned. */
 int fos_problem_set_loss(fos_problem* p, int loss);
 int fos_problem_get_loss(const fos_problem* p, int* loss);
+/* The multinomial (softmax) loss with `classes` = C classes, 2 <= C <= 16 (FOS_LOSS_MULTINOMIAL; fos_problem_get_loss then
+ * reports it, fos_problem_set_loss itself keeps refusing the value: the loss needs C).  b holds the class index of every row,
+ * 0 .. C-1, as a float; the unknown is one coefficient vector per class and the data term is
+ *   sum_i logsumexp_c(a_i.x_c) - a_i.x_{b_i}     (gradient of class c: A^T (softmax(A X)_c - [b = c]); Hessian <= 1/2 I (x) A^T A).
+ * The 16 columns of the lockstep hold the C class vectors of floor(16 / C) fits: columns s*C .. s*C + C-1 are "segment" s.
+ * On a multinomial problem
+ *   - fos_fista_run_multi and fos_fista_run_multi_folds advance nv / C joint fits: handle s*C + c is class c of segment s.
+ *     Product 1 runs in its plain storing form (the panel's logits), a link kernel turns the panel into the softmax residuals
+ *     in place (csrc/softmax_link.hpp) and product 2 and the updates are the launches of every other lockstep; row weights
+ *     (fos_row_weights_bind), penalty factors and bounds (fos_coord_bind) and the fold mask compose.  FOS_ERR_UNSUPPORTED,
+ *     before any launch or change of handle state, unless nv is a multiple of C, the handles of a segment carry identical
+ *     parameters (and, for folds, identical held ids) and every handle is a plain one: no adaptive restart and no step,
+ *     ratio or gradient tolerance - a stop rule decided per column would break the joint fit;
+ *   - fos_residual_batch (use_b = 1) and fos_residual_batch_folds take nv = a multiple of C columns (FOS_ERR_ARG otherwise;
+ *     for folds also when a segment's held ids differ) and return in out16[s*C] the (weighted; held-out) sum of the loss of
+ *     segment s, 0 in its other entries;
+ *   - every other entry point behaves as on a logistic problem: the loss-free ones (fos_power_iter, fos_gram_apply, plans,
+ *     handles) serve, the rest returns FOS_ERR_UNSUPPORTED before any launch or change of handle state.
+ * The data comes first, the handle second.  FOS_ERR_ARG (checked before any HIP call): null p, classes outside 2..16.
+ * FOS_ERR_UNSUPPORTED under the conditions of fos_problem_set_loss(p, FOS_LOSS_LOGISTIC): no b, a sharded problem, a shape
+ * without the matrix-core pair.  No buffer depends on the loss or on C; nothing is replanned.  fos_problem_get_classes reads C
+ * back (0 on a problem that is not multinomial); fos_problem_set_loss(p, FOS_LOSS_SQUARED / _LOGISTIC) leaves the multinomial
+ * loss again. */
+int fos_problem_set_multinomial(int classes, fos_problem* p);
+int fos_problem_get_classes(int* classes, const fos_problem* p);
 /* Per-row sample weights w_i >= 0 of the data term: sum_i w_i 0.5 (a_i.x - b_i)^2 (gradient A^T (w * (Ax - b))) or, on a
  * logistic problem, sum_i w_i (log(1 + exp(a_i.x)) - b_i a_i.x) (gradient A^T (w * (sigma(Ax) - b))); the penalties are
  * unchanged.  w: m floats on the device, borrowed, 16-byte aligned and readable up to m rounded up to 4 (product 1 fetches the
