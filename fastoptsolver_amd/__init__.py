@@ -8,6 +8,7 @@ from .lbfgs import LBFGSSolver                                        # noqa: F4
 from .logistic import LogisticCVResult, logistic_cv, logistic_objective, logistic_path   # noqa: F401
 from .multinomial import (MultinomialCVResult, multinomial_cv, multinomial_objective, multinomial_path,   # noqa: F401
                           prepare_multinomial)
+from .multitask import multitask_objective, multitask_path         # noqa: F401
 from .objective_functions import compute_objective                    # noqa: F401
 from .operators import ElasticNetProx, L1Prox, LeastSquares           # noqa: F401
 from .prox_operators import prox_elastic_net, prox_l1                 # noqa: F401
@@ -15,4 +16,5 @@ from .prox_operators import prox_elastic_net, prox_l1                 # noqa: F4
 __all__ = ["fista", "fista_delta", "fista_path", "fista_cv", "CVResult", "ista", "estimate_lipschitz", "reset_metrics", "get_metrics", "LBFGSSolver",
            "compute_objective", "prox_l1", "prox_elastic_net", "LeastSquares", "L1Prox", "ElasticNetProx",
            "prepare", "prepare_weighted", "prepare_penalized", "Problem", "FosError", "logistic_path", "logistic_cv", "logistic_objective", "LogisticCVResult",
-           "multinomial_path", "multinomial_cv", "multinomial_objective", "MultinomialCVResult", "prepare_multinomial"]
+           "multinomial_path", "multinomial_cv", "multinomial_objective", "MultinomialCVResult", "prepare_multinomial",
+           "multitask_path", "multitask_objective"]

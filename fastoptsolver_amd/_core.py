@@ -50,6 +50,7 @@ UPLOAD_CHUNK_BYTES = 256 << 20
 LOSSES = {"squared": _lib.LOSS_SQUARED, "logistic": _lib.LOSS_LOGISTIC, "multinomial": _lib.LOSS_MULTINOMIAL}
 MAX_CLASSES = 16                         # a class group of the multinomial lockstep is C of its 16 columns
 LOGIT_MAX_N = 16384                      # device columns the matrix-core pair serves (csrc/fos_plan.hip pair_dd_multi_supported)
+GROUPED_BOUNDS = "the group penalty does not compose with box bounds (lower / upper); penalty factors do"
 LOGIT_MIN_N = {"f32": 68, "bf16": 72}    # the narrowest streaming width: 64 columns plus one 16-byte chunk
 
 
@@ -275,6 +276,7 @@ class Problem:
         self.sample_weight = None
         self._coord = (None, None, None)
         self.penalty_max = 1.0
+        self.grouped = False
         self._bind(b, lib)
         if coord:
             self._set_checked(*coord)
@@ -292,6 +294,7 @@ class Problem:
         sib.A, sib.m, sib.n, sib.n_dev, sib.lda = self.A, self.m, self.n, self.n_dev, self.lda
         sib.device, sib.dtype, sib.loss, sib.sample_weight = self.device, self.dtype, self.loss, None
         sib.classes = self.classes
+        sib.grouped = self.grouped
         if self.loss == "multinomial":              # the sibling's own labels, checked against the same C on the host
             b = checked_labels(b, self.classes)[0]
         sib._coord, sib.penalty_max = (None, None, None), 1.0
@@ -335,6 +338,17 @@ class Problem:
         with self.ctx():
             _lib.check(self.lib.fos_row_weights_bind(ptr(w), self.h), "fos_row_weights_bind")
         self.sample_weight = w
+
+    def set_grouped(self, on=True):
+        """The penalty of a multinomial handle becomes (on) or stops being the group penalty over the classes, alpha1 sum_j p_j
+        ||X[j, :]||_2 + 0.5 alpha2 sum_j p_j ||X[j, :]||_2^2 (`.grouped`; `multinomial_path` / `multinomial_cv` /
+        `multinomial_objective` read it and set fos_fista_params.group = C on every class handle).  Host state only.  ValueError on
+        a handle of another loss and on one with box bounds, with which the group penalty has no composed closed-form prox."""
+        if on and self.loss != "multinomial":
+            raise ValueError(f"the grouped penalty belongs to a multinomial handle; this one has the {self.loss} loss")
+        if on and (self.lower is not None or self.upper is not None):
+            raise ValueError(GROUPED_BOUNDS)
+        self.grouped = bool(on)
 
     def set_penalty(self, penalty_factor=None, lower=None, upper=None):
         """Per-coordinate penalty factors p_j >= 0 and box bounds lower_j <= 0 <= upper_j (fos_coord_bind): the penalties become
@@ -649,12 +663,15 @@ class Fista:
             self.h = None
 
     def reset(self, tau, alpha1, alpha2, mode=_lib.MODE_FISTA, prox_kind=_lib.PROX_L1, delta=0.0,
-              adaptive_restart=False, restart_threshold=1.0, tol_step=0.0, tol_ratio=0.0, tol_grad=0.0, x0=None):
+              adaptive_restart=False, restart_threshold=1.0, tol_step=0.0, tol_ratio=0.0, tol_grad=0.0, x0=None, group=0):
+        """group: 0 (or 1) the separable penalty; G in 2..16 makes this handle one of G consecutive lockstep columns under the
+        row-group penalty alpha1 p_j ||X[j,:]||_2 + 0.5 alpha2 p_j ||X[j,:]||_2^2 (fos_fista_params.group), served by
+        `run_multi` / `run_multi_rhs` / `run_multi_folds` alone."""
         p = self.prm
         p.tau, p.alpha1, p.alpha2, p.delta = float(tau), float(alpha1), float(alpha2), float(delta)
         p.restart_threshold, p.tol_step, p.tol_ratio = float(restart_threshold), float(tol_step), float(tol_ratio)
         p.tol_grad = float(tol_grad)
-        p.mode, p.prox_kind, p.adaptive_restart, p.reserved = int(mode), int(prox_kind), int(bool(adaptive_restart)), 0
+        p.mode, p.prox_kind, p.adaptive_restart, p.group = int(mode), int(prox_kind), int(bool(adaptive_restart)), int(group)
         if x0 is not None:
             x0 = self.prob.vec_in(x0, torch.float64)
         with self.prob.ctx():

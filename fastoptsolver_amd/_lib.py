@@ -20,7 +20,7 @@ class FistaParams(C.Structure):
     _fields_ = [("tau", C.c_double), ("alpha1", C.c_double), ("alpha2", C.c_double), ("delta", C.c_double),
                 ("restart_threshold", C.c_double), ("tol_step", C.c_double), ("tol_ratio", C.c_double),
                 ("tol_grad", C.c_double), ("mode", C.c_int32), ("prox_kind", C.c_int32), ("adaptive_restart", C.c_int32),
-                ("reserved", C.c_int32)]
+                ("group", C.c_int32)]
 
 
 class LineSearchState(C.Structure):

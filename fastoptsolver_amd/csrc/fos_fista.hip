@@ -77,6 +77,7 @@ static void to_dev_params(const fos_fista_params* s, fos::FistaParams* d) {
   d->tol_ratio = s->tol_ratio;
   d->tol_grad = s->tol_grad;
   d->tau_from_state = 0;
+  d->group = s->group;
 }
 
 int fos_fista_reset(fos_fista* f, const fos_fista_params* prm, const double* x0) {
@@ -84,6 +85,8 @@ int fos_fista_reset(fos_fista* f, const fos_fista_params* prm, const double* x0)
   if (prm->mode < 0 || prm->mode > 2 || prm->prox_kind < 0 || prm->prox_kind > 1 || !(prm->tau > 0.0) ||
       prm->tol_grad < 0.0 || prm->tol_step < 0.0 || prm->tol_ratio < 0.0)
     return fail(FOS_ERR_ARG, "fos_fista_reset: bad mode/prox_kind/tau/tolerance");
+  if (prm->group < 0 || prm->group > fos::BT_NV)
+    return fail(FOS_ERR_ARG, "fos_fista_reset: group outside 0..16 (the columns of one group penalty)");
   to_dev_params(prm, &f->prm);
   fos_problem* p = f->p;
   const size_t nb = (size_t)p->n * sizeof(double);
@@ -111,6 +114,17 @@ int fos_fista_set_tau(fos_fista* f, double tau) {
   if (!f || !(tau > 0.0)) return fail(FOS_ERR_ARG, "fos_fista_set_tau: bad argument");
   f->prm.tau = tau;
   f->tau_on_device = false;
+  return FOS_OK;
+}
+
+// The one guard of the entry points that advance or evaluate a single state machine: a handle under the group penalty
+// (fos_fista_params.group >= 2) is one column of a joint fit and its prox needs the other columns, so none of them may answer
+// for it with the separable prox.  Refuses before any launch or change of handle state; the lockstep entry points serve it.
+static bool grouped(const fos::FistaParams& prm) { return prm.group >= 2; }
+static int need_separable(const fos_fista* f, const char* fn) {
+  if (f && grouped(f->prm))
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": not served on a handle under the group penalty (fos_fista_params.group >= 2); "
+                                     "it runs through fos_fista_run_multi / _run_multi_rhs / _run_multi_folds");
   return FOS_OK;
 }
 
@@ -382,6 +396,7 @@ int fos_fista_run_resident(fos_fista* f, int iters, int backtracking, double eta
   if (!f || iters < 0 || !iters_done || !tau_out || (backtracking && !(eta > 0.0 && eta < 1.0)))
     return fail(FOS_ERR_ARG, "fos_fista_run_resident: bad argument");
   if (int rc_ = need_squared(f->p, "fos_fista_run_resident")) return rc_;
+  if (int rc_ = need_separable(f, "fos_fista_run_resident")) return rc_;
   fos_problem* p = f->p;
   if (!p->pass.resident) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_resident: problem does not fit the LDS-resident loop");
   *iters_done = 0;
@@ -412,6 +427,7 @@ int fos_fista_run_history(fos_fista* f, int iters, double* x_hist, double* hist,
   if (!f || iters < 0 || (iters > 0 && (!x_hist || !hist || !work)))
     return fail(FOS_ERR_ARG, "fos_fista_run_history: bad argument");
   if (int rc_ = need_squared(f->p, "fos_fista_run_history")) return rc_;
+  if (int rc_ = need_separable(f, "fos_fista_run_history")) return rc_;
   fos_problem* p = f->p;
   if (plain_run(f) && p->pass.resident) return iters == 0 ? FOS_OK : run_resident(f, iters, x_hist, hist);
   if (!plain_run(f) || p->pass.path != 0 || p->pass.colblock || p->pass.entry->dual == nullptr || p->comm != nullptr)
@@ -454,6 +470,7 @@ int fos_fista_run_history(fos_fista* f, int iters, double* x_hist, double* hist,
 int fos_fista_run(fos_fista* f, int iters) {
   if (!f || iters < 0) return fail(FOS_ERR_ARG, "fos_fista_run: bad argument");
   if (int rc_ = need_squared(f->p, "fos_fista_run")) return rc_;
+  if (int rc_ = need_separable(f, "fos_fista_run")) return rc_;
   fos_problem* p = f->p;
   if (iters == 0) return FOS_OK;
   if (p->pass.resident) return run_resident(f, iters, nullptr, nullptr);
@@ -536,6 +553,7 @@ int fos_problem_set_fused_stamps(fos_problem* p, unsigned long long* stamps) {
 int fos_fista_run_fused(fos_fista* f, int iters) {
   if (!f || iters < 0) return fail(FOS_ERR_ARG, "fos_fista_run_fused: bad argument");
   if (int rc_ = need_squared(f->p, "fos_fista_run_fused")) return rc_;
+  if (int rc_ = need_separable(f, "fos_fista_run_fused")) return rc_;
   fos_problem* p = f->p;
   const int G = p->ncu;
   if (p->dtype != FOS_F32 || p->pass.path != 0 || p->pass.tall || p->pass.colblock || p->pass.resident || p->comm || p->n % 2048 != 0 ||
@@ -593,6 +611,7 @@ int fos_fista_run_fused(fos_fista* f, int iters) {
 int fos_fista_run_chip(fos_fista* f, int iters) {
   if (!f || iters < 0) return fail(FOS_ERR_ARG, "fos_fista_run_chip: bad argument");
   if (int rc_ = need_squared(f->p, "fos_fista_run_chip")) return rc_;
+  if (int rc_ = need_separable(f, "fos_fista_run_chip")) return rc_;
   fos_problem* p = f->p;
   const int nc = p->n <= 8 ? 8 : 16;
   const int64_t cap = fos::cr_rows_cap(nc);
@@ -692,6 +711,11 @@ static fos::MultiUpdate multi_update(fos_fista* const* fs, int nv, bool controll
 // kernel (softmax_link.hpp) turns the panel into softmax(A_panel Y) - onehot(b) in place with the weights and the fold mask
 // applied, and everything after it is the same.  Plain runs only (run_multi_softmax).
 
+// Handles under the group penalty (fos_fista_params.group = G >= 2; checked by group_refusal before they get here): always the
+// two-product form, plain; the G columns of a fit are updated together by the one launch of launch_group_update, in front of
+// the two update sites of the separable penalty.  Penalty factors compose (the factor of a coordinate scales its row's
+// threshold); box bounds do not and are refused.
+
 // Row splits of product 2 in the two-product form: the planned ones, or - on a problem planned for the cluster form, whose slab
 // count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated.
 static int two_product_splits(const fos_problem* p, int* g_splits) {
@@ -727,6 +751,19 @@ static int launch_gram_panel(fos_problem* p, const char* Ap, int64_t rows, int g
   return FOS_OK;
 }
 
+// The update of nv / G joint fits under the group penalty in one launch (fista_update_group_kernel): grid (nupd, nv / G).
+static int launch_group_update(fos_fista* const* fs, int nv, int g_splits, int y_mode) {
+  fos_problem* p = fs[0]->p;
+  const int G = fs[0]->prm.group;
+  const fos::MultiUpdate mu = multi_update(fs, nv, false);
+  int prox_bits = 0;
+  for (int s = 0; s < nv / G; ++s) prox_bits |= (fs[s * G]->prm.prox_kind == fos::PROX_ENET ? 1 : 0) << s;
+  hipLaunchKernelGGL(fos::fista_update_group_kernel, dim3(fs[0]->nupd, nv / G), dim3(256), 0, p->stream, p->multi.slabs16, g_splits,
+                     (int)p->n, mu, G, prox_bits, p->cand.xp, y_mode, p->coord_factor);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
 static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controlled, bool same_family,
                           const float* b16 = nullptr, const uint8_t* fold_of_row = nullptr,
                           const fos::FoldHeld* held = nullptr) {
@@ -747,7 +784,9 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
   const bool coord = has_coord(p);   // fos_coord_bind: the two update launches below take the coordinate kernels
   const fos::CoordData cd{p->coord_factor, p->coord_lo, p->coord_hi};
   const bool softmax = p->loss == FOS_LOSS_MULTINOMIAL;      // the link kernel sits between the two products of every panel
-  const bool two_products = b16 || fold_of_row || logit || weighted || coord;
+  const bool group_penalty = grouped(fs[0]->prm);            // the fits' columns are updated together (launch_group_update)
+  bool two_products = b16 || fold_of_row || logit || weighted || coord;
+  two_products = two_products || group_penalty;
   bool use_cluster = p->multi.cp_cs && !two_products && !softmax;
   int g_splits = p->multi.gram_splits;
   if ((two_products || softmax) && (rc = two_product_splits(p, &g_splits))) return rc;
@@ -815,7 +854,7 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
     // row-sharded problem: the 16 partial gradients (all row splits) are summed over the ranks before the updates
     // (column-sharded: the gradient block is local)
     if (!cols && (rc = reduce_across(p, p->multi.slabs16, (size_t)g_splits * fos::BT_NV * p->n, false))) return rc;
-    if (controlled || same_family) {             // one launch updates all state machines
+    if (group_penalty) { if ((rc = launch_group_update(fs, nv, g_splits, y_mode))) return rc; } else if (controlled || same_family) {             // one launch updates all state machines
       const fos::MultiUpdate mu = multi_update(fs, nv, controlled);
       if (coord)
         hipLaunchKernelGGL(fos::fista_update_multi_coord_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->multi.slabs16,
@@ -900,12 +939,71 @@ static int run_multi_logit(fos_fista* const* fs, int nv, int iters, const uint8_
   return run_multi_mfma(fs, nv, iters, !all_plain, same_family, nullptr, fold_of_row, held);
 }
 
+// What the lockstep serves under the group penalty (fos_fista_params.group = G >= 2), checked before any launch or change of
+// handle state; FOS_OK without a grouped handle.  All handles are grouped with one G, nv is a multiple of G, the G handles of a
+// fit carry identical parameters and hold out one fold (held: HOST ids or null), every handle is a plain run without the fp64
+// split gradient or a device-held step, G is the class count of a multinomial problem, no box bound is bound (group norm plus
+// box has no composed closed-form prox; penalty factors alone compose) and the problem is unsharded with the matrix-core pair.
+static int group_refusal(fos_fista* const* fs, int nv, const int32_t* held, const char* fn) {
+  bool any = false, all = true;
+  for (int v = 0; v < nv; ++v) { any = any || grouped(fs[v]->prm); all = all && grouped(fs[v]->prm); }
+  if (!any) return FOS_OK;
+  const fos_problem* p = fs[0]->p;
+  const int G = fs[0]->prm.group;
+  const char* why = nullptr;
+  if (!all) why = "grouped and ungrouped handles do not mix in one call";
+  else if (nv % G != 0) why = "nv is a multiple of the group size";
+  for (int v = 0; v < nv && !why; ++v) {
+    const fos_fista* f = fs[v];
+    const fos::FistaParams &a = fs[v / G * G]->prm, &c = f->prm;
+    if (a.group != c.group || a.tau != c.tau || a.alpha1 != c.alpha1 || a.alpha2 != c.alpha2 || a.delta != c.delta ||
+        a.mode != c.mode || a.prox_kind != c.prox_kind || (held && held[v] != held[v / G * G]))
+      why = "the handles of a group carry identical parameters and hold out one fold";
+    else if (!plain_run(f) || f->precise || c.tau_from_state)
+      why = "plain runs only (no adaptive restart, no step / ratio / gradient tolerance, no fp64 split gradient, no device-held "
+            "step: a rule decided per column would break the joint fit)";
+  }
+  if (!why && p->loss == FOS_LOSS_MULTINOMIAL && G != p->classes) why = "on a multinomial problem the group size is the class count";
+  if (!why && (p->coord_lo || p->coord_hi))
+    why = "box bounds (fos_coord_bind) do not compose with the group norm; penalty factors alone do";
+  if (!why && (p->comm || p->col_sharded || !pair_dd_multi_supported(p))) why = "an unsharded problem with the matrix-core pair is needed";
+  if (why) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the group penalty (fos_fista_params.group >= 2): " + why);
+  return FOS_OK;
+}
+
+// Joint fits under the group penalty on a squared-loss or logistic problem: nv / G fits of G columns each on the two
+// matrix-core products, for any nv (nv == G == 2 included) - never the VALU multi-vector pass, the cluster form or the
+// single-vector run.  B: the right-hand-side block of fos_fista_run_multi_rhs (the targets of a multi-task fit), which product 1
+// takes for the unweighted squared loss alone; fold_of_row / held: the masks of fos_fista_run_multi_folds.
+static int run_multi_group(fos_fista* const* fs, int nv, int iters, const float* B, int64_t ldb, const uint8_t* fold_of_row,
+                           const int32_t* held_ids, const fos::FoldHeld* held, const char* fn) {
+  fos_problem* p = fs[0]->p;
+  if (int rc = group_refusal(fs, nv, held_ids, fn)) return rc;
+  if (B ? (p->loss != FOS_LOSS_SQUARED || p->row_weight != nullptr) : (!p->b && (fold_of_row || p->loss != FOS_LOSS_SQUARED || p->row_weight)))
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the group penalty (fos_fista_params.group >= 2): a right-hand-side block "
+                                                         "needs the unweighted squared loss, everything else the problem's own b");
+  if (iters == 0) return FOS_OK;
+  if (B) { if (int rc = stage_b16(p, B, ldb, nv)) return rc; }
+  return run_multi_mfma(fs, nv, iters, false, true, B ? p->ws.b16.get() : nullptr, fold_of_row, held);
+}
+static bool any_grouped(fos_fista* const* fs, int nv) {
+  for (int v = 0; v < nv; ++v)
+    if (grouped(fs[v]->prm)) return true;
+  return false;
+}
+// fos_fista_run_multi_rhs: grouped handles on an unweighted squared-loss problem (with or without coordinate data) go to the
+// group route; everything else meets need_squared as before
+static bool group_takes_block(fos_fista* const* fs, int nv) {
+  return any_grouped(fs, nv) && fs[0]->p->loss == FOS_LOSS_SQUARED && fs[0]->p->row_weight == nullptr;
+}
+
 // A multinomial problem: the two matrix-core products with the link kernel between them, for nv / C joint fits of C columns
 // each.  A stop or restart decided per column would break a joint fit, so only plain runs are served, and the columns of a
 // fit share their parameters (and the fold they hold out).
 static int run_multi_softmax(fos_fista* const* fs, int nv, int iters, const uint8_t* fold_of_row, const int32_t* held_ids,
                              const fos::FoldHeld* held, const char* fn) {
   fos_problem* p = fs[0]->p;
+  if (int rc = group_refusal(fs, nv, held_ids, fn)) return rc;     // the grouped form: G = C, no bounds, one G for all
   if (!p->b || p->comm || p->col_sharded || !pair_dd_multi_supported(p))
     return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the multinomial loss needs b, an unsharded problem and the matrix-core pair");
   if (!softmax_groups_ok(p, nv, held_ids))
@@ -919,7 +1017,7 @@ static int run_multi_softmax(fos_fista* const* fs, int nv, int iters, const uint
   for (int v = 0; v < nv; ++v) {
     const fos::FistaParams &a = fs[v / p->classes * p->classes]->prm, &c = fs[v]->prm;
     if (a.tau != c.tau || a.alpha1 != c.alpha1 || a.alpha2 != c.alpha2 || a.delta != c.delta || a.mode != c.mode ||
-        a.prox_kind != c.prox_kind)
+        a.prox_kind != c.prox_kind || a.group != c.group)
       return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the handles of a class group of a multinomial problem carry identical "
                                                            "parameters");
   }
@@ -931,6 +1029,8 @@ static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, in
   fos_problem* p = fs[0]->p;
   const bool rhs = B != nullptr;
   if (p->loss == FOS_LOSS_MULTINOMIAL) return run_multi_softmax(fs, nv, iters, nullptr, nullptr, nullptr, "fos_fista_run_multi");
+  if (any_grouped(fs, nv))
+    return run_multi_group(fs, nv, iters, B, ldb, nullptr, nullptr, nullptr, rhs ? "fos_fista_run_multi_rhs" : "fos_fista_run_multi");
   if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight || has_coord(p))
     return run_multi_logit(fs, nv, iters, nullptr, nullptr, "fos_fista_run_multi");
   if (rhs && (p->comm || p->col_sharded))
@@ -1026,7 +1126,9 @@ int fos_fista_run_multi_rhs(fos_fista* const* fs, int nv, const float* B, int64_
     return fail(FOS_ERR_ARG, "fos_fista_run_multi_rhs: bad argument (null pointer, nv outside 1..16, ldb < nv or iters < 0)");
   for (int v = 0; v < nv; ++v)
     if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi_rhs: handles must share one problem");
-  if (int rc_ = need_squared(fs[0]->p, "fos_fista_run_multi_rhs")) return rc_;
+  // (grouped handles on the unweighted squared loss pass: penalty factors compose with the group penalty, the group route
+  // refuses bounds itself)
+  if (int rc_ = group_takes_block(fs, nv) ? FOS_OK : need_squared(fs[0]->p, "fos_fista_run_multi_rhs")) return rc_;
   return run_multi(fs, nv, iters, B, ldb);
 }
 
@@ -1040,6 +1142,7 @@ int fos_fista_run_multi_folds(fos_fista* const* fs, int nv, int iters, const uin
     if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi_folds: handles must share one problem");
   fos_problem* p = fs[0]->p;
   if (p->loss == FOS_LOSS_MULTINOMIAL) return run_multi_softmax(fs, nv, iters, fold_of_row, held, &hb, "fos_fista_run_multi_folds");
+  if (any_grouped(fs, nv)) return run_multi_group(fs, nv, iters, nullptr, 0, fold_of_row, held, &hb, "fos_fista_run_multi_folds");
   if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight || has_coord(p))
     return run_multi_logit(fs, nv, iters, fold_of_row, &hb, "fos_fista_run_multi_folds");
   if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the problem has no b of its own");
@@ -1093,6 +1196,7 @@ int fos_gram_apply(const float* X, int nv, fos_problem* p, float* G) {
 int fos_fista_grad(fos_fista* f) {
   if (!f) return fail(FOS_ERR_ARG, "fos_fista_grad: null");
   if (int rc_ = need_squared(f->p, "fos_fista_grad")) return rc_;
+  if (int rc_ = need_separable(f, "fos_fista_grad")) return rc_;
   fos_problem* p = f->p;
   int n_rr = 0, rc;
   if (f->precise && !p->pass.resident) {
@@ -1114,6 +1218,7 @@ int fos_fista_grad(fos_fista* f) {
 int fos_fista_grad_dual(fos_fista* f) {
   if (!f) return fail(FOS_ERR_ARG, "fos_fista_grad_dual: null");
   if (int rc_ = need_squared(f->p, "fos_fista_grad_dual")) return rc_;
+  if (int rc_ = need_separable(f, "fos_fista_grad_dual")) return rc_;
   fos_problem* p = f->p;
   int n_rr = 0, rc;
   if ((rc = flush_pending(f))) return rc;
@@ -1141,6 +1246,7 @@ int fos_fista_grad_dual(fos_fista* f) {
 int fos_fista_update(fos_fista* f) {
   if (!f) return fail(FOS_ERR_ARG, "fos_fista_update: null");
   if (int rc_ = need_squared(f->p, "fos_fista_update")) return rc_;
+  if (int rc_ = need_separable(f, "fos_fista_update")) return rc_;
   fos_problem* p = f->p;
   if (plain_run(f) && f->host_valid && !p->col_sharded) {
     // host-driven momentum (see fos_fista_run): no per-iteration bookkeeping launch, y handed on as one fp32 vector
@@ -1155,6 +1261,7 @@ int fos_fista_update(fos_fista* f) {
 int fos_fista_trial(fos_fista* f, double t, int with_residual, double out8[8]) {
   if (!f || !out8 || !(t > 0.0)) return fail(FOS_ERR_ARG, "fos_fista_trial: bad argument");
   if (int rc_ = need_squared(f->p, "fos_fista_trial")) return rc_;
+  if (int rc_ = need_separable(f, "fos_fista_trial")) return rc_;
   fos_problem* p = f->p;
   if (p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_trial: no column-sharded form (||A dlt||^2 needs an m-vector exchange per candidate)");
   { int rcf = flush_pending(f); if (rcf) return rcf; }
@@ -1251,6 +1358,7 @@ int fos_fista_run_backtracking(fos_fista* f, int iters, double eta, double armij
   if (!f || iters < 0 || !(eta > 0.0 && eta < 1.0) || !(grad_eps >= 0.0))
     return fail(FOS_ERR_ARG, "fos_fista_run_backtracking: bad argument");
   if (int rc_ = need_squared(f->p, "fos_fista_run_backtracking")) return rc_;
+  if (int rc_ = need_separable(f, "fos_fista_run_backtracking")) return rc_;
   fos_problem* p = f->p;
   if (!batch_supported(p) || p->pass.resident)
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_backtracking: needs the matrix-core candidate pass (streaming plans)");
@@ -1264,6 +1372,7 @@ int fos_fista_run_recorded(fos_fista* f, int iters, int backtracking, double eta
       (backtracking && (!(eta > 0.0 && eta < 1.0) || !(grad_eps >= 0.0))))
     return fail(FOS_ERR_ARG, "fos_fista_run_recorded: bad argument");
   if (int rc_ = need_squared(f->p, "fos_fista_run_recorded")) return rc_;
+  if (int rc_ = need_separable(f, "fos_fista_run_recorded")) return rc_;
   fos_problem* p = f->p;
   if (p->pass.resident || (backtracking && !batch_supported(p)))
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_recorded: resident problems record inside their one launch; "
@@ -1275,6 +1384,7 @@ int fos_fista_run_recorded(fos_fista* f, int iters, int backtracking, double eta
 int fos_fista_resume_after_stall(fos_fista* f, double* tau_out) {
   if (!f || !tau_out) return fail(FOS_ERR_ARG, "fos_fista_resume_after_stall: null");
   if (int rc_ = need_squared(f->p, "fos_fista_resume_after_stall")) return rc_;
+  if (int rc_ = need_separable(f, "fos_fista_resume_after_stall")) return rc_;
   fos_problem* p = f->p;
   fos::FistaScalars h;
   HIP_TRY(hipMemcpyAsync(&h, f->scal, sizeof(h), hipMemcpyDeviceToHost, p->stream));
@@ -1290,6 +1400,7 @@ int fos_fista_trial_batch(fos_fista* f, double t, double eta, int nv, double* ou
   if (!f || !out || !(t > 0.0) || !(eta > 0.0) || nv < 1 || nv > fos::BT_NV)
     return fail(FOS_ERR_ARG, "fos_fista_trial_batch: bad argument");
   if (int rc_ = need_squared(f->p, "fos_fista_trial_batch")) return rc_;
+  if (int rc_ = need_separable(f, "fos_fista_trial_batch")) return rc_;
   fos_problem* p = f->p;
   { int rcf = flush_pending(f); if (rcf) return rcf; }
   if (!batch_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_trial_batch: needs the fused path");
@@ -1360,6 +1471,11 @@ int fos_fista_run_batch(const void* A, int a_dtype, const float* b, const fos_ba
         q.tol_step < 0.0 || q.tol_ratio < 0.0)
       return fail(FOS_ERR_ARG, "fos_fista_run_batch: bad argument (prm " + std::to_string(i) +
                                    ": mode / prox_kind / tau / tolerance)");
+    if (q.group < 0 || q.group > fos::BT_NV)
+      return fail(FOS_ERR_ARG, "fos_fista_run_batch: bad argument (prm " + std::to_string(i) + ": group outside 0..16)");
+    if (q.group >= 2)
+      return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_batch: the group penalty (fos_fista_params.group >= 2) couples lockstep "
+                                       "columns; a batch member is a problem of its own");
     n_small += items[i].n <= fos::RS_CHUNK && items[i].m <= fos::RS_SMALL_M;
   }
   // SMALL problems (rows of A in registers: run_resident's rule) at [0, n_small), the others after them, each class one

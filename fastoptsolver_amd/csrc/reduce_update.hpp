@@ -52,6 +52,7 @@ struct FistaParams {
   int prox_kind;       // PROX_*
   int adaptive_restart;
   int tau_from_state;  // 1: the update takes the step from FistaScalars::tau (device-driven backtracking), not from `tau`
+  int group;           // 0 / 1: separable penalty; G in 2..16: one of G lockstep columns under the row-group penalty (fos.h)
 };
 
 // ---- candidate / multi-lambda block layouts of the matrix-core kernels (batch_trial.hpp, gram_batch.hpp) -----------
@@ -441,6 +442,122 @@ static __global__ __launch_bounds__(256) void fista_update_multi_coord_kernel(co
   fista_update_body<true, true, true>(slabs + (int64_t)v * n, nslabs, GradSrc{nullptr, nullptr}, n, mu.x_cur[v], mu.x_prev[v],
                                       mu.scal[v], prm, mu.part[v], host_beta, mu.beta[v], nullptr, host_beta ? y_block : nullptr,
                                       mu.beta_next[v], (int64_t)BT_NV * n, y_mode, v, cd);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Group penalty across lockstep columns (fos_fista_params.group = G in 2..16): the G columns s*G .. s*G+G-1 of the lockstep
+// are one fit (the classes of a grouped multinomial model, the targets of a multi-task lasso) and coordinate j is penalised by
+// alpha1 p_j ||X[j,:]||_2 + 0.5 alpha2 p_j ||X[j,:]||_2^2.  The prox is the block soft threshold of row j: with
+// v_c = y_c - tau g_c,  x_next_c = max(0, 1 - tau alpha1 p_j / ||v||_2) v_c  (divided by 1 + tau alpha2 p_j for PROX_ENET); a row
+// with ||v||_2 <= tau alpha1 p_j becomes exactly 0.0 in all G columns.
+//
+// grid (nupd, nv / G), blockIdx.y = the fit; the 64-column block and quad ownership of fista_update_body.  Pass 1 over the
+// columns c of the fit: reduce slab set s*G + c, form y_c, the full gradient and v_c in fp64, add v_c^2 to the owned
+// coordinates' row norms and park v_c in LDS - a register array indexed by c would live in scratch.  Pass 2: scale, write
+// x_prev <- x_cur, x_cur <- x_next, y_{k+1} into slot s*G + c of the candidate block and the four partial sums into column
+// c's own `part`, so the closing bookkeeping and fos_fista_status_get see what the separable update leaves them (xnorm1 is
+// the column's sum |x|, not the group norm).  Plain runs only: beta comes from the host, as do the weights of the fit
+// (taken from its first handle; the dispatcher has checked that the G handles agree).
+//
+// The stash is double[16][4][16] = 8 KiB, indexed [c][e][q]: the 16 owner lanes (one ds_write_b64 / ds_read_b64 lane group)
+// touch 16 consecutive doubles, all 32 / 64 banks once.  A thread reads back only what it wrote, so the stash needs no barrier;
+// the owners are threads 0..15, so the partial sums are sums over wave 0.  With the 4 KiB of the slab reduction a workgroup
+// holds 12 KiB of LDS: at 256 threads the wave slots, not the LDS, bound the workgroups per CU.
+// ---------------------------------------------------------------------------------------------------------
+__device__ inline void write_y_block(float* __restrict__ y_block, int y_mode, int64_t k, int slot, float yn) {
+  if (y_mode == YOUT_XP) {
+    y_block[xp_index(k, slot)] = yn;
+  } else {                                             // bf16 A: three bf16 terms
+    unsigned short* xq = reinterpret_cast<unsigned short*>(y_block);
+    const unsigned short hi = f32_to_bf16_rn(yn);
+    const float r1 = yn - bf16_to_f32(hi);
+    const unsigned short mid = f32_to_bf16_rn(r1);
+    xq[xq_index(k, slot, 0)] = hi;
+    xq[xq_index(k, slot, 1)] = mid;
+    xq[xq_index(k, slot, 2)] = f32_to_bf16_rn(r1 - bf16_to_f32(mid));
+  }
+}
+
+// prox_bits: bit s = the prox kind of fit s (PROX_ENET = 1); factor: the penalty factors of fos_coord_bind or null (all 1)
+static __global__ __launch_bounds__(256) void fista_update_group_kernel(const float* __restrict__ slabs, int nslabs, int n,
+                                                                        MultiUpdate mu, int G, int prox_bits,
+                                                                        float* __restrict__ y_block, int y_mode,
+                                                                        const float* __restrict__ factor) {
+  const int seg = blockIdx.y, v0 = seg * G;
+  if (mu.scal[v0]->stopped != 0) return;
+  __shared__ f32x4 lds[RG][RQ];
+  __shared__ double stash[BT_NV][4][RQ];
+  const int col0 = blockIdx.x * RCOLS;
+  const int q = threadIdx.x % RQ, grp = threadIdx.x / RQ;
+  const int col = col0 + 4 * q;
+  const bool owner = (grp == 0) && (col < n);
+  const int cnt = owner ? (n - col < 4 ? n - col : 4) : 0;      // ragged n (padded slab rows): the last quad is partial
+  const int prox_kind = (prox_bits >> seg) & 1;
+  const double tau = mu.tau[v0], alpha1 = mu.alpha1[v0], alpha2 = mu.alpha2[v0];
+  f32x4 pf4 = {1.f, 1.f, 1.f, 1.f};
+  if (cnt > 0 && factor != nullptr) pf4 = *reinterpret_cast<const f32x4*>(factor + col);
+  double nrm2[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int c = 0; c < G; ++c) {
+    const int v = v0 + c;
+    const f32x4 tot = reduce_slab_block(slabs + (int64_t)v * n, nslabs, n, col0, lds, (int64_t)BT_NV * n);
+    const double* __restrict__ xc_p = mu.x_cur[v];
+    const double* __restrict__ xp_p = mu.x_prev[v];
+    const double beta = mu.beta[v];
+    double g2 = 0.0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (e < cnt) {
+        const double y = form_y(xc_p[col + e], xp_p[col + e], beta);
+        double gf = (double)quad_lane(tot, e);
+        if (prox_kind == PROX_L1 && alpha2 > 0.0) gf += alpha2 * (double)quad_lane(pf4, e) * y;
+        const double vv = y - tau * gf;
+        nrm2[e] += vv * vv;
+        g2 += gf * gf;
+        stash[c][e][q] = vv;
+      }
+    }
+    if (threadIdx.x < 64) {                            // the owners sit in wave 0: sum g_full^2 of this column
+      g2 = wave_sum(g2);
+      if (threadIdx.x == 0) mu.part[v][blockIdx.x * 4 + 1] = g2;
+    }
+    __syncthreads();                                   // the next column's reduction writes `lds` again
+  }
+  if (threadIdx.x >= 64) return;
+  double scale[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const double pe = (double)quad_lane(pf4, e);
+    const double nrm = sqrt(nrm2[e]), thr = tau * alpha1 * pe;
+    double s = alpha1 > 0.0 ? (nrm <= thr ? 0.0 : 1.0 - thr / nrm) : 1.0;     // a NaN norm stays one
+    if (prox_kind == PROX_ENET) s *= 1.0 / (1.0 + tau * (alpha2 * pe));
+    scale[e] = s;
+  }
+  for (int c = 0; c < G; ++c) {
+    const int v = v0 + c;
+    double* __restrict__ xc_p = mu.x_cur[v];
+    double* __restrict__ xp_p = mu.x_prev[v];
+    const double beta_next = mu.beta_next[v];
+    double a0 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (e < cnt) {
+        const double xc = xc_p[col + e];
+        const double xn = scale[e] == 0.0 ? 0.0 : scale[e] * stash[c][e][q];
+        const double d = xn - xc;
+        a0 += d * d;
+        a2 += fabs(xn);
+        a3 += xn * xn;
+        xp_p[col + e] = xc;
+        xc_p[col + e] = xn;
+        write_y_block(y_block, y_mode, col + e, v, (float)form_y(xn, xc, beta_next));
+      }
+    }
+    a0 = wave_sum(a0); a2 = wave_sum(a2); a3 = wave_sum(a3);
+    if (threadIdx.x == 0) {
+      double* part = mu.part[v] + blockIdx.x * 4;
+      part[0] = a0; part[2] = a2; part[3] = a3;
+    }
+  }
 }
 
 // One wave: fold the partials and advance the scalar state.  iterative_solvers.py:204-221, :235-242, :325-342.

@@ -217,7 +217,7 @@ def _pos(v):
 
 
 def _params(tau, alpha1, alpha2, *, mode, prox_kind=_lib.PROX_L1, delta=None, tol=0.0, tol_ratio=0.0, grad_rule=False,
-            adaptive_restart=False, restart_threshold=1.0):
+            adaptive_restart=False, restart_threshold=1.0, group=0):
     """The fields of fos_fista_params from the solvers' arguments, under the names `_core.Fista.reset` and
     `_lib.FistaParams` take them.  `tol` is the step stop and, where `grad_rule` says so, the gradient-norm rule (ref:179) as
     well; momentum restarts exist for FISTA only.  Tolerances reach the device as given: a caller for which a non-positive
@@ -227,6 +227,8 @@ def _params(tau, alpha1, alpha2, *, mode, prox_kind=_lib.PROX_L1, delta=None, to
                prox_kind=int(prox_kind), adaptive_restart=int(bool(adaptive_restart) and mode == _lib.MODE_FISTA))
     if grad_rule:                   # absent means 0.0, off: stand-in states without the rule (CPU tests) never meet the field
         prm["tol_grad"] = float(tol)
+    if group:                       # likewise absent means 0, the separable penalty (fos_fista_params.group)
+        prm["group"] = int(group)
     return prm
 
 

@@ -13,6 +13,17 @@ This is the symmetric (over-parametrised) softmax model glmnet and scikit-learn 
 picks the solution.  A per-class intercept is a constant column with penalty factor 0 (``prepare_penalized``); rows weights
 (``prepare_weighted``) multiply the data term per row.
 
+A grouped handle (``prepare_multinomial(..., grouped=True)`` or ``Problem.set_grouped``; glmnet's ``type.multinomial =
+"grouped"``) replaces the l1 penalty by the group penalty over the classes,
+
+    alpha1 sum_j p_j ||X[j, :]||_2  +  0.5 alpha2 sum_j p_j ||X[j, :]||_2^2 ,
+
+so that a feature is in the model for all C classes or for none: every class handle carries ``group = C``
+(fos_fista_params.group) and the update kernel of the lockstep thresholds row j of X across the C columns of a fit together
+(csrc/reduce_update.hpp, fista_update_group_kernel).  Like the penalty factors and bounds, the choice belongs to the handle:
+``multinomial_path`` / ``multinomial_cv`` / ``multinomial_objective`` keep their signatures and answer with the grouped
+quantities on a grouped handle.  Penalty factors compose with it; box bounds do not (ValueError).  Not served: sparse-group mixtures, groups of coefficients within one column, sharded problems.
+
 The fits of a class group are one joint problem, so only plain runs exist: there is no ``tol_ratio``, ``adaptive_restart`` or
 ``restart_threshold`` here - a stop or restart decided per column would break the fit.
 """
@@ -44,16 +55,23 @@ def pack_groups(count, classes):
     return [(first, min(per, count - first)) for first in range(0, count, per)]
 
 
-def prepare_multinomial(A, y, classes=None, dtype=None, *, sample_weight=None, penalty_factor=None, lower=None, upper=None):
+def prepare_multinomial(A, y, classes=None, dtype=None, *, sample_weight=None, penalty_factor=None, lower=None, upper=None,
+                        grouped=False):
     """``prepare(A, y, loss="multinomial")`` with the number of classes given: ``y`` holds one integral class index 0 .. C-1 per
     row (``classes=None``: C = max(y) + 1), 2 <= C <= 16, checked on the host before any device work (ValueError).  With
     ``sample_weight`` the handle is a weighted one (``prepare_weighted``), with ``penalty_factor`` / ``lower`` / ``upper`` one
     with per-coefficient penalty factors and box bounds (``prepare_penalized``; they belong to the coefficient's row of X and
     hold for every class).  Pass the handle as ``A`` (``y`` None) to ``multinomial_path`` / ``multinomial_cv`` /
-    ``multinomial_objective``; ``.classes`` is C."""
+    ``multinomial_objective``; ``.classes`` is C.  ``grouped=True``: the penalty of the handle is the group penalty over the
+    classes (module docstring; ``.grouped``, ``Problem.set_grouped``) - with ``lower`` / ``upper`` a ValueError, before any
+    device work."""
     if isinstance(A, _core.Problem):
         raise ValueError("prepare_multinomial binds an array or tensor; this is already a Problem")
-    return _core.Problem.multinomial(A, y, classes, dtype, sample_weight, penalty_factor, lower, upper)
+    if grouped and (lower is not None or upper is not None):
+        raise ValueError(_core.GROUPED_BOUNDS)
+    prob = _core.Problem.multinomial(A, y, classes, dtype, sample_weight, penalty_factor, lower, upper)
+    prob.set_grouped(grouped)
+    return prob
 
 
 def _problem(A, y, classes, dtype):
@@ -73,10 +91,21 @@ def _lipschitz(prob, L):
     return float(L) if L is not None else _its.estimate_lipschitz(prob) / 2.0
 
 
-def _params_of(prob, alphas, L, t_init_factor, delta):
+def _grouped(prob):
+    """Whether the handle carries the group penalty.  The group penalty and box bounds have no composed closed-form prox: a
+    grouped handle that has been given bounds since is refused on the host, before any device work."""
+    grouped = bool(getattr(prob, "grouped", False))
+    if grouped and (prob.lower is not None or prob.upper is not None):
+        raise ValueError(_core.GROUPED_BOUNDS)
+    return grouped
+
+
+def _params_of(prob, alphas, L, t_init_factor, delta, grouped=False):
     L_val = _lipschitz(prob, L)
     mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
-    return [_its._params(_its._tau(L_val, a2, t_init_factor, prob.penalty_max), a1, a2, mode=mode, delta=delta) for a1, a2 in alphas]
+    group = prob.classes if grouped else 0
+    return [_its._params(_its._tau(L_val, a2, t_init_factor, prob.penalty_max), a1, a2, mode=mode, delta=delta, group=group)
+            for a1, a2 in alphas]
 
 
 def _class_handles(prob, prms):
@@ -123,11 +152,15 @@ def multinomial_path(A, y, alphas, classes=None, t_init_factor: float = 1.0, max
     X0 = 0 with that step for exactly ``max_iter`` iterations.  No stopping rule and no momentum restart: the columns of a fit
     are one joint problem.  A: an array / tensor (padded on the device as a logistic problem is; at most 16384 device columns)
     or a ``prepare(A, y, loss="multinomial")`` / ``prepare_multinomial`` handle (``y`` may then be None), weighted or penalised
-    handles included."""
+    handles included.
+
+    A grouped handle (``prepare_multinomial(..., grouped=True)``): the group penalty over the classes (module docstring)
+    instead of the l1 penalty - row j of every result is zero in all C classes or in none.  Same step, same contract; a grouped
+    handle with box bounds raises ValueError."""
     _its.reset_metrics()
     alphas = _check_path_args(alphas, delta)
     prob = _problem(A, y, classes, dtype)
-    X, info = _run_groups(prob, _params_of(prob, alphas, L, t_init_factor, delta), max_iter)
+    X, info = _run_groups(prob, _params_of(prob, alphas, L, t_init_factor, delta, _grouped(prob)), max_iter)
     xs = [_core.from_device_vec(X[:, :, a], prob.like) for a in range(len(alphas))]
     return (xs, info) if return_info else xs
 
@@ -147,17 +180,21 @@ def multinomial_cv(A, y, alphas, folds=5, classes=None, t_init_factor: float = 1
     cross-entropy (K x L float64 ndarray; on a weighted handle the weighted sum over the held-out weight sum), ``mean_logloss``
     its mean over the folds, ``best`` the argmin (first on ties), ``x`` the n x C fit on all rows at ``alphas[best]``
     (``refit=True``; else None), ``coefs`` the n x C x K x L fits (``return_coefs=True``; else None), ``info[f][a] =
-    (iterations, stop_code)``."""
+    (iterations, stop_code)``.
+
+    A grouped handle: every fit (the refit included) carries the group penalty over the classes, as in ``multinomial_path``;
+    the held-out score is the same cross-entropy."""
     _its.reset_metrics()
     alphas = _check_path_args(alphas, delta)
     m = A.m if isinstance(A, _core.Problem) else int(A.shape[0] if hasattr(A, "shape") else np.shape(A)[0])
     ids, sizes = _its._cv_folds(folds, m)
     K, La = len(sizes), len(alphas)
     prob = _problem(A, y, classes, dtype)
+    grouped = _grouped(prob)
     C = prob.classes
     if _its._weighted(prob):         # weighted held-out sums over the held-out weight sums; a zero-weight fold raises here
         sizes = _its._cv_weight_sums(prob, ids, K)
-    prms = _params_of(prob, alphas, L, t_init_factor, delta)
+    prms = _params_of(prob, alphas, L, t_init_factor, delta, grouped)
     pairs = [(f, a) for f in range(K) for a in range(La)]
     ids_dev = _core.fold_ids_tensor(ids, prob.device)
     X = torch.zeros(prob.n, C, K, La, dtype=torch.float64, device=prob.device)
@@ -199,8 +236,10 @@ def multinomial_objective(X, A, y, alpha1, alpha2):
     (fos_residual_batch on a multinomial problem; X is rounded to fp32 for the pass over A; weighted per row on a weighted
     handle).  ``X``: n x C (returns a float) or an n x C x k block (returns k float64 values), floor(16 / C) members per pass.
     Synchronises.  On a handle with penalty factors the penalties are the factored ones, alpha1 sum_j p_j sum_c |x_jc| + 0.5
-    alpha2 sum_j p_j sum_c x_jc^2 (the fp32 factors as bound); the box is not checked."""
+    alpha2 sum_j p_j sum_c x_jc^2 (the fp32 factors as bound); the box is not checked.  On a grouped handle the l1 term is the
+    group penalty alpha1 sum_j p_j ||X[j, :]||_2 (the row norms over the classes, with the factors)."""
     prob = _problem(A, y, None, None)
+    grouped = _grouped(prob)
     C = prob.classes
     xt = X.detach() if _core.is_tensor(X) else torch.from_numpy(np.asarray(X, dtype=np.float64))
     single = xt.dim() == 2
@@ -214,6 +253,7 @@ def multinomial_objective(X, A, y, alpha1, alpha2):
         nll += prob.residual_batch(block, use_b=True)[::C]
     Xh = Xd.cpu().numpy()
     pf = np.ones(prob.n) if prob.penalty_factor is None else prob.penalty_factor.to("cpu", torch.float64).numpy()
-    val = (np.asarray(nll, dtype=np.float64) + float(alpha1) * (pf[:, None, None] * np.abs(Xh)).sum(axis=(0, 1)) +
+    l1 = (pf[:, None] * np.sqrt((Xh * Xh).sum(axis=1))).sum(axis=0) if grouped else (pf[:, None, None] * np.abs(Xh)).sum(axis=(0, 1))
+    val = (np.asarray(nll, dtype=np.float64) + float(alpha1) * l1 +
            0.5 * float(alpha2) * (pf[:, None, None] * Xh * Xh).sum(axis=(0, 1)))
     return float(val[0]) if single else val

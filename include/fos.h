@@ -69,7 +69,16 @@ typedef struct fos_fista_params {
   int32_t mode;             /* FOS_MODE_*                                                         */
   int32_t prox_kind;        /* FOS_PROX_L1: l2 in the gradient; FOS_PROX_ENET: l2 in the prox     */
   int32_t adaptive_restart; /*                                             :209                   */
-  int32_t reserved;
+  int32_t group;            /* 0 or 1: the separable penalty.  G in 2..16: this handle is one of G consecutive lockstep
+                               columns (fos_fista_run_multi / _run_multi_rhs / _run_multi_folds) whose coefficients of one
+                               coordinate j are penalised together by their Euclidean norm,
+                                   alpha1 p_j ||X[j,:]||_2 + 0.5 alpha2 p_j ||X[j,:]||_2^2
+                               (grouped multinomial, multi-task lasso): the update is the block soft threshold of row j
+                               across the G columns.  Served by the two-product matrix-core lockstep alone, for plain runs
+                               whose G handles carry identical parameters (and hold out one fold), nv a multiple of G, on an
+                               unsharded problem without box bounds (penalty factors compose; G = the class count on a
+                               multinomial problem); every other entry point refuses such a handle
+                               (FOS_ERR_UNSUPPORTED).  Outside 0..16: FOS_ERR_ARG from fos_fista_reset.                */
 } fos_fista_params;
 
 /* Host copy of the device-resident loop state (fos_fista_status synchronises). */
@@ -77,7 +86,7 @@ typedef struct fos_fista_status {
   double t_prev, beta, this_step, prev_step, ratio;
   double rr;        /* ||A y - b||^2 of the last gradient   */
   double gnorm2;    /* ||grad_smooth(y)||^2 of the last update */
-  double xnorm1;    /* ||x_k||_1   */
+  double xnorm1;    /* ||x_k||_1 (of this handle's column, also under a group penalty: not the group norm) */
   double xnorm2;    /* ||x_k||_2^2 */
   double rr_x;      /* ||A x_k - b||^2 at the iterate the last fos_fista_grad_dual started from */
   double tau;       /* device-driven backtracking: the step after the last search (fos_fista_run_backtracking) */
