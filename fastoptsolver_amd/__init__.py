@@ -1,6 +1,6 @@
 """fastoptsolver_amd — MI355X-native inner loops (FISTA / ISTA / FISTA-Δ / L-BFGS) behind the call signatures
 of ElBaldo1/FastOptSolver.  Hand-written HIP for gfx950 through a C ABI (include/fos.h); no CPU fallback."""
-from ._core import Problem, prepare, prepare_weighted, prepare_penalized                               # noqa: F401
+from ._core import Problem, prepare, prepare_grouped, prepare_weighted, prepare_penalized                               # noqa: F401
 from ._lib import FosError                                            # noqa: F401
 from .iterative_solvers import (CVResult, estimate_lipschitz, fista, fista_cv, fista_delta, fista_path,  # noqa: F401
                                 get_metrics, ista, reset_metrics)
@@ -9,7 +9,7 @@ from .logistic import LogisticCVResult, logistic_cv, logistic_objective, logisti
 from .multinomial import (MultinomialCVResult, multinomial_cv, multinomial_objective, multinomial_path,   # noqa: F401
                           prepare_multinomial)
 from .multitask import multitask_objective, multitask_path         # noqa: F401
-from .objective_functions import compute_objective                    # noqa: F401
+from .objective_functions import compute_objective, group_lasso_objective                    # noqa: F401
 from .operators import ElasticNetProx, L1Prox, LeastSquares           # noqa: F401
 from .prox_operators import prox_elastic_net, prox_l1                 # noqa: F401
 
@@ -17,4 +17,4 @@ __all__ = ["fista", "fista_delta", "fista_path", "fista_cv", "CVResult", "ista",
            "compute_objective", "prox_l1", "prox_elastic_net", "LeastSquares", "L1Prox", "ElasticNetProx",
            "prepare", "prepare_weighted", "prepare_penalized", "Problem", "FosError", "logistic_path", "logistic_cv", "logistic_objective", "LogisticCVResult",
            "multinomial_path", "multinomial_cv", "multinomial_objective", "MultinomialCVResult", "prepare_multinomial",
-           "multitask_path", "multitask_objective"]
+           "multitask_path", "multitask_objective", "prepare_grouped", "group_lasso_objective"]

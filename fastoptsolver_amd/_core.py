@@ -1,6 +1,7 @@
 """Device-side plumbing: tensors in, C-ABI handles out.  torch is used for device memory, streams and
 events only; every arithmetic operation on the hot path is a HIP kernel behind include/fos.h."""
 import ctypes as C
+import collections
 import math
 
 import numpy as np
@@ -147,6 +148,50 @@ def checked_coord(penalty_factor, lower, upper, n):
     return pf, lo, hi
 
 
+FeatureGroups = collections.namedtuple("FeatureGroups", "start weight l1_ratio")
+
+
+def checked_feature_groups(groups, group_weight, l1_ratio, n):
+    """The feature groups of `Problem.set_feature_groups` as (start, weight, l1_ratio): start the ngroups + 1 boundaries (int32
+    ndarray, start[0] = 0, start[-1] = n), weight ngroups float64 values (sqrt(size) where none are given), l1_ratio a float in
+    [0, 1].  groups: n labels whose equal labels are contiguous, or positive sizes summing to n (a sequence of n entries is read
+    as labels).  ValueError otherwise.  Checked on the host, before any device work."""
+    g = np.asarray(groups.detach().cpu().numpy() if is_tensor(groups) else groups)
+    if g.ndim != 1 or g.shape[0] < 1:
+        raise ValueError(f"groups: n = {n} labels or a sequence of group sizes expected, got shape {g.shape}")
+    if g.shape[0] == n:                                  # labels
+        change = np.flatnonzero(g[1:] != g[:-1]) + 1
+        start = np.concatenate(([0], change, [n]))
+        first = g[start[:-1]]
+        if len(set(first.tolist())) != len(first):
+            raise ValueError("groups: a label reappears after a gap - the columns of a group must be contiguous: permute the "
+                             "columns of A so that every group is one block")
+    else:                                                # sizes
+        if g.dtype.kind not in "iu" and not (g.dtype.kind == "f" and np.all(np.isfinite(g)) and np.all(g == np.floor(g))):
+            raise ValueError("groups: integer group sizes expected")
+        sizes = g.astype(np.int64)
+        if (sizes < 1).any() or int(sizes.sum()) != n:
+            raise ValueError(f"groups: {g.shape[0]} entries are neither n = {n} labels nor positive sizes summing to n "
+                             f"(sum {int(sizes.sum())})")
+        start = np.concatenate(([0], np.cumsum(sizes)))
+    start = start.astype(np.int32)
+    ngroups = len(start) - 1
+    if group_weight is None:
+        w = np.sqrt(np.diff(start).astype(np.float64))
+    else:
+        w = np.asarray(group_weight.detach().cpu().numpy() if is_tensor(group_weight) else group_weight, dtype=np.float64)
+        if w.ndim == 0:
+            w = np.full(ngroups, float(w))
+        if w.ndim != 1 or w.shape[0] != ngroups:
+            raise ValueError(f"group_weight must be a scalar or have one entry per group ({ngroups}), got shape {w.shape}")
+        if not (np.isfinite(w) & (w >= 0)).all():
+            raise ValueError("group_weight must be finite and >= 0")
+    r = float(l1_ratio)
+    if not (0.0 <= r <= 1.0):                            # NaN fails too
+        raise ValueError(f"l1_ratio must lie in [0, 1], got {l1_ratio!r}")
+    return start, w, r
+
+
 class Like:
     """What the caller handed in (so results come back as the same kind) without keeping the object alive."""
 
@@ -210,14 +255,22 @@ class Problem:
         prob._setup(A, y, dtype, None, "multinomial", sample_weight, penalty_factor, lower, upper, classes)
         return prob
 
-    def _setup(self, A, b, dtype, pad, loss, sample_weight, penalty_factor=None, lower=None, upper=None, classes=None):
+    @classmethod
+    def grouped_features(cls, A, b, groups, group_weight=None, l1_ratio=0.0, dtype=None, loss="squared", sample_weight=None):
+        """The handle of a problem with feature groups (`prepare_grouped`): the constructor that takes them."""
+        prob = cls.__new__(cls)
+        prob._setup(A, b, dtype, None, loss, sample_weight, feature_groups=(groups, group_weight, l1_ratio))
+        return prob
+
+    def _setup(self, A, b, dtype, pad, loss, sample_weight, penalty_factor=None, lower=None, upper=None, classes=None,
+               feature_groups=None):
         """__init__, and with penalty_factor / lower / upper (`prepare_penalized`; `set_penalty`, fos_coord_bind) the handle of a
         problem with per-coordinate penalty factors and box bounds: it runs on the matrix-core pair alone too and is padded by
         the rules of a logistic problem."""
         if loss not in LOSSES:
             raise ValueError(f"loss: one of {sorted(LOSSES)} expected, got {loss!r}")
         coord = any(v is not None for v in (penalty_factor, lower, upper))
-        pair_only = loss != "squared" or sample_weight is not None or coord       # served by the matrix-core pair alone
+        pair_only = loss != "squared" or sample_weight is not None or coord or feature_groups is not None   # served by the matrix-core pair alone
         self.classes = None
         if loss == "multinomial":                                        # before any device work
             if isinstance(b, Problem) or isinstance(A, Problem):
@@ -227,6 +280,10 @@ class Problem:
             raise ValueError('classes belongs to loss="multinomial"')
         if coord:                                                        # before any device work
             coord = checked_coord(penalty_factor, lower, upper, int(A.shape[1] if hasattr(A, "shape") else np.shape(A)[1]))
+        if feature_groups is not None:                                   # before any device work
+            if coord or loss == "multinomial":
+                raise ValueError("feature groups compose with neither penalty factors / bounds nor the multinomial loss")
+            feature_groups = checked_feature_groups(*feature_groups, int(A.shape[1] if hasattr(A, "shape") else np.shape(A)[1]))
         if sample_weight is not None:                                    # before any device work
             sample_weight = checked_weights(sample_weight, int(A.shape[0] if hasattr(A, "shape") else np.shape(A)[0]))
         require_gpu()
@@ -277,9 +334,12 @@ class Problem:
         self._coord = (None, None, None)
         self.penalty_max = 1.0
         self.grouped = False
+        self._fgroups = None
         self._bind(b, lib)
         if coord:
             self._set_checked(*coord)
+        if feature_groups is not None:
+            self._bind_feature_groups(*feature_groups)
         if sample_weight is not None:
             # zero-padded to a multiple of 4 entries: product 1 fetches the weights of 4 rows with one 16-byte load
             buf = torch.zeros((m + 3) // 4 * 4, dtype=torch.float32, device=self.device)
@@ -298,7 +358,10 @@ class Problem:
         if self.loss == "multinomial":              # the sibling's own labels, checked against the same C on the host
             b = checked_labels(b, self.classes)[0]
         sib._coord, sib.penalty_max = (None, None, None), 1.0
+        sib._fgroups = None
         sib._bind(b, self.lib)
+        if self._fgroups is not None:               # the columns are the same columns: the library copies the table again
+            sib._bind_feature_groups(*self._fgroups)
         if self.has_coord:                          # the columns are the same columns: the device vectors are shared
             sib._bind_coord(self._coord, self.penalty_max)
         if self.sample_weight is not None:          # the rows are the same rows: a sibling of a weighted handle is weighted
@@ -377,6 +440,49 @@ class Problem:
             _lib.check(self.lib.fos_coord_bind(ptr(bufs[0]), ptr(bufs[1]), ptr(bufs[2]), self.h), "fos_coord_bind")
         self._coord = tuple(bufs)                   # the device vectors live as long as the handle borrows them
         self.penalty_max = float(penalty_max) if bufs[0] is not None else 1.0
+
+    def set_feature_groups(self, groups, group_weight=None, l1_ratio=0.0):
+        """Feature groups of the fit (fos_feature_groups_bind): the penalty becomes alpha1 [(1 - l1_ratio) sum_g w_g ||x_g||_2 +
+        l1_ratio ||x||_1] + 0.5 alpha2 ||x||_2^2 - the group lasso (l1_ratio = 0), the sparse-group lasso, the plain lasso
+        (l1_ratio = 1).  groups: n labels whose equal labels are contiguous (a label that reappears after a gap is a ValueError:
+        permute the columns), or positive sizes summing to n; None detaches.  group_weight: one w_g >= 0 per group (a scalar
+        broadcasts), None for sqrt(size); w_g = 0 keeps a group - an intercept column - out of the group term.  Checked on the
+        host before any device work.  The handle then runs on the matrix-core lockstep alone (``fista_path`` / ``fista_cv`` /
+        ``logistic_path`` / ``logistic_cv``) with the step of the separable penalty; every other solver refuses it, and so does
+        the library where the handle carries penalty factors or bounds, is multinomial, sharded or of a shape without the
+        matrix-core pair (FosError)."""
+        if groups is None:
+            with self.ctx():
+                _lib.check(self.lib.fos_feature_groups_bind(None, None, 0, 0.0, self.h), "fos_feature_groups_bind")
+            self._fgroups = None
+            return
+        self._bind_feature_groups(*checked_feature_groups(groups, group_weight, l1_ratio, self.n))
+
+    def _bind_feature_groups(self, start, weight, l1_ratio):
+        """set_feature_groups with what checked_feature_groups returned.  The zero columns the device copy of A is padded with
+        form one more group of weight 0: they stay exactly zero."""
+        s, w = start, weight
+        if self.n_dev > self.n:
+            s, w = np.concatenate((start, [self.n_dev])).astype(np.int32), np.concatenate((weight, [0.0]))
+        s = np.ascontiguousarray(s, dtype=np.int32)
+        w32 = np.ascontiguousarray(w, dtype=np.float32)
+        with self.ctx():
+            _lib.check(self.lib.fos_feature_groups_bind(s.ctypes.data_as(C.POINTER(C.c_int32)), w32.ctypes.data_as(C.POINTER(C.c_float)),
+                                                        len(s) - 1, float(l1_ratio), self.h), "fos_feature_groups_bind")
+        self._fgroups = (np.array(start, dtype=np.int32), np.array(weight, dtype=np.float64), float(l1_ratio))
+
+    @property
+    def has_feature_groups(self):
+        return getattr(self, "_fgroups", None) is not None
+
+    @property
+    def feature_groups(self):
+        """The bound feature groups as FeatureGroups(start, weight, l1_ratio) - ngroups + 1 boundaries, the weights as given (fp64;
+        the device holds them in fp32) - or None."""
+        if not self.has_feature_groups:
+            return None
+        start, weight, ratio = self._fgroups
+        return FeatureGroups(start.copy(), weight.copy(), ratio)
 
     @property
     def has_coord(self):
@@ -631,6 +737,29 @@ def prepare_penalized(A, b, penalty_factor=None, lower=None, upper=None, dtype=N
     if penalty_factor is None and lower is None and upper is None:
         raise ValueError("penalty_factor, lower or upper is needed")
     return Problem.penalized(A, b, penalty_factor, lower, upper, dtype, loss, sample_weight)
+
+
+def prepare_grouped(A, b, groups, group_weight=None, l1_ratio=0.0, dtype=None, *, loss="squared", sample_weight=None):
+    """``prepare`` with feature groups: the group lasso of Yuan & Lin over groups of coordinates of one fit (the dummy columns of a
+    categorical variable, a spline basis, a gene set) and, with ``l1_ratio`` > 0, the sparse-group lasso of Simon et al.:
+
+        data term + alpha1 [ (1 - l1_ratio) sum_g w_g ||x_g||_2 + l1_ratio ||x||_1 ] + 0.5 alpha2 ||x||_2^2
+
+    with the squared or (``loss="logistic"``) the logistic data term, weighted per row with ``sample_weight``.  ``groups``: n
+    labels whose equal labels are contiguous, or positive group sizes summing to n; ``group_weight``: one w_g >= 0 per group,
+    None for sqrt(size), 0 for a group outside the group term (an intercept).  The groups belong to the handle
+    (``.feature_groups``; ``Problem.set_feature_groups`` rebinds or detaches): pass it as ``A`` (``b`` None) to ``fista_path`` /
+    ``fista_cv`` (squared loss) or ``logistic_path`` / ``logistic_cv``, which then run on the matrix-core lockstep alone with the
+    step t_init_factor / (L + alpha2); every other solver refuses the handle.  Padded as a logistic problem is (at most 16384
+    device columns).  ValueError, before any device work, for labels that are not contiguous, sizes that do not sum to n, a wrong
+    number of weights, a weight that is not finite and >= 0 or an l1_ratio outside [0, 1]."""
+    if isinstance(A, Problem):
+        raise ValueError("prepare_grouped binds an array or tensor; on a Problem use its set_feature_groups")
+    if b is None:
+        raise ValueError("a problem with feature groups needs b")
+    if groups is None:
+        raise ValueError("groups is needed")
+    return Problem.grouped_features(A, b, groups, group_weight, l1_ratio, dtype, loss, sample_weight)
 
 
 def as_problem(A, b, dtype=None):

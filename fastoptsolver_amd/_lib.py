@@ -158,6 +158,13 @@ class FosError(RuntimeError):
     pass
 
 
+# include/fos_feature_groups.h: the entry points declared beside fos.h (SIGNATURES is the table of fos.h itself)
+FEATURE_GROUP_SIGNATURES = {
+    "fos_feature_groups_bind": (_i32, [C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int32, C.c_double, _vp]),
+    "fos_feature_groups_get": (_i32, [C.POINTER(C.c_int32), C.POINTER(C.c_double), _vp]),
+}
+
+
 def load():
     """Return the loaded CDLL (cached).  Raises FosError if the library is absent."""
     global _lib
@@ -168,7 +175,7 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension is the only compute path of fastoptsolver_amd.\n"
             "Build it with:  python -m fastoptsolver_amd.build   (needs hipcc; cross-compiles for gfx950)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **FEATURE_GROUP_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

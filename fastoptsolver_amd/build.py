@@ -18,6 +18,7 @@ SOURCES = [os.path.join(CSRC, u + ".hip") for u in UNITS]
 SRC = SOURCES[0]                       # (kept for callers that want "a" source of the library)
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
 HEADERS.append(os.path.join(os.path.dirname(HERE), "include", "fos.h"))
+HEADERS.append(os.path.join(os.path.dirname(HERE), "include", "fos_feature_groups.h"))
 DEPS = SOURCES + HEADERS
 OBJ_DIR = os.path.join(CSRC, "build")
 OUT = os.path.join(HERE, "libfos_hip.so")

@@ -764,6 +764,30 @@ static int launch_group_update(fos_fista* const* fs, int nv, int g_splits, int y
   return FOS_OK;
 }
 
+// The update on a problem with feature groups (fos_feature_groups_bind) in three launches (reduce_update.hpp): u and the
+// gradient partial over (nupd, nv), the group norms with one wave per (group, column), the scaling over (nupd, nv) again.  One
+// MultiUpdate serves all three: a plain run's momentum step is advanced once.  The prox kind travels per column, so a plain run
+// of mixed families takes the same launches.
+static int launch_fgroup_update(fos_fista* const* fs, int nv, int g_splits, int y_mode, bool controlled) {
+  fos_problem* p = fs[0]->p;
+  const fos::MultiUpdate mu = multi_update(fs, nv, controlled);
+  int prox_bits = 0;
+  for (int v = 0; v < nv; ++v) prox_bits |= (fs[v]->prm.prox_kind == fos::PROX_ENET ? 1 : 0) << v;
+  const fos::FeatureGroupData fg{p->fg.start, p->fg.weight, p->fg.of_coord, p->fg.u, p->fg.nrm2, p->fg.ngroups, (p->n + 3) / 4 * 4,
+                                 p->fg.l1_mix};
+  const int host_beta = controlled ? 0 : 1;
+  hipLaunchKernelGGL(fos::fgroup_form_u_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->multi.slabs16, g_splits, (int)p->n,
+                     mu, prox_bits, host_beta, fg);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(fos::fgroup_norm_kernel, dim3((fg.ngroups + fos::FG_WAVES - 1) / fos::FG_WAVES, nv), dim3(64 * fos::FG_WAVES), 0,
+                     p->stream, mu, fg);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(fos::fgroup_scale_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, (int)p->n, mu, prox_bits, p->cand.xp,
+                     y_mode, host_beta, fg);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
 static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controlled, bool same_family,
                           const float* b16 = nullptr, const uint8_t* fold_of_row = nullptr,
                           const fos::FoldHeld* held = nullptr) {
@@ -787,6 +811,8 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
   const bool group_penalty = grouped(fs[0]->prm);            // the fits' columns are updated together (launch_group_update)
   bool two_products = b16 || fold_of_row || logit || weighted || coord;
   two_products = two_products || group_penalty;
+  const bool fgroup = has_fgroups(p);                        // fos_feature_groups_bind: the update is launch_fgroup_update
+  two_products = two_products || fgroup;
   bool use_cluster = p->multi.cp_cs && !two_products && !softmax;
   int g_splits = p->multi.gram_splits;
   if ((two_products || softmax) && (rc = two_product_splits(p, &g_splits))) return rc;
@@ -854,6 +880,7 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
     // row-sharded problem: the 16 partial gradients (all row splits) are summed over the ranks before the updates
     // (column-sharded: the gradient block is local)
     if (!cols && (rc = reduce_across(p, p->multi.slabs16, (size_t)g_splits * fos::BT_NV * p->n, false))) return rc;
+    if (fgroup) { if ((rc = launch_fgroup_update(fs, nv, g_splits, y_mode, controlled))) return rc; } else   // (never with group_penalty)
     if (group_penalty) { if ((rc = launch_group_update(fs, nv, g_splits, y_mode))) return rc; } else if (controlled || same_family) {             // one launch updates all state machines
       const fos::MultiUpdate mu = multi_update(fs, nv, controlled);
       if (coord)
@@ -967,6 +994,7 @@ static int group_refusal(fos_fista* const* fs, int nv, const int32_t* held, cons
   if (!why && (p->coord_lo || p->coord_hi))
     why = "box bounds (fos_coord_bind) do not compose with the group norm; penalty factors alone do";
   if (!why && (p->comm || p->col_sharded || !pair_dd_multi_supported(p))) why = "an unsharded problem with the matrix-core pair is needed";
+  if (!why && has_fgroups(p)) why = "feature groups (fos_feature_groups_bind) are bound; the two group norms do not compose";
   if (why) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the group penalty (fos_fista_params.group >= 2): " + why);
   return FOS_OK;
 }
@@ -1033,6 +1061,7 @@ static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, in
     return run_multi_group(fs, nv, iters, B, ldb, nullptr, nullptr, nullptr, rhs ? "fos_fista_run_multi_rhs" : "fos_fista_run_multi");
   if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight || has_coord(p))
     return run_multi_logit(fs, nv, iters, nullptr, nullptr, "fos_fista_run_multi");
+  if (has_fgroups(p)) return run_multi_logit(fs, nv, iters, nullptr, nullptr, "fos_fista_run_multi");   // (a block B met need_squared)
   if (rhs && (p->comm || p->col_sharded))
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs: row- or column-sharded problems are not served");
   if (nv == 1) {
@@ -1145,6 +1174,7 @@ int fos_fista_run_multi_folds(fos_fista* const* fs, int nv, int iters, const uin
   if (any_grouped(fs, nv)) return run_multi_group(fs, nv, iters, nullptr, 0, fold_of_row, held, &hb, "fos_fista_run_multi_folds");
   if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight || has_coord(p))
     return run_multi_logit(fs, nv, iters, fold_of_row, &hb, "fos_fista_run_multi_folds");
+  if (has_fgroups(p)) return run_multi_logit(fs, nv, iters, fold_of_row, &hb, "fos_fista_run_multi_folds");
   if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the problem has no b of its own");
   if (p->comm || p->col_sharded)
     return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: row- or column-sharded problems are not served");

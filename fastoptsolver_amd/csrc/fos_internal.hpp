@@ -17,6 +17,7 @@
 // the library is built with -fvisibility=hidden: only what include/fos.h declares is exported
 #pragma GCC visibility push(default)
 #include "../../include/fos.h"
+#include "../../include/fos_feature_groups.h"
 #pragma GCC visibility pop
 #include "batch_trial.hpp"
 #include "cluster_pass.hpp"
@@ -240,6 +241,20 @@ struct CandPlan {
   void reset() { *this = CandPlan{}; }
 };
 
+// Feature groups of the lockstep's update (fos_feature_groups_bind; reduce_update.hpp).  From: the caller's table alone - no plan
+// input enters, so fosapi::invalidate leaves the group as it is; a second bind overwrites it, a detaching bind and the
+// destruction of the problem reset it.  Filled by fos_feature_groups_bind, which reserves everything once.
+struct FeatureGroups {
+  int32_t ngroups = 0;               // 0: none bound
+  double l1_mix = 0.0;
+  DevBuf<int32_t> start;             // ngroups + 1 boundaries
+  DevBuf<float> weight;              // ngroups weights
+  DevBuf<int32_t> of_coord;          // the group of every coordinate: n rounded up to 4 entries
+  DevBuf<double> u;                  // 16 x (n rounded up to 4): the thresholded point of every lockstep column
+  DevBuf<double> nrm2;               // 16 x ngroups squared group norms
+  void reset() { *this = FeatureGroups{}; }
+};
+
 // Scratch sized by the shape and the CU count alone: nothing invalidates it.  gbuf_own ... part: fos_problem_create; the rest
 // on first use by the entry point named.
 struct Scratch {
@@ -295,6 +310,7 @@ struct fos_problem {
   MultiPlan multi;
   DdMultiPlan dm;
   CandPlan cand;
+  FeatureGroups fg;
   Scratch ws;
   std::unique_ptr<LbfgsWork> lbfgs;              // fos_lbfgs_minimize workspace, allocated by the first fit
   std::unique_ptr<LbfgsMultiWork> lbfgs_multi;   // fos_lbfgs_minimize_multi workspace
@@ -425,6 +441,10 @@ int need_squared(const fos_problem* p, const char* fn);
 // the three vectors is bound, coord_refusal is need_squared's third refusal (FOS_OK on a problem without coordinate data).
 inline bool has_coord(const fos_problem* p) { return p->coord_factor || p->coord_lo || p->coord_hi; }
 int coord_refusal(const fos_problem* p, const char* fn);
+// Feature groups (fos_feature_groups_bind) likewise: has_fgroups says whether a table is bound, fgroup_refusal is need_squared's
+// refusal of such a problem, in front of the coordinate one (FOS_OK on a problem without feature groups).
+inline bool has_fgroups(const fos_problem* p) { return p->fg.ngroups > 0; }
+int fgroup_refusal(const fos_problem* p, const char* fn);
 // q[j] = ||A Xp_j - use_b*b||^2 -> out16 (device); Xp already in p->xp.  b16 (unsharded only): subtract its column j instead
 int launch_residual_batch(fos_problem* p, int use_b, double* out16, const int* stopped = nullptr, const float* b16 = nullptr);
 int launch_cluster_pass(fos_problem* p);

@@ -691,6 +691,14 @@ int coord_refusal(const fos_problem* p, const char* fn) {
   return FOS_OK;
 }
 
+// ... and of a problem with feature groups: only the three update launches of the two-product lockstep apply the group prox.
+int fgroup_refusal(const fos_problem* p, const char* fn) {
+  if (p && has_fgroups(p))
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": not served on a problem with feature groups (fos_feature_groups_bind); "
+                                     "with the squared or the logistic loss they run through fos_fista_run_multi / _run_multi_folds");
+  return FOS_OK;
+}
+
 int need_squared(const fos_problem* p, const char* fn) {
   if (p && p->row_weight != nullptr)
     return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": not served on a problem with row weights (fos_row_weights_bind); the "
@@ -701,6 +709,7 @@ int need_squared(const fos_problem* p, const char* fn) {
                                                              ? ": not served on a multinomial problem (fos_problem_set_multinomial); the multinomial "
                                                              : ": not served on a logistic problem (fos_problem_set_loss); the logistic ") +
                                      "loss runs through fos_fista_run_multi / _run_multi_folds and fos_residual_batch / _folds");
+  if (int rc = fgroup_refusal(p, fn)) return rc;
   return coord_refusal(p, fn);
 }
 
@@ -1263,6 +1272,9 @@ int fos_problem_set_multinomial(int classes, fos_problem* p) {
   if (!pair_dd_multi_supported(p))
     return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_multinomial: the multinomial loss runs on the matrix-core pair (aligned "
                                      "streaming layout, 65..16384 columns)");
+  if (has_fgroups(p))
+    return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_multinomial: feature groups (fos_feature_groups_bind) are bound; the group "
+                                     "lasso over features serves the squared and the logistic loss");
   p->loss = FOS_LOSS_MULTINOMIAL;    // no buffer depends on the loss or on the number of classes: nothing to invalidate
   p->classes = classes;
   return FOS_OK;
@@ -1310,6 +1322,9 @@ int fos_coord_bind(const float* penalty_factor, const float* lower, const float*
     if (!pair_dd_multi_supported(p))
       return fail(FOS_ERR_UNSUPPORTED, "fos_coord_bind: penalty factors and bounds run on the matrix-core pair (aligned streaming "
                                        "layout, 65..16384 columns)");
+    if (has_fgroups(p))
+      return fail(FOS_ERR_UNSUPPORTED, "fos_coord_bind: feature groups (fos_feature_groups_bind) are bound; group weights cover the "
+                                       "unpenalised coordinate, factors and bounds do not compose with the group norm");
   }
   p->coord_factor = penalty_factor;  // no buffer depends on the coordinate data: nothing to invalidate
   p->coord_lo = lower;
@@ -1322,6 +1337,67 @@ int fos_coord_get(const float** penalty_factor, const float** lower, const float
   *penalty_factor = p->coord_factor;
   *lower = p->coord_lo;
   *upper = p->coord_hi;
+  return FOS_OK;
+}
+
+// The table is checked on the host before any HIP call: a bad table never reaches a kernel.  What does not need the handle is
+// checked first, so that a null handle and a malformed table are told apart without one.
+int fos_feature_groups_bind(const int32_t* group_start, const float* group_weight, int32_t ngroups, double l1_mix, fos_problem* p) {
+  if (!p) return fail(FOS_ERR_ARG, "fos_feature_groups_bind: null problem");
+  const bool detach = ngroups == 0 && !group_start;
+  if (!detach) {
+    if (!group_start || ngroups < 1) return fail(FOS_ERR_ARG, "fos_feature_groups_bind: a table of ngroups >= 1 groups is needed");
+    if (!(l1_mix >= 0.0 && l1_mix <= 1.0)) return fail(FOS_ERR_ARG, "fos_feature_groups_bind: l1_mix outside [0, 1]");
+    if (group_start[0] != 0) return fail(FOS_ERR_ARG, "fos_feature_groups_bind: group_start[0] is not 0");
+    for (int32_t g = 0; g < ngroups; ++g) {
+      if (group_start[g + 1] <= group_start[g])
+        return fail(FOS_ERR_ARG, "fos_feature_groups_bind: group_start is not strictly increasing at group " + std::to_string(g));
+      if (group_weight && !(std::isfinite(group_weight[g]) && group_weight[g] >= 0.0f))
+        return fail(FOS_ERR_ARG, "fos_feature_groups_bind: the weight of group " + std::to_string(g) + " is not finite and >= 0");
+    }
+    if ((int64_t)ngroups > p->n || (int64_t)group_start[ngroups] != p->n)
+      return fail(FOS_ERR_ARG, "fos_feature_groups_bind: the groups do not partition the n = " + std::to_string(p->n) + " coordinates");
+    if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_feature_groups_bind: a problem with feature groups needs b");
+    if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_feature_groups_bind: sharded problems are not served");
+    if (!pair_dd_multi_supported(p))
+      return fail(FOS_ERR_UNSUPPORTED, "fos_feature_groups_bind: feature groups run on the matrix-core pair (aligned streaming "
+                                       "layout, 65..16384 columns)");
+    if (has_coord(p))
+      return fail(FOS_ERR_UNSUPPORTED, "fos_feature_groups_bind: penalty factors or bounds (fos_coord_bind) are bound; they do not "
+                                       "compose with the group norm");
+    if (p->loss == FOS_LOSS_MULTINOMIAL)
+      return fail(FOS_ERR_UNSUPPORTED, "fos_feature_groups_bind: a multinomial problem is not served (squared and logistic loss)");
+  }
+  HIP_TRY(hipStreamSynchronize(p->stream));       // launches of an earlier binding may still read the buffers
+  if (detach) {
+    p->fg.reset();
+    return FOS_OK;
+  }
+  const int64_t n4 = (p->n + 3) / 4 * 4;
+  std::vector<float> w((size_t)ngroups);
+  std::vector<int32_t> of_coord((size_t)n4, 0);
+  for (int32_t g = 0; g < ngroups; ++g) {
+    w[g] = group_weight ? group_weight[g] : std::sqrt((float)(group_start[g + 1] - group_start[g]));
+    for (int32_t j = group_start[g]; j < group_start[g + 1]; ++j) of_coord[j] = g;
+  }
+  p->fg.ngroups = 0;                              // a failure below leaves the problem without feature groups
+  int rc;
+  if ((rc = p->fg.start.reserve((size_t)ngroups + 1)) || (rc = p->fg.weight.reserve((size_t)ngroups)) ||
+      (rc = p->fg.of_coord.reserve((size_t)n4)) || (rc = p->fg.u.reserve((size_t)fos::BT_NV * n4)) ||
+      (rc = p->fg.nrm2.reserve((size_t)fos::BT_NV * ngroups)))
+    return rc;
+  HIP_TRY(hipMemcpy(p->fg.start, group_start, ((size_t)ngroups + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(p->fg.weight, w.data(), (size_t)ngroups * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(p->fg.of_coord, of_coord.data(), (size_t)n4 * sizeof(int32_t), hipMemcpyHostToDevice));
+  p->fg.l1_mix = l1_mix;
+  p->fg.ngroups = ngroups;
+  return FOS_OK;
+}
+
+int fos_feature_groups_get(int32_t* ngroups, double* l1_mix, const fos_problem* p) {
+  if (!p || !ngroups || !l1_mix) return fail(FOS_ERR_ARG, "fos_feature_groups_get: null");
+  *ngroups = p->fg.ngroups;
+  *l1_mix = p->fg.ngroups ? p->fg.l1_mix : 0.0;
   return FOS_OK;
 }
 

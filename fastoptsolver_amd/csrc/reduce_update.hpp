@@ -560,6 +560,142 @@ static __global__ __launch_bounds__(256) void fista_update_group_kernel(const fl
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Group lasso over feature groups (fos_feature_groups_bind): the coordinates 0..n-1 of ONE fit are partitioned into contiguous
+// groups g = [start[g], start[g+1]) and the penalty is alpha1 [(1 - mix) sum_g w_g ||x_g||_2 + mix ||x||_1] + 0.5 alpha2 ||x||_2^2.
+// The prox: u = soft_threshold(y - tau g_full, tau alpha1 mix), then the block soft threshold of every group,
+// x_g = (||u_g|| <= thr_g ? 0 : 1 - thr_g / ||u_g||) u_g with thr_g = tau alpha1 (1 - mix) w_g (divided by 1 + tau alpha2 for
+// PROX_ENET).  The norm runs over coordinates: it crosses quads, the 64-column blocks of the update workgroups and, in general,
+// workgroups, so the update is three launches and every reduction across workgroups happens at a kernel boundary:
+//   fgroup_form_u_kernel   grid (nupd, nv): the slab reduction, block and quad ownership of fista_update_body; u -> fg.u[v][.],
+//                          the g_full^2 partial -> part[wg][1]
+//   fgroup_norm_kernel     grid (ceil(ngroups / 4), nv), one wave per (group, column): lane l adds u_i^2 for i = start + l,
+//                          start + l + 64, ... in index order, then the fixed ladder of wave_sum -> fg.nrm2[v][g]
+//   fgroup_scale_kernel    grid (nupd, nv): group of each owned coordinate from the coordinate-to-group map, scale, x_prev <- x_cur,
+//                          x_cur <- x_next, y_{k+1} (plain runs), the partials [0], [2], [3]
+// No atomics and no waiting between workgroups: the sums do not depend on timing and two runs are bitwise equal.  A group whose
+// norm is at or below its threshold becomes exactly 0.0; thr = 0 with a zero norm gives 0 (the comparison comes first); a NaN
+// norm fails the comparison and stays a NaN.  alpha1 (1 - mix) = 0 (mix = 1, the plain lasso) bypasses the group step: every
+// value and every partial sum is then formed by the expressions of fista_update_body, in its order.
+// A stopped state machine is a no-op in all three launches.
+// ---------------------------------------------------------------------------------------------------------
+struct FeatureGroupData {
+  const int32_t* start;      // ngroups + 1 group boundaries
+  const float* weight;       // ngroups group weights w_g >= 0
+  const int32_t* of_coord;   // group of every coordinate (n rounded up to 4 entries, 16-byte aligned)
+  double* u;                 // BT_NV x n4 doubles: the thresholded point of every column
+  double* nrm2;              // BT_NV x ngroups doubles: ||u_g||_2^2
+  int ngroups;
+  int64_t n4;                // n rounded up to 4
+  double l1_mix;
+};
+
+// prox_bits: bit v = the prox kind of state machine v (PROX_ENET = 1)
+static __global__ __launch_bounds__(256) void fgroup_form_u_kernel(const float* __restrict__ slabs, int nslabs, int n, MultiUpdate mu,
+                                                                   int prox_bits, int host_beta, FeatureGroupData fg) {
+  const int v = blockIdx.y;
+  if (mu.scal[v]->stopped != 0) return;
+  __shared__ f32x4 lds[RG][RQ];
+  __shared__ double dl[4];
+  const int col0 = blockIdx.x * RCOLS;
+  const int q = threadIdx.x % RQ, grp = threadIdx.x / RQ;
+  const int col = col0 + 4 * q;
+  const bool owner = (grp == 0) && (col < n);
+  const f32x4 tot = reduce_slab_block(slabs + (int64_t)v * n, nslabs, n, col0, lds, (int64_t)BT_NV * n);
+  const int cnt = owner ? (n - col < 4 ? n - col : 4) : 0;      // ragged n (padded slab rows): the last quad is partial
+  const int prox_kind = (prox_bits >> v) & 1;
+  const double beta = host_beta ? mu.beta[v] : mu.scal[v]->beta;
+  const double tau = mu.tau[v], alpha1 = mu.alpha1[v], alpha2 = mu.alpha2[v];
+  const double thr = tau * alpha1 * fg.l1_mix;                   // mix = 1: tau * alpha1, the threshold of the plain update
+  const double* __restrict__ xc_p = mu.x_cur[v];
+  const double* __restrict__ xp_p = mu.x_prev[v];
+  double* __restrict__ u = fg.u + (int64_t)v * fg.n4;
+  double acc[1] = {0.0};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (e < cnt) {
+      const double y = form_y(xc_p[col + e], xp_p[col + e], beta);
+      double gf = (double)quad_lane(tot, e);
+      if (prox_kind == PROX_L1 && alpha2 > 0.0) gf += alpha2 * y;
+      const double vv = y - tau * gf;
+      u[col + e] = alpha1 > 0.0 ? soft_threshold(vv, thr) : vv;
+      acc[0] += gf * gf;
+    }
+  }
+  block_sum_256<1>(acc, dl);
+  if (threadIdx.x == 0) mu.part[v][blockIdx.x * 4 + 1] = acc[0];
+}
+
+constexpr int FG_WAVES = 4;        // (group, column) pairs per workgroup of the norm launch
+static __global__ __launch_bounds__(64 * FG_WAVES) void fgroup_norm_kernel(MultiUpdate mu, FeatureGroupData fg) {
+  const int v = blockIdx.y;
+  if (mu.scal[v]->stopped != 0) return;
+  const int lane = threadIdx.x & 63, g = blockIdx.x * FG_WAVES + (threadIdx.x >> 6);
+  if (g >= fg.ngroups) return;                         // whole waves leave: wave_sum sees all 64 lanes
+  const double* __restrict__ u = fg.u + (int64_t)v * fg.n4;
+  const int end = fg.start[g + 1];
+  double s = 0.0;
+#pragma unroll 4
+  for (int i = fg.start[g] + lane; i < end; i += 64) {
+    const double uu = u[i];
+    s += uu * uu;
+  }
+  s = wave_sum(s);
+  if (lane == 0) fg.nrm2[(int64_t)v * fg.ngroups + g] = s;
+}
+
+__device__ inline int quad_lane(const int4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+
+static __global__ __launch_bounds__(256) void fgroup_scale_kernel(int n, MultiUpdate mu, int prox_bits, float* __restrict__ y_block,
+                                                                  int y_mode, int host_beta, FeatureGroupData fg) {
+  const int v = blockIdx.y;
+  if (mu.scal[v]->stopped != 0) return;
+  __shared__ double dl[3 * 4];
+  const int q = threadIdx.x % RQ, grp = threadIdx.x / RQ;
+  const int col = blockIdx.x * RCOLS + 4 * q;
+  const bool owner = (grp == 0) && (col < n);
+  const int cnt = owner ? (n - col < 4 ? n - col : 4) : 0;
+  const int prox_kind = (prox_bits >> v) & 1;
+  const double tau = mu.tau[v], alpha1 = mu.alpha1[v], alpha2 = mu.alpha2[v];
+  const double shrink = 1.0 / (1.0 + tau * alpha2);
+  const double gcoef = tau * alpha1 * (1.0 - fg.l1_mix);         // thr_g = gcoef * w_g; 0: no group step (mix = 1, alpha1 = 0)
+  double* __restrict__ xc_p = mu.x_cur[v];
+  double* __restrict__ xp_p = mu.x_prev[v];
+  const double* __restrict__ u = fg.u + (int64_t)v * fg.n4;
+  const double* __restrict__ nrm2 = fg.nrm2 + (int64_t)v * fg.ngroups;
+  const double beta_next = mu.beta_next[v];
+  int4 gi = {0, 0, 0, 0};
+  if (cnt > 0 && gcoef != 0.0) gi = *reinterpret_cast<const int4*>(fg.of_coord + col);
+  double acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (e < cnt) {
+      const double xc = xc_p[col + e];
+      double xn = u[col + e];
+      if (gcoef != 0.0) {
+        const int g = quad_lane(gi, e);
+        const double nrm = sqrt(nrm2[g]), thr = gcoef * (double)fg.weight[g];
+        const double s = nrm <= thr ? 0.0 : 1.0 - thr / nrm;     // a NaN norm fails the comparison and stays a NaN
+        xn = s == 0.0 ? 0.0 : s * xn;
+      }
+      if (prox_kind == PROX_ENET) xn *= shrink;
+      const double d = xn - xc;
+      acc[0] += d * d;
+      acc[1] += fabs(xn);
+      acc[2] += xn * xn;
+      xp_p[col + e] = xc;
+      xc_p[col + e] = xn;
+      // plain runs: beta_{k+1} is known; controlled runs leave y to form_y_multi_kernel behind the bookkeeping
+      if (host_beta) write_y_block(y_block, y_mode, col + e, v, (float)form_y(xn, xc, beta_next));
+    }
+  }
+  block_sum_256<3>(acc, dl);
+  if (threadIdx.x == 0) {
+    double* part = mu.part[v] + blockIdx.x * 4;
+    part[0] = acc[0]; part[2] = acc[1]; part[3] = acc[2];
+  }
+}
+
 // One wave: fold the partials and advance the scalar state.  iterative_solvers.py:204-221, :235-242, :325-342.
 __device__ inline void fista_finalize_body(const double* __restrict__ part, int nparts,
                                            const double* __restrict__ rr_part, int n_rr,

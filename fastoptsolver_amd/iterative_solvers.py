@@ -129,9 +129,9 @@ def _weighted(A):
 
 
 def _has_coord(A):
-    """Whether A is a handle with penalty factors or bounds bound (`Problem.set_penalty`): it runs on the matrix-core lockstep
-    alone."""
-    return isinstance(A, _core.Problem) and A.has_coord
+    """Whether A is a handle with penalty factors or bounds (`Problem.set_penalty`) or feature groups
+    (`Problem.set_feature_groups`) bound: it runs on the matrix-core lockstep alone."""
+    return isinstance(A, _core.Problem) and (A.has_coord or A.has_feature_groups)
 
 
 def _refuse_multinomial(A, who):
@@ -1194,14 +1194,17 @@ def fista_path(A, b, alphas, t_init_factor: float = 1.0, max_iter: int = 500, *,
     + alpha1 sum_j p_j |x_j| + 0.5 alpha2 sum_j p_j x_j^2 subject to lower_j <= x_j <= upper_j (``lower=0.0``: the non-negative
     lasso; p_j = 0: an unpenalised coordinate).  Such a problem runs on the matrix-core lockstep alone, a single weight as a one-column lockstep, with the step t_init_factor / (L + alpha2 max_j p_j)
     (L is the constant of the data term and does not depend on the constraints); ``tol``, ``comm=`` and ``cols=`` are
-    ValueErrors and a refusal raises."""
+    ValueErrors and a refusal raises.
+    A handle with feature groups (``prepare_grouped`` / ``Problem.set_feature_groups``): the penalty is alpha1 [(1 - l1_ratio)
+    sum_g w_g ||x_g||_2 + l1_ratio ||x||_1] + 0.5 alpha2 ||x||_2^2, the (sparse-)group lasso; the lockstep alone likewise, with
+    the step of the separable penalty, t_init_factor / (L + alpha2)."""
     reset_metrics()
     _refuse_multinomial(A, "fista_path")
     if delta is not None:
         assert delta > 2, "In FISTA-Δ, delta must be > 2 for convergence (course requirement)"
     weighted = _weighted(A) or _has_coord(A)
     if weighted and (tol != 0.0 or comm is not None or cols is not None):
-        raise ValueError("a handle with sample weights, penalty factors or bounds runs on the lockstep alone: no tol (the "
+        raise ValueError("a handle with sample weights, penalty factors, bounds or feature groups runs on the lockstep alone: no tol (the "
                          "gradient-norm rule), comm= or cols=")
     prob, _ = _sharded_problem(A, b, dtype, comm, None, cols)    # comm: A, b are this rank's rows (matrix-core pass, one
     like = prob.like                                             # all-reduce of the 16 gradients per iteration)
@@ -1362,7 +1365,10 @@ def fista_cv(A, b, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int = 
 
     A handle with penalty factors or bounds (``prepare_penalized``), as in ``fista_path``: the constraints belong to
     the coordinates, so every fold's fit carries them; the step is t_init_factor / (L + alpha2 max_j p_j); the refit runs in
-    the lockstep and a refusal raises - there is no slow path."""
+    the lockstep and a refusal raises - there is no slow path.
+
+    A handle with feature groups (``prepare_grouped``) likewise: every fold's fit is the (sparse-)group lasso of its training
+    rows."""
     reset_metrics()
     _refuse_multinomial(A, "fista_cv")
     if delta is not None:

@@ -154,6 +154,9 @@ def logistic_objective(x, A, y, alpha1, alpha2):
     0.5 alpha2 sum_j p_j x_j^2 (the fp32 factors as bound); the box is not checked - solver outputs lie inside it by
     construction."""
     prob = _problem(A, y, None)
+    if prob.has_feature_groups:      # the separable penalty would answer for another objective
+        raise ValueError("logistic_objective: the handle has feature groups (Problem.set_feature_groups): use "
+                         'group_lasso_objective(x, handle, None, alpha1, alpha2, groups, ..., loss="logistic")')
     xt = x.detach() if _core.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=np.float64))
     vector = xt.dim() == 1
     X = (xt.reshape(-1, 1) if vector else xt).to(device=prob.device, dtype=torch.float64)

@@ -65,6 +65,9 @@ def _problem(A, dtype):
             raise ValueError("the group penalty does not compose with box bounds (lower / upper); penalty factors do")
         if getattr(A, "comm", None) is not None:
             raise ValueError("the multi-task lockstep does not serve sharded problems")
+        if A.has_feature_groups:
+            raise ValueError("the multi-task lockstep does not serve feature groups (Problem.set_feature_groups): the two group "
+                             "norms do not compose")
         return A
     return _core.Problem(A, None, dtype, True)
 

@@ -38,3 +38,46 @@ def _objective_targets(X, A, B, value):
                 rr, x2, x1 = rrs[i], st[0], st[4]
             total += value(rr, x2, x1)
     return total
+
+
+def group_lasso_objective(x, A, b, alpha1, alpha2, groups, group_weight=None, l1_ratio=0.0, *, loss="squared", sample_weight=None):
+    """data term + alpha1 [(1 - l1_ratio) sum_g w_g ||x_g||_2 + l1_ratio ||x||_1] + 0.5 alpha2 ||x||_2^2 in fp64 on the host:
+    the objective of a handle with feature groups (``prepare_grouped``).  The data term is sum_i w_i 0.5 (a_i.x - b_i)^2 or
+    (``loss="logistic"``) sum_i w_i (log(1 + e^{a_i.x}) - b_i a_i.x), w = ``sample_weight`` (None: 1).  ``groups`` /
+    ``group_weight`` / ``l1_ratio`` as ``prepare_grouped`` takes them.  A: an array / tensor, or a handle - its stored A (bf16
+    storage: the rounded values), its b, loss and weights are then used where the arguments are None / default.  ``x``: a vector
+    (returns a float) or an n x k block (returns k float64 values).  No device work on arrays."""
+    import numpy as np
+    import torch
+
+    def host(v):
+        if v is None:
+            return None
+        return (v.detach().to("cpu", torch.float64).numpy() if _core.is_tensor(v) else np.asarray(v, dtype=np.float64))
+    if isinstance(A, _core.Problem):
+        prob = A
+        A = prob.A[:, : prob.n]
+        b = prob.b if b is None else b
+        loss = prob.loss if loss == "squared" else loss
+        sample_weight = prob.sample_weight if sample_weight is None else sample_weight
+    if loss not in ("squared", "logistic"):
+        raise ValueError(f'loss: "squared" or "logistic" expected, got {loss!r}')
+    Ah, bh, wh, xh = host(A), host(b), host(sample_weight), host(x)
+    if Ah.ndim != 2 or bh is None or bh.shape != (Ah.shape[0],):
+        raise ValueError("A must be 2-D and b must have m entries")
+    n = Ah.shape[1]
+    vector = xh.ndim == 1
+    X = xh.reshape(n, 1) if vector else xh
+    if X.ndim != 2 or X.shape[0] != n:
+        raise ValueError(f"x: a vector of length {n} or an {n} x k block expected")
+    start, w, mix = _core.checked_feature_groups(groups, group_weight, l1_ratio, n)
+    rw = np.ones(Ah.shape[0]) if wh is None else wh
+    Z = Ah @ X
+    if loss == "squared":
+        data = 0.5 * (rw[:, None] * (Z - bh[:, None]) ** 2).sum(axis=0)
+    else:
+        data = (rw[:, None] * (np.logaddexp(0.0, Z) - bh[:, None] * Z)).sum(axis=0)
+    norms = np.sqrt(np.add.reduceat(X * X, start[:-1], axis=0))          # ngroups x k
+    val = (data + float(alpha1) * ((1.0 - mix) * (w[:, None] * norms).sum(axis=0) + mix * np.abs(X).sum(axis=0)) +
+           0.5 * float(alpha2) * (X * X).sum(axis=0))
+    return float(val[0]) if vector else val

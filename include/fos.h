@@ -218,6 +218,9 @@ int fos_row_weights_get(const float** w_out, const fos_problem* p);
  * nothing is replanned.  fos_coord_get reads the three bound pointers back (NULL: none). */
 int fos_coord_bind(const float* penalty_factor, const float* lower, const float* upper, fos_problem* p);
 int fos_coord_get(const float** penalty_factor, const float** lower, const float** upper, const fos_problem* p);
+/* The group lasso over feature groups of one fit (groups of coordinates bound to a problem; the bind and the get of such groups)
+ * is declared in fos_feature_groups.h, a header of its own beside this one: it includes this header and adds two entry points
+ * to the same library. */
 /* G + j*n (n floats, device) = A^T W A X_j for the nv <= 16 columns of X (the layout of fos_residual_batch: n x 16 floats,
  * row-major).  W: the bound row weights, the identity when none are bound; neither b nor the loss enters, so logistic and
  * weighted problems are served.  Product 1 (R = w * (A X), kept), product 2 over every row panel, one slab sum.  Enqueues only.
