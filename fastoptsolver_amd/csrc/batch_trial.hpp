@@ -32,6 +32,14 @@ constexpr int BT_F4_ROW = BT_COLS / 4;                               // float4 p
 constexpr int BT_A_LOADS = BT_ROWS * BT_F4_ROW / BT_THREADS;         // float4 of A per thread per tile
 constexpr int BT_X_LOADS = BT_COLS * BT_NV / 4 / BT_THREADS;         // float4 of the candidate block per thread per tile
 constexpr int BT_W = 3 * BT_NV + 2;  // per-workgroup outputs of the candidate kernel
+// fp32 kernel: a row's k-ordered fma chain runs over n / 2 products per accumulator.  It is cut every BT_CHAIN_TILES column
+// tiles (16384 columns: the y-in-LDS and column-block plans alone have wider rows) and the pieces are summed: at 3 x 65540 one
+// chain put 7e-6 (relative) on ||A dlt||^2, more than the bound of an fp32 pass (tests/test_gpu_armijo.py, case blocks: 1.18 of
+// it, 0.17 with the cut) and several times the noise term of the Armijo test that reads it.  Up to 16384 columns the sum is bit
+// for bit the uncut chain and the time is the same (65536 x 8192: 343 us before and after).  Wider (us before -> after):
+// 65536 x 20000 773 -> 775, 32768 x 32768 640 -> 646; where a few workgroups of one row group each have the device to
+// themselves, 8192 x 20000 233 -> 261, 2048 x 65536 740 -> 833 (profiles/armijo/README.md).
+constexpr int BT_CHAIN_TILES = 256;  // a power of two
 
 static_assert(BT_COLS % 16 == 0 && BT_A_LOADS >= 1 && BT_X_LOADS >= 1, "tile shape");
 
@@ -227,9 +235,14 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const f
   };
   // two accumulators per row block (even / odd MFMA steps): v_mfma_f32_16x16x4_f32 issues every 32 cycles but a
   // dependent one needs 40 - one chain would leave the pipe idle a fifth of the time
-  f32x4 acc[RB], acc_odd[RB];
+  // `tot`: the finished pieces of a cut chain (BT_CHAIN_TILES above); it stays zero up to BT_CHAIN_TILES column tiles
+  f32x4 acc[RB], acc_odd[RB], tot[RB];
 #pragma unroll
-  for (int rb = 0; rb < RB; ++rb) { acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f}; acc_odd[rb] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  for (int rb = 0; rb < RB; ++rb) {
+    acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    acc_odd[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    tot[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
   double qsum = 0.0;                              // this lane's candidate j = lane & 15, its 4 rows per row block
   const unsigned held_id = FOLD != FOLD_OFF ? fold_held_of(held, lane & 15) : 0u;
   auto compute_tile = [&](int buf, int64_t t) {
@@ -246,11 +259,22 @@ __global__ __launch_bounds__(BT_THREADS) void residual_batch_mfma_kernel(const f
         acc_odd[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.w, x4.w, acc_odd[rb], 0, 0, 0);
       }
     }
-    if ((t + 1) % ktiles == 0) {
+    const int kt_next = (int)((t + 1) % ktiles);
+    if (kt_next != 0 && (kt_next & (BT_CHAIN_TILES - 1)) == 0) {
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) {
+        tot[rb] += acc[rb] + acc_odd[rb];
+        acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        acc_odd[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    if (kt_next == 0) {
       // row group complete: D[row = 4*(lane>>4)+reg][candidate = lane&15]
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb) {
         acc[rb] += acc_odd[rb];
+        acc[rb] += tot[rb];
+        tot[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
         const int64_t row0 = (g_lo + t / ktiles) * ROWS + 16 * (wave * RB + rb) + 4 * (lane >> 4);
         unsigned ids4 = 0u;
         if constexpr (FOLD != FOLD_OFF) ids4 = fold_ids_of(fold_of_row, row0, m);
