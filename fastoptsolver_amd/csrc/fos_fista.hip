@@ -3,6 +3,7 @@
 #include "fos_internal.hpp"
 #include "fused_step.hpp"
 #include "chip_resident.hpp"
+#include <cassert>
 
 using namespace fosapi;
 
@@ -674,14 +675,15 @@ int fos_fista_run_chip(fos_fista* f, int iters) {
   return finish_plain(f, stats, iters >= 2 ? stats + 4 : nullptr, 1, stats + 8, 1);
 }
 
-// The arguments of fista_update_multi_kernel: every state machine's buffers and weights; plain runs also take its next
-// momentum step (controlled runs take beta from the device scalars).
+// The arguments of the lockstep update kernels: every state machine's buffers, weights, step and prox kind (bit v of
+// prox_bits); plain runs also take its next momentum step (controlled runs take beta from the device scalars).
 static fos::MultiUpdate multi_update(fos_fista* const* fs, int nv, bool controlled) {
   fos::MultiUpdate mu{};
   for (int v = 0; v < nv; ++v) {
     fos_fista* f = fs[v];
     mu.x_cur[v] = f->x_cur; mu.x_prev[v] = f->x_prev; mu.scal[v] = f->scal; mu.part[v] = f->part2;
     mu.alpha1[v] = f->prm.alpha1; mu.alpha2[v] = f->prm.alpha2; mu.tau[v] = f->prm.tau;
+    mu.prox_bits |= (f->prm.prox_kind == fos::PROX_ENET ? 1 : 0) << v;
     if (!controlled) {
       const PlainStep s = advance_plain(f, false);
       mu.part[v] = s.part; mu.beta[v] = s.beta; mu.beta_next[v] = s.beta_next;
@@ -693,7 +695,7 @@ static fos::MultiUpdate multi_update(fos_fista* const* fs, int nv, bool controll
 // Up to 16 state machines in lockstep on the matrix cores (gram_batch.hpp): per iteration and per row panel, product 1
 // (R = A_panel Y - b, from HBM) and product 2 (G += R^T A_panel, the panel again from the Infinity Cache), then the updates,
 // which leave every y_{k+1} in the candidate block of the next product 1.  The layout: plan_multi_mfma (fos_plan.hip).
-// same_family: the state machines differ in weights and steps only (a regularisation path does) - one update launch for all.
+// The separable update is one launch for all state machines (launch_separable_update), whatever their families.
 // b16 (several right-hand sides, unsharded): product 1 subtracts column j of this m x 16 block from candidate column j
 // instead of the problem's b; always the two-product form (the planner's cluster layout, if any, is left as it is).
 // fold_of_row / held (K-fold cross-validation, unsharded, the problem's own b): product 1 zeroes column j's residual on the
@@ -704,17 +706,17 @@ static fos::MultiUpdate multi_update(fos_fista* const* fs, int nv, bool controll
 // A problem with row weights (fos_row_weights_bind): product 1 is the weighted form of its loss, R = w (A_panel Y - b) or
 // w (sigma(A_panel Y) - b); the two-product form, and everything after product 1 is the same.
 // A problem with coordinate data (fos_coord_bind: penalty factors and box bounds): the two-product form as well; both products
-// are the launches they were and the two update launch sites take the coordinate kernels (reduce_update.hpp, COORD), which
-// scale the penalties per coordinate and clamp to the box.  Composes with the fold mask, the logistic loss and row weights.
+// are the launches they were and the separable update launch takes the coordinate form (reduce_update.hpp, COORD), which
+// scales the penalties per coordinate and clamps to the box.  Composes with the fold mask, the logistic loss and row weights.
 // A multinomial problem (fos_problem_set_multinomial): the 16 columns are the class vectors of floor(16 / C) joint fits.
 // Product 1 is the plain storing form, R = A_panel Y (the logits; neither b nor a mask nor the weights enter it), the link
 // kernel (softmax_link.hpp) turns the panel into softmax(A_panel Y) - onehot(b) in place with the weights and the fold mask
-// applied, and everything after it is the same.  Plain runs only (run_multi_softmax).
+// applied, and everything after it is the same.  Plain runs only (lockstep_route).
 
 // Handles under the group penalty (fos_fista_params.group = G >= 2; checked by group_refusal before they get here): always the
-// two-product form, plain; the G columns of a fit are updated together by the one launch of launch_group_update, in front of
-// the two update sites of the separable penalty.  Penalty factors compose (the factor of a coordinate scales its row's
-// threshold); box bounds do not and are refused.
+// two-product form, plain; the G columns of a fit are updated together by the one launch of launch_group_update, in place of
+// the separable update.  Penalty factors compose (the factor of a coordinate scales its row's threshold); box bounds do not
+// and are refused.
 
 // Row splits of product 2 in the two-product form: the planned ones, or - on a problem planned for the cluster form, whose slab
 // count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated.
@@ -756,44 +758,77 @@ static int launch_group_update(fos_fista* const* fs, int nv, int g_splits, int y
   fos_problem* p = fs[0]->p;
   const int G = fs[0]->prm.group;
   const fos::MultiUpdate mu = multi_update(fs, nv, false);
-  int prox_bits = 0;
-  for (int s = 0; s < nv / G; ++s) prox_bits |= (fs[s * G]->prm.prox_kind == fos::PROX_ENET ? 1 : 0) << s;
   hipLaunchKernelGGL(fos::fista_update_group_kernel, dim3(fs[0]->nupd, nv / G), dim3(256), 0, p->stream, p->multi.slabs16, g_splits,
-                     (int)p->n, mu, G, prox_bits, p->cand.xp, y_mode, p->coord_factor);
+                     (int)p->n, mu, G, p->cand.xp, y_mode, p->coord_factor);
   LAUNCH_CHECK();
   return FOS_OK;
 }
 
 // The update on a problem with feature groups (fos_feature_groups_bind) in three launches (reduce_update.hpp): u and the
 // gradient partial over (nupd, nv), the group norms with one wave per (group, column), the scaling over (nupd, nv) again.  One
-// MultiUpdate serves all three: a plain run's momentum step is advanced once.  The prox kind travels per column, so a plain run
-// of mixed families takes the same launches.
+// MultiUpdate serves all three: a plain run's momentum step is advanced once.
 static int launch_fgroup_update(fos_fista* const* fs, int nv, int g_splits, int y_mode, bool controlled) {
   fos_problem* p = fs[0]->p;
   const fos::MultiUpdate mu = multi_update(fs, nv, controlled);
-  int prox_bits = 0;
-  for (int v = 0; v < nv; ++v) prox_bits |= (fs[v]->prm.prox_kind == fos::PROX_ENET ? 1 : 0) << v;
   const fos::FeatureGroupData fg{p->fg.start, p->fg.weight, p->fg.of_coord, p->fg.u, p->fg.nrm2, p->fg.ngroups, (p->n + 3) / 4 * 4,
                                  p->fg.l1_mix};
   const int host_beta = controlled ? 0 : 1;
   hipLaunchKernelGGL(fos::fgroup_form_u_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->multi.slabs16, g_splits, (int)p->n,
-                     mu, prox_bits, host_beta, fg);
+                     mu, host_beta, fg);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(fos::fgroup_norm_kernel, dim3((fg.ngroups + fos::FG_WAVES - 1) / fos::FG_WAVES, nv), dim3(64 * fos::FG_WAVES), 0,
                      p->stream, mu, fg);
   LAUNCH_CHECK();
-  hipLaunchKernelGGL(fos::fgroup_scale_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, (int)p->n, mu, prox_bits, p->cand.xp,
-                     y_mode, host_beta, fg);
+  hipLaunchKernelGGL(fos::fgroup_scale_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, (int)p->n, mu, p->cand.xp, y_mode,
+                     host_beta, fg);
   LAUNCH_CHECK();
   return FOS_OK;
 }
 
-static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controlled, bool same_family,
-                          const float* b16 = nullptr, const uint8_t* fold_of_row = nullptr,
-                          const fos::FoldHeld* held = nullptr) {
+// The separable update of all nv state machines in ONE launch (fista_update_multi_kernel), grid (nupd, nv): one family or
+// mixed families (the prox kind travels per column), plain or controlled, with or without coordinate data.
+static int launch_separable_update(fos_fista* const* fs, int nv, int g_splits, int y_mode, bool controlled) {
   fos_problem* p = fs[0]->p;
+  const fos::MultiUpdate mu = multi_update(fs, nv, controlled);
+  const fos::CoordData cd{p->coord_factor, p->coord_lo, p->coord_hi};
+  auto kern = has_coord(p) ? fos::fista_update_multi_kernel<true> : fos::fista_update_multi_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->multi.slabs16, g_splits, (int)p->n, mu, p->cand.xp,
+                     y_mode, controlled ? 0 : 1, cd);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
+// One call of a lockstep entry point, as its arguments came in (checked), and what lockstep_route decides for it.
+struct LockstepCall {
+  fos_fista* const* fs;
+  int nv, iters;
+  const float* B;                    // fos_fista_run_multi_rhs: column v of this m x nv block for state machine v (null: the problem's b)
+  int64_t ldb;
+  const uint8_t* fold_of_row;        // fos_fista_run_multi_folds: the fold of every row, the HOST held ids and their block (null: no mask)
+  const int32_t* held_ids;
+  const fos::FoldHeld* held;
+  const char* fn;                    // the entry point, for messages
+};
+enum LockstepEngine { ENGINE_SINGLE, ENGINE_VALU, ENGINE_MFMA };
+struct LockstepRoute {
+  LockstepEngine engine;             // fos_fista_run on the one handle, the VALU multi-vector pass, the matrix-core pair
+  MultiLaunch valu;                  // ENGINE_VALU: its kernel
+  bool controlled;                   // momentum and stops decided on the device, per state machine
+  bool same_family;                  // the state machines share mode / prox kind / delta (what the lockstep bookkeeping takes from fs[0])
+  bool stage_b;                      // B is staged into p->ws.b16 before the engine runs
+};
+
+static int run_multi_mfma(const LockstepCall& c, const LockstepRoute& r) {
+  fos_fista* const* fs = c.fs;
+  const int nv = c.nv, iters = c.iters;
+  const bool controlled = r.controlled;
+  const uint8_t* fold_of_row = c.fold_of_row;
+  const fos::FoldHeld* held = c.held;
+  fos_problem* p = fs[0]->p;
+  const float* b16 = r.stage_b ? p->ws.b16.get() : nullptr;
   const bool cols = p->col_sharded;
   if (cols && !controlled) return fail(FOS_ERR_STATE, "run_multi_mfma: a column-sharded lockstep is device-controlled");
+  assert(!controlled || r.same_family);       // the bookkeeping kernels take mode / delta from fs[0] (lockstep_route refuses the rest)
   int rc = ensure_batch_workspace(p);
   if (rc) return rc;
   if (cols && (rc = p->ws.mfold.reserve((size_t)fos::BT_NV * 4))) return rc;
@@ -801,18 +836,12 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
   const bool is_bf16 = p->dtype == FOS_BF16;
   const int64_t esz = is_bf16 ? 2 : 4;
   const int y_mode = is_bf16 ? fos::YOUT_XQ : fos::YOUT_XP;
-  // row splits of product 2: the planned ones, or - a B-block run on a problem planned for the cluster form, whose slab
-  // count is the number of clusters - the two-product splits, which must fit the slabs the cluster form allocated
   const bool logit = p->loss == FOS_LOSS_LOGISTIC;
   const bool weighted = p->row_weight != nullptr;
-  const bool coord = has_coord(p);   // fos_coord_bind: the two update launches below take the coordinate kernels
-  const fos::CoordData cd{p->coord_factor, p->coord_lo, p->coord_hi};
   const bool softmax = p->loss == FOS_LOSS_MULTINOMIAL;      // the link kernel sits between the two products of every panel
   const bool group_penalty = grouped(fs[0]->prm);            // the fits' columns are updated together (launch_group_update)
-  bool two_products = b16 || fold_of_row || logit || weighted || coord;
-  two_products = two_products || group_penalty;
   const bool fgroup = has_fgroups(p);                        // fos_feature_groups_bind: the update is launch_fgroup_update
-  two_products = two_products || fgroup;
+  const bool two_products = b16 || fold_of_row || logit || weighted || has_coord(p) || group_penalty || fgroup;
   bool use_cluster = p->multi.cp_cs && !two_products && !softmax;
   int g_splits = p->multi.gram_splits;
   if ((two_products || softmax) && (rc = two_product_splits(p, &g_splits))) return rc;
@@ -841,8 +870,7 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
     if ((rc = begin_plain(f, &stopped))) return rc;
     if (stopped) return fail(FOS_ERR_STATE, "fos_fista_run_multi: a handle has already stopped");
     hipLaunchKernelGGL(fos::form_y_block_kernel, dim3(grid_1d(p->n, 256, 256)), dim3(256), 0, p->stream, f->x_cur, f->x_prev,
-                       f->h_beta, (int)p->n, v, is_bf16 ? (float*)nullptr : p->cand.xp,
-                       is_bf16 ? (unsigned short*)p->cand.xp.get() : (unsigned short*)nullptr);
+                       f->h_beta, (int)p->n, v, p->cand.xp, y_mode);
     LAUNCH_CHECK();
     restart_plain(f);                // y lives in the candidate block; part2 partials are counted from this run on
   }
@@ -880,31 +908,11 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
     // row-sharded problem: the 16 partial gradients (all row splits) are summed over the ranks before the updates
     // (column-sharded: the gradient block is local)
     if (!cols && (rc = reduce_across(p, p->multi.slabs16, (size_t)g_splits * fos::BT_NV * p->n, false))) return rc;
-    if (fgroup) { if ((rc = launch_fgroup_update(fs, nv, g_splits, y_mode, controlled))) return rc; } else   // (never with group_penalty)
-    if (group_penalty) { if ((rc = launch_group_update(fs, nv, g_splits, y_mode))) return rc; } else if (controlled || same_family) {             // one launch updates all state machines
-      const fos::MultiUpdate mu = multi_update(fs, nv, controlled);
-      if (coord)
-        hipLaunchKernelGGL(fos::fista_update_multi_coord_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->multi.slabs16,
-                           g_splits, (int)p->n, mu, fs[0]->prm, p->cand.xp, y_mode, controlled ? 0 : 1, cd);
-      else
-      hipLaunchKernelGGL(fos::fista_update_multi_kernel, dim3(fs[0]->nupd, nv), dim3(256), 0, p->stream, p->multi.slabs16, g_splits,
-                         (int)p->n, mu, fs[0]->prm, p->cand.xp, y_mode, controlled ? 0 : 1);
-      LAUNCH_CHECK();
-    } else {
-      for (int v = 0; v < nv; ++v) {
-        const PlainStep s = advance_plain(fs[v], false);
-        if (coord) {
-          hipLaunchKernelGGL(fos::fista_update_coord_kernel, dim3(fs[v]->nupd), dim3(256), 0, p->stream,
-                             p->multi.slabs16 + (size_t)v * p->n, g_splits, (int)p->n, fs[v]->x_cur, fs[v]->x_prev, fs[v]->scal,
-                             fs[v]->prm, s.part, 1, s.beta, p->cand.xp, s.beta_next, (int64_t)fos::BT_NV * p->n, y_mode, v, cd);
-          LAUNCH_CHECK();
-          continue;
-        }
-        if ((rc = launch_update_from_slabs(fs[v], s.part, 1, s.beta, nullptr, p->cand.xp, s.beta_next, p->multi.slabs16 + (size_t)v * p->n,
-                                           (int64_t)fos::BT_NV * p->n, g_splits, y_mode, v)))
-          return rc;
-      }
-    }
+    // the update stage: feature groups - three launches; the group penalty - one; everything else - the one separable launch
+    if (fgroup) rc = launch_fgroup_update(fs, nv, g_splits, y_mode, controlled);      // (never with group_penalty)
+    else if (group_penalty) rc = launch_group_update(fs, nv, g_splits, y_mode);
+    else rc = launch_separable_update(fs, nv, g_splits, y_mode, controlled);
+    if (rc) return rc;
     if (controlled) {                            // bookkeeping of all weights (device beta) -> their y_{k+1}
       if (cols) {                                // step norms, ||x||^2, ||x||_1 are sums over the column blocks of all ranks
         hipLaunchKernelGGL(fold4_multi_kernel, dim3(nv), dim3(64), 0, p->stream, mc, fs[0]->nupd, p->ws.mfold);
@@ -935,36 +943,24 @@ static int run_multi_mfma(fos_fista* const* fs, int nv, int iters, bool controll
   return FOS_OK;
 }
 
-// The lockstep dispatcher of fos_fista_run_multi (B == nullptr: the problem's b) and fos_fista_run_multi_rhs (B: column v of
-// the caller's m x nv block for state machine v, staged once per call into the m x 16 block p->ws.b16).  Arguments are checked.
-// The checks the masked and the logistic lockstep share: no gradient-norm rule, fp64 split gradient or device-held step, and
-// device control (adaptive restart, step / ratio stops) only for one family - it is one update launch for all state machines.
-static int lockstep_forms(fos_fista* const* fs, int nv, const char* fn, bool* all_plain, bool* same_family) {
-  *all_plain = *same_family = true;
-  for (int v = 0; v < nv; ++v) {
-    if (fs[v]->prm.tol_grad != 0.0 || fs[v]->precise || fs[v]->prm.tau_from_state)
-      return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": no gradient-norm rule, fp64 split gradient or device-held step");
-    *all_plain = *all_plain && plain_run(fs[v]);
-    const fos::FistaParams &a = fs[0]->prm, &c = fs[v]->prm;
-    *same_family = *same_family && a.mode == c.mode && a.prox_kind == c.prox_kind && a.delta == c.delta;
-  }
-  if (!*all_plain && !*same_family) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": a device-controlled lockstep serves one family");
-  return FOS_OK;
+// ---- The route decision of the lockstep: which engine serves a call of fos_fista_run_multi / _rhs / _folds, or why none does ----
+static bool any_grouped(fos_fista* const* fs, int nv) {
+  for (int v = 0; v < nv; ++v)
+    if (grouped(fs[v]->prm)) return true;
+  return false;
 }
 
-// A logistic problem, one with row weights or one with coordinate data: always the two matrix-core products, for any number of state machines (one
-// included - there is no single-vector logistic or weighted pass), never the cluster form or the VALU multi-vector pass.
-static int run_multi_logit(fos_fista* const* fs, int nv, int iters, const uint8_t* fold_of_row, const fos::FoldHeld* held,
-                           const char* fn) {
-  fos_problem* p = fs[0]->p;
-  if (!p->b || p->comm || p->col_sharded || !pair_dd_multi_supported(p))
-    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the logistic loss, row weights and penalty factors / bounds need b, an unsharded problem and the "
-                                                         "matrix-core pair");
-  bool all_plain, same_family;
-  if (int rc = lockstep_forms(fs, nv, fn, &all_plain, &same_family)) return rc;
-  if (iters == 0) return FOS_OK;
-  return run_multi_mfma(fs, nv, iters, !all_plain, same_family, nullptr, fold_of_row, held);
+// Handle v carries the parameters of the first handle of its fit (`width` consecutive columns: G, or the class count) and,
+// with held ids, holds out the same fold.  The caller words the refusal.
+static bool fit_column_agrees(fos_fista* const* fs, int v, int width, const int32_t* held) {
+  const int v0 = v / width * width;
+  const fos::FistaParams &a = fs[v0]->prm, &c = fs[v]->prm;
+  return a.group == c.group && a.tau == c.tau && a.alpha1 == c.alpha1 && a.alpha2 == c.alpha2 && a.delta == c.delta &&
+         a.mode == c.mode && a.prox_kind == c.prox_kind && !(held && held[v] != held[v0]);
 }
+
+// What everything but the plain squared loss needs: the problem's own b, no sharding, the matrix-core pair.
+static bool unsharded_pair(const fos_problem* p) { return !p->comm && !p->col_sharded && pair_dd_multi_supported(p); }
 
 // What the lockstep serves under the group penalty (fos_fista_params.group = G >= 2), checked before any launch or change of
 // handle state; FOS_OK without a grouped handle.  All handles are grouped with one G, nv is a multiple of G, the G handles of a
@@ -982,102 +978,105 @@ static int group_refusal(fos_fista* const* fs, int nv, const int32_t* held, cons
   else if (nv % G != 0) why = "nv is a multiple of the group size";
   for (int v = 0; v < nv && !why; ++v) {
     const fos_fista* f = fs[v];
-    const fos::FistaParams &a = fs[v / G * G]->prm, &c = f->prm;
-    if (a.group != c.group || a.tau != c.tau || a.alpha1 != c.alpha1 || a.alpha2 != c.alpha2 || a.delta != c.delta ||
-        a.mode != c.mode || a.prox_kind != c.prox_kind || (held && held[v] != held[v / G * G]))
+    if (!fit_column_agrees(fs, v, G, held))
       why = "the handles of a group carry identical parameters and hold out one fold";
-    else if (!plain_run(f) || f->precise || c.tau_from_state)
+    else if (!plain_run(f) || f->precise || f->prm.tau_from_state)
       why = "plain runs only (no adaptive restart, no step / ratio / gradient tolerance, no fp64 split gradient, no device-held "
             "step: a rule decided per column would break the joint fit)";
   }
   if (!why && p->loss == FOS_LOSS_MULTINOMIAL && G != p->classes) why = "on a multinomial problem the group size is the class count";
   if (!why && (p->coord_lo || p->coord_hi))
     why = "box bounds (fos_coord_bind) do not compose with the group norm; penalty factors alone do";
-  if (!why && (p->comm || p->col_sharded || !pair_dd_multi_supported(p))) why = "an unsharded problem with the matrix-core pair is needed";
+  if (!why && !unsharded_pair(p)) why = "an unsharded problem with the matrix-core pair is needed";
   if (!why && has_fgroups(p)) why = "feature groups (fos_feature_groups_bind) are bound; the two group norms do not compose";
   if (why) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the group penalty (fos_fista_params.group >= 2): " + why);
   return FOS_OK;
 }
 
-// Joint fits under the group penalty on a squared-loss or logistic problem: nv / G fits of G columns each on the two
-// matrix-core products, for any nv (nv == G == 2 included) - never the VALU multi-vector pass, the cluster form or the
-// single-vector run.  B: the right-hand-side block of fos_fista_run_multi_rhs (the targets of a multi-task fit), which product 1
-// takes for the unweighted squared loss alone; fold_of_row / held: the masks of fos_fista_run_multi_folds.
-static int run_multi_group(fos_fista* const* fs, int nv, int iters, const float* B, int64_t ldb, const uint8_t* fold_of_row,
-                           const int32_t* held_ids, const fos::FoldHeld* held, const char* fn) {
-  fos_problem* p = fs[0]->p;
-  if (int rc = group_refusal(fs, nv, held_ids, fn)) return rc;
-  if (B ? (p->loss != FOS_LOSS_SQUARED || p->row_weight != nullptr) : (!p->b && (fold_of_row || p->loss != FOS_LOSS_SQUARED || p->row_weight)))
-    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the group penalty (fos_fista_params.group >= 2): a right-hand-side block "
-                                                         "needs the unweighted squared loss, everything else the problem's own b");
-  if (iters == 0) return FOS_OK;
-  if (B) { if (int rc = stage_b16(p, B, ldb, nv)) return rc; }
-  return run_multi_mfma(fs, nv, iters, false, true, B ? p->ws.b16.get() : nullptr, fold_of_row, held);
-}
-static bool any_grouped(fos_fista* const* fs, int nv) {
-  for (int v = 0; v < nv; ++v)
-    if (grouped(fs[v]->prm)) return true;
-  return false;
-}
-// fos_fista_run_multi_rhs: grouped handles on an unweighted squared-loss problem (with or without coordinate data) go to the
-// group route; everything else meets need_squared as before
+// fos_fista_run_multi_rhs: grouped handles on an unweighted squared-loss problem (with or without coordinate data) pass its
+// need_squared - penalty factors compose with the group penalty, and group_refusal refuses bounds itself
 static bool group_takes_block(fos_fista* const* fs, int nv) {
   return any_grouped(fs, nv) && fs[0]->p->loss == FOS_LOSS_SQUARED && fs[0]->p->row_weight == nullptr;
 }
 
-// A multinomial problem: the two matrix-core products with the link kernel between them, for nv / C joint fits of C columns
-// each.  A stop or restart decided per column would break a joint fit, so only plain runs are served, and the columns of a
-// fit share their parameters (and the fold they hold out).
-static int run_multi_softmax(fos_fista* const* fs, int nv, int iters, const uint8_t* fold_of_row, const int32_t* held_ids,
-                             const fos::FoldHeld* held, const char* fn) {
+// Fills *r from the call, or refuses it; launches nothing and touches neither a handle nor device state.  In order: the
+// multinomial loss, the group penalty, the logistic loss / row weights / coordinate data / feature groups (all on the
+// matrix-core pair, for any number of state machines - there is no single-vector or VALU pass for them; a block B met
+// need_squared), the fold masks on the squared loss, and the squared loss on its own b or on B.
+static int lockstep_route(const LockstepCall& c, LockstepRoute* r) {
+  fos_fista* const* fs = c.fs;
+  const int nv = c.nv;
   fos_problem* p = fs[0]->p;
-  if (int rc = group_refusal(fs, nv, held_ids, fn)) return rc;     // the grouped form: G = C, no bounds, one G for all
-  if (!p->b || p->comm || p->col_sharded || !pair_dd_multi_supported(p))
-    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the multinomial loss needs b, an unsharded problem and the matrix-core pair");
-  if (!softmax_groups_ok(p, nv, held_ids))
-    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": on a multinomial problem nv is a multiple of the classes and the handles of "
-                                                         "a class group hold out one fold");
-  bool all_plain, same_family;
-  if (int rc = lockstep_forms(fs, nv, fn, &all_plain, &same_family)) return rc;
-  if (!all_plain)
-    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": a multinomial problem is served plain runs only (no adaptive restart, no "
-                                                         "step or ratio tolerance: a rule decided per column would break the joint fit)");
-  for (int v = 0; v < nv; ++v) {
-    const fos::FistaParams &a = fs[v / p->classes * p->classes]->prm, &c = fs[v]->prm;
-    if (a.tau != c.tau || a.alpha1 != c.alpha1 || a.alpha2 != c.alpha2 || a.delta != c.delta || a.mode != c.mode ||
-        a.prox_kind != c.prox_kind || a.group != c.group)
-      return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the handles of a class group of a multinomial problem carry identical "
-                                                           "parameters");
-  }
-  if (iters == 0) return FOS_OK;
-  return run_multi_mfma(fs, nv, iters, false, same_family, nullptr, fold_of_row, held);
-}
-
-static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, int64_t ldb) {
-  fos_problem* p = fs[0]->p;
-  const bool rhs = B != nullptr;
-  if (p->loss == FOS_LOSS_MULTINOMIAL) return run_multi_softmax(fs, nv, iters, nullptr, nullptr, nullptr, "fos_fista_run_multi");
-  if (any_grouped(fs, nv))
-    return run_multi_group(fs, nv, iters, B, ldb, nullptr, nullptr, nullptr, rhs ? "fos_fista_run_multi_rhs" : "fos_fista_run_multi");
-  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight || has_coord(p))
-    return run_multi_logit(fs, nv, iters, nullptr, nullptr, "fos_fista_run_multi");
-  if (has_fgroups(p)) return run_multi_logit(fs, nv, iters, nullptr, nullptr, "fos_fista_run_multi");   // (a block B met need_squared)
-  if (rhs && (p->comm || p->col_sharded))
-    return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs: row- or column-sharded problems are not served");
-  if (nv == 1) {
-    if (rhs) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs: one column runs as a problem of its own");
-    return fos_fista_run(fs[0], iters);
-  }
-  // B is staged once per call, after the kernel choice and only when there are iterations to run
-  auto stage = [&]() { return rhs ? stage_b16(p, B, ldb, nv) : FOS_OK; };
+  const std::string fn = c.fn;
+  const bool rhs = c.B != nullptr;
   bool all_plain = true, controllable = true, same_family = true;
   for (int v = 0; v < nv; ++v) {
     all_plain = all_plain && plain_run(fs[v]);
     // what the lockstep bookkeeping decides on the device: adaptive restart, step and ratio tolerances (the gradient-norm
     // rule sits BEFORE the update and backtracking needs its own candidates per weight: those run one by one)
     controllable = controllable && fs[v]->prm.tol_grad == 0.0 && !fs[v]->precise && !fs[v]->prm.tau_from_state;
-    const fos::FistaParams &a = fs[0]->prm, &c = fs[v]->prm;
-    same_family = same_family && a.mode == c.mode && a.prox_kind == c.prox_kind && a.delta == c.delta;
+    const fos::FistaParams &a = fs[0]->prm, &q = fs[v]->prm;
+    same_family = same_family && a.mode == q.mode && a.prox_kind == q.prox_kind && a.delta == q.delta;
+  }
+  // the matrix-core pair for whatever follows, unless a squared-loss decision below says otherwise
+  *r = LockstepRoute{ENGINE_MFMA, nullptr, !all_plain, same_family, rhs};
+  // device control (adaptive restart, step / ratio stops) is the bookkeeping of ONE family, and nothing else is decided there
+  auto control_refusal = [&]() {
+    if (!controllable) return fail(FOS_ERR_UNSUPPORTED, fn + ": no gradient-norm rule, fp64 split gradient or device-held step");
+    if (!all_plain && !same_family) return fail(FOS_ERR_UNSUPPORTED, fn + ": a device-controlled lockstep serves one family");
+    return (int)FOS_OK;
+  };
+  if (p->loss == FOS_LOSS_MULTINOMIAL) {
+    // nv / C joint fits of C columns each.  A stop or restart decided per column would break a joint fit, so only plain runs
+    // are served, and the columns of a fit share their parameters (and the fold they hold out).
+    if (int rc = group_refusal(fs, nv, c.held_ids, c.fn)) return rc;     // the grouped form: G = C, no bounds, one G for all
+    if (!p->b || !unsharded_pair(p))
+      return fail(FOS_ERR_UNSUPPORTED, fn + ": the multinomial loss needs b, an unsharded problem and the matrix-core pair");
+    if (!softmax_groups_ok(p, nv, c.held_ids))
+      return fail(FOS_ERR_UNSUPPORTED, fn + ": on a multinomial problem nv is a multiple of the classes and the handles of "
+                                            "a class group hold out one fold");
+    if (int rc = control_refusal()) return rc;
+    if (!all_plain)
+      return fail(FOS_ERR_UNSUPPORTED, fn + ": a multinomial problem is served plain runs only (no adaptive restart, no "
+                                            "step or ratio tolerance: a rule decided per column would break the joint fit)");
+    for (int v = 0; v < nv; ++v)
+      if (!fit_column_agrees(fs, v, p->classes, nullptr))
+        return fail(FOS_ERR_UNSUPPORTED, fn + ": the handles of a class group of a multinomial problem carry identical "
+                                              "parameters");
+    return FOS_OK;
+  }
+  if (any_grouped(fs, nv)) {
+    // nv / G fits of G columns each, for any nv (nv == G == 2 included).  B (the targets of a multi-task fit) is taken by
+    // product 1 for the unweighted squared loss alone.
+    if (int rc = group_refusal(fs, nv, c.held_ids, c.fn)) return rc;
+    if (rhs ? (p->loss != FOS_LOSS_SQUARED || p->row_weight != nullptr)
+            : (!p->b && (c.fold_of_row || p->loss != FOS_LOSS_SQUARED || p->row_weight)))
+      return fail(FOS_ERR_UNSUPPORTED, fn + ": the group penalty (fos_fista_params.group >= 2): a right-hand-side block "
+                                            "needs the unweighted squared loss, everything else the problem's own b");
+    return FOS_OK;
+  }
+  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight || has_coord(p) || has_fgroups(p)) {
+    if (!p->b || !unsharded_pair(p))
+      return fail(FOS_ERR_UNSUPPORTED, fn + ": the logistic loss, row weights and penalty factors / bounds need b, an unsharded problem and the "
+                                            "matrix-core pair");
+    return control_refusal();
+  }
+  if (c.fold_of_row) {
+    // always the two matrix-core products, for any number of state machines: the alternative is a copy of A per fold
+    if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the problem has no b of its own");
+    if (p->comm || p->col_sharded)
+      return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: row- or column-sharded problems are not served");
+    if (!pair_dd_multi_supported(p))
+      return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the shape has no matrix-core pair");
+    return control_refusal();
+  }
+  // the squared loss on the problem's b, or on the columns of B
+  if (rhs && (p->comm || p->col_sharded))
+    return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs: row- or column-sharded problems are not served");
+  if (nv == 1) {
+    if (rhs) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_rhs: one column runs as a problem of its own");
+    r->engine = ENGINE_SINGLE;
+    return FOS_OK;
   }
   const bool shape_ok = batch_supported(p) && !p->pass.colblock && !p->pass.resident && !p->col_sharded;
   // Column-sharded (very wide A): the two products per panel with ONE exchange of the panel's 16 residual columns between
@@ -1086,30 +1085,29 @@ static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, in
     if (!(controllable && same_family))
       return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi: a column-sharded lockstep serves one family without the "
                                        "gradient-norm rule / fp64 gradient / persisted step");
-    if (iters == 0) return FOS_OK;
-    return run_multi_mfma(fs, nv, iters, true, true);
+    r->controlled = true;
+    return FOS_OK;
   }
-  if (!all_plain && controllable && same_family && shape_ok && p->pass.entry != wide_entry(p->dtype) && (nv >= 3 || p->comm)) {
-    if (iters == 0) return FOS_OK;
-    int rc = stage();
-    if (rc) return rc;
-    return run_multi_mfma(fs, nv, iters, true, true, rhs ? p->ws.b16 : nullptr);
-  }
-  const bool streaming = shape_ok && all_plain;
-  // (a sharded problem takes the matrix-core pass for any number of weights: its 16 gradients are one 16 x n all-reduce)
-  MultiLaunch fn = (streaming && !p->pass.tall && !p->comm && p->dtype == FOS_F32 && p->pass.entry != wide_entry(p->dtype)) ? find_multi(p->n, nv, rhs) : nullptr;
   // the two-product pass costs about two single-vector passes per iteration whatever the number of weights: it pays
   // from three weights on (profiles/r02_multilambda.md); two weights without a VALU multi-vector kernel run one by one
-  if (!fn && streaming && p->pass.entry != wide_entry(p->dtype) && (nv >= 3 || p->comm)) {
-    if (iters == 0) return FOS_OK;
-    int rc = stage();
-    if (rc) return rc;
-    return run_multi_mfma(fs, nv, iters, false, same_family, rhs ? p->ws.b16 : nullptr);   // 5..16 weights, n up to 16384, fp32 and bf16
-  }
-  if (!fn) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi: no multi-vector kernel for this shape / configuration");
-  if (iters == 0) return FOS_OK;
-  int rc = stage();
-  if (rc) return rc;
+  // (a sharded problem takes the matrix-core pass for any number of weights: its 16 gradients are one 16 x n all-reduce)
+  const bool pair_pays = shape_ok && p->pass.entry != wide_entry(p->dtype) && (nv >= 3 || p->comm);
+  if (!all_plain && controllable && same_family && pair_pays) return FOS_OK;
+  const bool streaming = shape_ok && all_plain;
+  r->valu = (streaming && !p->pass.tall && !p->comm && p->dtype == FOS_F32 && p->pass.entry != wide_entry(p->dtype)) ? find_multi(p->n, nv, rhs) : nullptr;
+  if (!r->valu && streaming && pair_pays) return FOS_OK;          // 5..16 weights, n up to 16384, fp32 and bf16
+  if (!r->valu) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi: no multi-vector kernel for this shape / configuration");
+  r->engine = ENGINE_VALU;
+  return FOS_OK;
+}
+
+// The VALU multi-vector pass (gemv_multi.hpp): 2..4 plain fp32 state machines, one pass over A for all, an update per handle
+// (their y are vectors of their own).
+static int run_multi_valu(const LockstepCall& c, const LockstepRoute& r) {
+  fos_fista* const* fs = c.fs;
+  const int nv = c.nv;
+  fos_problem* p = fs[0]->p;
+  int rc;
   // workspace: nv interleaved slab sets and rr partials per workgroup
   const int nwg = p->pass.nwg;
   if ((rc = p->pass.slabs.reserve((size_t)nwg * nv * p->n)) || (rc = p->pass.rr_part.reserve((size_t)nwg * nv)) ||
@@ -1126,9 +1124,9 @@ static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, in
     ys.y[v] = f->ynext;
   }
   for (int v = nv; v < 4; ++v) ys.y[v] = ys.y[0];
-  for (int it = 0; it < iters; ++it) {
+  for (int it = 0; it < c.iters; ++it) {
     if ((rc = prof_mark(p, true))) return rc;
-    fn((const float*)p->A, p->lda, rhs ? p->ws.b16 : p->b, p->m, (int)p->n, ys, p->pass.rows_per_wg, p->pass.slabs, p->pass.rr_part, nwg, p->stream);
+    r.valu((const float*)p->A, p->lda, r.stage_b ? p->ws.b16 : p->b, p->m, (int)p->n, ys, p->pass.rows_per_wg, p->pass.slabs, p->pass.rr_part, nwg, p->stream);
     LAUNCH_CHECK();
     if ((rc = prof_mark(p, false))) return rc;
     for (int v = 0; v < nv; ++v) {
@@ -1143,11 +1141,23 @@ static int run_multi(fos_fista* const* fs, int nv, int iters, const float* B, in
   return FOS_OK;
 }
 
+// A lockstep call behind its argument checks: the route (every refusal comes before the iters == 0 return), then B staged once
+// per call and only when there are iterations to run, then the engine.
+static int run_lockstep(const LockstepCall& c) {
+  LockstepRoute r;
+  if (int rc = lockstep_route(c, &r)) return rc;
+  if (c.iters == 0) return FOS_OK;
+  if (r.engine == ENGINE_SINGLE) return fos_fista_run(c.fs[0], c.iters);
+  if (r.stage_b)
+    if (int rc = stage_b16(c.fs[0]->p, c.B, c.ldb, c.nv)) return rc;
+  return r.engine == ENGINE_VALU ? run_multi_valu(c, r) : run_multi_mfma(c, r);
+}
+
 int fos_fista_run_multi(fos_fista* const* fs, int nv, int iters) {
   if (!fs || nv < 1 || nv > fos::BT_NV || iters < 0) return fail(FOS_ERR_ARG, "fos_fista_run_multi: bad argument");
   for (int v = 0; v < nv; ++v)
     if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi: handles must share one problem");
-  return run_multi(fs, nv, iters, nullptr, 0);
+  return run_lockstep(LockstepCall{fs, nv, iters, nullptr, 0, nullptr, nullptr, nullptr, "fos_fista_run_multi"});
 }
 
 int fos_fista_run_multi_rhs(fos_fista* const* fs, int nv, const float* B, int64_t ldb, int iters) {
@@ -1155,10 +1165,8 @@ int fos_fista_run_multi_rhs(fos_fista* const* fs, int nv, const float* B, int64_
     return fail(FOS_ERR_ARG, "fos_fista_run_multi_rhs: bad argument (null pointer, nv outside 1..16, ldb < nv or iters < 0)");
   for (int v = 0; v < nv; ++v)
     if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi_rhs: handles must share one problem");
-  // (grouped handles on the unweighted squared loss pass: penalty factors compose with the group penalty, the group route
-  // refuses bounds itself)
   if (int rc_ = group_takes_block(fs, nv) ? FOS_OK : need_squared(fs[0]->p, "fos_fista_run_multi_rhs")) return rc_;
-  return run_multi(fs, nv, iters, B, ldb);
+  return run_lockstep(LockstepCall{fs, nv, iters, B, ldb, nullptr, nullptr, nullptr, "fos_fista_run_multi_rhs"});
 }
 
 int fos_fista_run_multi_folds(fos_fista* const* fs, int nv, int iters, const uint8_t* fold_of_row, const int32_t* held) {
@@ -1169,22 +1177,7 @@ int fos_fista_run_multi_folds(fos_fista* const* fs, int nv, int iters, const uin
                              "not 4-byte aligned or a held id outside -1..254)");
   for (int v = 0; v < nv; ++v)
     if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, "fos_fista_run_multi_folds: handles must share one problem");
-  fos_problem* p = fs[0]->p;
-  if (p->loss == FOS_LOSS_MULTINOMIAL) return run_multi_softmax(fs, nv, iters, fold_of_row, held, &hb, "fos_fista_run_multi_folds");
-  if (any_grouped(fs, nv)) return run_multi_group(fs, nv, iters, nullptr, 0, fold_of_row, held, &hb, "fos_fista_run_multi_folds");
-  if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight || has_coord(p))
-    return run_multi_logit(fs, nv, iters, fold_of_row, &hb, "fos_fista_run_multi_folds");
-  if (has_fgroups(p)) return run_multi_logit(fs, nv, iters, fold_of_row, &hb, "fos_fista_run_multi_folds");
-  if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the problem has no b of its own");
-  if (p->comm || p->col_sharded)
-    return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: row- or column-sharded problems are not served");
-  if (!pair_dd_multi_supported(p))
-    return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the shape has no matrix-core pair");
-  bool all_plain, same_family;
-  if (int rc = lockstep_forms(fs, nv, "fos_fista_run_multi_folds", &all_plain, &same_family)) return rc;
-  if (iters == 0) return FOS_OK;
-  // always the two matrix-core products, for any number of state machines: the alternative is a copy of A per fold
-  return run_multi_mfma(fs, nv, iters, !all_plain, same_family, nullptr, fold_of_row, &hb);
+  return run_lockstep(LockstepCall{fs, nv, iters, nullptr, 0, fold_of_row, held, &hb, "fos_fista_run_multi_folds"});
 }
 
 // G[j][c] = sum over the row splits of slabs16[split][j][c]: the slab sum of fos_gram_apply.

@@ -237,23 +237,11 @@ __global__ __launch_bounds__(GB_THREADS) void gram_batch_mfma_bf16_kernel(const 
   }
 }
 
-// y_k of state machine `slot` into the candidate block of product 1: fp32 Xp layout, or three bf16 terms (Xq) for bf16 A.
+// y_k of state machine `slot` into the candidate block of product 1 (store_y: YOUT_XP, or YOUT_XQ for bf16 A).
 static __global__ __launch_bounds__(256) void form_y_block_kernel(const double* __restrict__ x_cur, const double* __restrict__ x_prev,
-                                                           double beta, int n, int slot, float* __restrict__ xp,
-                                                           unsigned short* __restrict__ xq) {
-  for (int col = blockIdx.x * 256 + threadIdx.x; col < n; col += gridDim.x * 256) {
-    const float y = (float)form_y(x_cur[col], x_prev[col], beta);
-    if (xp != nullptr) {
-      xp[xp_index(col, slot)] = y;
-    } else {
-      const unsigned short hi = f32_to_bf16_rn(y);
-      const float r1 = y - bf16_to_f32(hi);
-      const unsigned short mid = f32_to_bf16_rn(r1);
-      xq[xq_index(col, slot, 0)] = hi;
-      xq[xq_index(col, slot, 1)] = mid;
-      xq[xq_index(col, slot, 2)] = f32_to_bf16_rn(r1 - bf16_to_f32(mid));
-    }
-  }
+                                                           double beta, int n, int slot, float* __restrict__ y_block, int y_mode) {
+  for (int col = blockIdx.x * 256 + threadIdx.x; col < n; col += gridDim.x * 256)
+    store_y(y_block, y_mode, col, slot, (float)form_y(x_cur[col], x_prev[col], beta));
 }
 
 }  // namespace fos

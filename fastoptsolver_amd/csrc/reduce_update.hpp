@@ -84,6 +84,22 @@ __device__ inline double grad_at(const GradSrc& g, int64_t i) { return g.f64 != 
 
 // where the update kernel leaves y_{k+1} for the next pass over A
 enum : int { YOUT_VECTOR = 0, YOUT_XP = 1, YOUT_XQ = 2 };
+// The one store of a y value: coordinate k of slot s (ignored by YOUT_VECTOR) of y_out under y_mode.
+__device__ inline void store_y(float* __restrict__ y_out, int y_mode, int64_t k, int s, float yn) {
+  if (y_mode == YOUT_VECTOR) {
+    y_out[k] = yn;
+  } else if (y_mode == YOUT_XP) {                      // slot of the multi-lambda block (gram_batch.hpp)
+    y_out[xp_index(k, s)] = yn;
+  } else {                                             // bf16 A: three bf16 terms
+    unsigned short* xq = reinterpret_cast<unsigned short*>(y_out);
+    const unsigned short hi = f32_to_bf16_rn(yn);
+    const float r1 = yn - bf16_to_f32(hi);
+    const unsigned short mid = f32_to_bf16_rn(r1);
+    xq[xq_index(k, s, 0)] = hi;
+    xq[xq_index(k, s, 1)] = mid;
+    xq[xq_index(k, s, 2)] = f32_to_bf16_rn(r1 - bf16_to_f32(mid));
+  }
+}
 
 __device__ inline double soft_threshold(double v, double thr) {
   double mag = fabs(v) - thr;
@@ -358,22 +374,7 @@ __device__ inline void fista_update_body(const float* __restrict__ slabs, int ns
     x_cur[col + e] = xn;
     if (x_hist != nullptr) x_hist[col + e] = xn;      // device-resident history (fos_fista_run_history)
     // plain runs: beta_{k+1} is known, hand the next A pass its y as ONE fp32 vector (same form_y, same rounding)
-    if (y_next != nullptr) {
-      const float yn = (float)form_y(xn, xc, beta_next);
-      if (y_mode == YOUT_VECTOR) {
-        y_next[col + e] = yn;
-      } else if (y_mode == YOUT_XP) {                  // slot of the multi-lambda block (gram_batch.hpp)
-        y_next[xp_index(col + e, y_slot)] = yn;
-      } else {                                         // bf16 A: three bf16 terms
-        unsigned short* xq = reinterpret_cast<unsigned short*>(y_next);
-        const unsigned short hi = f32_to_bf16_rn(yn);
-        const float r1 = yn - bf16_to_f32(hi);
-        const unsigned short mid = f32_to_bf16_rn(r1);
-        xq[xq_index(col + e, y_slot, 0)] = hi;
-        xq[xq_index(col + e, y_slot, 1)] = mid;
-        xq[xq_index(col + e, y_slot, 2)] = f32_to_bf16_rn(r1 - bf16_to_f32(mid));
-      }
-    }
+    if (y_next != nullptr) store_y(y_next, y_mode, col + e, y_slot, (float)form_y(xn, xc, beta_next));
   }
   block_sum_256<4>(acc, dl);
   if (threadIdx.x == 0) {
@@ -397,18 +398,6 @@ __global__ __launch_bounds__(256) void fista_update_kernel(const float* __restri
                                      y_next, beta_next, slab_stride, y_mode, y_slot);
 }
 
-// The per-handle update of the two-product lockstep on a problem with coordinate data (fos_coord_bind): the slab form with
-// float4 epilogues, y_{k+1} into the handle's slot of the candidate block.
-static __global__ __launch_bounds__(256) void fista_update_coord_kernel(const float* __restrict__ slabs, int nslabs, int n,
-                                                                        double* __restrict__ x_cur, double* __restrict__ x_prev,
-                                                                        const FistaScalars* __restrict__ scal, FistaParams prm,
-                                                                        double* __restrict__ part, int host_beta, double beta_val,
-                                                                        float* __restrict__ y_next, double beta_next,
-                                                                        int64_t slab_stride, int y_mode, int y_slot, CoordData cd) {
-  fista_update_body<true, true, true>(slabs, nslabs, GradSrc{nullptr, nullptr}, n, x_cur, x_prev, scal, prm, part, host_beta,
-                                      beta_val, nullptr, y_next, beta_next, slab_stride, y_mode, y_slot, cd);
-}
-
 // The updates of up to 16 lockstep state machines in ONE launch (multi-lambda pass, gram_batch.hpp): blockIdx.y selects
 // the state machine; its slab set is slabs + y*n with slab stride 16*n, its y_{k+1} goes to slot y of the block.
 struct MultiUpdate {
@@ -418,30 +407,24 @@ struct MultiUpdate {
   double* part[BT_NV];
   double beta[BT_NV], beta_next[BT_NV];
   double alpha1[BT_NV], alpha2[BT_NV], tau[BT_NV];
+  int prox_bits;                                // bit v = the prox kind of state machine v (PROX_ENET = 1)
 };
-// host_beta = 0 (controlled runs): beta comes from each state machine's device scalars and no y is written (beta_{k+1} is
-// decided by fista_finalize_multi_kernel behind this launch; form_y_multi_kernel then fills the block).
-static __global__ __launch_bounds__(256) void fista_update_multi_kernel(const float* __restrict__ slabs, int nslabs, int n,
-                                                                MultiUpdate mu, FistaParams prm0, float* __restrict__ y_block,
-                                                                int y_mode, int host_beta = 1) {
+// The weights, the step and the prox kind travel per state machine, so one launch serves plain runs of mixed families too (the
+// update reads nothing else of a handle's parameters).  host_beta = 0 (controlled runs): beta comes from each state machine's
+// device scalars and no y is written (beta_{k+1} is decided by fista_finalize_multi_kernel behind this launch;
+// form_y_multi_kernel then fills the block).  COORD: the problem's coordinate data (fos_coord_bind) - the factors and bounds
+// belong to the columns of A, so all state machines share them.
+template <bool COORD>
+__global__ __launch_bounds__(256) void fista_update_multi_kernel(const float* __restrict__ slabs, int nslabs, int n, MultiUpdate mu,
+                                                                 float* __restrict__ y_block, int y_mode, int host_beta,
+                                                                 CoordData cd) {
   const int v = blockIdx.y;
-  FistaParams prm = prm0;                       // mode / prox kind / delta are common to the path; weights and steps are not
-  prm.alpha1 = mu.alpha1[v]; prm.alpha2 = mu.alpha2[v]; prm.tau = mu.tau[v];
-  fista_update_body<true, true>(slabs + (int64_t)v * n, nslabs, GradSrc{nullptr, nullptr}, n, mu.x_cur[v], mu.x_prev[v], mu.scal[v], prm,
-                                mu.part[v], host_beta, mu.beta[v], nullptr, host_beta ? y_block : nullptr, mu.beta_next[v],
-                                (int64_t)BT_NV * n, y_mode, v);
-}
-
-// ... on a problem with coordinate data: the factors and bounds belong to the columns of A, so all state machines share them
-static __global__ __launch_bounds__(256) void fista_update_multi_coord_kernel(const float* __restrict__ slabs, int nslabs, int n,
-                                                                      MultiUpdate mu, FistaParams prm0, float* __restrict__ y_block,
-                                                                      int y_mode, int host_beta, CoordData cd) {
-  const int v = blockIdx.y;
-  FistaParams prm = prm0;
-  prm.alpha1 = mu.alpha1[v]; prm.alpha2 = mu.alpha2[v]; prm.tau = mu.tau[v];
-  fista_update_body<true, true, true>(slabs + (int64_t)v * n, nslabs, GradSrc{nullptr, nullptr}, n, mu.x_cur[v], mu.x_prev[v],
-                                      mu.scal[v], prm, mu.part[v], host_beta, mu.beta[v], nullptr, host_beta ? y_block : nullptr,
-                                      mu.beta_next[v], (int64_t)BT_NV * n, y_mode, v, cd);
+  if (mu.scal[v]->stopped != 0) return;         // a masked column: nothing is read or written for it (the body asks again)
+  FistaParams prm{};
+  prm.alpha1 = mu.alpha1[v]; prm.alpha2 = mu.alpha2[v]; prm.tau = mu.tau[v]; prm.prox_kind = (mu.prox_bits >> v) & 1;
+  fista_update_body<true, true, COORD>(slabs + (int64_t)v * n, nslabs, GradSrc{nullptr, nullptr}, n, mu.x_cur[v], mu.x_prev[v],
+                                       mu.scal[v], prm, mu.part[v], host_beta, mu.beta[v], nullptr, host_beta ? y_block : nullptr,
+                                       mu.beta_next[v], (int64_t)BT_NV * n, y_mode, v, cd);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -464,23 +447,9 @@ static __global__ __launch_bounds__(256) void fista_update_multi_coord_kernel(co
 // the owners are threads 0..15, so the partial sums are sums over wave 0.  With the 4 KiB of the slab reduction a workgroup
 // holds 12 KiB of LDS: at 256 threads the wave slots, not the LDS, bound the workgroups per CU.
 // ---------------------------------------------------------------------------------------------------------
-__device__ inline void write_y_block(float* __restrict__ y_block, int y_mode, int64_t k, int slot, float yn) {
-  if (y_mode == YOUT_XP) {
-    y_block[xp_index(k, slot)] = yn;
-  } else {                                             // bf16 A: three bf16 terms
-    unsigned short* xq = reinterpret_cast<unsigned short*>(y_block);
-    const unsigned short hi = f32_to_bf16_rn(yn);
-    const float r1 = yn - bf16_to_f32(hi);
-    const unsigned short mid = f32_to_bf16_rn(r1);
-    xq[xq_index(k, slot, 0)] = hi;
-    xq[xq_index(k, slot, 1)] = mid;
-    xq[xq_index(k, slot, 2)] = f32_to_bf16_rn(r1 - bf16_to_f32(mid));
-  }
-}
-
-// prox_bits: bit s = the prox kind of fit s (PROX_ENET = 1); factor: the penalty factors of fos_coord_bind or null (all 1)
+// the prox kind of a fit is that of its first column; factor: the penalty factors of fos_coord_bind or null (all 1)
 static __global__ __launch_bounds__(256) void fista_update_group_kernel(const float* __restrict__ slabs, int nslabs, int n,
-                                                                        MultiUpdate mu, int G, int prox_bits,
+                                                                        MultiUpdate mu, int G,
                                                                         float* __restrict__ y_block, int y_mode,
                                                                         const float* __restrict__ factor) {
   const int seg = blockIdx.y, v0 = seg * G;
@@ -492,7 +461,7 @@ static __global__ __launch_bounds__(256) void fista_update_group_kernel(const fl
   const int col = col0 + 4 * q;
   const bool owner = (grp == 0) && (col < n);
   const int cnt = owner ? (n - col < 4 ? n - col : 4) : 0;      // ragged n (padded slab rows): the last quad is partial
-  const int prox_kind = (prox_bits >> seg) & 1;
+  const int prox_kind = (mu.prox_bits >> v0) & 1;
   const double tau = mu.tau[v0], alpha1 = mu.alpha1[v0], alpha2 = mu.alpha2[v0];
   f32x4 pf4 = {1.f, 1.f, 1.f, 1.f};
   if (cnt > 0 && factor != nullptr) pf4 = *reinterpret_cast<const f32x4*>(factor + col);
@@ -549,7 +518,7 @@ static __global__ __launch_bounds__(256) void fista_update_group_kernel(const fl
         a3 += xn * xn;
         xp_p[col + e] = xc;
         xc_p[col + e] = xn;
-        write_y_block(y_block, y_mode, col + e, v, (float)form_y(xn, xc, beta_next));
+        store_y(y_block, y_mode, col + e, v, (float)form_y(xn, xc, beta_next));
       }
     }
     a0 = wave_sum(a0); a2 = wave_sum(a2); a3 = wave_sum(a3);
@@ -590,9 +559,8 @@ struct FeatureGroupData {
   double l1_mix;
 };
 
-// prox_bits: bit v = the prox kind of state machine v (PROX_ENET = 1)
 static __global__ __launch_bounds__(256) void fgroup_form_u_kernel(const float* __restrict__ slabs, int nslabs, int n, MultiUpdate mu,
-                                                                   int prox_bits, int host_beta, FeatureGroupData fg) {
+                                                                   int host_beta, FeatureGroupData fg) {
   const int v = blockIdx.y;
   if (mu.scal[v]->stopped != 0) return;
   __shared__ f32x4 lds[RG][RQ];
@@ -603,7 +571,7 @@ static __global__ __launch_bounds__(256) void fgroup_form_u_kernel(const float* 
   const bool owner = (grp == 0) && (col < n);
   const f32x4 tot = reduce_slab_block(slabs + (int64_t)v * n, nslabs, n, col0, lds, (int64_t)BT_NV * n);
   const int cnt = owner ? (n - col < 4 ? n - col : 4) : 0;      // ragged n (padded slab rows): the last quad is partial
-  const int prox_kind = (prox_bits >> v) & 1;
+  const int prox_kind = (mu.prox_bits >> v) & 1;
   const double beta = host_beta ? mu.beta[v] : mu.scal[v]->beta;
   const double tau = mu.tau[v], alpha1 = mu.alpha1[v], alpha2 = mu.alpha2[v];
   const double thr = tau * alpha1 * fg.l1_mix;                   // mix = 1: tau * alpha1, the threshold of the plain update
@@ -646,7 +614,7 @@ static __global__ __launch_bounds__(64 * FG_WAVES) void fgroup_norm_kernel(Multi
 
 __device__ inline int quad_lane(const int4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
 
-static __global__ __launch_bounds__(256) void fgroup_scale_kernel(int n, MultiUpdate mu, int prox_bits, float* __restrict__ y_block,
+static __global__ __launch_bounds__(256) void fgroup_scale_kernel(int n, MultiUpdate mu, float* __restrict__ y_block,
                                                                   int y_mode, int host_beta, FeatureGroupData fg) {
   const int v = blockIdx.y;
   if (mu.scal[v]->stopped != 0) return;
@@ -655,7 +623,7 @@ static __global__ __launch_bounds__(256) void fgroup_scale_kernel(int n, MultiUp
   const int col = blockIdx.x * RCOLS + 4 * q;
   const bool owner = (grp == 0) && (col < n);
   const int cnt = owner ? (n - col < 4 ? n - col : 4) : 0;
-  const int prox_kind = (prox_bits >> v) & 1;
+  const int prox_kind = (mu.prox_bits >> v) & 1;
   const double tau = mu.tau[v], alpha1 = mu.alpha1[v], alpha2 = mu.alpha2[v];
   const double shrink = 1.0 / (1.0 + tau * alpha2);
   const double gcoef = tau * alpha1 * (1.0 - fg.l1_mix);         // thr_g = gcoef * w_g; 0: no group step (mix = 1, alpha1 = 0)
@@ -686,7 +654,7 @@ static __global__ __launch_bounds__(256) void fgroup_scale_kernel(int n, MultiUp
       xp_p[col + e] = xc;
       xc_p[col + e] = xn;
       // plain runs: beta_{k+1} is known; controlled runs leave y to form_y_multi_kernel behind the bookkeeping
-      if (host_beta) write_y_block(y_block, y_mode, col + e, v, (float)form_y(xn, xc, beta_next));
+      if (host_beta) store_y(y_block, y_mode, col + e, v, (float)form_y(xn, xc, beta_next));
     }
   }
   block_sum_256<3>(acc, dl);
@@ -805,18 +773,7 @@ static __global__ __launch_bounds__(256) void form_y_multi_kernel(MultiControl m
   if (!force && mc.scal[v]->stopped != 0) return;
   const double beta = mc.scal[v]->beta;
   for (int col = blockIdx.x * 256 + threadIdx.x; col < n; col += gridDim.x * 256) {
-    const float yn = (float)form_y(mc.x_cur[v][col], mc.x_prev[v][col], beta);
-    if (y_mode == YOUT_XP) {
-      y_block[xp_index(col, v)] = yn;
-    } else {
-      unsigned short* xq = reinterpret_cast<unsigned short*>(y_block);
-      const unsigned short hi = f32_to_bf16_rn(yn);
-      const float r1 = yn - bf16_to_f32(hi);
-      const unsigned short mid = f32_to_bf16_rn(r1);
-      xq[xq_index(col, v, 0)] = hi;
-      xq[xq_index(col, v, 1)] = mid;
-      xq[xq_index(col, v, 2)] = f32_to_bf16_rn(r1 - bf16_to_f32(mid));
-    }
+    store_y(y_block, y_mode, col, v, (float)form_y(mc.x_cur[v][col], mc.x_prev[v][col], beta));
   }
 }
 

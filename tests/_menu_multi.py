@@ -79,7 +79,7 @@ def is_tall(dtype, n):
 
 
 def lockstep_form(dtype, n, nv, rhs):
-    """run_multi (fos_fista.hip) for plain runs on an aligned, unsharded problem of 65..16384 columns:
+    """lockstep_route (fos_fista.hip) for plain runs on an aligned, unsharded problem of 65..16384 columns:
     single (one handle: fos_fista_run), valu (find_multi), mfma (run_multi_mfma) or refused (FOS_ERR_UNSUPPORTED)."""
     if nv == 1:
         return "refused" if rhs == "B" else "single"
@@ -279,7 +279,7 @@ def build(cus):
         add("dd", dtype, "residual", "p1", "dd", _dd_small(dtype)[:3] + _dd_acc(dtype, cus)[:1])
         add("dd", dtype, "gram", "first", "dd", _dd_small(dtype))
         add("dd", dtype, "gram", "acc", "dd", _dd_acc(dtype, cus))
-    # the second run with alpha1 > 0 (the prox step of fista_update_multi_kernel / the per-handle update): one cell per family
+    # the second run with alpha1 > 0 (the prox step of fista_update_multi_kernel / the per-handle update of the VALU pass): one cell per family
     for key, i in ((("valu", "f32", "256x4", "nvec4"), 1), (("valu", "f32", "512x4", "nvec3-B"), 2),
                    (("p1", "f32", "RB1", "store"), 2), (("p2", "bf16", "gram", "first"), 1),
                    (("cluster", "f32", "cs8", "pass"), 0)):

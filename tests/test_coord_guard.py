@@ -40,15 +40,18 @@ def test_no_refusing_body_names_the_new_fields():
 
 def test_the_serving_dispatchers_send_coordinate_data_to_the_two_product_lockstep():
     text = _text(FISTA)
-    multi = _body(text, r"static\s+int\s+run_multi\s*\([^)]*\)\s*(?=\{)")
-    first = multi.index("run_multi_logit")
-    assert re.search(r"if\s*\(\s*p->loss\s*==\s*FOS_LOSS_LOGISTIC\s*\|\|\s*p->row_weight\s*\|\|\s*has_coord\(p\)\s*\)\s*return\s+run_multi_logit",
-                     multi)
-    assert "fos_fista_run(" not in multi[:first] and "launch_cluster_pass" not in multi[:first]
-    folds = gd.body_of("fos_fista_run_multi_folds")
-    assert re.search(r"p->row_weight\s*\|\|\s*has_coord\(p\)\s*\)\s*return\s+run_multi_logit", folds)
+    # one branch of the one route decision serves both entry points: the matrix-core pair (the route's default engine), for
+    # any nv - the single run, the VALU pass and the cluster form are decided behind it, for the plain squared loss alone
+    route = _body(text, r"static\s+int\s+lockstep_route\s*\([^)]*\)\s*(?=\{)")
+    m = re.search(r"if\s*\(\s*p->loss\s*==\s*FOS_LOSS_LOGISTIC\s*\|\|\s*p->row_weight\s*\|\|\s*has_coord\(p\)\s*\|\|\s*has_fgroups\(p\)\s*\)\s*\{", route)
+    assert m and re.search(r"\*r\s*=\s*LockstepRoute\{ENGINE_MFMA,", route[:m.start()])
+    branch = _body(route[m.start():], r"has_fgroups\(p\)\s*\)\s*(?=\{)")
+    assert re.search(r"return\s+control_refusal\(\)\s*;\s*$", branch.strip()) and "engine" not in branch
+    assert "ENGINE_SINGLE" not in route[:m.start()] and "ENGINE_VALU" not in route[:m.start()] and "launch_cluster_pass" not in route
+    for name in ("fos_fista_run_multi", "fos_fista_run_multi_folds"):
+        assert re.search(r"return\s+run_lockstep\(LockstepCall\{", gd.body_of(name)), name
     mfma = _body(text, r"static\s+int\s+run_multi_mfma\s*\([^)]*\)\s*(?=\{)")
-    assert re.search(r"two_products\s*=\s*b16\s*\|\|\s*fold_of_row\s*\|\|\s*logit\s*\|\|\s*weighted\s*\|\|\s*coord\s*;", mfma)
+    assert re.search(r"const\s+bool\s+two_products\s*=\s*b16\s*\|\|\s*fold_of_row\s*\|\|\s*logit\s*\|\|\s*weighted\s*\|\|\s*has_coord\(p\)\s*\|\|", mfma)
     # fos_residual_batch keeps its rule: use_b = 1 is served (the data term does not depend on the coordinate data)
     rb = gd.body_of("fos_residual_batch")
     assert re.search(r"if\s*\(\s*!use_b\s*\)[^;]*" + gd.GUARD, rb, flags=re.S) and "has_coord" not in rb

@@ -112,11 +112,15 @@ def test_the_guard_reaches_the_feature_group_refusal_and_the_dispatchers_serve_i
     assert "fos_feature_groups_bind" in refusal and "std::string(fn)" in refusal     # a message of its own, naming the caller
     assert "hipLaunchKernelGGL" not in refusal and not re.search(r"->\w+\s*=[^=]", refusal)
     text = _text(FISTA)
-    multi = _body(text, r"static\s+int\s+run_multi\s*\([^)]*\)\s*(?=\{)")
-    assert re.search(r"if\s*\(has_fgroups\(p\)\)\s*return\s+run_multi_logit", multi)
-    assert re.search(r"if\s*\(has_fgroups\(p\)\)\s*return\s+run_multi_logit", gd.body_of("fos_fista_run_multi_folds"))
+    # both entry points reach the matrix-core pair through the pair-only branch of the one route decision
+    route = _body(text, r"static\s+int\s+lockstep_route\s*\([^)]*\)\s*(?=\{)")
+    m = re.search(r"if\s*\([^{]*\|\|\s*has_fgroups\(p\)\s*\)\s*\{", route)
+    assert m and re.search(r"\*r\s*=\s*LockstepRoute\{ENGINE_MFMA,", route[:m.start()])
+    assert "engine" not in _body(route[m.start():], r"has_fgroups\(p\)\s*\)\s*(?=\{)")
+    for name in ("fos_fista_run_multi", "fos_fista_run_multi_folds"):
+        assert re.search(r"return\s+run_lockstep\(LockstepCall\{", gd.body_of(name)), name
     mfma = _body(text, r"static\s+int\s+run_multi_mfma\s*\([^)]*\)\s*(?=\{)")
-    assert re.search(r"two_products\s*=\s*two_products\s*\|\|\s*fgroup\s*;", mfma) and "launch_fgroup_update" in mfma
+    assert re.search(r"const\s+bool\s+two_products\s*=[^;]*\|\|\s*fgroup\s*;", mfma) and "launch_fgroup_update" in mfma
     assert "has_fgroups(p)" in _body(text, r"static\s+int\s+group_refusal\s*\([^)]*\)\s*(?=\{)")
 
 

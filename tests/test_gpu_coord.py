@@ -82,7 +82,7 @@ def test_cells_match_the_reference(fos, cus, name, kind, form, prox):
     elif form == "one-launch-controlled":
         ctl, keep = cd.controlled(*key)              # decisions fp32 cannot take the other way, chosen on the reference alone
         specs = [(a1, a2, None, str(cd.CONTROL_MENU.index(ctl))) for a1, a2 in keep]
-    else:                                        # two families in one call: the per-handle update launches
+    else:                                        # two families in one call: the same one launch, the prox kind per column
         specs = [(a[1][0], a[1][1], None, False), (a[2][0], a[2][1], 3.0, False), (a[1][0], a[1][1], 3.0, False)]
     hs = []
     for a1, a2, delta, ctrl in specs:

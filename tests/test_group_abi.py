@@ -1,8 +1,8 @@
 """CPU: the group penalty is a solver parameter - fos_fista_params.group stands where `reserved` stood, the struct keeps its size
 and the ABI its version, no handle-taking entry point was added; fos_fista_reset refuses a bad group before any HIP call; the
 packing and right-hand-side tiling of multitask_path are what the documentation says; bad arguments are ValueErrors before any
-device work; every single-handle entry point calls the one group guard before anything launch-like and the grouped update sits
-in front of the two update sites of run_multi_mfma."""
+device work; every single-handle entry point calls the one group guard before anything launch-like and the grouped update takes the
+place of the one separable update launch of run_multi_mfma."""
 import ctypes
 import inspect
 import os
@@ -216,26 +216,46 @@ def test_the_batch_entry_point_refuses_grouped_parameters_before_its_first_copy(
     assert not re.search(r"hipLaunchKernelGGL|hipMemcpy|hipMemset", body[:m.start()])
 
 
-def test_the_grouped_update_sits_in_front_of_the_two_update_sites():
+def test_the_grouped_update_takes_the_place_of_the_separable_launch():
+    from tests import _menu_coord as mc
     text = _text(FISTA)
     mfma = _body(text, r"static\s+int\s+run_multi_mfma\s*\([^)]*\)\s*(?=\{)")
-    m = re.search(r"if\s*\(\s*group_penalty\s*\)\s*\{\s*if\s*\(\(rc\s*=\s*launch_group_update\([^;]*\)\)\)\s*return\s+rc;\s*\}\s*else\s+if\s*\(\s*"
-                  r"controlled\s*\|\|\s*same_family\s*\)\s*\{", mfma)
-    assert m, "the grouped branch of run_multi_mfma"
-    assert m.start() < mfma.index("fista_update_multi_coord_kernel") < mfma.index("fista_update_coord_kernel")
+    # the update stage: feature groups, else the group penalty, else the one separable launch - each launcher named once
+    m = re.search(mc.UPDATE_STAGE, mfma)
+    assert m, "the update stage of run_multi_mfma"
+    assert mfma.index("launch_group_update") < mfma.index("launch_separable_update")
     assert mfma.count("launch_group_update") == 1 and "fista_update_group_kernel" not in mfma
-    assert re.search(r"two_products\s*=\s*two_products\s*\|\|\s*group_penalty\s*;", mfma)          # never the cluster form
+    assert mfma.count("launch_separable_update") == 1 and "fista_update_multi_kernel" not in mfma
+    # never the cluster form: the one expression of two_products names the group penalty
+    assert re.search(r"const\s+bool\s+two_products\s*=[^;]*\|\|\s*group_penalty\b[^;]*;", mfma) and len(re.findall(r"\btwo_products\s*=[^=]", mfma)) == 1
     helper = _body(text, r"static\s+int\s+launch_group_update\s*\([^)]*\)\s*(?=\{)")
     assert re.search(r"fos::fista_update_group_kernel,\s*dim3\(fs\[0\]->nupd,\s*nv\s*/\s*G\),\s*dim3\(256\)", helper)
-    # the dispatchers ask the one refusal helper before the lockstep: the multinomial route, the group route
-    for route in ("run_multi_softmax", "run_multi_group"):
-        body = _body(text, r"static\s+int\s+" + route + r"\s*\([^)]*\)\s*(?=\{)")
-        assert body.index("group_refusal(") < body.index("run_multi_mfma("), route
+    # one launch site each in the whole unit
+    for kernel in ("fista_update_multi_kernel", "fista_update_group_kernel", "fgroup_form_u_kernel", "fgroup_norm_kernel", "fgroup_scale_kernel"):
+        assert len(re.findall(r"fos::" + kernel + r"\b", text)) == (2 if kernel == "fista_update_multi_kernel" else 1), kernel
+    assert text.count("hipLaunchKernelGGL(kern, dim3(fs[0]->nupd, nv)") == 1      # (<true> and <false> meet in that one launch)
+    # the route decision asks the one refusal helper before anything runs: on the multinomial branch and on the group branch,
+    # and the executor decides the route before its first launch
+    route = _body(text, r"static\s+int\s+lockstep_route\s*\([^)]*\)\s*(?=\{)")
+    assert len(re.findall(r"group_refusal\(fs,\s*nv,\s*c\.held_ids,\s*c\.fn\)", route)) == 2
+    soft, group = route.index("p->loss == FOS_LOSS_MULTINOMIAL"), route.index("any_grouped(fs, nv)")
+    first = [route.index("group_refusal(", at) for at in (soft, group)]
+    assert soft < first[0] < group < first[1] and "FOS_ERR_UNSUPPORTED" not in route[soft:first[0]] + route[group:first[1]]
+    assert "hipLaunchKernelGGL" not in route and "run_multi_mfma" not in route and not re.search(r"[^r]->\w+\s*=[^=]", route)
+    run = _body(text, r"static\s+int\s+run_lockstep\s*\([^)]*\)\s*(?=\{)")
+    assert run.index("lockstep_route(c, &r)") < run.index("c.iters == 0") < run.index("stage_b16(") < run.index("run_multi_mfma(c, r)")
     refusal = _body(text, r"static\s+int\s+group_refusal\s*\([^)]*\)\s*(?=\{)")
     assert "FOS_ERR_ARG" not in refusal and "hipLaunchKernelGGL" not in refusal and not re.search(r"->\w+\s*=[^=]", refusal)
     for cond in (r"nv\s*%\s*G", r"p->classes", r"p->coord_lo\s*\|\|\s*p->coord_hi", r"plain_run\(f\)", r"f->precise", r"tau_from_state",
-                 r"p->comm\s*\|\|\s*p->col_sharded", r"pair_dd_multi_supported\(p\)", r"a\.group\s*!=\s*c\.group"):
+                 r"!unsharded_pair\(p\)", r"!fit_column_agrees\(fs,\s*v,\s*G,\s*held\)"):
         assert re.search(cond, refusal), cond
+    # ... and the two shared helpers it calls hold the conditions it used to spell out
+    pair = _body(text, r"static\s+bool\s+unsharded_pair\s*\([^)]*\)\s*(?=\{)")
+    assert re.search(r"!p->comm\s*&&\s*!p->col_sharded\s*&&\s*pair_dd_multi_supported\(p\)", pair)
+    agrees = _body(text, r"static\s+bool\s+fit_column_agrees\s*\([^)]*\)\s*(?=\{)")
+    for cond in (r"a\.group\s*==\s*c\.group", r"a\.tau\s*==\s*c\.tau", r"a\.alpha1\s*==\s*c\.alpha1", r"a\.alpha2\s*==\s*c\.alpha2", r"a\.delta\s*==\s*c\.delta",
+                 r"a\.mode\s*==\s*c\.mode", r"a\.prox_kind\s*==\s*c\.prox_kind", r"held\s*&&\s*held\[v\]\s*!=\s*held\[v0\]"):
+        assert re.search(cond, agrees), cond
 
 
 def test_the_group_kernel_has_no_atomics_flags_or_waits():

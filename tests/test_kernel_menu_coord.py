@@ -1,5 +1,5 @@
-"""CPU guard: the coverage table of the coordinate update cells (tests/_menu_coord.py) is in step with the two update launch
-sites of run_multi_mfma and with the COORD form of the update body, and its shapes are the ones the update can go wrong at."""
+"""CPU guard: the coverage table of the coordinate update cells (tests/_menu_coord.py) is in step with the one separable update
+launch behind run_multi_mfma and with the COORD form of the update body, and its shapes are the ones the update can go wrong at."""
 import pytest
 
 from tests import _menu_coord as mc, _menu_cv
@@ -27,11 +27,12 @@ def test_shapes(cus):
 
 
 def test_guard_names_a_removed_branch(tmp_path):
-    """The guard itself: a launch site or a prox kind removed from a copy of the source fails naming the cell."""
+    """The guard itself: the coordinate form, the per-column prox kind or a prox kind of the body removed from a copy of the source
+    fails naming the cell."""
     fista, upd = _text(mc.FISTA), _text(mc.UPDATE)
     cuts = (
-        (fista, "fos_fista.hip", "      if (coord)\n        hipLaunchKernelGGL(fos::fista_update_multi_coord_kernel", "      if (false)\n        hipLaunchKernelGGL(fos::fista_update_multi_coord_kernel", "upd/bf16/one-launch-controlled/PROX_ENET"),
-        (fista, "fos_fista.hip", "        if (coord) {\n          hipLaunchKernelGGL(fos::fista_update_coord_kernel", "        if (false) {\n          hipLaunchKernelGGL(fos::fista_update_coord_kernel", "upd/f32/per-handle-plain/PROX_L1"),
+        (fista, "fos_fista.hip", "has_coord(p) ? fos::fista_update_multi_kernel<true>", "false ? fos::fista_update_multi_kernel<true>", "upd/bf16/one-launch-controlled/PROX_ENET"),
+        (fista, "fos_fista.hip", "    mu.prox_bits |= (f->prm.prox_kind == fos::PROX_ENET ? 1 : 0) << v;\n", "", "upd/f32/mixed-families-plain/PROX_L1"),
         (upd, "reduce_update.hpp", "      if (prm.prox_kind == PROX_ENET) xn *= 1.0 / (1.0 + tau * a2p);\n", "", "upd/f32/one-launch-plain/PROX_ENET"),
     )
     for text, name, old, new, cell in cuts:

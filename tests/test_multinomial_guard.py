@@ -36,15 +36,21 @@ def test_the_guard_names_the_loss_it_refuses():
 
 def test_the_dispatchers_take_the_link_kernel_route_first():
     text = _text(FISTA)
-    multi = _body(text, r"static\s+int\s+run_multi\s*\([^)]*\)\s*(?=\{)")
-    assert multi.index("run_multi_softmax") < multi.index("run_multi_logit")
-    folds = gd.body_of("fos_fista_run_multi_folds")
-    assert folds.index("run_multi_softmax") < folds.index("run_multi_logit")
-    route = _body(text, r"static\s+int\s+run_multi_softmax\s*\([^)]*\)\s*(?=\{)")
-    # every refusal of the route is FOS_ERR_UNSUPPORTED and sits before the one call that launches
-    assert "FOS_ERR_ARG" not in route and len(re.findall(r"FOS_ERR_UNSUPPORTED", route)) == 4
-    assert route.rindex("FOS_ERR_UNSUPPORTED") < route.index("run_multi_mfma(")
-    assert "hipLaunchKernelGGL" not in route and not re.search(r"->\w+\s*=[^=]", route)
+    # both entry points go through the one route decision, whose multinomial branch comes before every other
+    for name in ("fos_fista_run_multi", "fos_fista_run_multi_folds"):
+        assert re.search(r"return\s+run_lockstep\(LockstepCall\{", gd.body_of(name)), name
+    decide = _body(text, r"static\s+int\s+lockstep_route\s*\([^)]*\)\s*(?=\{)")
+    soft = decide.index("if (p->loss == FOS_LOSS_MULTINOMIAL) {")
+    assert soft < decide.index("any_grouped(fs, nv)") < decide.index("p->loss == FOS_LOSS_LOGISTIC") < decide.index("if (c.fold_of_row)")
+    shared = _body(decide, r"control_refusal\s*=\s*\[&\]\(\)\s*(?=\{)")          # (defined ahead of the branches, called inside them)
+    assert "FOS_ERR_UNSUPPORTED" not in decide[:soft].replace(shared, "")
+    route = _body(decide, r"if\s*\(p->loss\s*==\s*FOS_LOSS_MULTINOMIAL\)\s*(?=\{)")
+    # every refusal of the branch is FOS_ERR_UNSUPPORTED (four of its own, the shared control refusal, the group refusal) and
+    # the branch ends by accepting; nothing in the whole decision launches or assigns to a handle or the problem
+    assert "FOS_ERR_ARG" not in decide and len(re.findall(r"FOS_ERR_UNSUPPORTED", route)) == 4
+    assert "control_refusal()" in route and "group_refusal(" in route and re.search(r"return\s+FOS_OK\s*;\s*$", route.strip())
+    assert route.rindex("FOS_ERR_UNSUPPORTED") < route.rindex("return FOS_OK")
+    assert "hipLaunchKernelGGL" not in decide and "run_multi_mfma" not in decide and not re.search(r"[^r]->\w+\s*=[^=]", decide)
     mfma = _body(text, r"static\s+int\s+run_multi_mfma\s*\([^)]*\)\s*(?=\{)")
     # product 1 gets neither b nor the mask nor the weights, and the link kernel sits before product 2 of the panel
     assert re.search(r"if\s*\(softmax\)\s*\{\s*L\.b\s*=\s*nullptr;\s*L\.use_b\s*=\s*0;\s*L\.fold_of_row\s*=\s*nullptr;\s*L\.held\s*=\s*nullptr;\s*"
