@@ -474,6 +474,7 @@ int fos_fista_run(fos_fista* f, int iters) {
   if (int rc_ = need_separable(f, "fos_fista_run")) return rc_;
   fos_problem* p = f->p;
   if (iters == 0) return FOS_OK;
+  if (int rc_ = ensure_packed(p)) return rc_;      // first run of a plan: the 28-bit copy of A, where it is served
   if (p->pass.resident) return run_resident(f, iters, nullptr, nullptr);
   // Tall-skinny runs without backtracking / history: A in the LDS of up to all CUs, one grid barrier per iteration
   // (chip_resident.hpp); adaptive restart and the step / ratio stops are decided on the device by every workgroup alike.  The
@@ -1338,6 +1339,7 @@ static int run_device_driven(fos_fista* f, int iters, bool backtracking, double 
   fos_problem* p = f->p;
   int rc = flush_pending(f);
   if (rc) return rc;
+  if ((rc = ensure_packed(p))) return rc;
   if (backtracking) {
     if ((rc = ensure_batch_workspace(p))) return rc;
     // the step lives on the device from here on (tau persists, :197)

@@ -241,6 +241,21 @@ struct CandPlan {
   void reset() { *this = CandPlan{}; }
 };
 
+// 28-bit packed copy of an fp32 A for the gradient pass (gemv_packed.hpp).  From: A's contents at pack time, shape, the fp32
+// pass group (streaming single pass, its grid and row order are reused), pack_mode, free device memory.  Filled by
+// ensure_packed on the first call of the fos_fista_run family; `tried` keeps a refused matrix from being examined again.
+struct PackPlan {
+  bool tried = false, active = false;
+  int threads = 0;                   // geometry the rows are laid out for: 1024 (n <= 16384) or 512 (n <= 8192)
+  unsigned e0 = 0;                   // first biased exponent of the 16-binade window (even)
+  int64_t nnz = 0;                   // out-of-window elements
+  DevBuf<unsigned char> P;           // m rows of pk::row_bytes(threads)
+  DevBuf<int> csr_ptr, csr_col, csc_ptr, csc_row;       // D = A - P, row-sorted and column-sorted
+  DevBuf<float> csr_tv, csr_pv, csc_tv, csc_pv;         // per exception: the true value and the stored placeholder
+  DevBuf<float> bprime, r;           // m floats each: b - D y, and the residual the pass stores
+  void reset() { *this = PackPlan{}; }
+};
+
 // Feature groups of the lockstep's update (fos_feature_groups_bind; reduce_update.hpp).  From: the caller's table alone - no plan
 // input enters, so fosapi::invalidate leaves the group as it is; a second bind overwrites it, a detaching bind and the
 // destruction of the problem reset it.  Filled by fos_feature_groups_bind, which reserves everything once.
@@ -302,6 +317,7 @@ struct fos_problem {
   int dd_nwg_hint = 0;               // fos_problem_tune_dd: workgroups of the streaming fp64 pass (0 = planner)
   int cp_mode = 0;                   // 0: planner's choice, 1: FOS_PLAN_CLUSTER, 2: FOS_PLAN_NO_CLUSTER
   int chip_mode = 0;                 // 0: planner (fos_fista_run_chip where it measured ahead), 1: FOS_PLAN_CHIP_RESIDENT, 2: never
+  int pack_mode = 0;                 // 0: planner (from the break-even size on), 1: FOS_PLAN_PACK, 2: FOS_PLAN_NO_PACK
   bool fused_on = false;             // FOS_PLAN_FUSED_MFMA: plain fos_fista_run calls take fos_fista_run_fused where served
   unsigned cp_epoch = 1;             // launch epoch of the one-read cluster pass
   // decisions and the workspace they size
@@ -310,6 +326,7 @@ struct fos_problem {
   MultiPlan multi;
   DdMultiPlan dm;
   CandPlan cand;
+  PackPlan pk;
   FeatureGroups fg;
   Scratch ws;
   std::unique_ptr<LbfgsWork> lbfgs;              // fos_lbfgs_minimize workspace, allocated by the first fit
@@ -389,6 +406,8 @@ int plan_multi_mfma(fos_problem* p);
 int ensure_workspace(fos_problem* p);
 int ensure_batch_workspace(fos_problem* p);
 int ensure_dd(fos_problem* p);
+// Make the packed copy of A where the plan, the data and free memory allow (PackPlan); a refusal is not an error.  Synchronises.
+int ensure_packed(fos_problem* p);
 int prof_drain(fos_problem* p);
 int prof_mark(fos_problem* p, bool start);
 int aligned_vec(fos_problem* p, const float* v, const float** out);

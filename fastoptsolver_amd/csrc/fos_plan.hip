@@ -2,6 +2,7 @@
 // (include/fos.h).  Host code only decides launch geometry and enqueues kernels; there is no CPU compute fallback.
 #include "fos_internal.hpp"
 #include "softmax_link.hpp"
+#include "gemv_packed.hpp"
 
 namespace fosapi {
 
@@ -399,8 +400,10 @@ int prof_mark(fos_problem* p, bool start) {
 // Enqueue the A pass for `ys`.  with_g: also produce the slabs (A^T r).  Returns number of rr partials.
 int launch_pass_inner(fos_problem* p, const YSource& ys, const float* b, bool with_g, int* n_rr, bool dual, double* rr_to);
 int launch_pass(fos_problem* p, const YSource& ys, const float* b, bool with_g, int* n_rr, bool dual, double* rr_to) {
-  int rc = prof_mark(p, true);
-  if (rc) return rc;
+  int rc;
+  // FOS_PLAN_PACK: the first with-gradient pass of ANY entry point packs (the planner's own choice waits for a FISTA run)
+  if (p->pack_mode == 1 && !p->pk.tried && with_g && !dual && (rc = ensure_packed(p))) return rc;
+  if ((rc = prof_mark(p, true))) return rc;
   if ((rc = launch_pass_inner(p, ys, b, with_g, n_rr, dual, rr_to))) return rc;
   return prof_mark(p, false);
 }
@@ -501,8 +504,180 @@ int launch_pass_colblock(fos_problem* p, const YSource& ys, const float* b, bool
   return FOS_OK;
 }
 
+// ---- 28-bit packed copy of an fp32 A for the gradient pass (gemv_packed.hpp; PackPlan) ------------------------------------
+// Where the planner packs without being asked (FOS_PLAN_PACK packs wherever the copy is served): the sweep in
+// profiles/packed/README.md.  Rows of 8193 .. 16384 columns (the 1024-thread geometry) from 2 GiB on - the smallest size
+// measured, ahead by 8-10 % there and at 4, 8, 16 and 64 GiB.  The 512-thread geometry (n <= 8192) measured 15 % BEHIND the
+// raw pass at every size (one workgroup of 8 waves per CU has too few bytes in flight with two 56-byte tiles): forced only.
+constexpr int64_t PACK_MIN_BYTES = 2ll << 30;
+constexpr int64_t PACK_MIN_N = 8193;
+constexpr double PACK_MAX_EXCEPTIONS = 1e-3;       // share of out-of-window elements above which A stays raw
+
+bool vec_layout(const fos_problem* p);
+bool pack_served(const fos_problem* p) {
+  const PassPlan& w = p->pass;
+  return p->dtype == FOS_F32 && w.path == 0 && !w.tall && !w.colblock && !w.resident && !p->col_sharded && w.entry != nullptr &&
+         w.entry != wide_entry(FOS_F32) && p->n % fos::pk::CPT == 0 && p->n <= 16384 && p->m < (1ll << 31) - 1 && vec_layout(p);
+}
+
+// first exponent (even) of the 16-binade window that holds most of hist[256]
+unsigned pack_window(const int64_t (&hist)[256]) {
+  unsigned best = 2;
+  int64_t best_cnt = -1;
+  for (unsigned e0 = 2; e0 <= fos::pk::E0_MAX; e0 += 2) {
+    int64_t c = 0;
+    for (unsigned e = e0; e < e0 + 16; ++e) c += hist[e];
+    if (c > best_cnt) { best_cnt = c; best = e0; }
+  }
+  return best;
+}
+
+int ensure_packed(fos_problem* p) {
+  namespace pk = fos::pk;
+  PackPlan& k = p->pk;
+  if (k.tried) return FOS_OK;
+  k.tried = true;
+  const int64_t m = p->m, n = p->n;
+  if (p->pack_mode == 2 || !pack_served(p)) return FOS_OK;
+  if (p->pack_mode == 0 && (m * n * 4 < PACK_MIN_BYTES || n < PACK_MIN_N)) return FOS_OK;
+  const int threads = n <= 8192 ? 512 : 1024;
+  const size_t p_bytes = (size_t)m * (size_t)pk::row_bytes(threads);
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  // the copy, the exception lists at their cap (8 values of 4 bytes each), the m-vectors, and a margin for the caller
+  const size_t need = p_bytes + (size_t)((double)m * n * PACK_MAX_EXCEPTIONS) * 32 + (size_t)m * 16 + p_bytes / 16 + ((size_t)256 << 20);
+  if (free_b < need) return FOS_OK;
+  const float* A = static_cast<const float*>(p->A);
+
+  // 1. window: exponent histogram of a sample of whole rows, on the host
+  unsigned e0;
+  {
+    const int64_t srows = std::min<int64_t>(m, std::max<int64_t>(1, (4ll << 20) / n)), stride = m / srows;
+    std::vector<float> sample((size_t)srows * n);
+    HIP_TRY(hipMemcpy2D(sample.data(), (size_t)n * 4, A, (size_t)stride * p->lda * 4, (size_t)n * 4, (size_t)srows, hipMemcpyDeviceToHost));
+    int64_t hist[256] = {0};
+    for (float v : sample) {
+      unsigned u;
+      std::memcpy(&u, &v, 4);
+      ++hist[(u >> 23) & 0xffu];
+    }
+    e0 = pack_window(hist);
+  }
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((m * threads + 255) / 256, (int64_t)p->ncu * 32));
+  auto refuse = [&]() { k.reset(); k.tried = true; return FOS_OK; };
+
+  // 2. count the exceptions of every row (and look for inf / NaN): the CSR row pointers
+  DevBuf<int> row_cnt;
+  DevBuf<unsigned> flags;
+  if (row_cnt.reserve((size_t)m) || flags.reserve(1)) return refuse();
+  HIP_TRY(hipMemsetAsync(row_cnt, 0, (size_t)m * sizeof(int), p->stream));
+  HIP_TRY(hipMemsetAsync(flags, 0, sizeof(unsigned), p->stream));
+  hipLaunchKernelGGL(pk::pack_rows_kernel<true>, dim3(grid), dim3(256), 0, p->stream, A, p->lda, m, (int)n, threads, e0,
+                     (unsigned char*)nullptr, row_cnt.get(), flags.get(), (const int*)nullptr, (int*)nullptr, (float*)nullptr,
+                     (float*)nullptr);
+  LAUNCH_CHECK();
+  std::vector<int> ptr((size_t)m + 1);
+  unsigned hflags = 0;
+  HIP_TRY(hipMemcpyAsync(ptr.data() + 1, row_cnt, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipMemcpyAsync(&hflags, flags, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  if (hflags) return refuse();                                       // inf or NaN in A
+  int64_t nnz = 0;
+  ptr[0] = 0;
+  for (int64_t i = 1; i <= m; ++i) {
+    nnz += ptr[i];
+    if (nnz > (1ll << 30)) return refuse();
+    ptr[i] = (int)nnz;
+  }
+  if ((double)nnz > PACK_MAX_EXCEPTIONS * (double)m * (double)n) return refuse();
+
+  // 3. pack; exceptions land in their row's segment in arrival order
+  const size_t cap = (size_t)std::max<int64_t>(nnz, 1);
+  if (k.P.reserve(p_bytes) || k.csr_ptr.reserve((size_t)m + 1) || k.csr_col.reserve(cap) || k.csr_tv.reserve(cap) ||
+      k.csr_pv.reserve(cap) || k.csc_ptr.reserve((size_t)n + 1) || k.csc_row.reserve(cap) || k.csc_tv.reserve(cap) ||
+      k.csc_pv.reserve(cap) || k.bprime.reserve((size_t)m) || k.r.reserve((size_t)m))
+    return refuse();
+  HIP_TRY(hipMemcpyAsync(k.csr_ptr, ptr.data(), ((size_t)m + 1) * sizeof(int), hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipMemsetAsync(row_cnt, 0, (size_t)m * sizeof(int), p->stream));
+  hipLaunchKernelGGL(pk::pack_rows_kernel<false>, dim3(grid), dim3(256), 0, p->stream, A, p->lda, m, (int)n, threads, e0, k.P.get(),
+                     row_cnt.get(), flags.get(), (const int*)k.csr_ptr.get(), k.csr_col.get(), k.csr_tv.get(), k.csr_pv.get());
+  LAUNCH_CHECK();
+  HIP_TRY(hipStreamSynchronize(p->stream));
+
+  // 4. fixed order: columns ascending within a row, rows ascending within a column (the column-sorted copy)
+  if (nnz > 0) {
+    std::vector<int> col((size_t)nnz), row((size_t)nnz), perm;
+    std::vector<float> tv((size_t)nnz), pv((size_t)nnz), tv2((size_t)nnz), pv2((size_t)nnz);
+    std::vector<int> col2((size_t)nnz), cptr((size_t)n + 1, 0);
+    HIP_TRY(hipMemcpy(col.data(), k.csr_col, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tv.data(), k.csr_tv, (size_t)nnz * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pv.data(), k.csr_pv, (size_t)nnz * sizeof(float), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < m; ++i) {
+      const int lo = ptr[i], hi = ptr[i + 1];
+      if (lo == hi) continue;
+      perm.resize((size_t)(hi - lo));
+      for (int q = lo; q < hi; ++q) perm[(size_t)(q - lo)] = q;
+      std::sort(perm.begin(), perm.end(), [&](int a, int b) { return col[(size_t)a] < col[(size_t)b]; });
+      for (int q = lo; q < hi; ++q) {
+        const size_t src = (size_t)perm[(size_t)(q - lo)];
+        col2[(size_t)q] = col[src]; tv2[(size_t)q] = tv[src]; pv2[(size_t)q] = pv[src];
+        ++cptr[(size_t)col[src] + 1];
+      }
+    }
+    for (int64_t j = 0; j < n; ++j) cptr[(size_t)j + 1] += cptr[(size_t)j];
+    std::vector<int> fill(cptr.begin(), cptr.end() - 1);
+    for (int64_t i = 0; i < m; ++i)
+      for (int q = ptr[i]; q < ptr[i + 1]; ++q) {
+        const size_t dst = (size_t)fill[(size_t)col2[(size_t)q]]++;
+        row[dst] = (int)i; tv[dst] = tv2[(size_t)q]; pv[dst] = pv2[(size_t)q];
+      }
+    HIP_TRY(hipMemcpy(k.csr_col, col2.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k.csr_tv, tv2.data(), (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k.csr_pv, pv2.data(), (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k.csc_ptr, cptr.data(), ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k.csc_row, row.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k.csc_tv, tv.data(), (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k.csc_pv, pv.data(), (size_t)nnz * sizeof(float), hipMemcpyHostToDevice));
+  }
+  k.threads = threads;
+  k.e0 = e0;
+  k.nnz = nnz;
+  k.active = true;
+  return FOS_OK;
+}
+
+// The with-gradient pass from the packed copy: b' = b - D y, the pass on b' (stores r), slab 0 += D^T r.
+int launch_pass_packed(fos_problem* p, const YSource& ys, const float* b, int* n_rr, double* rr_to) {
+  namespace pk = fos::pk;
+  PackPlan& k = p->pk;
+  const float* bp = b;
+  if (k.nnz > 0) {
+    hipLaunchKernelGGL(pk::pk_bprime_kernel, dim3((unsigned)((p->m + 255) / 256)), dim3(256), 0, p->stream, (const int*)k.csr_ptr.get(),
+                       (const int*)k.csr_col.get(), (const float*)k.csr_tv.get(), (const float*)k.csr_pv.get(), b, p->m, ys,
+                       k.bprime.get());
+    LAUNCH_CHECK();
+    bp = k.bprime;
+  }
+  auto kern = k.threads == 1024 ? (p->il ? pk::gemv_packed_kernel<1024, true> : pk::gemv_packed_kernel<1024, false>)
+                                : (p->il ? pk::gemv_packed_kernel<512, true> : pk::gemv_packed_kernel<512, false>);
+  hipLaunchKernelGGL(kern, dim3(p->pass.nwg), dim3(k.threads), 0, p->stream, (const unsigned char*)k.P.get(), bp, p->m, (int)p->n, ys,
+                     (k.e0 >> 1) * 0x01010101u, p->pass.rows_per_wg, p->pass.slabs.get(), k.r.get(),
+                     rr_to ? rr_to : p->pass.rr_part.get());
+  LAUNCH_CHECK();
+  if (k.nnz > 0) {
+    hipLaunchKernelGGL(pk::pk_dtr_kernel, dim3((unsigned)((p->n + 3) / 4)), dim3(256), 0, p->stream, (const int*)k.csc_ptr.get(),
+                       (const int*)k.csc_row.get(), (const float*)k.csc_tv.get(), (const float*)k.csc_pv.get(), (const float*)k.r.get(),
+                       (int)p->n, ys.stopped, p->pass.slabs.get());
+    LAUNCH_CHECK();
+  }
+  *n_rr = p->pass.nwg;
+  return FOS_OK;
+}
+
 int launch_pass_inner(fos_problem* p, const YSource& ys, const float* b, bool with_g, int* n_rr, bool dual, double* rr_to) {
   if (p->pass.path == 0 && p->pass.colblock) return launch_pass_colblock(p, ys, b, with_g, n_rr);
+  if (p->pk.active && with_g && !dual) return launch_pass_packed(p, ys, b, n_rr, rr_to);
   if (p->pass.path == 0) {
     FusedLaunch fn = dual ? p->pass.entry->dual : (with_g ? p->pass.entry->with_g : p->pass.entry->resid_only);
     if (p->il) {
@@ -1019,6 +1194,7 @@ int invalidate(fos_problem* p, unsigned changed) {
   // these two follow launches of the same call or tuning loop: the stream drains before their buffers go
   if (changed & (IN_TUNE_DD | IN_CLUSTER)) HIP_TRY(hipStreamSynchronize(p->stream));
   if (changed & IN_PLAN) p->pass.reset();
+  if (changed & (IN_PLAN | IN_TUNE | IN_COMM)) p->pk.reset();         // a tuned grid or row order keeps serving: the next run packs again
   if (changed & IN_COMM) plan_resident(p);
   if (changed & (IN_PLAN | IN_TUNE | IN_TUNE_DD | IN_COMM)) p->dd.reset();
   if (changed & (IN_PLAN | IN_COMM | IN_CLUSTER)) p->multi.reset();
@@ -1445,13 +1621,14 @@ int fos_problem_replan(fos_problem* p, unsigned flags) {
   if (p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_problem_replan: a column-sharded problem keeps its two-phase plan");
   if (flags & ~(unsigned)(FOS_PLAN_NO_RESIDENT | FOS_PLAN_NO_TALL | FOS_PLAN_NO_WIDE | FOS_PLAN_NO_COLBLOCK | FOS_PLAN_CLUSTER |
                            FOS_PLAN_INTERLEAVE | FOS_PLAN_NO_INTERLEAVE | FOS_PLAN_NO_CLUSTER | FOS_PLAN_FUSED_MFMA |
-                           FOS_PLAN_CHIP_RESIDENT | FOS_PLAN_NO_CHIP_RESIDENT))
+                           FOS_PLAN_CHIP_RESIDENT | FOS_PLAN_NO_CHIP_RESIDENT | FOS_PLAN_PACK | FOS_PLAN_NO_PACK))
     return fail(FOS_ERR_ARG, "fos_problem_replan: unknown flag");
   p->cp_mode = (flags & FOS_PLAN_CLUSTER) ? 1 : (flags & FOS_PLAN_NO_CLUSTER) ? 2 : 0;
   p->fused_on = (flags & FOS_PLAN_FUSED_MFMA) != 0;
   p->chip_mode = (flags & FOS_PLAN_CHIP_RESIDENT) ? 1 : (flags & FOS_PLAN_NO_CHIP_RESIDENT) ? 2 : 0;
+  p->pack_mode = (flags & FOS_PLAN_NO_PACK) ? 2 : (flags & FOS_PLAN_PACK) ? 1 : 0;
   flags &= ~(unsigned)(FOS_PLAN_CLUSTER | FOS_PLAN_NO_CLUSTER | FOS_PLAN_FUSED_MFMA | FOS_PLAN_CHIP_RESIDENT |
-                       FOS_PLAN_NO_CHIP_RESIDENT);
+                       FOS_PLAN_NO_CHIP_RESIDENT | FOS_PLAN_PACK | FOS_PLAN_NO_PACK);
   int rc = invalidate(p, IN_PLAN);
   if (rc) return rc;
   apply_plan(p, flags);
@@ -1536,7 +1713,7 @@ int fos_problem_plan(const fos_problem* p, int32_t plan[8]) {
   plan[5] = p->pass.nslabs;
   plan[6] = (p->pass.path == 0 ? 1 : 0) | (p->pass.resident ? 2 : 0) | (p->pass.tall ? 4 : 0) | (p->pass.colblock ? 8 : 0) | (p->multi.cp_cs ? 16 : 0) |
             ((p->il && p->pass.entry && p->pass.entry->with_g_il && p->pass.path == 0 && !p->pass.colblock && !p->pass.tall) ? 32 : 0) |
-            (p->fused_on ? 64 : 0) | (p->chip_mode == 1 ? 128 : 0);
+            (p->fused_on ? 64 : 0) | (p->chip_mode == 1 ? 128 : 0) | (p->pk.active ? 256 : 0);
   plan[7] = p->ncu;
   return FOS_OK;
 }
