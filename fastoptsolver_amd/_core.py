@@ -621,15 +621,20 @@ class Problem:
         v = self.scratch[:3].cpu()
         return float(v[0]), float(v[1]), float(v[2])
 
+    def _block16(self, X):
+        """(X (n x nv, nv <= 16) zero-padded to the n_dev x 16 fp32 device block the MFMA passes read, nv)."""
+        X = torch.as_tensor(X, device=self.device, dtype=torch.float32)
+        nv = X.shape[1]
+        Xf = torch.zeros(self.n_dev, 16, dtype=torch.float32, device=self.device)
+        Xf[: X.shape[0], :nv] = X
+        return Xf, nv
+
     def residual_batch(self, X, use_b=True):
         """||A X_j - b||^2 for the <= 16 columns of X (n x nv) in one MFMA pass; host list.  Synchronises.  On a multinomial
         handle (use_b) the columns are whole class groups and entry s * C is the loss sum of group s, the others 0."""
         if self.classes and use_b:
             checked_class_groups(int(X.shape[1]), self.classes)
-        X = torch.as_tensor(X, device=self.device, dtype=torch.float32)
-        nv = X.shape[1]
-        Xf = torch.zeros(self.n_dev, 16, dtype=torch.float32, device=self.device)
-        Xf[: X.shape[0], :nv] = X
+        Xf, nv = self._block16(X)
         with self.ctx():
             _lib.check(self.lib.fos_residual_batch(self.h, ptr(Xf), nv, int(bool(use_b)), ptr(self.scratch)),
                        "fos_residual_batch")
@@ -639,10 +644,7 @@ class Problem:
         """||A X_j - B_j||^2 for the nv <= 16 columns of X (n x nv) against the columns of B (m x nv fp32 device tensor with
         unit column stride, any row stride) in one MFMA pass; host list, or None where the shape has no such pass.
         Synchronises."""
-        X = torch.as_tensor(X, device=self.device, dtype=torch.float32)
-        nv = X.shape[1]
-        Xf = torch.zeros(self.n_dev, 16, dtype=torch.float32, device=self.device)
-        Xf[: X.shape[0], :nv] = X
+        Xf, nv = self._block16(X)
         with self.ctx():
             rc = self.lib.fos_residual_batch_rhs(self.h, ptr(Xf), nv, ptr(B), int(B.stride(0)), ptr(self.scratch))
         if not _lib.served(rc, "fos_residual_batch_rhs"):
@@ -653,10 +655,7 @@ class Problem:
         """Held-out squared errors: sum over the rows i with fold_ids[i] == held[j] of (A_i . X_j - b_i)^2 for the nv <= 16
         columns of X (n x nv) in one MFMA pass (fos_residual_batch_folds); fold_ids: `fold_ids_tensor`, held: nv ints
         (-1: no row).  Host list, or None where the shape has no such pass.  Synchronises."""
-        X = torch.as_tensor(X, device=self.device, dtype=torch.float32)
-        nv = X.shape[1]
-        Xf = torch.zeros(self.n_dev, 16, dtype=torch.float32, device=self.device)
-        Xf[: X.shape[0], :nv] = X
+        Xf, nv = self._block16(X)
         with self.ctx():
             rc = self.lib.fos_residual_batch_folds(self.h, ptr(Xf), nv, ptr(fold_ids), (C.c_int32 * nv)(*held), ptr(self.scratch))
         if not _lib.served(rc, "fos_residual_batch_folds"):
@@ -666,10 +665,7 @@ class Problem:
     def gram_apply(self, X):
         """A^T W A X_j for the nv <= 16 columns of X (n x nv), W the bound weights or the identity (fos_gram_apply): an n x nv
         float32 device tensor.  Enqueues only."""
-        X = torch.as_tensor(X, device=self.device, dtype=torch.float32)
-        nv = X.shape[1]
-        Xf = torch.zeros(self.n_dev, 16, dtype=torch.float32, device=self.device)
-        Xf[: X.shape[0], :nv] = X
+        Xf, nv = self._block16(X)
         G = torch.empty(nv, self.n_dev, dtype=torch.float32, device=self.device)
         with self.ctx():
             _lib.check(self.lib.fos_gram_apply(ptr(Xf), nv, self.h, ptr(G)), "fos_gram_apply")

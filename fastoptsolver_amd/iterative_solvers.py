@@ -1065,16 +1065,16 @@ def _run_batch_group(bt, kind, sub, params, lp, record=False, obj=None):
 # FISTA                                                        ref:132-245
 # FISTA-Δ                                                      ref:251-344
 # ---------------------------------------------------------------------
-def _lipschitz(prob, L, *, comm=None, cols=None, group=None):
+def _lipschitz(prob, L, *, comm=None, cols=None, group=None, divisor=1.0):
     """L as the caller gave it, or estimated the way the problem is sharded (ref:155 / :273): one power iteration, one draw
-    from the global NumPy stream."""
+    from the global NumPy stream.  divisor: what bounds the Hessian of the data term by lambda_max(A^T A) / divisor."""
     if L is not None:
         return float(L)
-    if _weighted(prob):              # lambda_max(A^T W A); sigma' <= 1/4 bounds the weighted logistic Hessian by a quarter of it
-        return estimate_lipschitz(prob) / (4.0 if prob.loss == "logistic" else 1.0)
+    if _weighted(prob):              # lambda_max(A^T W A); sigma' <= 1/4 bounds the weighted logistic Hessian by a quarter of it,
+        return estimate_lipschitz(prob) / (4.0 if prob.loss == "logistic" else divisor)     # whichever front end took the handle
     if cols is not None:
         return _lipschitz_cols(prob, comm, cols)
-    return estimate_lipschitz(prob, group=group)
+    return estimate_lipschitz(prob, group=group) / divisor
 
 
 def _solve(A, b, reg_type, lp, return_history, L, dtype, check_every, comm, group, cols):
@@ -1146,28 +1146,127 @@ def fista_delta(A, b, reg_type: str, alpha1: float, alpha2: float, delta: float,
 # ---------------------------------------------------------------------
 # Regularisation path (extension)
 # ---------------------------------------------------------------------
-def _run_path(prob, prms, max_iter, cols=None, lockstep_only=False):
-    """One state machine per parameter set on `prob`, advanced max_iter iterations in lockstep groups (fos_fista_run_multi;
-    what it does not serve runs one by one); one grad_call_times entry per lockstep iteration per group.  The handles.
-    lockstep_only (a logistic or weighted problem: the lockstep is its one form): groups of 16, a group of one included, and a
-    refusal raises."""
-    handles = [_new_state(prob, prm) for prm in prms]
+# The host driver of the lockstep, shared by the four model families (squared and logistic here and in logistic.py, multinomial.py,
+# multitask.py).  A family states what differs: how many adjacent columns one fit takes, fos_fista_params.group, the divisor of
+# lambda_max(A^T A) in L, the launch of one group of fits, and what a refusal means.
+LOCKSTEP_COLUMNS = 16
+
+# width: columns per fit.  group: fos_fista_params.group of every handle.  divisor: L = lambda_max(A^T A) / divisor.
+# launch(handles, first, number) -> served: `number` fits from fit `first` on, their width * number handles in one lockstep call.
+# refusal: the text of the FosError a refused launch raises (fos_last_error appended), or None for the plain squared-loss path -
+# what the lockstep does not serve, and a single fit, runs one by one (Fista.run).
+_Family = collections.namedtuple("_Family", "width group divisor launch refusal")
+
+
+def _columns(max_iter, lockstep_only, divisor=1.0):
+    """The family of one column per fit on the problem's own b (fos_fista_run_multi): squared loss, and logistic with divisor 4.
+    lockstep_only: a handle with sample weights, penalty factors, bounds, feature groups or the logistic loss."""
+    return _Family(1, 0, divisor, lambda handles, first, number: _core.run_multi(handles, max_iter),
+                   "fos_fista_run_multi refused the lockstep: " if lockstep_only else None)
+
+
+def _refused(prob, text):
+    return _lib.FosError(text + prob.lib.fos_last_error().decode("utf-8", "replace"))
+
+
+def _rows(A):
+    return A.m if isinstance(A, _core.Problem) else int(A.shape[0] if hasattr(A, "shape") else np.shape(A)[0])
+
+
+def _check_path_args(alphas, delta):
+    alphas = [(float(a1), float(a2)) for a1, a2 in alphas]
+    if not alphas:
+        raise ValueError("alphas: at least one (alpha1, alpha2) pair is needed")
+    if delta is not None and not delta > 2:
+        raise ValueError("delta: FISTA-Δ needs delta > 2")
+    return alphas
+
+
+def _groups(count, per):
+    return [(first, min(per, count - first)) for first in range(0, count, per)]
+
+
+def pack_groups(count, classes):
+    """How `count` fits of a C-class model share the 16 lockstep columns: ``[(first, number), ...]``, floor(16 / C) fits per
+    group, the last group partial.  Fit i of a group owns columns ``i * C .. i * C + C - 1``.  Pure: no device work."""
+    classes = int(classes)
+    if not 2 <= classes <= _core.MAX_CLASSES:
+        raise ValueError(f"classes: 2 <= C <= {_core.MAX_CLASSES} expected, got {classes}")
+    if count < 0:
+        raise ValueError("count must be >= 0")
+    return _groups(count, LOCKSTEP_COLUMNS // classes)
+
+
+def _path_params(prob, alphas, L, fam, t_init_factor, delta, *, comm=None, cols=None, **control):
+    """One parameter set per weight pair: the step from L of the family's data term (estimated unless given: one draw from the
+    global NumPy stream) and the handle's largest penalty factor; control: the stopping and restart fields of `_params`."""
+    L_val = _lipschitz(prob, L, comm=comm, cols=cols, divisor=fam.divisor)
+    mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
+    return [_params(_tau(L_val, a2, t_init_factor, prob.penalty_max), a1, a2, mode=mode, delta=delta, group=fam.group, **control)
+            for a1, a2 in alphas]
+
+
+def _run_path(prob, prms, fam, max_iter, cols=None):
+    """fam.width state machines per parameter set on `prob`, fit-major, advanced max_iter iterations in lockstep groups of up
+    to 16 columns; one grad_call_times entry per lockstep iteration per group.  The handles.  A family with a refusal text has
+    the lockstep as its one form: groups of 16 columns, a group of one included.  The plain squared-loss path (fam.refusal
+    None) takes groups of 4 for up to 4 weights - the multi-vector VALU pass where the shape has one."""
+    W = fam.width
+    handles = [_new_state(prob, prm) for prm in prms for _ in range(W)]
     gtimer = _EventTimer(grad_call_times)
-    # up to 4 weights: the multi-vector VALU pass where the shape has one; up to 16: the matrix-core pass
-    width = 4 if len(handles) <= 4 and cols is None and not lockstep_only else 16
-    for i in range(0, len(handles), width):
-        group = handles[i:i + width]
+    per = 4 if fam.refusal is None and len(prms) <= 4 and cols is None else LOCKSTEP_COLUMNS // W
+    for first, number in _groups(len(prms), per):
+        group = handles[first * W:(first + number) * W]
         ev = gtimer.start()
-        if lockstep_only:
-            if not _core.run_multi(group, max_iter):
-                raise _lib.FosError("fos_fista_run_multi refused the lockstep: " +
-                                    prob.lib.fos_last_error().decode("utf-8", "replace"))
-        elif len(group) == 1 or not _core.run_multi(group, max_iter):
+        if (fam.refusal is None and len(group) == 1) or not fam.launch(group, first, number):
+            if fam.refusal is not None:
+                raise _refused(prob, fam.refusal)
             for st in group:
                 st.run(max_iter)
         gtimer.stop(ev, max_iter)
     gtimer.flush()
     return handles
+
+
+def _path_result(handles, fam, like, return_info):
+    """What a path call returns: per fit x (a vector, or n x width with the fit's columns stacked) as the kind that went in, and
+    with return_info (iterations, stop_code) read from the first handle of every fit."""
+    W = fam.width
+    xs = [_core.from_device_vec(handles[i].x_tensor() if W == 1 else torch.stack([st.x_tensor() for st in handles[i:i + W]], dim=1),
+                                like) for i in range(0, len(handles), W)]
+    if return_info:
+        stats = [st.status() for st in handles[::W]]
+        return xs, [(int(s.k), int(s.stopped)) for s in stats]
+    return xs
+
+
+def _objective_block(prob, X, width):
+    """The members an objective is asked for as an n x width x k float64 device block, and whether one member came in: a vector
+    (width 1) or an n x width matrix, or k of them along a last axis.  ValueError for any other shape."""
+    xt = X.detach() if _core.is_tensor(X) else torch.from_numpy(np.asarray(X, dtype=np.float64))
+    member = (prob.n,) if width == 1 else (prob.n, width)
+    single = xt.dim() == len(member)
+    if xt.dim() not in (len(member), len(member) + 1) or tuple(xt.shape[:len(member)]) != member:
+        raise ValueError(f"x: a vector of length {prob.n} or an {prob.n} x k block expected" if width == 1 else
+                         f"X: an {prob.n} x {width} matrix or an {prob.n} x {width} x k block expected, got shape {tuple(xt.shape)}")
+    return xt.reshape(prob.n, width, 1 if single else xt.shape[-1]).to(device=prob.device, dtype=torch.float64), single
+
+
+def _objective_value(prob, Xd, single, data_term, alpha1, alpha2, row_groups=False):
+    """data term + penalties of every member of Xd (`_objective_block`): a float for a single member, else k float64 values.
+    data_term(block, number) -> the data terms of `number` members, block their n x (number * width) columns member-major, at
+    most 16.  The penalties are alpha1 sum_j p_j |x_j| - with row_groups alpha1 sum_j p_j ||X[j, :]||_2 - plus 0.5 alpha2 sum_j p_j
+    x_j^2 over all columns of a member, p the fp32 penalty factors of the handle as bound (else 1)."""
+    n, W, k = Xd.shape
+    data = []
+    for first, number in _groups(k, LOCKSTEP_COLUMNS // W):
+        data += data_term(Xd[:, :, first:first + number].permute(0, 2, 1).reshape(n, number * W), number)
+    Xh = Xd.cpu().numpy()
+    pf = np.ones(n) if prob.penalty_factor is None else prob.penalty_factor.to("cpu", torch.float64).numpy()
+    l1 = (pf[:, None] * np.sqrt((Xh * Xh).sum(axis=1))).sum(axis=0) if row_groups else (pf[:, None, None] * np.abs(Xh)).sum(axis=(0, 1))
+    val = (np.asarray(data, dtype=np.float64) + float(alpha1) * l1 +
+           0.5 * float(alpha2) * (pf[:, None, None] * Xh * Xh).sum(axis=(0, 1)))
+    return float(val[0]) if single else val
 
 
 def fista_path(A, b, alphas, t_init_factor: float = 1.0, max_iter: int = 500, *, delta=None, L=None, dtype=None,
@@ -1206,20 +1305,13 @@ def fista_path(A, b, alphas, t_init_factor: float = 1.0, max_iter: int = 500, *,
     if weighted and (tol != 0.0 or comm is not None or cols is not None):
         raise ValueError("a handle with sample weights, penalty factors, bounds or feature groups runs on the lockstep alone: no tol (the "
                          "gradient-norm rule), comm= or cols=")
-    prob, _ = _sharded_problem(A, b, dtype, comm, None, cols)    # comm: A, b are this rank's rows (matrix-core pass, one
-    like = prob.like                                             # all-reduce of the 16 gradients per iteration)
-    L_val = _lipschitz(prob, L, comm=comm, cols=cols)
-    mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
+    # comm: A, b are this rank's rows (matrix-core pass, one all-reduce of the 16 gradients per iteration)
+    prob, _ = _sharded_problem(A, b, dtype, comm, None, cols)
+    fam = _columns(max_iter, weighted)
     # the tolerances go to the device as given: a negative one is refused there (fos_fista_reset), not read as "off"
-    handles = _run_path(prob, [_params(_tau(L_val, a2, t_init_factor, prob.penalty_max), a1, a2, mode=mode, delta=delta, tol=tol,
-                                       tol_ratio=tol_ratio, grad_rule=delta is None, adaptive_restart=adaptive_restart,
-                                       restart_threshold=restart_threshold) for a1, a2 in alphas], max_iter, cols,
-                        lockstep_only=weighted)
-    xs = [_core.from_device_vec(st.x_tensor(), like) for st in handles]
-    if return_info:
-        stats = [st.status() for st in handles]
-        return xs, [(int(s.k), int(s.stopped)) for s in stats]
-    return xs
+    prms = _path_params(prob, alphas, L, fam, t_init_factor, delta, comm=comm, cols=cols, tol=tol, tol_ratio=tol_ratio,
+                        grad_rule=delta is None, adaptive_restart=adaptive_restart, restart_threshold=restart_threshold)
+    return _path_result(_run_path(prob, prms, fam, max_iter, cols), fam, prob.like, return_info)
 
 
 # ---------------------------------------------------------------------
@@ -1267,37 +1359,64 @@ def _cv_weight_sums(prob, ids, K):
     return sums
 
 
-def _cv_lockstep(prob, ids, K, prms, max_iter):
-    """Every (fold, weight) pair as a column of the masked lockstep on the one bound A: groups of up to 16 columns,
-    fold-major, each one fos_fista_run_multi_folds call and one fos_residual_batch_folds pass.  (x n x K x L float64 device,
-    held-out SSE K x L, info) or None where the entry point does not serve the problem (decided on the first group)."""
-    La = len(prms)
-    cols = [(f, a) for f in range(K) for a in range(La)]
+def _cv_sizes(prob, ids, sizes):
+    """The denominators of the held-out scores: the fold sizes, on a weighted handle the folds' weight sums."""
+    return _cv_weight_sums(prob, ids, len(sizes)) if _weighted(prob) else sizes
+
+
+def _run_cv(prob, ids, K, prms, fam, max_iter, refusal=None):
+    """Every (fold, weight) pair as fam.width columns of the masked lockstep on the one bound A: groups of up to 16 columns,
+    fold-major, each one fos_fista_run_multi_folds call and one fos_residual_batch_folds pass.  (x n x K x L float64 device - n x
+    width x K x L for a family of several columns per fit -, held-out totals K x L, info).  A refused launch raises `refusal`
+    (fos_last_error appended); with None the result is None where the entry point does not serve the problem, which the first
+    group decides."""
+    W, La = fam.width, len(prms)
+    pairs = [(f, a) for f in range(K) for a in range(La)]
     ids_dev = _core.fold_ids_tensor(ids, prob.device)
-    X = torch.zeros(prob.n, K, La, dtype=torch.float64, device=prob.device)
-    sse = np.zeros((K, La))
+    X = torch.zeros(prob.n, W, K, La, dtype=torch.float64, device=prob.device)
+    total = np.zeros((K, La))
     info = [[None] * La for _ in range(K)]
     gtimer = _EventTimer(grad_call_times)
-    for g0 in range(0, len(cols), 16):
-        grp = cols[g0:g0 + 16]
-        held = [f for f, _ in grp]
-        handles = [_new_state(prob, prms[a]) for _, a in grp]
+    for first, number in _groups(len(pairs), LOCKSTEP_COLUMNS // W):
+        grp = pairs[first:first + number]
+        held = [f for f, _ in grp for _ in range(W)]
+        handles = [_new_state(prob, prms[a]) for _, a in grp for _ in range(W)]
         ev = gtimer.start()
         if not _core.run_multi_folds(handles, ids_dev, held, max_iter):
-            if g0 == 0:
+            if refusal is not None:
+                raise _refused(prob, refusal)
+            if first == 0:
                 return None
             raise _lib.FosError("fos_fista_run_multi_folds refused a later group of a problem it served")
         gtimer.stop(ev, max_iter)
-        stats = [st.status() for st in handles]
-        gtimer.recount(max(int(s.k) for s in stats))             # the lockstep iterations actually run
-        xg = torch.stack([st.x_tensor() for st in handles], dim=1)
+        xg = torch.stack([st.x_tensor() for st in handles], dim=1)   # enqueued behind the run; the status reads below wait for it
         q = prob.residual_batch_folds(xg, ids_dev, held)
-        for j, (f, a) in enumerate(grp):
-            X[:, f, a] = xg[:, j]
-            sse[f, a] = q[j]
-            info[f][a] = (int(stats[j].k), int(stats[j].stopped))
+        if q is None:
+            raise _refused(prob, f"fos_residual_batch_folds refused the {'multinomial ' if prob.classes else ''}problem: ")
+        stats = [st.status() for st in handles[::W]]             # a fit's status is that of its first handle
+        if W == 1:                                               # (the columns of a joint fit have no stopping rule)
+            gtimer.recount(max(int(s.k) for s in stats))         # the lockstep iterations actually run
+        for i, (f, a) in enumerate(grp):
+            X[:, :, f, a] = xg[:, i * W:(i + 1) * W]
+            total[f, a] = q[i * W]
+            info[f][a] = (int(stats[i].k), int(stats[i].stopped))
     gtimer.flush()
-    return X, sse, info
+    return (X[:, 0] if W == 1 else X), total, info
+
+
+def _refit(prob, prm, fam, max_iter):
+    """The fit on all rows at one parameter set, through the path driver."""
+    return _path_result(_run_path(prob, [prm], fam, max_iter), fam, prob.like, False)[0]
+
+
+def _cv_result(kind, like, alphas, total, sizes, refit, X, info):
+    """The CV result tuple `kind` from the held-out totals (K x L) and their denominators: the scores, their mean over the folds,
+    the argmin, x = refit(best) (refit None: no refit) and the fits X as the kind that went in (None: not asked for)."""
+    score = total / sizes[:, None].astype(np.float64)       # weighted: the held-out weighted sum over the held-out weight sum
+    mean = score.mean(axis=0)
+    best = int(np.argmin(mean))
+    x = None if refit is None else refit(best)
+    return kind(alphas, score, mean, best, x, None if X is None else _core.from_device_vec(X, like), info)
 
 
 def _cv_fold_by_fold(prob, ids, K, prms, max_iter):
@@ -1312,7 +1431,7 @@ def _cv_fold_by_fold(prob, ids, K, prms, max_iter):
     for f in range(K):
         rows = torch.nonzero(idt != f).squeeze(1)
         sub = _core.Problem(prob.A.index_select(0, rows), prob.b.index_select(0, rows), prob.dtype)
-        handles, recorded = _metrics_of(lambda: _run_path(sub, prms, max_iter))
+        handles, recorded = _metrics_of(lambda: _run_path(sub, prms, _columns(max_iter, False), max_iter))
         _metrics_add(recorded)
         del sub
         rows = torch.nonzero(idt == f).squeeze(1)
@@ -1376,38 +1495,27 @@ def fista_cv(A, b, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int = 
     alphas = [(float(a1), float(a2)) for a1, a2 in alphas]
     if not alphas:
         raise ValueError("alphas: at least one (alpha1, alpha2) pair is needed")
-    m = A.m if isinstance(A, _core.Problem) else int(A.shape[0] if hasattr(A, "shape") else np.shape(A)[0])
-    ids, sizes = _cv_folds(folds, m)
+    ids, sizes = _cv_folds(folds, _rows(A))
     K = len(sizes)
     prob = _core.as_problem(A, b, dtype)
     if prob.b is None:
         raise ValueError("fista_cv needs b")
-    like = prob.like
-    weighted = _weighted(prob)
-    lockstep_only = weighted or _has_coord(prob)
-    if weighted:
-        sizes = _cv_weight_sums(prob, ids, K)
-    L_val = _lipschitz(prob, L)
-    mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
-    prms = [_params(_tau(L_val, a2, t_init_factor, prob.penalty_max), a1, a2, mode=mode, delta=delta, tol_ratio=tol_ratio,
-                    adaptive_restart=adaptive_restart, restart_threshold=restart_threshold) for a1, a2 in alphas]
-    out = _cv_lockstep(prob, ids, K, prms, max_iter)
+    lockstep_only = _weighted(prob) or _has_coord(prob)
+    sizes = _cv_sizes(prob, ids, sizes)
+    fam = _columns(max_iter, lockstep_only)
+    prms = _path_params(prob, alphas, L, fam, t_init_factor, delta, tol_ratio=tol_ratio, adaptive_restart=adaptive_restart,
+                        restart_threshold=restart_threshold)
+    out = _run_cv(prob, ids, K, prms, fam, max_iter)
     if out is None:
         if lockstep_only:            # no unweighted or unconstrained slow path may answer for such a handle
-            raise _lib.FosError("fos_fista_run_multi_folds refused the lockstep of a handle with sample weights, penalty factors or bounds: " +
-                                prob.lib.fos_last_error().decode("utf-8", "replace"))
+            raise _refused(prob, "fos_fista_run_multi_folds refused the lockstep of a handle with sample weights, penalty factors or bounds: ")
         out = _cv_fold_by_fold(prob, ids, K, prms, max_iter)
     X, sse, info = out
-    mse = sse / sizes[:, None].astype(np.float64)       # weighted: the held-out weighted sum over the held-out weight sum
-    mean_mse = mse.mean(axis=0)
-    best = int(np.argmin(mean_mse))
-    x = None
-    if refit:
+
+    def refit_at(best):
         if lockstep_only:
-            st = _run_path(prob, [prms[best]], max_iter, lockstep_only=True)[0]
-        else:
-            st = _new_state(prob, prms[best])
-            st.run(max_iter)
-        x = _core.from_device_vec(st.x_tensor(), like)
-    coefs = _core.from_device_vec(X, like) if return_coefs else None
-    return CVResult(alphas, mse, mean_mse, best, x, coefs, info)
+            return _refit(prob, prms[best], fam, max_iter)
+        st = _new_state(prob, prms[best])                        # a plain handle: the single-target run, no metric entries
+        st.run(max_iter)
+        return _core.from_device_vec(st.x_tensor(), prob.like)
+    return _cv_result(CVResult, prob.like, alphas, sse, sizes, refit_at if refit else None, X if return_coefs else None, info)

@@ -22,22 +22,10 @@ from __future__ import annotations
 
 import collections
 
-import numpy as np
-import torch
-
-from . import _core, _lib
+from . import _core
 from . import iterative_solvers as _its
 
 LogisticCVResult = collections.namedtuple("LogisticCVResult", "alphas logloss mean_logloss best x coefs info")
-
-
-def _check_path_args(alphas, delta):
-    alphas = [(float(a1), float(a2)) for a1, a2 in alphas]
-    if not alphas:
-        raise ValueError("alphas: at least one (alpha1, alpha2) pair is needed")
-    if delta is not None and not delta > 2:
-        raise ValueError("delta: FISTA-Δ needs delta > 2")
-    return alphas
 
 
 def _problem(A, y, dtype):
@@ -51,18 +39,9 @@ def _problem(A, y, dtype):
     return _core.Problem(A, y, dtype, None, "logistic")
 
 
-def _params_of(prob, alphas, L, t_init_factor, delta, tol_ratio, adaptive_restart, restart_threshold):
-    """L of the logistic data term (lambda_max(A^T A) / 4 unless given; lambda_max(A^T W A) / 4 on a weighted handle) and one
-    parameter set per weight."""
-    if L is not None:
-        L_val = float(L)
-    elif _its._weighted(prob):       # a quarter of lambda_max(A^T W A)
-        L_val = _its._lipschitz(prob, None)
-    else:
-        L_val = _its.estimate_lipschitz(prob) / 4.0
-    mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
-    return [_its._params(_its._tau(L_val, a2, t_init_factor, prob.penalty_max), a1, a2, mode=mode, delta=delta, tol_ratio=tol_ratio,
-                         adaptive_restart=adaptive_restart, restart_threshold=restart_threshold) for a1, a2 in alphas]
+def _family(max_iter):
+    """One column per fit; sigma' <= 1/4 bounds the Hessian A^T diag(sigma') A by A^T A / 4 (A^T W A / 4 on a weighted handle)."""
+    return _its._columns(max_iter, True, 4.0)
 
 
 def logistic_path(A, y, alphas, t_init_factor: float = 1.0, max_iter: int = 500, *, delta=None, L=None, dtype=None,
@@ -91,15 +70,11 @@ def logistic_path(A, y, alphas, t_init_factor: float = 1.0, max_iter: int = 500,
     column with factor 0.  The step is then ``t_init_factor / (L + alpha2 max_j
     p_j)``; L does not depend on the constraints."""
     _its.reset_metrics()
-    alphas = _check_path_args(alphas, delta)
-    prob = _problem(A, y, dtype)
-    prms = _params_of(prob, alphas, L, t_init_factor, delta, tol_ratio, adaptive_restart, restart_threshold)
-    handles = _its._run_path(prob, prms, max_iter, lockstep_only=True)
-    xs = [_core.from_device_vec(st.x_tensor(), prob.like) for st in handles]
-    if return_info:
-        stats = [st.status() for st in handles]
-        return xs, [(int(s.k), int(s.stopped)) for s in stats]
-    return xs
+    alphas = _its._check_path_args(alphas, delta)
+    prob, fam = _problem(A, y, dtype), _family(max_iter)
+    prms = _its._path_params(prob, alphas, L, fam, t_init_factor, delta, tol_ratio=tol_ratio, adaptive_restart=adaptive_restart,
+                             restart_threshold=restart_threshold)
+    return _its._path_result(_its._run_path(prob, prms, fam, max_iter), fam, prob.like, return_info)
 
 
 def logistic_cv(A, y, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int = 500, *, delta=None, L=None, dtype=None,
@@ -122,28 +97,19 @@ def logistic_cv(A, y, alphas, folds=5, t_init_factor: float = 1.0, max_iter: int
     A handle with penalty factors or bounds, as in ``logistic_path``: every fold's fit carries them (they belong to the
     coordinates, not the rows), with the step ``t_init_factor / (L + alpha2 max_j p_j)``."""
     _its.reset_metrics()
-    alphas = _check_path_args(alphas, delta)
-    m = A.m if isinstance(A, _core.Problem) else int(A.shape[0] if hasattr(A, "shape") else np.shape(A)[0])
-    ids, sizes = _its._cv_folds(folds, m)
-    K = len(sizes)
-    prob = _problem(A, y, dtype)
-    if _its._weighted(prob):         # weighted held-out sums over the held-out weight sums; a zero-weight fold raises here
-        sizes = _its._cv_weight_sums(prob, ids, K)
-    prms = _params_of(prob, alphas, L, t_init_factor, delta, tol_ratio, adaptive_restart, restart_threshold)
-    out = _its._cv_lockstep(prob, ids, K, prms, max_iter)
+    alphas = _its._check_path_args(alphas, delta)
+    ids, sizes = _its._cv_folds(folds, _its._rows(A))
+    prob, fam = _problem(A, y, dtype), _family(max_iter)
+    sizes = _its._cv_sizes(prob, ids, sizes)             # a weighted handle: the weight sums; a zero-weight fold raises here
+    prms = _its._path_params(prob, alphas, L, fam, t_init_factor, delta, tol_ratio=tol_ratio, adaptive_restart=adaptive_restart,
+                             restart_threshold=restart_threshold)
+    out = _its._run_cv(prob, ids, len(sizes), prms, fam, max_iter)
     if out is None:
-        raise _lib.FosError("fos_fista_run_multi_folds refused the lockstep: " +
-                            prob.lib.fos_last_error().decode("utf-8", "replace"))
+        raise _its._refused(prob, "fos_fista_run_multi_folds refused the lockstep: ")
     X, total, info = out
-    logloss = total / sizes[:, None].astype(np.float64)
-    mean_logloss = logloss.mean(axis=0)
-    best = int(np.argmin(mean_logloss))
-    x = None
-    if refit:
-        st =_its._run_path(prob, [prms[best]], max_iter, lockstep_only=True)[0]
-        x = _core.from_device_vec(st.x_tensor(), prob.like)
-    coefs = _core.from_device_vec(X, prob.like) if return_coefs else None
-    return LogisticCVResult(alphas, logloss, mean_logloss, best, x, coefs, info)
+    return _its._cv_result(LogisticCVResult, prob.like, alphas, total, sizes,
+                           (lambda best: _its._refit(prob, prms[best], fam, max_iter)) if refit else None,
+                           X if return_coefs else None, info)
 
 
 def logistic_objective(x, A, y, alpha1, alpha2):
@@ -157,16 +123,5 @@ def logistic_objective(x, A, y, alpha1, alpha2):
     if prob.has_feature_groups:      # the separable penalty would answer for another objective
         raise ValueError("logistic_objective: the handle has feature groups (Problem.set_feature_groups): use "
                          'group_lasso_objective(x, handle, None, alpha1, alpha2, groups, ..., loss="logistic")')
-    xt = x.detach() if _core.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=np.float64))
-    vector = xt.dim() == 1
-    X = (xt.reshape(-1, 1) if vector else xt).to(device=prob.device, dtype=torch.float64)
-    if X.dim() != 2 or X.shape[0] != prob.n:
-        raise ValueError(f"x: a vector of length {prob.n} or an {prob.n} x k block expected")
-    nll = []
-    for j0 in range(0, X.shape[1], 16):
-        nll += prob.residual_batch(X[:, j0:j0 + 16], use_b=True)
-    Xh = X.cpu().numpy()
-    pf = np.ones(prob.n) if prob.penalty_factor is None else prob.penalty_factor.to("cpu", torch.float64).numpy()
-    val = (np.asarray(nll, dtype=np.float64) + float(alpha1) * (pf[:, None] * np.abs(Xh)).sum(axis=0) +
-           0.5 * float(alpha2) * (pf[:, None] * Xh * Xh).sum(axis=0))
-    return float(val[0]) if vector else val
+    X, single = _its._objective_block(prob, x, 1)
+    return _its._objective_value(prob, X, single, lambda block, number: prob.residual_batch(block, use_b=True), alpha1, alpha2)

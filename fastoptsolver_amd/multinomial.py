@@ -31,28 +31,11 @@ from __future__ import annotations
 
 import collections
 
-import numpy as np
-import torch
-
-from . import _core, _lib
+from . import _core
 from . import iterative_solvers as _its
-from .logistic import _check_path_args
+from .iterative_solvers import LOCKSTEP_COLUMNS, pack_groups        # (public here: the packing of the class groups)
 
 MultinomialCVResult = collections.namedtuple("MultinomialCVResult", "alphas logloss mean_logloss best x coefs info")
-
-LOCKSTEP_COLUMNS = 16
-
-
-def pack_groups(count, classes):
-    """How `count` fits of a C-class model share the 16 lockstep columns: ``[(first, number), ...]``, floor(16 / C) fits per
-    group, the last group partial.  Fit i of a group owns columns ``i * C .. i * C + C - 1``.  Pure: no device work."""
-    classes = int(classes)
-    if not 2 <= classes <= _core.MAX_CLASSES:
-        raise ValueError(f"classes: 2 <= C <= {_core.MAX_CLASSES} expected, got {classes}")
-    if count < 0:
-        raise ValueError("count must be >= 0")
-    per = LOCKSTEP_COLUMNS // classes
-    return [(first, min(per, count - first)) for first in range(0, count, per)]
 
 
 def prepare_multinomial(A, y, classes=None, dtype=None, *, sample_weight=None, penalty_factor=None, lower=None, upper=None,
@@ -85,12 +68,6 @@ def _problem(A, y, classes, dtype):
     return _core.Problem.multinomial(A, y, classes, dtype)
 
 
-def _lipschitz(prob, L):
-    """L of the multinomial data term: Boehning's bound, the softmax Hessian is <= 1/2 I (x) A^T A (A^T W A on a weighted
-    handle), so lambda_max / 2 unless given."""
-    return float(L) if L is not None else _its.estimate_lipschitz(prob) / 2.0
-
-
 def _grouped(prob):
     """Whether the handle carries the group penalty.  The group penalty and box bounds have no composed closed-form prox: a
     grouped handle that has been given bounds since is refused on the host, before any device work."""
@@ -100,39 +77,12 @@ def _grouped(prob):
     return grouped
 
 
-def _params_of(prob, alphas, L, t_init_factor, delta, grouped=False):
-    L_val = _lipschitz(prob, L)
-    mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
-    group = prob.classes if grouped else 0
-    return [_its._params(_its._tau(L_val, a2, t_init_factor, prob.penalty_max), a1, a2, mode=mode, delta=delta, group=group)
-            for a1, a2 in alphas]
-
-
-def _class_handles(prob, prms):
-    """C state machines per parameter set, class-minor: the columns of one lockstep group."""
-    return [_its._new_state(prob, prm) for prm in prms for _ in range(prob.classes)]
-
-
-def _run_groups(prob, prms, max_iter):
-    """Every parameter set as a class group of the lockstep (fos_fista_run_multi on a multinomial problem), floor(16 / C) per
-    call: (X n x C x len(prms) float64 device, [(iterations, stop_code)]).  A refusal raises."""
-    C = prob.classes
-    X = torch.zeros(prob.n, C, len(prms), dtype=torch.float64, device=prob.device)
-    info = []
-    gtimer = _its._EventTimer(_its.grad_call_times)
-    for first, number in pack_groups(len(prms), C):
-        handles = _class_handles(prob, prms[first:first + number])
-        ev = gtimer.start()
-        if not _core.run_multi(handles, max_iter):
-            raise _lib.FosError("fos_fista_run_multi refused the multinomial lockstep: " +
-                                prob.lib.fos_last_error().decode("utf-8", "replace"))
-        gtimer.stop(ev, max_iter)
-        for i in range(number):
-            X[:, :, first + i] = torch.stack([st.x_tensor() for st in handles[i * C:(i + 1) * C]], dim=1)
-            s = handles[i * C].status()
-            info.append((int(s.k), int(s.stopped)))
-    gtimer.flush()
-    return X, info
+def _family(prob, max_iter):
+    """C columns per fit, group = C on a grouped handle.  Boehning's bound: the softmax Hessian is <= 1/2 I (x) A^T A (A^T W A on
+    a weighted handle), so L = lambda_max / 2 unless given.  A refusal raises."""
+    return _its._Family(prob.classes, prob.classes if _grouped(prob) else 0, 2.0,
+                        lambda handles, first, number: _core.run_multi(handles, max_iter),
+                        "fos_fista_run_multi refused the multinomial lockstep: ")
 
 
 def multinomial_path(A, y, alphas, classes=None, t_init_factor: float = 1.0, max_iter: int = 500, *, delta=None, L=None,
@@ -158,11 +108,11 @@ def multinomial_path(A, y, alphas, classes=None, t_init_factor: float = 1.0, max
     instead of the l1 penalty - row j of every result is zero in all C classes or in none.  Same step, same contract; a grouped
     handle with box bounds raises ValueError."""
     _its.reset_metrics()
-    alphas = _check_path_args(alphas, delta)
+    alphas = _its._check_path_args(alphas, delta)
     prob = _problem(A, y, classes, dtype)
-    X, info = _run_groups(prob, _params_of(prob, alphas, L, t_init_factor, delta, _grouped(prob)), max_iter)
-    xs = [_core.from_device_vec(X[:, :, a], prob.like) for a in range(len(alphas))]
-    return (xs, info) if return_info else xs
+    fam = _family(prob, max_iter)
+    prms = _its._path_params(prob, alphas, L, fam, t_init_factor, delta)
+    return _its._path_result(_its._run_path(prob, prms, fam, max_iter), fam, prob.like, return_info)
 
 
 def multinomial_cv(A, y, alphas, folds=5, classes=None, t_init_factor: float = 1.0, max_iter: int = 500, *, delta=None, L=None,
@@ -185,50 +135,17 @@ def multinomial_cv(A, y, alphas, folds=5, classes=None, t_init_factor: float = 1
     A grouped handle: every fit (the refit included) carries the group penalty over the classes, as in ``multinomial_path``;
     the held-out score is the same cross-entropy."""
     _its.reset_metrics()
-    alphas = _check_path_args(alphas, delta)
-    m = A.m if isinstance(A, _core.Problem) else int(A.shape[0] if hasattr(A, "shape") else np.shape(A)[0])
-    ids, sizes = _its._cv_folds(folds, m)
-    K, La = len(sizes), len(alphas)
+    alphas = _its._check_path_args(alphas, delta)
+    ids, sizes = _its._cv_folds(folds, _its._rows(A))
     prob = _problem(A, y, classes, dtype)
-    grouped = _grouped(prob)
-    C = prob.classes
-    if _its._weighted(prob):         # weighted held-out sums over the held-out weight sums; a zero-weight fold raises here
-        sizes = _its._cv_weight_sums(prob, ids, K)
-    prms = _params_of(prob, alphas, L, t_init_factor, delta, grouped)
-    pairs = [(f, a) for f in range(K) for a in range(La)]
-    ids_dev = _core.fold_ids_tensor(ids, prob.device)
-    X = torch.zeros(prob.n, C, K, La, dtype=torch.float64, device=prob.device)
-    total = np.zeros((K, La))
-    info = [[None] * La for _ in range(K)]
-    gtimer = _its._EventTimer(_its.grad_call_times)
-    for first, number in pack_groups(len(pairs), C):
-        grp = pairs[first:first + number]
-        held = [f for f, _ in grp for _ in range(C)]
-        handles = _class_handles(prob, [prms[a] for _, a in grp])
-        ev = gtimer.start()
-        if not _core.run_multi_folds(handles, ids_dev, held, max_iter):
-            raise _lib.FosError("fos_fista_run_multi_folds refused the multinomial lockstep: " +
-                                prob.lib.fos_last_error().decode("utf-8", "replace"))
-        gtimer.stop(ev, max_iter)
-        xg = torch.stack([st.x_tensor() for st in handles], dim=1)
-        q = prob.residual_batch_folds(xg, ids_dev, held)
-        if q is None:
-            raise _lib.FosError("fos_residual_batch_folds refused the multinomial problem: " +
-                                prob.lib.fos_last_error().decode("utf-8", "replace"))
-        for i, (f, a) in enumerate(grp):
-            X[:, :, f, a] = xg[:, i * C:(i + 1) * C]
-            total[f, a] = q[i * C]
-            s = handles[i * C].status()
-            info[f][a] = (int(s.k), int(s.stopped))
-    gtimer.flush()
-    logloss = total / sizes[:, None].astype(np.float64)
-    mean_logloss = logloss.mean(axis=0)
-    best = int(np.argmin(mean_logloss))
-    x = None
-    if refit:
-        x = _core.from_device_vec(_run_groups(prob, [prms[best]], max_iter)[0][:, :, 0], prob.like)
-    coefs = _core.from_device_vec(X, prob.like) if return_coefs else None
-    return MultinomialCVResult(alphas, logloss, mean_logloss, best, x, coefs, info)
+    fam = _family(prob, max_iter)
+    sizes = _its._cv_sizes(prob, ids, sizes)             # a weighted handle: the weight sums; a zero-weight fold raises here
+    prms = _its._path_params(prob, alphas, L, fam, t_init_factor, delta)
+    X, total, info = _its._run_cv(prob, ids, len(sizes), prms, fam, max_iter,
+                                  "fos_fista_run_multi_folds refused the multinomial lockstep: ")
+    return _its._cv_result(MultinomialCVResult, prob.like, alphas, total, sizes,
+                           (lambda best: _its._refit(prob, prms[best], fam, max_iter)) if refit else None,
+                           X if return_coefs else None, info)
 
 
 def multinomial_objective(X, A, y, alpha1, alpha2):
@@ -241,19 +158,6 @@ def multinomial_objective(X, A, y, alpha1, alpha2):
     prob = _problem(A, y, None, None)
     grouped = _grouped(prob)
     C = prob.classes
-    xt = X.detach() if _core.is_tensor(X) else torch.from_numpy(np.asarray(X, dtype=np.float64))
-    single = xt.dim() == 2
-    if xt.dim() not in (2, 3) or xt.shape[0] != prob.n or xt.shape[1] != C:
-        raise ValueError(f"X: an {prob.n} x {C} matrix or an {prob.n} x {C} x k block expected, got shape {tuple(xt.shape)}")
-    Xd = (xt.unsqueeze(2) if single else xt).to(device=prob.device, dtype=torch.float64)
-    k = Xd.shape[2]
-    nll = []
-    for first, number in pack_groups(k, C):
-        block = Xd[:, :, first:first + number].permute(0, 2, 1).reshape(prob.n, number * C)      # member-major, class-minor
-        nll += prob.residual_batch(block, use_b=True)[::C]
-    Xh = Xd.cpu().numpy()
-    pf = np.ones(prob.n) if prob.penalty_factor is None else prob.penalty_factor.to("cpu", torch.float64).numpy()
-    l1 = (pf[:, None] * np.sqrt((Xh * Xh).sum(axis=1))).sum(axis=0) if grouped else (pf[:, None, None] * np.abs(Xh)).sum(axis=(0, 1))
-    val = (np.asarray(nll, dtype=np.float64) + float(alpha1) * l1 +
-           0.5 * float(alpha2) * (pf[:, None, None] * Xh * Xh).sum(axis=(0, 1)))
-    return float(val[0]) if single else val
+    Xd, single = _its._objective_block(prob, X, C)
+    return _its._objective_value(prob, Xd, single, lambda block, number: prob.residual_batch(block, use_b=True)[::C],
+                                 alpha1, alpha2, grouped)

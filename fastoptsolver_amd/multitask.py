@@ -16,12 +16,10 @@ bounds (group norm plus box has no composed closed-form prox).
 from __future__ import annotations
 
 import numpy as np
-import torch
 
-from . import _core, _lib
+from . import _core
 from . import iterative_solvers as _its
-from .logistic import _check_path_args
-from .multinomial import pack_groups
+from .iterative_solvers import pack_groups        # (public here: the packing of the target groups)
 
 __all__ = ["multitask_path", "multitask_objective", "pack_groups", "tile_targets"]
 
@@ -47,10 +45,6 @@ def _check_targets(B, m=None):
     if m is not None and int(shape[0]) != m:
         raise ValueError(f"B must have m = {m} rows, got {shape[0]}")
     return T
-
-
-def _rows(A):
-    return A.m if isinstance(A, _core.Problem) else int(A.shape[0] if hasattr(A, "shape") else np.shape(A)[0])
 
 
 def _problem(A, dtype):
@@ -97,33 +91,15 @@ def multitask_path(A, B, alphas, t_init_factor: float = 1.0, max_iter: int = 500
     most 16384 device columns); anything else raises FosError.  Out of scope: cross-validation, sparse-group mixtures, groups
     within one column, sharded problems (module docstring)."""
     _its.reset_metrics()
-    alphas = _check_path_args(alphas, delta)
-    T = _check_targets(B, _rows(A))
+    alphas = _its._check_path_args(alphas, delta)
+    T = _check_targets(B, _its._rows(A))
     prob = _problem(A, dtype)
-    L_val = float(L) if L is not None else _its.estimate_lipschitz(prob)
-    mode = _lib.MODE_FISTA if delta is None else _lib.MODE_DELTA
-    prms = [_its._params(_its._tau(L_val, a2, t_init_factor, prob.penalty_max), a1, a2, mode=mode, delta=delta, group=T)
-            for a1, a2 in alphas]
-    Bt = _core.to_device(B, prob.device)
-    X = torch.zeros(prob.n, T, len(prms), dtype=torch.float64, device=prob.device)
-    info = []
-    gtimer = _its._EventTimer(_its.grad_call_times)
-    per = pack_groups(len(prms), T)
-    Bfull = tile_targets(Bt, per[0][1])
-    for first, number in per:
-        handles = [_its._new_state(prob, prm) for prm in prms[first:first + number] for _ in range(T)]
-        ev = gtimer.start()
-        if not _core.run_multi_rhs(handles, Bfull[:, :number * T], max_iter):
-            raise _lib.FosError("fos_fista_run_multi_rhs refused the multi-task lockstep: " +
-                                prob.lib.fos_last_error().decode("utf-8", "replace"))
-        gtimer.stop(ev, max_iter)
-        for i in range(number):
-            X[:, :, first + i] = torch.stack([st.x_tensor() for st in handles[i * T:(i + 1) * T]], dim=1)
-            s = handles[i * T].status()
-            info.append((int(s.k), int(s.stopped)))
-    gtimer.flush()
-    xs = [_core.from_device_vec(X[:, :, a], prob.like) for a in range(len(alphas))]
-    return (xs, info) if return_info else xs
+    L_val = _its._lipschitz(prob, L)                     # (estimated before B goes to the device)
+    Bfull = tile_targets(_core.to_device(B, prob.device), pack_groups(len(alphas), T)[0][1])
+    fam = _its._Family(T, T, 1.0, lambda handles, first, number: _core.run_multi_rhs(handles, Bfull[:, :number * T], max_iter),
+                       "fos_fista_run_multi_rhs refused the multi-task lockstep: ")
+    prms = _its._path_params(prob, alphas, L_val, fam, t_init_factor, delta)
+    return _its._path_result(_its._run_path(prob, prms, fam, max_iter), fam, prob.like, return_info)
 
 
 def multitask_objective(X, A, B, alpha1, alpha2):
@@ -131,29 +107,15 @@ def multitask_objective(X, A, B, alpha1, alpha2):
     device (fos_residual_batch_rhs; X is rounded to fp32 for the pass over A).  ``X``: n x T (returns a float) or an n x T x k
     block (returns k float64 values), floor(16 / T) members per pass.  p: the fp32 penalty factors of the handle as bound
     (else 1).  Synchronises."""
-    T = _check_targets(B, _rows(A))
+    T = _check_targets(B, _its._rows(A))
     prob = _problem(A, None)
-    xt = X.detach() if _core.is_tensor(X) else torch.from_numpy(np.asarray(X, dtype=np.float64))
-    single = xt.dim() == 2
-    if xt.dim() not in (2, 3) or xt.shape[0] != prob.n or xt.shape[1] != T:
-        raise ValueError(f"X: an {prob.n} x {T} matrix or an {prob.n} x {T} x k block expected, got shape {tuple(xt.shape)}")
-    Xd = (xt.unsqueeze(2) if single else xt).to(device=prob.device, dtype=torch.float64)
-    k = Xd.shape[2]
+    Xd, single = _its._objective_block(prob, X, T)
     data = _data_handle(prob)
-    Bt = _core.to_device(B, prob.device)
-    per = pack_groups(k, T)
-    Bfull = tile_targets(Bt, per[0][1])
-    rr = []
-    for first, number in per:
-        block = Xd[:, :, first:first + number].permute(0, 2, 1).reshape(prob.n, number * T)      # member-major, target-minor
+    Bfull = tile_targets(_core.to_device(B, prob.device), pack_groups(Xd.shape[2], T)[0][1])
+
+    def half_squares(block, number):
         q = data.residual_batch_rhs(block, Bfull[:, :number * T])
         if q is None:
-            raise _lib.FosError("fos_residual_batch_rhs does not serve this shape: " +
-                                prob.lib.fos_last_error().decode("utf-8", "replace"))
-        rr += np.asarray(q, dtype=np.float64).reshape(number, T).sum(axis=1).tolist()
-    Xh = Xd.cpu().numpy()
-    pf = np.ones(prob.n) if prob.penalty_factor is None else prob.penalty_factor.to("cpu", torch.float64).numpy()
-    row2 = (Xh * Xh).sum(axis=1)                                                                  # n x k
-    val = (0.5 * np.asarray(rr, dtype=np.float64) + float(alpha1) * (pf[:, None] * np.sqrt(row2)).sum(axis=0) +
-           0.5 * float(alpha2) * (pf[:, None] * row2).sum(axis=0))
-    return float(val[0]) if single else val
+            raise _its._refused(prob, "fos_residual_batch_rhs does not serve this shape: ")
+        return (0.5 * np.asarray(q, dtype=np.float64).reshape(number, T).sum(axis=1)).tolist()
+    return _its._objective_value(prob, Xd, single, half_squares, alpha1, alpha2, row_groups=True)
