@@ -547,10 +547,11 @@ class Problem:
         plan["fused_mfma"] = (flags >> 6) & 1     # opt-in: plain runs take the one-launch persistent step
         plan["chip_resident"] = (flags >> 7) & 1  # tall-skinny plain runs keep A in the LDS of up to all CUs: forced on
         plan["packed"] = (flags >> 8) & 1         # the gradient pass streams the 28-bit copy of A (after the first run packed it)
+        plan["pack_rows"] = (flags >> 9) & 7      # rows per burst of that pass on this plan: replan(pack_rows=) or the planner's (0: not served)
         return plan
 
     def replan(self, no_resident=False, no_tall=False, no_wide=False, no_colblock=False, cluster=None, interleave=None,
-               fused_mfma=False, chip_resident=None, pack=None):
+               fused_mfma=False, chip_resident=None, pack=None, pack_rows=None):
         """Re-run the planner with kernel families switched off; ``cluster`` / ``interleave``: True / False force the
         one-read cluster form of the multi-weight pass / the round-robin row order on or off, None leaves the planner's
         choice; ``fused_mfma=True`` opts plain runs in to the one-launch persistent step (fos_fista_run_fused),
@@ -558,7 +559,9 @@ class Problem:
         wherever it is served / never, None leaves the planner's region (n <= 8, up to 131072 rows);
         ``pack=True`` / ``False`` streams the gradient pass of FISTA runs from a lossless 28-bit copy of an fp32 A at any
         size it is served for / never, None leaves the planner's size threshold (the copy costs 87.5 % of A in device
-        memory and assumes A does not change while bound; any replan drops it and the next run packs again)
+        memory and assumes A does not change while bound; any replan drops it and the next run packs again);
+        ``pack_rows=1 .. 4`` (1 .. 3 above 8192 columns) makes that pass drain its loads every so many rows instead of the
+        planner's number for the geometry (same bits, another speed) until the next replan / tune
         (fos_problem_replan): tests and A/B measurements.
         Call before creating Fista handles on this problem."""
         flags = ((_lib.PLAN_NO_RESIDENT if no_resident else 0) | (_lib.PLAN_NO_TALL if no_tall else 0) |
@@ -568,6 +571,10 @@ class Problem:
                  (_lib.PLAN_FUSED_MFMA if fused_mfma else 0) |
                  (0 if chip_resident is None else (_lib.PLAN_CHIP_RESIDENT if chip_resident else _lib.PLAN_NO_CHIP_RESIDENT)) |
                  (0 if pack is None else (_lib.PLAN_PACK if pack else _lib.PLAN_NO_PACK)))
+        if pack_rows is not None:
+            if int(pack_rows) not in (1, 2, 3, 4):
+                raise ValueError("pack_rows: 1 .. 4 rows per burst")
+            flags |= int(pack_rows) * _lib.PLAN_PACK_ROWS
         with self.ctx():
             _lib.check(self.lib.fos_problem_replan(self.h, flags), "fos_problem_replan")
 

@@ -14,6 +14,7 @@ LOSS_MULTINOMIAL = 2          # set with fos_problem_set_multinomial (it takes t
 STOP_NONE, STOP_STEP, STOP_RATIO, STOP_GRAD, STOP_LS_STALL = 0, 1, 2, 3, 4
 ERR_UNSUPPORTED = -4            # FOS_ERR_UNSUPPORTED: this problem / plan has no such form (callers take the next one)
 PLAN_NO_RESIDENT, PLAN_NO_TALL, PLAN_NO_WIDE, PLAN_NO_COLBLOCK, PLAN_CLUSTER, PLAN_INTERLEAVE, PLAN_NO_INTERLEAVE, PLAN_NO_CLUSTER, PLAN_FUSED_MFMA, PLAN_CHIP_RESIDENT, PLAN_NO_CHIP_RESIDENT, PLAN_PACK, PLAN_NO_PACK = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096
+PLAN_PACK_ROWS = 8192          # FOS_PLAN_PACK_ROWS(r) = r * PLAN_PACK_ROWS, r = 1 .. 4
 
 
 class FistaParams(C.Structure):

@@ -247,6 +247,8 @@ struct CandPlan {
 struct PackPlan {
   bool tried = false, active = false;
   int threads = 0;                   // geometry the rows are laid out for: 1024 (n <= 16384) or 512 (n <= 8192)
+  int rows = 0;                      // rows per burst of the pass: FOS_PLAN_PACK_ROWS(1 .. 4) of the replan that made this plan,
+                                     // 0: the planner's for the geometry and row order (pack_rows); dropped with the copy
   unsigned e0 = 0;                   // first biased exponent of the 16-binade window (even)
   int64_t nnz = 0;                   // out-of-window elements
   DevBuf<unsigned char> P;           // m rows of pk::row_bytes(threads)

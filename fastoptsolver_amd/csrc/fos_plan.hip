@@ -507,11 +507,21 @@ int launch_pass_colblock(fos_problem* p, const YSource& ys, const float* b, bool
 // ---- 28-bit packed copy of an fp32 A for the gradient pass (gemv_packed.hpp; PackPlan) ------------------------------------
 // Where the planner packs without being asked (FOS_PLAN_PACK packs wherever the copy is served): the sweep in
 // profiles/packed/README.md.  Rows of 8193 .. 16384 columns (the 1024-thread geometry) from 2 GiB on - the smallest size
-// measured, ahead by 8-10 % there and at 4, 8, 16 and 64 GiB.  The 512-thread geometry (n <= 8192) measured 15 % BEHIND the
-// raw pass at every size (one workgroup of 8 waves per CU has too few bytes in flight with two 56-byte tiles): forced only.
+// measured, ahead by 8-10 % there and at 4, 8, 16 and 64 GiB.  The 512-thread geometry (n <= 8192) measured 11-15 % BEHIND the
+// raw pass with one row per drain and 3-10 % ahead with 4 rows per burst, but at 4 and 8 GiB by 1.6 times the raw pass's spread
+// between repeats where the rule for moving this bound asks for 5 (a noisy run; README "Rows per burst"): still forced only.
 constexpr int64_t PACK_MIN_BYTES = 2ll << 30;
 constexpr int64_t PACK_MIN_N = 8193;
 constexpr double PACK_MAX_EXCEPTIONS = 1e-3;       // share of out-of-window elements above which A stays raw
+
+// Rows per burst of the packed pass (gemv_packed.hpp): the override of the last replan, else what the probe measured fastest
+// for the geometry and row order (profiles/packed/README.md, "Rows per burst").  1024 threads: 3 with interleaved rows (64 GiB:
+// 8454 us against 8492 with 2 and 8831 for one row per drain from two tiles), 2 with row blocks (8 GiB: 1053 / 1058 / 1067 us
+// for 2 / 3 / one row).  512 threads: 4 at every size from 2 to 16 GiB, both row orders.
+int pack_rows(const fos_problem* p) {
+  if (p->pk.rows) return p->pk.rows;
+  return p->n <= 8192 ? 4 : (p->il ? 3 : 2);
+}
 
 bool vec_layout(const fos_problem* p);
 bool pack_served(const fos_problem* p) {
@@ -565,7 +575,7 @@ int ensure_packed(fos_problem* p) {
     e0 = pack_window(hist);
   }
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((m * threads + 255) / 256, (int64_t)p->ncu * 32));
-  auto refuse = [&]() { k.reset(); k.tried = true; return FOS_OK; };
+  auto refuse = [&]() { const int rows = k.rows; k.reset(); k.tried = true; k.rows = rows; return FOS_OK; };
 
   // 2. count the exceptions of every row (and look for inf / NaN): the CSR row pointers
   DevBuf<int> row_cnt;
@@ -659,8 +669,18 @@ int launch_pass_packed(fos_problem* p, const YSource& ys, const float* b, int* n
     LAUNCH_CHECK();
     bp = k.bprime;
   }
-  auto kern = k.threads == 1024 ? (p->il ? pk::gemv_packed_kernel<1024, true> : pk::gemv_packed_kernel<1024, false>)
-                                : (p->il ? pk::gemv_packed_kernel<512, true> : pk::gemv_packed_kernel<512, false>);
+  const int rows = pack_rows(p);
+  auto pick = [&](auto il) {                 // instantiations kept, as probed: 1, 2, 3 rows at 1024 threads, 1 .. 4 at 512
+    constexpr bool IL = decltype(il)::value;
+    using Kern = decltype(&pk::gemv_packed_kernel<1024, IL, 1>);
+    static const Kern menu[2][pk::MAX_ROWS] = {
+        {pk::gemv_packed_kernel<512, IL, 1>, pk::gemv_packed_kernel<512, IL, 2>, pk::gemv_packed_kernel<512, IL, 3>,
+         pk::gemv_packed_kernel<512, IL, 4>},
+        {pk::gemv_packed_kernel<1024, IL, 1>, pk::gemv_packed_kernel<1024, IL, 2>, pk::gemv_packed_kernel<1024, IL, 3>, nullptr}};
+    return menu[k.threads == 1024][rows - 1];
+  };
+  auto kern = p->il ? pick(std::true_type{}) : pick(std::false_type{});
+  if (!kern) return fail(FOS_ERR_UNSUPPORTED, "packed pass: 4 rows per burst are not instantiated for the 1024-thread geometry");
   hipLaunchKernelGGL(kern, dim3(p->pass.nwg), dim3(k.threads), 0, p->stream, (const unsigned char*)k.P.get(), bp, p->m, (int)p->n, ys,
                      (k.e0 >> 1) * 0x01010101u, p->pass.rows_per_wg, p->pass.slabs.get(), k.r.get(),
                      rr_to ? rr_to : p->pass.rr_part.get());
@@ -1621,16 +1641,20 @@ int fos_problem_replan(fos_problem* p, unsigned flags) {
   if (p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_problem_replan: a column-sharded problem keeps its two-phase plan");
   if (flags & ~(unsigned)(FOS_PLAN_NO_RESIDENT | FOS_PLAN_NO_TALL | FOS_PLAN_NO_WIDE | FOS_PLAN_NO_COLBLOCK | FOS_PLAN_CLUSTER |
                            FOS_PLAN_INTERLEAVE | FOS_PLAN_NO_INTERLEAVE | FOS_PLAN_NO_CLUSTER | FOS_PLAN_FUSED_MFMA |
-                           FOS_PLAN_CHIP_RESIDENT | FOS_PLAN_NO_CHIP_RESIDENT | FOS_PLAN_PACK | FOS_PLAN_NO_PACK))
+                           FOS_PLAN_CHIP_RESIDENT | FOS_PLAN_NO_CHIP_RESIDENT | FOS_PLAN_PACK | FOS_PLAN_NO_PACK | FOS_PLAN_PACK_ROWS_MASK))
     return fail(FOS_ERR_ARG, "fos_problem_replan: unknown flag");
+  const int pack_rows_req = (int)((flags & FOS_PLAN_PACK_ROWS_MASK) / FOS_PLAN_PACK_ROWS(1));
+  if (pack_rows_req > (p->n <= 8192 ? 4 : 3))
+    return fail(FOS_ERR_ARG, "fos_problem_replan: FOS_PLAN_PACK_ROWS takes 1 .. 4 rows per burst for n <= 8192 and 1 .. 3 above");
   p->cp_mode = (flags & FOS_PLAN_CLUSTER) ? 1 : (flags & FOS_PLAN_NO_CLUSTER) ? 2 : 0;
   p->fused_on = (flags & FOS_PLAN_FUSED_MFMA) != 0;
   p->chip_mode = (flags & FOS_PLAN_CHIP_RESIDENT) ? 1 : (flags & FOS_PLAN_NO_CHIP_RESIDENT) ? 2 : 0;
   p->pack_mode = (flags & FOS_PLAN_NO_PACK) ? 2 : (flags & FOS_PLAN_PACK) ? 1 : 0;
   flags &= ~(unsigned)(FOS_PLAN_CLUSTER | FOS_PLAN_NO_CLUSTER | FOS_PLAN_FUSED_MFMA | FOS_PLAN_CHIP_RESIDENT |
-                       FOS_PLAN_NO_CHIP_RESIDENT | FOS_PLAN_PACK | FOS_PLAN_NO_PACK);
+                       FOS_PLAN_NO_CHIP_RESIDENT | FOS_PLAN_PACK | FOS_PLAN_NO_PACK | FOS_PLAN_PACK_ROWS_MASK);
   int rc = invalidate(p, IN_PLAN);
   if (rc) return rc;
+  p->pk.rows = pack_rows_req;                // lives with the copy: the next invalidating call puts the planner's back
   apply_plan(p, flags);
   return ensure_workspace(p);
 }
@@ -1713,7 +1737,7 @@ int fos_problem_plan(const fos_problem* p, int32_t plan[8]) {
   plan[5] = p->pass.nslabs;
   plan[6] = (p->pass.path == 0 ? 1 : 0) | (p->pass.resident ? 2 : 0) | (p->pass.tall ? 4 : 0) | (p->pass.colblock ? 8 : 0) | (p->multi.cp_cs ? 16 : 0) |
             ((p->il && p->pass.entry && p->pass.entry->with_g_il && p->pass.path == 0 && !p->pass.colblock && !p->pass.tall) ? 32 : 0) |
-            (p->fused_on ? 64 : 0) | (p->chip_mode == 1 ? 128 : 0) | (p->pk.active ? 256 : 0);
+            (p->fused_on ? 64 : 0) | (p->chip_mode == 1 ? 128 : 0) | (p->pk.active ? 256 : 0) | ((pack_served(p) ? pack_rows(p) : 0) << 9);
   plan[7] = p->ncu;
   return FOS_OK;
 }

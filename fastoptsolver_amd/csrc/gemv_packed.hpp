@@ -10,6 +10,10 @@
 // Decode: 4 VALU instructions turn four nibbles into the four top bytes [sign | exponent >> 1], then one v_perm_b32 each for
 // a, b, c and three for d - 10 per 4 elements, all exact.  Threads beyond n read zero bytes against a zero slice of y.
 //
+// The pass.  Drained, in bursts of R rows from one register tile: R x 56 bytes per thread in flight, then one barrier and one
+// cross-wave ladder for the R rows (see gemv_packed_kernel).  R is the planner's (fos_plan.hip pack_rows: what measured
+// fastest per geometry and row order) or FOS_PLAN_PACK_ROWS; the result does not depend on it bit for bit.
+//
 // Exceptions.  An element outside the window (zero, denormal, too small, too large) is stored as an in-window placeholder and
 // listed in a sparse D with A = P + D exactly (two entries per exception, +true and -placeholder, so nothing is rounded at
 // pack time).  D never enters the streaming loop: pk_bprime_kernel forms b' = b - D y before the pass, the pass runs on b'
@@ -78,18 +82,30 @@ __device__ inline u32x2 load8nt(const void* p) { return __builtin_nontemporal_lo
 
 // ---- the pass -----------------------------------------------------------------------------------------------------------
 // slab[w] = sum over the rows of workgroup w of P_i^T (P_i . y - b_i),  r_out[i] = P_i . y - b_i,  rr_part[w] = sum r_i^2.
-// The pipeline of gemv_pair_kernel with R = 1, two register tiles and DRAIN: a straight-line steady state, prefetch rows
-// clamped instead of predicated.  Rows: contiguous blocks of rows_per_wg (IL = false) or dealt round-robin (IL = true).
-// The cross-wave sum is one LDS read per lane plus the DPP ladder; both products are v_pk_fma_f32.
+// Rows: contiguous blocks of rows_per_wg (IL = false) or dealt round-robin (IL = true); step s of workgroup w is row
+// row_lo + first + s * group.  The loop is DRAINED and works in bursts of R steps from ONE register tile:
+//   issue the loads of R rows (rows past the end clamped, not predicated: loaded and weighted by zero); s_waitcnt vmcnt(0);
+//   per row: decode, the dot with y (v_pk_fma_f32, acc0 / acc1), the wave sum, lane 0 -> red[pb][r][wave];
+//   ONE barrier; lanes 16r .. 16r+NW-1 read row r's partials (all others 0); ONE row_shr 1/2/4/8 ladder leaves the sum of
+//   row r in lane 16r+15, a readlane per row; then per row, in step order: s -= b, rr += s^2, r_out, gv += a[r] * s
+// with the decoded a[R][8] kept in registers across the barrier, so nothing is decoded twice.  The load latency, the barrier,
+// the LDS round trip and the cross-wave ladder are paid once per R * 56 * THREADS bytes in flight instead of once per row:
+// that, not overlap (a wave never computes while its own loads are in flight), is what R buys - profiles/packed/README.md.
+// Every row sees the same operations in the same order for every R (the 16-lane ladder is the 64-lane wave_sum of one
+// partial per lane without its additions of zero), so slabs, rr_part and r_out do not depend on R bit for bit.
+// ADJ (IL only; the probe's variant, no product launch uses it) takes the rows of a burst adjacent in memory instead:
+// workgroup w owns rows R*(w + k*grid) .. +R-1.  That changes which rows a workgroup sums, so its bits depend on R.
 // Requirements (checked on the host): n % 16 == 0, n <= 16 * THREADS, P 16-byte aligned with rows of row_bytes(THREADS).
-template <int THREADS, bool IL>
+constexpr int MAX_ROWS = 4;                  // rows per burst: one 16-lane DPP row each
+
+template <int THREADS, bool IL, int R, bool ADJ = false>
 __global__ __launch_bounds__(THREADS, THREADS / 256) void gemv_packed_kernel(
     const unsigned char* __restrict__ P, const float* __restrict__ b, int64_t m, int n, YSource ys, unsigned e0h4,
     int64_t rows_per_wg, float* __restrict__ slabs, float* __restrict__ r_out, double* __restrict__ rr_part) {
   constexpr int NW = THREADS / 64;
-  constexpr int NBUF = 2;
-  static_assert(NW >= 8 && NW <= 64, "one partial per lane in the cross-wave sum");
-  __shared__ float red[2][NW];
+  static_assert(NW >= 8 && NW <= 16 && R >= 1 && R <= MAX_ROWS, "the partials of one row fill at most one 16-lane DPP row");
+  static_assert(IL || !ADJ, "rows of a block are adjacent already");
+  __shared__ float red[2][R][NW];
 
   if (ys.stopped != nullptr && *ys.stopped != 0) return;
   if (ys.t_stamp != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *ys.t_stamp = wall_clock64();
@@ -122,73 +138,76 @@ __global__ __launch_bounds__(THREADS, THREADS / 256) void gemv_packed_kernel(
   const int64_t group = IL ? gridDim.x : 1;
   const int64_t first = IL ? (int64_t)blockIdx.x : 0;
   const int64_t nsteps = nrows > first ? (nrows - first + group - 1) / group : 0;
+  const int64_t nbursts = ADJ ? (nrows > first * R ? (nrows - first * R + group * R - 1) / (group * R) : 0) : (nsteps + R - 1) / R;
+  auto row_of = [&](int64_t k, int r) -> int64_t {       // row of step k*R + r; at or past row_hi beyond the last step
+    return ADJ ? (first + k * group) * R + r : row_lo + first + (k * R + r) * group;
+  };
   const int64_t rbytes = row_bytes(THREADS);
   const unsigned voff16 = (unsigned)tid * 16u, voff8 = (unsigned)THREADS * 48u + (unsigned)tid * 8u;
   double rr = 0.0;
 
-  u32x4 tile[NBUF][3];
-  u32x2 nib[NBUF];
-  float bval[NBUF];
+  u32x4 tile[R][3];
+  u32x2 nib[R];
+  float bval[R];
   const float* b_src = b != nullptr ? b : reinterpret_cast<const float*>(P);   // dummy source, discarded by select
-  auto issue = [&](int buf, int64_t step) {
-    int64_t row = row_lo + first + step * group;
-    if (row >= row_hi) row = row_hi - 1;     // clamp: loaded but weighted by zero below
-    bval[buf] = b_src[b != nullptr ? row : 0];
-    const unsigned char* rp = P + row * rbytes;
+  for (int64_t k = 0; k < nbursts; ++k) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) tile[buf][c] = load16<true>(rp + voff16 + (unsigned)c * THREADS * 16u);
-    nib[buf] = load8nt(rp + voff8);
-  };
-  auto consume = [&](int buf, int64_t step) {
-    f32x2 a[CPT / 2];
+    for (int r = 0; r < R; ++r) {
+      int64_t row = row_of(k, r);
+      if (row >= row_hi) row = row_hi - 1;   // clamp: loaded but weighted by zero below (nbursts > 0: the workgroup has a row)
+      bval[r] = b_src[b != nullptr ? row : 0];
+      const unsigned char* rp = P + row * rbytes;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const unsigned w = (g >> 1) ? nib[buf].y : nib[buf].x;
-      const unsigned top = top_bytes((g & 1) ? (w >> 4) : w, e0h4);
-      float f[4];
-      decode_group(tile[buf][0][g], tile[buf][1][g], tile[buf][2][g], top, f);
-      a[2 * g] = f32x2{f[0], f[1]}; a[2 * g + 1] = f32x2{f[2], f[3]};
+      for (int c = 0; c < 3; ++c) tile[r][c] = load16<true>(rp + voff16 + (unsigned)c * THREADS * 16u);
+      nib[r] = load8nt(rp + voff8);
     }
-    f32x2 acc0 = f32x2{0.f, 0.f}, acc1 = f32x2{0.f, 0.f};
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    f32x2 a[R][CPT / 2];
+    const int pb = (int)(k & 1);
 #pragma unroll
-    for (int e = 0; e < CPT / 2; e += 2) {
-      acc0 = __builtin_elementwise_fma(a[e], yv[e], acc0);
-      acc1 = __builtin_elementwise_fma(a[e + 1], yv[e + 1], acc1);
-    }
-    acc0 += acc1;
-    const float part = wave_sum(acc0.x + acc0.y);
-    const int pb = (int)(step & 1);
-    if (lane == 0) red[pb][wave] = part;
-    __syncthreads();
-    float s = wave_sum(lane < NW ? red[pb][lane] : 0.f);
-    const int64_t row = row_lo + first + step * group;
-    const float bi = b != nullptr ? bval[buf] : 0.f;
-    if (row < row_hi) {
-      s -= bi;
-      rr += (double)s * (double)s;
-      if (tid == 0) r_out[row] = s;
-    } else {
-      s = 0.f;
-    }
-    const f32x2 s2 = f32x2{s, s};
+    for (int r = 0; r < R; ++r) {
 #pragma unroll
-    for (int e = 0; e < CPT / 2; ++e) gv[e] = __builtin_elementwise_fma(a[e], s2, gv[e]);
-  };
-
-  if (nsteps > 0) {
-    issue(0, 0);
-    int64_t s = 0;
-    for (; s + NBUF <= nsteps; s += NBUF) {
-#pragma unroll
-      for (int u = 0; u < NBUF; ++u) {
-        issue((u + NBUF - 1) % NBUF, s + u + NBUF - 1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        consume(u, s + u);
-        __builtin_amdgcn_sched_barrier(0);
+      for (int g = 0; g < 4; ++g) {
+        const unsigned w = (g >> 1) ? nib[r].y : nib[r].x;
+        const unsigned top = top_bytes((g & 1) ? (w >> 4) : w, e0h4);
+        float f[4];
+        decode_group(tile[r][0][g], tile[r][1][g], tile[r][2][g], top, f);
+        a[r][2 * g] = f32x2{f[0], f[1]}; a[r][2 * g + 1] = f32x2{f[2], f[3]};
       }
+      f32x2 acc0 = f32x2{0.f, 0.f}, acc1 = f32x2{0.f, 0.f};
+#pragma unroll
+      for (int e = 0; e < CPT / 2; e += 2) {
+        acc0 = __builtin_elementwise_fma(a[r][e], yv[e], acc0);
+        acc1 = __builtin_elementwise_fma(a[r][e + 1], yv[e + 1], acc1);
+      }
+      acc0 += acc1;
+      const float part = wave_sum(acc0.x + acc0.y);
+      if (lane == 0) red[pb][r][wave] = part;
     }
-    if (s < nsteps) consume(0, s);           // its tile is already in flight
+    __syncthreads();                         // red[pb] is written again two bursts on, behind the next burst's barrier
+    float v = ((lane >> 4) < R && (lane & 15) < NW) ? red[pb][lane >> 4][lane & 15] : 0.f;
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xF, 0xF, false));   // row_shr:1
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xF, 0xF, false));   // row_shr:2
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xF, 0xF, false));   // row_shr:4
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xF, 0xF, false));   // row_shr:8
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float s = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16 * r + 15));
+      const int64_t row = row_of(k, r);
+      const float bi = b != nullptr ? bval[r] : 0.f;
+      if (row < row_hi) {
+        s -= bi;
+        rr += (double)s * (double)s;
+        if (tid == 0) r_out[row] = s;
+      } else {
+        s = 0.f;
+      }
+      const f32x2 s2 = f32x2{s, s};
+#pragma unroll
+      for (int e = 0; e < CPT / 2; ++e) gv[e] = __builtin_elementwise_fma(a[r][e], s2, gv[e]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
   }
 
   if (live) {

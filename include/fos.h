@@ -54,14 +54,20 @@ enum { FOS_PLAN_NO_RESIDENT = 1, FOS_PLAN_NO_TALL = 2, FOS_PLAN_NO_WIDE = 4, FOS
                                        fp32 A (csrc/gemv_packed.hpp) at ANY size the copy is served for - streaming single
                                        pass, n a multiple of 16 up to 16384, no inf / NaN, at most 1e-3 of the elements
                                        outside the exponent window; the first with-gradient pass of any entry point packs ... */
-       FOS_PLAN_NO_PACK = 4096      /* ... or never; neither bit: the planner packs where it measured ahead - rows of 8193 ..
+       FOS_PLAN_NO_PACK = 4096,     /* ... or never; neither bit: the planner packs where it measured ahead - rows of 8193 ..
                                        16384 columns from 2 GiB on (profiles/packed/README.md).  The copy is made by the first fos_fista_run /
                                        _run_backtracking / _run_recorded call after the plan was made and
                                        costs 87.5 % of A in device memory on top of A (it is skipped, and the raw pass kept,
                                        when that much is not free).  A PACKED HANDLE ASSUMES THAT A DOES NOT CHANGE WHILE
                                        IT IS BOUND: fos_problem_replan (any flags) drops the copy and the next run packs
                                        again.  Results are deterministic and agree with the raw pass to rounding (the
-                                       products of out-of-window elements are summed separately in fp64). */ };
+                                       products of out-of-window elements are summed separately in fp64). */
+       FOS_PLAN_PACK_ROWS_MASK = 7 * 8192 /* FOS_PLAN_PACK_ROWS(r), r = 1 .. 4 (1 .. 3 above 8192 columns; else FOS_ERR_ARG): the
+                                       packed pass drains its loads every r rows (csrc/gemv_packed.hpp) on THIS plan - tests and
+                                       A/B runs; results do not depend on r bit for bit.  No bits: the planner's choice for the
+                                       geometry and row order, which every later fos_problem_replan / fos_problem_tune /
+                                       fos_problem_set_comm puts back, as it drops the copy. */ };
+#define FOS_PLAN_PACK_ROWS(r) ((unsigned)(r) * 8192u)
 
 typedef struct fos_problem fos_problem;   /* A, b, launch plan, workspace            */
 typedef struct fos_comm fos_comm;         /* communicator of a row-sharded problem   */
@@ -127,7 +133,9 @@ int fos_problem_set_stream(fos_problem* p, void* stream);
  *               any single-pass kernel - column blocks through the streaming kernel in two phases, A read twice;
  *               bit 4: set once fos_fista_run_multi has planned the one-read cluster form of the matrix-core pass;
  *               bit 5: the streaming pass deals its rows round-robin to the workgroups; bit 6: FOS_PLAN_FUSED_MFMA; bit 7: the chip-resident loop is forced on;
- *               bit 8: the gradient pass currently streams the 28-bit packed copy of A (set once a run has packed)), CUs} */
+ *               bit 8: the gradient pass currently streams the 28-bit packed copy of A (set once a run has packed);
+ *               bits 9-11: rows per burst the packed pass takes on this plan, FOS_PLAN_PACK_ROWS or the planner's (0: no copy is
+ *               served for this plan)), CUs} */
 int fos_problem_plan(const fos_problem* p, int32_t plan[8]);
 /* Re-run the planner with kernel families switched off (FOS_PLAN_* bits): NO_RESIDENT keeps small problems off the
  * one-launch LDS-resident loop, NO_TALL keeps n <= 64 off the row-per-thread pass, NO_WIDE keeps 16384 < n <= 32768 off

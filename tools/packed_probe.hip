@@ -5,8 +5,12 @@
 //   loads_pack  : loads-only pass over the packed buffer (0.875 x the bytes)
 //   raw_body    : the library's instantiation of fos::gemv_pair_kernel for that width, rows ordered as the planner would
 //   packed_body : loads + decode + both products from the packed copy, no exceptions (out-of-window elements are
-//                 clamped into the window in BOTH buffers before anything is timed, so both bodies see the same matrix)
-// Both bodies are checked against the two-pass fp64-accumulating fallback kernels.
+//                 clamped into the window in BOTH buffers before anything is timed, so both bodies see the same matrix):
+//                 one row per drain from two register tiles, the library's pass before it worked in bursts
+//   rowsR       : the library's fos::pk::gemv_packed_kernel with R rows per burst (1, 2, 3 at 1024 threads; 2, 3, 4 at 512)
+//   rowsR_adj   : the same with the rows of a burst adjacent in memory (interleaved row order only; not bit-identical)
+// All bodies are checked against the two-pass fp64-accumulating fallback kernels, and every rowsR bit for bit against packed_body.
+// Last lines: each variant against packed_body and the stop rule (median faster by 5 x packed_body's max - min).
 //
 // Packed format (one row = 3 planes of THREADS*16 bytes + 1 plane of THREADS*8 bytes; thread t owns columns 16t..16t+15):
 //   see fastoptsolver_amd/csrc/gemv_packed.hpp, whose kernel and packer this probe runs.
@@ -15,6 +19,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <string>
+#include <type_traits>
 #include <vector>
 #include "../fastoptsolver_amd/csrc/gemv_packed.hpp"
 
@@ -65,6 +72,131 @@ __global__ void reduce_slabs(const float* slabs, int nslabs, int n, float* g) {
   for (int s = 0; s < nslabs; ++s) acc += (double)slabs[(size_t)s * n + j];
   g[j] = (float)acc;
 }
+
+// packed_body, the baseline of the rows-per-burst stop rule: the pass as the library had it before it worked in bursts, kept here
+// so that the tables in profiles/packed/README.md can be taken again.  One row per drain, TWO register tiles (the second buys
+// nothing in a drained loop), a 64-lane ladder for the cross-wave sum.
+namespace fos {
+namespace pk {
+template <int THREADS, bool IL>
+__global__ __launch_bounds__(THREADS, THREADS / 256) void packed_2tile_kernel(
+    const unsigned char* __restrict__ P, const float* __restrict__ b, int64_t m, int n, YSource ys, unsigned e0h4,
+    int64_t rows_per_wg, float* __restrict__ slabs, float* __restrict__ r_out, double* __restrict__ rr_part) {
+  constexpr int NW = THREADS / 64;
+  constexpr int NBUF = 2;
+  static_assert(NW >= 8 && NW <= 64, "one partial per lane in the cross-wave sum");
+  __shared__ float red[2][NW];
+
+  if (ys.stopped != nullptr && *ys.stopped != 0) return;
+  if (ys.t_stamp != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *ys.t_stamp = wall_clock64();
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t row_lo = IL ? 0 : (int64_t)blockIdx.x * rows_per_wg;
+  int64_t row_hi = IL ? m : row_lo + rows_per_wg;
+  if (row_hi > m) row_hi = m;
+
+  const int col = tid * CPT;
+  const bool live = col < n;                 // n % 16 == 0: a thread is wholly live or wholly dead
+  f32x2 yv[CPT / 2], gv[CPT / 2];
+#pragma unroll
+  for (int e = 0; e < CPT / 2; ++e) { yv[e] = f32x2{0.f, 0.f}; gv[e] = f32x2{0.f, 0.f}; }
+  if (live) {
+    const double beta = source_beta(ys);
+#pragma unroll
+    for (int q = 0; q < CPT / 4; ++q) {
+      if (ys.y != nullptr) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(ys.y + col + 4 * q);
+        yv[2 * q] = f32x2{t.x, t.y}; yv[2 * q + 1] = f32x2{t.z, t.w};
+      } else {                               // the same form_y as the update kernel: both kernels see the same y_k
+        yv[2 * q] = f32x2{(float)source_y(ys, col + 4 * q, beta), (float)source_y(ys, col + 4 * q + 1, beta)};
+        yv[2 * q + 1] = f32x2{(float)source_y(ys, col + 4 * q + 2, beta), (float)source_y(ys, col + 4 * q + 3, beta)};
+      }
+    }
+  }
+
+  const int64_t nrows = row_hi - row_lo;     // may be <= 0 for trailing workgroups
+  const int64_t group = IL ? gridDim.x : 1;
+  const int64_t first = IL ? (int64_t)blockIdx.x : 0;
+  const int64_t nsteps = nrows > first ? (nrows - first + group - 1) / group : 0;
+  const int64_t rbytes = row_bytes(THREADS);
+  const unsigned voff16 = (unsigned)tid * 16u, voff8 = (unsigned)THREADS * 48u + (unsigned)tid * 8u;
+  double rr = 0.0;
+
+  u32x4 tile[NBUF][3];
+  u32x2 nib[NBUF];
+  float bval[NBUF];
+  const float* b_src = b != nullptr ? b : reinterpret_cast<const float*>(P);   // dummy source, discarded by select
+  auto issue = [&](int buf, int64_t step) {
+    int64_t row = row_lo + first + step * group;
+    if (row >= row_hi) row = row_hi - 1;     // clamp: loaded but weighted by zero below
+    bval[buf] = b_src[b != nullptr ? row : 0];
+    const unsigned char* rp = P + row * rbytes;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) tile[buf][c] = load16<true>(rp + voff16 + (unsigned)c * THREADS * 16u);
+    nib[buf] = load8nt(rp + voff8);
+  };
+  auto consume = [&](int buf, int64_t step) {
+    f32x2 a[CPT / 2];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const unsigned w = (g >> 1) ? nib[buf].y : nib[buf].x;
+      const unsigned top = top_bytes((g & 1) ? (w >> 4) : w, e0h4);
+      float f[4];
+      decode_group(tile[buf][0][g], tile[buf][1][g], tile[buf][2][g], top, f);
+      a[2 * g] = f32x2{f[0], f[1]}; a[2 * g + 1] = f32x2{f[2], f[3]};
+    }
+    f32x2 acc0 = f32x2{0.f, 0.f}, acc1 = f32x2{0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < CPT / 2; e += 2) {
+      acc0 = __builtin_elementwise_fma(a[e], yv[e], acc0);
+      acc1 = __builtin_elementwise_fma(a[e + 1], yv[e + 1], acc1);
+    }
+    acc0 += acc1;
+    const float part = wave_sum(acc0.x + acc0.y);
+    const int pb = (int)(step & 1);
+    if (lane == 0) red[pb][wave] = part;
+    __syncthreads();
+    float s = wave_sum(lane < NW ? red[pb][lane] : 0.f);
+    const int64_t row = row_lo + first + step * group;
+    const float bi = b != nullptr ? bval[buf] : 0.f;
+    if (row < row_hi) {
+      s -= bi;
+      rr += (double)s * (double)s;
+      if (tid == 0) r_out[row] = s;
+    } else {
+      s = 0.f;
+    }
+    const f32x2 s2 = f32x2{s, s};
+#pragma unroll
+    for (int e = 0; e < CPT / 2; ++e) gv[e] = __builtin_elementwise_fma(a[e], s2, gv[e]);
+  };
+
+  if (nsteps > 0) {
+    issue(0, 0);
+    int64_t s = 0;
+    for (; s + NBUF <= nsteps; s += NBUF) {
+#pragma unroll
+      for (int u = 0; u < NBUF; ++u) {
+        issue((u + NBUF - 1) % NBUF, s + u + NBUF - 1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        consume(u, s + u);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if (s < nsteps) consume(0, s);           // its tile is already in flight
+  }
+
+  if (live) {
+    float* slab = slabs + (int64_t)blockIdx.x * n + col;
+#pragma unroll
+    for (int q = 0; q < CPT / 4; ++q)
+      *reinterpret_cast<f32x4*>(slab + 4 * q) = f32x4{gv[2 * q].x, gv[2 * q].y, gv[2 * q + 1].x, gv[2 * q + 1].y};
+  }
+  if (tid == 0) rr_part[blockIdx.x] = rr;
+}
+}  // namespace pk
+}  // namespace fos
 
 // the library's streaming instantiation for full rows of 16 * THREADS columns (fos_plan.hip kMenu): 1024 x 4 chunks, two
 // tiles, drained; 512 x 4 chunks, three tiles
@@ -132,7 +264,7 @@ int run(int64_t m, int iters, int rounds) {
     else launch_raw<THREADS, false>(A, b, m, n, ys, rpw, slabs, rr, nwg, st);
   };
   auto run_packed = [&] {
-    auto kern = il ? pk::gemv_packed_kernel<THREADS, true> : pk::gemv_packed_kernel<THREADS, false>;
+    auto kern = il ? pk::packed_2tile_kernel<THREADS, true> : pk::packed_2tile_kernel<THREADS, false>;
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(THREADS), 0, st, (const unsigned char*)P, (const float*)b, m, n, ys, e0h4, rpw, slabs,
                        rout, rr);
   };
@@ -179,14 +311,63 @@ int run(int64_t m, int iters, int rounds) {
     printf("packed_body  residual relerr vs fp64 %.3e\n", std::sqrt(e / nn));
   }
 
-  struct Var { const char* name; double bytes; std::vector<double> us; };
-  Var vars[4] = {{"loads_raw", (double)raw_bytes, {}}, {"loads_pack", (double)pk_bytes, {}}, {"raw_body", (double)raw_bytes, {}},
-                 {"packed_body", (double)pk_bytes, {}}};
+  // the library's pass with R rows per burst: R = 1, 2, 3 at 1024 threads, 2, 3, 4 at 512; strided (the library's row assignment) and, where the rows
+  // are interleaved, adjacent.  Each strided variant must reproduce packed_body bit for bit (slabs, stored r, rr partials).
+  constexpr int RA = THREADS == 1024 ? 1 : 2;
+  auto launch_rows = [&](int R, bool adj) {
+    auto go = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(nwg), dim3(THREADS), 0, st, (const unsigned char*)P, (const float*)b, m, n, ys, e0h4, rpw, slabs,
+                         rout, rr);
+    };
+    auto pick = [&](auto rc) {
+      constexpr int RR = decltype(rc)::value;
+      if (!il) go(pk::gemv_packed_kernel<THREADS, false, RR>);
+      else if (adj) go(pk::gemv_packed_kernel<THREADS, true, RR, true>);
+      else go(pk::gemv_packed_kernel<THREADS, true, RR>);
+    };
+    if (R == RA) pick(std::integral_constant<int, RA>{});
+    else if (R == RA + 1) pick(std::integral_constant<int, RA + 1>{});
+    else pick(std::integral_constant<int, RA + 2>{});
+  };
+  {
+    std::vector<float> s0((size_t)nwg * n), s1((size_t)nwg * n), r0(m), r1(m);
+    std::vector<double> q0(nwg), q1(nwg);
+    run_packed();
+    CK(hipStreamSynchronize(st));
+    CK(hipMemcpy(s0.data(), slabs, s0.size() * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(r0.data(), rout, (size_t)m * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(q0.data(), rr, (size_t)nwg * 8, hipMemcpyDeviceToHost));
+    for (int R = RA; R < RA + 3; ++R)
+      for (int adj = 0; adj <= (il ? 1 : 0); ++adj) {
+        CK(hipMemsetAsync(slabs, 0xff, s0.size() * 4, st));
+        CK(hipMemsetAsync(rout, 0xff, (size_t)m * 4, st));
+        launch_rows(R, adj != 0);
+        char name[32];
+        snprintf(name, sizeof name, "rows%d%s", R, adj ? "_adj" : "");
+        check(name);
+        CK(hipMemcpy(s1.data(), slabs, s1.size() * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(r1.data(), rout, (size_t)m * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(q1.data(), rr, (size_t)nwg * 8, hipMemcpyDeviceToHost));
+        const bool same = !memcmp(s0.data(), s1.data(), s0.size() * 4) && !memcmp(r0.data(), r1.data(), (size_t)m * 4) &&
+                          !memcmp(q0.data(), q1.data(), (size_t)nwg * 8);
+        const bool same_r = !memcmp(r0.data(), r1.data(), (size_t)m * 4);
+        printf("%-12s bitwise vs packed_body: slabs+r+rr %s, stored r %s\n", name, same ? "IDENTICAL" : "differ", same_r ? "IDENTICAL" : "differ");
+        if (!adj && !same) { fprintf(stderr, "the strided burst is not bit-identical with packed_body\n"); return 1; }
+      }
+  }
+
+  struct Var { std::string name; double bytes; int R; bool adj; std::vector<double> us; };
+  std::vector<Var> vars = {{"loads_raw", (double)raw_bytes, 0, false, {}}, {"loads_pack", (double)pk_bytes, 0, false, {}},
+                           {"raw_body", (double)raw_bytes, 0, false, {}}, {"packed_body", (double)pk_bytes, 0, false, {}}};
+  for (int adj = 0; adj <= (il ? 1 : 0); ++adj)
+    for (int R = RA; R < RA + 3; ++R)
+      vars.push_back({"rows" + std::to_string(R) + (adj ? "_adj" : ""), (double)pk_bytes, R, adj != 0, {}});
   for (int round = -1; round < rounds; ++round) {       // round -1: warm-up, not recorded
-    for (int v = 0; v < 4; ++v) {
+    for (size_t v = 0; v < vars.size(); ++v) {
       CK(hipEventRecord(e0v, st));
       for (int i = 0; i < iters; ++i) {
-        if (v == 0) run_loads_raw(); else if (v == 1) run_loads_pack(); else if (v == 2) run_raw(); else run_packed();
+        if (v == 0) run_loads_raw(); else if (v == 1) run_loads_pack(); else if (v == 2) run_raw(); else if (v == 3) run_packed();
+        else launch_rows(vars[v].R, vars[v].adj);
       }
       CK(hipEventRecord(e1v, st));
       CK(hipEventSynchronize(e1v));
@@ -196,14 +377,24 @@ int run(int64_t m, int iters, int rounds) {
     }
   }
   for (auto& v : vars) {
+    printf("%-12s rounds:", v.name.c_str());             // in the order taken: an outlier round shows in every variant or in one
+    for (double t : v.us) printf(" %.1f", t);
+    printf("\n");
     std::sort(v.us.begin(), v.us.end());
     const double med = v.us[v.us.size() / 2];
-    printf("%-12s us/pass min %.1f med %.1f max %.1f   %.0f GB/s own bytes (%.1f%% of 8 TB/s)\n", v.name, v.us.front(), med,
+    printf("%-12s us/pass min %.1f med %.1f max %.1f   %.0f GB/s own bytes (%.1f%% of 8 TB/s)\n", v.name.c_str(), v.us.front(), med,
            v.us.back(), v.bytes / (med * 1e-6) / 1e9, v.bytes / (med * 1e-6) / 8e12 * 100);
   }
   const double mr = vars[2].us[vars[2].us.size() / 2], mp = vars[3].us[vars[3].us.size() / 2];
   printf("packed_body / raw_body median time %.4f  (bytes ratio 0.8750; raw spread %.4f, packed spread %.4f of median)\n", mp / mr,
          (vars[2].us.back() - vars[2].us.front()) / mr, (vars[3].us.back() - vars[3].us.front()) / mp);
+  // stop rule: a rows variant counts only if its median beats packed_body's by 5 x packed_body's own max - min
+  const double spread = vars[3].us.back() - vars[3].us.front();
+  for (size_t v = 4; v < vars.size(); ++v) {
+    const double med = vars[v].us[vars[v].us.size() / 2];
+    printf("%-12s / packed_body %.4f  / raw_body %.4f  gain %.1f us = %.1f x packed_body spread (%.1f us): %s\n", vars[v].name.c_str(),
+           med / mp, med / mr, mp - med, spread > 0 ? (mp - med) / spread : 0.0, spread, mp - med >= 5 * spread ? "PASS" : "no");
+  }
   for (void* q : {(void*)A, (void*)P, (void*)b, (void*)rout, (void*)y, (void*)rvec, (void*)slabs, (void*)g, (void*)gref, (void*)rr,
                   (void*)counts, (void*)row_cnt})
     CK(hipFree(q));
