@@ -12,6 +12,8 @@ from .multitask import multitask_objective, multitask_path         # noqa: F401
 from .objective_functions import compute_objective, group_lasso_objective                    # noqa: F401
 from .operators import ElasticNetProx, L1Prox, LeastSquares           # noqa: F401
 from .prox_operators import prox_elastic_net, prox_l1                 # noqa: F401
+# the working-set solve: importable from the package; __all__ stays the list the guard tables of the handle kinds file name by name
+from .working_set import WorkingSetInfo, alpha_max, kkt_excess, working_set_path   # noqa: F401
 
 __all__ = ["fista", "fista_delta", "fista_path", "fista_cv", "CVResult", "ista", "estimate_lipschitz", "reset_metrics", "get_metrics", "LBFGSSolver",
            "compute_objective", "prox_l1", "prox_elastic_net", "LeastSquares", "L1Prox", "ElasticNetProx",

@@ -678,6 +678,56 @@ class Problem:
             _lib.check(self.lib.fos_gram_apply(ptr(Xf), nv, self.h, ptr(G)), "fos_gram_apply")
         return self.vec_out(G).t()
 
+    # ---- working-set solve (include/fos_working_set.h; working_set.py drives these) ----------------------------------
+    def gradient_block(self, X, want_loss=False):
+        """The gradient of the data term at the nv <= 16 columns of X (n x nv): A^T W (A X_j - b), or A^T W (sigma(A X_j) - b) on
+        a logistic handle (fos_gradient_batch), as the nv x n_dev float32 device block fos_kkt_scan reads (row j: column j).
+        want_loss: also the data-term sums of `residual_batch` from the same pass, as a host list (synchronises)."""
+        Xf, nv = self._block16(X)
+        G = torch.empty(nv, self.n_dev, dtype=torch.float32, device=self.device)
+        with self.ctx():
+            _lib.check(self.lib.fos_gradient_batch(ptr(Xf), nv, self.h, ptr(G), ptr(self.scratch) if want_loss else None),
+                       "fos_gradient_batch")
+        return (G, self.scratch[:nv].cpu().tolist()) if want_loss else G
+
+    def gradient_batch(self, X):
+        """`gradient_block` in the layout of `gram_apply`: an n x nv float32 device tensor.  Enqueues only."""
+        return self.vec_out(self.gradient_block(X)).t()
+
+    def gather_columns(self, idx, n_ws_pad=None, out=None):
+        """The device columns idx of A as an m x n_ws_pad tensor of A's element type, zero from column len(idx) on
+        (fos_gather_columns).  idx: strictly increasing device column numbers in 0 .. n_dev - 1 (checked here: ValueError);
+        n_ws_pad: a multiple of 8, default len(idx) rounded up to 8; out: a tensor to write into (row stride a multiple of 8
+        elements, at least n_ws_pad)."""
+        idx = torch.as_tensor(idx, device=self.device).to(torch.int64).reshape(-1)
+        n_ws = int(idx.numel())
+        if n_ws < 1 or n_ws > self.n_dev:
+            raise ValueError(f"gather_columns: 1 .. {self.n_dev} columns expected, got {n_ws}")
+        if int(idx[0]) < 0 or int(idx[-1]) >= self.n_dev or (n_ws > 1 and not bool((idx[1:] > idx[:-1]).all())):
+            raise ValueError(f"gather_columns: idx must be strictly increasing within 0 .. {self.n_dev - 1}")
+        n_ws_pad = (n_ws + 7) // 8 * 8 if n_ws_pad is None else int(n_ws_pad)
+        if out is None:
+            out = torch.empty(self.m, n_ws_pad, dtype=self.A.dtype, device=self.device)
+        idx32 = idx.to(torch.int32)
+        lda_ws = int(out.stride(0)) if self.m > 1 else n_ws_pad
+        with self.ctx():
+            _lib.check(self.lib.fos_gather_columns(ptr(idx32), n_ws, ptr(out), lda_ws, n_ws_pad, self.h), "fos_gather_columns")
+        return out
+
+    def kkt_scan(self, G, alpha1, slack, in_ws):
+        """The optimality check of the coordinates outside a working set (fos_kkt_scan) on the nv x n_dev block G of
+        `gradient_block`: (excess - n_dev floats on the device -, the violators in increasing order as an int32 device tensor).
+        alpha1: nv host weights; in_ws: n_dev device bytes, non-zero inside the set.  Synchronises (the count is read)."""
+        nv = int(G.shape[0])
+        a1 = (C.c_double * nv)(*[float(a) for a in alpha1])
+        excess = torch.empty(self.n_dev, dtype=torch.float32, device=self.device)
+        viol = torch.empty(self.n_dev, dtype=torch.int32, device=self.device)
+        count = torch.zeros(1, dtype=torch.int32, device=self.device)
+        with self.ctx():
+            _lib.check(self.lib.fos_kkt_scan(ptr(G), nv, a1, float(slack), ptr(in_ws), self.h, ptr(excess), ptr(viol), ptr(count)),
+                       "fos_kkt_scan")
+        return excess, viol[: int(count.item())]
+
     def power_iter(self, v0, n_iter=100, tol=1e-6):
         """The reference's power iteration (ref:45-60) from v0 (n values, need not be normalised): ``(L, it, v)``.  On every
         plan ``it`` is the step at which ``|L_k - L_{k-1}| < tol`` fired (``n_iter`` when it never did), ``L`` the norm of that

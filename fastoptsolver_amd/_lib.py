@@ -166,6 +166,14 @@ FEATURE_GROUP_SIGNATURES = {
 }
 
 
+# include/fos_working_set.h: the gradient of the data term, the column gather and the KKT scan of a working-set solve
+WORKING_SET_SIGNATURES = {
+    "fos_gradient_batch": (_i32, [_vp, _i32, _vp, _vp, _vp]),
+    "fos_gather_columns": (_i32, [_vp, C.c_int32, _vp, _i64, C.c_int32, _vp]),
+    "fos_kkt_scan": (_i32, [_vp, _i32, C.POINTER(C.c_double), C.c_double, _vp, _vp, _vp, _vp, _vp]),
+}
+
+
 def load():
     """Return the loaded CDLL (cached).  Raises FosError if the library is absent."""
     global _lib
@@ -176,7 +184,7 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension is the only compute path of fastoptsolver_amd.\n"
             "Build it with:  python -m fastoptsolver_amd.build   (needs hipcc; cross-compiles for gfx950)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **FEATURE_GROUP_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **FEATURE_GROUP_SIGNATURES, **WORKING_SET_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

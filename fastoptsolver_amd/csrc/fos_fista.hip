@@ -3,6 +3,7 @@
 #include "fos_internal.hpp"
 #include "fused_step.hpp"
 #include "chip_resident.hpp"
+#include "working_set.hpp"
 #include <cassert>
 
 using namespace fosapi;
@@ -1545,6 +1546,105 @@ int fos_fista_run_batch(const void* A, int a_dtype, const float* b, const fos_ba
     if (n_large) FOS_RSB_LAUNCH(fos::bf16_t, false, n_large, desc + n_small);
   }
 #undef FOS_RSB_LAUNCH
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
+}  // extern "C"
+
+// ---- Working-set solve (include/fos_working_set.h, working_set.hpp) ---------------------------------------------------------
+extern "C" {
+
+// The gradient of the data term at the nv columns of X: per row panel product 1 in its storing form (b, the problem's loss
+// epilogue, the bound weights) and product 2, then the slab sum of fos_gram_apply.  Product 1 leaves the loss partials of the
+// panel in cand.q_part; with several panels they are copied behind each other (ws.grad_part) and folded once.
+int fos_gradient_batch(const float* X, int nv, fos_problem* p, float* G, double* loss16) {
+  if (!X || !p || !G || nv < 1 || nv > fos::BT_NV)
+    return fail(FOS_ERR_ARG, "fos_gradient_batch: bad argument (null pointer or nv outside 1..16)");
+  if (p->loss == FOS_LOSS_MULTINOMIAL)
+    return fail(FOS_ERR_UNSUPPORTED, "fos_gradient_batch: a multinomial problem is not served (squared and logistic loss)");
+  if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_gradient_batch: the gradient of the data term needs b");
+  if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_gradient_batch: sharded problems are not served");
+  if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_gradient_batch: the shape has no matrix-core pair");
+  int rc = ensure_batch_workspace(p);
+  if (rc) return rc;
+  if ((rc = plan_multi_mfma(p))) return rc;
+  int g_splits = 0;
+  if ((rc = two_product_splits(p, &g_splits))) return rc;
+  const int64_t panels = (p->m + p->multi.panel_rows - 1) / p->multi.panel_rows;
+  const size_t part_rows = (size_t)(3 * p->ncu + 8);               // the rows of cand.q_part
+  if (loss16 && panels > 1 && (rc = p->ws.grad_part.reserve((size_t)panels * part_rows * fos::BT_NV))) return rc;
+  const int64_t esz = p->dtype == FOS_BF16 ? 2 : 4;
+  if ((rc = pack_candidates(p, X, nv))) return rc;
+  int nparts = 0;
+  for (int64_t row0 = 0, panel = 0; row0 < p->m; row0 += p->multi.panel_rows, ++panel) {
+    const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
+    const char* Ap = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz;
+    int nwg1 = 0;
+    BatchLaunch L{};                 // R = w (A_panel X - b) or w (sigma(A_panel X) - b); labels and weights are offset with the panel
+    L.A = Ap; L.b = p->b + row0; L.use_b = 1; L.rows = rows; L.rout = p->multi.rbuf16;
+    L.row_weight = p->row_weight ? p->row_weight + row0 : nullptr;
+    if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
+    if (loss16 && panels > 1) {
+      if ((size_t)nwg1 > part_rows) return fail(FOS_ERR_STATE, "fos_gradient_batch: product 1 wrote more partials than cand.q_part holds");
+      HIP_TRY(hipMemcpyAsync(p->ws.grad_part + (size_t)nparts * fos::BT_NV, p->cand.q_part, (size_t)nwg1 * fos::BT_NV * sizeof(double),
+                             hipMemcpyDeviceToDevice, p->stream));
+    }
+    nparts += nwg1;
+    if ((rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
+  }
+  hipLaunchKernelGGL(gram_slab_sum_kernel, dim3(grid_1d((int64_t)nv * p->n, 256, 1024)), dim3(256), 0, p->stream, p->multi.slabs16,
+                     g_splits, p->n, nv, G);
+  LAUNCH_CHECK();
+  if (loss16) {
+    hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream,
+                       panels > 1 ? p->ws.grad_part.get() : p->cand.q_part.get(), nparts, fos::BT_NV, loss16);
+    LAUNCH_CHECK();
+  }
+  return FOS_OK;
+}
+
+int fos_gather_columns(const int32_t* idx, int32_t n_ws, void* A_ws, int64_t lda_ws, int32_t n_ws_pad, const fos_problem* p) {
+  if (!idx || !A_ws || !p) return fail(FOS_ERR_ARG, "fos_gather_columns: null pointer");
+  if (n_ws < 1 || n_ws > p->n) return fail(FOS_ERR_ARG, "fos_gather_columns: n_ws outside 1..n");
+  if (n_ws_pad < n_ws || n_ws_pad % 8 != 0) return fail(FOS_ERR_ARG, "fos_gather_columns: n_ws_pad is below n_ws or not a multiple of 8");
+  if (lda_ws < n_ws_pad || lda_ws % 8 != 0) return fail(FOS_ERR_ARG, "fos_gather_columns: lda_ws is below n_ws_pad or not a multiple of 8");
+  if (((uintptr_t)A_ws & 15) != 0) return fail(FOS_ERR_ARG, "fos_gather_columns: A_ws is not 16-byte aligned");
+  // whole rows per workgroup, a multiple of the rows in flight; up to four workgroups (32 KiB of LDS each) per CU
+  int64_t rows_per_wg = (p->m + 4 * (int64_t)p->ncu - 1) / (4 * (int64_t)p->ncu);
+  rows_per_wg = (rows_per_wg + fos::WS_ROWS - 1) / fos::WS_ROWS * fos::WS_ROWS;
+  const unsigned grid = (unsigned)((p->m + rows_per_wg - 1) / rows_per_wg);
+  if (p->dtype == FOS_BF16)
+    hipLaunchKernelGGL(fos::gather_columns_kernel<2>, dim3(grid), dim3(fos::WS_THREADS), 0, p->stream, p->A, p->lda, p->m, (int)p->n, idx,
+                       (int)n_ws, (int)n_ws_pad, A_ws, lda_ws, rows_per_wg);
+  else
+    hipLaunchKernelGGL(fos::gather_columns_kernel<4>, dim3(grid), dim3(fos::WS_THREADS), 0, p->stream, p->A, p->lda, p->m, (int)p->n, idx,
+                       (int)n_ws, (int)n_ws_pad, A_ws, lda_ws, rows_per_wg);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
+int fos_kkt_scan(const float* G, int nv, const double* alpha1, double slack, const uint8_t* in_ws, fos_problem* p, float* excess,
+                 int32_t* viol_idx, int32_t* viol_count) {
+  if (!G || !alpha1 || !in_ws || !p || !excess || !viol_idx || !viol_count || nv < 1 || nv > fos::BT_NV)
+    return fail(FOS_ERR_ARG, "fos_kkt_scan: bad argument (null pointer or nv outside 1..16)");
+  if (!(std::isfinite(slack) && slack >= 0.0)) return fail(FOS_ERR_ARG, "fos_kkt_scan: slack is not finite and >= 0");
+  fos::KktWeights w{};
+  for (int j = 0; j < nv; ++j) {
+    if (!(std::isfinite(alpha1[j]) && alpha1[j] >= 0.0))
+      return fail(FOS_ERR_ARG, "fos_kkt_scan: weight " + std::to_string(j) + " is not finite and >= 0");
+    w.a[j] = alpha1[j];
+  }
+  if (p->coord_lo || p->coord_hi)
+    return fail(FOS_ERR_UNSUPPORTED, "fos_kkt_scan: box bounds (fos_coord_bind) are bound; a coordinate at a bound has another "
+                                     "optimality condition");
+  if (has_fgroups(p))
+    return fail(FOS_ERR_UNSUPPORTED, "fos_kkt_scan: feature groups (fos_feature_groups_bind) are bound; the group norm has another "
+                                     "optimality condition");
+  if (p->loss == FOS_LOSS_MULTINOMIAL)
+    return fail(FOS_ERR_UNSUPPORTED, "fos_kkt_scan: a multinomial problem is not served (squared and logistic loss)");
+  hipLaunchKernelGGL(fos::kkt_scan_kernel, dim3(1), dim3(fos::KS_THREADS), 0, p->stream, G, p->n, nv, w, 1.0 + slack, in_ws,
+                     p->coord_factor, excess, viol_idx, viol_count);
   LAUNCH_CHECK();
   return FOS_OK;
 }

@@ -18,6 +18,7 @@
 #pragma GCC visibility push(default)
 #include "../../include/fos.h"
 #include "../../include/fos_feature_groups.h"
+#include "../../include/fos_working_set.h"
 #pragma GCC visibility pop
 #include "batch_trial.hpp"
 #include "cluster_pass.hpp"
@@ -284,6 +285,7 @@ struct Scratch {
   DevBuf<float> rcols16;             // column-sharded candidate pass: m x 16 partial residuals (summed over the ranks)
   DevBuf<float> b16;                 // several right-hand sides: m x 16 zero-padded block of the caller's B (stage_b16)
   DevBuf<double> link_part;          // multinomial fos_residual_batch / _folds: the link kernel's partials of all panels (panels x ncu x 16)
+  DevBuf<double> grad_part;          // fos_gradient_batch with loss16 on several row panels: product 1's partials of all panels (panels x (3 ncu + 8) x 16)
   DevBuf<double> mfold;              // column-sharded lockstep: 16 x 4 folded step partials (summed over the ranks)
   DevBuf<double> cr_part;            // chip-resident loop (chip_resident.hpp): [2][G][17] partials + [8] step sums + [1] rr
   DevBuf<unsigned> cr_bar;
