@@ -135,7 +135,9 @@ def test_refused_matrices_keep_the_raw_plan(fos):
     sparse01 = (rng.random((m, n)) < 0.05).astype(np.float32)           # above the exception cap
     with_inf = rng.standard_normal((m, n)).astype(np.float32)
     with_inf[7, 100] = np.inf
-    for A in (sparse01, with_inf):
+    with_nan, with_ninf = with_inf.copy(), with_inf.copy()             # the other two refusals of tests/test_packed_format.py
+    with_nan[7, 100], with_ninf[7, 100] = np.nan, -np.inf
+    for A in (sparse01, with_inf, with_nan, with_ninf):
         prob = fos.prepare(A, b)
         prob.replan(no_resident=True, pack=True)
         g = prob.gemv_pair(_dev(y)).cpu().numpy()
