@@ -15,6 +15,11 @@ from .prox_operators import prox_elastic_net, prox_l1                 # noqa: F4
 # the working-set solve: importable from the package; __all__ stays the list the guard tables of the handle kinds file name by name
 from .working_set import WorkingSetInfo, alpha_max, kkt_excess, working_set_path   # noqa: F401
 
+# the Huber and squared-hinge losses: importable from the package likewise
+from ._core import prepare_hinge, prepare_huber                                                      # noqa: F401
+from .robust import (HingeCVResult, HuberCVResult, hinge_cv, hinge_objective, hinge_path,            # noqa: F401
+                     huber_cv, huber_objective, huber_path)
+
 __all__ = ["fista", "fista_delta", "fista_path", "fista_cv", "CVResult", "ista", "estimate_lipschitz", "reset_metrics", "get_metrics", "LBFGSSolver",
            "compute_objective", "prox_l1", "prox_elastic_net", "LeastSquares", "L1Prox", "ElasticNetProx",
            "prepare", "prepare_weighted", "prepare_penalized", "Problem", "FosError", "logistic_path", "logistic_cv", "logistic_objective", "LogisticCVResult",

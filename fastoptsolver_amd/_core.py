@@ -49,6 +49,9 @@ def stores_bf16(A, dtype=None):
 
 UPLOAD_CHUNK_BYTES = 256 << 20
 LOSSES = {"squared": _lib.LOSS_SQUARED, "logistic": _lib.LOSS_LOGISTIC, "multinomial": _lib.LOSS_MULTINOMIAL}
+# the losses behind the pointwise link kernel (fos_problem_set_link_loss): they take a parameter, so `prepare_huber` /
+# `prepare_hinge` build their handles, not `prepare(loss=...)`
+LINK_LOSSES = {"huber": _lib.LOSS_HUBER, "squared_hinge": _lib.LOSS_SQUARED_HINGE}
 MAX_CLASSES = 16                         # a class group of the multinomial lockstep is C of its 16 columns
 LOGIT_MAX_N = 16384                      # device columns the matrix-core pair serves (csrc/fos_plan.hip pair_dd_multi_supported)
 GROUPED_BOUNDS = "the group penalty does not compose with box bounds (lower / upper); penalty factors do"
@@ -113,6 +116,30 @@ def checked_labels(y, classes=None):
     if a.max() > classes - 1:
         raise ValueError(f"multinomial labels must lie in 0 .. {classes - 1}, got {int(a.max())}")
     return a, classes
+
+
+def checked_threshold(threshold):
+    """The Huber threshold as a float: finite and > 0 - ValueError otherwise, before any device work."""
+    if isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+        raise ValueError(f"threshold: a number expected, got {threshold!r}")
+    threshold = float(threshold)
+    if not (np.isfinite(threshold) and threshold > 0):
+        raise ValueError(f"threshold: finite and > 0 expected, got {threshold}")
+    return threshold
+
+
+def checked_signs(y):
+    """The labels of a squared-hinge problem as a float64 ndarray: one value per row, each exactly -1 or +1 - ValueError
+    otherwise.  Checked on the host, before any device work."""
+    if y is None:
+        raise ValueError("a squared-hinge problem needs its labels")
+    a = np.asarray(y.detach().cpu().numpy() if is_tensor(y) else y)
+    if a.ndim != 1 or a.size == 0 or a.dtype.kind not in "iuf":
+        raise ValueError(f"squared-hinge labels: one value -1 / +1 per row expected, got shape {a.shape} and dtype {a.dtype}")
+    a = a.astype(np.float64)
+    if not (np.abs(a) == 1.0).all():
+        raise ValueError("squared-hinge labels must be exactly -1 or +1")
+    return a
 
 
 def checked_class_groups(ncols, classes):
@@ -256,6 +283,16 @@ class Problem:
         return prob
 
     @classmethod
+    def link(cls, A, b, loss, threshold=None, dtype=None, sample_weight=None):
+        """The handle of a Huber (`prepare_huber`; `threshold` is c) or squared-hinge (`prepare_hinge`; b holds the labels -1 /
+        +1) problem, with or without row weights: the constructor that takes the loss's parameter."""
+        if loss not in LINK_LOSSES:
+            raise ValueError(f"loss: one of {sorted(LINK_LOSSES)} expected, got {loss!r}")
+        prob = cls.__new__(cls)
+        prob._setup(A, b, dtype, None, loss, sample_weight, threshold=threshold)
+        return prob
+
+    @classmethod
     def grouped_features(cls, A, b, groups, group_weight=None, l1_ratio=0.0, dtype=None, loss="squared", sample_weight=None):
         """The handle of a problem with feature groups (`prepare_grouped`): the constructor that takes them."""
         prob = cls.__new__(cls)
@@ -263,12 +300,28 @@ class Problem:
         return prob
 
     def _setup(self, A, b, dtype, pad, loss, sample_weight, penalty_factor=None, lower=None, upper=None, classes=None,
-               feature_groups=None):
+               feature_groups=None, threshold=None):
         """__init__, and with penalty_factor / lower / upper (`prepare_penalized`; `set_penalty`, fos_coord_bind) the handle of a
         problem with per-coordinate penalty factors and box bounds: it runs on the matrix-core pair alone too and is padded by
         the rules of a logistic problem."""
-        if loss not in LOSSES:
+        if loss not in LOSSES and loss not in LINK_LOSSES:
             raise ValueError(f"loss: one of {sorted(LOSSES)} expected, got {loss!r}")
+        self.threshold = None
+        if loss in LINK_LOSSES:                                          # before any device work
+            if isinstance(b, Problem) or isinstance(A, Problem):
+                raise ValueError("a Huber or squared-hinge problem binds an array or tensor")
+            if b is None:
+                raise ValueError("a Huber or squared-hinge problem needs b")
+            if loss == "huber":
+                if threshold is None:
+                    raise ValueError("a Huber problem takes its threshold: prepare_huber(A, b, threshold)")
+                self.threshold = checked_threshold(threshold)
+            else:
+                if threshold is not None:
+                    raise ValueError("threshold belongs to the Huber loss")
+                b = checked_signs(b)
+        elif threshold is not None:
+            raise ValueError("threshold belongs to the Huber loss")
         coord = any(v is not None for v in (penalty_factor, lower, upper))
         pair_only = loss != "squared" or sample_weight is not None or coord or feature_groups is not None   # served by the matrix-core pair alone
         self.classes = None
@@ -354,6 +407,9 @@ class Problem:
         sib.A, sib.m, sib.n, sib.n_dev, sib.lda = self.A, self.m, self.n, self.n_dev, self.lda
         sib.device, sib.dtype, sib.loss, sib.sample_weight = self.device, self.dtype, self.loss, None
         sib.classes = self.classes
+        sib.threshold = self.threshold
+        if self.loss == "squared_hinge":            # the sibling's own labels, checked on the host
+            b = checked_signs(b)
         sib.grouped = self.grouped
         if self.loss == "multinomial":              # the sibling's own labels, checked against the same C on the host
             b = checked_labels(b, self.classes)[0]
@@ -391,6 +447,9 @@ class Problem:
             _lib.check(lib.fos_problem_set_gbuf(self.h, ptr(self.gbuf)), "fos_problem_set_gbuf")
             if self.loss == "multinomial":
                 _lib.check(lib.fos_problem_set_multinomial(int(self.classes), self.h), "fos_problem_set_multinomial")
+            elif self.loss in LINK_LOSSES:
+                _lib.check(lib.fos_problem_set_link_loss(LINK_LOSSES[self.loss], float(self.threshold or 0.0), self.h),
+                           "fos_problem_set_link_loss")
             elif self.loss != "squared":
                 _lib.check(lib.fos_problem_set_loss(self.h, LOSSES[self.loss]), "fos_problem_set_loss")
         self.lib = lib
@@ -773,6 +832,28 @@ def prepare_weighted(A, b, sample_weight, dtype=None, *, loss="squared"):
     return Problem(A, b, dtype, None, loss, sample_weight=sample_weight)
 
 
+def prepare_huber(A, b, threshold, dtype=None, *, sample_weight=None):
+    """The handle of a Huber regression: data term sum_i w_i rho_c(a_i.x - b_i) with c = ``threshold`` > 0, rho_c(r) = r^2 / 2
+    for |r| <= c and c |r| - c^2 / 2 otherwise, w the ``sample_weight`` (None: 1).  Pass it as ``A`` (``b`` None) to
+    ``huber_path`` / ``huber_cv`` / ``huber_objective`` / ``working_set_path``; `.threshold` is c.  ``Problem.set_penalty`` and
+    ``Problem.set_feature_groups`` compose.  Runs on the matrix-core lockstep alone and is padded by the rules of a logistic
+    problem; every squared-loss entry point refuses the handle."""
+    if isinstance(A, Problem):
+        raise ValueError("prepare_huber binds an array or tensor")
+    return Problem.link(A, b, "huber", threshold, dtype, sample_weight)
+
+
+def prepare_hinge(A, y, dtype=None, *, sample_weight=None):
+    """The handle of a squared-hinge classifier (the L2-loss linear SVM): data term sum_i w_i max(0, 1 - y_i a_i.x)^2 / 2 with
+    labels ``y`` exactly -1 or +1 (checked on the host; ValueError before any device work), w the ``sample_weight`` (None: 1).
+    Pass it as ``A`` (``y`` None) to ``hinge_path`` / ``hinge_cv`` / ``hinge_objective`` / ``working_set_path``.
+    ``Problem.set_penalty`` and ``Problem.set_feature_groups`` compose.  Runs on the matrix-core lockstep alone and is padded by
+    the rules of a logistic problem; every squared-loss entry point refuses the handle."""
+    if isinstance(A, Problem):
+        raise ValueError("prepare_hinge binds an array or tensor")
+    return Problem.link(A, y, "squared_hinge", None, dtype, sample_weight)
+
+
 def prepare_penalized(A, b, penalty_factor=None, lower=None, upper=None, dtype=None, *, loss="squared", sample_weight=None):
     """``prepare`` with per-coordinate penalty factors p_j >= 0 and box bounds lower_j <= 0 <= upper_j (glmnet's penalty.factor
     and lower.limits / upper.limits, sklearn's positive=True): the objective is
@@ -820,8 +901,17 @@ def prepare_grouped(A, b, groups, group_weight=None, l1_ratio=0.0, dtype=None, *
     return Problem.grouped_features(A, b, groups, group_weight, l1_ratio, dtype, loss, sample_weight)
 
 
+def refuse_link(A, who):
+    """A Huber or squared-hinge handle (`prepare_huber` / `prepare_hinge`) belongs to the functions of `robust` and to
+    `working_set_path`: no other front end may answer for it with another loss's quantity.  ValueError before any device work."""
+    if isinstance(A, Problem) and A.loss in LINK_LOSSES:
+        own = "huber_path / huber_cv / huber_objective" if A.loss == "huber" else "hinge_path / hinge_cv / hinge_objective"
+        raise ValueError(f"{who}: A was prepared for the {A.loss} loss: use {own} (or working_set_path)")
+
+
 def as_problem(A, b, dtype=None):
     if isinstance(A, Problem):
+        refuse_link(A, "a squared-loss solver")
         if b is not None and A.b is None:
             raise ValueError("Problem was prepared without b")
         return A

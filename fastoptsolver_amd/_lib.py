@@ -11,6 +11,7 @@ MODE_FISTA, MODE_DELTA, MODE_ISTA = 0, 1, 2
 PROX_L1, PROX_ENET = 0, 1
 LOSS_SQUARED, LOSS_LOGISTIC = 0, 1
 LOSS_MULTINOMIAL = 2          # set with fos_problem_set_multinomial (it takes the number of classes)
+LOSS_HUBER, LOSS_SQUARED_HINGE = 3, 4    # set with fos_problem_set_link_loss (it takes the loss's parameter)
 STOP_NONE, STOP_STEP, STOP_RATIO, STOP_GRAD, STOP_LS_STALL = 0, 1, 2, 3, 4
 ERR_UNSUPPORTED = -4            # FOS_ERR_UNSUPPORTED: this problem / plan has no such form (callers take the next one)
 PLAN_NO_RESIDENT, PLAN_NO_TALL, PLAN_NO_WIDE, PLAN_NO_COLBLOCK, PLAN_CLUSTER, PLAN_INTERLEAVE, PLAN_NO_INTERLEAVE, PLAN_NO_CLUSTER, PLAN_FUSED_MFMA, PLAN_CHIP_RESIDENT, PLAN_NO_CHIP_RESIDENT, PLAN_PACK, PLAN_NO_PACK = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096
@@ -174,6 +175,13 @@ WORKING_SET_SIGNATURES = {
 }
 
 
+# include/fos_link_loss.h: the Huber and the squared-hinge loss behind the pointwise link kernel
+LINK_LOSS_SIGNATURES = {
+    "fos_problem_set_link_loss": (_i32, [_i32, C.c_double, _vp]),
+    "fos_problem_get_link_loss": (_i32, [C.POINTER(_i32), C.POINTER(C.c_double), _vp]),
+}
+
+
 def load():
     """Return the loaded CDLL (cached).  Raises FosError if the library is absent."""
     global _lib
@@ -184,7 +192,7 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension is the only compute path of fastoptsolver_amd.\n"
             "Build it with:  python -m fastoptsolver_amd.build   (needs hipcc; cross-compiles for gfx950)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **FEATURE_GROUP_SIGNATURES, **WORKING_SET_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **FEATURE_GROUP_SIGNATURES, **WORKING_SET_SIGNATURES, **LINK_LOSS_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -714,6 +714,9 @@ static fos::MultiUpdate multi_update(fos_fista* const* fs, int nv, bool controll
 // Product 1 is the plain storing form, R = A_panel Y (the logits; neither b nor a mask nor the weights enter it), the link
 // kernel (softmax_link.hpp) turns the panel into softmax(A_panel Y) - onehot(b) in place with the weights and the fold mask
 // applied, and everything after it is the same.  Plain runs only (lockstep_route).
+// A Huber or squared-hinge problem (fos_problem_set_link_loss): the same sequence with the pointwise link kernel
+// (pointwise_link.hpp), R = clip(A_panel Y - b, -c, c) or -b max(0, 1 - b A_panel Y).  The columns are independent fits: any nv,
+// plain or controlled.
 
 // Handles under the group penalty (fos_fista_params.group = G >= 2; checked by group_refusal before they get here): always the
 // two-product form, plain; the G columns of a fit are updated together by the one launch of launch_group_update, in place of
@@ -841,12 +844,13 @@ static int run_multi_mfma(const LockstepCall& c, const LockstepRoute& r) {
   const bool logit = p->loss == FOS_LOSS_LOGISTIC;
   const bool weighted = p->row_weight != nullptr;
   const bool softmax = p->loss == FOS_LOSS_MULTINOMIAL;      // the link kernel sits between the two products of every panel
+  const bool link = link_loss(p);                            // the pointwise link kernel, in the same place
   const bool group_penalty = grouped(fs[0]->prm);            // the fits' columns are updated together (launch_group_update)
   const bool fgroup = has_fgroups(p);                        // fos_feature_groups_bind: the update is launch_fgroup_update
   const bool two_products = b16 || fold_of_row || logit || weighted || has_coord(p) || group_penalty || fgroup;
-  bool use_cluster = p->multi.cp_cs && !two_products && !softmax;
+  bool use_cluster = p->multi.cp_cs && !two_products && !softmax && !link;
   int g_splits = p->multi.gram_splits;
-  if ((two_products || softmax) && (rc = two_product_splits(p, &g_splits))) return rc;
+  if ((two_products || softmax || link) && (rc = two_product_splits(p, &g_splits))) return rc;
   // candidate block: zero everywhere (padding columns, unused slots), then y_k of every state machine
   const size_t per_entry = is_bf16 ? 3 * sizeof(unsigned short) : sizeof(float);
   HIP_TRY(hipMemsetAsync(p->cand.xp, 0, (size_t)p->cand.n_pad * fos::BT_NV * per_entry, p->stream));
@@ -899,9 +903,13 @@ static int run_multi_mfma(const LockstepCall& c, const LockstepRoute& r) {
       L.bblock = b16 != nullptr; L.fold_of_row = fold_of_row ? fold_of_row + row0 : nullptr; L.held = held;
       L.row_weight = weighted ? p->row_weight + row0 : nullptr;
       if (softmax) { L.b = nullptr; L.use_b = 0; L.fold_of_row = nullptr; L.held = nullptr; L.row_weight = nullptr; }     // the logits alone
+      if (link) { L.b = nullptr; L.use_b = 0; L.fold_of_row = nullptr; L.held = nullptr; L.row_weight = nullptr; }        // A_panel Y alone
       if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
       if (softmax && (rc = launch_softmax_link(p, row0, rows, nv, fold_of_row ? fos::FOLD_TRAIN : fos::FOLD_OFF, fold_of_row, held,
                                                p->cand.q_part, &nwg1)))
+        return rc;
+      if (link && (rc = launch_pointwise_link(p, row0, rows, nv, fold_of_row ? fos::FOLD_TRAIN : fos::FOLD_OFF, fold_of_row, held,
+                                              p->cand.q_part, &nwg1)))
         return rc;
       if (cols && (rc = reduce_across(p, p->multi.rbuf16, (size_t)rows * fos::BT_NV, false))) return rc;
       if ((rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
@@ -991,6 +999,7 @@ static int group_refusal(fos_fista* const* fs, int nv, const int32_t* held, cons
     why = "box bounds (fos_coord_bind) do not compose with the group norm; penalty factors alone do";
   if (!why && !unsharded_pair(p)) why = "an unsharded problem with the matrix-core pair is needed";
   if (!why && has_fgroups(p)) why = "feature groups (fos_feature_groups_bind) are bound; the two group norms do not compose";
+  if (!why && link_loss(p)) why = "not served with the Huber or the squared-hinge loss (fos_problem_set_link_loss)";
   if (why) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the group penalty (fos_fista_params.group >= 2): " + why);
   return FOS_OK;
 }
@@ -1004,7 +1013,7 @@ static bool group_takes_block(fos_fista* const* fs, int nv) {
 // Fills *r from the call, or refuses it; launches nothing and touches neither a handle nor device state.  In order: the
 // multinomial loss, the group penalty, the logistic loss / row weights / coordinate data / feature groups (all on the
 // matrix-core pair, for any number of state machines - there is no single-vector or VALU pass for them; a block B met
-// need_squared), the fold masks on the squared loss, and the squared loss on its own b or on B.
+// need_squared), the Huber / squared-hinge loss (the pair likewise), the fold masks on the squared loss, and the squared loss on its own b or on B.
 static int lockstep_route(const LockstepCall& c, LockstepRoute* r) {
   fos_fista* const* fs = c.fs;
   const int nv = c.nv;
@@ -1056,6 +1065,14 @@ static int lockstep_route(const LockstepCall& c, LockstepRoute* r) {
       return fail(FOS_ERR_UNSUPPORTED, fn + ": the group penalty (fos_fista_params.group >= 2): a right-hand-side block "
                                             "needs the unweighted squared loss, everything else the problem's own b");
     return FOS_OK;
+  }
+  if (link_loss(p)) {
+    // independent columns behind a pointwise link (group_refusal has refused the group penalty): any nv, plain or controlled,
+    // refused as on a logistic problem otherwise
+    if (!p->b || !unsharded_pair(p))
+      return fail(FOS_ERR_UNSUPPORTED, fn + ": the Huber and squared-hinge losses need b, an unsharded problem and the "
+                                            "matrix-core pair");
+    return control_refusal();
   }
   if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight || has_coord(p) || has_fgroups(p)) {
     if (!p->b || !unsharded_pair(p))
@@ -1558,6 +1575,7 @@ extern "C" {
 // The gradient of the data term at the nv columns of X: per row panel product 1 in its storing form (b, the problem's loss
 // epilogue, the bound weights) and product 2, then the slab sum of fos_gram_apply.  Product 1 leaves the loss partials of the
 // panel in cand.q_part; with several panels they are copied behind each other (ws.grad_part) and folded once.
+// On a Huber or squared-hinge problem product 1 runs plain and the pointwise link kernel leaves R and the partials instead.
 int fos_gradient_batch(const float* X, int nv, fos_problem* p, float* G, double* loss16) {
   if (!X || !p || !G || nv < 1 || nv > fos::BT_NV)
     return fail(FOS_ERR_ARG, "fos_gradient_batch: bad argument (null pointer or nv outside 1..16)");
@@ -1571,6 +1589,7 @@ int fos_gradient_batch(const float* X, int nv, fos_problem* p, float* G, double*
   if ((rc = plan_multi_mfma(p))) return rc;
   int g_splits = 0;
   if ((rc = two_product_splits(p, &g_splits))) return rc;
+  const bool link = link_loss(p);
   const int64_t panels = (p->m + p->multi.panel_rows - 1) / p->multi.panel_rows;
   const size_t part_rows = (size_t)(3 * p->ncu + 8);               // the rows of cand.q_part
   if (loss16 && panels > 1 && (rc = p->ws.grad_part.reserve((size_t)panels * part_rows * fos::BT_NV))) return rc;
@@ -1584,7 +1603,9 @@ int fos_gradient_batch(const float* X, int nv, fos_problem* p, float* G, double*
     BatchLaunch L{};                 // R = w (A_panel X - b) or w (sigma(A_panel X) - b); labels and weights are offset with the panel
     L.A = Ap; L.b = p->b + row0; L.use_b = 1; L.rows = rows; L.rout = p->multi.rbuf16;
     L.row_weight = p->row_weight ? p->row_weight + row0 : nullptr;
+    if (link) { L.b = nullptr; L.use_b = 0; L.row_weight = nullptr; }      // Z = A_panel X; the link kernel forms R and the loss partials
     if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
+    if (link && (rc = launch_pointwise_link(p, row0, rows, nv, fos::FOLD_OFF, nullptr, nullptr, p->cand.q_part, &nwg1))) return rc;
     if (loss16 && panels > 1) {
       if ((size_t)nwg1 > part_rows) return fail(FOS_ERR_STATE, "fos_gradient_batch: product 1 wrote more partials than cand.q_part holds");
       HIP_TRY(hipMemcpyAsync(p->ws.grad_part + (size_t)nparts * fos::BT_NV, p->cand.q_part, (size_t)nwg1 * fos::BT_NV * sizeof(double),

@@ -18,6 +18,7 @@
 #pragma GCC visibility push(default)
 #include "../../include/fos.h"
 #include "../../include/fos_feature_groups.h"
+#include "../../include/fos_link_loss.h"
 #include "../../include/fos_working_set.h"
 #pragma GCC visibility pop
 #include "batch_trial.hpp"
@@ -284,7 +285,7 @@ struct Scratch {
   DevBuf<float> vring;               // fos_power_iter, streaming plans: the iterates of the last 16 steps (16 x n rounded up to 4)
   DevBuf<float> rcols16;             // column-sharded candidate pass: m x 16 partial residuals (summed over the ranks)
   DevBuf<float> b16;                 // several right-hand sides: m x 16 zero-padded block of the caller's B (stage_b16)
-  DevBuf<double> link_part;          // multinomial fos_residual_batch / _folds: the link kernel's partials of all panels (panels x ncu x 16)
+  DevBuf<double> link_part;          // fos_residual_batch / _folds behind a link kernel: its partials of all panels (panels x ncu x 16; pointwise link: x 2 ncu)
   DevBuf<double> grad_part;          // fos_gradient_batch with loss16 on several row panels: product 1's partials of all panels (panels x (3 ncu + 8) x 16)
   DevBuf<double> mfold;              // column-sharded lockstep: 16 x 4 folded step partials (summed over the ranks)
   DevBuf<double> cr_part;            // chip-resident loop (chip_resident.hpp): [2][G][17] partials + [8] step sums + [1] rr
@@ -305,6 +306,7 @@ struct fos_problem {
   int64_t m = 0, n = 0, lda = 0;
   int dtype = FOS_F32;
   int loss = FOS_LOSS_SQUARED;       // fos_problem_set_loss / _set_multinomial: what b means to the matrix-core lockstep (no buffer depends on it)
+  double link_param = 0.0;           // fos_problem_set_link_loss: the threshold c of a Huber problem; 0 otherwise
   int classes = 0;                   // fos_problem_set_multinomial: C of a multinomial problem (b holds class indices 0 .. C-1); 0 otherwise
   const float* row_weight = nullptr; // fos_row_weights_bind: the caller's m per-row weights of the data term (borrowed; nullptr: none)
   // fos_coord_bind: per-coordinate penalty factors and box bounds of the lockstep's update (borrowed; nullptr: 1, -inf, +inf)
@@ -454,6 +456,15 @@ int launch_batch_product(fos_problem* p, const BatchLaunch& L, int* nwg_out);
 // held non-null unless FOLD_OFF).  *nwg_out = the rows of q_part written (at most p->ncu).
 int launch_softmax_link(fos_problem* p, int64_t row0, int64_t rows, int nv, int fold, const uint8_t* fold_of_row,
                         const fos::FoldHeld* held, double* q_part, int* nwg_out);
+// A problem with the Huber or the squared-hinge loss (fos_problem_set_link_loss): the pointwise link kernel sits between the
+// two products.
+inline bool link_loss(const fos_problem* p) { return p->loss == FOS_LOSS_HUBER || p->loss == FOS_LOSS_SQUARED_HINGE; }
+// need_squared's refusal of such a problem, with a text of its own (FOS_OK on any other problem).
+int link_refusal(const fos_problem* p, const char* fn);
+// The link kernel of such a problem (pointwise_link.hpp), with the panel contract of launch_softmax_link: any nv in 1..16,
+// *nwg_out = the rows of q_part written (at most 2 * p->ncu).
+int launch_pointwise_link(fos_problem* p, int64_t row0, int64_t rows, int nv, int fold, const uint8_t* fold_of_row,
+                          const fos::FoldHeld* held, double* q_part, int* nwg_out);
 // Whether the nv columns split into whole class groups of a multinomial problem and (held non-null: HOST ids) every group
 // holds out one fold.
 bool softmax_groups_ok(const fos_problem* p, int nv, const int32_t* held);

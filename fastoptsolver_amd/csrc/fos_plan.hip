@@ -2,6 +2,7 @@
 // (include/fos.h).  Host code only decides launch geometry and enqueues kernels; there is no CPU compute fallback.
 #include "fos_internal.hpp"
 #include "softmax_link.hpp"
+#include "pointwise_link.hpp"
 #include "gemv_packed.hpp"
 
 namespace fosapi {
@@ -894,11 +895,21 @@ int fgroup_refusal(const fos_problem* p, const char* fn) {
   return FOS_OK;
 }
 
+// ... and of a problem with the Huber or the squared-hinge loss: only the link kernel between the two products forms its residual.
+int link_refusal(const fos_problem* p, const char* fn) {
+  if (p && link_loss(p))
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": not served on a problem with the Huber or the squared-hinge loss "
+                                     "(fos_problem_set_link_loss); like the logistic loss these run through fos_fista_run_multi / "
+                                     "_run_multi_folds, fos_residual_batch / _folds and fos_gradient_batch");
+  return FOS_OK;
+}
+
 int need_squared(const fos_problem* p, const char* fn) {
   if (p && p->row_weight != nullptr)
     return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": not served on a problem with row weights (fos_row_weights_bind); the "
                                      "weighted squared and logistic losses run through fos_fista_run_multi / _run_multi_folds and fos_residual_batch / "
                                      "_folds");
+  if (int rc = link_refusal(p, fn)) return rc;
   if (p && p->loss != FOS_LOSS_SQUARED)
     return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + (p->loss == FOS_LOSS_MULTINOMIAL
                                                              ? ": not served on a multinomial problem (fos_problem_set_multinomial); the multinomial "
@@ -942,6 +953,33 @@ int launch_softmax_link(fos_problem* p, int64_t row0, int64_t rows, int nv, int 
   if (fold == fos::FOLD_TRAIN) { if (w) FOS_LINK(FOLD_TRAIN, true); else FOS_LINK(FOLD_TRAIN, false); }
   else if (fold == fos::FOLD_HELD) { if (w) FOS_LINK(FOLD_HELD, true); else FOS_LINK(FOLD_HELD, false); }
   else { if (w) FOS_LINK(FOLD_OFF, true); else FOS_LINK(FOLD_OFF, false); }
+#undef FOS_LINK
+  LAUNCH_CHECK();
+  *nwg_out = nwg;
+  return FOS_OK;
+}
+
+// The link kernel (pointwise_link.hpp) behind product 1 on one row panel of a Huber or squared-hinge problem.  One lane per
+// 16-byte quad of a row, grid-stride: at most 2 * ncu workgroups, within the 3 * ncu + 8 rows of cand.q_part.
+int launch_pointwise_link(fos_problem* p, int64_t row0, int64_t rows, int nv, int fold, const uint8_t* fold_of_row,
+                          const fos::FoldHeld* held, double* q_part, int* nwg_out) {
+  if (!link_loss(p) || rows < 1 || rows > p->multi.panel_rows || nv < 1 || nv > fos::BT_NV ||
+      ((fold != fos::FOLD_OFF) && (!fold_of_row || !held)))
+    return fail(FOS_ERR_STATE, "launch_pointwise_link: not a panel of a Huber or squared-hinge problem");
+  const int nwg = (int)std::min<int64_t>((4 * rows + fos::PL_THREADS - 1) / fos::PL_THREADS, 2 * (int64_t)p->ncu);
+  const fos::FoldHeld hb = held ? *held : fos::FoldHeld{};
+  const float* w = p->row_weight ? p->row_weight + row0 : nullptr;
+  const uint8_t* ids = fold != fos::FOLD_OFF ? fold_of_row + row0 : nullptr;
+  const float c = (float)p->link_param;
+#define FOS_LINK(K, F, W)                                                                                                           \
+  hipLaunchKernelGGL((fos::pointwise_link_kernel<fos::K, fos::F, W>), dim3(nwg), dim3(fos::PL_THREADS), 0, p->stream,              \
+                     p->multi.rbuf16.get(), rows, p->b + row0, c, nv, w, ids, hb, q_part, (const int*)nullptr)
+#define FOS_LINK_FORM(K)                                                                                              \
+  if (fold == fos::FOLD_TRAIN) { if (w) FOS_LINK(K, FOLD_TRAIN, true); else FOS_LINK(K, FOLD_TRAIN, false); }         \
+  else if (fold == fos::FOLD_HELD) { if (w) FOS_LINK(K, FOLD_HELD, true); else FOS_LINK(K, FOLD_HELD, false); }       \
+  else { if (w) FOS_LINK(K, FOLD_OFF, true); else FOS_LINK(K, FOLD_OFF, false); }
+  if (p->loss == FOS_LOSS_HUBER) { FOS_LINK_FORM(LINK_HUBER) } else { FOS_LINK_FORM(LINK_SQUARED_HINGE) }
+#undef FOS_LINK_FORM
 #undef FOS_LINK
   LAUNCH_CHECK();
   *nwg_out = nwg;
@@ -1457,6 +1495,32 @@ int fos_problem_set_loss(fos_problem* p, int loss) {
                                        "layout, 65..16384 columns)");
   }
   p->loss = loss;                    // no buffer depends on the loss: nothing to invalidate
+  p->link_param = 0.0;
+  return FOS_OK;
+}
+
+int fos_problem_set_link_loss(int loss, double param, fos_problem* p) {
+  if (!p) return fail(FOS_ERR_ARG, "fos_problem_set_link_loss: null problem");
+  if (loss != FOS_LOSS_HUBER && loss != FOS_LOSS_SQUARED_HINGE)
+    return fail(FOS_ERR_ARG, "fos_problem_set_link_loss: the loss is FOS_LOSS_HUBER or FOS_LOSS_SQUARED_HINGE");
+  if (loss == FOS_LOSS_HUBER && !(std::isfinite(param) && param > 0.0))
+    return fail(FOS_ERR_ARG, "fos_problem_set_link_loss: the Huber threshold is not finite and > 0");
+  if (loss == FOS_LOSS_SQUARED_HINGE && param != 0.0)
+    return fail(FOS_ERR_ARG, "fos_problem_set_link_loss: the squared hinge takes no parameter (param = 0)");
+  if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_link_loss: the Huber and squared-hinge losses need b");
+  if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_link_loss: sharded problems are not served");
+  if (!pair_dd_multi_supported(p))
+    return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_link_loss: the Huber and squared-hinge losses run on the matrix-core pair "
+                                     "(aligned streaming layout, 65..16384 columns)");
+  p->loss = loss;                    // no buffer depends on the loss or on its parameter: nothing to invalidate
+  p->link_param = loss == FOS_LOSS_HUBER ? param : 0.0;
+  return FOS_OK;
+}
+
+int fos_problem_get_link_loss(int* loss, double* param, const fos_problem* p) {
+  if (!p || !loss || !param) return fail(FOS_ERR_ARG, "fos_problem_get_link_loss: null");
+  *loss = link_loss(p) ? p->loss : 0;
+  *param = link_loss(p) ? p->link_param : 0.0;
   return FOS_OK;
 }
 
@@ -1472,6 +1536,7 @@ int fos_problem_set_multinomial(int classes, fos_problem* p) {
     return fail(FOS_ERR_UNSUPPORTED, "fos_problem_set_multinomial: feature groups (fos_feature_groups_bind) are bound; the group "
                                      "lasso over features serves the squared and the logistic loss");
   p->loss = FOS_LOSS_MULTINOMIAL;    // no buffer depends on the loss or on the number of classes: nothing to invalidate
+  p->link_param = 0.0;
   p->classes = classes;
   return FOS_OK;
 }
@@ -2002,6 +2067,36 @@ static int residual_batch_softmax(fos_problem* p, const char* fn, const float* X
   return FOS_OK;
 }
 
+// ... and on a Huber or squared-hinge problem: the same with the pointwise link kernel (pointwise_link.hpp), any nv in 1..16:
+// out16[j] = the data term of column j (its 1/2 included), weighted per row on a problem with row weights, over all rows or over
+// the rows of the fold that column holds out.
+static int residual_batch_link(fos_problem* p, const char* fn, const float* X, int nv, double* out16, const uint8_t* fold_of_row,
+                               const fos::FoldHeld* held) {
+  if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the shape has no matrix-core pair");
+  int rc = ensure_batch_workspace(p);
+  if (rc) return rc;
+  if ((rc = plan_multi_mfma(p))) return rc;
+  const int64_t panels = (p->m + p->multi.panel_rows - 1) / p->multi.panel_rows;
+  if ((rc = p->ws.link_part.reserve((size_t)panels * 2 * p->ncu * fos::BT_NV))) return rc;
+  if ((rc = pack_candidates(p, X, nv))) return rc;
+  const int64_t esz = p->dtype == FOS_BF16 ? 2 : 4;
+  int nparts = 0;
+  for (int64_t row0 = 0; row0 < p->m; row0 += p->multi.panel_rows) {
+    const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
+    int nwg1 = 0, nwg = 0;
+    BatchLaunch L{};                 // Z = A_panel X: no b, no mask, no weights
+    L.A = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz; L.rows = rows; L.rout = p->multi.rbuf16;
+    if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
+    if ((rc = launch_pointwise_link(p, row0, rows, nv, held ? fos::FOLD_HELD : fos::FOLD_OFF, fold_of_row, held,
+                                    p->ws.link_part + (size_t)nparts * fos::BT_NV, &nwg)))
+      return rc;
+    nparts += nwg;
+  }
+  hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->ws.link_part, nparts, fos::BT_NV, out16);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
 int fos_residual_batch(fos_problem* p, const float* X, int nv, int use_b, double* out16) {
   if (!p || !X || !out16 || nv < 1 || nv > fos::BT_NV) return fail(FOS_ERR_ARG, "fos_residual_batch: bad argument");
   if (!use_b)                        // ||A X_j||^2 is a squared-loss quantity
@@ -2010,6 +2105,7 @@ int fos_residual_batch(fos_problem* p, const float* X, int nv, int use_b, double
     if (!softmax_groups_ok(p, nv, nullptr)) return fail(FOS_ERR_ARG, "fos_residual_batch: on a multinomial problem nv is a multiple of the classes");
     return residual_batch_softmax(p, "fos_residual_batch", X, nv, out16, nullptr, nullptr);
   }
+  if (link_loss(p)) return residual_batch_link(p, "fos_residual_batch", X, nv, out16, nullptr, nullptr);
   if (p->loss == FOS_LOSS_LOGISTIC || p->row_weight) return residual_batch_pair(p, "fos_residual_batch", X, nv, out16, nullptr, nullptr);
   if (!batch_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_residual_batch: needs the fused path");
   int rc = ensure_batch_workspace(p);
@@ -2046,6 +2142,7 @@ int fos_residual_batch_folds(fos_problem* p, const float* X, int nv, const uint8
                                "a class group hold out one fold");
     return residual_batch_softmax(p, "fos_residual_batch_folds", X, nv, out16, fold_of_row, &hb);
   }
+  if (link_loss(p)) return residual_batch_link(p, "fos_residual_batch_folds", X, nv, out16, fold_of_row, &hb);
   return residual_batch_pair(p, "fos_residual_batch_folds", X, nv, out16, fold_of_row, &hb);
 }
 

@@ -140,6 +140,7 @@ def _refuse_multinomial(A, who):
     if isinstance(A, _core.Problem) and A.loss == "multinomial":
         raise ValueError(f"{who}: A was prepared for the multinomial loss: use multinomial_path / multinomial_cv / "
                          "multinomial_objective")
+    _core.refuse_link(A, who)        # a Huber or squared-hinge handle likewise
 
 
 def _weighted_lipschitz(prob, v0, n_iter=100, tol=1e-6):

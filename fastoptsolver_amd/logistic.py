@@ -31,6 +31,7 @@ LogisticCVResult = collections.namedtuple("LogisticCVResult", "alphas logloss me
 def _problem(A, y, dtype):
     """The logistic handle on (A, y): a prepared one as it is, anything else bound (and padded) here."""
     if isinstance(A, _core.Problem):
+        _core.refuse_link(A, "logistic_path / logistic_cv / logistic_objective")
         if A.loss != "logistic":
             raise ValueError(f'A was prepared for the {A.loss} loss: use prepare(A, y, loss="logistic")')
         return A

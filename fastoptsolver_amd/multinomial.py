@@ -60,6 +60,7 @@ def prepare_multinomial(A, y, classes=None, dtype=None, *, sample_weight=None, p
 def _problem(A, y, classes, dtype):
     """The multinomial handle on (A, y): a prepared one as it is, anything else bound (and padded) here."""
     if isinstance(A, _core.Problem):
+        _core.refuse_link(A, "multinomial_path / multinomial_cv / multinomial_objective")
         if A.loss != "multinomial":
             raise ValueError(f'A was prepared for the {A.loss} loss: use prepare(A, y, loss="multinomial")')
         if classes is not None and int(classes) != A.classes:

@@ -51,6 +51,7 @@ def _problem(A, dtype):
     """The squared-loss handle on A: a prepared one as it is (penalty factors allowed; row weights and box bounds refused),
     anything else bound here with rows padded to the matrix-core pair's granularity."""
     if isinstance(A, _core.Problem):
+        _core.refuse_link(A, "multitask_path / multitask_objective")
         if A.loss != "squared":
             raise ValueError(f"A was prepared for the {A.loss} loss: the multi-task model has the squared loss")
         if A.sample_weight is not None:

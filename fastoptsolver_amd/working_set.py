@@ -58,7 +58,19 @@ def _family(prob, max_iter):
     """The lockstep family `fista_path` / `logistic_path` give this kind of handle."""
     if prob.loss == "logistic":
         return _its._columns(max_iter, True, 4.0)
+    if prob.loss in _core.LINK_LOSSES:           # `huber_path` / `hinge_path`: the squared loss's L, the lockstep alone
+        return _its._columns(max_iter, True, 1.0)
     return _its._columns(max_iter, _its._weighted(prob) or _its._has_coord(prob))
+
+
+def _sub_problem(prob, A_ws, p_ws):
+    """The problem on the gathered columns: the handle's b, loss (with the Huber threshold), row weights and the factors p_ws."""
+    if prob.loss in _core.LINK_LOSSES:
+        sub = _core.Problem.link(A_ws, prob.b, prob.loss, prob.threshold, sample_weight=prob.sample_weight)
+        if p_ws is not None:
+            sub.set_penalty(p_ws)
+        return sub
+    return _core.Problem.penalized(A_ws, prob.b, p_ws, loss=prob.loss, sample_weight=prob.sample_weight)
 
 
 def _factors(prob):
@@ -182,7 +194,7 @@ def _solve_group(prob, fam, alphas, max_iter, kkt_tol, max_rounds, grow, max_fra
             p_ws = torch.ones(n_ws_pad, dtype=torch.float64)
             p_ws[:n_ws] = pf[idx].to("cpu", torch.float64)
             p_ws = p_ws.numpy()
-        sub = _core.Problem.penalized(A_ws, prob.b, p_ws, loss=prob.loss, sample_weight=prob.sample_weight)
+        sub = _sub_problem(prob, A_ws, p_ws)
         prms = _its._path_params(sub, alphas, L, fam, t_init_factor, None)
         X0 = None
         if len(sizes) > 1 or bool((X != 0).any()):
