@@ -1,0 +1,916 @@
+"""Cells, moves and fp64 references of the tests that run every ordered pair of lockstep configurations on ONE problem handle
+(a helper: no tests in here).  tests/test_handle_pairs.py checks the table on the CPU, tests/test_gpu_handle_pairs.py runs it.
+
+fos_problem_set_loss, fos_problem_set_link_loss, fos_problem_set_multinomial, fos_row_weights_bind and fos_coord_bind end with
+"no buffer depends on ...: nothing to invalidate"; fos_feature_groups_bind and fos_problem_replan re-bind or drop buffers beside
+the bindings that stay.  All of them act on one handle whose workspace every lockstep call shares (cand.xp / q_part / bt_out,
+multi.rbuf16 / slabs16, ws.b16 / link_part / grad_part, fg.u / nrm2, the borrowed b, row_weight and coord_* pointers, loss,
+link_param and classes).  A CELL is a configuration of the handle plus one call on it; move(X, Y) is the shortest sequence of
+binding calls a caller would make to get from X's configuration to Y's, ordered so that the library's refusal rules allow every
+step.  The GPU file compares what a cell returns after any other cell, and after a replan, bit for bit with what it returns on a
+fresh handle, whose own result is checked against the family's fp64 reference here.
+
+One data set per (shape, storage type), shared by every cell: one seeded Gaussian design (tests/_data.synth) and one target per
+loss - b with a tenth of gross outliers (tests/_link.huber_recipe) for the squared and Huber cells, labels of the planted model
+in {0, 1} (tests/_logit.labels) and in {-1, +1} (tests/_link.hinge_recipe), class indices for C = 3 and C = 7
+(tests/_multinomial.labels) - "counts" row weights (tests/_weighted.weights), penalty factors with exact zeros
+(tests/_coord.factors) under the lower bound 0, and the "weights" group layout (tests/_fgroup.layout: seeded sizes 1..7, every
+sixth group of weight 0).  The handle BORROWS b (fos.h: "the caller's: never freed here"), so a cell of another loss overwrites the
+bound device vector in place; anything that cached a function of b would show.
+
+Every run takes ITERS = 12 iterations with L of the reference passed to both sides: lambda_max(A^T A) from the oracle's power
+iteration (of A^T W A with row weights), a quarter of it for the logistic and half for the multinomial loss.
+
+Shapes, for the CU count the planner reports: "padded" 1003 x 37 (the device copy has 68 fp32 / 72 bf16 columns: the extra
+zero group, the padded factor vectors, rows % 4 != 0) and tests/_menu_cv's "panels" (two row panels, the second short:
+ws.link_part / ws.grad_part and the fold ids offset with the panel)."""
+import collections
+import functools
+import glob
+import os
+import re
+
+import numpy as np
+
+from oracle import fos_oracle as orc
+from tests import (_coord as cd, _data, _fgroup as fg, _forms, _group as gp, _link as lk, _logit as lg, _menu_cv as mcv,
+                   _menu_multi as mm, _multinomial as mn, _weighted as wt, _working_set as ws)
+from tests._menu_product1 import CSRC, PLAN, _body, _text
+
+ITERS = 12
+TOL = lg.TOL                              # the project's standing 1e-5 of the lockstep against the fp64 oracle
+KINDS = ("f32", "bf16")
+SHAPES = ("padded", "panels")
+PADDED = (1003, 37)
+WEIGHT_MAX = 3.0                          # tests/_weighted.weights("counts"): integers 0..3
+MU = 0.5                                  # l1_ratio of the feature-group cells
+# The planted model has 11 of 37 coefficients (tests/_data.synth's default leaves 2: nothing for a working set to grow into), and
+# the seed is the one of 1 .. 8 at which every precondition of tests/test_handle_pairs.py holds for both storage types - the
+# working set of both losses grows and ends certified, the controlled ladder has an early stop, a full run and a genuine restart:
+# found on the references alone.
+SEED = 6
+DENSITY = 0.3
+INCLUDE = os.path.join(os.path.dirname(CSRC), os.pardir, "include")
+
+
+def shape(name, kind, cus=mm.GPU_CUS):
+    if name == "padded":
+        return PADDED
+    c = mcv.shapes(kind, cus)["panels"]
+    return c["m"], c["n"]
+
+
+# ---- configurations ------------------------------------------------------------------------------------------------------------
+Config = collections.namedtuple("Config", "loss classes grouped weights coord groups", defaults=("squared", 0, False, False, False, False))
+PLAIN = Config()
+TARGET = {"squared": "b", "huber": "b", "logistic": "y01", "squared_hinge": "ysign"}
+LOSS_IDS = {"squared": 0, "logistic": 1, "multinomial": 2, "huber": 3, "squared_hinge": 4}     # include/fos.h, fos_link_loss.h
+SETTER = {"squared": "fos_problem_set_loss", "logistic": "fos_problem_set_loss", "multinomial": "fos_problem_set_multinomial",
+          "huber": "fos_problem_set_link_loss", "squared_hinge": "fos_problem_set_link_loss"}
+
+
+def target_key(cfg):
+    return f"y{cfg.classes}" if cfg.loss == "multinomial" else TARGET[cfg.loss]
+
+
+def plan_move(X, Y):
+    """The steps from configuration X to Y as (entry point or "target" / "grouped", argument) pairs: only what differs, in the
+    order the refusal rules of csrc/fos_plan.hip allow - feature groups come off before factors or the multinomial loss go on,
+    factors come off before feature groups go on, the loss leaves multinomial before feature groups are bound.  Bindings that X
+    and Y share stay bound."""
+    steps = []
+    if X.groups and not Y.groups:
+        steps.append(("fos_feature_groups_bind", False))
+    if X.coord and not Y.coord:
+        steps.append(("fos_coord_bind", False))
+    if target_key(X) != target_key(Y):
+        steps.append(("target", target_key(Y)))
+    if (X.loss, X.classes) != (Y.loss, Y.classes):
+        steps.append((SETTER[Y.loss], (Y.loss, Y.classes)))
+    if X.weights != Y.weights:
+        steps.append(("fos_row_weights_bind", Y.weights))
+    if Y.coord and not X.coord:
+        steps.append(("fos_coord_bind", True))
+    if Y.groups and not X.groups:
+        steps.append(("fos_feature_groups_bind", True))
+    if X.grouped != Y.grouped:
+        steps.append(("grouped", Y.grouped))
+    return steps
+
+
+class Refused(Exception):
+    pass
+
+
+class HostModel:
+    """The refusal rules of the binding entry points, written from their guard texts in csrc/fos_plan.hip (GUARDS pins each to
+    the source): what a step needs of the bindings that are in place when it is made.  The shape rules (b, no sharding, the
+    matrix-core pair) hold for every handle of these tests and are not modelled."""
+
+    def __init__(self, cfg=PLAIN):
+        self.loss, self.coord, self.groups = cfg.loss, cfg.coord, cfg.groups
+
+    def step(self, entry, arg):
+        if entry == "fos_problem_set_multinomial" and self.groups:
+            raise Refused("fos_problem_set_multinomial: feature groups (fos_feature_groups_bind) are bound")
+        if entry == "fos_coord_bind" and arg and self.groups:
+            raise Refused("fos_coord_bind: feature groups (fos_feature_groups_bind) are bound")
+        if entry == "fos_feature_groups_bind" and arg:
+            if self.coord:
+                raise Refused("fos_feature_groups_bind: penalty factors or bounds (fos_coord_bind) are bound")
+            if self.loss == "multinomial":
+                raise Refused("fos_feature_groups_bind: a multinomial problem is not served")
+        if entry in SETTER.values():
+            self.loss = arg[0]
+        elif entry == "fos_coord_bind":
+            self.coord = bool(arg)
+        elif entry == "fos_feature_groups_bind":
+            self.groups = bool(arg)
+
+
+# entry point -> (the condition of each guard the model knows, the start of its message), beside the shape rules every setter shares
+GUARDS = {
+    "fos_problem_set_multinomial": [(r"has_fgroups\(p\)", "fos_problem_set_multinomial: feature groups (fos_feature_groups_bind) are bound")],
+    "fos_coord_bind": [(r"has_fgroups\(p\)", "fos_coord_bind: feature groups (fos_feature_groups_bind) are bound")],
+    "fos_feature_groups_bind": [(r"has_coord\(p\)", "fos_feature_groups_bind: penalty factors or bounds (fos_coord_bind) are bound"),
+                                (r"p->loss\s*==\s*FOS_LOSS_MULTINOMIAL", "fos_feature_groups_bind: a multinomial problem is not served")],
+    "fos_problem_set_loss": [], "fos_problem_set_link_loss": [], "fos_row_weights_bind": [],
+}
+SHAPE_RULES = (r"!p->b", r"p->comm\s*\|\|\s*p->col_sharded", r"!pair_dd_multi_supported\(p\)")
+
+
+def check_guards(plan=PLAN):
+    """Every FOS_ERR_UNSUPPORTED of a binding entry point is a shape rule or a guard of HostModel: a new refusal rule fails here
+    until the model (and with it the order of plan_move) knows it."""
+    text = _text(plan)
+    for entry, guards in GUARDS.items():
+        body = _body(text, r"\bint\s+" + entry + r"\s*\([^)]*\)\s*(?=\{)")
+        conds = re.findall(r"if\s*\(((?:[^()]|\([^()]*\))*)\)\s*return\s+fail\(FOS_ERR_UNSUPPORTED", body)
+        left = [c for c in conds if not any(re.fullmatch(r"\s*" + s + r"\s*", c) for s in SHAPE_RULES)]
+        assert len(left) == len(guards), (entry, left)
+        for (cond, message), got in zip(guards, left):
+            assert re.fullmatch(r"\s*" + cond + r"\s*", got), (entry, got)
+            assert message in body, (entry, message)
+
+
+# what sets a handle's configuration without being a step of a move, and why
+NOT_A_MOVE = {
+    "fos_problem_set_stream": "the stream the handle works on: Problem.ctx follows torch's current stream",
+    "fos_problem_set_gbuf": "the caller's gradient buffer, bound once by Problem._bind",
+    "fos_problem_set_comm": "row sharding: no lockstep feature of these cells serves a sharded handle",
+    "fos_problem_set_comm_cols": "column sharding likewise",
+    "fos_problem_set_fused_stamps": "a debugging hook of the one-launch persistent step",
+    "fos_problem_replan": "no step of a move: part 3 of tests/test_gpu_handle_pairs.py replans with every cell's bindings in place",
+}
+
+
+def binding_entry_points(include=INCLUDE):
+    """The entry points of include/*.h that bind or change a handle's configuration, by name."""
+    names = set()
+    for path in sorted(glob.glob(os.path.join(include, "*.h"))):
+        with open(path) as fh:
+            names |= set(re.findall(r"\bint\s+(fos_problem_set_\w+|fos_\w+_bind|fos_problem_replan)\s*\(", fh.read()))
+    return names
+
+
+# ---- data ------------------------------------------------------------------------------------------------------------------------
+def _frozen(d):
+    for v in d.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return d
+
+
+@functools.lru_cache(maxsize=4)
+def data(name, kind, cus=mm.GPU_CUS):
+    """The data of a shape and storage type, computed once and never modified."""
+    m, n = shape(name, kind, cus)
+    A, b, xt = _data.synth(m, n, SEED, density=DENSITY)
+    A32 = A.astype(np.float32)
+    A64 = (_forms.bf16_round_np(A32) if kind == "bf16" else A32).astype(np.float64)
+    rng = np.random.default_rng(20)                                  # tests/_link.huber_recipe: a tenth of gross outliers
+    out = rng.choice(m, size=max(1, m // 10), replace=False)
+    b = b.copy()
+    b[out] += rng.choice([-1.0, 1.0], size=out.size) * 10.0 * np.std(b)
+    b = b.astype(np.float32).astype(np.float64)
+    s = A @ xt                                                       # tests/_link.hinge_recipe
+    ysign = np.sign(s + 0.5 * np.std(s) * np.random.default_rng(SEED + 7).standard_normal(m))
+    ysign[ysign == 0] = 1.0
+    start, gw = fg.layout("weights", n, SEED)
+    rngb = np.random.default_rng(600 + SEED)                         # tests/_cluster_planned.targets
+    B = (b[:, None] * rngb.uniform(0.5, 1.5, size=5)[None, :] + 0.3 * rngb.standard_normal((m, 5))).astype(np.float32)
+    ids = np.random.default_rng(800 + SEED).integers(0, 3, size=m)   # shuffled fold ids, no fold empty
+    ids[:3] = np.arange(3)
+    w = wt.as_stored(wt.weights("counts", m, SEED))
+    assert w.max() <= WEIGHT_MAX and gw is not None and (gw == 0).any() and (gw > 0).any()
+    v0 = np.random.default_rng(SEED + 1).standard_normal(n)
+    L, Lw = float(orc.estimate_lipschitz(A64, v0=v0)), wt.estimate_lipschitz(A64, w, v0)
+    return _frozen(dict(name=name, kind=kind, cus=cus, m=m, n=n, A32=A32, A=A64, b=b, threshold=float(np.float32(np.median(np.abs(b)))),
+                        y01=lg.labels(A, xt, SEED), ysign=ysign, y3=mn.labels(A, 3, SEED), y7=mn.labels(A, 7, SEED), w=w,
+                        p=cd.factors(n, SEED), lo=np.zeros(n), start=start, gw=gw, B=B, ids3=ids.astype(np.int64),
+                        ids2=(ids % 2).astype(np.int64), L=L, Lw=Lw))
+
+
+def L_of(d, cfg):
+    return d["Lw" if cfg.weights else "L"] / {"logistic": 4.0, "multinomial": 2.0}.get(cfg.loss, 1.0)
+
+
+def parts(d, cfg, rows=None):
+    """What a reference of the configuration takes: A, the target, w, p, lo (None where not bound), on `rows` (a mask) or all."""
+    A, t = d["A"], d[target_key(cfg)]
+    w = d["w"] if cfg.weights else None
+    if rows is not None:
+        A, t, w = A[rows], t[rows], None if w is None else w[rows]
+    return A, t, w, (d["p"] if cfg.coord else None), (d["lo"] if cfg.coord else None)
+
+
+def gradient0(d, cfg):
+    """Minus the gradient of the data term at 0 (up to its sign per coordinate, which no weight depends on)."""
+    A, t, w, _, _ = parts(d, cfg)
+    ww = np.ones(d["m"]) if w is None else w
+    r = {"squared": t, "logistic": t - 0.5, "huber": lk.psi(lk.HUBER, np.zeros(d["m"]), t, d["threshold"]), "squared_hinge": t}[cfg.loss]
+    return A.T @ (ww * r)
+
+
+def ladder(amax, count, first=0.5, last=0.02):
+    """`count` weights from `first` to `last` of alpha_max, geometric, every third an elastic net."""
+    ratio = (last / first) ** (1.0 / max(count - 1, 1))
+    return [(amax * first * ratio ** i, 0.5 if i % 3 == 1 else 0.0) for i in range(count)]
+
+
+def alphas(d, cfg, count):
+    """`count` weights below alpha_max of the configuration (above it 0 is the solution), lasso and elastic net mixed."""
+    if cfg.loss == "multinomial":
+        A, y, w, _, _ = parts(d, cfg)
+        return (gp.multinomial_weights(A, y, cfg.classes, count, w) if cfg.grouped else mn.weights(A, y, cfg.classes, count))
+    g0 = gradient0(d, cfg)
+    if cfg.groups:
+        return ladder(fg.alpha_max(g0, d["start"], fg.weights_of(d["start"], d["gw"]), MU), count)
+    if cfg.coord:
+        return ladder(float((np.abs(g0)[d["p"] > 0] / d["p"][d["p"] > 0]).max()), count)
+    return ladder(float(np.abs(g0).max()), count, *((0.03, 0.003) if cfg.loss == lk.HINGE else ()))   # (weaker: both hinge branches)
+
+
+def fit(d, cfg, a1, a2, rows=None, **control):
+    """The fp64 reference of one fit of the configuration after ITERS iterations from 0: a dict with x (n, or n x C) and, for
+    the families with device control, what tests/_coord.run records."""
+    A, t, w, p, lo = parts(d, cfg, rows)
+    L = L_of(d, cfg)
+    if cfg.loss == "multinomial":
+        if cfg.grouped:
+            return dict(x=gp.iterate(gp.GroupMultinomial(A, t, cfg.classes, a1, a2, w, p), L, ITERS)[0])
+        return dict(x=mn.run(A, t, cfg.classes, a1, a2, L, ITERS, w=w, p=p, lo=lo))
+    if cfg.loss in (lk.HUBER, lk.HINGE):
+        assert not cfg.coord and not cfg.groups
+        return dict(x=lk.run(cfg.loss, A, t, a1, a2, L, ITERS, c=d["threshold"] if cfg.loss == lk.HUBER else None, w=w)[0])
+    if cfg.groups:
+        return fg.run(A, t, a1, a2, L, ITERS, start=d["start"], gw=d["gw"], mu=MU, loss=cfg.loss, w=w, **control)
+    return cd.run(A, t, a1, a2, L, ITERS, p=p, lo=lo, loss=cfg.loss, w=w, **control)
+
+
+def data_term(d, cfg, X, rows=None):
+    """(the data term of every column of X - of every class group for the multinomial loss -, the bound of its fp32 sum) on all
+    rows or on `rows`."""
+    A, t, w, _, _ = parts(d, cfg, rows)
+    ww = np.ones(A.shape[0]) if w is None else w
+    if cfg.loss == "multinomial":
+        C = cfg.classes
+        groups = [X[:, i:i + C] for i in range(0, X.shape[1], C)]
+        return (np.array([mn.nll(A, G, t, w) for G in groups]), np.array([WEIGHT_MAX ** cfg.weights * mn.nll_tolerance(A, G) for G in groups]))
+    if cfg.loss == "logistic":
+        return wt.wnll(A, X, t, ww), wt.wnll_tolerance(A, X, ww)
+    if cfg.loss in (lk.HUBER, lk.HINGE):
+        c = d["threshold"] if cfg.loss == lk.HUBER else None
+        return lk.data_term(cfg.loss, A, X, t, c, w), lk.loss_tolerance(cfg.loss, A, X, t, c, w)
+    sse = wt.wsse(A, X, t, ww)                         # the squared sums (no 1/2), as fos_residual_batch answers
+    sw = np.sqrt(ww)
+    _, tol = _data.fp32_pass_tolerances_cols(sw[:, None] * A, X, sw * t, np.zeros_like(X), sse)
+    return sse, tol
+
+
+def penalties(d, cfg, X, a1, a2):
+    """The separable penalties of the columns of X (of the class groups for the multinomial loss) with the factors as bound."""
+    p = d["p"][:, None] if cfg.coord else 1.0
+    W = cfg.classes if cfg.loss == "multinomial" else 1
+    l1 = (p * np.abs(X)).sum(axis=0).reshape(-1, W).sum(axis=1)
+    return a1 * l1 + 0.5 * a2 * (p * X * X).sum(axis=0).reshape(-1, W).sum(axis=1)
+
+
+def block(d, columns, seed):
+    """A sparse seeded n x columns block of fp32 values (what an objective or a certificate is asked for), in fp64."""
+    rng = np.random.default_rng(900 + seed)
+    X = 0.1 * rng.standard_normal((d["n"], columns)) * (rng.random((d["n"], columns)) < 0.3)
+    return X.astype(np.float32).astype(np.float64)
+
+
+# ---- the device side -------------------------------------------------------------------------------------------------------------
+class Ctx:
+    """The device matrix and targets of a (shape, storage type), shared by every handle of its tests."""
+
+    def __init__(self, fos, d):
+        import torch
+        self.fos, self.d, self.torch = fos, d, torch
+        self.At = torch.as_tensor(np.array(d["A32"])).to(torch.bfloat16 if d["kind"] == "bf16" else torch.float32).cuda()
+        self.targets = {k: torch.as_tensor(d[k].astype(np.float32)).cuda() for k in ("b", "y01", "ysign", "y3", "y7")}
+        self.wbuf = torch.zeros((d["m"] + 3) // 4 * 4, dtype=torch.float32, device="cuda")      # Problem._setup's padding
+        self.wbuf[:d["m"]] = torch.as_tensor(d["w"].astype(np.float32))
+        self.B = torch.as_tensor(np.array(d["B"])).cuda()
+
+    def fresh(self):
+        """A plain squared-loss handle on a b of its own.  Bound through prepare_weighted and detached at once: only a handle
+        that is served by the matrix-core pair alone gets the padding to 68 / 72 device columns that every binding needs at
+        n <= 64, and no call has run on it."""
+        P = self.fos.prepare_weighted(self.At, self.targets["b"].clone(), self.d["w"])
+        P.set_sample_weight(None)
+        return P
+
+    def apply(self, P, steps):
+        """The steps of plan_move on the handle, with the Python attributes the front ends read."""
+        from fastoptsolver_amd import _lib
+        d = self.d
+        for entry, arg in steps:
+            if entry == "target":
+                with P.ctx():                              # on the handle's stream
+                    P.b.copy_(self.targets[arg])
+            elif entry == "grouped":
+                P.set_grouped(arg)
+            elif entry == "fos_row_weights_bind":
+                P.set_sample_weight(self.wbuf[:d["m"]] if arg else None)
+            elif entry == "fos_coord_bind":
+                P.set_penalty(*((np.array(d["p"]), np.array(d["lo"]), None) if arg else ()))
+            elif entry == "fos_feature_groups_bind":
+                P.set_feature_groups(*((np.diff(d["start"]), np.array(d["gw"]), MU) if arg else (None,)))
+            else:
+                loss, classes = arg
+                if loss == "multinomial":
+                    _lib.check(P.lib.fos_problem_set_multinomial(int(classes), P.h), entry)
+                elif loss in (lk.HUBER, lk.HINGE):
+                    _lib.check(P.lib.fos_problem_set_link_loss(LOSS_IDS[loss], d["threshold"] if loss == lk.HUBER else 0.0, P.h), entry)
+                else:
+                    _lib.check(P.lib.fos_problem_set_loss(P.h, LOSS_IDS[loss]), entry)
+                if loss != "multinomial":
+                    P.grouped = False
+                P.loss, P.classes = loss, (classes or None)
+                P.threshold = d["threshold"] if loss == lk.HUBER else None
+
+    def move(self, P, X, Y):
+        self.apply(P, plan_move(X.cfg if isinstance(X, Cell) else X, Y.cfg if isinstance(Y, Cell) else Y))
+
+    def run(self, cell, P):
+        """cell.call on the handle as host arrays, with the assertion that the cell was served: every answer of an entry point
+        that may decline (fastoptsolver_amd._lib.served: the front ends of the plain squared loss then run one by one, or column
+        by column, without a word) was a yes, and the entry points the cell names were asked."""
+        from fastoptsolver_amd import _lib
+        asked, served = [], _lib.served
+
+        def spy(rc, what=""):
+            ok = served(rc, what)
+            asked.append((what, ok))
+            return ok
+        _lib.served = spy
+        try:
+            out = cell.call(self, P)
+        finally:
+            _lib.served = served
+        assert all(ok for _, ok in asked), (cell.name, asked, P.lib.fos_last_error())
+        assert set(cell.reaches + cell.serves) & MAY_DECLINE <= {what for what, _ in asked}, (cell.name, asked)
+        return {k: _host(v) for k, v in out.items()}
+
+    def getters(self, P):
+        """What the library's getters report of the handle, as a Config-shaped tuple and the Huber parameter."""
+        import ctypes as C
+        lib, h = P.lib, P.h
+        loss, link, classes, ng = C.c_int(-1), C.c_int(-1), C.c_int(-1), C.c_int32(-1)
+        param, mix = C.c_double(-1.0), C.c_double(-1.0)
+        w, pf, lo, hi = C.c_void_p(1), C.c_void_p(1), C.c_void_p(1), C.c_void_p(1)
+        assert lib.fos_problem_get_loss(h, C.byref(loss)) == 0 and lib.fos_problem_get_link_loss(C.byref(link), C.byref(param), h) == 0
+        assert lib.fos_problem_get_classes(C.byref(classes), h) == 0 and lib.fos_row_weights_get(C.byref(w), h) == 0
+        assert lib.fos_coord_get(C.byref(pf), C.byref(lo), C.byref(hi), h) == 0
+        assert lib.fos_feature_groups_get(C.byref(ng), C.byref(mix), h) == 0
+        return dict(loss=loss.value, link=link.value, param=param.value, classes=classes.value, weights=w.value,
+                    coord=(pf.value, lo.value, hi.value), ngroups=ng.value, mix=mix.value)
+
+    def check_getters(self, P, cfg, where):
+        """The getters report the configuration just set, and the handle's own attributes agree."""
+        d, g = self.d, self.getters(P)
+        link = cfg.loss in (lk.HUBER, lk.HINGE)
+        ngroups = len(d["start"]) - 1 + (1 if P.n_dev > P.n else 0)          # the padding columns form one more group
+        want = dict(loss=LOSS_IDS[cfg.loss], link=LOSS_IDS[cfg.loss] if link else 0,
+                    param=np.float64(d["threshold"]) if cfg.loss == lk.HUBER else 0.0, classes=cfg.classes,
+                    weights=self.wbuf.data_ptr() if cfg.weights else None,
+                    coord=(P._coord[0].data_ptr(), P._coord[1].data_ptr(), None) if cfg.coord else (None, None, None),
+                    ngroups=ngroups if cfg.groups else 0, mix=MU if cfg.groups else 0.0)
+        assert g == want, (where, g, want)
+        assert (P.loss, P.classes or 0, bool(P.grouped), P.sample_weight is not None, P.has_coord, P.has_feature_groups) == tuple(cfg), where
+
+
+# ---- cells -----------------------------------------------------------------------------------------------------------------------
+def _host(v):
+    """A result leaf as an ndarray (device tensors come to the host; bit for bit)."""
+    if hasattr(v, "detach"):
+        return v.detach().cpu().numpy()
+    return np.asarray(v)
+
+
+def same_bits(a, b):
+    """None where two results of a cell are bit for bit equal, else the first key that differs with the largest difference."""
+    assert set(a) == set(b)
+    for k in a:
+        x, y = _host(a[k]), _host(b[k])
+        if x.shape != y.shape or x.dtype != y.dtype:
+            return k, "shape", x.shape, y.shape
+        if x.tobytes() != y.tobytes():
+            return k, float(np.nanmax(np.abs(x.astype(np.float64) - y.astype(np.float64))))
+    return None
+
+
+def _rel_ok(got, want, where):
+    err = _data.rel(np.asarray(_host(got), dtype=np.float64), want)
+    assert err < TOL, (where, err)
+
+
+class Cell:
+    """A configuration of the handle and one call on it.  reaches: the lockstep entry points the call goes through.
+    sized_by_panels: whether a buffer of the call is sized by the number of row panels (the pairs run at "panels")."""
+    reaches, serves, sized_by_panels = (), (), False
+
+    def __init__(self, name, cfg):
+        self.name, self.cfg = name, cfg
+
+    def reference(self, d):
+        raise NotImplementedError
+
+    def precondition(self, d, ref):
+        """What the reference must show so that the cell cannot pass vacuously (asserted at the padded shape on the CPU)."""
+
+    def ref(self, d):
+        return _reference(self.name, d["name"], d["kind"], d["cus"])
+
+
+class Path(Cell):
+    """The family's path call with `count` weights and return_info."""
+    FRONT = {"squared": "fista_path", "logistic": "logistic_path", "huber": "huber_path", "squared_hinge": "hinge_path",
+             "multinomial": "multinomial_path"}
+    reaches = ("fos_fista_run_multi",)
+
+    def __init__(self, name, cfg, count):
+        super().__init__(name, cfg)
+        self.count = count
+        self.sized_by_panels = cfg.loss == "multinomial"
+
+    def weights(self, d):
+        return alphas(d, self.cfg, self.count)
+
+    def call(self, c, P):
+        xs, info = getattr(c.fos, self.FRONT[self.cfg.loss])(P, None, self.weights(c.d), max_iter=ITERS, L=L_of(c.d, self.cfg), return_info=True)
+        return dict(x=c.torch.stack(list(xs)), info=np.array(info))
+
+    def reference(self, d):
+        refs = [fit(d, self.cfg, a1, a2) for a1, a2 in self.weights(d)]
+        out = dict(x=np.stack([r["x"] for r in refs]))
+        if self.cfg.groups:                                   # no group norm so close to its threshold that fp32 may decide otherwise
+            out["closest"] = np.array([r["closest"] for r in refs])
+            assert out["closest"].min() >= fg.CLOSE, out["closest"]
+        return out
+
+    def precondition(self, d, ref):
+        X = ref["x"]
+        flat = X.reshape(len(X), -1)
+        assert all((x != 0).any() for x in flat) and (flat[0] == 0).any(), "the penalty must bite"
+        if self.cfg.coord:                                    # the lower bound binds and an unpenalised coordinate is in the model
+            A, t, w, p, _ = parts(d, self.cfg)
+            unc = cd.run(A, t, *self.weights(d)[-1], L_of(d, self.cfg), ITERS, p=p, loss=self.cfg.loss, w=w)["x"]
+            assert (unc < 0).any() and (X >= 0).all() and (X[:, d["p"] == 0] != 0).any()
+        if self.cfg.groups:
+            zero, _ = fg.zero_groups(X[0], d["start"])
+            assert zero.any() and (~zero).any()
+        if self.cfg.grouped:
+            rows0 = np.abs(X[0]).sum(axis=1) == 0.0
+            assert rows0.any() and (~rows0).any(), "the group penalty must bite"
+        if self.cfg.loss == lk.HUBER:
+            A, b, _, _, _ = parts(d, self.cfg)
+            shares = [lk.clipped_share(A, x, b, d["threshold"]) for x in [np.zeros(d["n"])] + list(X)]
+            assert all(0.05 <= s <= 0.95 for s in shares), shares
+
+    def check(self, d, out):
+        ref = self.ref(d)
+        for i in range(self.count):
+            _rel_ok(out["x"][i], ref["x"][i], (self.name, i))
+        assert (out["info"] == [ITERS, 0]).all(), out["info"]
+
+
+class Controlled(Path):
+    """fista_path with adaptive restart and the ratio stop, decided per weight on the device: the weights of a ladder whose every
+    decision tests/_coord.fp32_proof accepts on the reference alone, of which at least one stops early (a masked column of the
+    block from then on) and one runs to the end."""
+    CANDIDATES = 24
+    MENU = (dict(adaptive_restart=True, restart_threshold=0.95, tol_ratio=0.5), cd.CONTROL_MENU[1], cd.CONTROL_MENU[0])
+
+    def __init__(self, name):
+        super().__init__(name, PLAIN, 0)
+
+    def chosen(self, d):
+        return _controlled(d["name"], d["kind"], d["cus"])
+
+    def weights(self, d):
+        return self.chosen(d)[1]
+
+    def call(self, c, P):
+        ctl, weights = self.chosen(c.d)
+        xs, info = c.fos.fista_path(P, None, weights, max_iter=ITERS, L=c.d["L"], return_info=True, **ctl)
+        return dict(x=c.torch.stack(list(xs)), info=np.array(info))
+
+    def reference(self, d):
+        ctl, weights = self.chosen(d)
+        refs = [fit(d, PLAIN, a1, a2, **ctl) for a1, a2 in weights]
+        assert all(cd.fp32_proof(r, ctl["restart_threshold"], ctl["tol_ratio"]) for r in refs)
+        return dict(x=np.stack([r["x"] for r in refs]), info=np.array([(r["k"], r["stopped"]) for r in refs]),
+                    restarts=np.array([cd.genuine_restarts(r, ctl["restart_threshold"]) for r in refs]))
+
+    def precondition(self, d, ref):
+        k, stopped = ref["info"][:, 0], ref["info"][:, 1]
+        assert ((stopped == cd.STOP_RATIO) & (k < ITERS)).any() and (k == ITERS).any() and ref["restarts"].sum() >= 1
+
+    def check(self, d, out):
+        ref = self.ref(d)
+        assert np.array_equal(out["info"], ref["info"]), (out["info"], ref["info"])
+        for i in range(len(ref["x"])):
+            _rel_ok(out["x"][i], ref["x"][i], (self.name, i))
+
+
+@functools.lru_cache(maxsize=None)
+def _controlled(name, kind, cus):
+    """(control parameters, weights): the fp32-proof weights of the ladder (at most 16, at least five: the matrix-core lockstep
+    takes a controlled call from three on) under the first entry of Controlled.MENU with which one of them stops early and one
+    runs to the end; where no entry gives both (the panels shape is so well conditioned that every weight stops at once) under
+    the first that gives five."""
+    d = data(name, kind, cus)
+    found = []
+    for ctl in Controlled.MENU:
+        keep, ks = [], []
+        for a1, a2 in ladder(float(np.abs(gradient0(d, PLAIN)).max()), Controlled.CANDIDATES, 0.6, 0.001):
+            r = fit(d, PLAIN, a1, a2, **ctl)
+            if cd.fp32_proof(r, ctl["restart_threshold"], ctl["tol_ratio"]) and len(keep) < 16:
+                keep.append((a1, a2))
+                ks.append((r["k"], r["stopped"]))
+        if len(keep) >= 5:
+            found.append((ctl, keep))
+            if any(k < ITERS and s == cd.STOP_RATIO for k, s in ks) and any(k == ITERS for k, _ in ks):
+                return ctl, keep
+    assert found, "no entry of Controlled.MENU gives five weights with fp32-proof decisions"
+    return found[0]
+
+
+class Single(Cell):
+    """fista(A, b) with one target: the single-pass kernels and gbuf."""
+
+    def call(self, c, P):
+        a1, a2 = alphas(c.d, PLAIN, 2)[1]
+        return dict(x=c.fos.fista(P, None, "elasticnet", a1, a2, max_iter=ITERS, L=c.d["L"]))
+
+    def reference(self, d):
+        return dict(x=fit(d, PLAIN, *alphas(d, PLAIN, 2)[1])["x"])
+
+    def check(self, d, out):
+        _rel_ok(out["x"], self.ref(d)["x"], self.name)
+
+
+class Rhs(Cell):
+    """fista(A, B) for a 2-D B of five targets (ws.b16), and the squared residuals of the fits against B in one further pass.
+    fista itself keeps a handle that has a b of its own on the single-target path, so the cell enters at the driver fista(A, B)
+    hands a 2-D B to."""
+    reaches = ("fos_fista_run_multi_rhs", "fos_residual_batch_rhs")
+
+    def call(self, c, P):
+        from fastoptsolver_amd import iterative_solvers as its
+        a1, a2 = alphas(c.d, PLAIN, 2)[1]
+        lp = its._Loop(None, a1, a2, False, 0.5, 1.0, ITERS, 0.0, 0.0, False, 1.0)          # fista's own defaults
+        X = its._solve_targets(P, c.B, lp, c.d["L"], None, None)
+        return dict(x=X, rr=np.asarray(P.residual_batch_rhs(X, c.B)))
+
+    def reference(self, d):
+        a1, a2 = alphas(d, PLAIN, 2)[1]
+        return dict(x=np.stack([orc.fista(d["A"], d["B"][:, j].astype(np.float64), "elasticnet", a1, a2, max_iter=ITERS, L=d["L"])
+                                for j in range(5)], axis=1))
+
+    def check(self, d, out):
+        X, ref = np.asarray(_host(out["x"]), dtype=np.float64), self.ref(d)["x"]
+        assert X.shape == ref.shape
+        for j in range(5):
+            _rel_ok(X[:, j], ref[:, j], (self.name, j))
+        X32, B = X.astype(np.float32).astype(np.float64), d["B"].astype(np.float64)       # the sums on the device's own fits
+        R = d["A"] @ X32 - B
+        rr = (R * R).sum(axis=0)
+        _, tol = _data.fp32_pass_tolerances_cols(d["A"], X32, B, np.zeros_like(X32), rr)
+        assert out["rr"].shape == (5,) and (np.abs(out["rr"] - rr) <= tol).all(), (out["rr"], rr, tol)
+
+
+class Lbfgs(Cell):
+    """LBFGSSolver.fit(A, B) with three targets: the fp64 multi-point pass and its plan (dm).  As in Rhs, the cell enters at
+    the driver fit hands a 2-D B to: fit keeps a handle with a b of its own on the single-target path."""
+    serves = ("fos_lbfgs_minimize_multi",)
+
+    def call(self, c, P):
+        from fastoptsolver_amd.lbfgs import LBFGSSolver
+        s = LBFGSSolver("ridge", 0.0, 1.0, max_iter=ITERS)._fit_targets(P, c.B[:, :3].contiguous())
+        return dict(x=s.x_, nit=np.asarray(s.nit_), nfev=np.asarray(s.nfev_), f=np.asarray(s.final_obj_))
+
+    def reference(self, d):
+        fits = [orc.LBFGSSolver("ridge", 0.0, 1.0, max_iter=ITERS).fit(d["A"], d["B"][:, j].astype(np.float64)) for j in range(3)]
+        return dict(x=np.stack([s.x_ for s in fits], axis=1))
+
+    def check(self, d, out):
+        X, ref = _host(out["x"]), self.ref(d)["x"]
+        for j in range(3):
+            _rel_ok(X[:, j], ref[:, j], (self.name, j))
+
+
+class Power(Cell):
+    """fos_power_iter past its first chunk of 16 steps: ws.vring and ws.lhist."""
+    reaches = ("fos_power_iter",)
+    STEPS = 20
+
+    def v0(self, d):
+        return np.random.default_rng(SEED + 3).standard_normal(d["n"]).astype(np.float32).astype(np.float64)
+
+    def call(self, c, P):
+        L, it, v = P.power_iter(self.v0(c.d), n_iter=self.STEPS, tol=0.0)
+        return dict(L=np.float64(L), it=np.int64(it), v=v)
+
+    def reference(self, d):
+        v = self.v0(d) / np.linalg.norm(self.v0(d))
+        for _ in range(self.STEPS):
+            w = d["A"].T @ (d["A"] @ v)
+            L = float(np.linalg.norm(w))
+            v = w / L
+        return dict(L=L, v=v)
+
+    def check(self, d, out):
+        ref = self.ref(d)
+        assert int(out["it"]) == self.STEPS and abs(float(out["L"]) - ref["L"]) <= TOL * ref["L"], (out["L"], ref["L"])
+        _rel_ok(out["v"], ref["v"], self.name)
+
+
+class Lipschitz(Cell):
+    """estimate_lipschitz on the weighted handle: one fos_gram_apply per step of the power iteration on A^T W A."""
+    STEPS = 30
+
+    def call(self, c, P):
+        state = np.random.get_state()
+        np.random.seed(SEED)                               # the front end draws its start vector from the global stream
+        try:
+            return dict(L=np.float64(c.fos.estimate_lipschitz(P, n_iter=self.STEPS, tol=0.0)))
+        finally:
+            np.random.set_state(state)
+
+    def reference(self, d):
+        return dict(L=wt.estimate_lipschitz(d["A"], d["w"], np.random.RandomState(SEED).randn(d["n"]), n_iter=self.STEPS, tol=0.0))
+
+    def check(self, d, out):
+        ref = self.ref(d)["L"]
+        assert abs(float(out["L"]) - ref) <= TOL * ref, (out["L"], ref)
+
+
+class Cv(Cell):
+    """The family's CV call on explicit fold ids with return_coefs: the train form of product 1 on every panel, the held-out
+    form (R not written) behind it, the refit."""
+    FRONT = {"squared": "fista_cv", "logistic": "logistic_cv", "huber": "huber_cv", "squared_hinge": "hinge_cv"}
+    reaches = ("fos_fista_run_multi_folds", "fos_residual_batch_folds")
+    sized_by_panels = True
+
+    def __init__(self, name, cfg, folds, count):
+        super().__init__(name, cfg)
+        self.folds, self.count = folds, count
+
+    def call(self, c, P):
+        res = getattr(c.fos, self.FRONT[self.cfg.loss])(P, None, alphas(c.d, self.cfg, self.count), folds=np.array(c.d[f"ids{self.folds}"]),
+                                                       max_iter=ITERS, L=L_of(c.d, self.cfg), return_coefs=True)
+        return dict(coefs=res.coefs, score=np.asarray(res[1]), mean=np.asarray(res[2]), best=np.int64(res.best), x=res.x,
+                    info=np.array(res.info))
+
+    def reference(self, d):
+        ids, weights = d[f"ids{self.folds}"], alphas(d, self.cfg, self.count)
+        coefs = np.stack([np.stack([fit(d, self.cfg, a1, a2, rows=ids != f)["x"] for a1, a2 in weights], axis=1)
+                          for f in range(self.folds)], axis=1)                 # n x K x L
+        return dict(coefs=coefs)
+
+    def precondition(self, d, ref):
+        assert (ref["coefs"] != 0).any(axis=0).all() and (ref["coefs"] == 0).any(), "the penalty must bite"
+        if self.cfg.loss == lk.HINGE:                                          # tests/_link.hinge_recipe's rule, at every fit
+            A, y, _, _, _ = parts(d, self.cfg)
+            shares = [lk.active_share(A, ref["coefs"][:, f, a], y) for f in range(self.folds) for a in range(self.count)]
+            assert all(0.1 <= s <= 0.9 for s in shares), shares
+
+    def check(self, d, out):
+        ref, ids = self.ref(d)["coefs"], d[f"ids{self.folds}"]
+        coefs = np.asarray(_host(out["coefs"]), dtype=np.float64)
+        assert coefs.shape == ref.shape
+        for f in range(self.folds):
+            held = ids == f
+            for a in range(self.count):
+                _rel_ok(coefs[:, f, a], ref[:, f, a], (self.name, f, a))
+            # the held-out score against fp64 on the device's own fits, as stored in fp32
+            X32 = coefs[:, f, :].astype(np.float32).astype(np.float64)
+            want, tol = data_term(d, self.cfg, X32, held)
+            den = float(d["w"][held].sum()) if self.cfg.weights else float(held.sum())
+            got = out["score"][f] * den
+            assert (np.abs(got - want) <= tol).all(), (self.name, f, got, want, tol)
+        assert int(out["best"]) == int(np.argmin(out["mean"])) and (out["info"][..., 0] == ITERS).all()
+        a1, a2 = alphas(d, self.cfg, self.count)[int(out["best"])]
+        _rel_ok(out["x"], fit(d, self.cfg, a1, a2)["x"], (self.name, "refit"))
+
+
+class Objective(Cell):
+    """The family's objective of `members` members of a seeded block: fos_residual_batch with the loss's link and the partial
+    sums it reserves (ws.link_part: twice the softmax size for a pointwise link)."""
+    FRONT = {"logistic": "logistic_objective", "huber": "huber_objective", "squared_hinge": "hinge_objective",
+             "multinomial": "multinomial_objective"}
+    reaches = ("fos_residual_batch",)
+    sized_by_panels = True
+
+    def __init__(self, name, cfg, members):
+        super().__init__(name, cfg)
+        self.members = members
+
+    def weight(self, d):
+        return alphas(d, self.cfg, 2)[1]
+
+    def block(self, d):
+        W = self.cfg.classes or 1
+        X = block(d, W * self.members, self.members)
+        return X, (X.reshape(d["n"], self.members, W).transpose(0, 2, 1) if W > 1 else X)     # member-major columns, and n x C x k
+
+    def call(self, c, P):
+        return dict(value=np.asarray(getattr(c.fos, self.FRONT[self.cfg.loss])(self.block(c.d)[1], P, None, *self.weight(c.d))))
+
+    def reference(self, d):
+        X, _ = self.block(d)
+        term, tol = data_term(d, self.cfg, X)
+        return dict(value=term + penalties(d, self.cfg, X, *self.weight(d)), tol=tol)
+
+    def check(self, d, out):
+        ref = self.ref(d)
+        assert out["value"].shape == ref["value"].shape and (np.abs(out["value"] - ref["value"]) <= ref["tol"]).all(), \
+            (self.name, out["value"], ref["value"], ref["tol"])
+
+
+class KktExcess(Cell):
+    """kkt_excess of a seeded block of 16 columns: one fos_gradient_batch (ws.grad_part with several panels) and one
+    fos_kkt_scan with an empty set."""
+    reaches = ("fos_gradient_batch", "fos_kkt_scan")
+    sized_by_panels = True
+
+    def call(self, c, P):
+        return dict(excess=c.fos.kkt_excess(P, c.torch.as_tensor(block(c.d, 16, 16)), alphas(c.d, self.cfg, 16)))
+
+    def reference(self, d):
+        A, t, w, _, _ = parts(d, self.cfg)
+        X = block(d, 16, 16)
+        G = ws.gradient(A, t, X, self.cfg.loss, w)
+        a1 = np.array([a for a, _ in alphas(d, self.cfg, 16)])
+        R = A @ X - t[:, None]
+        # a coordinate of a gradient column is off by no more than the column's bound in the 2-norm (tests/_data); the excess
+        # itself is stored in fp32
+        g_tol, _ = _data.fp32_pass_tolerances_cols(A, X, t, G, (R * R).sum(axis=0))
+        excess = (np.abs(G) / a1).max(axis=1)
+        return dict(excess=excess, tol=float((g_tol / a1).max()) + 2.0 * float(np.finfo(np.float32).eps) * excess)
+
+    def check(self, d, out):
+        ref = self.ref(d)
+        got = np.asarray(_host(out["excess"]), dtype=np.float64)
+        assert got.shape == (d["n"],) and (np.abs(got - ref["excess"]) <= ref["tol"]).all(), \
+            (self.name, np.abs(got - ref["excess"]).max(), ref["tol"].max())
+
+
+class WorkingSet(Cell):
+    """working_set_path on the handle: the KKT scans read fos_gradient_batch on the full problem, fos_gather_columns copies the
+    set's columns, the rounds themselves run on handles of their own.  max_rounds rounds of ITERS iterations from the scan at 0;
+    the reference (tests/_working_set.solve) must grow its set and end certified, every scan decision further than MARGIN from
+    its threshold and the last excess value the growth step takes further than GAP from the first it leaves."""
+    reaches = ("fos_gradient_batch", "fos_gather_columns", "fos_kkt_scan")
+    sized_by_panels = True
+    COUNT, KKT_TOL, MARGIN, GAP = 5, 1e-2, 1e-3, 1e-4
+
+    def weights(self, d):
+        return ladder(float(np.abs(gradient0(d, self.cfg)).max()), self.COUNT, 0.9, 0.3)
+
+    def call(self, c, P):
+        xs, infos = c.fos.working_set_path(P, None, self.weights(c.d), ITERS, L=L_of(c.d, self.cfg), kkt_tol=self.KKT_TOL,
+                                           max_fraction=1.0, return_info=True)
+        i = infos[0]
+        return dict(x=c.torch.stack(list(xs)), rounds=np.int64(i.rounds), sizes=np.array(i.sizes), grads=np.int64(i.full_gradients),
+                    fell_back=np.bool_(i.fell_back), worst=np.float64(i.worst_excess))
+
+    def reference(self, d):
+        A, t, w, _, _ = parts(d, self.cfg)
+        margins, gaps = [], []
+        scan = ws.scan
+
+        def recording(G, alpha1, slack, in_ws, p=None):
+            excess, viol = scan(G, alpha1, slack, in_ws, p)
+            out = np.asarray(in_ws) == 0
+            e = np.asarray(excess, dtype=np.float64)[out]
+            margins.append(float(np.abs(e - (1.0 + slack)).min()) if out.any() else np.inf)
+            want, top = int((np.asarray(in_ws) != 0).sum()), np.sort(e[e > 0])[::-1]      # grow = 2: the set doubles
+            if slack > 0 and 0 < viol.size < want < top.size:                            # the growth step takes the `want` largest
+                gaps.append(float(top[want - 1] - top[want]))
+            return excess, viol
+        ws.scan = recording
+        try:
+            X, info = self.solve(d, A, t, w)
+        finally:
+            ws.scan = scan
+        assert min(margins) >= self.MARGIN and min(gaps + [np.inf]) >= self.GAP and not info["fell_back"], (margins, gaps, info)
+        return dict(x=X.T, rounds=np.int64(info["rounds"]), sizes=np.array(info["sizes"]), grads=np.int64(info["full_gradients"]),
+                    worst=np.float64(info["worst_excess"]), margin=np.float64(min(margins)), gap=np.float64(min(gaps + [np.inf])))
+
+    def precondition(self, d, ref):
+        assert ref["rounds"] >= 2 and ref["sizes"][-1] > ref["sizes"][0], ref["sizes"]                      # grown
+        assert ref["worst"] <= 1.0 + self.KKT_TOL and ref["sizes"][-1] < d["n"], (ref["worst"], ref["sizes"])     # and certified
+
+    def solve(self, d, A, t, w):
+        if self.cfg.loss == lk.HUBER:
+            return solve_link(A, t, d["threshold"], self.weights(d), L_of(d, self.cfg), self.KKT_TOL)
+        return ws.solve(A, t, self.weights(d), ITERS, loss=self.cfg.loss, w=w, L=L_of(d, self.cfg), kkt_tol=self.KKT_TOL, max_fraction=1.0)
+
+    def check(self, d, out):
+        ref = self.ref(d)
+        assert (int(out["rounds"]), list(out["sizes"]), int(out["grads"]), bool(out["fell_back"])) == \
+            (int(ref["rounds"]), list(ref["sizes"]), int(ref["grads"]), False), (out, ref)
+        for i in range(self.COUNT):
+            _rel_ok(out["x"][i], ref["x"][i], (self.name, i))
+
+
+def solve_link(A, b, c, weights, L, kkt_tol):
+    """tests/_working_set.solve for the Huber loss (one group, from the scan at 0, no fall-back): the gradient of the data term is
+    tests/_link.gradient and a round is tests/_link.run's loop from the set's current values."""
+    n, nv = A.shape[1], len(weights)
+    a1s = [a for a, _ in weights]
+    X = np.zeros((n, nv))
+
+    def check(slack, mask):
+        return ws.scan(lk.gradient(lk.HUBER, A, X, b, c).T.astype(np.float32), a1s, slack, mask, np.ones(n))
+    mask = np.zeros(n, dtype=np.uint8)
+    excess, viol = check(0.0, mask)
+    grads, sizes, worst = 1, [], float(excess.max())
+    mask[viol] = 1
+    while mask.any():
+        idx = np.nonzero(mask)[0]
+        sizes.append(int(idx.size))
+        for j, (a1, a2) in enumerate(weights):
+            prob = lk.LinkProblem(lk.HUBER, A[:, idx], b, a1, a2, c)
+            st = prob.init_state(L)
+            st.x, st.x_old, st.y = X[idx, j].copy(), X[idx, j].copy(), X[idx, j].copy()
+            for _ in range(ITERS):
+                prob.step(st)
+            X[idx, j] = st.x
+        excess, viol = check(kkt_tol, mask)
+        grads, worst = grads + 1, float(excess.max())
+        if viol.size == 0:
+            break
+        mask[viol] = 1
+        want = int(idx.size)                                         # grow = 2
+        if viol.size < want:
+            order = np.argsort(-excess.astype(np.float64), kind="stable")[:want]
+            mask[order[excess[order] > 0]] = 1
+    return X, dict(rounds=len(sizes), sizes=sizes, full_gradients=grads, worst_excess=worst, fell_back=False)
+
+
+W, COORD, GROUPS = PLAIN._replace(weights=True), PLAIN._replace(coord=True), PLAIN._replace(groups=True)
+LOGIT, HUBER, HINGE_W = PLAIN._replace(loss="logistic"), PLAIN._replace(loss="huber"), W._replace(loss="squared_hinge")
+M3, M7G = PLAIN._replace(loss="multinomial", classes=3), PLAIN._replace(loss="multinomial", classes=7, grouped=True)
+
+CELLS = collections.OrderedDict((c.name, c) for c in (
+    Path("path16", PLAIN, 16), Path("path3", PLAIN, 3), Rhs("rhs5", PLAIN), Single("single", PLAIN), Cv("cv", PLAIN, 3, 4),
+    Lbfgs("lbfgs3", PLAIN), Power("power", PLAIN),
+    Path("weights_path5", W, 5), Lipschitz("weights_lipschitz", W),
+    Path("factors_path16", COORD, 16),
+    Path("groups_path3", GROUPS, 3), Cv("groups_cv", GROUPS, 3, 2),
+    Path("logistic_path16", LOGIT, 16), Objective("logistic_objective5", LOGIT, 5),
+    Cv("logistic_weights_factors_cv", LOGIT._replace(weights=True, coord=True), 2, 3),
+    Path("huber_path5", HUBER, 5), Objective("huber_objective16", HUBER, 16),
+    Cv("hinge_weights_cv", HINGE_W, 2, 3),
+    Path("multinomial3_path5", M3, 5), Objective("multinomial3_objective5", M3, 5),
+    Path("multinomial7_grouped_path2", M7G, 2),
+    WorkingSet("working_set", PLAIN), WorkingSet("working_set_huber", HUBER), KktExcess("kkt_excess", PLAIN),
+    Controlled("controlled"),
+))
+LOCKSTEP_ENTRY_POINTS = ("fos_fista_run_multi", "fos_fista_run_multi_rhs", "fos_fista_run_multi_folds", "fos_residual_batch",
+                         "fos_residual_batch_rhs", "fos_residual_batch_folds", "fos_gradient_batch", "fos_gather_columns",
+                         "fos_kkt_scan", "fos_power_iter")
+MAY_DECLINE = {"fos_fista_run_multi", "fos_fista_run_multi_rhs", "fos_fista_run_multi_folds", "fos_residual_batch_rhs",
+               "fos_residual_batch_folds", "fos_lbfgs_minimize_multi"}
+PAIRS = [(x, y) for x in CELLS for y in CELLS if x != y]
+PANEL_PAIRS = [(x, y) for x, y in PAIRS if CELLS[x].sized_by_panels or CELLS[y].sized_by_panels]
+# the same call at another width on one handle: (wide, narrow) per configuration; C = 7 with two fits fills 14 columns, C = 3 with
+# five fits 15
+_NARROW = [Path("factors_path3", COORD, 3), Path("logistic_path3", LOGIT, 3), Path("multinomial7_path2", M7G._replace(grouped=False), 2)]
+ALL_CELLS = dict(CELLS, **{c.name: c for c in _NARROW})
+WIDTHS = {"plain": ("path16", "path3"), "factors": ("factors_path16", "factors_path3"), "logistic": ("logistic_path16", "logistic_path3"),
+          "multinomial": ("multinomial7_path2", "multinomial3_path5")}
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(cell, name, kind, cus):
+    """The fp64 reference of a cell, computed once and never modified."""
+    return _frozen(ALL_CELLS[cell].reference(data(name, kind, cus)))

@@ -1,0 +1,197 @@
+"""GPU: every ordered pair of lockstep configurations on ONE problem handle (tests/_handle_pairs.py has the cells, the moves and
+the fp64 references; tests/test_handle_pairs.py checks that table on the CPU).
+
+fos_problem_set_loss / _set_link_loss / _set_multinomial, fos_row_weights_bind and fos_coord_bind say "nothing to invalidate",
+fos_feature_groups_bind and fos_problem_replan re-bind or drop buffers beside the bindings that stay, and every lockstep call of a
+handle shares its workspace.  Four parts, per storage type (f32, bf16):
+
+1. each cell on a fresh handle: served (asserted), within the project's 1e-5 of its fp64 reference (the sums within the bounds of
+   their fp32 passes), and a second fresh handle gives the same bits - the precondition of everything below;
+2. every ordered pair (X, Y), X != Y: configure(X), call(X), move(X, Y), call(Y), move(Y, X), call(X) on one handle; Y's result
+   and the second X's are bit for bit those of the fresh handles, and after each move the getters report the configuration just
+   set.  All 600 pairs at the padded shape; at the two-panel shape the pairs in which X or Y is a CV, objective, working-set or
+   multinomial cell (buffers sized by the panel count);
+3. a replan with the bindings in place: call(X), move(X, Y), replan(), call(Y) gives the fresh bits, replan(interleave=True)
+   stays within 1e-5 of the reference where the plan then deals the rows round-robin (at these shapes it does not: the fresh
+   bits), and back gives the fresh bits again; the getters still report Y;
+4. the same call at another width: path 16 -> path 3 -> path 16 on the plain, factor and logistic configurations, C = 7 (14
+   columns) -> C = 3 (15 columns) -> C = 7 on the multinomial one.
+
+No pair comparison has a tolerance and nothing skips.  25 cells (28 with the narrow twins of part 4), 600 ordered pairs per
+storage type at the padded shape and 444 at the two-panel shape; the 328 tests take 28 s on the MI355X.
+
+What fails when the library is wrong (five temporary edits, each run against this file on the MI355X).  No defect was found, and
+four of the five edits change no bit - each removes one of two layers that keep an unused column harmless:
+- xp_pack_kernel / xq_pack_kernel copy columns j >= nv of the caller's block: nothing fails, and nothing can from Python -
+  Problem._block16 hands the library an n_dev x 16 block that is zero beyond nv, so the copy writes the same zeros;
+- softmax_link_kernel and pointwise_link_kernel leave columns >= nv of the panel as they came in: nothing fails - the lockstep
+  zeroes the candidate block at every call and writes y into columns < nv only, so product 1 leaves exact zeros there for a
+  link loss (Z = A Y, no b), and the updates read columns < nv of product 2 alone;
+- fos_problem_set_loss keeps link_param: nothing fails, and nothing can - the parameter is read on a Huber or squared-hinge
+  handle only (fos_problem_get_link_loss answers 0 otherwise), and the one way to such a handle, fos_problem_set_link_loss, sets
+  it;
+- stage_b16_kernel leaves columns >= nv of ws.b16 unwritten: nothing fails - those columns of R, of the slabs and of the sums
+  are whatever the allocation held, and every reader (updates, q_part) is bounded by nv: columns never meet in either product;
+- no memset of the candidate block in run_multi_mfma (the edit of tests/test_gpu_cluster_planned.py): 207 of the 328 tests
+  fail, 57 of them in part 1 (first test_cell_on_a_fresh_handle[path16-panels-bf16]) with NaN iterates against the reference -
+  the rows n .. n_pad of the block and the columns >= nv keep what the allocation held."""
+import time
+
+import pytest
+import torch
+
+from tests import _handle_pairs as hp
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def fos():
+    import fastoptsolver_amd as f
+    assert torch.cuda.is_available()
+    torch.cuda.set_device(0)
+    return f
+
+
+class Bench:
+    """The contexts and the fresh results of the module: one device matrix per (shape, storage type), one result per cell."""
+
+    def __init__(self, fos):
+        self.fos, self.ctxs, self.results = fos, {}, {}
+        self.cus = fos.prepare(torch.zeros(8, 8, device="cuda")).plan()["cus"]
+
+    def ctx(self, name, kind):
+        if (name, kind) not in self.ctxs:
+            self.ctxs[(name, kind)] = hp.Ctx(self.fos, hp.data(name, kind, self.cus))
+        return self.ctxs[(name, kind)]
+
+    def on_fresh(self, c, cell):
+        P = c.fresh()
+        c.move(P, hp.PLAIN, cell)
+        c.check_getters(P, cell.cfg, ("fresh", cell.name))
+        return c.run(cell, P)
+
+    def fresh(self, name, kind, cell):
+        """The result of the cell on a fresh handle, checked against its fp64 reference; computed once per module."""
+        key = (name, kind, cell.name)
+        if key not in self.results:
+            c = self.ctx(name, kind)
+            out = self.on_fresh(c, cell)
+            cell.check(c.d, out)
+            self.results[key] = out
+        return self.results[key]
+
+
+@pytest.fixture(scope="module")
+def bench(fos):
+    t0 = time.perf_counter()
+    b = Bench(fos)
+    yield b
+    torch.cuda.synchronize()
+    print(f"\nhandle pairs: {len(b.results)} fresh results, {time.perf_counter() - t0:.1f} s in all")
+    b.ctxs.clear()
+    b.results.clear()
+    hp.data.cache_clear()
+    hp._reference.cache_clear()
+    torch.cuda.empty_cache()
+
+
+_differs = hp.same_bits
+
+
+# ---- 1. each cell on a fresh handle ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", hp.KINDS)
+@pytest.mark.parametrize("shape", hp.SHAPES)
+@pytest.mark.parametrize("cell", list(hp.ALL_CELLS))
+def test_cell_on_a_fresh_handle(bench, cell, shape, kind):
+    c, cl = bench.ctx(shape, kind), hp.ALL_CELLS[cell]
+    if shape == "padded":
+        assert (c.d["m"], c.d["n"]) == hp.PADDED
+        P = c.fresh()
+        assert P.n == 37 and P.n_dev == (72 if kind == "bf16" else 68) and P.sample_weight is None
+    first = bench.fresh(shape, kind, cl)                   # served, and within the bounds of its fp64 reference
+    again = bench.on_fresh(c, cl)
+    assert _differs(again, first) is None, (cell, _differs(again, first))
+
+
+# ---- 2. every ordered pair -----------------------------------------------------------------------------------------------------------
+def _pair(bench, c, shape, kind, x, y):
+    """The six steps of a pair on one handle; the list of what differed from the fresh handles."""
+    X, Y = hp.CELLS[x], hp.CELLS[y]
+    fx, fy = bench.fresh(shape, kind, X), bench.fresh(shape, kind, Y)
+    P = c.fresh()
+    c.move(P, hp.PLAIN, X)
+    bad = []
+    for step, (cell, want, move) in enumerate(((X, fx, None), (Y, fy, (X, Y)), (X, fx, (Y, X)))):
+        if move is not None:
+            c.move(P, *move)
+            c.check_getters(P, cell.cfg, (x, y, step))
+        d = _differs(c.run(cell, P), want)
+        if d is not None:
+            bad.append((f"{x} -> {y}", ("first X", "Y after X", "X after Y")[step], d))
+    return bad
+
+
+@pytest.mark.parametrize("kind", hp.KINDS)
+@pytest.mark.parametrize("x", list(hp.CELLS))
+def test_every_ordered_pair_at_the_padded_shape(bench, x, kind):
+    c = bench.ctx("padded", kind)
+    bad = [b for (a, y) in hp.PAIRS if a == x for b in _pair(bench, c, "padded", kind, x, y)]
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("kind", hp.KINDS)
+@pytest.mark.parametrize("x", list(hp.CELLS))
+def test_the_pairs_of_the_panel_sized_buffers_at_the_two_panel_shape(bench, x, kind):
+    c = bench.ctx("panels", kind)
+    assert c.d["m"] > 256 * bench.cus                      # two row panels, the second short
+    bad = [b for (a, y) in hp.PANEL_PAIRS if a == x for b in _pair(bench, c, "panels", kind, x, y)]
+    assert not bad, bad
+
+
+# ---- 3. a replan with the bindings in place ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", hp.KINDS)
+@pytest.mark.parametrize("shape", hp.SHAPES)
+@pytest.mark.parametrize("y", list(hp.CELLS))
+def test_replan_with_the_bindings_in_place(bench, y, shape, kind):
+    c, Y = bench.ctx(shape, kind), hp.CELLS[y]
+    X = hp.CELLS["huber_path5" if Y.cfg.loss == "logistic" else "logistic_path16"]        # a cell of another loss
+    assert X.cfg.loss != Y.cfg.loss
+    fy = bench.fresh(shape, kind, Y)
+    P = c.fresh()
+    c.move(P, hp.PLAIN, X)
+    c.run(X, P)
+    c.move(P, X, Y)
+    P.replan()
+    c.check_getters(P, Y.cfg, (y, "replan"))
+    out = c.run(Y, P)
+    assert _differs(out, fy) is None, (y, "after replan()", _differs(out, fy))
+    P.replan(interleave=True)
+    c.check_getters(P, Y.cfg, (y, "interleave"))
+    out = c.run(Y, P)
+    if P.plan()["interleave"]:                             # the row order changes the summation: the reference's bounds
+        Y.check(c.d, out)
+    else:                                                  # the planner does not deal these rows round-robin: the same sums
+        assert _differs(out, fy) is None, (y, "after replan(interleave=True)", _differs(out, fy))
+    P.replan(interleave=False)
+    c.check_getters(P, Y.cfg, (y, "back"))
+    out = c.run(Y, P)
+    assert _differs(out, fy) is None, (y, "after replan(interleave=False)", _differs(out, fy))
+
+
+# ---- 4. the same call at another width -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", hp.KINDS)
+@pytest.mark.parametrize("shape", hp.SHAPES)
+@pytest.mark.parametrize("config", list(hp.WIDTHS))
+def test_the_same_call_at_another_width(bench, config, shape, kind):
+    c = bench.ctx(shape, kind)
+    wide, narrow = (hp.ALL_CELLS[n] for n in hp.WIDTHS[config])
+    fw, fn = bench.fresh(shape, kind, wide), bench.fresh(shape, kind, narrow)
+    P = c.fresh()
+    at = hp.PLAIN
+    for cell, want in ((wide, fw), (narrow, fn), (wide, fw), (narrow, fn)):
+        c.move(P, at, cell)
+        at = cell.cfg
+        c.check_getters(P, cell.cfg, (config, cell.name))
+        out = c.run(cell, P)
+        assert _differs(out, want) is None, (config, cell.name, _differs(out, want))
