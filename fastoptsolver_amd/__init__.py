@@ -20,6 +20,9 @@ from ._core import prepare_hinge, prepare_huber                                 
 from .robust import (HingeCVResult, HuberCVResult, hinge_cv, hinge_objective, hinge_path,            # noqa: F401
                      huber_cv, huber_objective, huber_path)
 
+# the duality-gap certificate and the gap-stopped path: importable from the package likewise
+from .duality import DualityGap, GapInfo, certified_path, duality_gap                                # noqa: F401
+
 __all__ = ["fista", "fista_delta", "fista_path", "fista_cv", "CVResult", "ista", "estimate_lipschitz", "reset_metrics", "get_metrics", "LBFGSSolver",
            "compute_objective", "prox_l1", "prox_elastic_net", "LeastSquares", "L1Prox", "ElasticNetProx",
            "prepare", "prepare_weighted", "prepare_penalized", "Problem", "FosError", "logistic_path", "logistic_cv", "logistic_objective", "LogisticCVResult",

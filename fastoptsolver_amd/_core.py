@@ -787,6 +787,20 @@ class Problem:
                        "fos_kkt_scan")
         return excess, viol[: int(count.item())]
 
+    # ---- duality-gap certificate (include/fos_duality.h; duality.py drives this) ---------------------------------------
+    def duality_gap_block(self, X, alpha1, alpha2):
+        """The duality-gap certificate of the nv <= 16 columns of X (n x nv) under the host weights alpha1, alpha2 (nv each;
+        fos_duality_gap): (out64 - 64 device doubles: primal[16], dual[16], gap[16], scale[16] -, G - the nv x n_dev float32
+        gradient block of `gradient_block` at X, from the same pass).  Enqueues only."""
+        Xf, nv = self._block16(X)
+        a1 = (C.c_double * nv)(*[float(a) for a in alpha1])
+        a2 = (C.c_double * nv)(*[float(a) for a in alpha2])
+        G = torch.empty(nv, self.n_dev, dtype=torch.float32, device=self.device)
+        out64 = torch.empty(64, dtype=torch.float64, device=self.device)
+        with self.ctx():
+            _lib.check(self.lib.fos_duality_gap(ptr(Xf), nv, a1, a2, self.h, ptr(G), ptr(out64)), "fos_duality_gap")
+        return out64, G
+
     def power_iter(self, v0, n_iter=100, tol=1e-6):
         """The reference's power iteration (ref:45-60) from v0 (n values, need not be normalised): ``(L, it, v)``.  On every
         plan ``it`` is the step at which ``|L_k - L_{k-1}| < tol`` fired (``n_iter`` when it never did), ``L`` the norm of that

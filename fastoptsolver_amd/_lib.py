@@ -182,6 +182,12 @@ LINK_LOSS_SIGNATURES = {
 }
 
 
+# include/fos_duality.h: the duality-gap certificate of lockstep solutions
+DUALITY_SIGNATURES = {
+    "fos_duality_gap": (_i32, [_vp, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp, _vp]),
+}
+
+
 def load():
     """Return the loaded CDLL (cached).  Raises FosError if the library is absent."""
     global _lib
@@ -192,7 +198,8 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension is the only compute path of fastoptsolver_amd.\n"
             "Build it with:  python -m fastoptsolver_amd.build   (needs hipcc; cross-compiles for gfx950)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **FEATURE_GROUP_SIGNATURES, **WORKING_SET_SIGNATURES, **LINK_LOSS_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **FEATURE_GROUP_SIGNATURES, **WORKING_SET_SIGNATURES, **LINK_LOSS_SIGNATURES,
+                              **DUALITY_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -4,6 +4,7 @@
 #include "fused_step.hpp"
 #include "chip_resident.hpp"
 #include "working_set.hpp"
+#include "duality.hpp"
 #include <cassert>
 
 using namespace fosapi;
@@ -1666,6 +1667,89 @@ int fos_kkt_scan(const float* G, int nv, const double* alpha1, double slack, con
     return fail(FOS_ERR_UNSUPPORTED, "fos_kkt_scan: a multinomial problem is not served (squared and logistic loss)");
   hipLaunchKernelGGL(fos::kkt_scan_kernel, dim3(1), dim3(fos::KS_THREADS), 0, p->stream, G, p->n, nv, w, 1.0 + slack, in_ws,
                      p->coord_factor, excess, viol_idx, viol_count);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
+}  // extern "C"
+
+// ---- Duality-gap certificate (include/fos_duality.h, duality.hpp) -----------------------------------------------------------
+// The row pass on the `rows` rows of p->multi.rbuf16 that product 1 in its plain storing form has just filled with Z of the panel
+// starting at row0: one lane per 16-byte quad of a row, grid-stride, at most 2 * ncu workgroups; *nwg_out = the rows of `part`
+// written.
+static int launch_dual_link(fos_problem* p, int64_t row0, int64_t rows, int nv, const double* scale, double* part, int* nwg_out) {
+  const int nwg = (int)std::min<int64_t>((4 * rows + fos::DL_THREADS - 1) / fos::DL_THREADS, 2 * (int64_t)p->ncu);
+  const float* w = p->row_weight ? p->row_weight + row0 : nullptr;
+  const float c = (float)p->link_param;
+#define FOS_DUAL(K, W)                                                                                                      \
+  hipLaunchKernelGGL((fos::dual_link_kernel<fos::K, W>), dim3(nwg), dim3(fos::DL_THREADS), 0, p->stream,                   \
+                     (const float*)p->multi.rbuf16.get(), rows, p->b + row0, c, nv, w, scale, part)
+#define FOS_DUAL_FORM(K) { if (w) FOS_DUAL(K, true); else FOS_DUAL(K, false); }
+  switch (p->loss) {
+    case FOS_LOSS_SQUARED: FOS_DUAL_FORM(DUAL_SQUARED) break;
+    case FOS_LOSS_LOGISTIC: FOS_DUAL_FORM(DUAL_LOGISTIC) break;
+    case FOS_LOSS_HUBER: FOS_DUAL_FORM(DUAL_HUBER) break;
+    case FOS_LOSS_SQUARED_HINGE: FOS_DUAL_FORM(DUAL_SQUARED_HINGE) break;
+    default: return fail(FOS_ERR_STATE, "launch_dual_link: the loss has no conjugate here");
+  }
+#undef FOS_DUAL_FORM
+#undef FOS_DUAL
+  LAUNCH_CHECK();
+  *nwg_out = nwg;
+  return FOS_OK;
+}
+
+extern "C" {
+
+int fos_duality_gap(const float* X, int nv, const double* alpha1, const double* alpha2, fos_problem* p, float* G, double* out64) {
+  if (!X || !alpha1 || !alpha2 || !p || !G || !out64 || nv < 1 || nv > fos::BT_NV)
+    return fail(FOS_ERR_ARG, "fos_duality_gap: bad argument (null pointer or nv outside 1..16)");
+  fos::DualWeights wts{};
+  for (int j = 0; j < nv; ++j) {
+    if (!(std::isfinite(alpha1[j]) && alpha1[j] >= 0.0 && std::isfinite(alpha2[j]) && alpha2[j] >= 0.0))
+      return fail(FOS_ERR_ARG, "fos_duality_gap: weight " + std::to_string(j) + " is not finite and >= 0");
+    wts.a1[j] = alpha1[j];
+    wts.a2[j] = alpha2[j];
+  }
+  if (p->loss == FOS_LOSS_MULTINOMIAL)
+    return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: a multinomial problem is not served (squared, logistic, Huber and squared-hinge loss)");
+  if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: the certificate needs b");
+  if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: sharded problems are not served");
+  if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: the shape has no matrix-core pair");
+  if (p->coord_lo || p->coord_hi)
+    return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: box bounds (fos_coord_bind) are bound; the penalty of a bounded coordinate has "
+                                     "another conjugate");
+  if (has_fgroups(p))
+    return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: feature groups (fos_feature_groups_bind) are bound; the group norm has another "
+                                     "conjugate");
+  // 1. the gradient block, by the launches of fos_gradient_batch (it plans the lockstep and leaves X packed in cand.xp)
+  int rc = fos_gradient_batch(X, nv, p, G, nullptr);
+  if (rc) return rc;
+  const int64_t panels = (p->m + p->multi.panel_rows - 1) / p->multi.panel_rows;
+  const size_t part_rows = (size_t)panels * 2 * (size_t)p->ncu;
+  if ((rc = p->ws.dual_part.reserve(part_rows * fos::DL_WIDTH))) return rc;
+  if ((rc = p->ws.dual_col.reserve(3 * fos::BT_NV))) return rc;
+  // 2. the column pass: the scale of every column, then its penalty and the conjugate of the ridge-carrying coordinates
+  hipLaunchKernelGGL(fos::dual_scale_kernel, dim3(nv), dim3(fos::DS_THREADS), 0, p->stream, X, (const float*)G, p->n, wts,
+                     p->coord_factor, p->ws.dual_col.get());
+  LAUNCH_CHECK();
+  // 3. Z = A_panel X once more (plain: no b, no weights, no mask), and the row pass on it
+  const int64_t esz = p->dtype == FOS_BF16 ? 2 : 4;
+  int nparts = 0;
+  for (int64_t row0 = 0; row0 < p->m; row0 += p->multi.panel_rows) {
+    const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
+    int nwg1 = 0, nwg = 0;
+    BatchLaunch L{};
+    L.A = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz; L.rows = rows; L.rout = p->multi.rbuf16;
+    if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
+    if ((size_t)nparts + 2 * (size_t)p->ncu > part_rows)
+      return fail(FOS_ERR_STATE, "fos_duality_gap: the row pass has more panels than its partial buffer holds");
+    if ((rc = launch_dual_link(p, row0, rows, nv, p->ws.dual_col, p->ws.dual_part + (size_t)nparts * fos::DL_WIDTH, &nwg))) return rc;
+    nparts += nwg;
+  }
+  // 4. the finish
+  hipLaunchKernelGGL(fos::dual_finish_kernel, dim3(1), dim3(fos::DF_THREADS), 0, p->stream, (const double*)p->ws.dual_part.get(), nparts,
+                     (const double*)p->ws.dual_col.get(), nv, out64);
   LAUNCH_CHECK();
   return FOS_OK;
 }
