@@ -22,7 +22,8 @@ import re
 
 import numpy as np
 
-from tests import _coord as cd, _data, _fgroup as fg, _logit as lg, _menu_multi as mm, _weighted as wt
+from oracle import fos_oracle as orc
+from tests import _coord as cd, _data, _duality as du, _fgroup as fg, _logit as lg, _menu_multi as mm, _weighted as wt
 from tests._menu_product1 import FISTA, PLAN, _body, _text
 
 ITERS = 12
@@ -207,6 +208,63 @@ GROUP_FRACTIONS = ((0.5, 0.0), (0.25, 0.5), (0.08, 0.0))
 def group_alphas(d, start, gw, mu):
     amax = fg.alpha_max(d["A"].T @ d["b"], start, fg.weights_of(start, gw), mu)
     return [(f * amax, a2) for f, a2 in GROUP_FRACTIONS]
+
+
+# ---- the duality-gap certificate -------------------------------------------------------------------------------------------------
+CERT_COLUMNS = 16
+CERT_ZERO = 0                             # the all-zero column
+CERT_ITERATES = (2, 3, 5)                 # the columns of the plain path's iterates: lasso columns (see certificate_case)
+CERT_CELLS = {"gap": ("squared", False), "weighted_logistic_gap": ("logistic", True)}
+
+
+@functools.lru_cache(maxsize=None)
+def certificate_case(name, cell):
+    """What a certificate cell is asked for on the shape, computed once and never modified: dict(loss, t, w, X - n x 16, as the
+    device takes it: fp32 values in fp64 -, alphas).  Column 0 is all zero, columns 2, 3 and 5 are the iterates of the plain path's
+    reference (the oracle's FISTA on b with the first, middle and last of plain_alphas), the others a seeded sparse block scaled so
+    that A x is of order 1.  The iterates sit in lasso columns: the first of them, in the elastic-net column 1, is so close to
+    that column's own optimum (a gap of 8.8e-4 of its terms' magnitude on cs4) that the gap would not stand clear of rounding.  The weights are a ladder from a half to a fiftieth of the configuration's alpha_max, every third an
+    elastic net: the certificate of a lasso column has a scale below 1, that of an elastic-net column the scale 1."""
+    d = data(name)
+    loss, weighted = CERT_CELLS[cell]
+    t, w = target(d, loss), (d["w"] if weighted else None)
+    rng = np.random.default_rng(950 + d["seed"])
+    X = 0.05 * rng.standard_normal((d["n"], CERT_COLUMNS)) * (rng.random((d["n"], CERT_COLUMNS)) < 0.1)
+    X[:, CERT_ZERO] = 0.0
+    weights = plain_alphas(d)
+    for col, i in zip(CERT_ITERATES, picks(len(weights))):
+        X[:, col] = orc.fista(d["A"], d["b"], "elasticnet", *weights[i], max_iter=ITERS, L=d["L"])
+    amax = float(np.abs(du.gradient(loss, d["A"], np.zeros((d["n"], 1)), t, None, w)).max())
+    ratio = (0.02 / 0.5) ** (1.0 / (CERT_COLUMNS - 1))
+    alphas = [(amax * 0.5 * ratio ** i, 0.5 if i % 3 == 1 else 0.0) for i in range(CERT_COLUMNS)]
+    return _frozen(dict(loss=loss, t=t, w=w, X=X.astype(np.float32).astype(np.float64), alphas=alphas))
+
+
+def check_certificate_case(name, cell, G=None):
+    """The preconditions of a certificate cell on its fp64 certificate: a scale inside (0, 1) and the scale 1, every value finite,
+    and the gap of every non-zero column far above what the fp32 passes can move it by - a gap made of rounding noise would let a
+    wrong dual pass.  G: the fp64 gradient block, n x 16, where it is at hand.  Returns the certificate."""
+    d, cs = data(name), certificate_case(name, cell)
+    ref = du.certificate(cs["loss"], d["A"], cs["t"], cs["X"], cs["alphas"], None, cs["w"], G=None if G is None else G.T)
+    s, live = ref["scale"], np.arange(CERT_COLUMNS) != CERT_ZERO
+    assert ((s > 0) & (s < 1)).any() and (s == 1).any(), s
+    assert all(np.isfinite(ref[k]).all() for k in ("primal", "dual", "gap", "scale"))
+    assert (ref["gap"][live] > 100.0 * du.TOL * ref["mag_gap"][live]).all(), ref["gap"] / ref["mag_gap"]
+    assert (cs["X"][:, CERT_ZERO] == 0).all() and (cs["X"][:, 1:] != 0).any(axis=0).all()
+    return ref
+
+
+@functools.lru_cache(maxsize=None)
+def certificate_gradient(name, cell):
+    """(the fp64 gradient block of a certificate cell, n x 16, the bound of a column of the device's in the 2-norm - that of
+    fos_gradient_batch, the pass on sqrt(w) A), computed once with the preconditions of the case."""
+    d, cs = data(name), certificate_case(name, cell)
+    G = du.gradient(cs["loss"], d["A"], cs["X"], cs["t"], None, cs["w"])
+    check_certificate_case(name, cell, G)
+    sw = np.ones(d["m"]) if cs["w"] is None else np.sqrt(cs["w"])
+    g_tol, _ = _data.fp32_pass_tolerances_cols(sw[:, None] * d["A"], cs["X"], sw * np.abs(cs["t"]), G, np.ones(CERT_COLUMNS))
+    G.setflags(write=False)
+    return G, g_tol
 
 
 # ---- the device-controlled case ------------------------------------------------------------------------------------------------

@@ -14,7 +14,8 @@ One data set per (shape, storage type), shared by every cell: one seeded Gaussia
 loss - b with a tenth of gross outliers (tests/_link.huber_recipe) for the squared and Huber cells, labels of the planted model
 in {0, 1} (tests/_logit.labels) and in {-1, +1} (tests/_link.hinge_recipe), class indices for C = 3 and C = 7
 (tests/_multinomial.labels) - "counts" row weights (tests/_weighted.weights), penalty factors with exact zeros
-(tests/_coord.factors) under the lower bound 0, and the "weights" group layout (tests/_fgroup.layout: seeded sizes 1..7, every
+(tests/_coord.factors) under the lower bound 0 - and the same factors with FREE_FACTOR in place of the zeros and no bound, the
+configuration with factors that the duality-gap certificate serves -, and the "weights" group layout (tests/_fgroup.layout: seeded sizes 1..7, every
 sixth group of weight 0).  The handle BORROWS b (fos.h: "the caller's: never freed here"), so a cell of another loss overwrites the
 bound device vector in place; anything that cached a function of b would show.
 
@@ -33,9 +34,9 @@ import re
 import numpy as np
 
 from oracle import fos_oracle as orc
-from tests import (_coord as cd, _data, _fgroup as fg, _forms, _group as gp, _link as lk, _logit as lg, _menu_cv as mcv,
+from tests import (_coord as cd, _data, _duality as du, _fgroup as fg, _forms, _group as gp, _link as lk, _logit as lg, _menu_cv as mcv,
                    _menu_multi as mm, _multinomial as mn, _weighted as wt, _working_set as ws)
-from tests._menu_product1 import CSRC, PLAN, _body, _text
+from tests._menu_product1 import CSRC, FISTA, PLAN, _body, _text
 
 ITERS = 12
 TOL = lg.TOL                              # the project's standing 1e-5 of the lockstep against the fp64 oracle
@@ -61,8 +62,11 @@ def shape(name, kind, cus=mm.GPU_CUS):
 
 
 # ---- configurations ------------------------------------------------------------------------------------------------------------
-Config = collections.namedtuple("Config", "loss classes grouped weights coord groups", defaults=("squared", 0, False, False, False, False))
+# coord: "" (nothing bound), "bounds" (penalty factors with exact zeros under the lower bound 0) or "factors" (strictly positive
+# penalty factors and no bound: what the certificate serves)
+Config = collections.namedtuple("Config", "loss classes grouped weights coord groups", defaults=("squared", 0, False, False, "", False))
 PLAIN = Config()
+FREE_FACTOR = 0.5                         # what the exact zeros of the penalty factors become under "factors"
 TARGET = {"squared": "b", "huber": "b", "logistic": "y01", "squared_hinge": "ysign"}
 LOSS_IDS = {"squared": 0, "logistic": 1, "multinomial": 2, "huber": 3, "squared_hinge": 4}     # include/fos.h, fos_link_loss.h
 SETTER = {"squared": "fos_problem_set_loss", "logistic": "fos_problem_set_loss", "multinomial": "fos_problem_set_multinomial",
@@ -77,7 +81,8 @@ def plan_move(X, Y):
     """The steps from configuration X to Y as (entry point or "target" / "grouped", argument) pairs: only what differs, in the
     order the refusal rules of csrc/fos_plan.hip allow - feature groups come off before factors or the multinomial loss go on,
     factors come off before feature groups go on, the loss leaves multinomial before feature groups are bound.  Bindings that X
-    and Y share stay bound."""
+    and Y share stay bound; between "bounds" and "factors" fos_coord_bind is called once, with the vectors of Y (Ctx.apply takes
+    them from Y's configuration: the step itself says bind or detach, which is all the refusal rules ask)."""
     steps = []
     if X.groups and not Y.groups:
         steps.append(("fos_feature_groups_bind", False))
@@ -89,7 +94,7 @@ def plan_move(X, Y):
         steps.append((SETTER[Y.loss], (Y.loss, Y.classes)))
     if X.weights != Y.weights:
         steps.append(("fos_row_weights_bind", Y.weights))
-    if Y.coord and not X.coord:
+    if Y.coord and X.coord != Y.coord:
         steps.append(("fos_coord_bind", True))
     if Y.groups and not X.groups:
         steps.append(("fos_feature_groups_bind", True))
@@ -108,7 +113,7 @@ class HostModel:
     matrix-core pair) hold for every handle of these tests and are not modelled."""
 
     def __init__(self, cfg=PLAIN):
-        self.loss, self.coord, self.groups = cfg.loss, cfg.coord, cfg.groups
+        self.loss, self.coord, self.groups = cfg.loss, bool(cfg.coord), cfg.groups        # (factors with or without the bound: alike)
 
     def step(self, entry, arg):
         if entry == "fos_problem_set_multinomial" and self.groups:
@@ -205,14 +210,20 @@ def data(name, kind, cus=mm.GPU_CUS):
     assert w.max() <= WEIGHT_MAX and gw is not None and (gw == 0).any() and (gw > 0).any()
     v0 = np.random.default_rng(SEED + 1).standard_normal(n)
     L, Lw = float(orc.estimate_lipschitz(A64, v0=v0)), wt.estimate_lipschitz(A64, w, v0)
+    p = cd.factors(n, SEED)
     return _frozen(dict(name=name, kind=kind, cus=cus, m=m, n=n, A32=A32, A=A64, b=b, threshold=float(np.float32(np.median(np.abs(b)))),
                         y01=lg.labels(A, xt, SEED), ysign=ysign, y3=mn.labels(A, 3, SEED), y7=mn.labels(A, 7, SEED), w=w,
-                        p=cd.factors(n, SEED), lo=np.zeros(n), start=start, gw=gw, B=B, ids3=ids.astype(np.int64),
+                        p=p, pp=np.where(p == 0, FREE_FACTOR, p), lo=np.zeros(n), start=start, gw=gw, B=B, ids3=ids.astype(np.int64),
                         ids2=(ids % 2).astype(np.int64), L=L, Lw=Lw))
 
 
 def L_of(d, cfg):
     return d["Lw" if cfg.weights else "L"] / {"logistic": 4.0, "multinomial": 2.0}.get(cfg.loss, 1.0)
+
+
+def factors(d, cfg):
+    """The penalty factors of the configuration: None, d["p"] with its exact zeros, or d["pp"] without."""
+    return {"": None, "bounds": d["p"], "factors": d["pp"]}[cfg.coord]
 
 
 def parts(d, cfg, rows=None):
@@ -221,7 +232,7 @@ def parts(d, cfg, rows=None):
     w = d["w"] if cfg.weights else None
     if rows is not None:
         A, t, w = A[rows], t[rows], None if w is None else w[rows]
-    return A, t, w, (d["p"] if cfg.coord else None), (d["lo"] if cfg.coord else None)
+    return A, t, w, factors(d, cfg), (d["lo"] if cfg.coord == "bounds" else None)
 
 
 def gradient0(d, cfg):
@@ -247,7 +258,8 @@ def alphas(d, cfg, count):
     if cfg.groups:
         return ladder(fg.alpha_max(g0, d["start"], fg.weights_of(d["start"], d["gw"]), MU), count)
     if cfg.coord:
-        return ladder(float((np.abs(g0)[d["p"] > 0] / d["p"][d["p"] > 0]).max()), count)
+        p = factors(d, cfg)
+        return ladder(float((np.abs(g0)[p > 0] / p[p > 0]).max()), count)
     return ladder(float(np.abs(g0).max()), count, *((0.03, 0.003) if cfg.loss == lk.HINGE else ()))   # (weaker: both hinge branches)
 
 
@@ -290,7 +302,7 @@ def data_term(d, cfg, X, rows=None):
 
 def penalties(d, cfg, X, a1, a2):
     """The separable penalties of the columns of X (of the class groups for the multinomial loss) with the factors as bound."""
-    p = d["p"][:, None] if cfg.coord else 1.0
+    p = factors(d, cfg)[:, None] if cfg.coord else 1.0
     W = cfg.classes if cfg.loss == "multinomial" else 1
     l1 = (p * np.abs(X)).sum(axis=0).reshape(-1, W).sum(axis=1)
     return a1 * l1 + 0.5 * a2 * (p * X * X).sum(axis=0).reshape(-1, W).sum(axis=1)
@@ -324,8 +336,9 @@ class Ctx:
         P.set_sample_weight(None)
         return P
 
-    def apply(self, P, steps):
-        """The steps of plan_move on the handle, with the Python attributes the front ends read."""
+    def apply(self, P, steps, coord=""):
+        """The steps of plan_move on the handle, with the Python attributes the front ends read.  coord: what a binding step of
+        fos_coord_bind binds - the configuration's "bounds" or "factors"."""
         from fastoptsolver_amd import _lib
         d = self.d
         for entry, arg in steps:
@@ -337,7 +350,7 @@ class Ctx:
             elif entry == "fos_row_weights_bind":
                 P.set_sample_weight(self.wbuf[:d["m"]] if arg else None)
             elif entry == "fos_coord_bind":
-                P.set_penalty(*((np.array(d["p"]), np.array(d["lo"]), None) if arg else ()))
+                P.set_penalty(*(() if not arg else (np.array(d["pp"]),) if coord == "factors" else (np.array(d["p"]), np.array(d["lo"]), None)))
             elif entry == "fos_feature_groups_bind":
                 P.set_feature_groups(*((np.diff(d["start"]), np.array(d["gw"]), MU) if arg else (None,)))
             else:
@@ -354,7 +367,8 @@ class Ctx:
                 P.threshold = d["threshold"] if loss == lk.HUBER else None
 
     def move(self, P, X, Y):
-        self.apply(P, plan_move(X.cfg if isinstance(X, Cell) else X, Y.cfg if isinstance(Y, Cell) else Y))
+        X, Y = (c.cfg if isinstance(c, Cell) else c for c in (X, Y))
+        self.apply(P, plan_move(X, Y), Y.coord)
 
     def run(self, cell, P):
         """cell.call on the handle as host arrays, with the assertion that the cell was served: every answer of an entry point
@@ -398,10 +412,11 @@ class Ctx:
         want = dict(loss=LOSS_IDS[cfg.loss], link=LOSS_IDS[cfg.loss] if link else 0,
                     param=np.float64(d["threshold"]) if cfg.loss == lk.HUBER else 0.0, classes=cfg.classes,
                     weights=self.wbuf.data_ptr() if cfg.weights else None,
-                    coord=(P._coord[0].data_ptr(), P._coord[1].data_ptr(), None) if cfg.coord else (None, None, None),
+                    coord=(P._coord[0].data_ptr(), P._coord[1].data_ptr() if cfg.coord == "bounds" else None, None) if cfg.coord else (None, None, None),
                     ngroups=ngroups if cfg.groups else 0, mix=MU if cfg.groups else 0.0)
         assert g == want, (where, g, want)
-        assert (P.loss, P.classes or 0, bool(P.grouped), P.sample_weight is not None, P.has_coord, P.has_feature_groups) == tuple(cfg), where
+        assert (P.loss, P.classes or 0, bool(P.grouped), P.sample_weight is not None, P.has_coord, P.has_feature_groups) == \
+            tuple(cfg._replace(coord=bool(cfg.coord))), where
 
 
 # ---- cells -----------------------------------------------------------------------------------------------------------------------
@@ -477,7 +492,7 @@ class Path(Cell):
         X = ref["x"]
         flat = X.reshape(len(X), -1)
         assert all((x != 0).any() for x in flat) and (flat[0] == 0).any(), "the penalty must bite"
-        if self.cfg.coord:                                    # the lower bound binds and an unpenalised coordinate is in the model
+        if self.cfg.coord == "bounds":                        # the lower bound binds and an unpenalised coordinate is in the model
             A, t, w, p, _ = parts(d, self.cfg)
             unc = cd.run(A, t, *self.weights(d)[-1], L_of(d, self.cfg), ITERS, p=p, loss=self.cfg.loss, w=w)["x"]
             assert (unc < 0).any() and (X >= 0).all() and (X[:, d["p"] == 0] != 0).any()
@@ -876,7 +891,121 @@ def solve_link(A, b, c, weights, L, kkt_tol):
     return X, dict(rounds=len(sizes), sizes=sizes, full_gradients=grads, worst_excess=worst, fell_back=False)
 
 
-W, COORD, GROUPS = PLAIN._replace(weights=True), PLAIN._replace(coord=True), PLAIN._replace(groups=True)
+class DualityGap(Cell):
+    """The duality-gap certificate (fos_duality_gap) of the nv columns of a seeded block, one of them all zero, under the
+    configuration's weights: the gradient block by the launches of fos_gradient_batch, product 1 once more in its plain storing
+    form into multi.rbuf16, b and the row weights offset per panel, ws.dual_part sized by the panel count, ws.dual_col written by
+    one launch and read by the next.  The lasso columns get a scale below 1 (an iterate that is not optimal), the elastic-net
+    columns - every third - the scale 1 exactly: both arms of the scale and of the conjugate."""
+    reaches = ("fos_duality_gap", "fos_gradient_batch")
+    sized_by_panels = True
+    ZERO = 0                                  # the all-zero column (a lasso column at every width)
+
+    def __init__(self, name, cfg, nv):
+        super().__init__(name, cfg)
+        self.count = nv
+
+    def points(self, d):
+        X = block(d, self.count, self.count).copy()
+        X[:, self.ZERO] = 0.0
+        return X
+
+    def call(self, c, P):
+        weights = alphas(c.d, self.cfg, self.count)
+        out64, G = P.duality_gap_block(c.torch.as_tensor(self.points(c.d)), [a for a, _ in weights], [a for _, a in weights])
+        return dict(out=out64.reshape(4, 16), G=G)
+
+    def _case(self, d):
+        A, t, w, p, _ = parts(d, self.cfg)
+        return A, t, (d["threshold"] if self.cfg.loss == lk.HUBER else None), w, p
+
+    def reference(self, d):
+        A, t, c, w, p = self._case(d)
+        X = self.points(d)
+        ref = du.certificate(self.cfg.loss, A, t, X, alphas(d, self.cfg, self.count), c, w, p)
+        G = du.gradient(self.cfg.loss, A, X, t, c, w)
+        # a gradient column is off by no more than the column's bound in the 2-norm, as in KktExcess (the pass on sqrt(w) A)
+        sw = np.ones(d["m"]) if w is None else np.sqrt(w)
+        g_tol, _ = _data.fp32_pass_tolerances_cols(sw[:, None] * A, X, sw * np.abs(t), G, np.ones(self.count))
+        return dict(ref, G=G, g_tol=g_tol)
+
+    def precondition(self, d, ref):
+        s, live = ref["scale"], np.arange(self.count) != self.ZERO
+        assert ((s > 0) & (s < 1)).any() and (s == 1).any(), s              # both arms of the scale, and with them of the conjugate
+        # a gap made of rounding noise would let a wrong dual pass
+        assert (ref["gap"][live] > 100.0 * du.TOL * ref["mag_gap"][live]).all(), ref["gap"] / ref["mag_gap"]
+        assert all(np.isfinite(ref[k]).all() for k in ("primal", "dual", "gap", "scale"))
+        if self.cfg.coord:
+            assert self.cfg.coord == "factors" and (factors(d, self.cfg) > 0).all()      # an unpenalised coordinate: every scale 0
+
+    def check(self, d, out):
+        A, t, c, w, p = self._case(d)
+        nv, n, ref = self.count, d["n"], self.ref(d)
+        got, G = np.asarray(out["out"], dtype=np.float64), np.asarray(out["G"])
+        assert got.shape == (4, 16) and G.shape[0] == nv and G.dtype == np.float32
+        assert np.isfinite(got).all() and (got[:, nv:] == 0).all() and (G[:, n:] == 0).all(), (self.name, got[:, nv:])
+        err = np.linalg.norm(G[:, :n].T.astype(np.float64) - ref["G"], axis=0)
+        assert (err <= ref["g_tol"]).all(), (self.name, (err / ref["g_tol"]).max())
+        weights = alphas(d, self.cfg, nv)
+        on = du.certificate(self.cfg.loss, A, t, self.points(d), weights, c, w, p, G=G[:, :n])      # scale and conjugate from the returned G
+        for row, key in enumerate(("primal", "dual", "gap")):
+            assert (np.abs(got[row, :nv] - on[key]) <= du.TOL * on["mag_" + key]).all(), \
+                (self.name, key, (np.abs(got[row, :nv] - on[key]) / on["mag_" + key]).max())
+        assert np.abs(got[3, :nv] - du.scale_of(G[:, :n], p, weights)).max() <= 1e-12, (self.name, got[3, :nv])
+        assert np.array_equal(got[2, :nv], got[0, :nv] - got[1, :nv])
+
+
+class CertifiedPath(Cell):
+    """certified_path on the handle: a certificate at 0, then rounds on handles of their own over gathered columns
+    (fos_gather_columns), one fos_duality_gap per round on the full problem, and a scan of its gradient block (fos_kkt_scan).  The
+    reference is tests/_duality.certified with the same L; every decision of it - the stop rule per column, the scans, the growth
+    step - is further from its threshold than fp32 can move it (reference asserts so, at every shape it is computed for): the
+    stop rule by STOP_MARGIN of the magnitude of the gap's terms, the scans and the growth step by the WorkingSet cell's MARGIN
+    and GAP.  A tenth of the rows of b are gross outliers, so P* is 0.9 P(0) and the terms of a converged gap sum to 1.95 P(0) in
+    magnitude: a bound of gap_tol P(0) lies gap_tol / 1.95 of that magnitude from a gap of 0, which is within STOP_MARGIN for
+    certified_path's default 1e-4 and for 1e-3 alike.  GAP_TOL = 1e-2 is the first power of ten at which the rule can hold on this
+    data, and the weights (a ladder from 0.3 to 0.05 of alpha_max) are the first of three ladders tried, on the reference alone,
+    with which it does for both shapes and storage types: two rounds at the padded shape (30 columns, then all 37), one or two
+    at the two-panel shape with the top-k branch of the growth step, smallest margins 3.9e-3 / 4.1e-3 / 9.0e-3."""
+    reaches = ("fos_duality_gap", "fos_gradient_batch", "fos_gather_columns", "fos_kkt_scan")
+    sized_by_panels = True
+    COUNT, FRACTIONS, GAP_TOL, PATH_ITERS, ROUNDS = 5, (0.3, 0.05), 1e-2, ITERS, 20
+    STOP_MARGIN = 100.0 * du.TOL
+
+    def weights(self, d):
+        return ladder(float(np.abs(gradient0(d, self.cfg)).max()), self.COUNT, *self.FRACTIONS)
+
+    def call(self, c, P):
+        xs, infos = c.fos.certified_path(P, None, self.weights(c.d), self.GAP_TOL, self.PATH_ITERS, max_rounds=self.ROUNDS, max_fraction=1.0,
+                                         L=L_of(c.d, self.cfg), return_info=True)
+        i = infos[0]
+        return dict(x=c.torch.stack(list(xs)), rounds=np.int64(i.rounds), sizes=np.array(i.sizes), certificates=np.int64(i.certificates),
+                    fell_back=np.bool_(i.fell_back), certified=np.array(i.certified), cert=np.stack([i.primal, i.dual, i.gap, i.scale]))
+
+    def reference(self, d):
+        A, t, w, p, _ = parts(d, self.cfg)
+        X, info = du.certified(self.cfg.loss, A, t, self.weights(d), self.GAP_TOL, self.PATH_ITERS, w=w, p=p, L=L_of(d, self.cfg),
+                               max_rounds=self.ROUNDS, max_fraction=1.0)
+        assert info["stop_margins"].min() > self.STOP_MARGIN and info["scan_margins"].min() >= WorkingSet.MARGIN and \
+            min(list(info["growth_gaps"]) + [np.inf]) >= WorkingSet.GAP, (info["stop_margins"], info["scan_margins"], info["growth_gaps"])
+        return dict(x=X.T, rounds=np.int64(info["rounds"]), sizes=np.array(info["sizes"]), certificates=np.int64(info["certificates"]),
+                    fell_back=np.bool_(info["fell_back"]), certified=info["certified"], gap=info["gap"], mag_gap=info["mag_gap"],
+                    stop_margin=np.float64(info["stop_margins"].min()))
+
+    def precondition(self, d, ref):
+        assert ref["rounds"] >= 2 and ref["sizes"][-1] > ref["sizes"][0] and ref["certified"].all() and not ref["fell_back"], ref
+
+    def check(self, d, out):
+        ref = self.ref(d)
+        assert (int(out["rounds"]), list(out["sizes"]), int(out["certificates"]), bool(out["fell_back"]), list(out["certified"])) == \
+            (int(ref["rounds"]), list(ref["sizes"]), int(ref["certificates"]), bool(ref["fell_back"]), list(ref["certified"])), (out, ref)
+        for i in range(self.COUNT):
+            _rel_ok(out["x"][i], ref["x"][i], (self.name, i))
+        assert (np.abs(out["cert"][2] - ref["gap"]) <= du.TOL * ref["mag_gap"]).all(), (out["cert"][2], ref["gap"])
+
+
+W, COORD, GROUPS = PLAIN._replace(weights=True), PLAIN._replace(coord="bounds"), PLAIN._replace(groups=True)
+FACTORS = PLAIN._replace(coord="factors")
 LOGIT, HUBER, HINGE_W = PLAIN._replace(loss="logistic"), PLAIN._replace(loss="huber"), W._replace(loss="squared_hinge")
 M3, M7G = PLAIN._replace(loss="multinomial", classes=3), PLAIN._replace(loss="multinomial", classes=7, grouped=True)
 
@@ -887,17 +1016,20 @@ CELLS = collections.OrderedDict((c.name, c) for c in (
     Path("factors_path16", COORD, 16),
     Path("groups_path3", GROUPS, 3), Cv("groups_cv", GROUPS, 3, 2),
     Path("logistic_path16", LOGIT, 16), Objective("logistic_objective5", LOGIT, 5),
-    Cv("logistic_weights_factors_cv", LOGIT._replace(weights=True, coord=True), 2, 3),
+    Cv("logistic_weights_factors_cv", LOGIT._replace(weights=True, coord="bounds"), 2, 3),
     Path("huber_path5", HUBER, 5), Objective("huber_objective16", HUBER, 16),
     Cv("hinge_weights_cv", HINGE_W, 2, 3),
     Path("multinomial3_path5", M3, 5), Objective("multinomial3_objective5", M3, 5),
     Path("multinomial7_grouped_path2", M7G, 2),
     WorkingSet("working_set", PLAIN), WorkingSet("working_set_huber", HUBER), KktExcess("kkt_excess", PLAIN),
     Controlled("controlled"),
+    DualityGap("gap16", PLAIN, 16), DualityGap("gap3", PLAIN, 3), DualityGap("weights_gap5", W, 5), DualityGap("logistic_gap16", LOGIT, 16),
+    DualityGap("huber_gap5", HUBER, 5), DualityGap("hinge_weights_gap5", HINGE_W, 5), DualityGap("positive_factors_gap16", FACTORS, 16),
+    CertifiedPath("certified_path", PLAIN),
 ))
 LOCKSTEP_ENTRY_POINTS = ("fos_fista_run_multi", "fos_fista_run_multi_rhs", "fos_fista_run_multi_folds", "fos_residual_batch",
                          "fos_residual_batch_rhs", "fos_residual_batch_folds", "fos_gradient_batch", "fos_gather_columns",
-                         "fos_kkt_scan", "fos_power_iter")
+                         "fos_kkt_scan", "fos_power_iter", "fos_duality_gap")
 MAY_DECLINE = {"fos_fista_run_multi", "fos_fista_run_multi_rhs", "fos_fista_run_multi_folds", "fos_residual_batch_rhs",
                "fos_residual_batch_folds", "fos_lbfgs_minimize_multi"}
 PAIRS = [(x, y) for x in CELLS for y in CELLS if x != y]
@@ -907,10 +1039,52 @@ PANEL_PAIRS = [(x, y) for x, y in PAIRS if CELLS[x].sized_by_panels or CELLS[y].
 _NARROW = [Path("factors_path3", COORD, 3), Path("logistic_path3", LOGIT, 3), Path("multinomial7_path2", M7G._replace(grouped=False), 2)]
 ALL_CELLS = dict(CELLS, **{c.name: c for c in _NARROW})
 WIDTHS = {"plain": ("path16", "path3"), "factors": ("factors_path16", "factors_path3"), "logistic": ("logistic_path16", "logistic_path3"),
-          "multinomial": ("multinomial7_path2", "multinomial3_path5")}
+          "multinomial": ("multinomial7_path2", "multinomial3_path5"), "gap": ("gap16", "gap3")}
 
 
 @functools.lru_cache(maxsize=None)
 def _reference(cell, name, kind, cus):
     """The fp64 reference of a cell, computed once and never modified."""
     return _frozen(ALL_CELLS[cell].reference(data(name, kind, cus)))
+
+
+# ---- what the certificate refuses --------------------------------------------------------------------------------------------------
+# (the condition of each guard of fos_duality_gap, a word of its message, whether a configuration of the table meets it), beside the
+# shape rules every lockstep entry point shares
+DUALITY_GUARDS = (
+    (r"p->loss\s*==\s*FOS_LOSS_MULTINOMIAL", "fos_duality_gap: a multinomial problem is not served", lambda cfg: cfg.loss == "multinomial"),
+    (r"p->coord_lo\s*\|\|\s*p->coord_hi", "fos_duality_gap: box bounds (fos_coord_bind) are bound", lambda cfg: cfg.coord == "bounds"),
+    (r"has_fgroups\(p\)", "fos_duality_gap: feature groups (fos_feature_groups_bind) are bound", lambda cfg: cfg.groups),
+)
+FOS_ERR_UNSUPPORTED = -4
+
+
+def refusal(cfg):
+    """The text fos_duality_gap refuses the configuration with (its first guard that applies), or None where it is served."""
+    return next((message for _, message, applies in DUALITY_GUARDS if applies(cfg)), None)
+
+
+# one cell per refusing configuration of the table: the first that has it
+REFUSED = collections.OrderedDict()
+for _c in ALL_CELLS.values():
+    if refusal(_c.cfg) and _c.cfg not in [r.cfg for r in REFUSED.values()]:
+        REFUSED[_c.name] = _c
+
+
+def check_duality_guards(fista=FISTA):
+    """Every FOS_ERR_UNSUPPORTED of fos_duality_gap is a shape rule or a row of DUALITY_GUARDS, in the order of the source; every
+    configuration of the table that a row refuses has a cell in REFUSED and every certificate cell has a configuration none does:
+    a new guard fails here until it has a row."""
+    body = _body(_text(fista), r"\bint\s+fos_duality_gap\s*\([^)]*\)\s*(?=\{)")
+    conds = re.findall(r"if\s*\(((?:[^()]|\([^()]*\))*)\)\s*return\s+fail\(FOS_ERR_UNSUPPORTED", body)
+    left = [c for c in conds if not any(re.fullmatch(r"\s*" + s + r"\s*", c) for s in SHAPE_RULES)]
+    assert len(left) == len(DUALITY_GUARDS), left
+    for (cond, message, _), got in zip(DUALITY_GUARDS, left):
+        assert re.fullmatch(r"\s*" + cond + r"\s*", got), got
+        assert message in body, message
+    assert list(REFUSED) == ["factors_path16", "groups_path3", "logistic_weights_factors_cv", "multinomial3_path5",
+                             "multinomial7_grouped_path2", "multinomial7_path2"], list(REFUSED)
+    assert {refusal(c.cfg) for c in REFUSED.values()} == {message for _, message, _ in DUALITY_GUARDS}
+    for c in ALL_CELLS.values():
+        if "fos_duality_gap" in c.reaches:
+            assert refusal(c.cfg) is None, c.name

@@ -106,6 +106,15 @@ def test_the_controlled_case_decides_by_a_margin(name):
     assert len(refs) == cp.CONTROL_WEIGHTS == 16
 
 
+@pytest.mark.parametrize("cell", list(cp.CERT_CELLS))
+@pytest.mark.parametrize("name", ["cs4", "cs8"])
+def test_the_certificate_cells_meet_their_preconditions(name, cell):
+    """Both arms of the scale and of the conjugate are live and no gap is rounding noise, on the fp64 certificate alone."""
+    ref = cp.check_certificate_case(name, cell)
+    print(f"{name} {cell}: scales {np.round(ref['scale'], 3).tolist()}, smallest gap / magnitude {(ref['gap'] / ref['mag_gap'])[1:].min():.2e}")
+    cp.certificate_case.cache_clear()
+
+
 def test_recipe_helpers():
     assert cp.picks(1) == [0] and cp.picks(3) == [0, 1, 2] and cp.picks(16) == [0, 8, 15]
     ids = cp.fold_ids(50, 3, 1)

@@ -155,3 +155,32 @@ def test_gap_tol_of_the_certified_path_is_met_by_the_reference_solver():
         p0 = du.certificate(loss, cs["A"], cs["b"], np.zeros_like(X), cs["alphas"])["primal"]
         print(loss, "rounds", info["rounds"], "gap / P(0)", (r["gap"] / p0).max())
         assert (r["gap"] <= 0.1 * du.GAP_TOL * p0).all(), r["gap"] / p0
+
+
+@pytest.mark.parametrize("name", list(du.CERTIFIED_CASES))
+def test_the_certified_reference_decides_by_a_margin(name):
+    """A device-decided run is compared only where fp32 cannot decide otherwise: every test of the stop rule of the fp64 loop
+    (tests/_duality.certified) is further than 100 * TOL of the magnitude of the gap's terms from its bound, every scan further than
+    the WorkingSet cell's MARGIN from its threshold, every growth step by its GAP.  gap_tol is 1e-3 and no case runs at GAP_TOL:
+    tests/_duality.py says why, next to the cases.  The branches: a set beyond max_fraction * n after a round, a round without a
+    violator whose set runs again, the warm start (every round but the first of a case, and the fall-back), 20 weights."""
+    groups = du.certified_reference(name)
+    count = du.CERTIFIED_CASES[name][4]
+    assert [len(info["gap"]) for _, info in groups] == ([16, 4] if count == 20 else [16])
+    for X, info in groups:
+        print(f"{name}: rounds {info['rounds']} sizes {info['sizes']} certificates {info['certificates']} fell back {info['fell_back']} "
+              f"certified {int(info['certified'].sum())}; margins: stop {info['stop_margins'].min():.2e} scan {info['scan_margins'].min():.2e} "
+              f"growth {info['growth_gaps'].tolist()}")
+        assert info["stop_margins"].min() > du.STOP_MARGIN, info["stop_margins"].min()
+        assert info["scan_margins"].min() >= du.SCAN_MARGIN and min(info["growth_gaps"].tolist() + [np.inf]) >= du.GROWTH_GAP
+        assert np.isfinite(X).all() and info["certified"].all()
+        assert info["certificates"] == info["rounds"] + 1 + info["fell_back"]
+    info = groups[0][1]
+    if name == "beyond_max_fraction":
+        assert info["fell_back"] and info["rounds"] == 1 and info["certificates"] == 3 and info["sizes"][0] <= 0.95 * 256
+    else:
+        assert not info["fell_back"] and info["rounds"] >= 1
+    if name == "same_set_again":
+        assert info["rounds"] >= 2 and info["sizes"][0] == info["sizes"][1], info["sizes"]
+    if name not in ("squared_weighted", "twenty_weights"):
+        assert info["rounds"] + info["fell_back"] >= 2                       # a warm start from a non-zero X

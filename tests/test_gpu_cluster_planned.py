@@ -3,7 +3,7 @@
 A problem planned for the one-read cluster form (replan(cluster=True); the planner's own choice at 131072 x 4096 and 65536 x
 8192) keeps one slab set per cluster, an exchange ring and flag words, and every feature - several right-hand sides, fold masks,
 the logistic and multinomial losses, row weights, penalty factors and bounds, the group penalty, feature groups, the working-set
-gradient batch - runs the two-product form on that layout.  Three things are checked at the smallest shapes the cluster form is
+gradient batch, the duality-gap certificate - runs the two-product form on that layout.  Three things are checked at the smallest shapes the cluster form is
 served at:
 
 1. every feature on a cluster-planned problem Pc against the same call on a two-product problem Pt on the same device matrix:
@@ -11,7 +11,8 @@ served at:
    sum the same slabs in the same order: only the allocation differs), and against the family's fp64 reference at the first,
    middle and last weight;
 2. the forms alternating on one problem: plain path (cluster form), feature (two products), plain path again, in every order,
-   and a replan in the middle;
+   and a replan in the middle; the same with the certificate (fos_duality_gap of 16 columns, squared loss and weighted
+   logistic) in the feature's place - every certificate bit for bit the fresh one, on either layout;
 3. the device-controlled lockstep (adaptive restart, ratio stop per weight) on the cluster form against the oracle's decisions.
 
 The refusal of two_product_splits has no cell here: tests/test_cluster_planned.py shows that no shape reaches it.
@@ -22,14 +23,21 @@ What fails when run_multi_mfma is wrong (three temporary edits, each run against
 - no memset of the candidate block: rows 5000 .. 5055 of the cs8 block (n_pad = 5056) keep what the allocation held, and the
   bitwise comparison of the cs8 cells fails (NaN iterates); cs4 has no padding rows (4096 = 64 x 64) and passes;
 - multi.gram_splits (the number of clusters) in place of the recomputed split count: nothing fails, and nothing can - the row
-  splits past the panel's rows sum no tile and write zero slabs, which the updates then add: same bits, more work."""
+  splits past the panel's rows sum no tile and write zero slabs, which the updates then add: same bits, more work.
+
+The certificate cells (54 tests in 17 s; 46 in 17 s before them) under the four temporary edits of fos_duality_gap that
+tests/test_gpu_handle_pairs.py lists: with the row weights also in product 1 the weighted logistic cell fails on both shapes
+against fp64 (first cs4-weighted_logistic_gap) and the squared one passes; with dual_scale_kernel skipped all eight tests fail
+(first cs4-gap); without + row0 in launch_dual_link, and with nparts not advanced, nothing fails here, and nothing can - both
+shapes are a single row panel on 256 CUs, so row0 is 0 and there is one set of partial sums.  The two-panel cells of
+tests/test_gpu_handle_pairs.py catch those two."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import fos_oracle as orc
-from tests import (_cluster_planned as cp, _coord as cd, _data, _fgroup as fg, _group as gp, _logit as lg, _menu_multi as mm,
-                   _multinomial as mn, _working_set as ws)
+from tests import (_cluster_planned as cp, _coord as cd, _data, _duality as du, _fgroup as fg, _group as gp, _logit as lg,
+                   _menu_multi as mm, _multinomial as mn, _working_set as ws)
 
 pytestmark = pytest.mark.gpu
 
@@ -50,6 +58,8 @@ def _release_the_recipes():
     yield
     cp.data.cache_clear()
     cp.bounds.cache_clear()
+    cp.certificate_case.cache_clear()
+    cp.certificate_gradient.cache_clear()
 
 
 def _np(x):
@@ -396,6 +406,40 @@ class Batches:
             assert (err <= g_tol).all(), (err / g_tol).max()
 
 
+class Certificate:
+    """fos_duality_gap on 16 columns (tests/_cluster_planned.certificate_case): the gradient block by the launches of
+    fos_gradient_batch - product 2 into the cluster layout's slabs -, product 1 once more into multi.rbuf16, the row pass per panel
+    of multi.panel_rows rows and ws.dual_part sized by the panel count of the plan."""
+    def __init__(self, cell):
+        self.cell = cell
+        self.loss, self.weighted = cp.CERT_CELLS[cell]
+
+    def build(self, c):
+        if self.weighted:
+            return c.fos.prepare_weighted(c.At, c.y32 if self.loss == "logistic" else c.b32, c.w32, loss=self.loss)
+        return c.fos.prepare(c.At, c.y32 if self.loss == "logistic" else c.b32, loss=self.loss)
+
+    def call(self, c, P):
+        cs = cp.certificate_case(c.name, self.cell)
+        out64, G = P.duality_gap_block(torch.as_tensor(cs["X"]), [a for a, _ in cs["alphas"]], [a for _, a in cs["alphas"]])
+        return [out64.clone(), G.clone()]
+
+    def check(self, c, out):
+        d, cs = c.d, cp.certificate_case(c.name, self.cell)
+        G64, g_tol = cp.certificate_gradient(c.name, self.cell)          # (with the preconditions of the case)
+        got, G = out[0].cpu().numpy().reshape(4, 16), out[1].cpu().numpy()
+        assert np.isfinite(got).all() and G.shape[0] == 16 and (G[:, d["n"]:] == 0).all()
+        G = G[:, :d["n"]]
+        ref = du.certificate(self.loss, d["A"], cs["t"], cs["X"], cs["alphas"], None, cs["w"], G=G)     # scale and conjugate from the returned G
+        for row, key in enumerate(("primal", "dual", "gap")):
+            err = np.abs(got[row] - ref[key]) / ref["mag_" + key]
+            assert (err <= du.TOL).all(), (self.cell, key, err.max())
+        assert np.abs(got[3] - ref["scale"]).max() <= 1e-12 and np.array_equal(got[2], got[0] - got[1])
+        assert ((got[3] > 0) & (got[3] < 1)).any() and (got[3] == 1).any(), got[3]
+        err = np.linalg.norm(G.T.astype(np.float64) - G64, axis=0)
+        assert (err <= g_tol).all(), (self.cell, (err / g_tol).max())
+
+
 CELLS = {
     "rhs": Rhs(), "multitask": Multitask(), "fista_cv": FistaCv(),
     "logistic_path": Path("logistic"), "logistic_cv": LogisticCv(),
@@ -405,6 +449,7 @@ CELLS = {
     "group_lasso": FeatureGroups(0.0), "sparse_group_lasso": FeatureGroups(0.5),
     "multinomial_c3": Multinomial(3, 5), "multinomial_c16": Multinomial(16, 2),
     "working_set": WorkingSet(), "batches": Batches(),
+    "gap": Certificate("gap"), "weighted_logistic_gap": Certificate("weighted_logistic_gap"),
 }
 # cs16: two cells only, to bound the time - the weighted squared loss with penalty factors, and the logistic loss
 CS16_CELLS = {"weighted_factors": Path("squared", True, "factors"), "logistic_path": CELLS["logistic_path"]}
@@ -524,6 +569,75 @@ def test_forms_alternate_on_one_problem(ctx, kind):
     t = cp.target(ctx.d, "logistic" if kind == "logistic" else "squared")
     a1, a2 = a.plain_alphas(ctx)[0]
     _check_iterates(plain0[0], [(0, orc.fista(ctx.d["A"], t, "elasticnet", a1, a2, max_iter=ITERS, L=ctx.L))], "plain")
+
+
+class AttachCertificate:
+    """A certificate cell on a plain squared-loss handle: what the cell binds goes on before the certificate and off after it."""
+    def __init__(self, cell):
+        self.cert = Certificate(cell)
+        self.plain_form = Attach("logistic" if self.cert.loss == "logistic" else "weights")     # (for its plain path alone)
+
+    def build(self, c):
+        return c.fos.prepare(c.At, c.y32 if self.cert.loss == "logistic" else c.b32)
+
+    def plain(self, c, P):
+        return self.plain_form.plain(c, P)
+
+    def bind(self, c, P, on):
+        from fastoptsolver_amd import _lib
+        if self.cert.loss == "logistic":
+            _lib.check(P.lib.fos_problem_set_loss(P.h, _lib.LOSS_LOGISTIC if on else _lib.LOSS_SQUARED), "fos_problem_set_loss")
+            P.loss = "logistic" if on else "squared"
+        if self.cert.weighted:
+            buf = None
+            if on:
+                buf = torch.zeros((c.d["m"] + 3) // 4 * 4, dtype=torch.float32, device=P.device)
+                buf[:c.d["m"]] = torch.as_tensor(c.w32)
+                buf = buf[:c.d["m"]]
+            P.set_sample_weight(buf)
+
+    def certificate(self, c, P):
+        self.bind(c, P, True)
+        out = self.cert.call(c, P)
+        self.bind(c, P, False)
+        return out
+
+
+@pytest.mark.parametrize("ctx", TWO_SHAPES, indirect=True)
+@pytest.mark.parametrize("cell", list(cp.CERT_CELLS))
+def test_the_certificate_alternates_with_the_plain_path(ctx, cell):
+    """Plain path (cluster form), certificate, plain path; certificate, plain path, certificate; then the same handle replanned
+    to the two-product layout and back: every plain path is bit for bit that of a fresh cluster-planned problem and every
+    certificate (out64 and G) bit for bit that of a fresh one, whichever layout it ran on."""
+    _served(ctx)
+    a = AttachCertificate(cell)
+    plain0 = a.plain(ctx, ctx.new(a.build, True))
+    cert0 = a.certificate(ctx, ctx.new(a.build, True))
+    a.cert.check(ctx, cert0)
+    # plain, certificate, plain
+    P1 = ctx.new(a.build, True)
+    assert_same_bits(a.plain(ctx, P1), plain0, "plain before the certificate")
+    assert_same_bits(a.certificate(ctx, P1), cert0, "the certificate after a plain path")
+    assert P1.plan()["cluster"] == 1
+    assert_same_bits(a.plain(ctx, P1), plain0, "plain after the certificate")
+    # certificate, plain, certificate
+    P2 = ctx.new(a.build, True)
+    assert_same_bits(a.certificate(ctx, P2), cert0, "the certificate as the first call")
+    assert P2.plan()["cluster"] == 1
+    assert_same_bits(a.plain(ctx, P2), plain0, "plain after a certificate that ran first")
+    assert_same_bits(a.certificate(ctx, P2), cert0, "the certificate again")
+    # a replan in the middle, in both orders
+    P2.replan(cluster=False)
+    assert_same_bits(a.certificate(ctx, P2), cert0, "the certificate after replan(cluster=False)")
+    assert P2.plan()["cluster"] == 0
+    P2.replan(cluster=True)
+    assert_same_bits(a.plain(ctx, P2), plain0, "plain after replan(cluster=True)")
+    assert P2.plan()["cluster"] == 1
+    assert_same_bits(a.certificate(ctx, P2), cert0, "the certificate after both replans")
+    P1.replan(cluster=False)
+    P1.replan(cluster=True)
+    assert_same_bits(a.certificate(ctx, P1), cert0, "the certificate first after a replan")
+    assert_same_bits(a.plain(ctx, P1), plain0, "plain after it")
 
 
 # ---- 3. the device-controlled lockstep on the cluster form ---------------------------------------------------------------------------

@@ -3,22 +3,33 @@ the fp64 references; tests/test_handle_pairs.py checks that table on the CPU).
 
 fos_problem_set_loss / _set_link_loss / _set_multinomial, fos_row_weights_bind and fos_coord_bind say "nothing to invalidate",
 fos_feature_groups_bind and fos_problem_replan re-bind or drop buffers beside the bindings that stay, and every lockstep call of a
-handle shares its workspace.  Four parts, per storage type (f32, bf16):
+handle shares its workspace.  Five parts, per storage type (f32, bf16):
 
 1. each cell on a fresh handle: served (asserted), within the project's 1e-5 of its fp64 reference (the sums within the bounds of
    their fp32 passes), and a second fresh handle gives the same bits - the precondition of everything below;
 2. every ordered pair (X, Y), X != Y: configure(X), call(X), move(X, Y), call(Y), move(Y, X), call(X) on one handle; Y's result
    and the second X's are bit for bit those of the fresh handles, and after each move the getters report the configuration just
-   set.  All 600 pairs at the padded shape; at the two-panel shape the pairs in which X or Y is a CV, objective, working-set or
-   multinomial cell (buffers sized by the panel count);
+   set.  All 1056 pairs at the padded shape; at the two-panel shape the pairs in which X or Y is a CV, objective, working-set,
+   certificate or multinomial cell (buffers sized by the panel count);
 3. a replan with the bindings in place: call(X), move(X, Y), replan(), call(Y) gives the fresh bits, replan(interleave=True)
    stays within 1e-5 of the reference where the plan then deals the rows round-robin (at these shapes it does not: the fresh
    bits), and back gives the fresh bits again; the getters still report Y;
 4. the same call at another width: path 16 -> path 3 -> path 16 on the plain, factor and logistic configurations, C = 7 (14
-   columns) -> C = 3 (15 columns) -> C = 7 on the multinomial one.
+   columns) -> C = 3 (15 columns) -> C = 7 on the multinomial one, the certificate of 16 columns -> 3 -> 16 (the columns >= nv of
+   its 4 x 16 answer are 0 each time);
+5. a refused certificate between two calls: for every configuration of the table that fos_duality_gap refuses (bounds, feature
+   groups, bounds under the weighted logistic loss, the three multinomial ones) call(X), fos_duality_gap through the C ABI -
+   FOS_ERR_UNSUPPORTED with the guard's text, nothing launched -, call(X): the fresh bits both times, getters and plan unchanged.
 
-No pair comparison has a tolerance and nothing skips.  25 cells (28 with the narrow twins of part 4), 600 ordered pairs per
-storage type at the padded shape and 444 at the two-panel shape; the 328 tests take 28 s on the MI355X.
+The certificate cells (fos_duality_gap on 16, 3, 5, 16, 5, 5 and 16 columns of a seeded block with one zero column, on the
+plain, weighted, logistic, Huber, weighted squared-hinge and positive-factor configurations, and certified_path) are checked on
+the fresh handle against tests/_duality.certificate - primal, dual and gap within 1e-5 of the magnitude of their terms, the scale
+to 1e-12, gap == primal - dual, G within the bound of fos_gradient_batch - and against tests/_duality.certified.
+
+No pair comparison has a tolerance and nothing skips.  33 cells (36 with the narrow twins of part 4), 1056 ordered pairs per
+storage type at the padded shape and 900 at the two-panel shape; the 452 tests take 41 to 47 s on the MI355X (the 328 tests of
+25 cells, 600 and 444 pairs before the certificate cells: 32 s in the same session; the slowest test 0.69 s then, and the
+slowest that the certificate cells add, the two-panel pairs of certified_path on bf16, 0.62 s).
 
 What fails when the library is wrong (five temporary edits, each run against this file on the MI355X).  No defect was found, and
 four of the five edits change no bit - each removes one of two layers that keep an unused column harmless:
@@ -34,7 +45,23 @@ four of the five edits change no bit - each removes one of two layers that keep 
   are whatever the allocation held, and every reader (updates, q_part) is bounded by nv: columns never meet in either product;
 - no memset of the candidate block in run_multi_mfma (the edit of tests/test_gpu_cluster_planned.py): 207 of the 328 tests
   fail, 57 of them in part 1 (first test_cell_on_a_fresh_handle[path16-panels-bf16]) with NaN iterates against the reference -
-  the rows n .. n_pad of the block and the columns >= nv keep what the allocation held."""
+  the rows n .. n_pad of the block and the columns >= nv keep what the allocation held.
+
+Four more temporary edits, of fos_duality_gap's host part alone (values only), each run once against this file,
+tests/test_gpu_cluster_planned.py and tests/test_gpu_duality.py with the certificate cells in place:
+- launch_dual_link passes p->b and p->row_weight without + row0: 100 of the 452 tests fail, all at the two-panel shape and
+  every padded one passes - the 16 fresh certificate cells there (first test_cell_on_a_fresh_handle[gap16-panels-f32], against
+  fp64), their 16 replans, the 66 two-panel pair tests and the two width runs.  The cluster-planned file passes: 8200 and 4200
+  rows are one panel.  tests/test_gpu_duality.py fails in its 12 two-panel end-to-end cases;
+- product 1 of fos_duality_gap also sets L.row_weight: 148 fail - the fresh weights_gap5 and hinge_weights_gap5 cells at both
+  shapes against fp64 (first test_cell_on_a_fresh_handle[weights_gap5-padded-f32]), and through their missing fresh results
+  every pair test; the unweighted cells pass.  The weighted logistic cell of the cluster-planned file fails, the squared one
+  passes;
+- the dual_scale_kernel launch is skipped: 200 fail, and not only "Y after X" as expected - ws.dual_col also carries the penalty
+  and the conjugate of the ridge term to the finish, so every certificate is wrong from the first call on a fresh handle (first
+  test_cell_on_a_fresh_handle[gap16-padded-f32], against fp64);
+- nparts is not advanced between panels (the second panel's partial sums overwrite the first's): the same 100 tests as under
+  the first edit fail, first test_cell_on_a_fresh_handle[gap16-panels-f32]; one-panel shapes pass."""
 import time
 
 import pytest
@@ -195,3 +222,30 @@ def test_the_same_call_at_another_width(bench, config, shape, kind):
         c.check_getters(P, cell.cfg, (config, cell.name))
         out = c.run(cell, P)
         assert _differs(out, want) is None, (config, cell.name, _differs(out, want))
+
+
+# ---- 5. a refused certificate between two calls ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", hp.KINDS)
+@pytest.mark.parametrize("shape", hp.SHAPES)
+@pytest.mark.parametrize("cell", list(hp.REFUSED))
+def test_a_refused_certificate_leaves_the_handle_alone(bench, cell, shape, kind):
+    import ctypes as C
+    c, X = bench.ctx(shape, kind), hp.REFUSED[cell]
+    want = bench.fresh(shape, kind, X)
+    P = c.fresh()
+    c.move(P, hp.PLAIN, X)
+    assert _differs(c.run(X, P), want) is None
+    getters, plan = c.getters(P), P.plan()
+    block = torch.zeros(P.n_dev, 16, device="cuda")
+    G = torch.full((2, P.n_dev), 9.0, device="cuda")
+    out64 = torch.full((64,), 7.0, dtype=torch.float64, device="cuda")
+    a = (C.c_double * 2)(0.5, 0.25)
+    with P.ctx():
+        rc = P.lib.fos_duality_gap(C.c_void_p(block.data_ptr()), 2, a, a, P.h, C.c_void_p(G.data_ptr()), C.c_void_p(out64.data_ptr()))
+    message = P.lib.fos_last_error().decode()
+    assert rc == hp.FOS_ERR_UNSUPPORTED and hp.refusal(X.cfg) in message, (rc, message)
+    torch.cuda.synchronize()
+    assert bool((G == 9.0).all()) and bool((out64 == 7.0).all())           # nothing was launched
+    assert c.getters(P) == getters and P.plan() == plan
+    c.check_getters(P, X.cfg, (cell, "refused"))
+    assert _differs(c.run(X, P), want) is None, (cell, "after the refusal", _differs(c.run(X, P), want))

@@ -6,7 +6,10 @@
 3. move is legal for every ordered pair of configurations: replayed against a host model of the refusal rules, which is itself
    pinned to the guards of csrc/fos_plan.hip;
 4. the fp64 references of all cells run at the padded shape and meet their own preconditions: penalties that bite, the branch
-   shares of the Huber and squared-hinge losses, fp32-proof decisions of the controlled cell, a grown and certified working set."""
+   shares of the Huber and squared-hinge losses, fp32-proof decisions of the controlled cell, a grown and certified working set,
+   certificates with a scale inside (0, 1) and the scale 1 whose gaps stand 100 times clear of fp32 rounding, a certified path
+   whose every decision does;
+5. the configurations that fos_duality_gap refuses are the guards of its source, each with a cell."""
 import numpy as np
 import pytest
 
@@ -52,18 +55,41 @@ def test_the_host_model_is_the_guards_of_the_source():
     hp.check_guards()
 
 
+def test_the_refusing_configurations_are_the_guards_of_the_certificate():
+    hp.check_duality_guards()
+    for cell in hp.ALL_CELLS.values():                     # a cell that drops fos_duality_gap from its reaches fails here
+        if isinstance(cell, (hp.DualityGap, hp.CertifiedPath)):
+            assert {"fos_duality_gap", "fos_gradient_batch"} <= set(cell.reaches) and cell.sized_by_panels, cell.name
+    assert "fos_duality_gap" in hp.LOCKSTEP_ENTRY_POINTS
+
+
+def test_a_changed_guard_of_the_certificate_fails_the_pin(tmp_path):
+    """A guard of fos_duality_gap that is reworded, dropped or added in a copy of the source fails check_duality_guards."""
+    with open(hp.FISTA) as fh:
+        text = fh.read()
+    new_guard = '  if (p->row_weight) return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: row weights are bound");\n  // 1. the gradient block'
+    for old, new in (('"fos_duality_gap: box bounds (fos_coord_bind) are bound;', '"fos_duality_gap: bounds are bound;'),
+                     ("  if (has_fgroups(p))\n    return fail(FOS_ERR_UNSUPPORTED, \"fos_duality_gap:", "  if (false)\n    return fail(FOS_ERR_UNSUPPORTED, \"fos_duality_gap:"),
+                     ("  // 1. the gradient block", new_guard)):
+        assert text.count(old) == 1, old
+        fake = tmp_path / "fos_fista.hip"
+        fake.write_text(text.replace(old, new))
+        with pytest.raises(AssertionError):
+            hp.check_duality_guards(str(fake))
+
+
 def test_every_move_is_legal_and_minimal():
     for x, y in _moves():
         model = hp.HostModel(x)
         steps = hp.plan_move(x, y)
         for entry, arg in steps:
             model.step(entry, arg)                         # raises Refused
-        assert (model.loss, model.coord, model.groups) == (y.loss, y.coord, y.groups), (x, y)
+        assert (model.loss, model.coord, model.groups) == (y.loss, bool(y.coord), y.groups), (x, y)
         entries = [e for e, _ in steps]
         assert len(entries) == len(set(entries)), (x, y, steps)        # every entry point at most once
         # only what differs: a binding that X and Y share is not touched
         assert ("fos_row_weights_bind" in entries) == (x.weights != y.weights)
-        assert ("fos_coord_bind" in entries) == (x.coord != y.coord)
+        assert ("fos_coord_bind" in entries) == (x.coord != y.coord)                  # "bounds" <-> "factors": the one rebind
         assert ("fos_feature_groups_bind" in entries) == (x.groups != y.groups)
         assert any(e in hp.SETTER.values() for e in entries) == ((x.loss, x.classes) != (y.loss, y.classes))
         assert ("target" in entries) == (hp.target_key(x) != hp.target_key(y))
@@ -78,11 +104,12 @@ def test_every_move_is_legal_and_minimal():
 
 
 def test_the_table_has_the_cells_and_the_pairs():
-    assert len(hp.CELLS) == 25 and len(hp.PAIRS) == 25 * 24
+    assert len(hp.CELLS) == 33 and len(hp.PAIRS) == 33 * 32
     sized = [n for n, c in hp.CELLS.items() if c.sized_by_panels]
-    assert len(hp.PANEL_PAIRS) == len(hp.PAIRS) - (25 - len(sized)) * (24 - len(sized))
+    assert len(hp.PANEL_PAIRS) == len(hp.PAIRS) - (33 - len(sized)) * (32 - len(sized))
     for name in ("cv", "groups_cv", "logistic_objective5", "huber_objective16", "multinomial3_path5", "multinomial7_grouped_path2",
-                 "working_set", "kkt_excess"):
+                 "working_set", "kkt_excess", "gap16", "gap3", "weights_gap5", "logistic_gap16", "huber_gap5", "hinge_weights_gap5",
+                 "positive_factors_gap16", "certified_path"):
         assert name in sized
     for wide, narrow in hp.WIDTHS.values():
         a, b = hp.ALL_CELLS[wide], hp.ALL_CELLS[narrow]
