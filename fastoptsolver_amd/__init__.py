@@ -23,6 +23,10 @@ from .robust import (HingeCVResult, HuberCVResult, hinge_cv, hinge_objective, hi
 # the duality-gap certificate and the gap-stopped path: importable from the package likewise
 from .duality import DualityGap, GapInfo, certified_path, duality_gap                                # noqa: F401
 
+# the working set and the duality gap of the multinomial lockstep: importable from the package likewise
+from .multinomial_ws import (multinomial_alpha_max, multinomial_certified_path, multinomial_duality_gap,   # noqa: F401
+                             multinomial_kkt_excess, multinomial_working_set_path)
+
 __all__ = ["fista", "fista_delta", "fista_path", "fista_cv", "CVResult", "ista", "estimate_lipschitz", "reset_metrics", "get_metrics", "LBFGSSolver",
            "compute_objective", "prox_l1", "prox_elastic_net", "LeastSquares", "L1Prox", "ElasticNetProx",
            "prepare", "prepare_weighted", "prepare_penalized", "Problem", "FosError", "logistic_path", "logistic_cv", "logistic_objective", "LogisticCVResult",

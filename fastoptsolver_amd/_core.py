@@ -801,6 +801,55 @@ class Problem:
             _lib.check(self.lib.fos_duality_gap(ptr(Xf), nv, a1, a2, self.h, ptr(G), ptr(out64)), "fos_duality_gap")
         return out64, G
 
+    # ---- working set and duality gap of the multinomial lockstep (include/fos_multinomial_ws.h; multinomial_ws.py drives these)
+    def multinomial_gradient_block(self, X, want_loss=False):
+        """The class gradients at the columns of X (n x nv, nv a multiple of C: column s * C + c is class c of fit s) on a
+        multinomial handle: A^T (w (softmax(A X_s)_c - [y = c])) as the nv x n_dev float32 device block `multinomial_kkt_scan`
+        reads (fos_multinomial_gradient_batch).  want_loss: also the cross-entropy sums of `residual_batch` from the same pass,
+        one per fit, as a host list (synchronises)."""
+        Xf, nv = self._block16(X)
+        G = torch.empty(nv, self.n_dev, dtype=torch.float32, device=self.device)
+        with self.ctx():
+            _lib.check(self.lib.fos_multinomial_gradient_batch(ptr(Xf), nv, self.h, ptr(G), ptr(self.scratch) if want_loss else None),
+                       "fos_multinomial_gradient_batch")
+        return (G, self.scratch[:nv:self.classes].cpu().tolist()) if want_loss else G
+
+    def multinomial_kkt_scan(self, G, alpha1, slack, in_ws, grouped=None):
+        """The optimality check of the coordinates (rows of X) outside a working set on the nv x n_dev block G of
+        `multinomial_gradient_block` (fos_multinomial_kkt_scan): (excess - n_dev floats on the device -, the violators in
+        increasing order as an int32 device tensor).  alpha1: one host weight per fit (nv / C); grouped: the group penalty over
+        the classes (None: as `.grouped` says).  Synchronises (the count is read)."""
+        nv = int(G.shape[0])
+        a1 = (C.c_double * len(alpha1))(*[float(a) for a in alpha1])
+        if self.classes and len(alpha1) * self.classes != nv:
+            raise ValueError(f"alpha1: one weight per fit expected ({nv} columns, {self.classes} classes), got {len(alpha1)}")
+        excess = torch.empty(self.n_dev, dtype=torch.float32, device=self.device)
+        viol = torch.empty(self.n_dev, dtype=torch.int32, device=self.device)
+        count = torch.zeros(1, dtype=torch.int32, device=self.device)
+        grouped = self.grouped if grouped is None else grouped
+        with self.ctx():
+            _lib.check(self.lib.fos_multinomial_kkt_scan(ptr(G), nv, int(bool(grouped)), a1, float(slack), ptr(in_ws), self.h, ptr(excess),
+                                                         ptr(viol), ptr(count)), "fos_multinomial_kkt_scan")
+        return excess, viol[: int(count.item())]
+
+    def multinomial_duality_gap_block(self, X, alpha1, alpha2, grouped=None):
+        """The duality-gap certificate of the fits in the columns of X (n x nv, nv a multiple of C) under the host weights alpha1,
+        alpha2 (one per fit; fos_multinomial_duality_gap): (out64 - 64 device doubles: primal[16], dual[16], gap[16], scale[16],
+        the values of fit s at entry s * C -, G - the block of `multinomial_gradient_block` at X, from the same pass).  grouped:
+        None takes `.grouped`.  Enqueues only."""
+        Xf, nv = self._block16(X)
+        if self.classes and (len(alpha1) * self.classes != nv or len(alpha2) != len(alpha1)):
+            raise ValueError(f"alpha1, alpha2: one weight per fit expected ({nv} columns, {self.classes} classes)")
+        a1 = (C.c_double * len(alpha1))(*[float(a) for a in alpha1])
+        a2 = (C.c_double * len(alpha2))(*[float(a) for a in alpha2])
+        G = torch.empty(nv, self.n_dev, dtype=torch.float32, device=self.device)
+        out64 = torch.empty(64, dtype=torch.float64, device=self.device)
+        grouped = self.grouped if grouped is None else grouped
+        with self.ctx():
+            _lib.check(self.lib.fos_multinomial_duality_gap(ptr(Xf), nv, int(bool(grouped)), a1, a2, self.h, ptr(G), ptr(out64)),
+                       "fos_multinomial_duality_gap")
+        return out64, G
+
     def power_iter(self, v0, n_iter=100, tol=1e-6):
         """The reference's power iteration (ref:45-60) from v0 (n values, need not be normalised): ``(L, it, v)``.  On every
         plan ``it`` is the step at which ``|L_k - L_{k-1}| < tol`` fired (``n_iter`` when it never did), ``L`` the norm of that

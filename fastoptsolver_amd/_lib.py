@@ -188,6 +188,14 @@ DUALITY_SIGNATURES = {
 }
 
 
+# include/fos_multinomial_ws.h: the working set and the duality gap of the multinomial lockstep
+MULTINOMIAL_WS_SIGNATURES = {
+    "fos_multinomial_gradient_batch": (_i32, [_vp, _i32, _vp, _vp, _vp]),
+    "fos_multinomial_kkt_scan": (_i32, [_vp, _i32, _i32, C.POINTER(C.c_double), C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "fos_multinomial_duality_gap": (_i32, [_vp, _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp, _vp]),
+}
+
+
 def load():
     """Return the loaded CDLL (cached).  Raises FosError if the library is absent."""
     global _lib
@@ -199,7 +207,7 @@ def load():
             "Build it with:  python -m fastoptsolver_amd.build   (needs hipcc; cross-compiles for gfx950)")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **FEATURE_GROUP_SIGNATURES, **WORKING_SET_SIGNATURES, **LINK_LOSS_SIGNATURES,
-                              **DUALITY_SIGNATURES}.items():
+                              **DUALITY_SIGNATURES, **MULTINOMIAL_WS_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -22,6 +22,7 @@ HEADERS.append(os.path.join(os.path.dirname(HERE), "include", "fos_feature_group
 HEADERS.append(os.path.join(os.path.dirname(HERE), "include", "fos_working_set.h"))
 HEADERS.append(os.path.join(os.path.dirname(HERE), "include", "fos_link_loss.h"))
 HEADERS.append(os.path.join(os.path.dirname(HERE), "include", "fos_duality.h"))
+HEADERS.append(os.path.join(os.path.dirname(HERE), "include", "fos_multinomial_ws.h"))
 DEPS = SOURCES + HEADERS
 OBJ_DIR = os.path.join(CSRC, "build")
 OUT = os.path.join(HERE, "libfos_hip.so")

@@ -5,6 +5,7 @@
 #include "chip_resident.hpp"
 #include "working_set.hpp"
 #include "duality.hpp"
+#include "multinomial_ws.hpp"
 #include <cassert>
 
 using namespace fosapi;
@@ -1748,6 +1749,158 @@ int fos_duality_gap(const float* X, int nv, const double* alpha1, const double* 
     nparts += nwg;
   }
   // 4. the finish
+  hipLaunchKernelGGL(fos::dual_finish_kernel, dim3(1), dim3(fos::DF_THREADS), 0, p->stream, (const double*)p->ws.dual_part.get(), nparts,
+                     (const double*)p->ws.dual_col.get(), nv, out64);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
+}  // extern "C"
+
+// ---- Working set and duality gap of the multinomial lockstep (include/fos_multinomial_ws.h, multinomial_ws.hpp) -------------
+// The checks the three entry points share, after their own FOS_ERR_ARG rows: a multinomial problem whose class count divides nv.
+static int need_class_segments(const fos_problem* p, int nv, const char* fn) {
+  if (p->loss != FOS_LOSS_MULTINOMIAL)
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the problem is not multinomial (fos_gradient_batch, fos_kkt_scan and "
+                                     "fos_duality_gap serve the other losses)");
+  if (p->classes < 2 || nv % p->classes != 0)
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": nv is not a multiple of the " + std::to_string(p->classes) + " classes");
+  return FOS_OK;
+}
+
+// The per-segment weights of a call (HOST memory, nv / C each; a2 may be null), checked: FOS_ERR_ARG before any HIP call.
+static int class_weights(const fos_problem* p, int nv, const double* a1, const double* a2, const char* fn, fos::ClassWeights* w) {
+  *w = fos::ClassWeights{};
+  for (int s = 0; s < nv / p->classes; ++s) {
+    if (!(std::isfinite(a1[s]) && a1[s] >= 0.0) || (a2 && !(std::isfinite(a2[s]) && a2[s] >= 0.0)))
+      return fail(FOS_ERR_ARG, std::string(fn) + ": weight " + std::to_string(s) + " is not finite and >= 0");
+    w->a1[s] = a1[s];
+    w->a2[s] = a2 ? a2[s] : 0.0;
+  }
+  return FOS_OK;
+}
+
+// The row pass on the `rows` rows of p->multi.rbuf16 that product 1 in its plain storing form has just filled with the logits of
+// the panel starting at row0: one thread per row, grid-stride, at most ncu workgroups; *nwg_out = the rows of `part` written.
+static int launch_dual_softmax(fos_problem* p, int64_t row0, int64_t rows, int nv, const double* col, double* part, int* nwg_out) {
+  const int nwg = (int)std::min<int64_t>((rows + fos::SL_THREADS - 1) / fos::SL_THREADS, p->ncu);
+  const float* w = p->row_weight ? p->row_weight + row0 : nullptr;
+  if (w)
+    hipLaunchKernelGGL(fos::dual_softmax_kernel<true>, dim3(nwg), dim3(fos::SL_THREADS), 0, p->stream,
+                       (const float*)p->multi.rbuf16.get(), rows, p->b + row0, p->classes, nv, w, col, part);
+  else
+    hipLaunchKernelGGL(fos::dual_softmax_kernel<false>, dim3(nwg), dim3(fos::SL_THREADS), 0, p->stream,
+                       (const float*)p->multi.rbuf16.get(), rows, p->b + row0, p->classes, nv, w, col, part);
+  LAUNCH_CHECK();
+  *nwg_out = nwg;
+  return FOS_OK;
+}
+
+extern "C" {
+
+// The class gradients at the nv columns of X: per row panel product 1 in its plain storing form (the logits), the softmax link
+// kernel (residuals in place, the loss partials of the panel behind those of the panels before it in ws.link_part), product 2;
+// then the slab sum and the partial fold of fos_gradient_batch.
+int fos_multinomial_gradient_batch(const float* X, int nv, fos_problem* p, float* G, double* loss16) {
+  const char* fn = "fos_multinomial_gradient_batch";
+  if (!X || !p || !G || nv < 1 || nv > fos::BT_NV)
+    return fail(FOS_ERR_ARG, std::string(fn) + ": bad argument (null pointer or nv outside 1..16)");
+  int rc = need_class_segments(p, nv, fn);
+  if (rc) return rc;
+  if (!p->b) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the gradient of the data term needs the labels");
+  if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": sharded problems are not served");
+  if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the shape has no matrix-core pair");
+  if ((rc = ensure_batch_workspace(p))) return rc;
+  if ((rc = plan_multi_mfma(p))) return rc;
+  int g_splits = 0;
+  if ((rc = two_product_splits(p, &g_splits))) return rc;
+  const int64_t panels = (p->m + p->multi.panel_rows - 1) / p->multi.panel_rows;
+  if ((rc = p->ws.link_part.reserve((size_t)panels * p->ncu * fos::BT_NV))) return rc;
+  const int64_t esz = p->dtype == FOS_BF16 ? 2 : 4;
+  if ((rc = pack_candidates(p, X, nv))) return rc;
+  int nparts = 0;
+  for (int64_t row0 = 0, panel = 0; row0 < p->m; row0 += p->multi.panel_rows, ++panel) {
+    const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
+    const char* Ap = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz;
+    int nwg1 = 0, nwg = 0;
+    BatchLaunch L{};                 // Z = A_panel X: no b, no mask, no weights
+    L.A = Ap; L.rows = rows; L.rout = p->multi.rbuf16;
+    if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
+    if ((rc = launch_softmax_link(p, row0, rows, nv, fos::FOLD_OFF, nullptr, nullptr, p->ws.link_part + (size_t)nparts * fos::BT_NV, &nwg)))
+      return rc;
+    nparts += nwg;
+    if ((rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
+  }
+  hipLaunchKernelGGL(gram_slab_sum_kernel, dim3(grid_1d((int64_t)nv * p->n, 256, 1024)), dim3(256), 0, p->stream, p->multi.slabs16,
+                     g_splits, p->n, nv, G);
+  LAUNCH_CHECK();
+  if (loss16) {
+    hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->ws.link_part.get(), nparts,
+                       fos::BT_NV, loss16);
+    LAUNCH_CHECK();
+  }
+  return FOS_OK;
+}
+
+int fos_multinomial_kkt_scan(const float* G, int nv, int grouped, const double* alpha1, double slack, const uint8_t* in_ws,
+                             fos_problem* p, float* excess, int32_t* viol_idx, int32_t* viol_count) {
+  const char* fn = "fos_multinomial_kkt_scan";
+  if (!G || !alpha1 || !in_ws || !p || !excess || !viol_idx || !viol_count || nv < 1 || nv > fos::BT_NV || grouped < 0 || grouped > 1)
+    return fail(FOS_ERR_ARG, std::string(fn) + ": bad argument (null pointer, nv outside 1..16 or grouped outside 0..1)");
+  if (!(std::isfinite(slack) && slack >= 0.0)) return fail(FOS_ERR_ARG, std::string(fn) + ": slack is not finite and >= 0");
+  int rc = need_class_segments(p, nv, fn);
+  if (rc) return rc;
+  fos::ClassWeights w;
+  if ((rc = class_weights(p, nv, alpha1, nullptr, fn, &w))) return rc;
+  if (p->coord_lo || p->coord_hi)
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": box bounds (fos_coord_bind) are bound; a coordinate at a bound has another "
+                                     "optimality condition");
+  hipLaunchKernelGGL(fos::class_kkt_scan_kernel, dim3(1), dim3(fos::KS_THREADS), 0, p->stream, G, p->n, nv, p->classes, grouped, w,
+                     1.0 + slack, in_ws, p->coord_factor, excess, viol_idx, viol_count);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
+int fos_multinomial_duality_gap(const float* X, int nv, int grouped, const double* alpha1, const double* alpha2, fos_problem* p,
+                                float* G, double* out64) {
+  const char* fn = "fos_multinomial_duality_gap";
+  if (!X || !alpha1 || !alpha2 || !p || !G || !out64 || nv < 1 || nv > fos::BT_NV || grouped < 0 || grouped > 1)
+    return fail(FOS_ERR_ARG, std::string(fn) + ": bad argument (null pointer, nv outside 1..16 or grouped outside 0..1)");
+  int rc = need_class_segments(p, nv, fn);
+  if (rc) return rc;
+  fos::ClassWeights wts;
+  if ((rc = class_weights(p, nv, alpha1, alpha2, fn, &wts))) return rc;
+  if (p->coord_lo || p->coord_hi)
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": box bounds (fos_coord_bind) are bound; the penalty of a bounded coordinate "
+                                     "has another conjugate");
+  if (has_fgroups(p))
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": feature groups (fos_feature_groups_bind) are bound; the group norm has "
+                                     "another conjugate");
+  // first the class gradients, by the launches of fos_multinomial_gradient_batch (its refusals; it plans the lockstep and leaves X packed)
+  if ((rc = fos_multinomial_gradient_batch(X, nv, p, G, nullptr))) return rc;
+  const int64_t panels = (p->m + p->multi.panel_rows - 1) / p->multi.panel_rows;
+  const size_t part_rows = (size_t)panels * 2 * (size_t)p->ncu;          // (the row pass writes at most ncu a panel)
+  if ((rc = p->ws.dual_part.reserve(part_rows * fos::DL_WIDTH))) return rc;
+  if ((rc = p->ws.dual_col.reserve(3 * fos::BT_NV))) return rc;
+  // then the column pass: the scale of every segment, then its penalty and the conjugate of the ridge-carrying coordinates
+  hipLaunchKernelGGL(fos::class_dual_scale_kernel, dim3(nv / p->classes), dim3(fos::DS_THREADS), 0, p->stream, X, (const float*)G,
+                     p->n, p->classes, grouped, wts, p->coord_factor, p->ws.dual_col.get());
+  LAUNCH_CHECK();
+  // the logits of every panel once more, and the row pass on them
+  const int64_t esz = p->dtype == FOS_BF16 ? 2 : 4;
+  int nparts = 0;
+  for (int64_t row0 = 0; row0 < p->m; row0 += p->multi.panel_rows) {
+    const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
+    int nwg1 = 0, nwg = 0;
+    BatchLaunch L{};
+    L.A = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz; L.rows = rows; L.rout = p->multi.rbuf16;
+    if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
+    if ((size_t)nparts + (size_t)p->ncu > part_rows)
+      return fail(FOS_ERR_STATE, std::string(fn) + ": the row pass has more panels than its partial buffer holds");
+    if ((rc = launch_dual_softmax(p, row0, rows, nv, p->ws.dual_col, p->ws.dual_part + (size_t)nparts * fos::DL_WIDTH, &nwg))) return rc;
+    nparts += nwg;
+  }
+  // and the finish of fos_duality_gap
   hipLaunchKernelGGL(fos::dual_finish_kernel, dim3(1), dim3(fos::DF_THREADS), 0, p->stream, (const double*)p->ws.dual_part.get(), nparts,
                      (const double*)p->ws.dual_col.get(), nv, out64);
   LAUNCH_CHECK();

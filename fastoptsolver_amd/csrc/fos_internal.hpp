@@ -21,6 +21,7 @@
 #include "../../include/fos_link_loss.h"
 #include "../../include/fos_working_set.h"
 #include "../../include/fos_duality.h"
+#include "../../include/fos_multinomial_ws.h"
 #pragma GCC visibility pop
 #include "batch_trial.hpp"
 #include "cluster_pass.hpp"
@@ -286,10 +287,10 @@ struct Scratch {
   DevBuf<float> vring;               // fos_power_iter, streaming plans: the iterates of the last 16 steps (16 x n rounded up to 4)
   DevBuf<float> rcols16;             // column-sharded candidate pass: m x 16 partial residuals (summed over the ranks)
   DevBuf<float> b16;                 // several right-hand sides: m x 16 zero-padded block of the caller's B (stage_b16)
-  DevBuf<double> link_part;          // fos_residual_batch / _folds behind a link kernel: its partials of all panels (panels x ncu x 16; pointwise link: x 2 ncu)
+  DevBuf<double> link_part;          // fos_residual_batch / _folds behind a link kernel: its partials of all panels (panels x ncu x 16; pointwise link: x 2 ncu); fos_multinomial_gradient_batch: the softmax link's likewise
   DevBuf<double> grad_part;          // fos_gradient_batch with loss16 on several row panels: product 1's partials of all panels (panels x (3 ncu + 8) x 16)
-  DevBuf<double> dual_part;          // fos_duality_gap: the row pass's partials of all panels (panels x 2 ncu x 32)
-  DevBuf<double> dual_col;           // fos_duality_gap: the column pass's 16 scales, 16 penalty sums and 16 conjugate sums
+  DevBuf<double> dual_part;          // fos_duality_gap, fos_multinomial_duality_gap: the row pass's partials of all panels (panels x 2 ncu x 32)
+  DevBuf<double> dual_col;           // fos_duality_gap, fos_multinomial_duality_gap: the column pass's 16 scales, 16 penalty sums and 16 conjugate sums
   DevBuf<double> mfold;              // column-sharded lockstep: 16 x 4 folded step partials (summed over the ranks)
   DevBuf<double> cr_part;            // chip-resident loop (chip_resident.hpp): [2][G][17] partials + [8] step sums + [1] rr
   DevBuf<unsigned> cr_bar;

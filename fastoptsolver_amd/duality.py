@@ -22,6 +22,8 @@ such a column is returned with ``certified`` False, never silently.
 
 Served: squared, logistic, Huber and squared-hinge loss, sample weights, penalty factors.  Not served (ValueError before any device
 work): box bounds, feature groups, the group penalty, the multinomial loss, sharded problems.
+The multinomial loss and the group penalty over the classes have names of their own: ``multinomial_ws.multinomial_duality_gap`` and
+``multinomial_ws.multinomial_certified_path``.
 """
 from __future__ import annotations
 
@@ -69,16 +71,20 @@ def duality_gap(prob, X, alphas):
     return DualityGap(*(np.concatenate([part[i] for part in parts]) for i in range(4)))
 
 
-def _certified_group(prob, fam, alphas, gap_tol, max_iter, max_rounds, grow, max_fraction, L, t_init_factor):
-    """One group of up to 16 weights: (X as an n_dev x nv float64 device block, GapInfo)."""
-    nv, a1s = len(alphas), [a1 for a1, _ in alphas]
+_STEPS = _ws._STEPS._replace(certificate=_certificate)
+
+
+def _certified_group(prob, fam, alphas, gap_tol, max_iter, max_rounds, grow, max_fraction, L, t_init_factor, steps=_STEPS):
+    """One group of weights (up to 16 columns; `working_set._Steps`): (X as an n_dev x (fits * width) float64 device block,
+    GapInfo)."""
+    nv, a1s = len(alphas) * steps.width, [a1 for a1, _ in alphas]
     pf = _ws._factors(prob)
     X = torch.zeros(prob.n_dev, nv, dtype=torch.float64, device=prob.device)
     free = _ws._mask(prob) if pf is None else (pf == 0).to(torch.uint8)
-    primal, dual, gap, scale, G = _certificate(prob, X, alphas)          # at X = 0: P_j(0) and the first violators
+    primal, dual, gap, scale, G = steps.certificate(prob, X, alphas)     # at X = 0: P_j(0) and the first violators
     certificates = 1
     bound = gap_tol * primal
-    _, viol = prob.kkt_scan(G, a1s, 0.0, free)
+    _, viol = steps.scan(prob, G, a1s, 0.0, free)
     mask = free.clone()
     mask[viol.long()] = 1
     limit = max_fraction * prob.n
@@ -99,7 +105,7 @@ def _certified_group(prob, fam, alphas, gap_tol, max_iter, max_rounds, grow, max
                 p_ws = torch.ones(n_ws_pad, dtype=torch.float64)
                 p_ws[:n_ws] = pf[idx].to("cpu", torch.float64)
                 p_ws = p_ws.numpy()
-            sub = _ws._sub_problem(prob, A_ws, p_ws)
+            sub = steps.sub_problem(prob, A_ws, p_ws)
             prms = _its._path_params(sub, alphas, L, fam, t_init_factor, None)
         X0 = None
         if len(sizes) > 1 or bool((X != 0).any()):
@@ -107,9 +113,9 @@ def _certified_group(prob, fam, alphas, gap_tol, max_iter, max_rounds, grow, max
             X0[:n_ws] = X[idx]
         Xs = _ws._lockstep(sub, fam, prms, X0, max_iter)
         X[idx] = Xs[:n_ws]
-        primal, dual, gap, scale, G = _certificate(prob, X, alphas)
+        primal, dual, gap, scale, G = steps.certificate(prob, X, alphas)
         certificates += 1
-        excess, viol = prob.kkt_scan(G, a1s, 0.0, mask)  # the certificate's own gradient: no second one is taken
+        excess, viol = steps.scan(prob, G, a1s, 0.0, mask)   # the certificate's own gradient: no second one is taken
         count = int(viol.numel())
         if count == 0:                                   # the zeros are right and the gap is not there yet: the same set again
             continue
@@ -123,7 +129,7 @@ def _certified_group(prob, fam, alphas, gap_tol, max_iter, max_rounds, grow, max
         sub = A_ws = None
         prms = _its._path_params(prob, alphas, L, fam, t_init_factor, None)
         X = _ws._lockstep(prob, fam, prms, X if bool((X != 0).any()) else None, max_iter)
-        primal, dual, gap, scale, G = _certificate(prob, X, alphas)
+        primal, dual, gap, scale, G = steps.certificate(prob, X, alphas)
         certificates += 1
     return X, GapInfo(len(sizes), sizes, certificates, primal, dual, gap, scale, gap <= bound, fell_back)
 

@@ -25,7 +25,9 @@ so that a feature is in the model for all C classes or for none: every class han
 quantities on a grouped handle.  Penalty factors compose with it; box bounds do not (ValueError).  Not served: sparse-group mixtures, groups of coefficients within one column, sharded problems.
 
 The fits of a class group are one joint problem, so only plain runs exist: there is no ``tol_ratio``, ``adaptive_restart`` or
-``restart_threshold`` here - a stop or restart decided per column would break the fit.
+``restart_threshold`` here - a stop or restart decided per column would break the fit.  What says how far a result is from the
+optimum, and a solve on the active rows of X alone, live in ``multinomial_ws`` (``multinomial_duality_gap``,
+``multinomial_certified_path``, ``multinomial_working_set_path``).
 """
 from __future__ import annotations
 

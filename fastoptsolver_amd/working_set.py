@@ -15,6 +15,7 @@ group is solved by the full lockstep, warm-started, and reported as fallen back:
 
 Served: squared and logistic loss, sample weights, penalty factors (p_i = 0 keeps a coordinate in every set).  Not served
 (ValueError before any device work): box bounds, feature groups, the group penalty, the multinomial loss, sharded problems.
+The multinomial loss and the group penalty over the classes have names of their own: ``multinomial_ws.multinomial_working_set_path``.
 """
 from __future__ import annotations
 
@@ -143,13 +144,14 @@ def alpha_max(prob):
 
 def _lockstep(prob, fam, prms, X0, max_iter):
     """The lockstep of one group on `prob`, warm-started from the columns of X0 (None: from zero, the handles `fista_path`
-    makes): the n_dev x nv float64 device block of the iterates after max_iter iterations."""
+    makes): the n_dev x nv float64 device block of the iterates after max_iter iterations.  A family of fam.width columns per
+    fit has that many handles per parameter set, fit-major (`_run_path`)."""
     handles = []
-    for v, prm in enumerate(prms):
+    for v, prm in enumerate(p for p in prms for _ in range(fam.width)):
         st = _core.Fista(prob)
         st.reset(**prm, x0=None if X0 is None else X0[:, v].contiguous())
         handles.append(st)
-    if (fam.refusal is None and len(handles) == 1) or not fam.launch(handles, 0, len(handles)):
+    if (fam.refusal is None and len(handles) == 1) or not fam.launch(handles, 0, len(prms)):
         if fam.refusal is not None:
             raise _its._refused(prob, fam.refusal)
         for st in handles:
@@ -160,9 +162,18 @@ def _lockstep(prob, fam, prms, X0, max_iter):
     return out
 
 
-def _solve_group(prob, fam, alphas, max_iter, kkt_tol, max_rounds, grow, max_fraction, L, t_init_factor, initial):
-    """One group of up to 16 weights: (X as an n_dev x nv float64 device block, WorkingSetInfo)."""
-    nv, a1s = len(alphas), [a1 for a1, _ in alphas]
+# What the outer loops (`_solve_group`, `duality._certified_group`) take from the device, so that a family whose fit spans
+# several columns runs the same loops (multinomial_ws.py).  width: columns per fit.  gradient(prob, X) -> the gradient block.
+# scan(prob, G, a1s, slack, in_ws) -> (excess, violators), one weight per fit.  sub_problem(prob, A_ws, p_ws) -> the problem on
+# the gathered columns.  certificate(prob, X, alphas) -> (primal, dual, gap, scale per fit, G): duality.py's.
+_Steps = collections.namedtuple("_Steps", "width gradient scan sub_problem certificate")
+_STEPS = _Steps(1, lambda prob, X: prob.gradient_block(X), lambda prob, G, a1s, slack, in_ws: prob.kkt_scan(G, a1s, slack, in_ws),
+                _sub_problem, None)
+
+
+def _solve_group(prob, fam, alphas, max_iter, kkt_tol, max_rounds, grow, max_fraction, L, t_init_factor, initial, steps=_STEPS):
+    """One group of weights (up to 16 columns): (X as an n_dev x (fits * width) float64 device block, WorkingSetInfo)."""
+    nv, a1s = len(alphas) * steps.width, [a1 for a1, _ in alphas]
     pf = _factors(prob)
     X = torch.zeros(prob.n_dev, nv, dtype=torch.float64, device=prob.device)
     full_gradients, sizes = 0, []
@@ -171,7 +182,7 @@ def _solve_group(prob, fam, alphas, max_iter, kkt_tol, max_rounds, grow, max_fra
         worst = float("nan")
     else:
         free = _mask(prob) if pf is None else (pf == 0).to(torch.uint8)
-        excess, viol = prob.kkt_scan(prob.gradient_block(X), a1s, 0.0, free)
+        excess, viol = steps.scan(prob, steps.gradient(prob, X), a1s, 0.0, free)
         full_gradients += 1
         mask = free.clone()
         mask[viol.long()] = 1
@@ -194,7 +205,7 @@ def _solve_group(prob, fam, alphas, max_iter, kkt_tol, max_rounds, grow, max_fra
             p_ws = torch.ones(n_ws_pad, dtype=torch.float64)
             p_ws[:n_ws] = pf[idx].to("cpu", torch.float64)
             p_ws = p_ws.numpy()
-        sub = _sub_problem(prob, A_ws, p_ws)
+        sub = steps.sub_problem(prob, A_ws, p_ws)
         prms = _its._path_params(sub, alphas, L, fam, t_init_factor, None)
         X0 = None
         if len(sizes) > 1 or bool((X != 0).any()):
@@ -203,7 +214,7 @@ def _solve_group(prob, fam, alphas, max_iter, kkt_tol, max_rounds, grow, max_fra
         Xs = _lockstep(sub, fam, prms, X0, max_iter)
         X[idx] = Xs[:n_ws]
         del sub, A_ws                                    # one gathered matrix at a time
-        excess, viol = prob.kkt_scan(prob.gradient_block(X), a1s, kkt_tol, mask)
+        excess, viol = steps.scan(prob, steps.gradient(prob, X), a1s, kkt_tol, mask)
         full_gradients += 1
         worst = float(excess.max())
         count = int(viol.numel())
@@ -217,7 +228,7 @@ def _solve_group(prob, fam, alphas, max_iter, kkt_tol, max_rounds, grow, max_fra
     if fell_back:
         prms = _its._path_params(prob, alphas, L, fam, t_init_factor, None)
         X = _lockstep(prob, fam, prms, X if bool((X != 0).any()) else None, max_iter)
-        excess, _ = prob.kkt_scan(prob.gradient_block(X), a1s, kkt_tol, (X != 0).any(dim=1).to(torch.uint8))
+        excess, _ = steps.scan(prob, steps.gradient(prob, X), a1s, kkt_tol, (X != 0).any(dim=1).to(torch.uint8))
         full_gradients += 1
         worst = float(excess.max())
     return X, WorkingSetInfo(len(sizes), sizes, full_gradients, worst, fell_back)
