@@ -742,12 +742,15 @@ class Problem:
         """The gradient of the data term at the nv <= 16 columns of X (n x nv): A^T W (A X_j - b), or A^T W (sigma(A X_j) - b) on
         a logistic handle (fos_gradient_batch), as the nv x n_dev float32 device block fos_kkt_scan reads (row j: column j).
         want_loss: also the data-term sums of `residual_batch` from the same pass, as a host list (synchronises)."""
+        return self._gradient_block("fos_gradient_batch", X, want_loss, 1)
+
+    def _gradient_block(self, entry, X, want_loss, stride):
+        """`gradient_block` / `multinomial_gradient_block`: the loss sums of the fits are every stride-th of the 16."""
         Xf, nv = self._block16(X)
         G = torch.empty(nv, self.n_dev, dtype=torch.float32, device=self.device)
         with self.ctx():
-            _lib.check(self.lib.fos_gradient_batch(ptr(Xf), nv, self.h, ptr(G), ptr(self.scratch) if want_loss else None),
-                       "fos_gradient_batch")
-        return (G, self.scratch[:nv].cpu().tolist()) if want_loss else G
+            _lib.check(getattr(self.lib, entry)(ptr(Xf), nv, self.h, ptr(G), ptr(self.scratch) if want_loss else None), entry)
+        return (G, self.scratch[:nv:stride].cpu().tolist()) if want_loss else G
 
     def gradient_batch(self, X):
         """`gradient_block` in the layout of `gram_apply`: an n x nv float32 device tensor.  Enqueues only."""
@@ -778,13 +781,15 @@ class Problem:
         `gradient_block`: (excess - n_dev floats on the device -, the violators in increasing order as an int32 device tensor).
         alpha1: nv host weights; in_ws: n_dev device bytes, non-zero inside the set.  Synchronises (the count is read)."""
         nv = int(G.shape[0])
-        a1 = (C.c_double * nv)(*[float(a) for a in alpha1])
+        return self._scan("fos_kkt_scan", G, (nv,), (C.c_double * nv)(*[float(a) for a in alpha1]), slack, in_ws)
+
+    def _scan(self, entry, G, head, a1, slack, in_ws):
+        """`kkt_scan` / `multinomial_kkt_scan`; head: the arguments between G and the weights."""
         excess = torch.empty(self.n_dev, dtype=torch.float32, device=self.device)
         viol = torch.empty(self.n_dev, dtype=torch.int32, device=self.device)
         count = torch.zeros(1, dtype=torch.int32, device=self.device)
         with self.ctx():
-            _lib.check(self.lib.fos_kkt_scan(ptr(G), nv, a1, float(slack), ptr(in_ws), self.h, ptr(excess), ptr(viol), ptr(count)),
-                       "fos_kkt_scan")
+            _lib.check(getattr(self.lib, entry)(ptr(G), *head, a1, float(slack), ptr(in_ws), self.h, ptr(excess), ptr(viol), ptr(count)), entry)
         return excess, viol[: int(count.item())]
 
     # ---- duality-gap certificate (include/fos_duality.h; duality.py drives this) ---------------------------------------
@@ -793,12 +798,15 @@ class Problem:
         fos_duality_gap): (out64 - 64 device doubles: primal[16], dual[16], gap[16], scale[16] -, G - the nv x n_dev float32
         gradient block of `gradient_block` at X, from the same pass).  Enqueues only."""
         Xf, nv = self._block16(X)
-        a1 = (C.c_double * nv)(*[float(a) for a in alpha1])
-        a2 = (C.c_double * nv)(*[float(a) for a in alpha2])
-        G = torch.empty(nv, self.n_dev, dtype=torch.float32, device=self.device)
+        return self._gap_block("fos_duality_gap", Xf, (nv,), (C.c_double * nv)(*[float(a) for a in alpha1]),
+                               (C.c_double * nv)(*[float(a) for a in alpha2]))
+
+    def _gap_block(self, entry, Xf, head, a1, a2):
+        """`duality_gap_block` / `multinomial_duality_gap_block`; head: the arguments between X and the weights, nv first."""
+        G = torch.empty(head[0], self.n_dev, dtype=torch.float32, device=self.device)
         out64 = torch.empty(64, dtype=torch.float64, device=self.device)
         with self.ctx():
-            _lib.check(self.lib.fos_duality_gap(ptr(Xf), nv, a1, a2, self.h, ptr(G), ptr(out64)), "fos_duality_gap")
+            _lib.check(getattr(self.lib, entry)(ptr(Xf), *head, a1, a2, self.h, ptr(G), ptr(out64)), entry)
         return out64, G
 
     # ---- working set and duality gap of the multinomial lockstep (include/fos_multinomial_ws.h; multinomial_ws.py drives these)
@@ -807,12 +815,7 @@ class Problem:
         multinomial handle: A^T (w (softmax(A X_s)_c - [y = c])) as the nv x n_dev float32 device block `multinomial_kkt_scan`
         reads (fos_multinomial_gradient_batch).  want_loss: also the cross-entropy sums of `residual_batch` from the same pass,
         one per fit, as a host list (synchronises)."""
-        Xf, nv = self._block16(X)
-        G = torch.empty(nv, self.n_dev, dtype=torch.float32, device=self.device)
-        with self.ctx():
-            _lib.check(self.lib.fos_multinomial_gradient_batch(ptr(Xf), nv, self.h, ptr(G), ptr(self.scratch) if want_loss else None),
-                       "fos_multinomial_gradient_batch")
-        return (G, self.scratch[:nv:self.classes].cpu().tolist()) if want_loss else G
+        return self._gradient_block("fos_multinomial_gradient_batch", X, want_loss, self.classes)
 
     def multinomial_kkt_scan(self, G, alpha1, slack, in_ws, grouped=None):
         """The optimality check of the coordinates (rows of X) outside a working set on the nv x n_dev block G of
@@ -823,14 +826,8 @@ class Problem:
         a1 = (C.c_double * len(alpha1))(*[float(a) for a in alpha1])
         if self.classes and len(alpha1) * self.classes != nv:
             raise ValueError(f"alpha1: one weight per fit expected ({nv} columns, {self.classes} classes), got {len(alpha1)}")
-        excess = torch.empty(self.n_dev, dtype=torch.float32, device=self.device)
-        viol = torch.empty(self.n_dev, dtype=torch.int32, device=self.device)
-        count = torch.zeros(1, dtype=torch.int32, device=self.device)
         grouped = self.grouped if grouped is None else grouped
-        with self.ctx():
-            _lib.check(self.lib.fos_multinomial_kkt_scan(ptr(G), nv, int(bool(grouped)), a1, float(slack), ptr(in_ws), self.h, ptr(excess),
-                                                         ptr(viol), ptr(count)), "fos_multinomial_kkt_scan")
-        return excess, viol[: int(count.item())]
+        return self._scan("fos_multinomial_kkt_scan", G, (nv, int(bool(grouped))), a1, slack, in_ws)
 
     def multinomial_duality_gap_block(self, X, alpha1, alpha2, grouped=None):
         """The duality-gap certificate of the fits in the columns of X (n x nv, nv a multiple of C) under the host weights alpha1,
@@ -840,15 +837,9 @@ class Problem:
         Xf, nv = self._block16(X)
         if self.classes and (len(alpha1) * self.classes != nv or len(alpha2) != len(alpha1)):
             raise ValueError(f"alpha1, alpha2: one weight per fit expected ({nv} columns, {self.classes} classes)")
-        a1 = (C.c_double * len(alpha1))(*[float(a) for a in alpha1])
-        a2 = (C.c_double * len(alpha2))(*[float(a) for a in alpha2])
-        G = torch.empty(nv, self.n_dev, dtype=torch.float32, device=self.device)
-        out64 = torch.empty(64, dtype=torch.float64, device=self.device)
         grouped = self.grouped if grouped is None else grouped
-        with self.ctx():
-            _lib.check(self.lib.fos_multinomial_duality_gap(ptr(Xf), nv, int(bool(grouped)), a1, a2, self.h, ptr(G), ptr(out64)),
-                       "fos_multinomial_duality_gap")
-        return out64, G
+        return self._gap_block("fos_multinomial_duality_gap", Xf, (nv, int(bool(grouped))), (C.c_double * len(alpha1))(*[float(a) for a in alpha1]),
+                               (C.c_double * len(alpha2))(*[float(a) for a in alpha2]))
 
     def power_iter(self, v0, n_iter=100, tol=1e-6):
         """The reference's power iteration (ref:45-60) from v0 (n values, need not be normalised): ``(L, it, v)``.  On every

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "batch_trial.hpp"
+#include "working_set.hpp"
 
 namespace fos {
 
@@ -33,8 +34,6 @@ constexpr int DL_WIDTH = 2 * BT_NV;      // a row of the partial buffer: 16 prim
 constexpr int DS_THREADS = 256;          // column pass: one workgroup per column
 // LOSS of dual_link_kernel: the loss ids of fos.h.  A multinomial problem (2) is refused before any launch.
 constexpr int DUAL_SQUARED = 0, DUAL_LOGISTIC = 1, DUAL_HUBER = 3, DUAL_SQUARED_HINGE = 4;
-
-struct DualWeights { double a1[BT_NV], a2[BT_NV]; };
 
 __device__ __forceinline__ double dual_xlogx(double q) { return q > 0.0 ? q * log(q) : 0.0; }
 
@@ -128,12 +127,17 @@ __global__ __launch_bounds__(DL_THREADS) void dual_link_kernel(const float* __re
 }
 
 // ---- column pass --------------------------------------------------------------------------------------------------------------
-// Workgroup j < nv walks the n coordinates of column j twice, all in fp64: first the scale
-//     s_j = min(1, min over {k : rho_k = 0 and G_jk != 0} of tau_k / (double)|G_jk|),   tau_k = a1[j] * (double)p_k,
-// (the minimum of an empty set is 1), then, with it, pen_j = sum_k tau_k |x_k| + rho_k x_k^2 / 2 and conj_j = sum over
-// {k : rho_k > 0} of max(s_j |G_jk| - tau_k, 0)^2 / (2 rho_k).  X: n x 16 floats, row-major (the layout of fos_gradient_batch);
-// G: nv x n floats; factor: the bound penalty factors or null (1).  col[j] = s_j, col[16 + j] = pen_j, col[32 + j] = conj_j.
-// Fixed-order trees through LDS.  Resources (gfx950, -O3): 32 VGPRs, no scratch, 2 KiB of LDS.
+// The columns of a block are fits of C columns each (the segments of kkt_scan_kernel; C = 1 for every loss but the multinomial
+// one).  Workgroup s < nv / C walks the n x C entries of segment s twice, all in fp64, with tau_k = a1[s] * (double)p_k and
+// rho_k = a2[s] * (double)p_k.  v runs over the entries (k, c), v = |G_kc| - or, grouped, over the rows k, v = ||G_k:||_2 (the
+// squares summed with c ascending).  First the scale
+//     s = min(1, min over {rho = 0 and v != 0} of tau / v)                    (the minimum of an empty set is 1),
+// then, with it, pen = sum tau |x| + rho x^2 / 2 (grouped: of the row norms) and conj = sum over {rho > 0} of
+// max(s v - tau, 0)^2 / (2 rho).  X: n x 16 floats, row-major (the layout of fos_gradient_batch; the C entries of a row are
+// adjacent); G: nv x n floats; factor: the bound penalty factors or null (1).  col[s*C] = the scale, col[16 + s*C] = pen,
+// col[32 + s*C] = conj, and 0 in the other C - 1 entries of the segment in all three, so that dual_finish_kernel adds entry j of
+// the column pass to entry j of the row pass for every family.
+// Fixed-order trees through LDS.  Resources (gfx950, -O3): 38 VGPRs, no scratch, 2 KiB of LDS.
 __device__ __forceinline__ double dual_block_sum(double v, double* red) {
   const int tid = threadIdx.x;
   __syncthreads();                   // the readers of the previous tree are done
@@ -161,38 +165,69 @@ __device__ __forceinline__ double dual_block_min(double v, double* red) {
 }
 
 static __global__ __launch_bounds__(DS_THREADS) void dual_scale_kernel(const float* __restrict__ X, const float* __restrict__ G,
-                                                                       int64_t n, DualWeights wts,
+                                                                       int64_t n, int classes, int grouped, ClassWeights wts,
                                                                        const float* __restrict__ factor,
                                                                        double* __restrict__ col) {
   __shared__ double red[DS_THREADS];
-  const int tid = threadIdx.x, j = blockIdx.x;
-  const double a1 = wts.a1[j], a2 = wts.a2[j];
-  const float* __restrict__ g = G + (int64_t)j * n;
+  const int tid = threadIdx.x, seg = blockIdx.x, lo = seg * classes;
+  const double a1 = wts.a1[seg], a2 = wts.a2[seg];
+  const float* __restrict__ g = G + (int64_t)lo * n;
   double smin = 1.0;
   for (int64_t k = tid; k < n; k += DS_THREADS) {
     const double pf = factor ? (double)factor[k] : 1.0;
     const double tau = a1 * pf, rho = a2 * pf;
-    const double a = (double)fabsf(g[k]);
-    if (rho == 0.0 && a != 0.0) smin = fmin(smin, tau / a);
+    if (rho != 0.0) continue;
+    if (grouped) {
+      double q = 0.0;
+      for (int c = 0; c < classes; ++c) {
+        const double a = (double)g[(int64_t)c * n + k];
+        q += a * a;
+      }
+      const double v = sqrt(q);
+      if (v != 0.0) smin = fmin(smin, tau / v);
+    } else {
+      for (int c = 0; c < classes; ++c) {
+        const double a = (double)fabsf(g[(int64_t)c * n + k]);
+        if (a != 0.0) smin = fmin(smin, tau / a);
+      }
+    }
   }
   const double s = dual_block_min(smin, red);
   double pen = 0.0, conj = 0.0;
   for (int64_t k = tid; k < n; k += DS_THREADS) {
     const double pf = factor ? (double)factor[k] : 1.0;
     const double tau = a1 * pf, rho = a2 * pf;
-    const double x = (double)X[k * BT_NV + j];
-    pen += tau * fabs(x) + 0.5 * rho * x * x;
-    if (rho > 0.0) {
-      const double e = fmax(s * (double)fabsf(g[k]) - tau, 0.0);
-      conj += e * e / (2.0 * rho);
+    const float* __restrict__ x = X + k * BT_NV + lo;
+    if (grouped) {
+      double x2 = 0.0, q = 0.0;
+      for (int c = 0; c < classes; ++c) {
+        const double xv = (double)x[c], a = (double)g[(int64_t)c * n + k];
+        x2 += xv * xv;
+        q += a * a;
+      }
+      pen += tau * sqrt(x2) + 0.5 * rho * x2;
+      if (rho > 0.0) {
+        const double e = fmax(s * sqrt(q) - tau, 0.0);
+        conj += e * e / (2.0 * rho);
+      }
+    } else {
+      for (int c = 0; c < classes; ++c) {
+        const double xv = (double)x[c];
+        pen += tau * fabs(xv) + 0.5 * rho * xv * xv;
+        if (rho > 0.0) {
+          const double e = fmax(s * (double)fabsf(g[(int64_t)c * n + k]) - tau, 0.0);
+          conj += e * e / (2.0 * rho);
+        }
+      }
     }
   }
   pen = dual_block_sum(pen, red);
   conj = dual_block_sum(conj, red);
-  if (tid == 0) {
-    col[j] = s;
-    col[BT_NV + j] = pen;
-    col[2 * BT_NV + j] = conj;
+  if (tid < classes) {
+    const bool first = tid == 0;
+    col[lo + tid] = first ? s : 0.0;
+    col[BT_NV + lo + tid] = first ? pen : 0.0;
+    col[2 * BT_NV + lo + tid] = first ? conj : 0.0;
   }
 }
 

@@ -1571,60 +1571,114 @@ int fos_fista_run_batch(const void* A, int a_dtype, const float* b, const fos_ba
 
 }  // extern "C"
 
-// ---- Working-set solve (include/fos_working_set.h, working_set.hpp) ---------------------------------------------------------
-extern "C" {
+// ---- Working-set solve and duality-gap certificate of every loss family (include/fos_working_set.h, fos_duality.h,
+// fos_multinomial_ws.h; working_set.hpp, duality.hpp, multinomial_ws.hpp) -------------------------------------------------------
+// The shapes the two-product walks serve: b (or the labels) bound, one card, the matrix-core pair.  needs_b: the caller's words
+// for a problem without b.
+static int need_two_products(const fos_problem* p, const std::string& fn, const char* needs_b) {
+  if (!p->b) return fail(FOS_ERR_UNSUPPORTED, fn + ": " + needs_b);
+  if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, fn + ": sharded problems are not served");
+  if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, fn + ": the shape has no matrix-core pair");
+  return FOS_OK;
+}
 
-// The gradient of the data term at the nv columns of X: per row panel product 1 in its storing form (b, the problem's loss
-// epilogue, the bound weights) and product 2, then the slab sum of fos_gram_apply.  Product 1 leaves the loss partials of the
-// panel in cand.q_part; with several panels they are copied behind each other (ws.grad_part) and folded once.
-// On a Huber or squared-hinge problem product 1 runs plain and the pointwise link kernel leaves R and the partials instead.
-int fos_gradient_batch(const float* X, int nv, fos_problem* p, float* G, double* loss16) {
-  if (!X || !p || !G || nv < 1 || nv > fos::BT_NV)
-    return fail(FOS_ERR_ARG, "fos_gradient_batch: bad argument (null pointer or nv outside 1..16)");
-  if (p->loss == FOS_LOSS_MULTINOMIAL)
-    return fail(FOS_ERR_UNSUPPORTED, "fos_gradient_batch: a multinomial problem is not served (squared and logistic loss)");
-  if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_gradient_batch: the gradient of the data term needs b");
-  if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_gradient_batch: sharded problems are not served");
-  if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_gradient_batch: the shape has no matrix-core pair");
-  int rc = ensure_batch_workspace(p);
+// The checks the three multinomial entry points share, after their own FOS_ERR_ARG rows: a multinomial problem whose class
+// count divides nv.
+static int need_class_segments(const fos_problem* p, int nv, const char* fn) {
+  if (p->loss != FOS_LOSS_MULTINOMIAL)
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the problem is not multinomial (fos_gradient_batch, fos_kkt_scan and "
+                                     "fos_duality_gap serve the other losses)");
+  if (p->classes < 2 || nv % p->classes != 0)
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": nv is not a multiple of the " + std::to_string(p->classes) + " classes");
+  return FOS_OK;
+}
+
+// The per-fit weights of a call (HOST memory, nfits each: nv, or nv / C on a multinomial problem; a2 may be null), checked:
+// FOS_ERR_ARG before any HIP call.
+static int class_weights(int nfits, const double* a1, const double* a2, const char* fn, fos::ClassWeights* w) {
+  *w = fos::ClassWeights{};
+  for (int s = 0; s < nfits; ++s) {
+    if (!(std::isfinite(a1[s]) && a1[s] >= 0.0) || (a2 && !(std::isfinite(a2[s]) && a2[s] >= 0.0)))
+      return fail(FOS_ERR_ARG, std::string(fn) + ": weight " + std::to_string(s) + " is not finite and >= 0");
+    w->a1[s] = a1[s];
+    w->a2[s] = a2 ? a2[s] : 0.0;
+  }
+  return FOS_OK;
+}
+
+// What a loss family puts between product 1 and product 2 of the gradient walk.
+enum class WalkLink { none, pointwise, softmax };
+struct GradientWalk {
+  const char* fn;        // the entry point, for the messages
+  const char* needs_b;   // its words for a problem without b
+  bool plain;            // product 1 without b and the bound weights (Z = A_panel X: a link kernel follows); else with them
+  WalkLink link;         // none: product 1's own loss epilogue; launch_pointwise_link; launch_softmax_link
+  bool staged;           // the panel's partials land in cand.q_part (several panels: copied behind each other into
+                         // ws.grad_part); else behind those of the panels before it in ws.link_part
+};
+
+// The gradient of the data term at the nv columns of X: per row panel product 1 in its storing form, the family's link stage and
+// product 2, then the slab sum of fos_gram_apply and, for loss16, one fold of the loss partials of all panels.
+static int gradient_walk(const GradientWalk& w, const float* X, int nv, fos_problem* p, float* G, double* loss16) {
+  int rc = need_two_products(p, w.fn, w.needs_b);
   if (rc) return rc;
+  if ((rc = ensure_batch_workspace(p))) return rc;
   if ((rc = plan_multi_mfma(p))) return rc;
   int g_splits = 0;
   if ((rc = two_product_splits(p, &g_splits))) return rc;
-  const bool link = link_loss(p);
   const int64_t panels = (p->m + p->multi.panel_rows - 1) / p->multi.panel_rows;
   const size_t part_rows = (size_t)(3 * p->ncu + 8);               // the rows of cand.q_part
-  if (loss16 && panels > 1 && (rc = p->ws.grad_part.reserve((size_t)panels * part_rows * fos::BT_NV))) return rc;
+  const bool copied = w.staged && loss16 && panels > 1;
+  if (copied && (rc = p->ws.grad_part.reserve((size_t)panels * part_rows * fos::BT_NV))) return rc;
+  if (!w.staged && (rc = p->ws.link_part.reserve((size_t)panels * p->ncu * fos::BT_NV))) return rc;
   const int64_t esz = p->dtype == FOS_BF16 ? 2 : 4;
   if ((rc = pack_candidates(p, X, nv))) return rc;
   int nparts = 0;
   for (int64_t row0 = 0, panel = 0; row0 < p->m; row0 += p->multi.panel_rows, ++panel) {
     const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
     const char* Ap = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz;
-    int nwg1 = 0;
-    BatchLaunch L{};                 // R = w (A_panel X - b) or w (sigma(A_panel X) - b); labels and weights are offset with the panel
-    L.A = Ap; L.b = p->b + row0; L.use_b = 1; L.rows = rows; L.rout = p->multi.rbuf16;
-    L.row_weight = p->row_weight ? p->row_weight + row0 : nullptr;
-    if (link) { L.b = nullptr; L.use_b = 0; L.row_weight = nullptr; }      // Z = A_panel X; the link kernel forms R and the loss partials
-    if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
-    if (link && (rc = launch_pointwise_link(p, row0, rows, nv, fos::FOLD_OFF, nullptr, nullptr, p->cand.q_part, &nwg1))) return rc;
-    if (loss16 && panels > 1) {
-      if ((size_t)nwg1 > part_rows) return fail(FOS_ERR_STATE, "fos_gradient_batch: product 1 wrote more partials than cand.q_part holds");
-      HIP_TRY(hipMemcpyAsync(p->ws.grad_part + (size_t)nparts * fos::BT_NV, p->cand.q_part, (size_t)nwg1 * fos::BT_NV * sizeof(double),
+    int nwg = 0;
+    BatchLaunch L{};                 // plain: Z = A_panel X; else R = w (A_panel X - b) or w (sigma(A_panel X) - b)
+    L.A = Ap; L.rows = rows; L.rout = p->multi.rbuf16;
+    if (!w.plain) {                  // labels and weights are offset with the panel
+      L.b = p->b + row0; L.use_b = 1;
+      L.row_weight = p->row_weight ? p->row_weight + row0 : nullptr;
+    }
+    if ((rc = launch_batch_product(p, L, &nwg))) return rc;
+    double* part = w.staged ? p->cand.q_part.get() : p->ws.link_part + (size_t)nparts * fos::BT_NV;
+    if (w.link == WalkLink::pointwise && (rc = launch_pointwise_link(p, row0, rows, nv, fos::FOLD_OFF, nullptr, nullptr, part, &nwg))) return rc;
+    if (w.link == WalkLink::softmax && (rc = launch_softmax_link(p, row0, rows, nv, fos::FOLD_OFF, nullptr, nullptr, part, &nwg))) return rc;
+    if (copied) {
+      if ((size_t)nwg > part_rows) return fail(FOS_ERR_STATE, std::string(w.fn) + ": product 1 wrote more partials than cand.q_part holds");
+      HIP_TRY(hipMemcpyAsync(p->ws.grad_part + (size_t)nparts * fos::BT_NV, part, (size_t)nwg * fos::BT_NV * sizeof(double),
                              hipMemcpyDeviceToDevice, p->stream));
     }
-    nparts += nwg1;
+    nparts += nwg;
     if ((rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
   }
   hipLaunchKernelGGL(gram_slab_sum_kernel, dim3(grid_1d((int64_t)nv * p->n, 256, 1024)), dim3(256), 0, p->stream, p->multi.slabs16,
                      g_splits, p->n, nv, G);
   LAUNCH_CHECK();
   if (loss16) {
-    hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream,
-                       panels > 1 ? p->ws.grad_part.get() : p->cand.q_part.get(), nparts, fos::BT_NV, loss16);
+    const double* parts = !w.staged ? p->ws.link_part.get() : copied ? p->ws.grad_part.get() : p->cand.q_part.get();
+    hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, parts, nparts, fos::BT_NV, loss16);
     LAUNCH_CHECK();
   }
   return FOS_OK;
+}
+
+extern "C" {
+
+// Product 1 runs with b, the problem's loss epilogue and the bound weights and leaves the loss partials itself; on a Huber or
+// squared-hinge problem it runs plain and the pointwise link kernel leaves R and the partials instead.
+int fos_gradient_batch(const float* X, int nv, fos_problem* p, float* G, double* loss16) {
+  if (!X || !p || !G || nv < 1 || nv > fos::BT_NV)
+    return fail(FOS_ERR_ARG, "fos_gradient_batch: bad argument (null pointer or nv outside 1..16)");
+  if (p->loss == FOS_LOSS_MULTINOMIAL)
+    return fail(FOS_ERR_UNSUPPORTED, "fos_gradient_batch: a multinomial problem is not served (squared and logistic loss)");
+  const bool link = link_loss(p);
+  return gradient_walk({"fos_gradient_batch", "the gradient of the data term needs b", link, link ? WalkLink::pointwise : WalkLink::none, true},
+                       X, nv, p, G, loss16);
 }
 
 int fos_gather_columns(const int32_t* idx, int32_t n_ws, void* A_ws, int64_t lda_ws, int32_t n_ws_pad, const fos_problem* p) {
@@ -1652,12 +1706,8 @@ int fos_kkt_scan(const float* G, int nv, const double* alpha1, double slack, con
   if (!G || !alpha1 || !in_ws || !p || !excess || !viol_idx || !viol_count || nv < 1 || nv > fos::BT_NV)
     return fail(FOS_ERR_ARG, "fos_kkt_scan: bad argument (null pointer or nv outside 1..16)");
   if (!(std::isfinite(slack) && slack >= 0.0)) return fail(FOS_ERR_ARG, "fos_kkt_scan: slack is not finite and >= 0");
-  fos::KktWeights w{};
-  for (int j = 0; j < nv; ++j) {
-    if (!(std::isfinite(alpha1[j]) && alpha1[j] >= 0.0))
-      return fail(FOS_ERR_ARG, "fos_kkt_scan: weight " + std::to_string(j) + " is not finite and >= 0");
-    w.a[j] = alpha1[j];
-  }
+  fos::ClassWeights w;
+  if (int rc = class_weights(nv, alpha1, nullptr, "fos_kkt_scan", &w)) return rc;
   if (p->coord_lo || p->coord_hi)
     return fail(FOS_ERR_UNSUPPORTED, "fos_kkt_scan: box bounds (fos_coord_bind) are bound; a coordinate at a bound has another "
                                      "optimality condition");
@@ -1674,10 +1724,9 @@ int fos_kkt_scan(const float* G, int nv, const double* alpha1, double slack, con
 
 }  // extern "C"
 
-// ---- Duality-gap certificate (include/fos_duality.h, duality.hpp) -----------------------------------------------------------
-// The row pass on the `rows` rows of p->multi.rbuf16 that product 1 in its plain storing form has just filled with Z of the panel
-// starting at row0: one lane per 16-byte quad of a row, grid-stride, at most 2 * ncu workgroups; *nwg_out = the rows of `part`
-// written.
+// The row pass of fos_duality_gap on the `rows` rows of p->multi.rbuf16 that product 1 in its plain storing form has just filled
+// with Z of the panel starting at row0: one lane per 16-byte quad of a row, grid-stride, at most 2 * ncu workgroups; *nwg_out =
+// the rows of `part` written.
 static int launch_dual_link(fos_problem* p, int64_t row0, int64_t rows, int nv, const double* scale, double* part, int* nwg_out) {
   const int nwg = (int)std::min<int64_t>((4 * rows + fos::DL_THREADS - 1) / fos::DL_THREADS, 2 * (int64_t)p->ncu);
   const float* w = p->row_weight ? p->row_weight + row0 : nullptr;
@@ -1700,88 +1749,8 @@ static int launch_dual_link(fos_problem* p, int64_t row0, int64_t rows, int nv, 
   return FOS_OK;
 }
 
-extern "C" {
-
-int fos_duality_gap(const float* X, int nv, const double* alpha1, const double* alpha2, fos_problem* p, float* G, double* out64) {
-  if (!X || !alpha1 || !alpha2 || !p || !G || !out64 || nv < 1 || nv > fos::BT_NV)
-    return fail(FOS_ERR_ARG, "fos_duality_gap: bad argument (null pointer or nv outside 1..16)");
-  fos::DualWeights wts{};
-  for (int j = 0; j < nv; ++j) {
-    if (!(std::isfinite(alpha1[j]) && alpha1[j] >= 0.0 && std::isfinite(alpha2[j]) && alpha2[j] >= 0.0))
-      return fail(FOS_ERR_ARG, "fos_duality_gap: weight " + std::to_string(j) + " is not finite and >= 0");
-    wts.a1[j] = alpha1[j];
-    wts.a2[j] = alpha2[j];
-  }
-  if (p->loss == FOS_LOSS_MULTINOMIAL)
-    return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: a multinomial problem is not served (squared, logistic, Huber and squared-hinge loss)");
-  if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: the certificate needs b");
-  if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: sharded problems are not served");
-  if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: the shape has no matrix-core pair");
-  if (p->coord_lo || p->coord_hi)
-    return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: box bounds (fos_coord_bind) are bound; the penalty of a bounded coordinate has "
-                                     "another conjugate");
-  if (has_fgroups(p))
-    return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: feature groups (fos_feature_groups_bind) are bound; the group norm has another "
-                                     "conjugate");
-  // 1. the gradient block, by the launches of fos_gradient_batch (it plans the lockstep and leaves X packed in cand.xp)
-  int rc = fos_gradient_batch(X, nv, p, G, nullptr);
-  if (rc) return rc;
-  const int64_t panels = (p->m + p->multi.panel_rows - 1) / p->multi.panel_rows;
-  const size_t part_rows = (size_t)panels * 2 * (size_t)p->ncu;
-  if ((rc = p->ws.dual_part.reserve(part_rows * fos::DL_WIDTH))) return rc;
-  if ((rc = p->ws.dual_col.reserve(3 * fos::BT_NV))) return rc;
-  // 2. the column pass: the scale of every column, then its penalty and the conjugate of the ridge-carrying coordinates
-  hipLaunchKernelGGL(fos::dual_scale_kernel, dim3(nv), dim3(fos::DS_THREADS), 0, p->stream, X, (const float*)G, p->n, wts,
-                     p->coord_factor, p->ws.dual_col.get());
-  LAUNCH_CHECK();
-  // 3. Z = A_panel X once more (plain: no b, no weights, no mask), and the row pass on it
-  const int64_t esz = p->dtype == FOS_BF16 ? 2 : 4;
-  int nparts = 0;
-  for (int64_t row0 = 0; row0 < p->m; row0 += p->multi.panel_rows) {
-    const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
-    int nwg1 = 0, nwg = 0;
-    BatchLaunch L{};
-    L.A = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz; L.rows = rows; L.rout = p->multi.rbuf16;
-    if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
-    if ((size_t)nparts + 2 * (size_t)p->ncu > part_rows)
-      return fail(FOS_ERR_STATE, "fos_duality_gap: the row pass has more panels than its partial buffer holds");
-    if ((rc = launch_dual_link(p, row0, rows, nv, p->ws.dual_col, p->ws.dual_part + (size_t)nparts * fos::DL_WIDTH, &nwg))) return rc;
-    nparts += nwg;
-  }
-  // 4. the finish
-  hipLaunchKernelGGL(fos::dual_finish_kernel, dim3(1), dim3(fos::DF_THREADS), 0, p->stream, (const double*)p->ws.dual_part.get(), nparts,
-                     (const double*)p->ws.dual_col.get(), nv, out64);
-  LAUNCH_CHECK();
-  return FOS_OK;
-}
-
-}  // extern "C"
-
-// ---- Working set and duality gap of the multinomial lockstep (include/fos_multinomial_ws.h, multinomial_ws.hpp) -------------
-// The checks the three entry points share, after their own FOS_ERR_ARG rows: a multinomial problem whose class count divides nv.
-static int need_class_segments(const fos_problem* p, int nv, const char* fn) {
-  if (p->loss != FOS_LOSS_MULTINOMIAL)
-    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the problem is not multinomial (fos_gradient_batch, fos_kkt_scan and "
-                                     "fos_duality_gap serve the other losses)");
-  if (p->classes < 2 || nv % p->classes != 0)
-    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": nv is not a multiple of the " + std::to_string(p->classes) + " classes");
-  return FOS_OK;
-}
-
-// The per-segment weights of a call (HOST memory, nv / C each; a2 may be null), checked: FOS_ERR_ARG before any HIP call.
-static int class_weights(const fos_problem* p, int nv, const double* a1, const double* a2, const char* fn, fos::ClassWeights* w) {
-  *w = fos::ClassWeights{};
-  for (int s = 0; s < nv / p->classes; ++s) {
-    if (!(std::isfinite(a1[s]) && a1[s] >= 0.0) || (a2 && !(std::isfinite(a2[s]) && a2[s] >= 0.0)))
-      return fail(FOS_ERR_ARG, std::string(fn) + ": weight " + std::to_string(s) + " is not finite and >= 0");
-    w->a1[s] = a1[s];
-    w->a2[s] = a2 ? a2[s] : 0.0;
-  }
-  return FOS_OK;
-}
-
-// The row pass on the `rows` rows of p->multi.rbuf16 that product 1 in its plain storing form has just filled with the logits of
-// the panel starting at row0: one thread per row, grid-stride, at most ncu workgroups; *nwg_out = the rows of `part` written.
+// The row pass of fos_multinomial_duality_gap, on the logits of the panel likewise: one thread per row, grid-stride, at most ncu
+// workgroups.
 static int launch_dual_softmax(fos_problem* p, int64_t row0, int64_t rows, int nv, const double* col, double* part, int* nwg_out) {
   const int nwg = (int)std::min<int64_t>((rows + fos::SL_THREADS - 1) / fos::SL_THREADS, p->ncu);
   const float* w = p->row_weight ? p->row_weight + row0 : nullptr;
@@ -1796,50 +1765,76 @@ static int launch_dual_softmax(fos_problem* p, int64_t row0, int64_t rows, int n
   return FOS_OK;
 }
 
+// The row pass of a certificate: its launcher and the rows of the partial buffer it writes per panel at most, in units of ncu.
+struct RowPass {
+  const char* fn;        // the entry point, for the message
+  int (*launch)(fos_problem* p, int64_t row0, int64_t rows, int nv, const double* col, double* part, int* nwg_out);
+  int per_cu;
+};
+
+// A certificate after its gradient block G (the gradient walk has planned the lockstep and left X packed in cand.xp): the column
+// pass - the scale of every fit, then its penalty and the conjugate of the ridge-carrying coordinates -, Z = A_panel X once more
+// (plain: no b, no weights, no mask) with the row pass on it, and the finish.
+static int certificate_tail(const RowPass& row, const float* X, const float* G, int nv, int classes, int grouped,
+                            const fos::ClassWeights& wts, fos_problem* p, double* out64) {
+  const int64_t panels = (p->m + p->multi.panel_rows - 1) / p->multi.panel_rows;
+  const size_t part_rows = (size_t)panels * 2 * (size_t)p->ncu;
+  int rc = p->ws.dual_part.reserve(part_rows * fos::DL_WIDTH);
+  if (rc) return rc;
+  if ((rc = p->ws.dual_col.reserve(3 * fos::BT_NV))) return rc;
+  hipLaunchKernelGGL(fos::dual_scale_kernel, dim3(nv / classes), dim3(fos::DS_THREADS), 0, p->stream, X, G, p->n, classes, grouped, wts,
+                     p->coord_factor, p->ws.dual_col.get());
+  LAUNCH_CHECK();
+  const int64_t esz = p->dtype == FOS_BF16 ? 2 : 4;
+  int nparts = 0;
+  for (int64_t row0 = 0; row0 < p->m; row0 += p->multi.panel_rows) {
+    const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
+    int nwg1 = 0, nwg = 0;
+    BatchLaunch L{};
+    L.A = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz; L.rows = rows; L.rout = p->multi.rbuf16;
+    if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
+    if ((size_t)nparts + (size_t)row.per_cu * (size_t)p->ncu > part_rows)
+      return fail(FOS_ERR_STATE, std::string(row.fn) + ": the row pass has more panels than its partial buffer holds");
+    if ((rc = row.launch(p, row0, rows, nv, p->ws.dual_col, p->ws.dual_part + (size_t)nparts * fos::DL_WIDTH, &nwg))) return rc;
+    nparts += nwg;
+  }
+  hipLaunchKernelGGL(fos::dual_finish_kernel, dim3(1), dim3(fos::DF_THREADS), 0, p->stream, (const double*)p->ws.dual_part.get(), nparts,
+                     (const double*)p->ws.dual_col.get(), nv, out64);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
 extern "C" {
 
-// The class gradients at the nv columns of X: per row panel product 1 in its plain storing form (the logits), the softmax link
-// kernel (residuals in place, the loss partials of the panel behind those of the panels before it in ws.link_part), product 2;
-// then the slab sum and the partial fold of fos_gradient_batch.
+int fos_duality_gap(const float* X, int nv, const double* alpha1, const double* alpha2, fos_problem* p, float* G, double* out64) {
+  if (!X || !alpha1 || !alpha2 || !p || !G || !out64 || nv < 1 || nv > fos::BT_NV)
+    return fail(FOS_ERR_ARG, "fos_duality_gap: bad argument (null pointer or nv outside 1..16)");
+  fos::ClassWeights wts;
+  int rc = class_weights(nv, alpha1, alpha2, "fos_duality_gap", &wts);
+  if (rc) return rc;
+  if (p->loss == FOS_LOSS_MULTINOMIAL)
+    return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: a multinomial problem is not served (squared, logistic, Huber and squared-hinge loss)");
+  if ((rc = need_two_products(p, "fos_duality_gap", "the certificate needs b"))) return rc;    // (before the gradient's own: in these words)
+  if (p->coord_lo || p->coord_hi)
+    return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: box bounds (fos_coord_bind) are bound; the penalty of a bounded coordinate has "
+                                     "another conjugate");
+  if (has_fgroups(p))
+    return fail(FOS_ERR_UNSUPPORTED, "fos_duality_gap: feature groups (fos_feature_groups_bind) are bound; the group norm has another "
+                                     "conjugate");
+  // 1. the gradient block, by the launches of fos_gradient_batch (it plans the lockstep and leaves X packed in cand.xp)
+  if ((rc = fos_gradient_batch(X, nv, p, G, nullptr))) return rc;
+  // 2. - 4. the column pass (every column a fit of its own, l1), the row pass on Z = A_panel X and the finish
+  return certificate_tail({"fos_duality_gap", launch_dual_link, 2}, X, G, nv, 1, 0, wts, p, out64);
+}
+
+// The class gradients at the nv columns of X: product 1 runs plain (the logits), the softmax link kernel leaves the residuals in
+// place and the loss partials.
 int fos_multinomial_gradient_batch(const float* X, int nv, fos_problem* p, float* G, double* loss16) {
   const char* fn = "fos_multinomial_gradient_batch";
   if (!X || !p || !G || nv < 1 || nv > fos::BT_NV)
     return fail(FOS_ERR_ARG, std::string(fn) + ": bad argument (null pointer or nv outside 1..16)");
-  int rc = need_class_segments(p, nv, fn);
-  if (rc) return rc;
-  if (!p->b) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the gradient of the data term needs the labels");
-  if (p->comm || p->col_sharded) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": sharded problems are not served");
-  if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the shape has no matrix-core pair");
-  if ((rc = ensure_batch_workspace(p))) return rc;
-  if ((rc = plan_multi_mfma(p))) return rc;
-  int g_splits = 0;
-  if ((rc = two_product_splits(p, &g_splits))) return rc;
-  const int64_t panels = (p->m + p->multi.panel_rows - 1) / p->multi.panel_rows;
-  if ((rc = p->ws.link_part.reserve((size_t)panels * p->ncu * fos::BT_NV))) return rc;
-  const int64_t esz = p->dtype == FOS_BF16 ? 2 : 4;
-  if ((rc = pack_candidates(p, X, nv))) return rc;
-  int nparts = 0;
-  for (int64_t row0 = 0, panel = 0; row0 < p->m; row0 += p->multi.panel_rows, ++panel) {
-    const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
-    const char* Ap = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz;
-    int nwg1 = 0, nwg = 0;
-    BatchLaunch L{};                 // Z = A_panel X: no b, no mask, no weights
-    L.A = Ap; L.rows = rows; L.rout = p->multi.rbuf16;
-    if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
-    if ((rc = launch_softmax_link(p, row0, rows, nv, fos::FOLD_OFF, nullptr, nullptr, p->ws.link_part + (size_t)nparts * fos::BT_NV, &nwg)))
-      return rc;
-    nparts += nwg;
-    if ((rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
-  }
-  hipLaunchKernelGGL(gram_slab_sum_kernel, dim3(grid_1d((int64_t)nv * p->n, 256, 1024)), dim3(256), 0, p->stream, p->multi.slabs16,
-                     g_splits, p->n, nv, G);
-  LAUNCH_CHECK();
-  if (loss16) {
-    hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, p->ws.link_part.get(), nparts,
-                       fos::BT_NV, loss16);
-    LAUNCH_CHECK();
-  }
-  return FOS_OK;
+  if (int rc = need_class_segments(p, nv, fn)) return rc;
+  return gradient_walk({fn, "the gradient of the data term needs the labels", true, WalkLink::softmax, false}, X, nv, p, G, loss16);
 }
 
 int fos_multinomial_kkt_scan(const float* G, int nv, int grouped, const double* alpha1, double slack, const uint8_t* in_ws,
@@ -1851,7 +1846,7 @@ int fos_multinomial_kkt_scan(const float* G, int nv, int grouped, const double* 
   int rc = need_class_segments(p, nv, fn);
   if (rc) return rc;
   fos::ClassWeights w;
-  if ((rc = class_weights(p, nv, alpha1, nullptr, fn, &w))) return rc;
+  if ((rc = class_weights(nv / p->classes, alpha1, nullptr, fn, &w))) return rc;
   if (p->coord_lo || p->coord_hi)
     return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": box bounds (fos_coord_bind) are bound; a coordinate at a bound has another "
                                      "optimality condition");
@@ -1869,7 +1864,7 @@ int fos_multinomial_duality_gap(const float* X, int nv, int grouped, const doubl
   int rc = need_class_segments(p, nv, fn);
   if (rc) return rc;
   fos::ClassWeights wts;
-  if ((rc = class_weights(p, nv, alpha1, alpha2, fn, &wts))) return rc;
+  if ((rc = class_weights(nv / p->classes, alpha1, alpha2, fn, &wts))) return rc;
   if (p->coord_lo || p->coord_hi)
     return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": box bounds (fos_coord_bind) are bound; the penalty of a bounded coordinate "
                                      "has another conjugate");
@@ -1878,33 +1873,7 @@ int fos_multinomial_duality_gap(const float* X, int nv, int grouped, const doubl
                                      "another conjugate");
   // first the class gradients, by the launches of fos_multinomial_gradient_batch (its refusals; it plans the lockstep and leaves X packed)
   if ((rc = fos_multinomial_gradient_batch(X, nv, p, G, nullptr))) return rc;
-  const int64_t panels = (p->m + p->multi.panel_rows - 1) / p->multi.panel_rows;
-  const size_t part_rows = (size_t)panels * 2 * (size_t)p->ncu;          // (the row pass writes at most ncu a panel)
-  if ((rc = p->ws.dual_part.reserve(part_rows * fos::DL_WIDTH))) return rc;
-  if ((rc = p->ws.dual_col.reserve(3 * fos::BT_NV))) return rc;
-  // then the column pass: the scale of every segment, then its penalty and the conjugate of the ridge-carrying coordinates
-  hipLaunchKernelGGL(fos::class_dual_scale_kernel, dim3(nv / p->classes), dim3(fos::DS_THREADS), 0, p->stream, X, (const float*)G,
-                     p->n, p->classes, grouped, wts, p->coord_factor, p->ws.dual_col.get());
-  LAUNCH_CHECK();
-  // the logits of every panel once more, and the row pass on them
-  const int64_t esz = p->dtype == FOS_BF16 ? 2 : 4;
-  int nparts = 0;
-  for (int64_t row0 = 0; row0 < p->m; row0 += p->multi.panel_rows) {
-    const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
-    int nwg1 = 0, nwg = 0;
-    BatchLaunch L{};
-    L.A = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz; L.rows = rows; L.rout = p->multi.rbuf16;
-    if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
-    if ((size_t)nparts + (size_t)p->ncu > part_rows)
-      return fail(FOS_ERR_STATE, std::string(fn) + ": the row pass has more panels than its partial buffer holds");
-    if ((rc = launch_dual_softmax(p, row0, rows, nv, p->ws.dual_col, p->ws.dual_part + (size_t)nparts * fos::DL_WIDTH, &nwg))) return rc;
-    nparts += nwg;
-  }
-  // and the finish of fos_duality_gap
-  hipLaunchKernelGGL(fos::dual_finish_kernel, dim3(1), dim3(fos::DF_THREADS), 0, p->stream, (const double*)p->ws.dual_part.get(), nparts,
-                     (const double*)p->ws.dual_col.get(), nv, out64);
-  LAUNCH_CHECK();
-  return FOS_OK;
+  return certificate_tail({fn, launch_dual_softmax, 1}, X, G, nv, p->classes, grouped, wts, p, out64);
 }
 
 }  // extern "C"

@@ -1,5 +1,7 @@
-// Working set and duality gap of the multinomial lockstep (include/fos_multinomial_ws.h): the class scan, the class column pass
-// and the fp64 row pass on the logit panel.  The finish is dual_finish_kernel of duality.hpp, unchanged.
+// Working set and duality gap of the multinomial lockstep (include/fos_multinomial_ws.h): the class scan - the instantiation of
+// the one scan body of working_set.hpp that takes C and the kind of penalty at run time - and the fp64 row pass on the logit
+// panel.  The column pass and the finish (dual_scale_kernel and dual_finish_kernel of duality.hpp) are those of every loss,
+// launched with C columns per fit.
 //
 // The 16 columns of a block are the C class vectors of nv / C fits ("segments": segment s is columns s*C .. s*C + C-1, as in
 // softmax_link.hpp).  For one segment with the weights alpha1, alpha2, Z = A X_seg (m x C), sigma_i = softmax(z_i), w_i the bound
@@ -24,156 +26,24 @@
 #include "batch_trial.hpp"
 #include "duality.hpp"
 #include "softmax_link.hpp"
-#include "working_set.hpp"
 
 namespace fos {
 
-struct ClassWeights { double a1[SL_MAX_SEG], a2[SL_MAX_SEG]; };      // per segment
-
 // ---- class scan ---------------------------------------------------------------------------------------------------------------
-// kkt_scan_kernel with the C columns of a fit seen together: ONE workgroup of 16 waves walks the n coordinates in order, 1024 at
-// a time.  For coordinate i outside the set, per segment s, all in fp64 from the float G:
-//     l1      v = max_c |G[s*C + c][i]|                                       violator: v > alpha1[s] p_i (1 + slack)
-//     group   q = sum_c G[s*C + c][i]^2 (c ascending),  v = sqrt(q)           violator: q > (alpha1[s] p_i (1 + slack))^2
-// (the grouped decision takes no square root: it is the comparison of the squares, exact in the products of the floats), and
-// excess[i] = (float) max_s v / (alpha1[s] p_i); a zero denominator gives +inf where v > 0 and 0 where v = 0.  The violators
-// leave in increasing order through per-wave ballots and a block prefix sum.  classes and grouped are the same for every lane.
-// Resources (gfx950, -O3): 45 VGPRs, 64 bytes of LDS, no scratch.
+// kkt_scan_body of working_set.hpp with the C columns of a fit seen together; classes and grouped are the same for every lane.
+// Resources (gfx950, -O3): 47 VGPRs, 64 bytes of LDS, no scratch.
 static __global__ __launch_bounds__(KS_THREADS) void class_kkt_scan_kernel(const float* __restrict__ G, int64_t n, int nv, int classes,
-                                                                           int grouped, ClassWeights w, double one_plus_slack,
+                                                                           int grouped, ScanWeights w, double one_plus_slack,
                                                                            const uint8_t* __restrict__ in_ws,
                                                                            const float* __restrict__ factor, float* __restrict__ excess,
                                                                            int32_t* __restrict__ viol_idx,
                                                                            int32_t* __restrict__ viol_count) {
-  __shared__ int wcount[KS_THREADS / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nseg = nv / classes;
-  int running = 0;
-  for (int64_t base = 0; base < n; base += KS_THREADS) {
-    const int64_t i = base + tid;
-    bool viol = false;
-    double ex = 0.0;
-    if (i < n && in_ws[i] == 0) {
-      const double pf = factor ? (double)factor[i] : 1.0;
-      for (int s = 0; s < nseg; ++s) {
-        const float* __restrict__ g = G + (int64_t)s * classes * n + i;
-        const double d = w.a1[s] * pf;
-        const double thr = d * one_plus_slack;
-        double v = 0.0;
-        if (grouped) {
-          double q = 0.0;
-          for (int c = 0; c < classes; ++c) {
-            const double a = (double)g[(int64_t)c * n];
-            q += a * a;
-          }
-          v = sqrt(q);
-          viol = viol || q > thr * thr;
-        } else {
-          for (int c = 0; c < classes; ++c) {
-            const double a = (double)fabsf(g[(int64_t)c * n]);
-            v = a > v ? a : v;
-          }
-          viol = viol || v > thr;
-        }
-        const double e = d > 0.0 ? v / d : (v > 0.0 ? (double)INFINITY : 0.0);
-        ex = e > ex ? e : ex;
-      }
-    }
-    if (i < n) excess[i] = (float)ex;
-    const unsigned long long bal = __ballot(viol);
-    if (lane == 0) wcount[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int v = 0; v < KS_THREADS / 64; ++v) {
-      const int c = wcount[v];
-      before += v < wave ? c : 0;
-      total += c;
-    }
-    if (viol) viol_idx[running + before + __popcll(bal & ((1ull << lane) - 1ull))] = (int32_t)i;
-    running += total;
-    __syncthreads();                 // wcount is rewritten by the next trip
-  }
-  if (tid == 0) *viol_count = running;
-}
-
-// ---- class column pass --------------------------------------------------------------------------------------------------------
-// Workgroup s < nv / C walks the n x C entries of segment s twice, all in fp64: first the scale (the minimum of an empty set is
-// 1), then, with it, the penalty and the conjugate of the ridge-carrying rows.  X: n x 16 floats, row-major - the C entries of a
-// row are adjacent; G: nv x n floats; factor: the bound penalty factors or null (1).  col[s*C] = the scale, col[16 + s*C] = the
-// penalty, col[32 + s*C] = the conjugate, and 0 in the other C - 1 entries of the segment in all three, so that
-// dual_finish_kernel (which adds entry j of the column pass to entry j of the row pass) serves unchanged.
-// Resources (gfx950, -O3): 38 VGPRs, 2 KiB of LDS, no scratch.
-static __global__ __launch_bounds__(DS_THREADS) void class_dual_scale_kernel(const float* __restrict__ X, const float* __restrict__ G,
-                                                                             int64_t n, int classes, int grouped, ClassWeights wts,
-                                                                             const float* __restrict__ factor,
-                                                                             double* __restrict__ col) {
-  __shared__ double red[DS_THREADS];
-  const int tid = threadIdx.x, seg = blockIdx.x, lo = seg * classes;
-  const double a1 = wts.a1[seg], a2 = wts.a2[seg];
-  const float* __restrict__ g = G + (int64_t)lo * n;
-  double smin = 1.0;
-  for (int64_t k = tid; k < n; k += DS_THREADS) {
-    const double pf = factor ? (double)factor[k] : 1.0;
-    const double tau = a1 * pf, rho = a2 * pf;
-    if (rho != 0.0) continue;
-    if (grouped) {
-      double q = 0.0;
-      for (int c = 0; c < classes; ++c) {
-        const double a = (double)g[(int64_t)c * n + k];
-        q += a * a;
-      }
-      const double v = sqrt(q);
-      if (v != 0.0) smin = fmin(smin, tau / v);
-    } else {
-      for (int c = 0; c < classes; ++c) {
-        const double a = (double)fabsf(g[(int64_t)c * n + k]);
-        if (a != 0.0) smin = fmin(smin, tau / a);
-      }
-    }
-  }
-  const double s = dual_block_min(smin, red);
-  double pen = 0.0, conj = 0.0;
-  for (int64_t k = tid; k < n; k += DS_THREADS) {
-    const double pf = factor ? (double)factor[k] : 1.0;
-    const double tau = a1 * pf, rho = a2 * pf;
-    const float* __restrict__ x = X + k * BT_NV + lo;
-    if (grouped) {
-      double x2 = 0.0, q = 0.0;
-      for (int c = 0; c < classes; ++c) {
-        const double xv = (double)x[c], a = (double)g[(int64_t)c * n + k];
-        x2 += xv * xv;
-        q += a * a;
-      }
-      pen += tau * sqrt(x2) + 0.5 * rho * x2;
-      if (rho > 0.0) {
-        const double e = fmax(s * sqrt(q) - tau, 0.0);
-        conj += e * e / (2.0 * rho);
-      }
-    } else {
-      for (int c = 0; c < classes; ++c) {
-        const double xv = (double)x[c];
-        pen += tau * fabs(xv) + 0.5 * rho * xv * xv;
-        if (rho > 0.0) {
-          const double e = fmax(s * (double)fabsf(g[(int64_t)c * n + k]) - tau, 0.0);
-          conj += e * e / (2.0 * rho);
-        }
-      }
-    }
-  }
-  pen = dual_block_sum(pen, red);
-  conj = dual_block_sum(conj, red);
-  if (tid < classes) {
-    const bool first = tid == 0;
-    col[lo + tid] = first ? s : 0.0;
-    col[BT_NV + lo + tid] = first ? pen : 0.0;
-    col[2 * BT_NV + lo + tid] = first ? conj : 0.0;
-  }
+  kkt_scan_body<false>(G, n, nv, classes, grouped, w, one_plus_slack, in_ws, factor, excess, viol_idx, viol_count);
 }
 
 // ---- row pass -----------------------------------------------------------------------------------------------------------------
 // z16: the panel Z = A_panel X (rows x 16 fp32, row-major) that product 1 left in its plain storing form; it is only read.
-// labels[i], row_weight[i] (WEIGHT): offset to the panel by the caller.  col: DEVICE, the output of class_dual_scale_kernel - the
+// labels[i], row_weight[i] (WEIGHT): offset to the panel by the caller.  col: DEVICE, the output of dual_scale_kernel - the
 // scale of segment s is col[s*C] (known on the device alone: the certificate enqueues and never waits).
 // One thread per row, as in softmax_link_kernel: four 16-byte loads; the row stays in registers (constant indices only) and
 // every branch is on a value all lanes share.  The segment's logits are shifted to the front of the row (four shifts by the bits

@@ -1,6 +1,6 @@
-// Working-set solve of a sparse path (include/fos_working_set.h): the column gather and the KKT scan.  The lockstep runs on the
-// gathered matrix as on any other fos_problem; these two kernels and fos_gradient_batch (existing launches) are all the outer
-// loop of fastoptsolver_amd/working_set.py needs from the device.
+// Working-set solve of a sparse path (include/fos_working_set.h, include/fos_multinomial_ws.h): the column gather and the KKT
+// scan of every loss family.  The lockstep runs on the gathered matrix as on any other fos_problem; these two kernels and the
+// gradient entry points (existing launches) are all the outer loop of fastoptsolver_amd/working_set.py needs from the device.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -67,20 +67,36 @@ static __global__ __launch_bounds__(WS_THREADS) void gather_columns_kernel(const
 }
 
 // ---- KKT scan -----------------------------------------------------------------------------------------------------------------
-// ONE workgroup of 16 waves walks the n coordinates in order, 1024 at a time: the excess and the violation flag per thread in the
-// fp64 arithmetic the header states, a ballot per wave, the 16 wave counts through LDS, and every violator writes its index at
-// (violators of earlier trips) + (of earlier waves) + (of lower lanes): increasing order, no atomics, the same bytes every run.
+// The 16 columns of a block are nv / C fits of C columns each ("segments": segment s is columns s*C .. s*C + C-1); C = 1 for
+// every loss but the multinomial one, whose C class vectors are seen together (softmax_link.hpp has the same layout).
+// ONE workgroup of 16 waves walks the n coordinates in order, 1024 at a time.  For coordinate i outside the set, per segment s,
+// all in fp64 from the float G, p_i the bound penalty factor (or 1):
+//     l1      v = max_c |G[s*C + c][i]|                                       violator: v > alpha1[s] p_i (1 + slack)
+//     group   q = sum_c G[s*C + c][i]^2 (c ascending),  v = sqrt(q)           violator: q > (alpha1[s] p_i (1 + slack))^2
+// (the grouped decision takes no square root: it is the comparison of the squares, exact in the products of the floats), and
+// excess[i] = (float) max_s v / (alpha1[s] p_i); a zero denominator gives +inf where v > 0 and 0 where v = 0.  A ballot per wave,
+// the 16 wave counts through LDS, and every violator writes its index at (violators of earlier trips) + (of earlier waves) +
+// (of lower lanes): increasing order, no read-modify-write, the same bytes every run.  classes and grouped are the same for
+// every lane.
 // n <= 16384 wherever the matrix-core pair is served: 16 trips over at most 1 MiB of gradients.
-// Resources (gfx950, -O3): 41 VGPRs, 64 bytes of LDS, no scratch.
+// The body is written once.  ONE_COLUMN fixes C = 1, l1 at compile time (classes_ and grouped_ are not read): the two inner loops
+// fold into one load per column, which the 16 loads of a coordinate need to be issued together (with C in a register the
+// scan is a fifth slower: profiles/ws_refactor/README.md).  kkt_scan_kernel below is that instantiation;
+// class_kkt_scan_kernel of multinomial_ws.hpp is the other.
 constexpr int KS_THREADS = 1024;
-struct KktWeights { double a[BT_NV]; };
+struct ScanWeights { double a1[BT_NV]; };                            // per segment: what a scan kernel takes (128 bytes of kernarg)
+struct ClassWeights : ScanWeights { double a2[BT_NV]; };             // what a call checks and the column pass of duality.hpp takes
 
-static __global__ __launch_bounds__(KS_THREADS) void kkt_scan_kernel(const float* __restrict__ G, int64_t n, int nv, KktWeights w,
-                                                                     double one_plus_slack, const uint8_t* __restrict__ in_ws,
-                                                                     const float* __restrict__ factor, float* __restrict__ excess,
-                                                                     int32_t* __restrict__ viol_idx, int32_t* __restrict__ viol_count) {
+template <bool ONE_COLUMN>
+__device__ __forceinline__ void kkt_scan_body(const float* __restrict__ G, int64_t n, int nv, int classes_, int grouped_,
+                                              const ScanWeights& w, double one_plus_slack, const uint8_t* __restrict__ in_ws,
+                                              const float* __restrict__ factor, float* __restrict__ excess,
+                                              int32_t* __restrict__ viol_idx, int32_t* __restrict__ viol_count) {
   __shared__ int wcount[KS_THREADS / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int classes = ONE_COLUMN ? 1 : classes_;
+  const bool grouped = ONE_COLUMN ? false : grouped_ != 0;
+  const int nseg = nv / classes;
   int running = 0;
   for (int64_t base = 0; base < n; base += KS_THREADS) {
     const int64_t i = base + tid;
@@ -88,12 +104,31 @@ static __global__ __launch_bounds__(KS_THREADS) void kkt_scan_kernel(const float
     double ex = 0.0;
     if (i < n && in_ws[i] == 0) {
       const double pf = factor ? (double)factor[i] : 1.0;
-      for (int j = 0; j < nv; ++j) {
-        const double a = (double)fabsf(G[(int64_t)j * n + i]);
-        const double d = w.a[j] * pf;
-        const double e = d > 0.0 ? a / d : (a > 0.0 ? (double)INFINITY : 0.0);
+      for (int s = 0; s < nseg; ++s) {
+        const float* __restrict__ g = G + (int64_t)s * classes * n + i;
+        const double d = w.a1[s] * pf;
+        const double thr = d * one_plus_slack;
+        double v = 0.0;
+        if constexpr (ONE_COLUMN) {                      // the maximum over one entry is the entry (a NaN gives no violator and
+          v = (double)fabsf(g[0]);                       // leaves the excess alone either way)
+          viol = viol || v > thr;
+        } else if (grouped) {
+          double q = 0.0;
+          for (int c = 0; c < classes; ++c) {
+            const double a = (double)g[(int64_t)c * n];
+            q += a * a;
+          }
+          v = sqrt(q);
+          viol = viol || q > thr * thr;
+        } else {
+          for (int c = 0; c < classes; ++c) {
+            const double a = (double)fabsf(g[(int64_t)c * n]);
+            v = a > v ? a : v;
+          }
+          viol = viol || v > thr;
+        }
+        const double e = d > 0.0 ? v / d : (v > 0.0 ? (double)INFINITY : 0.0);
         ex = e > ex ? e : ex;
-        viol = viol || a > d * one_plus_slack;
       }
     }
     if (i < n) excess[i] = (float)ex;
@@ -112,6 +147,15 @@ static __global__ __launch_bounds__(KS_THREADS) void kkt_scan_kernel(const float
     __syncthreads();                 // wcount is rewritten by the next trip
   }
   if (tid == 0) *viol_count = running;
+}
+
+// The scan of fos_kkt_scan: every column a fit of its own, the l1 condition.
+// Resources (gfx950, -O3): 43 VGPRs, 64 bytes of LDS, no scratch.
+static __global__ __launch_bounds__(KS_THREADS) void kkt_scan_kernel(const float* __restrict__ G, int64_t n, int nv, ScanWeights w,
+                                                                     double one_plus_slack, const uint8_t* __restrict__ in_ws,
+                                                                     const float* __restrict__ factor, float* __restrict__ excess,
+                                                                     int32_t* __restrict__ viol_idx, int32_t* __restrict__ viol_count) {
+  kkt_scan_body<true>(G, n, nv, 1, 0, w, one_plus_slack, in_ws, factor, excess, viol_idx, viol_count);
 }
 
 }  // namespace fos

@@ -32,7 +32,6 @@ import collections
 import numpy as np
 import torch
 
-from . import _core
 from . import iterative_solvers as _its
 from . import working_set as _ws
 
@@ -47,12 +46,20 @@ of certificates taken (each reads A three times), the last certificate per colum
 ``certified[j]`` - whether gap_j <= gap_tol * P_j(0) - and whether the group fell back to the full lockstep."""
 
 
-def _certificate(prob, X, alphas):
-    """(primal, dual, gap, scale as float64 ndarrays of len(alphas) <= 16 entries, the gradient block G).  Synchronises."""
-    nv = len(alphas)
-    out64, G = prob.duality_gap_block(X, [a1 for a1, _ in alphas], [a2 for _, a2 in alphas])
-    out = out64.cpu().numpy().reshape(4, 16)[:, :nv].copy()
+def _certificate(prob, steps, X, alphas):
+    """(primal, dual, gap, scale as float64 ndarrays, one entry per fit in the columns of X - at most 16 columns -, the gradient
+    block G).  Synchronises."""
+    out64, G = steps.certificate(prob, X, [a1 for a1, _ in alphas], [a2 for _, a2 in alphas])
+    out = out64.cpu().numpy().reshape(4, 16)[:, :len(alphas) * steps.width:steps.width].copy()
     return out[0], out[1], out[2], out[3], G
+
+
+def _gaps(prob, steps, Xd, alphas):
+    """`duality_gap` on the device block Xd (one fit per weight): the certificates of the groups, joined."""
+    W = steps.width
+    parts = [_certificate(prob, steps, Xd[:, first * W:(first + number) * W], alphas[first:first + number])[:4]
+             for first, number in steps.groups(len(alphas))]
+    return DualityGap(*(np.concatenate([part[i] for part in parts]) for i in range(4)))
 
 
 def duality_gap(prob, X, alphas):
@@ -66,22 +73,16 @@ def duality_gap(prob, X, alphas):
     Xd = _ws._block(prob, X)
     if Xd.shape[1] != len(alphas):
         raise ValueError(f"X has {Xd.shape[1]} columns for {len(alphas)} weights")
-    parts = [_certificate(prob, Xd[:, first:first + number], alphas[first:first + number])[:4]
-             for first, number in _its._groups(len(alphas), _its.LOCKSTEP_COLUMNS)]
-    return DualityGap(*(np.concatenate([part[i] for part in parts]) for i in range(4)))
+    return _gaps(prob, _ws._steps(prob), Xd, alphas)
 
 
-_STEPS = _ws._STEPS._replace(certificate=_certificate)
-
-
-def _certified_group(prob, fam, alphas, gap_tol, max_iter, max_rounds, grow, max_fraction, L, t_init_factor, steps=_STEPS):
+def _certified_group(prob, fam, steps, alphas, gap_tol, max_iter, max_rounds, grow, max_fraction, L, t_init_factor):
     """One group of weights (up to 16 columns; `working_set._Steps`): (X as an n_dev x (fits * width) float64 device block,
     GapInfo)."""
     nv, a1s = len(alphas) * steps.width, [a1 for a1, _ in alphas]
-    pf = _ws._factors(prob)
     X = torch.zeros(prob.n_dev, nv, dtype=torch.float64, device=prob.device)
-    free = _ws._mask(prob) if pf is None else (pf == 0).to(torch.uint8)
-    primal, dual, gap, scale, G = steps.certificate(prob, X, alphas)     # at X = 0: P_j(0) and the first violators
+    free = _ws._free(prob)
+    primal, dual, gap, scale, G = _certificate(prob, steps, X, alphas)   # at X = 0: P_j(0) and the first violators
     certificates = 1
     bound = gap_tol * primal
     _, viol = steps.scan(prob, G, a1s, 0.0, free)
@@ -98,38 +99,19 @@ def _certified_group(prob, fam, alphas, gap_tol, max_iter, max_rounds, grow, max
             break
         sizes.append(n_ws)
         if sub is None:
-            n_ws_pad = max(_ws.MIN_COLUMNS, (n_ws + _ws.PAD_COLUMNS - 1) // _ws.PAD_COLUMNS * _ws.PAD_COLUMNS)
-            A_ws = prob.gather_columns(idx, n_ws_pad)
-            p_ws = None
-            if pf is not None:                           # padding coordinates get factor 1: their columns are zero
-                p_ws = torch.ones(n_ws_pad, dtype=torch.float64)
-                p_ws[:n_ws] = pf[idx].to("cpu", torch.float64)
-                p_ws = p_ws.numpy()
-            sub = steps.sub_problem(prob, A_ws, p_ws)
-            prms = _its._path_params(sub, alphas, L, fam, t_init_factor, None)
-        X0 = None
-        if len(sizes) > 1 or bool((X != 0).any()):
-            X0 = torch.zeros(n_ws_pad, nv, dtype=torch.float64, device=prob.device)
-            X0[:n_ws] = X[idx]
-        Xs = _ws._lockstep(sub, fam, prms, X0, max_iter)
-        X[idx] = Xs[:n_ws]
-        primal, dual, gap, scale, G = steps.certificate(prob, X, alphas)
+            sub, prms = _ws._gather(prob, fam, alphas, idx, L, t_init_factor)
+        _ws._round(sub, fam, prms, X, idx, len(sizes) == 1, max_iter)
+        primal, dual, gap, scale, G = _certificate(prob, steps, X, alphas)
         certificates += 1
         excess, viol = steps.scan(prob, G, a1s, 0.0, mask)   # the certificate's own gradient: no second one is taken
-        count = int(viol.numel())
-        if count == 0:                                   # the zeros are right and the gap is not there yet: the same set again
+        if int(viol.numel()) == 0:                       # the zeros are right and the gap is not there yet: the same set again
             continue
-        mask[viol.long()] = 1
-        want = int((grow - 1.0) * n_ws)
-        if count < want:                                 # working_set_path's growth rule
-            vals, cand = torch.topk(excess, min(want, prob.n_dev))
-            mask[cand[vals > 0]] = 1
-        sub = A_ws = prms = None
+        _ws._grow(mask, excess, viol, n_ws, grow)        # working_set_path's growth rule
+        sub = prms = None
     if fell_back:
-        sub = A_ws = None
-        prms = _its._path_params(prob, alphas, L, fam, t_init_factor, None)
-        X = _ws._lockstep(prob, fam, prms, X if bool((X != 0).any()) else None, max_iter)
-        primal, dual, gap, scale, G = steps.certificate(prob, X, alphas)
+        sub = None
+        X = _ws._fall_back(prob, fam, alphas, X, L, t_init_factor, max_iter)
+        primal, dual, gap, scale, G = _certificate(prob, steps, X, alphas)
         certificates += 1
     return X, GapInfo(len(sizes), sizes, certificates, primal, dual, gap, scale, gap <= bound, fell_back)
 
@@ -161,11 +143,6 @@ def certified_path(A, b, alphas, gap_tol: float = 1e-4, max_iter: int = 500, *, 
         raise ValueError("certified_path: gap_tol >= 0, grow > 1, 0 < max_fraction <= 1 and max_rounds >= 1 expected")
     prob = _ws._handle(A, b, dtype, "certified_path")
     _ws._check_weights(prob, alphas)
-    fam = _ws._family(prob, max_iter)
-    xs, infos = [], []
-    for first, number in _its._groups(len(alphas), _its.LOCKSTEP_COLUMNS):
-        X, info = _certified_group(prob, fam, alphas[first:first + number], gap_tol, max_iter, max_rounds, grow, max_fraction, L,
-                                   t_init_factor)
-        xs += [_core.from_device_vec(prob.vec_out(X[:, v]), prob.like) for v in range(number)]
-        infos.append(info)
-    return (xs, infos) if return_info else xs
+    fam, steps = _ws._family(prob, max_iter), _ws._steps(prob)
+    return _ws._drive(prob, alphas, steps, lambda part: _certified_group(prob, fam, steps, part, gap_tol, max_iter, max_rounds, grow,
+                                                                          max_fraction, L, t_init_factor), return_info)

@@ -4,8 +4,8 @@
 A multinomial fit occupies C of the 16 lockstep columns, so only floor(16 / C) weights advance per pass over A; the multinomial
 lockstep has no stopping rule (``multinomial_path``: exactly ``max_iter`` iterations); and a grouped fit is sparse in whole rows
 of X.  The names here are to ``multinomial_path`` what ``working_set_path`` and ``certified_path`` are to ``fista_path``: the
-same outer loops (``working_set._solve_group``, ``duality._certified_group``), given the device steps that see the C columns of
-a fit together (include/fos_multinomial_ws.h).
+same outer loops (``working_set._solve_group``, ``duality._certified_group``) and driver, given the device steps that see the C
+columns of a fit together (``working_set._steps``; include/fos_multinomial_ws.h).
 
 For one fit X (n x C) with the weights (alpha1, alpha2): Z = A X, sigma_i = softmax(z_i), row weights w (or 1), penalty factors p
 (or 1), tau = alpha1 p, rho = alpha2 p and G = A^T (w (sigma - onehot(y))) (n x C):
@@ -62,29 +62,6 @@ def _handle(A, y, classes, dtype, who):
     return A
 
 
-def _sub_problem(prob, A_ws, p_ws):
-    """The multinomial problem on the gathered columns: the handle's labels, class count, row weights and kind of penalty, the
-    factors p_ws."""
-    sub = _core.Problem.multinomial(A_ws, prob.b, prob.classes, None, prob.sample_weight, p_ws)
-    sub.set_grouped(prob.grouped)
-    return sub
-
-
-def _certificate(prob, X, alphas):
-    """(primal, dual, gap, scale as float64 ndarrays, one entry per fit in the columns of X, the gradient block G).
-    Synchronises."""
-    C = prob.classes
-    out64, G = prob.multinomial_duality_gap_block(X, [a1 for a1, _ in alphas], [a2 for _, a2 in alphas])
-    out = out64.cpu().numpy().reshape(4, 16)[:, :len(alphas) * C:C].copy()
-    return out[0], out[1], out[2], out[3], G
-
-
-def _steps(prob):
-    """The device steps of the outer loops on a multinomial handle (`working_set._Steps`)."""
-    return _ws._Steps(prob.classes, lambda prob, X: prob.multinomial_gradient_block(X),
-                      lambda prob, G, a1s, slack, in_ws: prob.multinomial_kkt_scan(G, a1s, slack, in_ws), _sub_problem, _certificate)
-
-
 def _block(prob, X):
     """Fits (an n x C matrix, an n x C x k block or a list of n x C matrices) as an n_dev x (k * C) float64 device block,
     fit-major: column s * C + c is class c of fit s."""
@@ -96,11 +73,6 @@ def _block(prob, X):
     return out
 
 
-def _fits(prob, X, number):
-    C = prob.classes
-    return [_core.from_device_vec(X[: prob.n, v * C:(v + 1) * C].contiguous(), prob.like) for v in range(number)]
-
-
 def multinomial_alpha_max(prob):
     """The smallest alpha1 at which X = 0 is optimal on a multinomial handle: max_k v_k(0) / p_k over the penalised coordinates,
     v_k = max_c |G_kc| on a plain handle and ||G_k:||_2 on a grouped one, G the gradient of the data term at 0 (one
@@ -108,11 +80,7 @@ def multinomial_alpha_max(prob):
     ``alpha_max`` has it.  Synchronises."""
     prob = _handle(prob, None, None, None, "multinomial_alpha_max")
     _mn._grouped(prob)
-    pf = _ws._factors(prob)
-    free = _ws._mask(prob) if pf is None else (pf == 0).to(torch.uint8)
-    G = prob.multinomial_gradient_block(torch.zeros(prob.n_dev, prob.classes, dtype=torch.float32, device=prob.device))
-    excess, _ = prob.multinomial_kkt_scan(G, [1.0], 0.0, free)
-    return float(excess.max())
+    return _ws._top_excess(prob, _ws._steps(prob))
 
 
 def multinomial_kkt_excess(prob, X, alphas):
@@ -128,12 +96,7 @@ def multinomial_kkt_excess(prob, X, alphas):
     Xd, C = _block(prob, X), prob.classes
     if Xd.shape[1] != len(alphas) * C:
         raise ValueError(f"X has {Xd.shape[1] // C} fits for {len(alphas)} weights")
-    empty, worst = _ws._mask(prob), None
-    for first, number in _its.pack_groups(len(alphas), C):
-        G = prob.multinomial_gradient_block(Xd[:, first * C:(first + number) * C])
-        excess, _ = prob.multinomial_kkt_scan(G, [a1 for a1, _ in alphas[first:first + number]], 0.0, empty)
-        worst = excess if worst is None else torch.maximum(worst, excess)
-    return _core.from_device_vec(prob.vec_out(worst), prob.like)
+    return _ws._worst_excess(prob, _ws._steps(prob), Xd, alphas)
 
 
 def multinomial_duality_gap(prob, X, alphas):
@@ -148,9 +111,7 @@ def multinomial_duality_gap(prob, X, alphas):
     Xd, C = _block(prob, X), prob.classes
     if Xd.shape[1] != len(alphas) * C:
         raise ValueError(f"X has {Xd.shape[1] // C} fits for {len(alphas)} weights")
-    parts = [_certificate(prob, Xd[:, first * C:(first + number) * C], alphas[first:first + number])[:4]
-             for first, number in _its.pack_groups(len(alphas), C)]
-    return DualityGap(*(np.concatenate([part[i] for part in parts]) for i in range(4)))
+    return _du._gaps(prob, _ws._steps(prob), Xd, alphas)
 
 
 def _begin(A, y, alphas, classes, dtype, who, ok, expected):
@@ -186,19 +147,10 @@ def multinomial_working_set_path(A, y, alphas, classes=None, max_iter: int = 500
     prob, alphas = _begin(A, y, alphas, classes, dtype, "multinomial_working_set_path",
                           grow > 1.0 and 0.0 < max_fraction <= 1.0 and max_rounds >= 1 and kkt_tol >= 0.0,
                           "grow > 1, 0 < max_fraction <= 1, max_rounds >= 1 and kkt_tol >= 0")
-    if initial is not None:
-        initial = torch.unique(torch.as_tensor(np.asarray(initial.cpu() if _core.is_tensor(initial) else initial)).to(torch.int64).reshape(-1))
-        if initial.numel() == 0 or int(initial[0]) < 0 or int(initial[-1]) >= prob.n:
-            raise ValueError(f"initial: coordinate numbers in 0 .. {prob.n - 1} expected")
-        initial = initial.to(prob.device)
-    fam, steps = _mn._family(prob, max_iter), _steps(prob)
-    xs, infos = [], []
-    for first, number in _its.pack_groups(len(alphas), prob.classes):
-        X, info = _ws._solve_group(prob, fam, alphas[first:first + number], max_iter, kkt_tol, max_rounds, grow, max_fraction, L,
-                                   t_init_factor, initial, steps)
-        xs += _fits(prob, X, number)
-        infos.append(info)
-    return (xs, infos) if return_info else xs
+    initial = _ws._initial(prob, initial, "coordinate")
+    fam, steps = _ws._family(prob, max_iter), _ws._steps(prob)
+    return _ws._drive(prob, alphas, steps, lambda part: _ws._solve_group(prob, fam, steps, part, max_iter, kkt_tol, max_rounds, grow,
+                                                                          max_fraction, L, t_init_factor, initial), return_info)
 
 
 def multinomial_certified_path(A, y, alphas, classes=None, gap_tol: float = 1e-4, max_iter: int = 500, *, max_rounds: int = 20,
@@ -218,11 +170,6 @@ def multinomial_certified_path(A, y, alphas, classes=None, gap_tol: float = 1e-4
     prob, alphas = _begin(A, y, alphas, classes, dtype, "multinomial_certified_path",
                           gap_tol >= 0.0 and np.isfinite(gap_tol) and grow > 1.0 and 0.0 < max_fraction <= 1.0 and max_rounds >= 1,
                           "gap_tol >= 0, grow > 1, 0 < max_fraction <= 1 and max_rounds >= 1")
-    fam, steps = _mn._family(prob, max_iter), _steps(prob)
-    xs, infos = [], []
-    for first, number in _its.pack_groups(len(alphas), prob.classes):
-        X, info = _du._certified_group(prob, fam, alphas[first:first + number], gap_tol, max_iter, max_rounds, grow, max_fraction, L,
-                                       t_init_factor, steps)
-        xs += _fits(prob, X, number)
-        infos.append(info)
-    return (xs, infos) if return_info else xs
+    fam, steps = _ws._family(prob, max_iter), _ws._steps(prob)
+    return _ws._drive(prob, alphas, steps, lambda part: _du._certified_group(prob, fam, steps, part, gap_tol, max_iter, max_rounds, grow,
+                                                                              max_fraction, L, t_init_factor), return_info)

@@ -26,6 +26,7 @@ import torch
 
 from . import _core
 from . import iterative_solvers as _its
+from . import multinomial as _mn
 
 WorkingSetInfo = collections.namedtuple("WorkingSetInfo", "rounds sizes full_gradients worst_excess fell_back")
 WorkingSetInfo.__doc__ = """What one group of up to 16 weights did: the rounds solved on a working set, the set's size in each, the
@@ -56,7 +57,9 @@ def _handle(A, b, dtype, who):
 
 
 def _family(prob, max_iter):
-    """The lockstep family `fista_path` / `logistic_path` give this kind of handle."""
+    """The lockstep family `fista_path` / `logistic_path` / `multinomial_path` give this kind of handle."""
+    if prob.loss == "multinomial":
+        return _mn._family(prob, max_iter)
     if prob.loss == "logistic":
         return _its._columns(max_iter, True, 4.0)
     if prob.loss in _core.LINK_LOSSES:           # `huber_path` / `hinge_path`: the squared loss's L, the lockstep alone
@@ -65,7 +68,12 @@ def _family(prob, max_iter):
 
 
 def _sub_problem(prob, A_ws, p_ws):
-    """The problem on the gathered columns: the handle's b, loss (with the Huber threshold), row weights and the factors p_ws."""
+    """The problem on the gathered columns: the handle's b (or labels and class count), loss (with the Huber threshold), row
+    weights and kind of penalty, and the factors p_ws."""
+    if prob.loss == "multinomial":
+        sub = _core.Problem.multinomial(A_ws, prob.b, prob.classes, None, prob.sample_weight, p_ws)
+        sub.set_grouped(prob.grouped)
+        return sub
     if prob.loss in _core.LINK_LOSSES:
         sub = _core.Problem.link(A_ws, prob.b, prob.loss, prob.threshold, sample_weight=prob.sample_weight)
         if p_ws is not None:
@@ -77,6 +85,12 @@ def _sub_problem(prob, A_ws, p_ws):
 def _factors(prob):
     """The penalty factors over the device columns (fp32, 1 on the padding), or None."""
     return None if prob._coord[0] is None else prob._coord[0][: prob.n_dev]
+
+
+def _free(prob):
+    """The mask of the unpenalised coordinates (factor 0): they are in every set."""
+    pf = _factors(prob)
+    return _mask(prob) if pf is None else (pf == 0).to(torch.uint8)
 
 
 def _check_weights(prob, alphas):
@@ -121,12 +135,7 @@ def kkt_excess(prob, X, alphas):
     Xd = _block(prob, X)
     if Xd.shape[1] != len(alphas):
         raise ValueError(f"X has {Xd.shape[1]} columns for {len(alphas)} weights")
-    empty, worst = _mask(prob), None
-    for first, number in _its._groups(len(alphas), _its.LOCKSTEP_COLUMNS):
-        G = prob.gradient_block(Xd[:, first:first + number])
-        excess, _ = prob.kkt_scan(G, [a1 for a1, _ in alphas[first:first + number]], 0.0, empty)
-        worst = excess if worst is None else torch.maximum(worst, excess)
-    return _core.from_device_vec(prob.vec_out(worst), prob.like)
+    return _worst_excess(prob, _steps(prob), Xd, alphas)
 
 
 def alpha_max(prob):
@@ -135,11 +144,7 @@ def alpha_max(prob):
     not a solution at any weight; the value is then the gradient's at 0 all the same, the customary top of a path.
     Synchronises."""
     prob = _handle(prob, None, None, "alpha_max")
-    pf = _factors(prob)
-    free = _mask(prob) if pf is None else (pf == 0).to(torch.uint8)
-    G = prob.gradient_block(torch.zeros(prob.n_dev, 1, dtype=torch.float32, device=prob.device))
-    excess, _ = prob.kkt_scan(G, [1.0], 0.0, free)
-    return float(excess.max())
+    return _top_excess(prob, _steps(prob))
 
 
 def _lockstep(prob, fam, prms, X0, max_iter):
@@ -162,26 +167,114 @@ def _lockstep(prob, fam, prms, X0, max_iter):
     return out
 
 
-# What the outer loops (`_solve_group`, `duality._certified_group`) take from the device, so that a family whose fit spans
-# several columns runs the same loops (multinomial_ws.py).  width: columns per fit.  gradient(prob, X) -> the gradient block.
-# scan(prob, G, a1s, slack, in_ws) -> (excess, violators), one weight per fit.  sub_problem(prob, A_ws, p_ws) -> the problem on
-# the gathered columns.  certificate(prob, X, alphas) -> (primal, dual, gap, scale per fit, G): duality.py's.
-_Steps = collections.namedtuple("_Steps", "width gradient scan sub_problem certificate")
-_STEPS = _Steps(1, lambda prob, X: prob.gradient_block(X), lambda prob, G, a1s, slack, in_ws: prob.kkt_scan(G, a1s, slack, in_ws),
-                _sub_problem, None)
+# What the outer loops (`_solve_group`, `duality._certified_group`) and their driver take from a loss family, so that a family
+# whose fit spans several columns runs the same loops.  width: columns per fit.  gradient(prob, X) -> the gradient block.
+# scan(prob, G, a1s, slack, in_ws) -> (excess, violators), one weight per fit.  certificate(prob, X, a1s, a2s) -> (out64, G), the
+# values of a fit at its first column (`duality._certificate` reads them).  groups(count) -> the (first, number) runs of weights
+# that share the 16 lockstep columns.  fits(prob, X, number) -> the solutions in the columns of X, of the kind that went in.
+_Steps = collections.namedtuple("_Steps", "width gradient scan certificate groups fits")
 
 
-def _solve_group(prob, fam, alphas, max_iter, kkt_tol, max_rounds, grow, max_fraction, L, t_init_factor, initial, steps=_STEPS):
+def _steps(prob):
+    P = _core.Problem
+    if prob.loss == "multinomial":
+        C = prob.classes
+        return _Steps(C, P.multinomial_gradient_block, P.multinomial_kkt_scan, P.multinomial_duality_gap_block,
+                      lambda count: _its.pack_groups(count, C),
+                      lambda prob, X, number: [_core.from_device_vec(X[: prob.n, v * C:(v + 1) * C].contiguous(), prob.like) for v in range(number)])
+    return _Steps(1, P.gradient_block, P.kkt_scan, P.duality_gap_block, lambda count: _its._groups(count, _its.LOCKSTEP_COLUMNS),
+                  lambda prob, X, number: [_core.from_device_vec(prob.vec_out(X[:, v]), prob.like) for v in range(number)])
+
+
+def _worst_excess(prob, steps, Xd, alphas):
+    """`kkt_excess` on the device block Xd (one fit per weight): the largest excess over the groups, with an empty set."""
+    empty, worst, W = _mask(prob), None, steps.width
+    for first, number in steps.groups(len(alphas)):
+        G = steps.gradient(prob, Xd[:, first * W:(first + number) * W])
+        excess, _ = steps.scan(prob, G, [a1 for a1, _ in alphas[first:first + number]], 0.0, empty)
+        worst = excess if worst is None else torch.maximum(worst, excess)
+    return _core.from_device_vec(prob.vec_out(worst), prob.like)
+
+
+def _top_excess(prob, steps):
+    """`alpha_max`: the largest excess of one fit at X = 0 under weight 1 over the penalised coordinates."""
+    G = steps.gradient(prob, torch.zeros(prob.n_dev, steps.width, dtype=torch.float32, device=prob.device))
+    excess, _ = steps.scan(prob, G, [1.0], 0.0, _free(prob))
+    return float(excess.max())
+
+
+# ---- the pieces the two outer loops share ---------------------------------------------------------------------------------------
+def _initial(prob, initial, what):
+    """`initial=` of a path as sorted, distinct device numbers (None stays None); what: "column" or "coordinate"."""
+    if initial is None:
+        return None
+    initial = torch.unique(torch.as_tensor(np.asarray(initial.cpu() if _core.is_tensor(initial) else initial)).to(torch.int64).reshape(-1))
+    if initial.numel() == 0 or int(initial[0]) < 0 or int(initial[-1]) >= prob.n:
+        raise ValueError(f"initial: {what} numbers in 0 .. {prob.n - 1} expected")
+    return initial.to(prob.device)
+
+
+def _gather(prob, fam, alphas, idx, L, t_init_factor):
+    """The set idx as a sub-problem with its lockstep parameters: A_ws with the columns rounded up to 64, at least 128, zero beyond
+    the set; the gathered factors (1 on the padding: its columns are zero)."""
+    n_ws = int(idx.numel())
+    n_ws_pad = max(MIN_COLUMNS, (n_ws + PAD_COLUMNS - 1) // PAD_COLUMNS * PAD_COLUMNS)
+    A_ws = prob.gather_columns(idx, n_ws_pad)
+    pf, p_ws = _factors(prob), None
+    if pf is not None:
+        p_ws = torch.ones(n_ws_pad, dtype=torch.float64)
+        p_ws[:n_ws] = pf[idx].to("cpu", torch.float64)
+        p_ws = p_ws.numpy()
+    sub = _sub_problem(prob, A_ws, p_ws)
+    return sub, _its._path_params(sub, alphas, L, fam, t_init_factor, None)
+
+
+def _round(sub, fam, prms, X, idx, first, max_iter):
+    """One round on the gathered set: the lockstep from X restricted to the set (from zero in a first round at X = 0), scattered
+    back into X."""
+    n_ws, X0 = int(idx.numel()), None
+    if not first or bool((X != 0).any()):
+        X0 = torch.zeros(sub.n, X.shape[1], dtype=torch.float64, device=X.device)
+        X0[:n_ws] = X[idx]
+    X[idx] = _lockstep(sub, fam, prms, X0, max_iter)[:n_ws]
+
+
+def _grow(mask, excess, viol, n_ws, grow):
+    """The violators join the set; when they are fewer than (grow - 1) |set|, so do the next largest excess values up to that
+    number (violators come first)."""
+    mask[viol.long()] = 1
+    want = int((grow - 1.0) * n_ws)
+    if int(viol.numel()) < want:
+        vals, cand = torch.topk(excess, min(want, int(excess.numel())))
+        mask[cand[vals > 0]] = 1
+
+
+def _fall_back(prob, fam, alphas, X, L, t_init_factor, max_iter):
+    """The full lockstep of the group, warm-started from X."""
+    prms = _its._path_params(prob, alphas, L, fam, t_init_factor, None)
+    return _lockstep(prob, fam, prms, X if bool((X != 0).any()) else None, max_iter)
+
+
+def _drive(prob, alphas, steps, group, return_info):
+    """A path front end after its checks: group(weights of one run) -> (X, info) over the runs of `steps.groups`."""
+    xs, infos = [], []
+    for first, number in steps.groups(len(alphas)):
+        X, info = group(alphas[first:first + number])
+        xs += steps.fits(prob, X, number)
+        infos.append(info)
+    return (xs, infos) if return_info else xs
+
+
+def _solve_group(prob, fam, steps, alphas, max_iter, kkt_tol, max_rounds, grow, max_fraction, L, t_init_factor, initial):
     """One group of weights (up to 16 columns): (X as an n_dev x (fits * width) float64 device block, WorkingSetInfo)."""
     nv, a1s = len(alphas) * steps.width, [a1 for a1, _ in alphas]
-    pf = _factors(prob)
     X = torch.zeros(prob.n_dev, nv, dtype=torch.float64, device=prob.device)
     full_gradients, sizes = 0, []
     if initial is not None:
         mask = _mask(prob, initial)
         worst = float("nan")
     else:
-        free = _mask(prob) if pf is None else (pf == 0).to(torch.uint8)
+        free = _free(prob)
         excess, viol = steps.scan(prob, steps.gradient(prob, X), a1s, 0.0, free)
         full_gradients += 1
         mask = free.clone()
@@ -198,36 +291,17 @@ def _solve_group(prob, fam, alphas, max_iter, kkt_tol, max_rounds, grow, max_fra
             fell_back = True
             break
         sizes.append(n_ws)
-        n_ws_pad = max(MIN_COLUMNS, (n_ws + PAD_COLUMNS - 1) // PAD_COLUMNS * PAD_COLUMNS)
-        A_ws = prob.gather_columns(idx, n_ws_pad)
-        p_ws = None
-        if pf is not None:                               # padding coordinates get factor 1: their columns are zero
-            p_ws = torch.ones(n_ws_pad, dtype=torch.float64)
-            p_ws[:n_ws] = pf[idx].to("cpu", torch.float64)
-            p_ws = p_ws.numpy()
-        sub = steps.sub_problem(prob, A_ws, p_ws)
-        prms = _its._path_params(sub, alphas, L, fam, t_init_factor, None)
-        X0 = None
-        if len(sizes) > 1 or bool((X != 0).any()):
-            X0 = torch.zeros(n_ws_pad, nv, dtype=torch.float64, device=prob.device)
-            X0[:n_ws] = X[idx]
-        Xs = _lockstep(sub, fam, prms, X0, max_iter)
-        X[idx] = Xs[:n_ws]
-        del sub, A_ws                                    # one gathered matrix at a time
+        sub, prms = _gather(prob, fam, alphas, idx, L, t_init_factor)
+        _round(sub, fam, prms, X, idx, len(sizes) == 1, max_iter)
+        del sub                                          # one gathered matrix at a time
         excess, viol = steps.scan(prob, steps.gradient(prob, X), a1s, kkt_tol, mask)
         full_gradients += 1
         worst = float(excess.max())
-        count = int(viol.numel())
-        if count == 0:
+        if int(viol.numel()) == 0:
             break
-        mask[viol.long()] = 1
-        want = int((grow - 1.0) * n_ws)
-        if count < want:                                 # the next largest excess values up to that size (violators come first)
-            vals, cand = torch.topk(excess, min(want, prob.n_dev))
-            mask[cand[vals > 0]] = 1
+        _grow(mask, excess, viol, n_ws, grow)
     if fell_back:
-        prms = _its._path_params(prob, alphas, L, fam, t_init_factor, None)
-        X = _lockstep(prob, fam, prms, X if bool((X != 0).any()) else None, max_iter)
+        X = _fall_back(prob, fam, alphas, X, L, t_init_factor, max_iter)
         excess, _ = steps.scan(prob, steps.gradient(prob, X), a1s, kkt_tol, (X != 0).any(dim=1).to(torch.uint8))
         full_gradients += 1
         worst = float(excess.max())
@@ -264,16 +338,7 @@ def working_set_path(A, b, alphas, max_iter: int = 500, *, kkt_tol: float = 1e-4
         raise ValueError("working_set_path: grow > 1, 0 < max_fraction <= 1, max_rounds >= 1 and kkt_tol >= 0 expected")
     prob = _handle(A, b, dtype, "working_set_path")
     _check_weights(prob, alphas)
-    if initial is not None:
-        initial = torch.unique(torch.as_tensor(np.asarray(initial.cpu() if _core.is_tensor(initial) else initial)).to(torch.int64).reshape(-1))
-        if initial.numel() == 0 or int(initial[0]) < 0 or int(initial[-1]) >= prob.n:
-            raise ValueError(f"initial: column numbers in 0 .. {prob.n - 1} expected")
-        initial = initial.to(prob.device)
-    fam = _family(prob, max_iter)
-    xs, infos = [], []
-    for first, number in _its._groups(len(alphas), _its.LOCKSTEP_COLUMNS):
-        X, info = _solve_group(prob, fam, alphas[first:first + number], max_iter, kkt_tol, max_rounds, grow, max_fraction, L,
-                               t_init_factor, initial)
-        xs += [_core.from_device_vec(prob.vec_out(X[:, v]), prob.like) for v in range(number)]
-        infos.append(info)
-    return (xs, infos) if return_info else xs
+    initial = _initial(prob, initial, "column")
+    fam, steps = _family(prob, max_iter), _steps(prob)
+    return _drive(prob, alphas, steps, lambda part: _solve_group(prob, fam, steps, part, max_iter, kkt_tol, max_rounds, grow, max_fraction,
+                                                                  L, t_init_factor, initial), return_info)

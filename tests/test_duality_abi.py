@@ -155,9 +155,12 @@ def _source():
 
 def test_kernel_source_has_no_atomics_flags_or_waits():
     text = _source()
-    for word in ("atomic", "volatile", "while", "__threadfence"):
+    for word in ("atomic", "volatile", "while", "__threadfence", "asm"):
         assert not re.search(word, text, flags=re.I), word
     code = re.sub(r"//[^\n]*", "", text)
+    # the column pass serves every loss family: it takes the class count and the kind of penalty (1 and 0 from fos_duality_gap)
+    assert re.search(r"dual_scale_kernel\(const float\* __restrict__ X, const float\* __restrict__ G,\s+int64_t n, int classes, int grouped, "
+                     r"ClassWeights wts", code)
     assert re.search(r"template\s*<int LOSS, bool WEIGHT>\s*__global__\s+__launch_bounds__\(DL_THREADS\)\s+void\s+dual_link_kernel", code)
     assert re.search(r"__global__\s+__launch_bounds__\(DS_THREADS\)\s+void\s+dual_scale_kernel", code)
     assert re.search(r"__global__\s+__launch_bounds__\(DF_THREADS\)\s+void\s+dual_finish_kernel", code)

@@ -60,8 +60,13 @@ def test_the_dispatchers_put_the_pointwise_link_between_the_products():
                      r"L\.row_weight\s*=\s*nullptr;\s*\}", mfma)
     assert mfma.index("launch_batch_product") < mfma.index("launch_pointwise_link") < mfma.index("launch_gram_panel")
     assert re.search(r"use_cluster\s*=\s*p->multi\.cp_cs\s*&&\s*!two_products\s*&&\s*!softmax\s*&&\s*!link", mfma)
-    grad = gd.body_of("fos_gradient_batch")
+    # fos_gradient_batch hands its panel loop to the walk it shares with the multinomial gradient: plain product 1 and the pointwise
+    # stage exactly on a link loss, and in the walk the stage stands between the products
+    assert re.search(r"const bool link = link_loss\(p\);\s*return gradient_walk\(\{\"fos_gradient_batch\",[^;]*, link, "
+                     r"link \? WalkLink::pointwise : WalkLink::none, true\},", gd.body_of("fos_gradient_batch"))
+    grad = _body(text, r"static\s+int\s+gradient_walk\s*\([^)]*\)\s*(?=\{)")
     assert grad.index("launch_batch_product") < grad.index("launch_pointwise_link") < grad.index("launch_gram_panel")
+    assert re.search(r"if \(w\.link == WalkLink::pointwise && \(rc = launch_pointwise_link\(", grad) and grad.count("launch_gram_panel") == 1
     assert re.search(r"residual_batch_link\(p,\s*\"fos_residual_batch\",\s*X,\s*nv,\s*out16,\s*nullptr,\s*nullptr\)", gd.body_of("fos_residual_batch"))
     assert re.search(r"residual_batch_link\(p,\s*\"fos_residual_batch_folds\",\s*X,\s*nv,\s*out16,\s*fold_of_row,\s*&hb\)",
                      gd.body_of("fos_residual_batch_folds"))

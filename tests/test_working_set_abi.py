@@ -68,6 +68,18 @@ def test_kernels_live_in_their_own_header_and_use_no_atomics():
     assert re.search(r"template\s*<int ESZ>\s*static\s+__global__\s+__launch_bounds__\(WS_THREADS\)\s+void\s+gather_columns_kernel", code)
     assert re.search(r"__global__\s+__launch_bounds__\(KS_THREADS\)\s+void\s+kkt_scan_kernel", code)
     assert "__builtin_nontemporal_load" in code and not re.search(r"atomic", code, flags=re.I)
+    # the scan's body is written once for every loss family (C columns of a fit seen together) and kkt_scan_kernel is its
+    # instantiation with C = 1, l1 known at compile time; that part of the header - comments too - has no atomics, flags or
+    # waits, and the grouped decision compares squares: the one square root of the body feeds the excess alone
+    assert re.search(r"template\s*<bool ONE_COLUMN>\s*__device__\s+__forceinline__\s+void\s+kkt_scan_body\(", code)
+    assert re.search(r"kkt_scan_kernel\([^)]*\)\s*\{\s*kkt_scan_body<true>\(G, n, nv, 1, 0, w,", code)
+    assert code.count("__global__") == 2
+    with open(os.path.join(ROOT, "fastoptsolver_amd", "csrc", "working_set.hpp")) as fh:
+        text = fh.read()
+    for word in ("atomic", "volatile", "while", "__threadfence", "asm"):
+        assert not re.search(word, text[text.index("---- KKT scan"):], flags=re.I), word
+    scan = code[code.index("kkt_scan_body"):]
+    assert scan.count("sqrt(") == 1 and re.search(r"viol\s*=\s*viol\s*\|\|\s*q\s*>\s*thr\s*\*\s*thr", scan)
     from fastoptsolver_amd import build
     assert os.path.join(ROOT, "include", "fos_working_set.h") in build.HEADERS
     assert os.path.join(ROOT, "fastoptsolver_amd", "csrc", "working_set.hpp") in build.HEADERS
