@@ -27,6 +27,10 @@ from .duality import DualityGap, GapInfo, certified_path, duality_gap           
 from .multinomial_ws import (multinomial_alpha_max, multinomial_certified_path, multinomial_duality_gap,   # noqa: F401
                              multinomial_kkt_excess, multinomial_working_set_path)
 
+# resampled fits in the lockstep (bootstrap paths, stability selection): importable from the package likewise
+from .resample import (ResampleResult, StabilityResult, bootstrap_counts, pack_counts, resampled_lipschitz,   # noqa: F401
+                       resampled_path, selection_frequencies, stability_selection, subsample_counts)
+
 __all__ = ["fista", "fista_delta", "fista_path", "fista_cv", "CVResult", "ista", "estimate_lipschitz", "reset_metrics", "get_metrics", "LBFGSSolver",
            "compute_objective", "prox_l1", "prox_elastic_net", "LeastSquares", "L1Prox", "ElasticNetProx",
            "prepare", "prepare_weighted", "prepare_penalized", "Problem", "FosError", "logistic_path", "logistic_cv", "logistic_objective", "LogisticCVResult",

@@ -196,6 +196,14 @@ MULTINOMIAL_WS_SIGNATURES = {
 }
 
 
+# include/fos_resample.h: a resample of the rows per lockstep column (bootstrap paths, stability selection)
+RESAMPLE_SIGNATURES = {
+    "fos_fista_run_multi_resampled": (_i32, [_vp, _i32, _i32, _vp]),
+    "fos_gradient_batch_resampled": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "fos_gram_apply_resampled": (_i32, [_vp, _i32, _vp, _vp, _vp]),
+}
+
+
 def load():
     """Return the loaded CDLL (cached).  Raises FosError if the library is absent."""
     global _lib
@@ -207,7 +215,7 @@ def load():
             "Build it with:  python -m fastoptsolver_amd.build   (needs hipcc; cross-compiles for gfx950)")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **FEATURE_GROUP_SIGNATURES, **WORKING_SET_SIGNATURES, **LINK_LOSS_SIGNATURES,
-                              **DUALITY_SIGNATURES, **MULTINOMIAL_WS_SIGNATURES}.items():
+                              **DUALITY_SIGNATURES, **MULTINOMIAL_WS_SIGNATURES, **RESAMPLE_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -23,6 +23,7 @@ HEADERS.append(os.path.join(os.path.dirname(HERE), "include", "fos_working_set.h
 HEADERS.append(os.path.join(os.path.dirname(HERE), "include", "fos_link_loss.h"))
 HEADERS.append(os.path.join(os.path.dirname(HERE), "include", "fos_duality.h"))
 HEADERS.append(os.path.join(os.path.dirname(HERE), "include", "fos_multinomial_ws.h"))
+HEADERS.append(os.path.join(os.path.dirname(HERE), "include", "fos_resample.h"))
 DEPS = SOURCES + HEADERS
 OBJ_DIR = os.path.join(CSRC, "build")
 OUT = os.path.join(HERE, "libfos_hip.so")

@@ -6,6 +6,7 @@
 #include "working_set.hpp"
 #include "duality.hpp"
 #include "multinomial_ws.hpp"
+#include "resample_link.hpp"
 #include <cassert>
 
 using namespace fosapi;
@@ -719,6 +720,9 @@ static fos::MultiUpdate multi_update(fos_fista* const* fs, int nv, bool controll
 // A Huber or squared-hinge problem (fos_problem_set_link_loss): the same sequence with the pointwise link kernel
 // (pointwise_link.hpp), R = clip(A_panel Y - b, -c, c) or -b max(0, 1 - b A_panel Y).  The columns are independent fits: any nv,
 // plain or controlled.
+// A resample of the rows per column (fos_fista_run_multi_resampled: counts, a nibble per row and column): the same sequence on
+// any of the four losses above with the resample link kernel (resample_link.hpp), which forms the loss's residual itself and
+// multiplies it by the bound weight and the column's multiplicity; any nv, plain or controlled.
 
 // Handles under the group penalty (fos_fista_params.group = G >= 2; checked by group_refusal before they get here): always the
 // two-product form, plain; the G columns of a fit are updated together by the one launch of launch_group_update, in place of
@@ -805,6 +809,44 @@ static int launch_separable_update(fos_fista* const* fs, int nv, int g_splits, i
   return FOS_OK;
 }
 
+// The resample link kernel (resample_link.hpp) behind product 1 on one row panel: the `rows` rows of p->multi.rbuf16 that product
+// 1 in its plain storing form has just filled with Z of the panel starting at row0.  counts: the words of ALL rows (offset by
+// row0 here, as b and the weights are).  gram: the loss-free form R = (w c) z; else the problem's loss.  oob: only the
+// out-of-bag sums, R is left as it is.  One lane per 16-byte quad of a row, grid-stride: at most 2 * ncu workgroups, within the
+// 3 * ncu + 8 rows of cand.q_part; *nwg_out = the rows of q_part written (0 in the Gram form, which has no sums).
+static int launch_resample_link(fos_problem* p, bool gram, int64_t row0, int64_t rows, int nv, const uint64_t* counts, int oob,
+                                double* q_part, int* nwg_out) {
+  if (!counts || rows < 1 || rows > p->multi.panel_rows || row0 < 0 || row0 + rows > p->m || nv < 1 || nv > fos::BT_NV ||
+      (gram ? oob != 0 : (!p->b || !q_part)))
+    return fail(FOS_ERR_STATE, "launch_resample_link: not a panel of a resampled pass");
+  const int nwg = (int)std::min<int64_t>((4 * rows + fos::RL_THREADS - 1) / fos::RL_THREADS, 2 * (int64_t)p->ncu);
+  const float* w = p->row_weight ? p->row_weight + row0 : nullptr;
+  const float* b = gram ? nullptr : p->b + row0;
+  const uint16_t* c16 = reinterpret_cast<const uint16_t*>(counts + row0);
+  const float c = (float)p->link_param;
+#define FOS_RESAMPLE(K, M, W)                                                                                                  \
+  hipLaunchKernelGGL((fos::resample_link_kernel<fos::K, fos::M, W>), dim3(nwg), dim3(fos::RL_THREADS), 0, p->stream,           \
+                     p->multi.rbuf16.get(), rows, b, c, nv, w, c16, q_part, (const int*)nullptr)
+#define FOS_RESAMPLE_FORM(K)                                                                                      \
+  {                                                                                                               \
+    if (oob) { if (w) FOS_RESAMPLE(K, RESAMPLE_OOB, true); else FOS_RESAMPLE(K, RESAMPLE_OOB, false); }           \
+    else { if (w) FOS_RESAMPLE(K, RESAMPLE_INBAG, true); else FOS_RESAMPLE(K, RESAMPLE_INBAG, false); }           \
+  }
+  if (gram) { if (w) FOS_RESAMPLE(RESAMPLE_GRAM, RESAMPLE_INBAG, true); else FOS_RESAMPLE(RESAMPLE_GRAM, RESAMPLE_INBAG, false); }
+  else switch (p->loss) {
+    case FOS_LOSS_SQUARED: FOS_RESAMPLE_FORM(RESAMPLE_SQUARED) break;
+    case FOS_LOSS_LOGISTIC: FOS_RESAMPLE_FORM(RESAMPLE_LOGISTIC) break;
+    case FOS_LOSS_HUBER: FOS_RESAMPLE_FORM(RESAMPLE_HUBER) break;
+    case FOS_LOSS_SQUARED_HINGE: FOS_RESAMPLE_FORM(RESAMPLE_SQUARED_HINGE) break;
+    default: return fail(FOS_ERR_STATE, "launch_resample_link: the loss has no resampled form");
+  }
+#undef FOS_RESAMPLE_FORM
+#undef FOS_RESAMPLE
+  LAUNCH_CHECK();
+  *nwg_out = gram ? 0 : nwg;
+  return FOS_OK;
+}
+
 // One call of a lockstep entry point, as its arguments came in (checked), and what lockstep_route decides for it.
 struct LockstepCall {
   fos_fista* const* fs;
@@ -815,6 +857,7 @@ struct LockstepCall {
   const int32_t* held_ids;
   const fos::FoldHeld* held;
   const char* fn;                    // the entry point, for messages
+  const uint64_t* counts = nullptr;  // fos_fista_run_multi_resampled: the multiplicity words of all rows (null: every row once)
 };
 enum LockstepEngine { ENGINE_SINGLE, ENGINE_VALU, ENGINE_MFMA };
 struct LockstepRoute {
@@ -850,9 +893,11 @@ static int run_multi_mfma(const LockstepCall& c, const LockstepRoute& r) {
   const bool group_penalty = grouped(fs[0]->prm);            // the fits' columns are updated together (launch_group_update)
   const bool fgroup = has_fgroups(p);                        // fos_feature_groups_bind: the update is launch_fgroup_update
   const bool two_products = b16 || fold_of_row || logit || weighted || has_coord(p) || group_penalty || fgroup;
-  bool use_cluster = p->multi.cp_cs && !two_products && !softmax && !link;
+  const uint64_t* counts = c.counts;                         // a resample per column: the resample link kernel, in the same place
+  bool use_cluster = p->multi.cp_cs && !two_products && !softmax && !link && !counts;
   int g_splits = p->multi.gram_splits;
   if ((two_products || softmax || link) && (rc = two_product_splits(p, &g_splits))) return rc;
+  if (counts && (rc = two_product_splits(p, &g_splits))) return rc;
   // candidate block: zero everywhere (padding columns, unused slots), then y_k of every state machine
   const size_t per_entry = is_bf16 ? 3 * sizeof(unsigned short) : sizeof(float);
   HIP_TRY(hipMemsetAsync(p->cand.xp, 0, (size_t)p->cand.n_pad * fos::BT_NV * per_entry, p->stream));
@@ -906,12 +951,14 @@ static int run_multi_mfma(const LockstepCall& c, const LockstepRoute& r) {
       L.row_weight = weighted ? p->row_weight + row0 : nullptr;
       if (softmax) { L.b = nullptr; L.use_b = 0; L.fold_of_row = nullptr; L.held = nullptr; L.row_weight = nullptr; }     // the logits alone
       if (link) { L.b = nullptr; L.use_b = 0; L.fold_of_row = nullptr; L.held = nullptr; L.row_weight = nullptr; }        // A_panel Y alone
+      if (counts) { L.b = nullptr; L.use_b = 0; L.bblock = false; L.row_weight = nullptr; }       // likewise, whatever the loss
       if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
+      if (counts && (rc = launch_resample_link(p, false, row0, rows, nv, counts, 0, p->cand.q_part, &nwg1))) return rc;
       if (softmax && (rc = launch_softmax_link(p, row0, rows, nv, fold_of_row ? fos::FOLD_TRAIN : fos::FOLD_OFF, fold_of_row, held,
                                                p->cand.q_part, &nwg1)))
         return rc;
-      if (link && (rc = launch_pointwise_link(p, row0, rows, nv, fold_of_row ? fos::FOLD_TRAIN : fos::FOLD_OFF, fold_of_row, held,
-                                              p->cand.q_part, &nwg1)))
+      if (link && !counts && (rc = launch_pointwise_link(p, row0, rows, nv, fold_of_row ? fos::FOLD_TRAIN : fos::FOLD_OFF, fold_of_row, held,
+                                                         p->cand.q_part, &nwg1)))
         return rc;
       if (cols && (rc = reduce_across(p, p->multi.rbuf16, (size_t)rows * fos::BT_NV, false))) return rc;
       if ((rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
@@ -1082,6 +1129,9 @@ static int lockstep_route(const LockstepCall& c, LockstepRoute* r) {
                                             "matrix-core pair");
     return control_refusal();
   }
+  // a resample per column (fos_fista_run_multi_resampled, which has refused what the pair does not serve: resample_refusal) on
+  // the plain squared loss: the pair for any nv, as the link kernel sits between its products
+  if (c.counts) return control_refusal();
   if (c.fold_of_row) {
     // always the two matrix-core products, for any number of state machines: the alternative is a copy of A per fold
     if (!p->b) return fail(FOS_ERR_UNSUPPORTED, "fos_fista_run_multi_folds: the problem has no b of its own");
@@ -1201,6 +1251,39 @@ int fos_fista_run_multi_folds(fos_fista* const* fs, int nv, int iters, const uin
   return run_lockstep(LockstepCall{fs, nv, iters, nullptr, 0, fold_of_row, held, &hb, "fos_fista_run_multi_folds"});
 }
 
+// What a resampled pass (include/fos_resample.h) does not serve, in its own words and before any launch or change of handle
+// state: the link kernel needs whole columns that are fits of their own, b, one card and the matrix-core pair.  needs_b: null for
+// the loss-free operator.
+static int resample_refusal(const fos_problem* p, const char* fn, const char* needs_b) {
+  if (p->loss == FOS_LOSS_MULTINOMIAL)
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": a multinomial problem is not served: its columns are the classes of joint "
+                                     "fits, not fits of their own (squared, logistic, Huber and squared-hinge loss)");
+  if (needs_b && !p->b) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": " + needs_b);
+  if (p->comm || p->col_sharded)
+    return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": row- or column-sharded problems are not served (the counts are those of all rows)");
+  if (!pair_dd_multi_supported(p)) return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the shape has no matrix-core pair");
+  return FOS_OK;
+}
+
+// (include/fos_resample.h declares it, not fos.h: the linkage is spelled out here, as on no entry point of fos.h's closed list)
+extern "C" int fos_fista_run_multi_resampled(fos_fista* const* fs, int nv, int iters, const uint64_t* counts) {
+  const char* fn = "fos_fista_run_multi_resampled";
+  if (!fs || !counts || nv < 1 || nv > fos::BT_NV || iters < 0 || ((uintptr_t)counts & 7) != 0)
+    return fail(FOS_ERR_ARG, std::string(fn) + ": bad argument (null pointer, nv outside 1..16, iters < 0 or counts not 8-byte aligned)");
+  for (int v = 0; v < nv; ++v)
+    if (!fs[v] || fs[v]->p != fs[0]->p) return fail(FOS_ERR_ARG, std::string(fn) + ": handles must share one problem");
+  if (int rc_ = resample_refusal(fs[0]->p, fn, "the resampled data term needs b")) return rc_;
+  for (int v = 0; v < nv; ++v) {
+    if (grouped(fs[v]->prm))
+      return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": the group penalty across columns (fos_fista_params.group >= 2) ties the "
+                                       "columns into one fit; a resample per column would break it");
+    if (fs[v]->prm.tol_grad != 0.0 || fs[v]->precise || fs[v]->prm.tau_from_state)
+      return fail(FOS_ERR_UNSUPPORTED, std::string(fn) + ": no gradient-norm rule, fp64 split gradient or device-held step (plain "
+                                       "runs, adaptive restart, step and ratio tolerance per column)");
+  }
+  return run_lockstep(LockstepCall{fs, nv, iters, nullptr, 0, nullptr, nullptr, nullptr, fn, counts});
+}
+
 // G[j][c] = sum over the row splits of slabs16[split][j][c]: the slab sum of fos_gram_apply.
 static __global__ __launch_bounds__(256) void gram_slab_sum_kernel(const float* __restrict__ slabs, int splits, int64_t n, int nv,
                                                                    float* __restrict__ G) {
@@ -1229,6 +1312,35 @@ int fos_gram_apply(const float* X, int nv, fos_problem* p, float* G) {
     BatchLaunch L{};                 // R = A_panel X, or w (A_panel X): neither b nor the loss enters
     L.A = Ap; L.rows = rows; L.rout = p->multi.rbuf16; L.row_weight = p->row_weight ? p->row_weight + row0 : nullptr;
     if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
+    if ((rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
+  }
+  hipLaunchKernelGGL(gram_slab_sum_kernel, dim3(grid_1d((int64_t)nv * p->n, 256, 1024)), dim3(256), 0, p->stream, p->multi.slabs16,
+                     g_splits, p->n, nv, G);
+  LAUNCH_CHECK();
+  return FOS_OK;
+}
+
+// fos_gram_apply with a resample per column: product 1 plain, the Gram form of the resample link kernel - R = (w c_j) z, the
+// bound weights enter there -, product 2.
+int fos_gram_apply_resampled(const float* X, int nv, const uint64_t* counts, fos_problem* p, float* G) {
+  if (!X || !counts || !p || !G || nv < 1 || nv > fos::BT_NV || ((uintptr_t)counts & 7) != 0)
+    return fail(FOS_ERR_ARG, "fos_gram_apply_resampled: bad argument (null pointer, nv outside 1..16 or counts not 8-byte aligned)");
+  int rc = resample_refusal(p, "fos_gram_apply_resampled", nullptr);
+  if (rc) return rc;
+  if ((rc = ensure_batch_workspace(p))) return rc;
+  if ((rc = plan_multi_mfma(p))) return rc;
+  int g_splits = 0;
+  if ((rc = two_product_splits(p, &g_splits))) return rc;
+  const int64_t esz = p->dtype == FOS_BF16 ? 2 : 4;
+  if ((rc = pack_candidates(p, X, nv))) return rc;
+  for (int64_t row0 = 0, panel = 0; row0 < p->m; row0 += p->multi.panel_rows, ++panel) {
+    const int64_t rows = std::min<int64_t>(p->multi.panel_rows, p->m - row0);
+    const char* Ap = reinterpret_cast<const char*>(p->A) + (size_t)row0 * p->lda * esz;
+    int nwg1 = 0;
+    BatchLaunch L{};                 // Z = A_panel X
+    L.A = Ap; L.rows = rows; L.rout = p->multi.rbuf16;
+    if ((rc = launch_batch_product(p, L, &nwg1))) return rc;
+    if ((rc = launch_resample_link(p, true, row0, rows, nv, counts, 0, nullptr, &nwg1))) return rc;
     if ((rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
   }
   hipLaunchKernelGGL(gram_slab_sum_kernel, dim3(grid_1d((int64_t)nv * p->n, 256, 1024)), dim3(256), 0, p->stream, p->multi.slabs16,
@@ -1607,14 +1719,16 @@ static int class_weights(int nfits, const double* a1, const double* a2, const ch
 }
 
 // What a loss family puts between product 1 and product 2 of the gradient walk.
-enum class WalkLink { none, pointwise, softmax };
+enum class WalkLink { none, pointwise, softmax, resample };
 struct GradientWalk {
   const char* fn;        // the entry point, for the messages
   const char* needs_b;   // its words for a problem without b
   bool plain;            // product 1 without b and the bound weights (Z = A_panel X: a link kernel follows); else with them
-  WalkLink link;         // none: product 1's own loss epilogue; launch_pointwise_link; launch_softmax_link
+  WalkLink link;         // none: product 1's own loss epilogue; launch_pointwise_link; launch_softmax_link; launch_resample_link
   bool staged;           // the panel's partials land in cand.q_part (several panels: copied behind each other into
                          // ws.grad_part); else behind those of the panels before it in ws.link_part
+  const uint64_t* counts = nullptr;      // WalkLink::resample: the multiplicity words of all rows
+  int oob = 0;           // ... and whether only the out-of-bag sums are wanted: product 2 and the slab sum do not run, G is not written
 };
 
 // The gradient of the data term at the nv columns of X: per row panel product 1 in its storing form, the family's link stage and
@@ -1648,17 +1762,20 @@ static int gradient_walk(const GradientWalk& w, const float* X, int nv, fos_prob
     double* part = w.staged ? p->cand.q_part.get() : p->ws.link_part + (size_t)nparts * fos::BT_NV;
     if (w.link == WalkLink::pointwise && (rc = launch_pointwise_link(p, row0, rows, nv, fos::FOLD_OFF, nullptr, nullptr, part, &nwg))) return rc;
     if (w.link == WalkLink::softmax && (rc = launch_softmax_link(p, row0, rows, nv, fos::FOLD_OFF, nullptr, nullptr, part, &nwg))) return rc;
+    if (w.link == WalkLink::resample && (rc = launch_resample_link(p, false, row0, rows, nv, w.counts, w.oob, part, &nwg))) return rc;
     if (copied) {
       if ((size_t)nwg > part_rows) return fail(FOS_ERR_STATE, std::string(w.fn) + ": product 1 wrote more partials than cand.q_part holds");
       HIP_TRY(hipMemcpyAsync(p->ws.grad_part + (size_t)nparts * fos::BT_NV, part, (size_t)nwg * fos::BT_NV * sizeof(double),
                              hipMemcpyDeviceToDevice, p->stream));
     }
     nparts += nwg;
-    if ((rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
+    if (!w.oob && (rc = launch_gram_panel(p, Ap, rows, g_splits, panel != 0))) return rc;
   }
-  hipLaunchKernelGGL(gram_slab_sum_kernel, dim3(grid_1d((int64_t)nv * p->n, 256, 1024)), dim3(256), 0, p->stream, p->multi.slabs16,
-                     g_splits, p->n, nv, G);
-  LAUNCH_CHECK();
+  if (!w.oob) {
+    hipLaunchKernelGGL(gram_slab_sum_kernel, dim3(grid_1d((int64_t)nv * p->n, 256, 1024)), dim3(256), 0, p->stream, p->multi.slabs16,
+                       g_splits, p->n, nv, G);
+    LAUNCH_CHECK();
+  }
   if (loss16) {
     const double* parts = !w.staged ? p->ws.link_part.get() : copied ? p->ws.grad_part.get() : p->cand.q_part.get();
     hipLaunchKernelGGL(fos::fold_partials_kernel, dim3(1), dim3(fos::FOLD_THREADS), 0, p->stream, parts, nparts, fos::BT_NV, loss16);
@@ -1679,6 +1796,18 @@ int fos_gradient_batch(const float* X, int nv, fos_problem* p, float* G, double*
   const bool link = link_loss(p);
   return gradient_walk({"fos_gradient_batch", "the gradient of the data term needs b", link, link ? WalkLink::pointwise : WalkLink::none, true},
                        X, nv, p, G, loss16);
+}
+
+// Product 1 runs plain whatever the loss; the resample link kernel leaves R and the partials (with oob the partials alone).
+int fos_gradient_batch_resampled(const float* X, int nv, const uint64_t* counts, int oob, fos_problem* p, float* G, double* loss16) {
+  const char* fn = "fos_gradient_batch_resampled";
+  if (!X || !counts || !p || nv < 1 || nv > fos::BT_NV || ((uintptr_t)counts & 7) != 0 || oob < 0 || oob > 1 || (oob ? !loss16 : !G))
+    return fail(FOS_ERR_ARG, std::string(fn) + ": bad argument (null pointer, nv outside 1..16, counts not 8-byte aligned or oob "
+                             "outside 0..1)");
+  if (int rc = resample_refusal(p, fn, "the resampled data term needs b")) return rc;
+  GradientWalk w{fn, "the resampled data term needs b", true, WalkLink::resample, true};
+  w.counts = counts; w.oob = oob;
+  return gradient_walk(w, X, nv, p, G, loss16);
 }
 
 int fos_gather_columns(const int32_t* idx, int32_t n_ws, void* A_ws, int64_t lda_ws, int32_t n_ws_pad, const fos_problem* p) {

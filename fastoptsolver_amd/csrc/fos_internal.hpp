@@ -22,6 +22,7 @@
 #include "../../include/fos_working_set.h"
 #include "../../include/fos_duality.h"
 #include "../../include/fos_multinomial_ws.h"
+#include "../../include/fos_resample.h"
 #pragma GCC visibility pop
 #include "batch_trial.hpp"
 #include "cluster_pass.hpp"
