@@ -267,6 +267,111 @@ def certificate_gradient(name, cell):
     return G, g_tol
 
 
+# ---- the resampled lockstep (include/fos_resample.h) -------------------------------------------------------------------------------
+# A resampled call is kept off the one-read cluster pass by one term of run_multi_mfma (use_cluster ... && !counts) and works the
+# row splits out again by a line of its own; fos_gradient_batch_resampled and fos_gram_apply_resampled call two_product_splits
+# themselves.  Column j fits the problem with the row weights w * c_j, so the references are tests/_resample.py's (the weighted
+# references).  The step: lambda_max(A^T diag(w c_j) A) <= max_i (w_i c_ij) lambda_max(A^T A), so L_j = max_i c_ij times the
+# bound of the whole A (times WEIGHT_MAX under the "counts" weights) - passed to both sides.
+# cell -> (loss, row weights, recipe of the counts, resamples = lockstep columns)
+RESAMPLE_CELLS = {"resampled_path": ("squared", False, "bootstrap", 5), "resampled_weighted_logistic_path": ("logistic", True, "binary", 3),
+                  "resampled_gradient": ("squared", False, "bootstrap", 16), "resampled_gram": ("squared", True, "binary", 16)}
+RESAMPLE_PLAIN = "resampled_as_the_plain_path"          # part 2: one 0/1 resample under the plain path's own weights and step
+
+
+@functools.lru_cache(maxsize=None)
+def resample_counts(name, recipe, nv):
+    """m x nv int64 multiplicities.  binary: a random half of the rows (0 / 1); bootstrap: m draws of the m rows with replacement
+    per column, as they fall (no planted 15: the largest count sets the step).  Never a column of zeros."""
+    m = SHAPES[name][0]
+    rng = np.random.default_rng(9300 + 31 * nv + m)
+    if recipe == "binary":
+        c = (rng.random((m, nv)) < 0.5).astype(np.int64)
+        c[0] = 1
+    else:
+        assert recipe == "bootstrap"
+        c = np.stack([np.bincount(rng.integers(0, m, size=m), minlength=m) for _ in range(nv)], axis=1).astype(np.int64)
+    assert c.min() == 0 and 1 <= c.max() <= 15 and (c.sum(axis=0) > 0).all()
+    c.setflags(write=False)
+    return c
+
+
+def resample_weights(d, cell, C):
+    """The m x nv weights of the references: w * c_j."""
+    weighted = RESAMPLE_CELLS[cell][1] if cell in RESAMPLE_CELLS else False
+    return C.astype(np.float64) * (d["w"][:, None] if weighted else 1.0)
+
+
+def resample_case(name, cell):
+    """dict(loss, weighted, counts, L - per resample, before the logistic quarter, as resampled_path takes it -, alphas) of a path
+    cell.  The squared cell takes the third weight of the plain ladder, the weighted logistic one the middle weight of its family
+    (a tenth of alpha_max of all rows: a fifth of that of half of them)."""
+    d = data(name)
+    if cell == RESAMPLE_PLAIN:
+        C = resample_counts(name, "binary", 1)
+        return dict(loss="squared", weighted=False, counts=C, L=np.full(1, d["L"]), alphas=plain_alphas(d))
+    loss, weighted, recipe, nv = RESAMPLE_CELLS[cell]
+    C = resample_counts(name, recipe, nv)
+    L = C.max(axis=0) * d["L"] * (WEIGHT_MAX if weighted else 1.0)
+    weights = [alphas(d, loss, weighted)[1] if loss == "logistic" else plain_alphas(d)[2]]
+    return dict(loss=loss, weighted=weighted, counts=C, L=L, alphas=weights)
+
+
+def resample_reference(name, cell, r, a=0):
+    """The fp64 fit of resample r at weight a of a path cell after ITERS iterations (tests/_resample.run on the weights w * c_r)."""
+    from tests import _resample as rsp
+    d, cs = data(name), resample_case(name, cell)
+    w = rsp.effective(d["w"] if cs["weighted"] else None, cs["counts"][:, r])
+    a1, a2 = cs["alphas"][a]
+    return rsp.run(cs["loss"], d["A"], target(d, cs["loss"]), w, a1, a2, cs["L"][r] / rsp.divisor(cs["loss"]), ITERS)[0]
+
+
+def resample_block(d):
+    """The n x 16 block the gradient and Gram cells are asked for (fp32 values): tests/test_gpu_cluster_planned.Batches' recipe
+    scaled so that A x is of order 1, with one all-zero column."""
+    rng = np.random.default_rng(930 + d["seed"])
+    X = 0.05 * rng.standard_normal((d["n"], 16)) * (rng.random((d["n"], 16)) < 0.1)
+    X[:, 1] = 0.0
+    return X.astype(np.float32)
+
+
+# The controlled resampled run: two 0/1 resamples under the 16 weights of the controlled case - 32 (resample, weight) cells, two
+# lockstep groups -, of which the cells stay whose every decision in the fp64 reference is fp32-proof (tests/_coord.fp32_proof;
+# a cell whose fit is still 0 decides on nothing and goes too) and stands MIN_CONTROL_MARGIN clear of its thresholds, as the
+# controlled case below does.  L is the bound of the whole A, valid for 0/1 counts; on half of the rows it is about twice the
+# resample's own constant, the steps are short and no ratio falls below CONTROL's tolerance of 0.5 within 12 iterations (scanned on
+# the reference alone over thresholds 0.95 / 1 and tolerances 0.5 .. 0.8: at 0.5 every cell of cs4 runs to the end, from 0.7 on
+# every cell of both shapes stops by iteration 5).  At 0.6 both shapes have early stops, full runs and genuine restarts.
+RESAMPLE_CONTROL_RESAMPLES = 2
+RESAMPLE_CONTROL = dict(adaptive_restart=True, restart_threshold=0.95, tol_ratio=0.6)
+
+
+@functools.lru_cache(maxsize=None)
+def resample_control_case(name):
+    """(counts m x 2, the 16 weights, {(r, a): the reference run (tests/_coord.run's dict without its problem)} of the kept cells)."""
+    d = data(name)
+    C = resample_counts(name, "binary", RESAMPLE_CONTROL_RESAMPLES)
+    weights = control_alphas(d)
+    kept = {}
+    for r in range(RESAMPLE_CONTROL_RESAMPLES):
+        for a, (a1, a2) in enumerate(weights):
+            ref = cd.run(d["A"], d["b"], a1, a2, d["L"], CONTROL_ITERS, w=C[:, r].astype(np.float64), **RESAMPLE_CONTROL)
+            ref.pop("prob")
+            thresholds = RESAMPLE_CONTROL["restart_threshold"], RESAMPLE_CONTROL["tol_ratio"]
+            if cd.fp32_proof(ref, *thresholds) and cd.decision_margin(ref, *thresholds) >= MIN_CONTROL_MARGIN:
+                kept[(r, a)] = ref
+    return C, weights, kept
+
+
+def check_resample_control(kept):
+    """At least half of the 32 cells stay, and among them one stops early, one runs to the end and one restarts on a finite ratio."""
+    refs = list(kept.values())
+    assert 2 * len(refs) >= RESAMPLE_CONTROL_RESAMPLES * CONTROL_WEIGHTS, len(refs)
+    assert any(r["stopped"] == cd.STOP_RATIO and r["k"] < CONTROL_ITERS for r in refs), "no kept cell stops early"
+    assert any(r["stopped"] == cd.STOP_NONE and r["k"] == CONTROL_ITERS for r in refs), "no kept cell runs to the end"
+    assert sum(cd.genuine_restarts(r, RESAMPLE_CONTROL["restart_threshold"]) for r in refs) >= 1, "no genuine restart"
+
+
 # ---- the device-controlled case ------------------------------------------------------------------------------------------------
 # test_fista_path_lockstep_with_restart_and_ratio_stop's second recipe with the restart threshold moved from 0.9 to 0.95: at 0.9 the
 # cs4 run has a ratio 4.1e-4 from the ratio tolerance (weight 4, iteration 11: 0.49959 against 0.5), which no fp32 run is bound to

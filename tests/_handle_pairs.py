@@ -19,6 +19,12 @@ configuration with factors that the duality-gap certificate serves -, and the "w
 sixth group of weight 0).  The handle BORROWS b (fos.h: "the caller's: never freed here"), so a cell of another loss overwrites the
 bound device vector in place; anything that cached a function of b would show.
 
+The resampled calls (include/fos_resample.h) bind nothing - the multiplicities travel with the call - and share all of the above:
+their cells sit on the existing configurations with the counts of tests/_resample.counts at the shape's rows (bootstrap with the
+planted 15 and 0, or 0/1), the weighted references with the weights w * c_j and L per resample from the oracle's power iteration
+on w * c_j.  The working set and the duality gap of the multinomial lockstep (include/fos_multinomial_ws.h) have two cells on the
+multinomial configurations, against tests/_multinomial_ws.py.
+
 Every run takes ITERS = 12 iterations with L of the reference passed to both sides: lambda_max(A^T A) from the oracle's power
 iteration (of A^T W A with row weights), a quarter of it for the logistic and half for the multinomial loss.
 
@@ -35,7 +41,8 @@ import numpy as np
 
 from oracle import fos_oracle as orc
 from tests import (_coord as cd, _data, _duality as du, _fgroup as fg, _forms, _group as gp, _link as lk, _logit as lg, _menu_cv as mcv,
-                   _menu_multi as mm, _multinomial as mn, _weighted as wt, _working_set as ws)
+                   _menu_multi as mm, _multinomial as mn, _multinomial_ws as mws, _power as pw, _resample as rsp, _weighted as wt,
+                   _working_set as ws)
 from tests._menu_product1 import CSRC, FISTA, PLAN, _body, _text
 
 ITERS = 12
@@ -1004,8 +1011,410 @@ class CertifiedPath(Cell):
         assert (np.abs(out["cert"][2] - ref["gap"]) <= du.TOL * ref["mag_gap"]).all(), (out["cert"][2], ref["gap"])
 
 
+# ---- the resampled lockstep (include/fos_resample.h) -----------------------------------------------------------------------------
+# A resampled call binds nothing: the multiplicities travel with the call, so these cells use the configurations above and no new
+# move.  Column j fits the problem with the row weights w * c_j; the references are the weighted references tests/_resample.py
+# picks.  The counts are tests/_resample.counts at the shape's row count; L per resample is the oracle's power iteration on w * c_j.
+def _divisor(cfg):
+    return 4.0 if cfg.loss == "logistic" else 1.0
+
+
+@functools.lru_cache(maxsize=None)
+def _resampled_L(name, kind, cus, weighted, recipe, resamples):
+    """lambda_max(A^T diag(w * c_r) A) per resample of rsp.counts(recipe, m, resamples, SEED), before the logistic quarter."""
+    d = data(name, kind, cus)
+    C = rsp.counts(recipe, d["m"], resamples, SEED)
+    v0 = np.random.default_rng(SEED + 1).standard_normal(d["n"])
+    return np.array([rsp.lipschitz(d["A"], rsp.effective(d["w"] if weighted else None, C[:, r]), v0) for r in range(resamples)])
+
+
+def resampled_fit(d, cfg, weff, a1, a2, L, bounded=True):
+    """The fp64 reference of one column of a resampled run: the configuration's fit with the row weights weff = w * c_j and the
+    constant L of ITS data term, as a dict with x (and closest under feature groups).  bounded=False: the factors without the bound."""
+    A, t, _, p, lo = parts(d, cfg)
+    lo = lo if bounded else None
+    if cfg.groups:
+        return fg.run(A, t, a1, a2, L, ITERS, start=d["start"], gw=d["gw"], mu=MU, loss=cfg.loss, w=weff)
+    if cfg.loss in (lk.HUBER, lk.HINGE):
+        c = d["threshold"] if cfg.loss == lk.HUBER else None
+        prob = lk.CoordLinkProblem(cfg.loss, A, t, a1, a2, c, weff).bind(p, lo, None) if cfg.coord else None
+        return dict(x=rsp.run(cfg.loss, A, t, weff, a1, a2, L, ITERS, c=c, prob=prob)[0])
+    if cfg.coord:
+        return cd.run(A, t, a1, a2, L, ITERS, p=p, lo=lo, loss=cfg.loss, w=weff)
+    return dict(x=rsp.run(cfg.loss, A, t, weff, a1, a2, L, ITERS)[0])
+
+
+class ResampledPath(Cell):
+    """resampled_path on `resamples` resamples x `weights` weights (count lockstep columns, resample-major), with return of the
+    info and, with oob, the out-of-bag sums from one more pass (fos_gradient_batch_resampled, oob = 1)."""
+    reaches = ("fos_fista_run_multi_resampled",)
+
+    def __init__(self, name, cfg, recipe, resamples, weights, oob=False):
+        super().__init__(name, cfg)
+        self.recipe, self.resamples, self.nweights, self.oob = recipe, resamples, weights, oob
+        self.count = resamples * weights
+        assert self.count <= 16
+        if oob:
+            self.reaches = self.reaches + ("fos_gradient_batch_resampled",)
+            self.sized_by_panels = True
+
+    def counts(self, d):
+        return rsp.counts(self.recipe, d["m"], self.resamples, SEED)
+
+    def Ls(self, d):
+        return _resampled_L(d["name"], d["kind"], d["cus"], self.cfg.weights, self.recipe, self.resamples)
+
+    def weights(self, d):
+        """The configuration's weights: fractions of alpha_max of all rows.  A 0/1 resample keeps half of the rows and with them
+        about half of the gradient at 0, so its weights are halved - at the first weight of the ladder (half of alpha_max) the fit
+        of a half would otherwise still be 0."""
+        scale = 0.5 if self.recipe == "binary" else 1.0
+        return [(scale * a1, a2) for a1, a2 in alphas(d, self.cfg, self.nweights)]
+
+    def call(self, c, P):
+        res = c.fos.resampled_path(P, self.weights(c.d), self.counts(c.d), ITERS, L=self.Ls(c.d), oob=self.oob)
+        out = dict(x=res.coefs, info=np.array(res.info))
+        return dict(out, oob=res.oob_loss, size=res.oob_size) if self.oob else out
+
+    def reference(self, d):
+        C, Ls, w = self.counts(d), self.Ls(d), (d["w"] if self.cfg.weights else None)
+        refs = [[resampled_fit(d, self.cfg, rsp.effective(w, C[:, r]), a1, a2, Ls[r] / _divisor(self.cfg)) for a1, a2 in self.weights(d)]
+                for r in range(self.resamples)]
+        out = dict(x=np.stack([np.stack([f["x"] for f in row]) for row in refs]))           # resamples x weights x n
+        if self.cfg.groups:                                   # no group norm so close to its threshold that fp32 may decide otherwise
+            out["closest"] = np.array([[f["closest"] for f in row] for row in refs])
+            assert out["closest"].min() >= fg.CLOSE, out["closest"]
+        return out
+
+    def precondition(self, d, ref):
+        C, X = self.counts(d), ref["x"]
+        flat = X.reshape(-1, d["n"])
+        assert all((x != 0).any() for x in flat) and any((x == 0).any() for x in flat), "the penalty must bite"
+        assert (C == 0).any(axis=0).all() and C.max() == (rsp.MAX_COUNT if self.recipe == "bootstrap" else 1)
+        if self.cfg.weights:                                  # an exact-zero weight under a positive count, and a positive one under 0
+            assert ((d["w"] == 0)[:, None] & (C > 0)).any() and ((d["w"] > 0)[:, None] & (C == 0)).any()
+        if self.cfg.coord == "bounds":                        # the lower bound binds and an unpenalised coordinate is in the model
+            w = d["w"] if self.cfg.weights else None
+            free = [resampled_fit(d, self.cfg, rsp.effective(w, C[:, r]), *self.weights(d)[-1], self.Ls(d)[r] / _divisor(self.cfg), bounded=False)
+                    for r in range(self.resamples)]
+            assert any((f["x"] < 0).any() for f in free) and (X >= 0).all() and (X[..., d["p"] == 0] != 0).any()
+        if self.cfg.groups:
+            zero = [fg.zero_groups(x, d["start"])[0] for x in flat]
+            assert all(z.any() and (~z).any() for z in zero)
+
+    def check(self, d, out):
+        ref = self.ref(d)
+        X = np.asarray(_host(out["x"]), dtype=np.float64)
+        assert X.shape == (d["n"], self.resamples, self.nweights)
+        for r in range(self.resamples):
+            for a in range(self.nweights):
+                _rel_ok(X[:, r, a], ref["x"][r, a], (self.name, r, a))
+        assert out["info"].shape == (self.resamples, self.nweights, 2) and (out["info"] == [ITERS, 0]).all(), out["info"]
+        if self.oob:                                          # the sums against fp64 on the device's own fits, as stored in fp32
+            A, t, w, _, _ = parts(d, self.cfg)
+            left = self.counts(d) == 0
+            size = left.sum(axis=0).astype(np.float64) if w is None else (w[:, None] * left).sum(axis=0)
+            assert np.allclose(out["size"], size, rtol=1e-12, atol=0) and (size > 0).all()
+            c = d["threshold"] if self.cfg.loss == lk.HUBER else None
+            for r in range(self.resamples):
+                X32 = X[:, r, :].astype(np.float32).astype(np.float64)
+                Wo = np.repeat((left[:, r] * (1.0 if w is None else w))[:, None], self.nweights, axis=1)
+                want, tol = rsp.data_term(self.cfg.loss, A, X32, t, Wo, c), rsp.loss_tolerance(self.cfg.loss, A, X32, t, Wo, c)
+                assert (np.abs(out["oob"][r] - want) <= tol).all(), (self.name, r, out["oob"][r], want, tol)
+
+
+class ResampledGradient(Cell):
+    """fos_gradient_batch_resampled through the C ABI at the 16 columns of a seeded block with one zero column, bootstrap counts:
+    G and loss16 in-bag, then loss16 out-of-bag with G = NULL (product 2 does not run).  With several panels the partial sums of
+    every panel are copied behind each other into ws.grad_part before the fold."""
+    reaches = ("fos_gradient_batch_resampled",)
+    sized_by_panels = True
+    ZERO = 3
+
+    def counts(self, d):
+        return rsp.counts("bootstrap", d["m"], 16, SEED)
+
+    def points(self, d):
+        """The seeded block times 4 (exact in fp32): at the block's own scale every margin 1 - y a.x of most columns is positive and
+        the hinge has one branch; at this one at least a twentieth of the rows is on either (precondition: the Huber cells' rule)."""
+        X = 4.0 * block(d, 16, 16)
+        X[:, self.ZERO] = 0.0
+        return X
+
+    def call(self, c, P):
+        from fastoptsolver_amd import _core, _lib, resample
+        words = resample.pack_counts(c.torch.from_numpy(np.ascontiguousarray(self.counts(c.d))).to(P.device))
+        Xf, nv = P._block16(c.torch.as_tensor(self.points(c.d)))
+        G = c.torch.full((nv, P.n_dev), float("nan"), dtype=c.torch.float32, device=P.device)
+        sums = []
+        for oob in (0, 1):
+            with P.ctx():
+                _lib.check(P.lib.fos_gradient_batch_resampled(_core.ptr(Xf), nv, _core.ptr(words), oob, P.h, None if oob else _core.ptr(G),
+                                                              _core.ptr(P.scratch)), "fos_gradient_batch_resampled")
+            sums.append(P.scratch[:16].clone())
+        return dict(G=G, inbag=sums[0], oob=sums[1])
+
+    def _case(self, d):
+        A, t, w, _, _ = parts(d, self.cfg)
+        C = self.counts(d)
+        return A, t, (d["threshold"] if self.cfg.loss == lk.HUBER else None), rsp.effective(None, C) * (1.0 if w is None else w[:, None]), \
+            (C == 0) * (1.0 if w is None else w[:, None])
+
+    def reference(self, d):
+        A, t, c, W, Wo = self._case(d)
+        X = self.points(d)
+        G = rsp.gradient(self.cfg.loss, A, X, t, W, c)
+        # a gradient column is off by no more than the column's bound in the 2-norm, as in KktExcess and DualityGap (the pass on
+        # sqrt(w c_j) A: tests/_resample.gradient_tolerance is that bound with every column's own weights)
+        return dict(G=G, g_tol=rsp.gradient_tolerance(A, X, t, W, G),
+                    inbag=rsp.data_term(self.cfg.loss, A, X, t, W, c), inbag_tol=rsp.loss_tolerance(self.cfg.loss, A, X, t, W, c),
+                    oob=rsp.data_term(self.cfg.loss, A, X, t, Wo, c), oob_tol=rsp.loss_tolerance(self.cfg.loss, A, X, t, Wo, c))
+
+    def precondition(self, d, ref):
+        C = self.counts(d)
+        assert C.max() == rsp.MAX_COUNT and (C == 0).any(axis=0).all() and (self.points(d)[:, self.ZERO] == 0).all()
+        assert (np.linalg.norm(ref["G"], axis=0) > 100.0 * ref["g_tol"]).all()              # no gradient of rounding noise
+        assert (ref["inbag"] > 100.0 * ref["inbag_tol"]).all() and (ref["oob"] > 100.0 * ref["oob_tol"]).all()
+        if self.cfg.loss == lk.HINGE:                         # both branches of the hinge at every non-zero column of the block
+            A, t, _, _, _ = self._case(d)
+            shares = [lk.active_share(A, x, t) for j, x in enumerate(self.points(d).T) if j != self.ZERO]
+            assert all(0.05 <= s <= 0.95 for s in shares), shares
+
+    def check(self, d, out):
+        ref, n = self.ref(d), d["n"]
+        G, inbag, oob = (np.asarray(out[k]) for k in ("G", "inbag", "oob"))
+        assert G.shape[0] == 16 and G.dtype == np.float32 and np.isfinite(G).all() and (G[:, n:] == 0).all()      # nv = 16: no entry >= nv
+        err = np.linalg.norm(G[:, :n].T.astype(np.float64) - ref["G"], axis=0)
+        assert (err <= ref["g_tol"]).all(), (self.name, (err / ref["g_tol"]).max())
+        for got, key in ((inbag, "inbag"), (oob, "oob")):
+            assert got.shape == (16,) and (np.abs(got - ref[key]) <= ref[key + "_tol"]).all(), (self.name, key, got, ref[key], ref[key + "_tol"])
+
+
+class ResampledLipschitz(Cell):
+    """resampled_lipschitz on 18 resamples - a group of 16 bootstrap columns and one of two 0/1 columns -: one
+    fos_gram_apply_resampled per step and group of the power iteration on A^T diag(w * c_r) A.  The front end draws its start
+    vectors from the global legacy stream, which the cell seeds itself: a fresh handle and a shared one draw the same."""
+    reaches = ("fos_gram_apply_resampled",)
+    STEPS = 30
+
+    def counts(self, d):
+        return np.concatenate([rsp.counts("bootstrap", d["m"], 16, SEED), rsp.counts("binary", d["m"], 2, SEED)], axis=1)
+
+    def call(self, c, P):
+        state = np.random.get_state()
+        np.random.seed(SEED)
+        try:
+            return dict(L=c.fos.resampled_lipschitz(P, self.counts(c.d), n_iter=self.STEPS, tol=0.0))
+        finally:
+            np.random.set_state(state)
+
+    def reference(self, d):
+        C, rs = self.counts(d), np.random.RandomState(SEED)
+        v0 = [rs.randn(d["n"]) for _ in range(18)]
+        return dict(L=np.array([wt.estimate_lipschitz(d["A"], rsp.effective(d["w"] if self.cfg.weights else None, C[:, r]), v0[r],
+                                                       n_iter=self.STEPS, tol=0.0) for r in range(18)]))
+
+    def precondition(self, d, ref):
+        assert self.cfg.weights and ref["L"].shape == (18,) and ref["L"][:16].max() > ref["L"][16:].max() > 0      # a row drawn 15 times weighs 15 times
+
+    def check(self, d, out):
+        ref = self.ref(d)["L"]
+        assert out["L"].shape == (18,) and out["L"].dtype == np.float64 and np.allclose(out["L"], ref, rtol=pw.TOL, atol=0), (out["L"], ref)
+
+
+class ResampledControlled(Cell):
+    """resampled_path with adaptive restart and the ratio stop per column, built like tests/_resample.controlled_case: RESAMPLES
+    0/1 resamples under a ladder of WEIGHTS weights with L of the whole A (valid for 0/1 counts), ITERATIONS iterations at the most.
+    Every (resample, weight) pair runs; those whose every decision in the fp64 reference tests/_coord.fp32_proof accepts - the
+    rule of the Controlled cell - are compared: their stop iteration, stop code and iterate."""
+    reaches = ("fos_fista_run_multi_resampled",)
+    RESAMPLES, WEIGHTS, ITERATIONS = 2, 8, 36
+    MENU = Controlled.MENU + rsp.CONTROL_MENU
+
+    def __init__(self, name):
+        super().__init__(name, PLAIN)
+
+    def counts(self, d):
+        return rsp.counts("binary", d["m"], self.RESAMPLES, SEED)
+
+    def weights(self, d):
+        return ladder(float(np.abs(gradient0(d, PLAIN)).max()), self.WEIGHTS, 0.3, 0.01)
+
+    def chosen(self, d):
+        return _resampled_controlled(d["name"], d["kind"], d["cus"])
+
+    def call(self, c, P):
+        ctl = self.chosen(c.d)[0]
+        res = c.fos.resampled_path(P, self.weights(c.d), self.counts(c.d), self.ITERATIONS, L=c.d["L"], **ctl)
+        return dict(x=res.coefs, info=np.array(res.info))
+
+    def runs(self, d, ctl):
+        C = self.counts(d)
+        return {(r, a): cd.run(d["A"], d["b"], a1, a2, d["L"], self.ITERATIONS, w=C[:, r].astype(np.float64), **ctl)
+                for r in range(self.RESAMPLES) for a, (a1, a2) in enumerate(self.weights(d))}
+
+    def reference(self, d):
+        ctl, kept = self.chosen(d)
+        pairs = sorted(kept)
+        return dict(pairs=np.array(pairs), x=np.stack([kept[p]["x"] for p in pairs]), info=np.array([(kept[p]["k"], kept[p]["stopped"]) for p in pairs]),
+                    restarts=np.array([cd.genuine_restarts(kept[p], ctl["restart_threshold"]) for p in pairs]))
+
+    def precondition(self, d, ref):
+        k, stopped = ref["info"][:, 0], ref["info"][:, 1]
+        assert 2 * len(ref["pairs"]) >= self.RESAMPLES * self.WEIGHTS, len(ref["pairs"])       # at least half of the pairs remain
+        assert ((stopped == cd.STOP_RATIO) & (k < self.ITERATIONS)).any() and (k == self.ITERATIONS).any() and ref["restarts"].sum() >= 1
+
+    def check(self, d, out):
+        ref = self.ref(d)
+        X = np.asarray(_host(out["x"]), dtype=np.float64)
+        assert X.shape == (d["n"], self.RESAMPLES, self.WEIGHTS) and out["info"].shape == (self.RESAMPLES, self.WEIGHTS, 2)
+        for (r, a), x, info in zip(ref["pairs"], ref["x"], ref["info"]):
+            assert tuple(out["info"][r, a]) == tuple(info), (self.name, r, a, out["info"][r, a], info)
+            _rel_ok(X[:, r, a], x, (self.name, r, a))
+
+
+@functools.lru_cache(maxsize=None)
+def _resampled_controlled(name, kind, cus):
+    """(control parameters, {(resample, weight): the reference run} of the fp32-proof pairs) under the first entry of
+    ResampledControlled.MENU with which at least half of the pairs are fp32-proof and one of them stops early, one runs to the end
+    and one restarts on a finite ratio; where no entry gives all three (the panels shape is so well conditioned that every pair
+    stops at once) under the first that keeps half.  Decided on the reference alone."""
+    d, cell = data(name, kind, cus), ALL_CELLS["resampled_controlled"]
+    found = []
+    for ctl in cell.MENU:
+        kept = {p: r for p, r in cell.runs(d, ctl).items() if cd.fp32_proof(r, ctl["restart_threshold"], ctl["tol_ratio"])}
+        if 2 * len(kept) >= cell.RESAMPLES * cell.WEIGHTS:
+            found.append((ctl, kept))
+            refs = list(kept.values())
+            if any(r["k"] < cell.ITERATIONS and r["stopped"] == cd.STOP_RATIO for r in refs) and any(r["k"] == cell.ITERATIONS for r in refs) \
+                    and sum(cd.genuine_restarts(r, ctl["restart_threshold"]) for r in refs) >= 1:
+                return ctl, kept
+    assert found, "no entry of ResampledControlled.MENU keeps half of the pairs"
+    return found[0]
+
+
+# ---- the working set and the duality gap of the multinomial lockstep (include/fos_multinomial_ws.h) ----------------------------------
+class MultinomialGap(Cell):
+    """multinomial_duality_gap's device call (fos_multinomial_duality_gap: the certificate of `count` fits of a seeded block, one of
+    them zero, with the gradient block of the same pass) and multinomial_kkt_excess (one fos_multinomial_gradient_batch and one
+    fos_multinomial_kkt_scan with an empty set), against tests/_multinomial_ws.certificate and .scan."""
+    reaches = ("fos_multinomial_gradient_batch", "fos_multinomial_kkt_scan", "fos_multinomial_duality_gap")
+    sized_by_panels = True
+    ZERO = 0
+
+    def __init__(self, name, cfg, count):
+        super().__init__(name, cfg)
+        self.count = count
+        assert count * cfg.classes <= 16
+
+    def fits(self, d):
+        C = self.cfg.classes
+        X = block(d, C * self.count, C * self.count + 1)
+        fits = [X[:, s * C:(s + 1) * C].copy() for s in range(self.count)]
+        fits[self.ZERO][:] = 0.0
+        return fits
+
+    def call(self, c, P):
+        weights = alphas(c.d, self.cfg, self.count)
+        fits = self.fits(c.d)
+        out64, G = P.multinomial_duality_gap_block(c.torch.as_tensor(mws.block(fits).astype(np.float32)).cuda(),
+                                                   [a for a, _ in weights], [a for _, a in weights])
+        return dict(out=out64.reshape(4, 16), G=G, excess=c.fos.multinomial_kkt_excess(P, fits, weights))
+
+    def reference(self, d):
+        A, y, w, p, _ = parts(d, self.cfg)
+        C, fits, weights = self.cfg.classes, self.fits(d), alphas(d, self.cfg, self.count)
+        ref = mws.certificate(A, y, C, fits, weights, self.cfg.grouped, w, p)
+        G = mws.gradient_block(A, y, C, fits, w)                                       # (count C) x n
+        # sigma - onehot(y) moves by at most half the largest error of the fit's C logits: a class column of the gradient is off by
+        # no more than the largest bound of fos_gradient_batch among the fit's columns (|t| <= 1 in b's place), as in KktExcess
+        col_tol, _ = _data.fp32_pass_tolerances_cols(A, mws.block(fits), np.ones(d["m"]), G.T, np.ones(C * self.count))
+        g_tol = np.repeat(col_tol.reshape(self.count, C).max(axis=1), C)
+        excess = np.zeros(d["n"])
+        for s, (a1, _) in enumerate(weights):
+            e, _, _ = mws.scan(G[s * C:(s + 1) * C].astype(np.float32), C, self.cfg.grouped, [a1], 0.0, np.zeros(d["n"]), p)
+            excess = np.maximum(excess, e.astype(np.float64))
+        a1s = np.repeat([a for a, _ in weights], C)
+        return dict(ref, G=G, g_tol=g_tol, excess=excess,
+                    excess_tol=(np.sqrt(C) if self.cfg.grouped else 1.0) * float((g_tol / a1s).max()) + 2.0 * float(np.finfo(np.float32).eps) * excess)
+
+    def precondition(self, d, ref):
+        s, live = ref["scale"], np.arange(self.count) != self.ZERO
+        assert ((s > 0) & (s < 1)).any() and (s == 1).any(), s
+        assert (ref["gap"][live] > 100.0 * mws.TOL * ref["mag_gap"][live]).all(), ref["gap"] / ref["mag_gap"]
+        assert all(np.isfinite(ref[k]).all() for k in ("primal", "dual", "gap", "scale", "excess")) and (ref["excess"] > 0).all()
+
+    def check(self, d, out):
+        A, y, w, p, _ = parts(d, self.cfg)
+        C, n, nv, ref = self.cfg.classes, d["n"], self.cfg.classes * self.count, self.ref(d)
+        got, G = np.asarray(out["out"], dtype=np.float64), np.asarray(out["G"])
+        used = np.arange(self.count) * C
+        off = np.setdiff1d(np.arange(16), used)
+        assert got.shape == (4, 16) and np.isfinite(got).all() and (got[:, off] == 0).all() and G.shape[0] == nv and (G[:, n:] == 0).all()
+        err = np.linalg.norm(G[:, :n].T.astype(np.float64) - ref["G"].T, axis=0)
+        assert (err <= ref["g_tol"]).all(), (self.name, (err / ref["g_tol"]).max())
+        weights = alphas(d, self.cfg, self.count)
+        on = mws.certificate(A, y, C, self.fits(d), weights, self.cfg.grouped, w, p, G=G[:, :n])      # scale and conjugate from the returned G
+        for row, key in enumerate(("primal", "dual", "gap")):
+            assert (np.abs(got[row, used] - on[key]) <= mws.TOL * on["mag_" + key]).all(), \
+                (self.name, key, (np.abs(got[row, used] - on[key]) / on["mag_" + key]).max())
+        assert np.abs(got[3, used] - on["scale"]).max() <= 1e-12 and np.array_equal(got[2, used], got[0, used] - got[1, used])
+        ex = np.asarray(_host(out["excess"]), dtype=np.float64)
+        assert ex.shape == (n,) and (np.abs(ex - ref["excess"]) <= ref["excess_tol"]).all(), (self.name, np.abs(ex - ref["excess"]).max())
+
+
+class MultinomialWorkingSet(Cell):
+    """multinomial_working_set_path on the handle, one group of floor(16 / C) weights: the scans read
+    fos_multinomial_gradient_batch and fos_multinomial_kkt_scan on the full problem, fos_gather_columns copies the set's columns,
+    the rounds run on handles of their own.  The reference is tests/_multinomial_ws.solve with the same L; as in WorkingSet it must
+    grow its set and end certified, every scan decision further than MARGIN (relative) from its threshold and every growth step
+    further than GAP.  The first set is every fifth coordinate (`initial`, no scan at X = 0) and the violators of round 1 join in
+    round 2: from the scan at 0 no ladder between 0.9 and 0.1 of alpha_max grows a set on this data within ITERS iterations a round
+    short of taking all 37 columns (tried on the reference alone: 0.9 .. 0.5, 0.7 .. 0.3, 0.6 .. 0.2, 0.5 .. 0.15 certify their
+    first set, 0.4 .. 0.1 ends with every column); with the first set given, the first ladder tried doubles it and certifies."""
+    reaches = ("fos_multinomial_gradient_batch", "fos_multinomial_kkt_scan", "fos_gather_columns")
+    sized_by_panels = True
+    KKT_TOL, FRACTIONS, EVERY = WorkingSet.KKT_TOL, (0.9, 0.5), 5
+
+    def initial(self, d):
+        return np.arange(0, d["n"], self.EVERY)
+
+    def weights(self, d):
+        A, y, w, p, _ = parts(d, self.cfg)
+        amax = mws.alpha_max(A, y, self.cfg.classes, self.cfg.grouped, w, p)
+        return [(amax * f, 0.0) for f in np.geomspace(*self.FRACTIONS, 16 // self.cfg.classes)]
+
+    def call(self, c, P):
+        xs, infos = c.fos.multinomial_working_set_path(P, None, self.weights(c.d), max_iter=ITERS, L=L_of(c.d, self.cfg), kkt_tol=self.KKT_TOL,
+                                                       max_fraction=1.0, initial=self.initial(c.d).tolist(), return_info=True)
+        assert len(infos) == 1
+        i = infos[0]
+        return dict(x=c.torch.stack([c.torch.as_tensor(x) for x in xs]), rounds=np.int64(i.rounds), sizes=np.array(i.sizes),
+                    grads=np.int64(i.full_gradients), fell_back=np.bool_(i.fell_back), worst=np.float64(i.worst_excess))
+
+    def reference(self, d):
+        A, y, w, _, _ = parts(d, self.cfg)
+        fits, info = mws.solve(A, y, self.cfg.classes, self.weights(d), self.cfg.grouped, ITERS, L_of(d, self.cfg), w=w, kkt_tol=self.KKT_TOL,
+                               max_fraction=1.0, initial=self.initial(d))
+        assert info["scan_margins"].min() >= WorkingSet.MARGIN and min(list(info["growth_gaps"]) + [np.inf]) >= WorkingSet.GAP and \
+            not info["fell_back"], info
+        return dict(x=np.stack(fits), rounds=np.int64(info["rounds"]), sizes=np.array(info["sizes"]), grads=np.int64(info["full_gradients"]),
+                    worst=np.float64(info["worst_excess"]), margin=np.float64(info["scan_margins"].min()))
+
+    def precondition(self, d, ref):
+        assert ref["rounds"] >= 2 and ref["sizes"][-1] > ref["sizes"][0], ref["sizes"]                      # grown
+        assert ref["worst"] <= 1.0 + self.KKT_TOL and ref["sizes"][-1] < d["n"], (ref["worst"], ref["sizes"])     # and certified
+
+    def check(self, d, out):
+        ref = self.ref(d)
+        assert (int(out["rounds"]), list(out["sizes"]), int(out["grads"]), bool(out["fell_back"])) == \
+            (int(ref["rounds"]), list(ref["sizes"]), int(ref["grads"]), False), (out, ref)
+        for i in range(len(ref["x"])):
+            _rel_ok(out["x"][i], ref["x"][i], (self.name, i))
+
+
 W, COORD, GROUPS = PLAIN._replace(weights=True), PLAIN._replace(coord="bounds"), PLAIN._replace(groups=True)
-FACTORS = PLAIN._replace(coord="factors")
+FACTORS =PLAIN._replace(coord="factors")
 LOGIT, HUBER, HINGE_W = PLAIN._replace(loss="logistic"), PLAIN._replace(loss="huber"), W._replace(loss="squared_hinge")
 M3, M7G = PLAIN._replace(loss="multinomial", classes=3), PLAIN._replace(loss="multinomial", classes=7, grouped=True)
 
@@ -1026,20 +1435,87 @@ CELLS = collections.OrderedDict((c.name, c) for c in (
     DualityGap("gap16", PLAIN, 16), DualityGap("gap3", PLAIN, 3), DualityGap("weights_gap5", W, 5), DualityGap("logistic_gap16", LOGIT, 16),
     DualityGap("huber_gap5", HUBER, 5), DualityGap("hinge_weights_gap5", HINGE_W, 5), DualityGap("positive_factors_gap16", FACTORS, 16),
     CertifiedPath("certified_path", PLAIN),
+    ResampledPath("resampled_path5", PLAIN, "bootstrap", 5, 1, oob=True),
+    ResampledPath("resampled_logistic_weights_path16", LOGIT._replace(weights=True), "binary", 4, 4),
+    ResampledPath("resampled_huber_bounds_path3", HUBER._replace(coord="bounds"), "bootstrap", 3, 1),
+    ResampledPath("resampled_groups_path3", GROUPS, "bootstrap", 3, 1),
+    ResampledGradient("resampled_gradient16", HINGE_W), ResampledLipschitz("resampled_lipschitz", W),
+    ResampledControlled("resampled_controlled"),
+    MultinomialGap("multinomial3_gap5", M3, 5), MultinomialWorkingSet("multinomial7_grouped_working_set", M7G),
 ))
 LOCKSTEP_ENTRY_POINTS = ("fos_fista_run_multi", "fos_fista_run_multi_rhs", "fos_fista_run_multi_folds", "fos_residual_batch",
                          "fos_residual_batch_rhs", "fos_residual_batch_folds", "fos_gradient_batch", "fos_gather_columns",
-                         "fos_kkt_scan", "fos_power_iter", "fos_duality_gap")
+                         "fos_kkt_scan", "fos_power_iter", "fos_duality_gap",
+                         "fos_fista_run_multi_resampled", "fos_gradient_batch_resampled", "fos_gram_apply_resampled",
+                         "fos_multinomial_gradient_batch", "fos_multinomial_kkt_scan", "fos_multinomial_duality_gap")
+# Every other `int fos_*(` of include/*.h that takes no part in the table, and why: an entry point a new header declares is a lockstep
+# entry point with a cell, a binding entry point (binding_entry_points: a step of a move or a row of NOT_A_MOVE) or a row here -
+# tests/test_handle_pairs.py fails until it is one of the three.
+_EXCUSED = (
+    ("no handle is involved: the version, the communicator, the proximal maps and the vector helpers of the L-BFGS loop",
+     "fos_abi_version fos_comm_unique_id fos_comm_create fos_comm_mesh_create fos_comm_mesh_connect fos_comm_check fos_comm_destroy "
+     "fos_comm_info fos_comm_mesh_info fos_comm_allreduce fos_prox_l1 fos_prox_l1_vec fos_prox_elastic_net fos_prox_elastic_net_vec "
+     "fos_lbfgs_two_loop fos_lbfgs_two_loop_dd fos_lbfgs_direction_cols fos_lbfgs_direction_dd fos_vec_stats fos_vec_axpby "
+     "fos_vec_stats_f64 fos_vec_axpby_f64 fos_vec_stats_dd fos_vec_axpby_dd fos_stream_read_probe"),
+    ("creation and destruction: Ctx.fresh and the front ends make and drop every handle and state machine of the table",
+     "fos_problem_create fos_problem_destroy fos_fista_create fos_fista_destroy"),
+    ("a getter: Ctx.check_getters reads it after every move, and the plan before and after a refusal",
+     "fos_problem_get_loss fos_problem_get_link_loss fos_problem_get_classes fos_row_weights_get fos_coord_get fos_feature_groups_get "
+     "fos_problem_plan fos_fista_status_get fos_fista_get_x"),
+    ("tuning and profiling of a handle's plan: no run form", "fos_problem_tune fos_problem_tune_dd fos_problem_profile "
+     "fos_problem_profile_read"),
+    ("a state machine's own parameters, set by the front ends before every run of a cell", "fos_fista_reset fos_fista_set_tau fos_fista_set_precise "
+     "fos_fista_set_gbuf64"),
+    ("a single-vector run form or step: the Single cell runs fos_fista_run beside the lockstep cells, tests/test_gpu_fista_forms.py and "
+     "tests/test_gpu_armijo.py cover the forms pair by pair",
+     "fos_fista_run fos_fista_run_resident fos_fista_run_history fos_fista_run_fused fos_fista_run_chip fos_fista_grad fos_fista_grad_dual "
+     "fos_fista_update fos_fista_trial fos_fista_trial_batch fos_fista_run_backtracking fos_fista_run_recorded fos_fista_resume_after_stall "
+     "fos_gemv_pair fos_gemv_pair_f64 fos_gemv_pair_dd fos_residual_objective"),
+    ("the L-BFGS optimiser: the Lbfgs cell serves fos_lbfgs_minimize_multi (it may decline: Cell.serves), tests/test_gpu_lbfgs_driver.py and "
+     "tests/test_gpu_lbfgs_multi.py cover the rest", "fos_lbfgs_minimize fos_lbfgs_minimize_multi fos_gemv_pair_dd_multi"),
+    ("the Gram operator of the weighted power iteration: the weights_lipschitz cell calls it at every step (estimate_lipschitz), "
+     "tests/test_gpu_weighted.py and tests/test_gpu_cluster_planned.py compare it with fp64", "fos_gram_apply"),
+    ("batches of small independent problems on handles of their own: tests/test_gpu_batch.py", "fos_fista_run_batch fos_power_iter_batch"),
+)
+NOT_LOCKSTEP = {name: reason for reason, names in _EXCUSED for name in names.split()}
+
+
+def declared_entry_points(include=INCLUDE):
+    """Every `int fos_*(` that include/*.h declares, by name."""
+    names = set()
+    for path in sorted(glob.glob(os.path.join(include, "*.h"))):
+        with open(path) as fh:
+            names |= set(re.findall(r"\bint\s+(fos_\w+)\s*\(", fh.read()))
+    return names
+
+
+def check_entry_points(include=INCLUDE, cells=None):
+    """Every entry point the headers declare is a lockstep entry point that a cell reaches, a binding entry point or a row of
+    NOT_LOCKSTEP - exactly one of the three -, and every name of the two lists is declared: a new header fails here until its
+    entry points have cells (or a stated reason), and a cell that drops an entry point from its reaches fails too."""
+    cells = CELLS if cells is None else cells
+    reached = {e for c in cells.values() for e in c.reaches}
+    assert reached == set(LOCKSTEP_ENTRY_POINTS), sorted(set(LOCKSTEP_ENTRY_POINTS) ^ reached)
+    declared, binding = declared_entry_points(include), binding_entry_points(include)
+    assert reached <= declared, sorted(reached - declared)
+    assert set(NOT_LOCKSTEP) <= declared, sorted(set(NOT_LOCKSTEP) - declared)
+    assert all(reason.strip() for reason in NOT_LOCKSTEP.values())
+    for a, b in ((reached, binding), (reached, set(NOT_LOCKSTEP)), (binding, set(NOT_LOCKSTEP))):
+        assert a.isdisjoint(b), sorted(a & b)
+    left = declared - reached - binding - set(NOT_LOCKSTEP)
+    assert not left, f"declared in include/*.h, reached by no cell and not excused: {sorted(left)}"
 MAY_DECLINE = {"fos_fista_run_multi", "fos_fista_run_multi_rhs", "fos_fista_run_multi_folds", "fos_residual_batch_rhs",
                "fos_residual_batch_folds", "fos_lbfgs_minimize_multi"}
 PAIRS = [(x, y) for x in CELLS for y in CELLS if x != y]
 PANEL_PAIRS = [(x, y) for x, y in PAIRS if CELLS[x].sized_by_panels or CELLS[y].sized_by_panels]
 # the same call at another width on one handle: (wide, narrow) per configuration; C = 7 with two fits fills 14 columns, C = 3 with
 # five fits 15
-_NARROW = [Path("factors_path3", COORD, 3), Path("logistic_path3", LOGIT, 3), Path("multinomial7_path2", M7G._replace(grouped=False), 2)]
+_NARROW = [Path("factors_path3", COORD, 3), Path("logistic_path3", LOGIT, 3), Path("multinomial7_path2", M7G._replace(grouped=False), 2),
+           ResampledPath("resampled_path16", PLAIN, "bootstrap", 8, 2, oob=True)]          # (the wide twin of resampled_path5)
 ALL_CELLS = dict(CELLS, **{c.name: c for c in _NARROW})
 WIDTHS = {"plain": ("path16", "path3"), "factors": ("factors_path16", "factors_path3"), "logistic": ("logistic_path16", "logistic_path3"),
-          "multinomial": ("multinomial7_path2", "multinomial3_path5"), "gap": ("gap16", "gap3")}
+          "multinomial": ("multinomial7_path2", "multinomial3_path5"), "gap": ("gap16", "gap3"),
+          "resampled": ("resampled_path16", "resampled_path5")}
 
 
 @functools.lru_cache(maxsize=None)
@@ -1083,7 +1559,7 @@ def check_duality_guards(fista=FISTA):
         assert re.fullmatch(r"\s*" + cond + r"\s*", got), got
         assert message in body, message
     assert list(REFUSED) == ["factors_path16", "groups_path3", "logistic_weights_factors_cv", "multinomial3_path5",
-                             "multinomial7_grouped_path2", "multinomial7_path2"], list(REFUSED)
+                             "multinomial7_grouped_path2", "resampled_huber_bounds_path3", "multinomial7_path2"], list(REFUSED)
     assert {refusal(c.cfg) for c in REFUSED.values()} == {message for _, message, _ in DUALITY_GUARDS}
     for c in ALL_CELLS.values():
         if "fos_duality_gap" in c.reaches:

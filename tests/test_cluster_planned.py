@@ -115,6 +115,36 @@ def test_the_certificate_cells_meet_their_preconditions(name, cell):
     cp.certificate_case.cache_clear()
 
 
+@pytest.mark.parametrize("cell", ["resampled_path", "resampled_weighted_logistic_path", cp.RESAMPLE_PLAIN])
+@pytest.mark.parametrize("name", ["cs4", "cs8"])
+def test_the_resampled_fits_have_left_zero(name, cell):
+    """Every reference fit of a resampled path cell has zero and non-zero coefficients after ITERS iterations under the bound
+    max_i c_ij L: the GPU comparison is not one of vectors that never left 0, and the penalty bites."""
+    cs = cp.resample_case(name, cell)
+    C = cs["counts"]
+    assert C.shape == (cp.SHAPES[name][0], len(cs["L"])) and (cs["L"] >= cp.data(name)["L"]).all()
+    if cell == "resampled_path":
+        assert C.max() >= 3 and (C.sum(axis=0) == C.shape[0]).all()       # bootstrap columns: a step several times shorter
+    else:
+        assert set(np.unique(C)) == {0, 1}
+    for r in range(C.shape[1]):
+        for a in range(len(cs["alphas"])):
+            x = cp.resample_reference(name, cell, r, a)
+            assert (x == 0).any() and (x != 0).any(), (r, a, int((x != 0).sum()))
+    print(f"{name} {cell}: largest count per resample {C.max(axis=0).tolist()}")
+
+
+@pytest.mark.parametrize("name", ["cs4", "cs8"])
+def test_the_resampled_controlled_case_keeps_half_of_its_cells(name):
+    """The (resample, weight) cells of the controlled resampled run that the fp64 reference decides fp32-proof: at least half of
+    the 32, with an early stop, a full run and a genuine restart among them."""
+    C, weights, kept = cp.resample_control_case(name)
+    cp.check_resample_control(kept)
+    assert len(weights) == cp.CONTROL_WEIGHTS and set(np.unique(C)) == {0, 1}
+    print(f"{name}: {len(kept)} of 32 cells kept, iterations {[(ra, r['k']) for ra, r in sorted(kept.items())]}")
+    cp.resample_control_case.cache_clear()
+
+
 def test_recipe_helpers():
     assert cp.picks(1) == [0] and cp.picks(3) == [0, 1, 2] and cp.picks(16) == [0, 8, 15]
     ids = cp.fold_ids(50, 3, 1)

@@ -30,14 +30,35 @@ tests/test_gpu_handle_pairs.py lists: with the row weights also in product 1 the
 against fp64 (first cs4-weighted_logistic_gap) and the squared one passes; with dual_scale_kernel skipped all eight tests fail
 (first cs4-gap); without + row0 in launch_dual_link, and with nparts not advanced, nothing fails here, and nothing can - both
 shapes are a single row panel on 256 CUs, so row0 is 0 and there is one set of partial sums.  The two-panel cells of
-tests/test_gpu_handle_pairs.py catch those two."""
+tests/test_gpu_handle_pairs.py catch those two.
+
+The resampled calls (include/fos_resample.h) on cs4 and cs8: run_multi_mfma keeps them off the cluster pass by the one term
+`!counts` and works the row splits out in a line of its own; fos_gradient_batch_resampled and fos_gram_apply_resampled call
+two_product_splits themselves.  Part 1 has a squared path of 5 bootstrap columns, the weighted logistic path of 3 subsamples, the
+gradient batch (in-bag and out-of-bag) and the Gram operator on 16 columns; part 2 a "resampled" kind whose fits must also DIFFER
+from the plain path's under the same weights and step; part 3 a controlled resampled run.  L is max_i c_ij times the bound of the
+whole A, the same on both sides.  66 tests in 24 s on the MI355X at 256 CUs, no skip (54 in 17 s before; the slowest, the
+controlled resampled run on cs4, 2.6 s).  No defect was found.  Under the five temporary edits of the resampled host code that
+tests/test_gpu_handle_pairs.py lists, each run once:
+- use_cluster without `&& !counts`: 6 tests fail - cs4-resampled_path and cs8-resampled_path (first; the bitwise comparison of
+  the two layouts, the fits 1.9 apart, before the fp64 check is reached), the "resampled" kind of part 2 on both shapes (at
+  "the two layouts": the replanned handle against the cluster-planned one; its "differs from the plain path" condition stands
+  last in the test and was not reached - the cluster pass served the call with the row splits of the two-product form, so the
+  update summed 8 of the 64 slab sets and the fits were neither the resampled nor the plain ones) and the controlled run on both
+  shapes.  The weighted logistic cell passes, and must: row weights make the call a two-product one before `!counts` is asked.
+  The gradient and Gram cells pass, and must: they do not go through run_multi_mfma.  Before these cells nothing failed under
+  this edit: that was the gap;
+- counts or p->row_weight without + row0 in launch_resample_link, and nparts not advanced in gradient_walk: nothing fails here,
+  and nothing can - one row panel;
+- L.row_weight left set in the resampled branch of run_multi_mfma: the weighted logistic resampled cell fails on both shapes
+  against fp64 (relative error 0.44: the weight applied twice); both layouts agree bit for bit."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import fos_oracle as orc
 from tests import (_cluster_planned as cp, _coord as cd, _data, _duality as du, _fgroup as fg, _group as gp, _logit as lg,
-                   _menu_multi as mm, _multinomial as mn, _working_set as ws)
+                   _menu_multi as mm, _multinomial as mn, _resample as rsp, _working_set as ws)
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +81,8 @@ def _release_the_recipes():
     cp.bounds.cache_clear()
     cp.certificate_case.cache_clear()
     cp.certificate_gradient.cache_clear()
+    cp.resample_counts.cache_clear()
+    cp.resample_control_case.cache_clear()
 
 
 def _np(x):
@@ -440,6 +463,104 @@ class Certificate:
         assert (err <= g_tol).all(), (self.cell, (err / g_tol).max())
 
 
+def _words(P, counts):
+    from fastoptsolver_amd import resample
+    return resample.pack_counts(torch.from_numpy(np.ascontiguousarray(counts)).to(P.device))
+
+
+class ResampledPath:
+    """resampled_path (fos_fista_run_multi_resampled): every column fits a resample of the rows of its own, and the one term
+    `!counts` of run_multi_mfma keeps the call off the one-read cluster pass, which knows no counts."""
+    def __init__(self, cell):
+        self.cell = cell
+
+    def build(self, c):
+        cs = cp.resample_case(c.name, self.cell)
+        t32 = c.y32 if cs["loss"] == "logistic" else c.b32
+        if cs["weighted"]:
+            return c.fos.prepare_weighted(c.At, t32, c.w32, loss=cs["loss"])
+        return c.fos.prepare(c.At, t32, loss=cs["loss"])
+
+    def call(self, c, P, **control):
+        cs = cp.resample_case(c.name, self.cell)
+        res = c.fos.resampled_path(P, cs["alphas"], cs["counts"], ITERS, L=cs["L"], **control)
+        return [res.coefs, res.info]
+
+    def check(self, c, out, columns=None):
+        cs = cp.resample_case(c.name, self.cell)
+        B, La = cs["counts"].shape[1], len(cs["alphas"])
+        coefs = _np(out[0])
+        assert coefs.shape == (c.d["n"], B, La) and out[1] == [[(ITERS, 0)] * La] * B
+        pairs = [(r, a) for r in range(B) for a in range(La)]
+        for j in cp.picks(len(pairs)) if columns is None else columns:
+            r, a = pairs[j]
+            ref = cp.resample_reference(c.name, self.cell, r, a)
+            assert (ref == 0).any() and (ref != 0).any(), "the penalty must bite"
+            assert _data.rel(coefs[:, r, a], ref) < TOL, (self.cell, r, a, _data.rel(coefs[:, r, a], ref))
+
+
+class ResampledGradient:
+    """fos_gradient_batch_resampled through the C ABI on 16 bootstrap columns: G and the in-bag sums, then the out-of-bag sums with
+    G = NULL (product 2 does not run) - gradient_walk calls two_product_splits itself."""
+    cell = "resampled_gradient"
+
+    def build(self, c):
+        return c.fos.prepare(c.At, c.b32)
+
+    def call(self, c, P):
+        from fastoptsolver_amd import _core, _lib
+        words = _words(P, cp.resample_counts(c.name, *cp.RESAMPLE_CELLS[self.cell][2:]))
+        Xf, nv = P._block16(torch.as_tensor(cp.resample_block(c.d)))
+        G = torch.full((nv, P.n_dev), float("nan"), dtype=torch.float32, device=P.device)
+        out = [G]
+        for oob in (0, 1):
+            with P.ctx():
+                _lib.check(P.lib.fos_gradient_batch_resampled(_core.ptr(Xf), nv, _core.ptr(words), oob, P.h, None if oob else _core.ptr(G),
+                                                              _core.ptr(P.scratch)), "fos_gradient_batch_resampled")
+            out.append(P.scratch[:16].clone())
+        return out
+
+    def check(self, c, out):
+        d, n = c.d, c.d["n"]
+        G, inbag, oob = (o.cpu().numpy() for o in out)
+        assert G.shape[0] == 16 and np.isfinite(G).all() and (G[:, n:] == 0).all()
+        cols = cp.picks(16)
+        C = cp.resample_counts(c.name, *cp.RESAMPLE_CELLS[self.cell][2:])[:, cols]
+        X = cp.resample_block(d).astype(np.float64)[:, cols]
+        W = cp.resample_weights(d, self.cell, C)
+        G_ref = rsp.gradient(rsp.SQUARED, d["A"], X, d["b"], W)
+        err, g_tol = np.linalg.norm(G[cols, :n].T.astype(np.float64) - G_ref, axis=0), rsp.gradient_tolerance(d["A"], X, d["b"], W, G_ref)
+        assert (err <= g_tol).all() and (np.linalg.norm(G_ref, axis=0) > 100.0 * g_tol).all(), (err, g_tol)
+        for got, Wk in ((inbag, W), (oob, (C == 0).astype(np.float64))):
+            ref, tol = rsp.data_term(rsp.SQUARED, d["A"], X, d["b"], Wk), rsp.loss_tolerance(rsp.SQUARED, d["A"], X, d["b"], Wk)
+            assert (np.abs(got[cols] - ref) <= tol).all() and (ref > 100.0 * tol).all(), (got[cols], ref, tol)
+
+
+class ResampledGram:
+    """fos_gram_apply_resampled on the weighted handle, 16 subsamples: A^T ((w * c_j) * (A x_j)), the operator of the power iteration
+    per resample - it calls two_product_splits itself."""
+    cell = "resampled_gram"
+
+    def build(self, c):
+        return c.fos.prepare_weighted(c.At, c.b32, c.w32)
+
+    def call(self, c, P):
+        from fastoptsolver_amd import resample
+        words = _words(P, cp.resample_counts(c.name, *cp.RESAMPLE_CELLS[self.cell][2:]))
+        return [resample._gram_apply(P, torch.as_tensor(cp.resample_block(c.d)), words).clone()]
+
+    def check(self, c, out):
+        d, cols = c.d, cp.picks(16)
+        got = _np(out[0])
+        assert got.shape == (d["n"], 16) and np.isfinite(got).all() and (got[:, 1] == 0).all()         # the zero column of the block
+        C = cp.resample_counts(c.name, *cp.RESAMPLE_CELLS[self.cell][2:])[:, cols]
+        X = cp.resample_block(d).astype(np.float64)[:, cols]
+        W = cp.resample_weights(d, self.cell, C)
+        ref = d["A"].T @ (W * (d["A"] @ X))
+        err, g_tol = np.linalg.norm(got[:, cols] - ref, axis=0), rsp.gram_tolerance(d["A"], X, W, ref)
+        assert (err <= g_tol).all() and (np.linalg.norm(ref, axis=0) > 100.0 * g_tol).all(), (err, g_tol)
+
+
 CELLS = {
     "rhs": Rhs(), "multitask": Multitask(), "fista_cv": FistaCv(),
     "logistic_path": Path("logistic"), "logistic_cv": LogisticCv(),
@@ -450,6 +571,8 @@ CELLS = {
     "multinomial_c3": Multinomial(3, 5), "multinomial_c16": Multinomial(16, 2),
     "working_set": WorkingSet(), "batches": Batches(),
     "gap": Certificate("gap"), "weighted_logistic_gap": Certificate("weighted_logistic_gap"),
+    "resampled_path": ResampledPath("resampled_path"), "resampled_weighted_logistic_path": ResampledPath("resampled_weighted_logistic_path"),
+    "resampled_gradient": ResampledGradient(), "resampled_gram": ResampledGram(),
 }
 # cs16: two cells only, to bound the time - the weighted squared loss with penalty factors, and the logistic loss
 CS16_CELLS = {"weighted_factors": Path("squared", True, "factors"), "logistic_path": CELLS["logistic_path"]}
@@ -479,7 +602,7 @@ class Attach:
     def __init__(self, kind):
         self.kind = kind
         self.path = {"weights": Path("squared", True), "penalty": Path("squared", False, "bounds"), "groups": FeatureGroups(0.5),
-                     "logistic": Path("logistic")}[kind]
+                     "logistic": Path("logistic"), "resampled": ResampledPath(cp.RESAMPLE_PLAIN)}[kind]
 
     def target32(self, c):
         return c.y32 if self.kind == "logistic" else c.b32           # labels are a squared-loss target as good as any
@@ -507,6 +630,8 @@ class Attach:
         elif self.kind == "groups":
             start, gw, _ = self.path.data(c)
             P.set_feature_groups(np.diff(start), gw, 0.5)
+        elif self.kind == "resampled":
+            pass                                                     # a resampled call binds nothing: the counts travel with the call
         else:
             _lib.check(P.lib.fos_problem_set_loss(P.h, _lib.LOSS_LOGISTIC), "fos_problem_set_loss")
             P.loss = "logistic"
@@ -519,6 +644,8 @@ class Attach:
             P.set_penalty()
         elif self.kind == "groups":
             P.set_feature_groups(None)
+        elif self.kind == "resampled":
+            pass
         else:
             _lib.check(P.lib.fos_problem_set_loss(P.h, _lib.LOSS_SQUARED), "fos_problem_set_loss")
             P.loss = "squared"
@@ -528,11 +655,15 @@ class Attach:
 
 
 @pytest.mark.parametrize("ctx", TWO_SHAPES, indirect=True)
-@pytest.mark.parametrize("kind", ["weights", "penalty", "groups", "logistic"])
+@pytest.mark.parametrize("kind", ["weights", "penalty", "groups", "logistic", "resampled"])
 def test_forms_alternate_on_one_problem(ctx, kind):
     """Plain path (cluster form), feature (two products), plain path; the feature as the first lockstep call of the problem;
     feature, plain, feature; a replan to the two-product layout in the middle.  The cluster form is bit-reproducible
-    (test_fista_path_one_read_cluster_pass) and so is the two-product form: every repeated result is bit for bit the first."""
+    (test_fista_path_one_read_cluster_pass) and so is the two-product form: every repeated result is bit for bit the first.
+    "resampled": the feature is resampled_path on one 0/1 resample under the plain path's own six weights and step - nothing is
+    bound, so only the counts of the call tell the two apart - and every fit of it must differ from the plain path's: a resampled
+    call served by the cluster pass, which ignores the counts, would return the plain path's bits on every handle alike and so
+    pass every "equal to the fresh one" above."""
     _served(ctx)
     a = Attach(kind)
     plain0 = a.plain(ctx, ctx.new(a.build, True))                   # a fresh cluster-planned problem
@@ -569,6 +700,11 @@ def test_forms_alternate_on_one_problem(ctx, kind):
     t = cp.target(ctx.d, "logistic" if kind == "logistic" else "squared")
     a1, a2 = a.plain_alphas(ctx)[0]
     _check_iterates(plain0[0], [(0, orc.fista(ctx.d["A"], t, "elasticnet", a1, a2, max_iter=ITERS, L=ctx.L))], "plain")
+    if kind == "resampled":
+        assert cp.resample_case(ctx.name, cp.RESAMPLE_PLAIN)["alphas"] == a.plain_alphas(ctx)
+        for i, x in enumerate(plain0[0]):
+            assert np.count_nonzero(_np(x)) and not np.array_equal(_np(f1[0][:, 0, i]), _np(x)), ("the resampled fit is the plain path's", i)
+        a.path.check(ctx, f1, columns=[0, 5])
 
 
 class AttachCertificate:
@@ -690,3 +826,39 @@ def test_controlled_lockstep_on_the_cluster_form(ctx):
             assert cd.fp32_proof(more, cp.CONTROL["restart_threshold"], cp.CONTROL["tol_ratio"]), i
             assert (int(s.k), int(s.stopped)) == (more["k"], more["stopped"]) and more["k"] > cp.CONTROL_ITERS, i
             assert _data.rel(_np(st.x_tensor()), more["x"]) < TOL, i
+
+
+@pytest.mark.parametrize("ctx", TWO_SHAPES, indirect=True)
+def test_controlled_resampled_lockstep_on_a_cluster_planned_problem(ctx):
+    """Adaptive restart and the ratio stop per column of a resampled run (two 0/1 resamples under 16 weights: two lockstep groups)
+    on a cluster-planned handle: the (resample, weight) cells the fp64 reference decides fp32-proof stop where it stops and end
+    within 1e-5 of it, the cluster-planned and the two-product problem agree bit for bit, and a plain controlled path (cluster
+    form) before and after is the fresh one."""
+    _served(ctx)
+    fos = ctx.fos
+    C, alphas, kept = cp.resample_control_case(ctx.name)
+    cp.check_resample_control(kept)
+    print(f"controlled resampled {ctx.name}: {len(kept)} of 32 cells, iterations {sorted({r['k'] for r in kept.values()})}")
+
+    def build(c):
+        return c.fos.prepare(c.At, c.b32)
+
+    def run(P):
+        res = fos.resampled_path(P, alphas, C, cp.CONTROL_ITERS, L=ctx.L, **cp.RESAMPLE_CONTROL)
+        return [res.coefs, res.info]
+
+    def plain(P):
+        return fos.fista_path(P, None, alphas, max_iter=cp.CONTROL_ITERS, L=ctx.L, return_info=True, **cp.CONTROL)
+    Pc, Pt = ctx.new(build, True), ctx.new(build, False)
+    plain0 = plain(ctx.new(build, True))
+    before = plain(Pc)                                       # leaves the state machines' device-held momentum behind it
+    rc, rt = run(Pc), run(Pt)
+    assert Pc.plan()["cluster"] == 1 and Pt.plan()["cluster"] == 0
+    assert_same_bits(rc, rt, "the two layouts")
+    coefs = _np(rc[0])
+    for (r, a), ref in sorted(kept.items()):
+        assert rc[1][r][a] == (ref["k"], ref["stopped"]), (r, a, rc[1][r][a], ref["k"], ref["stopped"])
+        assert _data.rel(coefs[:, r, a], ref["x"]) < TOL, (r, a, _data.rel(coefs[:, r, a], ref["x"]))
+    assert_same_bits(before, plain0, "the controlled plain path before")
+    assert_same_bits(plain(Pc), plain0, "the controlled plain path after the resampled run")
+    assert_same_bits(run(Pc), rc, "the resampled run again")

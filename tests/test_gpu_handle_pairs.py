@@ -9,7 +9,7 @@ handle shares its workspace.  Five parts, per storage type (f32, bf16):
    their fp32 passes), and a second fresh handle gives the same bits - the precondition of everything below;
 2. every ordered pair (X, Y), X != Y: configure(X), call(X), move(X, Y), call(Y), move(Y, X), call(X) on one handle; Y's result
    and the second X's are bit for bit those of the fresh handles, and after each move the getters report the configuration just
-   set.  All 1056 pairs at the padded shape; at the two-panel shape the pairs in which X or Y is a CV, objective, working-set,
+   set.  All 1722 pairs at the padded shape; at the two-panel shape the pairs in which X or Y is a CV, objective, working-set,
    certificate or multinomial cell (buffers sized by the panel count);
 3. a replan with the bindings in place: call(X), move(X, Y), replan(), call(Y) gives the fresh bits, replan(interleave=True)
    stays within 1e-5 of the reference where the plan then deals the rows round-robin (at these shapes it does not: the fresh
@@ -18,7 +18,7 @@ handle shares its workspace.  Five parts, per storage type (f32, bf16):
    columns) -> C = 3 (15 columns) -> C = 7 on the multinomial one, the certificate of 16 columns -> 3 -> 16 (the columns >= nv of
    its 4 x 16 answer are 0 each time);
 5. a refused certificate between two calls: for every configuration of the table that fos_duality_gap refuses (bounds, feature
-   groups, bounds under the weighted logistic loss, the three multinomial ones) call(X), fos_duality_gap through the C ABI -
+   groups, bounds under the weighted logistic and under the Huber loss, the three multinomial ones) call(X), fos_duality_gap through the C ABI -
    FOS_ERR_UNSUPPORTED with the guard's text, nothing launched -, call(X): the fresh bits both times, getters and plan unchanged.
 
 The certificate cells (fos_duality_gap on 16, 3, 5, 16, 5, 5 and 16 columns of a seeded block with one zero column, on the
@@ -26,8 +26,8 @@ plain, weighted, logistic, Huber, weighted squared-hinge and positive-factor con
 the fresh handle against tests/_duality.certificate - primal, dual and gap within 1e-5 of the magnitude of their terms, the scale
 to 1e-12, gap == primal - dual, G within the bound of fos_gradient_batch - and against tests/_duality.certified.
 
-No pair comparison has a tolerance and nothing skips.  33 cells (36 with the narrow twins of part 4), 1056 ordered pairs per
-storage type at the padded shape and 900 at the two-panel shape; the 452 tests take 41 to 47 s on the MI355X (the 328 tests of
+No pair comparison has a tolerance and nothing skips.  Before the resampled cells (below): 33 cells (36 with the narrow twins of
+part 4), 1056 ordered pairs per storage type at the padded shape and 900 at the two-panel shape; the 452 tests took 41 to 47 s on the MI355X (the 328 tests of
 25 cells, 600 and 444 pairs before the certificate cells: 32 s in the same session; the slowest test 0.69 s then, and the
 slowest that the certificate cells add, the two-panel pairs of certified_path on bf16, 0.62 s).
 
@@ -61,7 +61,37 @@ tests/test_gpu_cluster_planned.py and tests/test_gpu_duality.py with the certifi
   and the conjugate of the ridge term to the finish, so every certificate is wrong from the first call on a fresh handle (first
   test_cell_on_a_fresh_handle[gap16-padded-f32], against fp64);
 - nparts is not advanced between panels (the second panel's partial sums overwrite the first's): the same 100 tests as under
-  the first edit fail, first test_cell_on_a_fresh_handle[gap16-panels-f32]; one-panel shapes pass."""
+  the first edit fail, first test_cell_on_a_fresh_handle[gap16-panels-f32]; one-panel shapes pass.
+
+The resampled cells (include/fos_resample.h: resampled_path5 with the out-of-bag sums and its 16-column twin, the weighted
+logistic path of 16 columns on 0/1 counts, the Huber path under factors and the lower bound 0, the feature-group path,
+fos_gradient_batch_resampled on the weighted squared-hinge handle, resampled_lipschitz on 18 resamples, the controlled run) and the
+two of include/fos_multinomial_ws.h (certificate and KKT excess of five fits at C = 3, the grouped working-set path at C = 7) go
+through all five parts like the others: 42 cells (46 with the twins of part 4), 1722 ordered pairs per storage type at the padded
+shape and 1416 at the two-panel shape; the 572 tests take 82 to 86 s on the MI355X at 256 CUs with no skip (452 tests in 41 to 47 s
+before these cells; the slowest test, the two-panel pairs of multinomial7_grouped_working_set, 2.2 s).  No defect was found.
+
+Five temporary edits of the resampled host code (values only, every read inside the buffers of the call), each run once against
+this file, tests/test_gpu_cluster_planned.py and tests/test_gpu_resample.py:
+- use_cluster of run_multi_mfma without `&& !counts`: nothing fails here, and nothing can - no shape of this table is planned
+  for the cluster form.  tests/test_gpu_cluster_planned.py fails in 6 tests (listed there);
+- launch_resample_link takes counts without + row0: 118 of the 572 tests fail, all at the two-panel shape - the 16 fresh
+  resampled cells (first test_cell_on_a_fresh_handle[resampled_path5-panels-f32], against fp64: the second panel is 37 rows
+  long and already moves a fit beyond 1e-5), 14 replans, the 84 two-panel pair tests, the resampled width run and the refused
+  certificate on resampled_huber_bounds_path3.  tests/test_gpu_resample.py fails in its 24 two-panel cases;
+- launch_resample_link takes p->row_weight without + row0: 96 fail, all at the two-panel shape - the fresh weighted cells
+  (resampled_logistic_weights_path16, resampled_gradient16, resampled_lipschitz, both storage types), their replans and the 84
+  two-panel pair tests; the unweighted resampled cells pass.  tests/test_gpu_resample.py fails in 10 two-panel cases (the
+  gradient, sums and Gram cases, which hold weighted cells, and the weighted out-of-bag cases);
+- gradient_walk does not advance nparts (every panel's partial sums are copied to the start of ws.grad_part and the fold reads
+  the last panel's count): 96 fail, all at the two-panel shape - the fresh cells with sums (resampled_path5, resampled_path16 and
+  resampled_gradient16: the out-of-bag and in-bag sums against fp64; the iterates and G are right), their replans, the width run and
+  the 84 two-panel pair tests.  tests/test_gpu_resample.py fails in 12 two-panel cases, the four new out-of-bag ones among them;
+- the resampled branch of run_multi_mfma leaves L.row_weight set (the weight enters product 1 and the link: applied twice): 142
+  fail - resampled_logistic_weights_path16 fresh at both shapes against fp64, and through its missing fresh result every pair
+  test; no other weighted resampled cell goes through run_multi_mfma (resampled_gradient16 and resampled_lipschitz are the
+  gradient walk and the Gram operator).  tests/test_gpu_resample.py fails test_path_matches_the_reference on the weighted
+  squared and logistic handles, tests/test_gpu_cluster_planned.py its weighted logistic resampled cell on both shapes."""
 import time
 
 import pytest

@@ -497,6 +497,37 @@ def test_out_of_bag_loss(fos, loss, weighted):
             assert np.all(np.abs(res.oob_loss[r] / res.oob_size[r] - mean_ref.mean(axis=0)) <= tol / size[r])
 
 
+@pytest.mark.parametrize("weighted", [False, True], ids=["plain", "weighted"])
+@pytest.mark.parametrize("cell", [(rsp.SQUARED, "f32"), (rsp.LOGISTIC, "bf16")], ids=lambda c: "-".join(c))
+def test_out_of_bag_loss_at_two_panels(fos, cell, weighted):
+    """resampled_path(..., oob=True) on 70001 rows: the out-of-bag form of the link reads counts, b and the weights of the second
+    panel at + row0, and its partial sums are copied behind the first panel's (ws.grad_part) before the fold."""
+    loss, kind = cell
+    m, n = rsp.SHAPES["panels"]
+    A64, b, c, _, alphas = rsp.recipe(loss, kind, m, n)
+    w = rsp.row_weights(m) if weighted else None
+    Cn, Ls = _path_case(loss, kind, "panels", 2, weighted)
+    P = _handle(fos, loss, kind, A64, b, c, w)
+    first = 256 * P.plan()["cus"]                                          # the rows of the first panel
+    out = Cn == 0
+    live = out if w is None else out & (w > 0)[:, None]
+    assert m > first and live[:first].any(axis=0).all() and live[first:].any(axis=0).all()
+    res = fos.resampled_path(P, list(alphas), Cn, ITERS, L=Ls, oob=True)
+    size = out.sum(axis=0).astype(np.float64) if w is None else (w[:, None] * out).sum(axis=0)
+    assert res.oob_loss.shape == (2, 3) and np.allclose(res.oob_size, size, rtol=1e-12, atol=0) and (size > 0).all()
+    coefs = _np(res.coefs)
+    for r in range(2):
+        X32 = coefs[:, r, :].astype(F32).astype(np.float64)                # the pass over A reads x in fp32
+        assert np.count_nonzero(X32, axis=0).all()
+        Wo = np.repeat((out[:, r] * (1.0 if w is None else w))[:, None], 3, axis=1)
+        ref, tol = rsp.data_term(loss, A64, X32, b, Wo, c), rsp.loss_tolerance(loss, A64, X32, b, Wo, c)
+        second = rsp.data_term(loss, A64[first:], X32, b[first:], Wo[first:], c)
+        print(f"{loss} {kind} weighted={weighted} resample {r}: oob sums err/tol {(np.abs(res.oob_loss[r] - ref) / tol).max():.3f}, "
+              f"the second panel's share / tol {(second / tol).min():.1f}")
+        assert (second > 10.0 * tol).all()                                 # a sum that lost or misplaced the second panel is out of bounds
+        assert np.isfinite(res.oob_loss[r]).all() and (np.abs(res.oob_loss[r] - ref) <= tol).all(), (r, res.oob_loss[r], ref, tol)
+
+
 # ---- 9. handle hygiene ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("loss", (rsp.SQUARED, rsp.HUBER))
 def test_a_handle_that_ran_resampled_serves_the_other_forms_as_a_fresh_one(fos, loss):

@@ -2,7 +2,8 @@
 
 1. every entry point of include/*.h that binds or changes a handle's configuration is a step of some move (or has a stated
    reason not to be one), so that a new setter fails here until it has a cell;
-2. every lockstep entry point is reached by a cell;
+2. every lockstep entry point is reached by a cell, and every `int fos_*(` the headers declare is such an entry point, a binding
+   entry point or excused with a reason (tests/_handle_pairs.NOT_LOCKSTEP): a new header fails here until it has cells;
 3. move is legal for every ordered pair of configurations: replayed against a host model of the refusal rules, which is itself
    pinned to the guards of csrc/fos_plan.hip;
 4. the fp64 references of all cells run at the padded shape and meet their own preconditions: penalties that bite, the branch
@@ -49,6 +50,45 @@ def test_every_lockstep_entry_point_is_reached_by_a_cell():
         with open(path) as fh:
             declared |= set(re.findall(r"\bint\s+(fos_\w+)\s*\(", fh.read()))
     assert reached <= declared, reached - declared
+    # ... and the other way round: what the headers declare is reached by a cell, binds, or is excused with a reason
+    assert declared == hp.declared_entry_points()
+    hp.check_entry_points()
+    for header, names in (("fos_resample.h", ("fos_fista_run_multi_resampled", "fos_gradient_batch_resampled", "fos_gram_apply_resampled")),
+                          ("fos_multinomial_ws.h", ("fos_multinomial_gradient_batch", "fos_multinomial_kkt_scan", "fos_multinomial_duality_gap"))):
+        with open(os.path.join(hp.INCLUDE, header)) as fh:
+            assert set(re.findall(r"\bint\s+(fos_\w+)\s*\(", fh.read())) == set(names) <= reached, header
+
+
+def test_an_entry_point_without_a_cell_fails_the_closed_check(tmp_path):
+    """Each of the six entry points of fos_resample.h and fos_multinomial_ws.h fails check_entry_points once no cell reaches it,
+    and so does a copy of the headers that declares an entry point which is neither reached nor excused; a declaration that binds
+    (fos_*_bind, fos_problem_set_*) is left to test_every_binding_entry_point_is_a_step_of_a_move."""
+    import copy
+    import os
+    import shutil
+    new = ("fos_fista_run_multi_resampled", "fos_gradient_batch_resampled", "fos_gram_apply_resampled",
+           "fos_multinomial_gradient_batch", "fos_multinomial_kkt_scan", "fos_multinomial_duality_gap")
+    for entry in new:
+        cells = {name: copy.copy(c) for name, c in hp.CELLS.items()}
+        for c in cells.values():
+            c.reaches = tuple(e for e in c.reaches if e != entry)
+        with pytest.raises(AssertionError):
+            hp.check_entry_points(cells=cells)
+    fake = tmp_path / "include"
+    shutil.copytree(hp.INCLUDE, fake)
+    hp.check_entry_points(include=str(fake))                      # the copy as it is passes
+    with open(fake / "fos_next.h", "w") as fh:
+        fh.write('#include "fos.h"\nint fos_fista_run_multi_next(fos_fista* const* fs, int nv, int iters);\n')
+    with pytest.raises(AssertionError, match="fos_fista_run_multi_next"):
+        hp.check_entry_points(include=str(fake))
+    os.remove(fake / "fos_next.h")
+    with open(fake / "fos_resample.h") as fh:                       # a declaration that goes: the table names an entry point no header has
+        text = fh.read()
+    assert text.count("int fos_gram_apply_resampled(") == 1
+    with open(fake / "fos_resample.h", "w") as fh:
+        fh.write(text.replace("int fos_gram_apply_resampled(", "int fos_gram_apply_resampled_v2("))
+    with pytest.raises(AssertionError):
+        hp.check_entry_points(include=str(fake))
 
 
 def test_the_host_model_is_the_guards_of_the_source():
@@ -104,13 +144,15 @@ def test_every_move_is_legal_and_minimal():
 
 
 def test_the_table_has_the_cells_and_the_pairs():
-    assert len(hp.CELLS) == 33 and len(hp.PAIRS) == 33 * 32
+    assert len(hp.CELLS) == 42 and len(hp.PAIRS) == 42 * 41 and len(hp.ALL_CELLS) == 46
     sized = [n for n, c in hp.CELLS.items() if c.sized_by_panels]
-    assert len(hp.PANEL_PAIRS) == len(hp.PAIRS) - (33 - len(sized)) * (32 - len(sized))
+    assert len(hp.PANEL_PAIRS) == len(hp.PAIRS) - (42 - len(sized)) * (41 - len(sized))
     for name in ("cv", "groups_cv", "logistic_objective5", "huber_objective16", "multinomial3_path5", "multinomial7_grouped_path2",
                  "working_set", "kkt_excess", "gap16", "gap3", "weights_gap5", "logistic_gap16", "huber_gap5", "hinge_weights_gap5",
-                 "positive_factors_gap16", "certified_path"):
+                 "positive_factors_gap16", "certified_path",
+                 "resampled_path5", "resampled_gradient16", "multinomial3_gap5", "multinomial7_grouped_working_set"):
         assert name in sized
+    assert len(sized) == 24 and len(hp.PANEL_PAIRS) == 42 * 41 - 18 * 17
     for wide, narrow in hp.WIDTHS.values():
         a, b = hp.ALL_CELLS[wide], hp.ALL_CELLS[narrow]
         assert a.count * (a.cfg.classes or 1) != b.count * (b.cfg.classes or 1) and a.cfg._replace(classes=0) == b.cfg._replace(classes=0)
@@ -132,6 +174,12 @@ def test_the_reference_meets_its_preconditions(cell, kind):
         ctl, weights = c.chosen(d)
         print(f"controlled {kind}: {ctl}, {len(weights)} weights, iterations {ref['info'][:, 0].tolist()}")
         assert 5 <= len(weights) <= 16
+    if isinstance(c, hp.ResampledControlled):
+        ctl, kept = c.chosen(d)
+        print(f"{cell} {kind}: {ctl}, {len(kept)} of {c.RESAMPLES * c.WEIGHTS} pairs, iterations {ref['info'][:, 0].tolist()}")
+        assert 2 * len(kept) >= c.RESAMPLES * c.WEIGHTS                      # at least half of the cell's pairs remain
+    if isinstance(c, hp.MultinomialWorkingSet):
+        print(f"{cell} {kind}: sizes {ref['sizes'].tolist()}, worst excess {ref['worst']:.4f}, smallest margin {ref['margin']:.2e}")
     if isinstance(c, hp.WorkingSet):
         print(f"{cell} {kind}: sizes {ref['sizes'].tolist()}, worst excess {ref['worst']:.4f}, smallest margin {ref['margin']:.2e}, gap {ref['gap']:.2e}")
 
